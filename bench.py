@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's headline metric on the fused HIP path.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5|film|c2_curric|c2_h256]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5|film|c2_curric|c2_h256] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline alone: set-up, W warm-up steps, K timed steps, the line.  --full adds everything else the
+benchmark measures (the sub-records, `sustained`, `cpu_baseline`; see Headline below).  --dump-outputs DIR writes what the last
+timed step computed (the step's return value and the state it updates) as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
 
 Metric  : directional samples / second (one sample = one (image, direction) pair through encoding -> SIREN ->
           loss -> gradients).
@@ -19,7 +24,8 @@ Workload: --config c2 (default, the configuration BASELINE.json's metric is quot
           --config c5 (BASELINE config 5): fp32 inference at 512x1024 directions, ND = 49, 4 images per step (SO2; the record also
                          carries the SO3 model of SURVEY 8(d) C5 as `so3`).
           --config c2_curric: config 2's step in the reference's REAL schedule (configs/experiment.yaml:29-34, callbacks.py:11-29):
-                         B = 100 at 16x32, 32x64 and 64x128, one record per resolution -- a step there is its dependent launches.
+                         B = 100 at 16x32, 32x64 and 64x128 (the headline: 64x128; --full: one record per resolution) -- a step
+                         there is its dependent launches.
           --config c2_h256: config 2's step at the width the reference's shipped configs use (configs/default.py:13: 5 x 256).
           Synthetic images / random-init weights (seed 42).
 Scaling : weak (per-GPU batch fixed; images and their latent rows sharded round-robin over ranks).
@@ -27,13 +33,13 @@ Launch  : with WORLD_SIZE / RANK in the environment (torchrun) this process is o
           it spawns N rank processes itself -- BEFORE anything touches the GPU -- and returns the worst exit code.
 
 Headline: `value` / `ms_per_step` / `roofline` are ONE measurement -- W warm-up steps, barrier, exactly K timed steps, barrier --
-          taken FIRST, right behind the set-up, identically with and without the sub-records (`--no-also`).  A GPU that has been idle
-          needs ~30 ms of load to reach its sustained clocks, so with a short warm-up that window reads
-          ~4 % below what a training run sees; the same W + K steps measured again behind the sub-records are reported beside it
-          as `sustained` (a side field, never `value`).
-Rank 0 prints ONE JSON line (contract in the task statement) including `roofline` (dominant kernel, timed live with HIP
-events on its own stream) and, at N = 1, `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded
-sample: B = 1 and B = 4 images, 3 warm-up + 10 timed steps each, reference-shaped and factored -- SURVEY.md 8d).
+          taken FIRST, right behind the set-up, identically with and without --full and the sub-records (`--no-also`).  A GPU that
+          has been idle needs ~30 ms of load to reach its sustained clocks, so with a short warm-up that window
+          reads ~4 % below what a training run sees; with --full the same W + K steps measured again behind the sub-records are
+          reported beside it as `sustained` (a side field, never `value`).
+Rank 0 prints ONE JSON line including `roofline` (dominant kernel, timed live with HIP events on its own stream) and, with --full
+at N = 1, `cpu_baseline` (the CPU oracle timed on the host's cores on a bounded sample: B = 1 and B = 4 images, 3 warm-up +
+10 timed steps each, reference-shaped and factored -- SURVEY.md 8d).
 """
 import argparse
 import json
@@ -71,9 +77,15 @@ def parse():
                          "for the counter passes of profiles/tools/gpu_profile_round.sh; c5 then runs in bf16)")
     ap.add_argument("--dense", action="store_true", help="c4: RENI_WEIGHT_SPARSE off (every tile, and the statistics pass)")
     ap.add_argument("--pixels", action="store_true", help="c4: RENI_WEIGHT_COMPACT (pixels with weight packed into each image's first tiles)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the sub-records (`also`), the `sustained` re-run and the CPU "
+                         "baseline; a plain run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32, "
+                         "at most 64 MB in all: a fixed, seeded sample of a larger array)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-steps", type=int, default=10)
-    ap.add_argument("--no-also", action="store_true", help="skip the c4 / c5 / film sub-records of the default (c2) line")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the sub-records of the c2 line")
     ap.add_argument("--no-fused-step", action="store_true",
                     help="the training step as two library calls (fwd+loss+bwd, then Adam) instead of reni_train_step_rows")
     ap.add_argument("--comm", default=None, choices=["torch", "capi"],
@@ -409,9 +421,24 @@ def run_config(cfg, args, rank, world, dev, batch=None, steps=None, warmup=None,
     except Exception as e:  # noqa: BLE001  (diagnostics only)
         paths = {"error": str(e)[:100]}
 
-    def measure():
-        return _measure(shape, args, world, dev, dtype, step, barrier, steps, warmup, eng, paths)
+    final = {}
 
+    def measure():
+        rec, final["last"] = _measure(shape, args, world, dev, dtype, step, barrier, steps, warmup, eng, paths)
+        return rec
+
+    def outputs():
+        """What a caller of the timed path holds after the last measured step: the step's return value and, for the optimising
+        configurations, the state the step updates in place (parameters, latent rows, Adam moments)."""
+        last = final["last"]
+        if eng is None:   # c5: the forward pass's images
+            return {"output": last}
+        out = {"loss_terms": last, "latents": eng.latent.data, "adam_m_latents": eng.m_lat, "adam_v_latents": eng.v_lat}
+        if eng.train_decoder:
+            out.update({"decoder_params": eng.flat, "adam_m_decoder": eng.m_dec, "adam_v_decoder": eng.v_dec})
+        return out
+
+    measure.outputs = outputs
     # defer: the caller decides when the measurement runs (the headline: first; again behind the sub-records as `sustained`)
     return measure if defer else measure()
 
@@ -557,7 +584,7 @@ def _measure(shape, args, world, dev, dtype, step, barrier, steps, warmup, eng, 
                            "avg_us_on_compute_stream": comm_us}
         if _COMM.get("error"):
             rec["exchange"]["comm_fallback"] = _COMM["error"]
-    return rec
+    return rec, last
 
 
 METRIC_FWD = "directional-samples/sec (fwd), 512x1024 equirect, ND=49 latent"
@@ -666,6 +693,27 @@ def contract_line(metric, rec, world, also, sustained, cpu):
     return _r(line)
 
 
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: at most this many bytes of arrays in all
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: every array as DIR/<name>.npy in float32.  The smaller arrays go whole; one that does not fit its share of
+    DUMP_BYTES is replaced by a fixed, seeded sample of its flattened elements (the same positions in every run at the same arguments),
+    so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    left = DUMP_BYTES
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i) - 256   # (room for the .npy header)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes + 256
+
+
 _OUT = None   # the process's REAL stdout once main() has parked fd 1 on stderr (see own_stdout)
 
 
@@ -723,8 +771,9 @@ def main():
 
     cfg = args.config
     also, sustained = None, None
-    if cfg == "c2_curric":   # the line's headline = the curriculum's final resolution; all three in `also`
-        also = {f"c2_curric_{h}x{w}": sub_record(f"c2_curric_{h}x{w}", args, rank, world, dev) for h, w in CURRIC}
+    if cfg == "c2_curric":   # the line's headline = the curriculum's final resolution; --full: all three in `also`
+        if args.full:
+            also = {f"c2_curric_{h}x{w}": sub_record(f"c2_curric_{h}x{w}", args, rank, world, dev) for h, w in CURRIC}
         head = run_config("c2", args, rank, world, dev, batch=args.batch or 100, res=CURRIC[-1], defer=True)
     elif cfg == "c2_h256":
         head = run_config("c2", args, rank, world, dev, batch=args.batch, hidden=256, defer=True)
@@ -735,7 +784,9 @@ def main():
                           hidden=256 if wide else 128, force_dtype="bf16" if (wide and cfg == "c5") else None)  # set-up only
     # THE headline: W warm-up + K timed steps, first, identically with and without the sub-records
     rec = head()
-    if cfg == "c2" and not args.no_also:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head.outputs())
+    if args.full and cfg == "c2" and not args.no_also:
         # The other BASELINE configurations, the reference's default conditioning, its shipped batch / schedule / width, measured in the
         # same process behind the headline: sub-records, each with its own ms_per_step / launches / roofline.  N > 1: only the two
         # configurations whose ranks are independent (c4, c5: rank 0's own replica).
@@ -759,7 +810,7 @@ def main():
     metric = METRIC_FWD if cfg == "c5" else METRIC_TRAIN.replace("128x256", "64x128") if cfg == "c2_curric" else METRIC_TRAIN
     if rank == 0:
         emit(contract_line(metric, rec, world, also, sustained,
-                           cpu_baseline(args.cpu_steps) if (world == 1 and not args.no_cpu_baseline) else None), also)
+                           cpu_baseline(args.cpu_steps) if (args.full and world == 1 and not args.no_cpu_baseline) else None), also)
     if _COMM.get("comm") is not None:
         _COMM["comm"].close()
     if world > 1:

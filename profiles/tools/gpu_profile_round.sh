@@ -32,7 +32,7 @@ cp $O/pmc_traffic.json profiles/pmc_traffic.json   # (so that the bench lines be
 # (round 6: bench.py prints `also <name> {json}` lines and then ONE contract line: the whole stdout is kept as .txt, the line as .json)
 run_bench() { out=$1; shift; python bench.py "$@" > $O/$out.txt 2>> $O/bench.err; tail -n 1 $O/$out.txt > $O/$out.json; cut -c1-200 $O/$out.json; }
 for c in c2 c4 c5 film c2_curric c2_h256; do
-  X="--config $c --no-cpu-baseline"; [ $c = c2 ] && X="--steps 20 --warmup 5"   # (c2: exactly the driver's command)
+  X="--full --config $c --no-cpu-baseline"; [ $c = c2 ] && X="--full --steps 20 --warmup 5"   # (c2: the benchmark command with all --full adds)
   run_bench bench_$c $X
 done
 run_bench bench_c4_dense --config c4 --dense --no-cpu-baseline        # RENI_WEIGHT_SPARSE off
@@ -41,9 +41,9 @@ run_bench bench_c4_h256 --config c4 --hidden 256 --no-cpu-baseline
 run_bench bench_c4_h256_dense --config c4 --hidden 256 --dense --no-cpu-baseline
 run_bench bench_fwd_h256 --config c5 --hidden 256 --no-cpu-baseline
 for c in c2 c4 c5 film c2_h256; do
-  # c2: the DEFAULT command as the driver runs it (the headline's 5 + 20 steps first, the sub-records, the same steps again): the
+  # c2: the benchmark command with --full (the headline's 5 + 20 steps first, the sub-records, the same steps again): the
   # summary's last two lines are the averages of the headline's and of the sustained window's 20 timed launches
-  X="--config $c --steps 10 --warmup 2 --no-also"; K=""; [ $c = c2 ] && { X="--steps 20 --warmup 5"; K="20 5"; }
+  X="--config $c --steps 10 --warmup 2 --no-also"; K=""; [ $c = c2 ] && { X="--full --steps 20 --warmup 5"; K="20 5"; }
   rocprofv3 --kernel-trace --stats -d $O/kt_$c -o k -- python3 bench.py $X --no-cpu-baseline > $O/kt_$c.txt 2> $O/kt_$c.log
   [ $c = c2 ] && tail -n 1 $O/kt_$c.txt > $O/bench_c2_profiled.json   # (the line of the PROFILED process: its kernel_avg_ms is what the summary's headline window must agree with)
   python3 profiles/summarize_rocpd.py $O/kt_$c/k_results.db $O/kernel_stats_$c.md $K > /dev/null 2>&1 || ls -R $O/kt_$c | head

@@ -7,4 +7,4 @@ timeout 900 python profiles/tools/gpu_soak.py 2>&1 | grep -v amdgpu.ids | tee $O
 python profiles/tools/gpu_film_train_h256.py 2>&1 | grep "FiLM" | tee $O/film_train.txt
 RENI_NO_PERSIST=1 python profiles/tools/gpu_film_train_h256.py 2>&1 | grep "FiLM" | tee -a $O/film_train.txt
 python profiles/tools/gpu_film_fwd_h256.py 2>&1 | grep "samples/s" | tee $O/film_fwd.txt
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.out 2> $O/bench.err; echo "bench rc=$? lines=$(wc -l < $O/bench.out) last_line_bytes=$(tail -n 1 $O/bench.out | wc -c)" | tee $O/bench_rc.txt
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.out 2> $O/bench.err; echo "bench rc=$? lines=$(wc -l < $O/bench.out) last_line_bytes=$(tail -n 1 $O/bench.out | wc -c)" | tee $O/bench_rc.txt

@@ -3,7 +3,7 @@
 # -> gpurun_out/r06_u/{kernel_stats_c2.md, bench_c2_profiled.json, step_timeline_c2.txt}
 cd /tmp; export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06_u; mkdir -p $O
-rocprofv3 --kernel-trace --stats -d $O/kt -o k -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2_profiled.txt 2> $O/kt.log
+rocprofv3 --kernel-trace --stats -d $O/kt -o k -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_c2_profiled.txt 2> $O/kt.log
 tail -n 1 $O/bench_c2_profiled.txt > $O/bench_c2_profiled.json
 python3 profiles/summarize_rocpd.py $O/kt/k_results.db $O/kernel_stats_c2.md 20 5 | tail -8
 python3 profiles/timeline_rocpd.py $O/kt/k_results.db > $O/step_timeline_c2.txt 2>/dev/null

@@ -592,8 +592,16 @@ def g15():
          W=np.int64(W), B=np.int64(B), steps=np.int64(steps), lr=np.float64(1e-3), **arrs)
 
 
+# ---------------------------------------------------------------- the reference's inpainting masks
+def masks():
+    """data/Masks/*.png as the pixel arrays PIL reads from them (uint8, H x W x 3), keyed by file name: what
+    tests/test_api_cpu.py resizes through utils.get_mask."""
+    mdir = os.path.join(REF, "data", "Masks")
+    save("masks.npz", **{f: np.asarray(Image.open(os.path.join(mdir, f))) for f in sorted(os.listdir(mdir))})
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15", "masks"]
     for w in which:
         globals()[w]()

@@ -231,17 +231,14 @@ def test_get_mask(tmp_path, golden):
 def test_get_mask_is_the_tensor_nearest_resize(tmp_path, golden, W):
     """utils.get_mask against what torchvision 0.11's tensor path of Resize(NEAREST) calls -- torch.nn.functional.interpolate(
     mode="nearest") on the ToTensor-equivalent CHW tensor (utils.py:81-91; the G7 golden's mask is generated the same way since
-    round 3): the fixture's Mask-3, random binary 512 x 256 masks (the index rule at a non-integer ratio too), and, where the
-    reference checkout is present, its five mask files."""
-    import os
+    round 3): the fixture's Mask-3, random binary 512 x 256 masks (the index rule at a non-integer ratio too), and the reference's
+    five mask files (their pixels travel in tests/golden/masks.npz)."""
     from PIL import Image
     srcs = {"mask3": golden("g7_latent_opt.npz")["mask_src"]}
     rng = np.random.default_rng(W)
     srcs["rand"] = (rng.random((256, 512)) > 0.5).astype(np.uint8) * 255
-    mdir = "/root/reference/data/Masks"
-    if os.path.isdir(mdir):
-        for f in sorted(os.listdir(mdir)):
-            srcs[f] = np.asarray(Image.open(os.path.join(mdir, f)))
+    srcs.update(golden("masks.npz"))
+    assert len(srcs) == 7
     for name, src in srcs.items():
         arr = src if src.ndim == 3 else np.stack([src] * 3, -1)
         path = tmp_path / f"{name}.png"
@@ -383,6 +380,24 @@ def test_bench_contract_line_stays_short_and_last(capsys):
     assert got["step_call"].startswith("reni_train_step_rows_dp") and set(got["cpu_baseline"]) >= {"value", "unit", "cores", "kind", "sample"}
     sub = json.loads(out[0].split(" ", 2)[2])
     assert out[0].split(" ", 2)[1] == "c4" and sub["roofline"]["kernel"] == roof["kernel"]
+
+
+def test_bench_dump_outputs_stays_within_its_budget(tmp_path):
+    """bench.py --dump-outputs: every array as float32 .npy; small ones whole, one larger than its share of 64 MB replaced by a seeded
+    sample of its elements -- the same positions in every run, so two builds' dumps compare element for element."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    big = torch.arange(16 * 524288 * 3, dtype=torch.float32).view(16, 524288, 3)   # 100 MB: config 5's output at 16 images
+    terms = torch.tensor([0.5, 0.25, 0.125, 0.0625], dtype=torch.float64)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"output": big, "loss_terms": terms})
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert [p.name for p in files] == ["loss_terms.npy", "output.npy"] and sum(p.stat().st_size for p in files) <= 64e6
+    t, o = np.load(tmp_path / "a" / "loss_terms.npy"), np.load(tmp_path / "a" / "output.npy")
+    assert t.dtype == np.float32 and np.array_equal(t, terms.numpy().astype(np.float32))
+    assert o.dtype == np.float32 and 15e6 < o.size < big.numel() and np.all(np.diff(o) >= 0)   # positions in order
+    assert np.array_equal(o, np.load(tmp_path / "b" / "output.npy"))
 
 
 def test_rocpd_summary_finds_the_training_instance_by_prefix(tmp_path):

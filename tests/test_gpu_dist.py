@@ -4,6 +4,7 @@ process gets from the union batch with every gradient scaled 1/W (the reference'
 import os
 import socket
 
+import numpy as np
 import pytest
 import torch
 import torch.multiprocessing as mp
@@ -222,11 +223,11 @@ def test_bench_spawns_its_own_ranks():
 
 
 def test_bench_default_line_carries_every_baseline_config_and_the_capi_exchange():
-    """bench.py's default output: the config-2 headline on ONE short contract line (last), and in front of it one `also` line per
+    """bench.py --full: the config-2 headline on ONE short contract line (last), and in front of it one `also` line per
     sub-record -- config 4, config 5, the FiLM step, the shipped batch / schedule / width -- measured in the same process, each with its
     own roofline; the contract line keeps [value, ms_per_step, frac_step] of each.  `--comm capi` at N = 1 runs the fused data-parallel
     step on a one-rank communicator (the same call path as N > 1)."""
-    line, also = _run_bench({}, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", with_also=True)
+    line, also = _run_bench({}, "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", with_also=True)
     curric = {"c2_curric_16x32", "c2_curric_32x64", "c2_curric_64x128"}   # configs/experiment.yaml:29-34, B = 100
     assert set(also) == {"c4", "c4_dense", "c4_pixels", "c4_f32", "c5", "film", "c2_b100", "c2_h256", "c4_h256", "c4_h256_dense", "fwd_h256", "film_h256"} | curric, {k: v.get("error") for k, v in also.items()}
     assert all("error" not in v for v in also.values()), {k: v.get("error") for k, v in also.items()}
@@ -282,6 +283,26 @@ def test_bench_default_line_carries_every_baseline_config_and_the_capi_exchange(
     assert "also" not in capi and capi["step_call"].startswith("reni_train_step_rows_dp") and capi["value"] > 0
     ex = capi["exchange"]   # (the library's own event pair around its all-reduce, not the bracket of the whole call)
     assert ex["kind"].startswith("inside reni_train_step_rows_dp") and 0 < ex["avg_us_on_compute_stream"] < 0.5e3 * capi["ms_per_step"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) measures the headline alone: exactly K timed steps, no sub-records, no `sustained`, no CPU baseline.
+    --dump-outputs writes what the last timed step computed -- its loss terms and the state it updated -- in float32, and the seeded
+    inputs make a second run with the same arguments compute the same arrays (to the rounding of the gradient reductions)."""
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        line, also = _run_bench({}, "--steps", "3", "--warmup", "1", "--dump-outputs", str(d), with_also=True)
+        assert also == {} and not {"also", "sustained", "cpu_baseline"} & set(line), sorted(line)
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["roofline"]["kernel_launches"] == 3
+        arrs = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(arrs) == {"loss_terms", "latents", "adam_m_latents", "adam_v_latents", "decoder_params", "adam_m_decoder", "adam_v_decoder"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 64e6
+        assert arrs["latents"].shape == (615, 36, 3) and arrs["loss_terms"].shape == (4,) and abs(arrs["loss_terms"][0] - line["config"]["result_check"]) <= 1e-5 * abs(line["config"]["result_check"])
+        runs.append(arrs)
+    for name, a in runs[0].items():
+        np.testing.assert_allclose(runs[1][name], a, rtol=1e-3, atol=1e-6, err_msg=name)
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="RCCL needs one GPU per rank")

@@ -375,6 +375,31 @@ int reni_envmap_shade_backward(int64_t B, int64_t NP, int64_t J, const float* no
                                const float* dcolors, float shininess, float kd, float ks, float* dlight_colors, void* ws,
                                size_t ws_bytes, void* stream);
 
+/* ---- mesh pipeline in front of the shader: vertex normals, camera, rasteriser, interpolation (FIT_INVERSE task) -----
+ * Replaces what build_renderer (src/utils/pytorch3d_envmap_shader.py:177-217) takes from pytorch3d after load_obj, for one
+ * mesh and one face per pixel: Meshes.verts_normals_packed, FoVPerspectiveCameras (fov 60, znear 1, zfar 100, aspect 1),
+ * MeshRasterizer(blur_radius = 0, faces_per_pixel = 1, perspective_correct = False, no culling) and the shader's two
+ * interpolate_face_attributes calls (:68-73).  fp32, deterministic (no float atomics: two calls give identical bits).
+ *   verts        : [V][3] world positions; faces: [F][3] int64 vertex indices (a face with an index outside [0, V) is skipped)
+ * reni_mesh_vertex_normals: normals[v] = s / max(|s|, 1e-6), s = sum of cross(v1 - v0, v2 - v0) over the faces of v, summed
+ *   in ascending face order.  vf_offsets [V+1] / vf_corners: the faces of vertex v as corner indices 3 f + k with
+ *   faces[f][k] == v, ascending, at vf_corners[vf_offsets[v] .. vf_offsets[v+1]) (entries that do not fit are ignored).
+ * reni_rasterize_mesh: R [9] row-major and T [3] (host memory) give p_view = p_world R + T (row vectors, look_at_view_transform's
+ *   convention); NDC x, y = view x, y / (view z * tan_half_fov), depth = view z, no clipping.  H == W = S; pixel (row, col) sits at
+ *   NDC (-1 + (2 (S-1-col) + 1) / S, -1 + (2 (S-1-row) + 1) / S).  Per pixel p = row * S + col, nearest covering face (exact depth
+ *   tie: the lower face index):
+ *     pix_to_face [S*S] int64 (-1 background), zbuf [S*S], bary [S*S][3] (NDC, not perspective-corrected), dists [S*S] (minus the
+ *     squared NDC distance to the face's edges), pixel_normals / pixel_positions [S*S][3] = the winner's barycentric interpolation
+ *     of vert_normals / verts (not normalised).  Background: -1 in pix_to_face, zbuf, bary and dists, 0 in the two G-buffers.
+ *   ws: reni_raster_workspace_bytes(V, F, H, W) bytes, 256-byte aligned (the per-face records). */
+size_t reni_raster_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W);
+int reni_mesh_vertex_normals(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int64_t* vf_offsets,
+                             const int64_t* vf_corners, float* normals, void* stream);
+int reni_rasterize_mesh(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* vert_normals,
+                        const float* R, const float* T, float tan_half_fov, int64_t H, int64_t W, int64_t* pix_to_face,
+                        float* zbuf, float* bary, float* dists, float* pixel_normals, float* pixel_positions, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* ---- HDR image epilogue / prologue ------------------------------------------------
  * reni_unnormalise_srgb replaces, on the device and in one call, the reference's viewing chain
  *   UnMinMaxNormlise(minmax)   src/utils/custom_transforms.py:14-21   y = exp(0.5 (x + 1)(m1 - m0) + m0)

@@ -7,7 +7,8 @@ pytorch_lightning is not installed here; when it is importable ``RENI`` derives 
 ``pl.LightningModule`` and can be handed to a ``pl.Trainer``; otherwise it derives from a small
 duck-typed base and ``reni_amd.trainer.fit`` drives it.  The FIT_INVERSE task shades through
 ``reni_amd.envmap_shader`` (HIP); the rasteriser that produces its G-buffer is pytorch3d's and outside this
-build, so the renderer is handed in with ``set_renderer`` (a stored G-buffer, or a pytorch3d MeshRenderer).
+build: ``on_fit_start`` builds the renderer from the config (``reni_amd.mesh``: OBJ loading and the HIP rasteriser, or
+pytorch3d when it is importable) unless one was handed in with ``set_renderer`` (a stored G-buffer, a pytorch3d MeshRenderer).
 """
 from __future__ import annotations
 
@@ -89,10 +90,26 @@ class RENI(_Base):
         self.model.load_state_dict(state_dict)
 
     def on_fit_start(self):
-        if self.task == "FIT_INVERSE" and self.renderer is None:
-            raise NotImplementedError("FIT_INVERSE renders through an environment-map shader: call set_renderer() with "
-                                      "reni_amd.envmap_shader.GBufferRenderer (stored G-buffer) or build_renderer's "
-                                      "pytorch3d MeshRenderer first")
+        """FIT_INVERSE: the renderer handed to set_renderer() (it survives the fit loop's setup()), else one built from the
+        config as the reference's on_fit_start does (RENI_module.py:56-73): pytorch3d's build_renderer when pytorch3d is
+        importable, reni_amd.mesh.build_hip_renderer otherwise; then the ground-truth renders."""
+        if self.task != "FIT_INVERSE" or self.renderer is not None:
+            return
+        if getattr(self, "_renderer_set", None) is not None:
+            self.set_renderer(*self._renderer_set)
+            return
+        t = self.config.RENI.FIT_INVERSE
+        obj_path = t.OBJECT_PATH
+        if not os.path.isfile(obj_path):
+            raise FileNotFoundError(f"RENI.FIT_INVERSE.OBJECT_PATH: OBJ file not found: {obj_path!r}")
+        device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        try:
+            import pytorch3d  # noqa: F401
+            from .envmap_shader import build_renderer
+        except ImportError:
+            from .mesh import build_hip_renderer as build_renderer
+        renderer, R, T, mesh = build_renderer(obj_path, 0, t.RENDER_RESOLUTION, t.KD_VALUE, device)
+        self.set_renderer(renderer, dict(meshes_world=mesh, R=R, T=T))
 
     # ------------------------------------------------------------------ FIT_INVERSE (RENI_module.py:65-73, 363-396)
     def set_renderer(self, renderer, render_kwargs=None):
@@ -100,6 +117,7 @@ class RENI(_Base):
         makes on its pytorch3d MeshRenderer (RENI_module.py:393-395).  Generates the ground-truth renders."""
         self.renderer = renderer
         self.render_kwargs = dict(render_kwargs or {})
+        self._renderer_set = (renderer, self.render_kwargs)  # setup() clears self.renderer; on_fit_start() reinstalls this
         self.generate_gt_renders()
 
     def get_render(self, model_output, directions, sineweight):

@@ -1,0 +1,232 @@
+"""The mesh pipeline of the FIT_INVERSE task without pytorch3d: OBJ loading, camera, rasteriser, G-buffer.
+
+Everything ``build_renderer`` (src/utils/pytorch3d_envmap_shader.py:177-217) takes from pytorch3d, restated from pytorch3d's
+documented behaviour for the one way the reference uses it -- one mesh, ``FoVPerspectiveCameras()`` with its defaults,
+``RasterizationSettings(image_size=S, blur_radius=0.0, faces_per_pixel=1, perspective_correct=False)`` -- with the
+per-vertex normals and the rasteriser + interpolation on the device (``reni_mesh_vertex_normals`` /
+``reni_rasterize_mesh``, include/reni_hip.h).  The shading is the existing HIP shader (``envmap_shader``), unchanged.
+
+Conventions (pytorch3d's): world -> view is ``p @ R + T`` with row vectors; NDC +X points left and +Y up, so image row 0
+is the top and column 0 the left edge at +x; the depth kept in ``zbuf`` is view-space z; barycentrics are NDC-space.
+Only the environment map carries a gradient (as in the reference): the mesh and the camera are constants.
+"""
+from __future__ import annotations
+
+import math
+import os
+from collections import namedtuple
+
+import torch
+import torch.nn as nn
+
+from . import _lib, ops
+from .envmap_shader import EnvironmentMap, _Materials, blinn_phong_shading_gbuffer
+
+Fragments = namedtuple("Fragments", ["pix_to_face", "zbuf", "bary_coords", "dists"])
+
+
+def load_obj(path, device="cpu"):
+    """``v`` and ``f`` lines of a Wavefront OBJ file -> (verts float32 [V,3], faces int64 [F,3]).
+
+    Face entries may be ``a``, ``a/b``, ``a//c`` or ``a/b/c``; indices are 1-based, a negative index counts back from the
+    last vertex read so far; a polygon is triangulated as the fan (0, i, i+1) (pytorch3d.io.load_obj).  ``vn`` / ``vt``
+    lines, groups and materials are ignored: the normals are recomputed from the faces, as ``Meshes`` does."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"OBJ file not found: {path}")
+    verts, faces = [], []
+    with open(path, "r") as fh:
+        for ln, line in enumerate(fh, 1):
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{ln}: a vertex needs three coordinates")
+                verts.append([float(t) for t in tok[1:4]])
+            elif tok[0] == "f":
+                idx = []
+                for t in tok[1:]:
+                    i = int(t.split("/", 1)[0])
+                    if i == 0:
+                        raise ValueError(f"{path}:{ln}: OBJ indices start at 1")
+                    idx.append(i - 1 if i > 0 else len(verts) + i)
+                if len(idx) < 3:
+                    raise ValueError(f"{path}:{ln}: a face needs at least three vertices")
+                faces.extend([idx[0], idx[i], idx[i + 1]] for i in range(1, len(idx) - 1))
+    v = torch.tensor(verts, dtype=torch.float32).reshape(-1, 3)
+    f = torch.tensor(faces, dtype=torch.int64).reshape(-1, 3)
+    return v.to(device), f.to(device)
+
+
+def rotate_axis_angle_y(verts: torch.Tensor, degrees: float) -> torch.Tensor:
+    """``RotateAxisAngle(degrees, "Y").transform_points(verts)``: a right-handed rotation about +Y (90 deg takes +X to -Z)."""
+    a = torch.tensor(float(degrees), dtype=torch.float32) / 180.0 * math.pi
+    c, s = torch.cos(a), torch.sin(a)
+    one, zero = torch.ones(()), torch.zeros(())
+    R = torch.stack([torch.stack([c, zero, s]), torch.stack([zero, one, zero]), torch.stack([-s, zero, c])])
+    return verts @ R.t().to(verts.device, verts.dtype)  # row vectors: p @ R^T = (R p^T)^T
+
+
+def look_at_view_transform(dist=1.0, elev=0.0, azim=0.0, degrees: bool = True, device="cpu"):
+    """Camera on a sphere round the origin looking at it with +Y up -> (R [1,3,3], T [1,3]); (2, 0, 0) gives
+    R = diag(-1, 1, -1), T = (0, 0, 2)."""
+    d = torch.tensor([float(dist)], dtype=torch.float32)
+    e = torch.tensor([float(elev)], dtype=torch.float32)
+    a = torch.tensor([float(azim)], dtype=torch.float32)
+    if degrees:
+        e, a = e * (math.pi / 180.0), a * (math.pi / 180.0)
+    C = torch.stack([d * torch.cos(e) * torch.sin(a), d * torch.sin(e), d * torch.cos(e) * torch.cos(a)], dim=1)  # [1,3]
+    up = torch.tensor([[0.0, 1.0, 0.0]])
+    z = torch.nn.functional.normalize(-C, eps=1e-5)  # at (origin) - C
+    x = torch.nn.functional.normalize(torch.cross(up, z, dim=1), eps=1e-5)
+    y = torch.nn.functional.normalize(torch.cross(z, x, dim=1), eps=1e-5)
+    if bool(torch.isclose(x, torch.zeros_like(x), atol=5e-3).all()):  # looking straight up or down
+        x = torch.nn.functional.normalize(torch.cross(y, z, dim=1), eps=1e-5)
+    R = torch.cat([x[:, None], y[:, None], z[:, None]], dim=1).transpose(1, 2)
+    T = -torch.bmm(R.transpose(1, 2), C[:, :, None])[:, :, 0]
+    return R.to(device), T.to(device)
+
+
+class FoVPerspectiveCameras:
+    """pytorch3d's FoVPerspectiveCameras as ``build_renderer`` creates it: fov 60 deg, znear 1, zfar 100, aspect 1, and
+    R = I, T = 0 unless given (R, T passed to a renderer call override them for that call)."""
+
+    def __init__(self, znear=1.0, zfar=100.0, aspect_ratio=1.0, fov=60.0, degrees=True, R=None, T=None, device="cpu"):
+        if float(aspect_ratio) != 1.0:
+            raise ValueError("only aspect_ratio 1 (square images) is supported")
+        self.znear, self.zfar, self.aspect_ratio = float(znear), float(zfar), 1.0
+        self.fov = float(fov) * (math.pi / 180.0 if degrees else 1.0)
+        self.R = torch.eye(3)[None] if R is None else torch.as_tensor(R, dtype=torch.float32).reshape(1, 3, 3)
+        self.T = torch.zeros(1, 3) if T is None else torch.as_tensor(T, dtype=torch.float32).reshape(1, 3)
+        self.device = device
+        self.R, self.T = self.R.to(device), self.T.to(device)
+
+    def tan_half_fov(self) -> float:
+        return math.tan(self.fov / 2.0)
+
+    def get_camera_center(self, R=None, T=None) -> torch.Tensor:
+        """World position of the camera [1,3]: the C with C @ R + T = 0."""
+        R = self.R if R is None else torch.as_tensor(R).reshape(1, 3, 3)
+        T = self.T if T is None else torch.as_tensor(T).reshape(1, 3)
+        return -torch.bmm(T[:, None, :].float(), R.float().transpose(1, 2))[:, 0, :]
+
+    def to(self, device):
+        self.R, self.T, self.device = self.R.to(device), self.T.to(device), device
+        return self
+
+
+class Meshes:
+    """One triangle mesh in pytorch3d's packed form: ``Meshes(verts=[v], faces=[f])``; the vertex normals come from the
+    HIP kernel (a device tensor is needed for them) and are computed once."""
+
+    def __init__(self, verts, faces):
+        if len(verts) != 1 or len(faces) != 1:
+            raise ValueError("one mesh per Meshes (several meshes per batch are not supported)")
+        self._verts = verts[0].to(torch.float32).contiguous()
+        self._faces = faces[0].to(torch.int64).contiguous()
+        self._normals = None
+
+    def verts_packed(self) -> torch.Tensor:
+        return self._verts
+
+    def faces_packed(self) -> torch.Tensor:
+        return self._faces
+
+    def verts_normals_packed(self) -> torch.Tensor:
+        if self._normals is None:
+            self._normals = ops.vertex_normals(self._verts, self._faces)
+        return self._normals
+
+    @property
+    def device(self):
+        return self._verts.device
+
+
+class RasterizationSettings:
+    """The settings the reference uses; anything else is outside what the HIP rasteriser implements."""
+
+    def __init__(self, image_size=256, blur_radius=0.0, faces_per_pixel=1, perspective_correct=False, cull_backfaces=False):
+        if not isinstance(image_size, int):
+            raise ValueError("image_size must be an int (square images only)")
+        if blur_radius != 0.0 or faces_per_pixel != 1 or perspective_correct or cull_backfaces:
+            raise ValueError("supported: blur_radius 0, faces_per_pixel 1, perspective_correct False, no back-face culling")
+        self.image_size = image_size
+        self.blur_radius, self.faces_per_pixel, self.perspective_correct = 0.0, 1, False
+        self.cull_backfaces = False
+
+
+class MeshRasterizer(nn.Module):
+    """``MeshRasterizer(cameras, raster_settings)(meshes_world, R=, T=) -> Fragments`` on the device.  The G-buffer of the
+    last (mesh, R, T, size) is kept: the reference re-rasterises its constant mesh and camera on every render, here a
+    training step then costs only the shader (same output).  The key is the identity and in-place version of the mesh's
+    tensors and of R, T, so modifying any of them in place re-rasterises."""
+
+    def __init__(self, cameras=None, raster_settings=None):
+        super().__init__()
+        self.cameras = cameras if cameras is not None else FoVPerspectiveCameras()
+        self.raster_settings = raster_settings if raster_settings is not None else RasterizationSettings()
+        self._cache = None
+
+    def gbuffer(self, meshes_world: Meshes, R=None, T=None):
+        """-> (Fragments, pixel_normals [S*S,3], pixel_positions [S*S,3]) (interpolated, not normalised)."""
+        R = self.cameras.R if R is None else torch.as_tensor(R)
+        T = self.cameras.T if T is None else torch.as_tensor(T)
+        S = self.raster_settings.image_size
+        v, f = meshes_world.verts_packed(), meshes_world.faces_packed()
+        key = tuple((id(t), t._version) for t in (v, f, R, T)) + (S, self.cameras.tan_half_fov())
+        if self._cache is not None and self._cache[0] == key:
+            return self._cache[2]
+        p2f, zbuf, bary, dists, nrm, pos = ops.rasterize_mesh(v, f, meshes_world.verts_normals_packed(), R, T, S,
+                                                              self.cameras.tan_half_fov())
+        out = (Fragments(p2f, zbuf, bary, dists), nrm, pos)
+        self._cache = (key, (v, f, R, T), out)  # (the tensors are held so that their ids stay theirs)
+        return out
+
+    def forward(self, meshes_world: Meshes, R=None, T=None, **kwargs) -> Fragments:
+        return self.gbuffer(meshes_world, R, T)[0]
+
+
+class HipMeshRenderer(nn.Module):
+    """``renderer(meshes_world=mesh, R=R, T=T, envmap=...) -> (colors [B,S,S,3], pixel_normals [B,S,S,3])``: the call the
+    reference makes on its pytorch3d MeshRenderer (RENI_module.py:393-396).  The rasteriser's G-buffer goes straight into
+    ``blinn_phong_shading_gbuffer`` (the existing HIP shader and its autograd function).
+
+    Reference quirk kept: the reference's shader asks ``cameras.get_camera_center()`` WITHOUT R and T
+    (pytorch3d_envmap_shader.py:78; MeshRenderer hands R and T to the rasteriser only as keyword arguments), so its
+    specular term uses the centre of the default camera -- the world origin -- not the rendering camera's (0, 0, 2).  The
+    same is done here.  With the default KD_VALUE = 1 (no specular term) it has no effect."""
+
+    def __init__(self, rasterizer: MeshRasterizer, kd: float, ks: float = None, materials=None, shader_cameras=None):
+        super().__init__()
+        self.rasterizer = rasterizer
+        self.kd = float(kd)
+        self.ks = 1.0 - self.kd if ks is None else float(ks)
+        self.materials = materials if materials is not None else _Materials(500.0)
+        shader_cameras = shader_cameras if shader_cameras is not None else rasterizer.cameras
+        # no R, T: the reference's quirk (see above); kept on the host, where the shader entry point reads it
+        self.camera_center = shader_cameras.get_camera_center().detach().reshape(3).cpu()
+
+    def forward(self, meshes_world: Meshes = None, R=None, T=None, envmap: EnvironmentMap = None, **kwargs):
+        _, nrm, pos = self.rasterizer.gbuffer(meshes_world, R, T)
+        S = self.rasterizer.raster_settings.image_size
+        B = envmap.environment_map.shape[0]
+        colors = blinn_phong_shading_gbuffer(nrm, pos, self.camera_center, envmap, self.materials.shininess, self.kd, self.ks)
+        normals = torch.nn.functional.normalize(nrm, p=2, dim=-1, eps=1e-6).reshape(1, S, S, 3).repeat(B, 1, 1, 1)
+        return colors.reshape(B, S, S, 3), normals
+
+
+def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device):
+    """Same arguments and return value as the reference's ``build_renderer`` (:177-217) -- ``(renderer, R, T, mesh)`` with
+    ``renderer(meshes_world=mesh, R=R, T=T, envmap=...)`` -- without pytorch3d: Materials(shininess=500), ks = 1 - kd, the
+    camera at look_at_view_transform(2, 0, 0).  ``device`` must be a GPU device (there is no CPU path)."""
+    verts, faces = load_obj(obj_path)
+    verts = rotate_axis_angle_y(verts, obj_rotation)
+    if torch.device(device).type != "cuda":
+        raise _lib.RENILibraryError(f"build_hip_renderer renders on a GPU device, got {device!r}; there is no CPU path")
+    mesh = Meshes(verts=[verts.to(device)], faces=[faces.to(device)])
+    mesh.verts_normals_packed()
+    cameras = FoVPerspectiveCameras(device=device)
+    raster = MeshRasterizer(cameras=cameras, raster_settings=RasterizationSettings(image_size=int(img_size)))
+    renderer = HipMeshRenderer(raster, kd=kd, materials=_Materials(500.0))
+    R, T = look_at_view_transform(2.0, 0.0, 0.0, degrees=True, device=device)
+    return renderer, R, T, mesh

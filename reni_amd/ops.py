@@ -612,6 +612,85 @@ def envmap_shade_backward(normals, positions, camera_center, light_dirs, dcolors
     return _shade_call(False, normals, positions, camera_center, light_dirs, dcolors, shininess, kd, ks)
 
 
+def _vertex_face_csr(faces: torch.Tensor, V: int):
+    """The faces of every vertex as corner indices 3 f + k, ascending per vertex (a stable sort of the flattened index list on
+    the device), and the [V+1] offsets into that list.  Corners whose index lies outside [0, V) are left out."""
+    flat = faces.reshape(-1)
+    corners = torch.arange(flat.numel(), device=flat.device, dtype=torch.int64)
+    ok = (flat >= 0) & (flat < V)
+    keys, corners = flat[ok], corners[ok]
+    keys, order = torch.sort(keys, stable=True)
+    offsets = torch.searchsorted(keys, torch.arange(V + 1, device=flat.device, dtype=torch.int64))
+    return offsets.contiguous(), corners[order].contiguous()
+
+
+def _mesh_inputs(verts, faces):
+    _require_cuda(verts, faces)
+    verts = verts.to(torch.float32).contiguous()
+    faces = faces.to(torch.int64).contiguous()
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError(f"verts must be [V, 3] with V >= 1, got {tuple(verts.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError(f"faces must be [F, 3] with F >= 1, got {tuple(faces.shape)}")
+    if faces.device != verts.device:
+        raise ValueError("verts and faces must be on the same device")
+    return verts, faces
+
+
+def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """reni_mesh_vertex_normals: Meshes.verts_normals_packed() of one mesh, [V, 3] -- the area-weighted sum of the adjacent
+    faces' cross(v1 - v0, v2 - v0), normalised with max(|n|, 1e-6).  Deterministic (a gather in ascending face order)."""
+    verts, faces = _mesh_inputs(verts, faces)
+    V, F = verts.shape[0], faces.shape[0]
+    offsets, corners = _vertex_face_csr(faces, V)
+    if corners.numel() == 0:
+        corners = torch.zeros(1, dtype=torch.int64, device=verts.device)  # (never read: every vertex's range is empty)
+    out = torch.empty(V, 3, dtype=torch.float32, device=verts.device)
+    with torch.cuda.device(verts.device):
+        _lib.check(_lib.load().reni_mesh_vertex_normals(V, F, verts.data_ptr(), faces.data_ptr(), offsets.data_ptr(),
+                                                        corners.data_ptr(), out.data_ptr(),
+                                                        torch.cuda.current_stream(verts.device).cuda_stream))
+    return out
+
+
+def rasterize_mesh(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch.Tensor, R, T, image_size: int,
+                   tan_half_fov: float = 0.5773502691896258):
+    """reni_rasterize_mesh: one mesh seen by FoVPerspectiveCameras (default tan(fov/2) = tan 30 deg) with world-to-view
+    p R + T, rasterised at image_size^2 with one face per pixel, and the shader's G-buffer.  Returns
+    (pix_to_face [1,S,S,1] int64, zbuf [1,S,S,1], bary [1,S,S,1,3], dists [1,S,S,1], pixel_normals [S*S,3],
+    pixel_positions [S*S,3]) -- the first four are pytorch3d's Fragments, the last two interpolate_face_attributes of the
+    vertex normals / positions (not normalised)."""
+    verts, faces = _mesh_inputs(verts, faces)
+    _require_cuda(vert_normals)
+    vert_normals = vert_normals.to(torch.float32).contiguous()
+    if tuple(vert_normals.shape) != tuple(verts.shape):
+        raise ValueError("vert_normals must be [V, 3] like verts")
+    S = int(image_size)
+    if S < 1:
+        raise ValueError("image_size must be >= 1")
+    Rv = [float(x) for x in torch.as_tensor(R).reshape(-1).tolist()]
+    Tv = [float(x) for x in torch.as_tensor(T).reshape(-1).tolist()]
+    if len(Rv) != 9 or len(Tv) != 3:
+        raise ValueError("R must hold 9 values ([1,3,3] or [3,3]) and T 3 ([1,3] or [3])")
+    Rh, Th = (ctypes.c_float * 9)(*Rv), (ctypes.c_float * 3)(*Tv)
+    lib = _lib.load()
+    V, F = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    p2f = torch.empty(1, S, S, 1, dtype=torch.int64, device=dev)
+    zbuf = torch.empty(1, S, S, 1, dtype=torch.float32, device=dev)
+    bary = torch.empty(1, S, S, 1, 3, dtype=torch.float32, device=dev)
+    dists = torch.empty(1, S, S, 1, dtype=torch.float32, device=dev)
+    nrm = torch.empty(S * S, 3, dtype=torch.float32, device=dev)
+    pos = torch.empty(S * S, 3, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_raster_workspace_bytes(V, F, S, S)), dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.reni_rasterize_mesh(V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th,
+                                           float(tan_half_fov), S, S, p2f.data_ptr(), zbuf.data_ptr(), bary.data_ptr(),
+                                           dists.data_ptr(), nrm.data_ptr(), pos.data_ptr(), wp, wn,
+                                           torch.cuda.current_stream(dev).cuda_stream))
+    return p2f, zbuf, bary, dists, nrm, pos
+
+
 def _ws256(nbytes, device):
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
     p = ws.data_ptr()

@@ -400,6 +400,39 @@ int reni_rasterize_mesh(int64_t V, int64_t F, const float* verts, const int64_t*
                         float* zbuf, float* bary, float* dists, float* pixel_normals, float* pixel_positions, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- environment-map baselines: spherical Gaussians and spherical harmonics ----------------------------------------
+ * What RENI is compared against.  fp32, deterministic (no float atomics; fixed summation order: two calls give identical
+ * bits, and map n's results are the same alone or inside a batch).
+ * Spherical Gaussians, SGEnvOptim (src/models/spherical_gaussians.py).  N >= 1 maps of H x W >= 1 pixels, 1 <= K <= 64 lobes.
+ *   params [N][K][6] raw = (w0, w1, w2, theta~, phi~, lambda~) per lobe k = row * SGCol + col; theta_c / phi_c [K] the lobe centres
+ *   (float32 of the reference's float64 meshgrid, :29-37); theta_range / phi_range the scalars of :38-39.  Lobe: theta = theta_range
+ *   tanh theta~ + theta_c, phi = phi_range tanh phi~ + phi_c, w = exp w~, lambda = exp lambda~, axis a = (sin theta cos phi,
+ *   sin theta sin phi, cos theta).  Pixel p = i W + j looks along l = (sin El cos Az, sin El sin Az, cos El), Az = ((j + 0.5) / W - 0.5)
+ *   2 pi, El = (i + 0.5) / H pi / 2 (a hemisphere, :41-52).
+ * reni_sg_render: rec [N][3][H][W] = sum_k w_kc exp(lambda_k (a_k . l_p - 1))                           (renderSG :109-137)
+ * reni_sg_loss_grad: log_target [N][3][H][W] = log(env + 1); weight s at weight[n sn + c sc + i sh + j sw] (stride 0 broadcasts).
+ *   loss_per_map [N] = mean over (c, p) of s (log(rec + 1) - log_target)^2; loss_total [1] their sum (WeightedMSE,
+ *   loss_functions.py:6-13); dparams [N][K][6] = d loss_total / d params.  ws: reni_sg_workspace_bytes(N, K, H, W) bytes, 256-byte
+ *   aligned (0 bytes -- ws may be NULL -- when H W <= 768). */
+size_t reni_sg_workspace_bytes(int64_t N, int64_t K, int64_t H, int64_t W);
+int reni_sg_render(int64_t N, int64_t K, int64_t H, int64_t W, const float* params, const float* theta_c, const float* phi_c,
+                   float theta_range, float phi_range, float* rec, void* stream);
+int reni_sg_loss_grad(int64_t N, int64_t K, int64_t H, int64_t W, const float* params, const float* theta_c, const float* phi_c,
+                      float theta_range, float phi_range, const float* log_target, const float* weight, int64_t w_stride_n,
+                      int64_t w_stride_c, int64_t w_stride_h, int64_t w_stride_w, float* loss_per_map, float* loss_total,
+                      float* dparams, void* ws, size_t ws_bytes, void* stream);
+/* Spherical harmonics (src/models/spherical_harmonics.py).  Equirectangular [N][H][W][3] maps, W even, H == W / 2, W <= 4096,
+ * 0 <= lmax <= 15, T = (lmax + 1)^2 terms, t = l^2 + l + m.  Y_t(y, x) = row_table[y][t] col_table[x][t]: row_table [H][T] =
+ * K_l|m| P_l|m|(cos(y pi / H)) (times sqrt 2 for m != 0), col_table [W][T] = cos(m x 2 pi / W) (m > 0), 1 (m = 0), sin(|m| x 2 pi / W)
+ * (m < 0) -- the pixel's top-left corner, as getCoefficientsMatrix.  For the projection the caller folds the solid angle of row y,
+ * 2 pi / W (cos(theta - pi / 2H) - cos(theta + pi / 2H)), theta = (1 - (y + 0.5) / H) pi (getSolidAngle), into row_table.
+ * reni_sh_project: coeffs [N][T][3] = sum_(y, x) img[n][y][x][c] row_table[y][t] col_table[x][t]       (getCoefficientsFromImage)
+ * reni_sh_reconstruct: out [N][H][W][3] = sum_t row_table[y][t] col_table[x][t] coeffs[n][t][c]         (shReconstructSignal) */
+int reni_sh_project(int64_t N, int64_t H, int64_t W, int64_t lmax, const float* img, const float* row_table,
+                    const float* col_table, float* coeffs, void* stream);
+int reni_sh_reconstruct(int64_t N, int64_t H, int64_t W, int64_t lmax, const float* coeffs, const float* row_table,
+                        const float* col_table, float* out, void* stream);
+
 /* ---- HDR image epilogue / prologue ------------------------------------------------
  * reni_unnormalise_srgb replaces, on the device and in one call, the reference's viewing chain
  *   UnMinMaxNormlise(minmax)   src/utils/custom_transforms.py:14-21   y = exp(0.5 (x + 1)(m1 - m0) + m0)

@@ -1,0 +1,315 @@
+"""Spherical-Gaussian and spherical-harmonic environment-map baselines on the GPU: what RENI is compared against.
+
+Restates the reference's src/models/spherical_gaussians.py (SGEnvOptim) and the projection / reconstruction part of
+src/models/spherical_harmonics.py with the same call shapes.  The arithmetic runs in libreni_hip.so
+(reni_tu_baselines.hip); torch supplies device memory and, for SGEnvOptim, its own LBFGS.  There is no CPU fallback.
+
+Differences from the reference, all deliberate:
+  - SGEnvOptim.optimize(envmap, sineweight=None) treats sineweight=None as a weight of 1 everywhere (the reference
+    crashes on None).
+  - getCoefficientsFromImage's resizeWidth / filterAmount (cv2 / scipy) raise NotImplementedError, and a map wider than
+    1000 pixels -- which the reference silently resizes to 1000 x 500 -- raises ValueError.
+  - The SH maps are read as float32 on the device; coefficients come back as float64 arrays, as in the reference.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+# ----------------------------------------------------------------------------------------------- spherical Gaussians
+
+
+def sg_lobe_centres(SGRow: int, SGCol: int, device=None):
+    """(theta_c [K], phi_c [K], theta_range, phi_range) as SGEnvOptim builds them (:29-39): lobe k = row * SGCol + col,
+    centres computed in float64 and rounded to float32."""
+    phi = ((np.arange(SGCol) + 0.5) / SGCol - 0.5) * np.pi * 2
+    theta = (np.arange(SGRow) + 0.5) / SGRow * np.pi / 2.0
+    phi, theta = np.meshgrid(phi, theta)
+    tc = torch.from_numpy(theta.reshape(-1).astype(np.float32))
+    pc = torch.from_numpy(phi.reshape(-1).astype(np.float32))
+    if device is not None:
+        tc, pc = tc.to(device), pc.to(device)
+    return tc, pc, (np.pi / 2 / SGRow) * 1.5, (2 * np.pi / SGCol) * 1.5
+
+
+def _raw(params, K=None):
+    N = params.shape[0]
+    K = params.numel() // (6 * N) if K is None else K
+    return params.reshape(N, K, 6)
+
+
+def sg_render(params: torch.Tensor, SGRow: int, SGCol: int, envHeight: int, envWidth: int) -> torch.Tensor:
+    """renderSG of the reparametrised raw parameters: params [N, K * 6] or [N, K, 6] (per lobe w~0..2, theta~, phi~,
+    lambda~) -> rec [N, 3, envHeight, envWidth].  Not differentiable (see sg_loss)."""
+    tc, pc, tr, pr = sg_lobe_centres(SGRow, SGCol, params.device)
+    return ops.sg_render(_raw(params.detach(), SGRow * SGCol), tc, pc, tr, pr, envHeight, envWidth)
+
+
+class _SGLoss(torch.autograd.Function):
+    """WeightedMSE(log(renderSG(params) + 1), log_target, weight) with the fused kernel's gradient."""
+
+    @staticmethod
+    def forward(ctx, params, theta_c, phi_c, theta_range, phi_range, log_target, weight):
+        total, _, grad = ops.sg_loss_grad(_raw(params.detach(), theta_c.numel()), theta_c, phi_c, theta_range, phi_range,
+                                          log_target, weight)
+        ctx.save_for_backward(grad)
+        ctx.shape = params.shape
+        return total
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g).reshape(ctx.shape), None, None, None, None, None, None
+
+
+def sg_loss(params: torch.Tensor, log_target: torch.Tensor, weight, SGRow: int, SGCol: int) -> torch.Tensor:
+    """Scalar loss sum_n mean_(c, p) weight (log(rec + 1) - log_target)^2, differentiable with respect to params
+    ([N, K * 6] or [N, K, 6]).  log_target [N, 3, H, W] = log(env + 1); weight broadcasts to [N, 3, H, W] (None: 1)."""
+    tc, pc, tr, pr = sg_lobe_centres(SGRow, SGCol, params.device)
+    if weight is None:
+        weight = torch.ones(1, 1, 1, 1, device=params.device)
+    return _SGLoss.apply(params, tc, pc, tr, pr, log_target, weight)
+
+
+class SGEnvOptim:
+    """SGEnvOptim (src/models/spherical_gaussians.py) on the fused HIP kernel: fits SGRow x SGCol spherical Gaussians to
+    each of envNum environment maps with torch's LBFGS(lr 0.2, max_iter 100), niter outer steps."""
+
+    def __init__(self, isCuda=True, gpuId=0, niter=10, envNum=19200, envWidth=32, envHeight=16, SGRow=2, SGCol=6, ch=3):
+        if not isCuda:
+            raise _lib.RENILibraryError("SGEnvOptim runs on a GPU device (isCuda=True); there is no CPU fallback")
+        if ch != 3:
+            raise ValueError(f"SGEnvOptim supports ch == 3 only, got {ch}")
+        self.SGNum = int(SGRow * SGCol)
+        if not 1 <= self.SGNum <= 64:
+            raise ValueError(f"SGRow * SGCol must be in [1, 64], got {self.SGNum}")
+        self.envNum, self.niter, self.ch = envNum, niter, ch
+        self.envHeight, self.envWidth = envHeight, envWidth
+        self.SGRow, self.SGCol = SGRow, SGCol
+        self.isCuda, self.gpuId = isCuda, gpuId
+        self.iterCount = 0
+        self.device = torch.device("cuda", gpuId)
+        self.thetaCenter, self.phiCenter, self.thetaRange, self.phiRange = sg_lobe_centres(SGRow, SGCol, self.device)
+        weight = torch.zeros(envNum, self.SGNum, 3)
+        theta = torch.zeros(envNum, self.SGNum, 1)
+        phi = torch.zeros(envNum, self.SGNum, 1)
+        lamb = torch.log(torch.ones(envNum, self.SGNum, 1) * np.pi / SGRow)
+        self.param = torch.cat([weight, theta, phi, lamb], dim=2).view(envNum, self.SGNum * 6).to(self.device)
+        self.param.requires_grad = True
+        self.optEnv = torch.optim.LBFGS([self.param], lr=0.2, max_iter=100)
+        self.loss = None
+
+    def deparameterize(self):
+        """(theta, phi, weight, lamb) [N, K, 1 | 1 | 3 | 1] after the reparametrisation of optimize's closure."""
+        p = self.param.detach().view(self.envNum, self.SGNum, 6)
+        theta = self.thetaRange * torch.tanh(p[:, :, 3:4]) + self.thetaCenter.view(1, -1, 1)
+        phi = self.phiRange * torch.tanh(p[:, :, 4:5]) + self.phiCenter.view(1, -1, 1)
+        return theta, phi, torch.exp(p[:, :, 0:3]), torch.exp(p[:, :, 5:6])
+
+    def renderSG(self):
+        """The current parameters' maps [envNum, 3, envHeight, envWidth]."""
+        return ops.sg_render(self.param.detach().view(self.envNum, self.SGNum, 6), self.thetaCenter, self.phiCenter,
+                             self.thetaRange, self.phiRange, self.envHeight, self.envWidth)
+
+    def optimize(self, envmap, sineweight=None):
+        """-> (thetaBest [N, K, 1], phiBest [N, K, 1], lambBest [N, K, 1], weightBest [N, K, 3], recImageBest [N, 3, H, W]),
+        float32 numpy arrays of the best outer step (all None if the first step's loss is not below 2e20 or is NaN)."""
+        assert (envmap.shape[0] == self.envNum and envmap.shape[1] == self.ch and envmap.shape[2] == self.envHeight
+                and envmap.shape[3] == self.envWidth)
+        env = torch.as_tensor(envmap).to(self.device, torch.float32)
+        log_target = torch.log(env + 1).contiguous()
+        if sineweight is None:
+            weight = torch.ones(1, 1, 1, 1, device=self.device)
+        else:
+            weight = torch.as_tensor(sineweight).to(self.device, torch.float32)
+        minLoss = 2e20
+        recImageBest = thetaBest = phiBest = weightBest = lambBest = None
+        self.loss = None
+        for _ in range(self.niter):
+
+            def closure():
+                loss = _SGLoss.apply(self.param, self.thetaCenter, self.phiCenter, self.thetaRange, self.phiRange,
+                                     log_target, weight)
+                self.loss = loss
+                self.optEnv.zero_grad()
+                loss.backward()
+                self.iterCount += 1
+                return loss
+
+            self.optEnv.step(closure)
+            loss = float(self.loss.item())
+            if loss < minLoss:
+                if torch.isnan(torch.sum(self.param)):
+                    break
+                theta, phi, weight_, lamb = self.deparameterize()
+                recImageBest = self.renderSG().cpu().numpy()
+                thetaBest = theta.cpu().numpy().reshape(self.envNum, self.SGNum, 1)
+                phiBest = phi.cpu().numpy().reshape(self.envNum, self.SGNum, 1)
+                lambBest = lamb.cpu().numpy().reshape(self.envNum, self.SGNum, 1)
+                weightBest = weight_.cpu().numpy().reshape(self.envNum, self.SGNum, 3)
+                minLoss = loss
+            else:
+                break
+        return thetaBest, phiBest, lambBest, weightBest, recImageBest
+
+
+# ----------------------------------------------------------------------------------------------- spherical harmonics
+
+
+def shTerms(lmax):
+    return (lmax + 1) * (lmax + 1)
+
+
+def shIndex(l, m):
+    return l * l + l + m
+
+
+def sh_lmax_from_terms(terms):
+    return int(np.sqrt(terms) - 1)
+
+
+def calc_num_sh_coeffs(order):
+    return sum(2 * i + 1 for i in range(order + 1))
+
+
+def get_sh_order(ndims):
+    order = 0
+    while calc_num_sh_coeffs(order) < ndims:
+        order += 1
+    return order
+
+
+def _legendre(l, m, x):
+    """associated Legendre P_l^m(x) by the reference's recursion (spherical_harmonics.py P, :45-68), float64"""
+    pmm = np.ones_like(x)
+    if m > 0:
+        somx2 = np.sqrt((1.0 - x) * (1.0 + x))
+        fact = 1.0
+        for _ in range(1, m + 1):
+            pmm = pmm * (-fact) * somx2
+            fact += 2.0
+    if l == m:
+        return pmm
+    pmmp1 = x * (2.0 * m + 1.0) * pmm
+    if l == m + 1:
+        return pmmp1
+    pll = np.zeros_like(x)
+    for ll in range(m + 2, l + 1):
+        pll = ((2.0 * ll - 1.0) * x * pmmp1 - (ll + m - 1.0) * pmm) / (ll - m)
+        pmm, pmmp1 = pmmp1, pll
+    return pll
+
+
+def _knorm(l, m):
+    return np.sqrt(((2 * l + 1) * float(math.factorial(l - m))) / (4 * np.pi * float(math.factorial(l + m))))
+
+
+def sh_tables(width: int, lmax: int, solid_angle: bool):
+    """The separable basis of getCoefficientsMatrix(width, lmax) in float64: row [H, T] (K P, sqrt 2 for m != 0; times
+    getSolidAngle of the row when solid_angle) and col [W, T] (cos(m phi), 1, sin(|m| phi)); Y_t(y, x) = row[y, t] col[x, t].
+    Angles of the pixel's top-left corner: theta = y pi / H, phi = x 2 pi / W."""
+    W = int(width)
+    H = W // 2
+    T = shTerms(lmax)
+    theta = np.arange(H) / (float(H) / np.pi)
+    phi = np.arange(W) / (float(W) / (np.pi * 2))
+    ct = np.cos(theta)
+    row = np.zeros((H, T))
+    col = np.zeros((W, T))
+    for l in range(lmax + 1):
+        for m in range(-l, l + 1):
+            t = shIndex(l, m)
+            if m == 0:
+                row[:, t] = _knorm(l, 0) * _legendre(l, 0, ct)
+                col[:, t] = 1.0
+            elif m > 0:
+                row[:, t] = np.sqrt(2.0) * _knorm(l, m) * _legendre(l, m, ct)
+                col[:, t] = np.cos(m * phi)
+            else:
+                row[:, t] = np.sqrt(2.0) * _knorm(l, -m) * _legendre(l, -m, ct)
+                col[:, t] = np.sin(-m * phi)
+    if solid_angle:
+        th = (1.0 - ((np.arange(H) + 0.5) / H)) * np.pi
+        row *= ((np.pi * 2) / W * (np.cos(th - (np.pi / H / 2.0)) - np.cos(th + (np.pi / H / 2.0))))[:, None]
+    return row, col
+
+
+_TABLES = {}
+
+
+def _device_tables(width, lmax, solid_angle, device):
+    key = (int(width), int(lmax), bool(solid_angle), str(device))
+    if key not in _TABLES:
+        row, col = sh_tables(width, lmax, solid_angle)
+        _TABLES[key] = (torch.from_numpy(row.astype(np.float32)).to(device),
+                        torch.from_numpy(col.astype(np.float32)).to(device))
+    return _TABLES[key]
+
+
+def _check_sh(width, lmax):
+    if not 0 <= int(lmax) <= 15:
+        raise ValueError(f"lmax must be in [0, 15], got {lmax}")
+    if int(width) < 2 or int(width) % 2:
+        raise ValueError(f"the map width must be even and >= 2, got {width}")
+
+
+def sh_project(imgs: torch.Tensor, lmax: int) -> torch.Tensor:
+    """getCoefficientsFromImage for a batch: imgs [N, W/2, W, 3] on the GPU -> coeffs [N, (lmax + 1)^2, 3] float32."""
+    if imgs.dim() != 4 or imgs.shape[3] != 3 or 2 * imgs.shape[1] != imgs.shape[2]:
+        raise ValueError(f"imgs must be [N, W/2, W, 3], got {tuple(imgs.shape)}")
+    _check_sh(imgs.shape[2], lmax)
+    ops._require_cuda(imgs)
+    row, col = _device_tables(imgs.shape[2], lmax, True, imgs.device)
+    return ops.sh_project(imgs, row, col, int(lmax))
+
+
+def sh_reconstruct(coeffs: torch.Tensor, width: int) -> torch.Tensor:
+    """shReconstructSignal for a batch: coeffs [N, T, 3] on the GPU (T a square) -> maps [N, width/2, width, 3] float32."""
+    if coeffs.dim() != 3 or coeffs.shape[2] != 3:
+        raise ValueError(f"coeffs must be [N, T, 3], got {tuple(coeffs.shape)}")
+    lmax = sh_lmax_from_terms(coeffs.shape[1])
+    if shTerms(lmax) != coeffs.shape[1]:
+        raise ValueError(f"the number of SH terms must be a square, got {coeffs.shape[1]}")
+    _check_sh(width, lmax)
+    ops._require_cuda(coeffs)
+    row, col = _device_tables(width, lmax, False, coeffs.device)
+    return ops.sh_reconstruct(coeffs, row, col, int(width) // 2, int(width), lmax)
+
+
+def _gpu():
+    if not torch.cuda.is_available():
+        raise _lib.RENILibraryError("the SH baselines run on a GPU device; there is no CPU fallback")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def getCoefficientsFromImage(ibl, lmax=2, resizeWidth=None, filterAmount=None):
+    """SH coefficients [(lmax + 1)^2, 3] float64 of an equirectangular map [W/2, W, >= 3] (numpy or tensor)."""
+    if resizeWidth is not None:
+        raise NotImplementedError("getCoefficientsFromImage(resizeWidth=...) needs cv2's bicubic resize; resize the map first")
+    if filterAmount is not None:
+        raise NotImplementedError("getCoefficientsFromImage(filterAmount=...) needs scipy's gaussian_filter; blur the map first")
+    img = torch.as_tensor(np.asarray(ibl) if not isinstance(ibl, torch.Tensor) else ibl)
+    if img.shape[1] > 1000:
+        raise ValueError(f"map width {img.shape[1]} > 1000: the reference silently resizes it to 1000 x 500 with cv2; "
+                         "resize the map first")
+    img = img[..., :3].to(_gpu(), torch.float32)
+    return sh_project(img.unsqueeze(0), lmax)[0].cpu().numpy().astype(np.float64)
+
+
+def shReconstructSignal(coeffs, sh_basis_matrix=None, width=600):
+    """The map [width/2, width, 3] float32 of SH coefficients [T, 3]."""
+    if sh_basis_matrix is not None:
+        raise NotImplementedError("shReconstructSignal(sh_basis_matrix=...) is not supported; pass width instead")
+    c = torch.as_tensor(np.asarray(coeffs) if not isinstance(coeffs, torch.Tensor) else coeffs)
+    c = c.to(_gpu(), torch.float32)
+    return sh_reconstruct(c.unsqueeze(0), width)[0].cpu().numpy()
+
+
+def get_spherical_harmonic_representation(img, nBands):
+    """The SH reconstruction of img [H, W, 3] with lmax = nBands (as the reference passes it), a float32 torch tensor."""
+    coeffs = getCoefficientsFromImage(img, nBands)
+    return torch.from_numpy(shReconstructSignal(coeffs, width=img.shape[1]))

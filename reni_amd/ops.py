@@ -691,6 +691,86 @@ def rasterize_mesh(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch
     return p2f, zbuf, bary, dists, nrm, pos
 
 
+def _sg_check(params, theta_c, phi_c, H, W):
+    _require_cuda(params, theta_c, phi_c)
+    if params.dim() != 3 or params.shape[2] != 6:
+        raise ValueError(f"params must be [N, K, 6], got {tuple(params.shape)}")
+    N, K = params.shape[0], params.shape[1]
+    if tuple(theta_c.shape) != (K,) or tuple(phi_c.shape) != (K,):
+        raise ValueError("theta_c and phi_c must be [K]")
+    return _f32c(params), _f32c(theta_c), _f32c(phi_c), N, K, int(H), int(W)
+
+
+def sg_render(params, theta_c, phi_c, theta_range: float, phi_range: float, H: int, W: int) -> torch.Tensor:
+    """reni_sg_render: SGEnvOptim.renderSG of raw parameters [N, K, 6] -> rec [N, 3, H, W]."""
+    params, theta_c, phi_c, N, K, H, W = _sg_check(params, theta_c, phi_c, H, W)
+    dev = params.device
+    rec = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().reni_sg_render(N, K, H, W, params.data_ptr(), theta_c.data_ptr(), phi_c.data_ptr(),
+                                              float(theta_range), float(phi_range), rec.data_ptr(),
+                                              torch.cuda.current_stream(dev).cuda_stream))
+    return rec
+
+
+def sg_loss_grad(params, theta_c, phi_c, theta_range: float, phi_range: float, log_target, weight):
+    """reni_sg_loss_grad: (loss_total [], loss_per_map [N], dparams [N, K, 6]) of WeightedMSE(log(rec + 1), log_target,
+    weight) at raw parameters [N, K, 6].  log_target [N, 3, H, W]; weight any tensor that broadcasts to [N, 3, H, W] (it is
+    read through its expanded strides, nothing is materialised)."""
+    _require_cuda(log_target, weight)
+    log_target = _f32c(log_target)
+    if log_target.dim() != 4 or log_target.shape[1] != 3:
+        raise ValueError(f"log_target must be [N, 3, H, W], got {tuple(log_target.shape)}")
+    N, _, H, W = log_target.shape
+    params, theta_c, phi_c, Np, K, H, W = _sg_check(params, theta_c, phi_c, H, W)
+    if Np != N:
+        raise ValueError("params and log_target disagree on N")
+    if weight.dtype != torch.float32:
+        weight = weight.float()
+    weight = weight.expand(N, 3, H, W)
+    dev = params.device
+    loss_map = torch.empty(N, dtype=torch.float32, device=dev)
+    total = torch.empty((), dtype=torch.float32, device=dev)
+    grad = torch.empty(N, K, 6, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws, wp, wn = _ws256(int(lib.reni_sg_workspace_bytes(N, K, H, W)), dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.reni_sg_loss_grad(N, K, H, W, params.data_ptr(), theta_c.data_ptr(), phi_c.data_ptr(),
+                                         float(theta_range), float(phi_range), log_target.data_ptr(), weight.data_ptr(),
+                                         *[int(x) for x in weight.stride()], loss_map.data_ptr(), total.data_ptr(),
+                                         grad.data_ptr(), wp, wn, torch.cuda.current_stream(dev).cuda_stream))
+    return total, loss_map, grad
+
+
+def _sh_call(project: bool, src, row_table, col_table, H: int, W: int, lmax: int):
+    _require_cuda(src, row_table, col_table)
+    src = _f32c(src)
+    T = (lmax + 1) ** 2
+    N = src.shape[0]
+    dev = src.device
+    out = torch.empty((N, T, 3) if project else (N, H, W, 3), dtype=torch.float32, device=dev)
+    fn = _lib.load().reni_sh_project if project else _lib.load().reni_sh_reconstruct
+    with torch.cuda.device(dev):
+        _lib.check(fn(N, H, W, lmax, src.data_ptr(), _f32c(row_table).data_ptr(), _f32c(col_table).data_ptr(),
+                      out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def sh_project(imgs, row_table, col_table, lmax: int) -> torch.Tensor:
+    """reni_sh_project: imgs [N, H, W, 3] -> coeffs [N, T, 3] against the separable basis tables (row_table [H, T] with
+    the solid angle folded in, col_table [W, T]; reni_hip.h)."""
+    if imgs.dim() != 4 or imgs.shape[3] != 3:
+        raise ValueError(f"imgs must be [N, H, W, 3], got {tuple(imgs.shape)}")
+    return _sh_call(True, imgs, row_table, col_table, imgs.shape[1], imgs.shape[2], int(lmax))
+
+
+def sh_reconstruct(coeffs, row_table, col_table, H: int, W: int, lmax: int) -> torch.Tensor:
+    """reni_sh_reconstruct: coeffs [N, T, 3] -> maps [N, H, W, 3] (row_table without the solid angle)."""
+    if coeffs.dim() != 3 or coeffs.shape[1] != (int(lmax) + 1) ** 2 or coeffs.shape[2] != 3:
+        raise ValueError(f"coeffs must be [N, (lmax + 1)^2, 3], got {tuple(coeffs.shape)}")
+    return _sh_call(False, coeffs, row_table, col_table, int(H), int(W), int(lmax))
+
+
 def _ws256(nbytes, device):
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
     p = ws.data_ptr()

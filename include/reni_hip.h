@@ -433,6 +433,25 @@ int reni_sh_project(int64_t N, int64_t H, int64_t W, int64_t lmax, const float* 
 int reni_sh_reconstruct(int64_t N, int64_t H, int64_t W, int64_t lmax, const float* coeffs, const float* row_table,
                         const float* col_table, float* out, void* stream);
 
+/* ---- diffuse irradiance (src/models/spherical_harmonics.py: getDiffuseMap, shRenderL2) --------------------------------
+ * fp32, deterministic (no float atomics; fixed summation order that depends on (P, Q) only: two calls give identical bits,
+ * and map n's results are the same alone or inside a batch).
+ * reni_diffuse_convolve: out [N][P][3] = scale sum_(i < Q) max(0, out_dirs[o] . in_dirs[i]) in_w[i] src(n, i, c), the
+ *   clamped-cosine convolution (getDiffuseMap :383-437 with scale = 1 / pi).  out_dirs [P][3], in_dirs [Q][3], in_w [Q] are
+ *   shared by the N maps; src(n, i, c) = src[n src_stride_n + i src_stride_i + c src_stride_c] (element strides >= 0:
+ *   [N][Q][3] is (3 Q, 3, 1), channel-planar [N][3][Q] is (3 Q, 1, Q)).  N, P, Q >= 1, 3 N P and 3 Q < 2^30.
+ *   ws: reni_diffuse_workspace_bytes(N, P, Q) bytes, 256-byte aligned (0 bytes -- ws may be NULL -- when the i range is not
+ *   split, which the library decides from (P, Q)).
+ * reni_sh_irradiance_l2: out [N][P][3] = shRenderL2(coeffs[n], normal) (Ramamoorthi & Hanrahan 2001, the reference's C1..C5,
+ *   its - C5 L6 term and its final / pi) for coeffs [N][9][3] and normal (x, y, z) = normals[n normals_stride_n + 3 p + 0..2];
+ *   normals_stride_n is 0 (normals [P][3] shared) or 3 P (normals [N][P][3] per map). */
+size_t reni_diffuse_workspace_bytes(int64_t N, int64_t P, int64_t Q);
+int reni_diffuse_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, const float* in_dirs, const float* in_w,
+                          const float* src, int64_t src_stride_n, int64_t src_stride_i, int64_t src_stride_c, float scale,
+                          float* out, void* ws, size_t ws_bytes, void* stream);
+int reni_sh_irradiance_l2(int64_t N, int64_t P, const float* coeffs, const float* normals, int64_t normals_stride_n, float* out,
+                          void* stream);
+
 /* ---- HDR image epilogue / prologue ------------------------------------------------
  * reni_unnormalise_srgb replaces, on the device and in one call, the reference's viewing chain
  *   UnMinMaxNormlise(minmax)   src/utils/custom_transforms.py:14-21   y = exp(0.5 (x + 1)(m1 - m0) + m0)

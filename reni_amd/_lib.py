@@ -32,6 +32,7 @@ EXPORTS = (
     "reni_envmap_shade_workspace_bytes", "reni_envmap_shade", "reni_envmap_shade_backward",
     "reni_raster_workspace_bytes", "reni_mesh_vertex_normals", "reni_rasterize_mesh",
     "reni_sg_workspace_bytes", "reni_sg_render", "reni_sg_loss_grad", "reni_sh_project", "reni_sh_reconstruct",
+    "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
     "reni_image_workspace_bytes", "reni_unnormalise_srgb", "reni_minmax_normalise",
     "reni_rccl_unique_id", "reni_rccl_comm_create", "reni_rccl_comm_destroy", "reni_allreduce_grads",
 )
@@ -191,6 +192,13 @@ def load():
     for fn in (lib.reni_sh_project, lib.reni_sh_reconstruct):
         fn.argtypes = [c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         fn.restype = c_int32
+    lib.reni_diffuse_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    lib.reni_diffuse_workspace_bytes.restype = c_size_t
+    lib.reni_diffuse_convolve.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                          c_int64, c_float, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_diffuse_convolve.restype = c_int32
+    lib.reni_sh_irradiance_l2.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+    lib.reni_sh_irradiance_l2.restype = c_int32
     lib.reni_image_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
     lib.reni_image_workspace_bytes.restype = c_size_t
     lib.reni_unnormalise_srgb.argtypes = [c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_int32, ctypes.c_double,

@@ -1,8 +1,11 @@
 """Spherical-Gaussian and spherical-harmonic environment-map baselines on the GPU: what RENI is compared against.
 
-Restates the reference's src/models/spherical_gaussians.py (SGEnvOptim) and the projection / reconstruction part of
-src/models/spherical_harmonics.py with the same call shapes.  The arithmetic runs in libreni_hip.so
-(reni_tu_baselines.hip); torch supplies device memory and, for SGEnvOptim, its own LBFGS.  There is no CPU fallback.
+Restates the reference's src/models/spherical_gaussians.py (SGEnvOptim) and src/models/spherical_harmonics.py with the
+same call shapes: the projection / reconstruction part, and the diffuse irradiance part (getDiffuseMap's brute-force
+clamped-cosine convolution, the Ramamoorthi-Hanrahan SH irradiance shRender / shRenderL2, Sloan's ringing window).  The
+arithmetic runs in libreni_hip.so (reni_tu_baselines.hip, reni_tu_diffuse.hip); torch supplies device memory and, for
+SGEnvOptim, its own LBFGS.  The small float64 helpers (grids, solid angles, diffuse coefficients, the windowing factor)
+stay on the host.  There is no CPU fallback.
 
 Differences from the reference, all deliberate:
   - SGEnvOptim.optimize(envmap, sineweight=None) treats sineweight=None as a weight of 1 everywhere (the reference
@@ -10,10 +13,22 @@ Differences from the reference, all deliberate:
   - getCoefficientsFromImage's resizeWidth / filterAmount (cv2 / scipy) raise NotImplementedError, and a map wider than
     1000 pixels -- which the reference silently resizes to 1000 x 500 -- raises ValueError.
   - The SH maps are read as float32 on the device; coefficients come back as float64 arrays, as in the reference.
+  - getDiffuseCoefficients uses the integer (l // 2)!.  The reference calls np.math.factorial(l / 2), which cannot run
+    here (numpy 2 has no np.math, and Python >= 3.10 rejects a float factorial); the integer form is the formula it
+    intends.
+  - getDiffuseMap(ibl, ...) accepts an array, a tensor, or a path read with reni_amd.exr.read_exr.  The reference always
+    resizes the map to `width` with cv2 (bicubic) and, when widthLowRes < outputWidth, upsamples the result with cv2
+    (Lanczos); both raise NotImplementedError here unless they are identities (the map is already width x width / 2 and
+    widthLowRes >= outputWidth).  The reference's prints and timing are dropped.
+  - shRender, shRenderL2 and getDiffuseMap compute in float32 on the device (the reference: float64 on the host).
+Kept on purpose (the golden pins them): getDiffuseMap's own grid (directions at pixel corners, v flipped, solid angles of
+the row centres, output pixel (x, y) looking along input pixel (int(x / wL W), int(y / hL H))), findWindowingFactor's
+m in range(-1, l + 1) and unsquared mean, and shReconstructDiffuseMap's L2 closed form for exactly 9 coefficients.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -313,3 +328,281 @@ def get_spherical_harmonic_representation(img, nBands):
     """The SH reconstruction of img [H, W, 3] with lmax = nBands (as the reference passes it), a float32 torch tensor."""
     coeffs = getCoefficientsFromImage(img, nBands)
     return torch.from_numpy(shReconstructSignal(coeffs, width=img.shape[1]))
+
+
+# ----------------------------------------------------------------------------------------------- diffuse irradiance
+
+
+def l_from_idx(idx):
+    return int(np.sqrt(idx))
+
+
+def getSolidAngle(y, width, is3D=False):
+    """Solid angle of row y of a width x width / 2 map (the row centre's band)."""
+    height = int(width / 2)
+    pi2OverWidth = (np.pi * 2) / width
+    piOverHeight = np.pi / height
+    theta = (1.0 - ((y + 0.5) / height)) * np.pi
+    return pi2OverWidth * (np.cos(theta - (piOverHeight / 2.0)) - np.cos(theta + (piOverHeight / 2.0)))
+
+
+def getSolidAngleMap(width):
+    height = int(width / 2)
+    return np.repeat(getSolidAngle(np.arange(0, height), width)[:, np.newaxis], width, axis=1)
+
+
+def xy2ll(x, y, width, height):
+    """(latitude y pi / height, longitude x 2 pi / width) as an object array, like the reference."""
+    return np.asarray([y / (float(height) / np.pi), x / (float(width) / (np.pi * 2))], dtype=object)
+
+
+def spherical2Cartesian2(theta, phi):
+    phi = phi + np.pi
+    x = np.sin(theta) * np.cos(phi)
+    y = np.cos(theta)
+    z = np.sin(theta) * np.sin(phi)
+    if not np.isscalar(x):
+        y = np.repeat(y, x.shape[1], axis=1)
+    return np.moveaxis(np.asarray([x, z, y]), 0, 2)
+
+
+def getNormalMap(width):
+    """[width / 2, width, 3] float64 normals at the pixels' top-left corners (the SH basis grid)."""
+    height = int(width / 2)
+    x = np.arange(0, width)
+    y = np.arange(0, height).reshape(height, 1)
+    latLon = xy2ll(x, y, width, height)
+    return spherical2Cartesian2(latLon[0], latLon[1])
+
+
+def getDiffuseCoefficients(lmax):
+    """Ramamoorthi & Hanrahan's clamped-cosine band factors A_l / pi, l = 0..lmax, float64."""
+    diffuseCoeffs = [np.pi, (2 * np.pi) / 3]
+    for l in range(2, lmax + 1):
+        if l % 2 == 0:
+            a = (-1.0) ** ((l / 2.0) - 1.0)
+            b = (l + 2.0) * (l - 1.0)
+            c = float(math.factorial(l)) / (2**l * math.factorial(l // 2) ** 2)
+            diffuseCoeffs.append(2 * np.pi * (a / b) * c)
+        else:
+            diffuseCoeffs.append(0)
+    return np.asarray(diffuseCoeffs) / np.pi
+
+
+def findWindowingFactor(coeffs, maxLaplacian=10.0):
+    """Sloan's windowing factor (http://www.ppsloan.org/publications/StupidSH36.pdf) by Newton's method, as the reference
+    computes it: m in range(-1, l + 1), the plain mean of the coefficients, at most 1e7 iterations."""
+    coeffs = np.asarray(coeffs)
+    lmax = sh_lmax_from_terms(coeffs.shape[0])
+    tableL = np.zeros((lmax + 1))
+    tableB = np.zeros((lmax + 1))
+    for l in range(1, lmax + 1):
+        tableL[l] = float((l * l) * ((l + 1) * (l + 1)))
+        B = 0.0
+        for m in range(-1, l + 1):
+            B += np.mean(coeffs[shIndex(l, m), :])
+        tableB[l] = B
+    squaredLaplacian = 0.0
+    for l in range(1, lmax + 1):
+        squaredLaplacian += tableL[l] * tableB[l]
+    targetSquaredLaplacian = maxLaplacian * maxLaplacian
+    if squaredLaplacian <= targetSquaredLaplacian:
+        return 0.0
+    windowingFactor = 0.0
+    for _ in range(0, 10000000):
+        f = 0.0
+        fd = 0.0
+        for l in range(1, lmax + 1):
+            f += tableL[l] * tableB[l] / ((1.0 + windowingFactor * tableL[l]) * (1.0 + windowingFactor * tableL[l]))
+            d = 1.0 + windowingFactor * tableL[l]
+            fd += (2.0 * (tableL[l] * tableL[l]) * tableB[l]) / (d * d * d)
+        f = targetSquaredLaplacian - f
+        delta = -f / fd
+        windowingFactor += delta
+        if abs(delta) < 0.0000001:
+            break
+    return windowingFactor
+
+
+def applyWindowing(coeffs, windowingFactor=None, verbose=False):
+    """Scales band l of coeffs [T, 3] by 1 / (1 + f l^2 (l + 1)^2) in place (f <= 0: unchanged) and returns it."""
+    lmax = sh_lmax_from_terms(coeffs.shape[0])
+    if windowingFactor is None:
+        windowingFactor = findWindowingFactor(coeffs)
+    if windowingFactor <= 0:
+        if verbose:
+            print("No windowing applied")
+        return coeffs
+    if verbose:
+        print("Using windowingFactor: %s" % (windowingFactor))
+    for l in range(0, lmax + 1):
+        s = 1.0 / (1.0 + windowingFactor * l * l * (l + 1.0) * (l + 1.0))
+        for m in range(-l, l + 1):
+            coeffs[shIndex(l, m), :] *= s
+    return coeffs
+
+
+def diffuse_map_tables(width, widthLowRes):
+    """getDiffuseMap's grid in float64: (in_dirs [H W, 3], in_weight [H W] (the row's solid angle), out_dirs [hL wL, 3]).
+    Pixel (x, y) looks along (cos phi sin theta, sin phi, cos phi cos theta), phi = pi ((1 - y / H) - 0.5),
+    theta = 2 pi (1 - x / W); output pixel (x, y) along input pixel (int(x / wL W), int(y / hL H))."""
+    width, widthLowRes = int(width), int(widthLowRes)
+    height, heightLowRes = int(width / 2), int(widthLowRes / 2)
+    uv_x = np.tile(np.arange(float(width)) / width, (height, 1))
+    uv_y = 1 - np.tile(np.arange(float(height)) / height, (width, 1)).transpose()
+    phi = np.pi * (uv_y - 0.5)
+    theta = 2 * np.pi * (1 - uv_x)
+    cos_phi = np.cos(phi)
+    d = np.stack([cos_phi * np.sin(theta), np.sin(phi), cos_phi * np.cos(theta)], -1)  # [H, W, 3]
+    xs = [int((float(x) / widthLowRes) * width) for x in range(widthLowRes)]
+    ys = [int((float(y) / heightLowRes) * height) for y in range(heightLowRes)]
+    out = d[np.asarray(ys)[:, None], np.asarray(xs)[None, :]]
+    return d.reshape(-1, 3), getSolidAngleMap(width).reshape(-1), out.reshape(-1, 3)
+
+
+def reni_grid_weights(width):
+    """The exact band solid angles of RENI's width x width / 2 grid, [H W] float64: row k covers polar angles
+    [k pi / H, (k + 1) pi / H], so each pixel gets (2 pi / W)(cos(k pi / H) - cos((k + 1) pi / H))."""
+    W = int(width)
+    H = W // 2
+    k = np.arange(H, dtype=np.float64)
+    band = (2 * np.pi / W) * (np.cos(k * np.pi / H) - np.cos((k + 1) * np.pi / H))
+    return np.repeat(band, W)
+
+
+_DTABLES = {}
+
+
+def _diffuse_device_tables(key, make, device):
+    key = key + (str(device),)
+    if key not in _DTABLES:
+        _DTABLES[key] = tuple(torch.as_tensor(np.asarray(t, np.float32) if isinstance(t, np.ndarray) else t)
+                              .to(device, torch.float32).contiguous() for t in make())
+    return _DTABLES[key]
+
+
+def diffuse_convolve(src: torch.Tensor, in_dirs: torch.Tensor, in_weight: torch.Tensor, out_dirs: torch.Tensor,
+                     scale: float = 1.0 / np.pi) -> torch.Tensor:
+    """E[n, o, c] = scale sum_i max(0, out_dirs[o] . in_dirs[i]) in_weight[i] src[n, i, c] on the GPU, without a [P, Q]
+    tensor.  src [N, Q, 3] or channel-planar [N, 3, Q] (any strides); in_dirs [Q, 3], in_weight [Q], out_dirs [P, 3]
+    -> [N, P, 3] float32."""
+    return ops.diffuse_convolve(src, in_dirs, in_weight, out_dirs, scale)
+
+
+def irradiance_map(envmaps: torch.Tensor, out_width=None) -> torch.Tensor:
+    """Diffuse irradiance (/ pi: a constant map of 1 gives 1) of maps on RENI's own grid (reni_amd.utils.get_directions):
+    envmaps [N, H W, 3] or [N, H, W, 3] on the GPU -> the same layout at out_width (default: the input width)."""
+    from .utils import get_directions
+    if envmaps.dim() == 4 and envmaps.shape[3] == 3 and 2 * envmaps.shape[1] == envmaps.shape[2]:
+        W = int(envmaps.shape[2])
+        src = envmaps.reshape(envmaps.shape[0], -1, 3)
+    elif envmaps.dim() == 3 and envmaps.shape[2] == 3:
+        W = int(round(math.sqrt(2 * envmaps.shape[1])))
+        if W * (W // 2) != envmaps.shape[1] or W % 2:
+            raise ValueError(f"[N, H W, 3] maps need H W = W^2 / 2 for an even W, got {envmaps.shape[1]} pixels")
+        src = envmaps
+    else:
+        raise ValueError(f"envmaps must be [N, H W, 3] or [N, W/2, W, 3], got {tuple(envmaps.shape)}")
+    Wo = W if out_width is None else int(out_width)
+    if Wo < 2 or Wo % 2:
+        raise ValueError(f"out_width must be even and >= 2, got {out_width}")
+    ops._require_cuda(envmaps)
+    dirs, w = _diffuse_device_tables(("reni", W), lambda: (get_directions(W)[0], reni_grid_weights(W)), envmaps.device)
+    (odirs,) = _diffuse_device_tables(("reni_out", Wo), lambda: (get_directions(Wo)[0],), envmaps.device)
+    out = ops.diffuse_convolve(src, dirs, w, odirs, 1.0 / np.pi)
+    return out.view(envmaps.shape[0], Wo // 2, Wo, 3) if envmaps.dim() == 4 else out
+
+
+def sh_irradiance(coeffs: torch.Tensor, width: int) -> torch.Tensor:
+    """shReconstructDiffuseMap for a batch: coeffs [N, T, 3] on the GPU -> [N, width / 2, width, 3] float32; the L2
+    closed form (shRenderL2) when T == 9, otherwise shRender (the SH reconstruction of the coefficients scaled by
+    getDiffuseCoefficients)."""
+    if coeffs.dim() != 3 or coeffs.shape[2] != 3:
+        raise ValueError(f"coeffs must be [N, T, 3], got {tuple(coeffs.shape)}")
+    lmax = sh_lmax_from_terms(coeffs.shape[1])
+    if shTerms(lmax) != coeffs.shape[1]:
+        raise ValueError(f"the number of SH terms must be a square, got {coeffs.shape[1]}")
+    _check_sh(width, lmax)
+    ops._require_cuda(coeffs)
+    W = int(width)
+    if coeffs.shape[1] == 9:
+        (nrm,) = _diffuse_device_tables(("normals", W), lambda: (getNormalMap(W).reshape(-1, 3),), coeffs.device)
+        return ops.sh_irradiance_l2(coeffs, nrm).view(coeffs.shape[0], W // 2, W, 3)
+    (band,) = _diffuse_device_tables(("band", lmax), lambda: (_band_scale(lmax),), coeffs.device)
+    return sh_reconstruct(coeffs * band.view(1, -1, 1), W)
+
+
+def _band_scale(lmax):
+    """getDiffuseCoefficients(lmax)[l] per term t, float64"""
+    d = getDiffuseCoefficients(lmax)
+    return np.asarray([d[l_from_idx(t)] for t in range(shTerms(lmax))])
+
+
+def _host_coeffs(iblCoeffs):
+    c = iblCoeffs.detach().cpu().numpy() if isinstance(iblCoeffs, torch.Tensor) else np.asarray(iblCoeffs)
+    return c.astype(np.float64)
+
+
+def shRender(iblCoeffs, width=600):
+    """Diffuse render [width / 2, width, 3] (float64 array of the float32 result) of SH coefficients [T, 3]: the
+    reconstruction of the coefficients scaled by getDiffuseCoefficients(lmax)[l] on the host."""
+    c = _host_coeffs(iblCoeffs)
+    lmax = sh_lmax_from_terms(c.shape[0])
+    scaled = torch.from_numpy((c * _band_scale(lmax)[:, None]).astype(np.float32))
+    return sh_reconstruct(scaled.to(_gpu()).unsqueeze(0), width)[0].cpu().numpy().astype(np.float64)
+
+
+def shRenderL2(iblCoeffs, normalMap):
+    """shRenderL2 of coefficients [9+, 3] at normals [..., 3] -> [..., 3] (float64 array of the float32 result)."""
+    c = _host_coeffs(iblCoeffs)[:9]
+    n = normalMap.detach() if isinstance(normalMap, torch.Tensor) else torch.from_numpy(np.asarray(normalMap, np.float64))
+    shape = tuple(n.shape)
+    if shape[-1] != 3:
+        raise ValueError(f"normalMap must be [..., 3], got {shape}")
+    dev = _gpu()
+    out = ops.sh_irradiance_l2(torch.from_numpy(c.astype(np.float32)).to(dev).unsqueeze(0),
+                               n.reshape(-1, 3).to(dev, torch.float32))
+    return out[0].cpu().numpy().astype(np.float64).reshape(shape)
+
+
+def shReconstructDiffuseMap(iblCoeffs, width=600):
+    """The diffuse map [width / 2, width, 3] float32 of SH coefficients [T, 3]: shRenderL2 on getNormalMap(width) when
+    T == 9, shRender otherwise."""
+    c = _host_coeffs(iblCoeffs)
+    if c.shape[0] == 9:
+        return shRenderL2(c, getNormalMap(width)).astype(np.float32)
+    return shRender(c, width).astype(np.float32)
+
+
+def shReconstructDiffuseNormalMap(iblCoeffs, normal_map):
+    return shRenderL2(iblCoeffs, normal_map).astype(np.float32)
+
+
+def _read_ibl(ibl):
+    if isinstance(ibl, (str, bytes, os.PathLike)):
+        from .exr import read_exr
+        return torch.from_numpy(np.ascontiguousarray(read_exr(ibl)))
+    return ibl if isinstance(ibl, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ibl))
+
+
+def getDiffuseMap(ibl_name, width=600, widthLowRes=32, outputWidth=None):
+    """The ground-truth diffuse map [widthLowRes / 2, widthLowRes, 3] float32 of an equirectangular map [width / 2, width,
+    >= 3] (array, tensor or EXR path): the brute-force clamped-cosine convolution / pi on getDiffuseMap's own grid."""
+    if outputWidth is None:
+        outputWidth = width
+    height = int(width / 2)
+    img = _read_ibl(ibl_name)
+    if img.dim() != 3 or img.shape[2] < 3:
+        raise ValueError(f"the map must be [H, W, >= 3], got {tuple(img.shape)}")
+    if tuple(img.shape[:2]) != (height, width):
+        raise NotImplementedError(f"getDiffuseMap resizes a {tuple(img.shape[:2])} map to ({height}, {width}) with cv2's "
+                                  "bicubic resize; resize the map first")
+    if widthLowRes < outputWidth:
+        raise NotImplementedError(f"getDiffuseMap upsamples the {widthLowRes}-wide result to {outputWidth} with cv2's "
+                                  "Lanczos resize; pass outputWidth=widthLowRes")
+    dev = _gpu()
+    dirs, w, odirs = _diffuse_device_tables(("ref", int(width), int(widthLowRes)),
+                                            lambda: diffuse_map_tables(width, widthLowRes), dev)
+    src = img[..., :3].to(dev, torch.float32).reshape(1, -1, 3)
+    out = ops.diffuse_convolve(src, dirs, w, odirs, 1.0 / np.pi)
+    return out.view(int(widthLowRes / 2), int(widthLowRes), 3).cpu().numpy()

@@ -771,6 +771,61 @@ def sh_reconstruct(coeffs, row_table, col_table, H: int, W: int, lmax: int) -> t
     return _sh_call(False, coeffs, row_table, col_table, int(H), int(W), int(lmax))
 
 
+def diffuse_convolve(src, in_dirs, in_weight, out_dirs, scale: float) -> torch.Tensor:
+    """reni_diffuse_convolve: out [N, P, 3] = scale sum_i max(0, out_dirs[o] . in_dirs[i]) in_weight[i] src[n, i, c].
+    src is [N, Q, 3] or channel-planar [N, 3, Q], read through its own strides (any float32 view of those shapes);
+    in_dirs [Q, 3], in_weight [Q], out_dirs [P, 3] are shared by the N maps."""
+    _require_cuda(src, in_dirs, in_weight, out_dirs)
+    in_dirs, in_weight, out_dirs = _f32c(in_dirs), _f32c(in_weight), _f32c(out_dirs)
+    if in_dirs.dim() != 2 or in_dirs.shape[1] != 3 or out_dirs.dim() != 2 or out_dirs.shape[1] != 3:
+        raise ValueError("in_dirs and out_dirs must be [Q, 3] and [P, 3]")
+    Q, P = in_dirs.shape[0], out_dirs.shape[0]
+    if tuple(in_weight.shape) != (Q,):
+        raise ValueError(f"in_weight must be [Q] = [{Q}], got {tuple(in_weight.shape)}")
+    if src.dtype != torch.float32:
+        src = src.float()
+    if src.dim() != 3:
+        raise ValueError(f"src must be [N, Q, 3] or [N, 3, Q], got {tuple(src.shape)}")
+    N = src.shape[0]
+    if src.shape[1] == Q and src.shape[2] == 3:
+        sn, si, sc = src.stride()
+    elif src.shape[1] == 3 and src.shape[2] == Q:
+        sn, sc, si = src.stride()
+    else:
+        raise ValueError(f"src must be [N, Q, 3] or [N, 3, Q] with Q = {Q}, got {tuple(src.shape)}")
+    dev = src.device
+    out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws, wp, wn = _ws256(int(lib.reni_diffuse_workspace_bytes(N, P, Q)), dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.reni_diffuse_convolve(N, P, Q, out_dirs.data_ptr(), in_dirs.data_ptr(), in_weight.data_ptr(),
+                                             src.data_ptr(), sn, si, sc, float(scale), out.data_ptr(), wp, wn,
+                                             torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+def sh_irradiance_l2(coeffs, normals) -> torch.Tensor:
+    """reni_sh_irradiance_l2: shRenderL2 of coeffs [N, 9, 3] at normals [P, 3] (shared) or [N, P, 3] (per map) -> [N, P, 3]."""
+    _require_cuda(coeffs, normals)
+    coeffs, normals = _f32c(coeffs), _f32c(normals)
+    if coeffs.dim() != 3 or coeffs.shape[1:] != (9, 3):
+        raise ValueError(f"coeffs must be [N, 9, 3], got {tuple(coeffs.shape)}")
+    N = coeffs.shape[0]
+    if normals.dim() == 2 and normals.shape[1] == 3:
+        P, stride = normals.shape[0], 0
+    elif normals.dim() == 3 and normals.shape[0] == N and normals.shape[2] == 3:
+        P = normals.shape[1]
+        stride = 3 * P
+    else:
+        raise ValueError(f"normals must be [P, 3] or [N, P, 3], got {tuple(normals.shape)}")
+    dev = coeffs.device
+    out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().reni_sh_irradiance_l2(N, P, coeffs.data_ptr(), normals.data_ptr(), stride, out.data_ptr(),
+                                                     torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 def _ws256(nbytes, device):
     ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
     p = ws.data_ptr()

@@ -474,6 +474,34 @@ int reni_unnormalise_srgb(int64_t B, int64_t H, int64_t W, const float* img, con
                           size_t ws_bytes, void* stream);
 int reni_minmax_normalise(int64_t n, const float* img, double minmax0, double minmax1, float* out, void* ws, size_t ws_bytes,
                           void* stream);
+/* reni_minmax_normalise_batch: the same transform over N images of n contiguous elements each ([N][n]); the clip bounds are
+ * each image's own, every element goes through the expression reni_minmax_normalise uses (image b's result is bit-identical
+ * to a single-image call), and with nan_to_num != 0 torch.nan_to_num follows (NaN -> 0, +-inf -> +-FLT_MAX; datasets.py:72).
+ * ws: reni_minmax_batch_workspace_bytes(N) bytes, 256-byte aligned.  1 <= N <= 65535, 1 <= n < 2^30. */
+size_t reni_minmax_batch_workspace_bytes(int64_t N);
+int reni_minmax_normalise_batch(int64_t N, int64_t n, const float* imgs, double minmax0, double minmax1, int32_t nan_to_num,
+                                float* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- image resampling and blur (reni_tu_resample.hip; the resident dataset, baselines.resizeImage / blurIBL) -------------
+ * fp32, no atomics: two calls give identical bits and an image's result is the same alone or inside a batch.
+ * reni_resample: the separable table-driven gather
+ *     out[n][c][y][x] = sum_(j < row_taps) row_w[y][j] ( sum_(k < col_taps) col_w[x][k] src(n, c, row_idx[y][j], col_idx[x][k]) )
+ *   with src(n, c, y, x) = src[n s0 + c s1 + y s2 + x s3] (element strides >= 0: channel-last [H][W][3] is {0, 1, 3 W, 3},
+ *   planar [N][3][H][W] is {3HW, HW, W, 1}) and out planar [N][C][Hd][Wd].  The tables are device arrays built by the host
+ *   (reni_amd/resample.py: coordinates in exact integers / float64, rounded to fp32 once): row_idx, row_w [Hd][row_taps],
+ *   col_idx, col_w [Wd][col_taps], 1 <= taps <= 8.  The interpolation mode lives in the tables alone.  Indices are clamped to
+ *   the source on the device, so a bad table cannot read outside it.  N, C <= 65535, Hs Ws < 2^30, N C Hd Wd < 2^30.
+ * reni_gaussian_blur: scipy.ndimage.gaussian_filter(img2d, sigma) per channel (blurIBL, spherical_harmonics.py:564-569):
+ *   separable, axis 0 (rows) first, then axis 1; boundary `reflect` (d c b a | a b c d | d c b a); the fp32 intermediate lives
+ *   in ws.  weights: device array [2 radius + 1] (the host normalises exp(-x^2 / 2 sigma^2) in float64, radius =
+ *   int(4 sigma + 0.5)).  Element (c, y, x) of src and of out at c s0 + y s1 + x s2 (out has the input's layout).
+ *   ws: reni_blur_workspace_bytes(C, H, W) bytes, 256-byte aligned. */
+int reni_resample(int64_t N, int64_t C, int64_t Hs, int64_t Ws, int64_t Hd, int64_t Wd, const float* src,
+                  const int64_t src_strides[4], const int32_t* row_idx, const float* row_w, int32_t row_taps,
+                  const int32_t* col_idx, const float* col_w, int32_t col_taps, float* out, void* stream);
+size_t reni_blur_workspace_bytes(int64_t C, int64_t H, int64_t W);
+int reni_gaussian_blur(int64_t C, int64_t H, int64_t W, const float* src, const int64_t strides[3], const float* weights,
+                       int32_t radius, float* out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- the data-parallel exchange step over RCCL -------------------------------
  * Replaces, for the flat decoder gradient, what Lightning's DDP wrapper does in the reference (run.py:97-110:

@@ -34,6 +34,8 @@ EXPORTS = (
     "reni_sg_workspace_bytes", "reni_sg_render", "reni_sg_loss_grad", "reni_sh_project", "reni_sh_reconstruct",
     "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
     "reni_image_workspace_bytes", "reni_unnormalise_srgb", "reni_minmax_normalise",
+    "reni_minmax_batch_workspace_bytes", "reni_minmax_normalise_batch",
+    "reni_resample", "reni_blur_workspace_bytes", "reni_gaussian_blur",
     "reni_rccl_unique_id", "reni_rccl_comm_create", "reni_rccl_comm_destroy", "reni_allreduce_grads",
 )
 
@@ -207,6 +209,19 @@ def load():
     lib.reni_minmax_normalise.argtypes = [c_int64, c_void_p, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_size_t,
                                           c_void_p]
     lib.reni_minmax_normalise.restype = c_int32
+    lib.reni_minmax_batch_workspace_bytes.argtypes = [c_int64]
+    lib.reni_minmax_batch_workspace_bytes.restype = c_size_t
+    lib.reni_minmax_normalise_batch.argtypes = [c_int64, c_int64, c_void_p, ctypes.c_double, ctypes.c_double, c_int32, c_void_p,
+                                                c_void_p, c_size_t, c_void_p]
+    lib.reni_minmax_normalise_batch.restype = c_int32
+    lib.reni_resample.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p,
+                                  c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
+    lib.reni_resample.restype = c_int32
+    lib.reni_blur_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    lib.reni_blur_workspace_bytes.restype = c_size_t
+    lib.reni_gaussian_blur.argtypes = [c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p, c_int32, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]
+    lib.reni_gaussian_blur.restype = c_int32
     lib.reni_rccl_unique_id.argtypes = [c_void_p]
     lib.reni_rccl_unique_id.restype = c_int32
     lib.reni_rccl_comm_create.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]

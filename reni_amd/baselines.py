@@ -12,6 +12,10 @@ Differences from the reference, all deliberate:
     crashes on None).
   - getCoefficientsFromImage's resizeWidth / filterAmount (cv2 / scipy) raise NotImplementedError, and a map wider than
     1000 pixels -- which the reference silently resizes to 1000 x 500 -- raises ValueError.
+    resizeImage (bicubic / Lanczos) and blurIBL below are the device restatements to do that with; the wrappers themselves
+    keep refusing, so nothing is resampled behind the caller's back.
+  - resizeImage has no "max_pooling" option (skimage), and cv2 is on no machine this was developed on: bicubic is pinned
+    against torch's float64 bicubic, Lanczos against its closed form, not against cv2 itself.
   - The SH maps are read as float32 on the device; coefficients come back as float64 arrays, as in the reference.
   - getDiffuseCoefficients uses the integer (l // 2)!.  The reference calls np.math.factorial(l / 2), which cannot run
     here (numpy 2 has no np.math, and Python >= 3.10 rejects a float factorial); the integer form is the formula it
@@ -313,6 +317,37 @@ def getCoefficientsFromImage(ibl, lmax=2, resizeWidth=None, filterAmount=None):
                          "resize the map first")
     img = img[..., :3].to(_gpu(), torch.float32)
     return sh_project(img.unsqueeze(0), lmax)[0].cpu().numpy().astype(np.float64)
+
+
+INTER_CUBIC, INTER_LANCZOS4 = 2, 4  # cv2's constants, as the reference passes them
+_INTERPOLATION = {INTER_CUBIC: "bicubic", INTER_LANCZOS4: "lanczos4"}
+
+
+def resizeImage(img, width, height, interpolation=INTER_CUBIC):
+    """The map [H, W, C] or [H, W] (numpy or tensor) resampled to [height, width, C] float32 numpy on the GPU, with cv2's
+    conventions for INTER_CUBIC (default) and INTER_LANCZOS4 on float images: half-pixel centres, replicated border, no
+    antialiasing when shrinking (reni_amd/resample.py).  This is the "resize the map first" that getCoefficientsFromImage and
+    getDiffuseMap ask for.  The reference's "max_pooling" option (skimage block_reduce) is not restated and raises."""
+    if isinstance(interpolation, str):
+        raise NotImplementedError(f"resizeImage(interpolation={interpolation!r}) is not supported; use INTER_CUBIC or INTER_LANCZOS4")
+    if interpolation not in _INTERPOLATION:
+        raise ValueError(f"interpolation must be INTER_CUBIC ({INTER_CUBIC}) or INTER_LANCZOS4 ({INTER_LANCZOS4}), got {interpolation!r}")
+    t = torch.as_tensor(np.asarray(img) if not isinstance(img, torch.Tensor) else img)
+    if t.dim() not in (2, 3):
+        raise ValueError(f"img must be [H, W] or [H, W, C], got {tuple(t.shape)}")
+    t = t.to(_gpu(), torch.float32)
+    out = ops.resample(t, (int(height), int(width)), _INTERPOLATION[interpolation], layout="hwc" if t.dim() == 3 else "chw")
+    return (out.permute(1, 2, 0) if t.dim() == 3 else out).contiguous().cpu().numpy()
+
+
+def blurIBL(ibl, amount=5):
+    """scipy.ndimage.gaussian_filter(channel, sigma=amount) of every channel of the map [H, W, C] (numpy or tensor), on the
+    GPU: float32 numpy of the same shape.  This is the "blur the map first" that getCoefficientsFromImage asks for."""
+    t = torch.as_tensor(np.asarray(ibl) if not isinstance(ibl, torch.Tensor) else ibl)
+    if t.dim() != 3:
+        raise ValueError(f"ibl must be [H, W, C], got {tuple(t.shape)}")
+    t = t.to(_gpu(), torch.float32)
+    return ops.gaussian_blur(t, float(amount), layout="hwc").cpu().numpy()
 
 
 def shReconstructSignal(coeffs, sh_basis_matrix=None, width=600):

@@ -144,14 +144,58 @@ __global__ void __launch_bounds__(256) k_img_minmax(const float* in, long long n
 
 __global__ void k_img_minmax_init(unsigned* mm) { mm[0] = 0x7f800000u; mm[1] = 0u; }
 
+DEV float img_normalise_one(float xi, float lo, float hi, float m0, float range) {
+  const float x = (xi != xi) ? xi : fminf(fmaxf(xi, lo), hi);  // torch.clip: min(max(x, lo), hi), NaN stays NaN (fmaxf would drop it)
+  return __fsub_rn(__fdiv_rn(__fmul_rn(2.f, __fsub_rn(logf(x), m0)), range), 1.f);  // 2 * (log x - m0) / (m1 - m0) - 1
+}
+
 __global__ void __launch_bounds__(256) k_img_normalise(const float* in, long long n, const unsigned* mm, float m0, float range,
                                                        float* out) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float lo = __uint_as_float(mm[0]), hi = __uint_as_float(mm[1]);
-  const float xi = in[i];
-  const float x = (xi != xi) ? xi : fminf(fmaxf(xi, lo), hi);  // torch.clip: min(max(x, lo), hi), NaN stays NaN (fmaxf would drop it)
-  out[i] = __fsub_rn(__fdiv_rn(__fmul_rn(2.f, __fsub_rn(logf(x), m0)), range), 1.f);  // 2 * (log x - m0) / (m1 - m0) - 1
+  out[i] = img_normalise_one(in[i], __uint_as_float(mm[0]), __uint_as_float(mm[1]), m0, range);
+}
+
+// the batched form (the resident dataset's levels): image b = blockIdx.y owns the n elements at in + b n and the words mm[2 b .. 2 b + 1]
+__global__ void k_img_minmax_init_batch(unsigned* mm, int N) {
+  const int b = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (b < N) { mm[2 * b] = 0x7f800000u; mm[2 * b + 1] = 0u; }
+}
+
+__global__ void __launch_bounds__(256) k_img_minmax_batch(const float* in, long long n, unsigned* mm) {
+  in += (long long)blockIdx.y * n;
+  unsigned lo = 0x7f800000u, hi = 0u;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float x = in[i];
+    if (x > 0.f) lo = min(lo, __float_as_uint(x));
+    if (x < INFINITY && x >= 0.f) hi = max(hi, __float_as_uint(x));
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    lo = min(lo, (unsigned)__shfl_xor((int)lo, d, 64));
+    hi = max(hi, (unsigned)__shfl_xor((int)hi, d, 64));
+  }
+  // one atomic pair per workgroup (the words of an image are one address each: every atomic on them is serialised).  Integer
+  // min / max of the float bits: order-independent, so the result is too.
+  __shared__ unsigned slo[4], shi[4];
+  if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicMin(&mm[2 * blockIdx.y], min(min(slo[0], slo[1]), min(slo[2], slo[3])));
+    atomicMax(&mm[2 * blockIdx.y + 1], max(max(shi[0], shi[1]), max(shi[2], shi[3])));
+  }
+}
+
+__global__ void __launch_bounds__(256) k_img_normalise_batch(const float* in, long long n, const unsigned* mm, float m0, float range,
+                                                             int nan_to_num, float* out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const long long e = (long long)blockIdx.y * n + i;
+  float v = img_normalise_one(in[e], __uint_as_float(mm[2 * blockIdx.y]), __uint_as_float(mm[2 * blockIdx.y + 1]), m0, range);
+  if (nan_to_num) {  // torch.nan_to_num (datasets.py:72): NaN -> 0, +-inf -> +-FLT_MAX
+    if (v != v) v = 0.f;
+    v = fminf(fmaxf(v, -3.402823466e+38f), 3.402823466e+38f);
+  }
+  out[e] = v;
 }
 
 }  // namespace reni
@@ -225,6 +269,27 @@ int reni_minmax_normalise(int64_t n, const float* img, double minmax0, double mi
   hipLaunchKernelGGL(reni::k_img_minmax, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s, img, (long long)n, mm);
   hipLaunchKernelGGL(reni::k_img_normalise, dim3((unsigned)nb), dim3(256), 0, s, img, (long long)n, (const unsigned*)mm, (float)minmax0,
                      (float)(minmax1 - minmax0), out);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return reni_set_error(RENI_EHIP, hipGetErrorString(e));
+  return RENI_OK;
+}
+
+size_t reni_minmax_batch_workspace_bytes(int64_t N) { return N < 1 || N > 65535 ? 0 : (size_t)N * 8 + 256; }
+
+int reni_minmax_normalise_batch(int64_t N, int64_t n, const float* imgs, double minmax0, double minmax1, int32_t nan_to_num,
+                                float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (N < 1 || N > 65535 || n < 1 || n > 0x3fffffffLL) return reni_set_error(RENI_EINVAL, "normalise batch: need 1 <= N <= 65535, 1 <= n < 2^30");
+  if (!imgs || !out) return reni_set_error(RENI_EINVAL, "normalise batch: NULL argument");
+  if (!(minmax1 > minmax0)) return reni_set_error(RENI_EINVAL, "normalise batch: minmax[1] must exceed minmax[0]");
+  if (!ws || ws_bytes < (size_t)N * 8 || ((uintptr_t)ws & 255))
+    return reni_set_error(RENI_EWORKSPACE, "normalise batch: workspace missing, too small or not 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned* mm = (unsigned*)ws;
+  hipLaunchKernelGGL(reni::k_img_minmax_init_batch, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, mm, (int)N);
+  const long long nb = (n + 255) / 256;
+  hipLaunchKernelGGL(reni::k_img_minmax_batch, dim3((unsigned)(nb < 128 ? nb : 128), (unsigned)N), dim3(256), 0, s, imgs, (long long)n, mm);
+  hipLaunchKernelGGL(reni::k_img_normalise_batch, dim3((unsigned)nb, (unsigned)N), dim3(256), 0, s, imgs, (long long)n,
+                     (const unsigned*)mm, (float)minmax0, (float)(minmax1 - minmax0), nan_to_num ? 1 : 0, out);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return reni_set_error(RENI_EHIP, hipGetErrorString(e));
   return RENI_OK;

@@ -262,6 +262,9 @@ class RENI(_Base):
                 transforms = transform_builder([["resize", list(img_size)]] + [list(t) for t in dcfg.TRANSFORMS])
                 split = "Train" if self.task == "FIT_DECODER" else "Test"
                 self.dataset = get_dataset(name, dcfg.PATH + os.sep + split, transforms, self.is_hdr)
+                if getattr(ds, "RESIDENT", False):  # (not in the reference) decode every file once, keep all levels on the GPU
+                    from .data import ResidentDataset
+                    self.dataset = ResidentDataset(self.dataset, levels=len(tcfg.CURRICULUM) if tcfg.MULTI_RES_TRAINING else 0)
         self.batch_size = tcfg.BATCH_SIZE
         self.dataloader = torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size)
 

@@ -875,6 +875,114 @@ def minmax_normalise(img: torch.Tensor, minmax):
     return out
 
 
+def minmax_normalise_batch(imgs: torch.Tensor, minmax, nan_to_num: bool = True):
+    """reni_minmax_normalise_batch: MinMaxNormalise(minmax) of every image imgs[n] of a batch [N, ...] with its own clip
+    bounds; imgs[n]'s result is bit-identical to ``minmax_normalise(imgs[n])``.  nan_to_num: torch.nan_to_num afterwards, as
+    the HDR dataset applies it."""
+    _require_cuda(imgs)
+    if imgs.dim() < 2 or imgs.shape[0] < 1 or imgs[0].numel() < 1:
+        raise ValueError(f"expected a batch [N, ...] of N >= 1 non-empty images, got {tuple(imgs.shape)}")
+    lib = _lib.load()
+    x = _f32c(imgs)
+    out = torch.empty_like(x)
+    N = x.shape[0]
+    ws, wp, wn = _ws256(int(lib.reni_minmax_batch_workspace_bytes(N)), x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.reni_minmax_normalise_batch(N, x[0].numel(), x.data_ptr(), float(minmax[0]), float(minmax[1]),
+                                                   1 if nan_to_num else 0, out.data_ptr(), wp, wn,
+                                                   torch.cuda.current_stream(x.device).cuda_stream))
+    return out
+
+
+def _image_layout(img: torch.Tensor, layout: str):
+    """(view [N, C, H, W] of img without copying, a function that gives a planar result the caller's rank).  layout: "chw"
+    (planar [H,W], [C,H,W], [N,C,H,W]), "hwc" (channel-last [H,W,C], [N,H,W,C]) or "auto": 2 and 4 dimensions are planar, 3
+    dimensions are channel-last when only the last axis is <= 4 long and planar when only the first is."""
+    if layout not in ("auto", "chw", "hwc"):
+        raise ValueError(f"layout must be 'auto', 'chw' or 'hwc', got {layout!r}")
+    d = img.dim()
+    if layout == "auto":
+        if d == 3:
+            first, last = img.shape[0] <= 4, img.shape[2] <= 4
+            if first == last:
+                raise ValueError(f"cannot tell whether {tuple(img.shape)} is [C,H,W] or [H,W,C]: pass layout='chw' or 'hwc'")
+            layout = "hwc" if last else "chw"
+        else:
+            layout = "chw"
+    if layout == "chw":
+        if d == 2:
+            return img[None, None], lambda o: o[0, 0]
+        if d == 3:
+            return img[None], lambda o: o[0]
+        if d == 4:
+            return img, lambda o: o
+    else:
+        if d == 3:
+            return img.permute(2, 0, 1)[None], lambda o: o[0]
+        if d == 4:
+            return img.permute(0, 3, 1, 2), lambda o: o
+    raise ValueError(f"expected an image or a batch of images, got {tuple(img.shape)} with layout {layout!r}")
+
+
+def resample(src: torch.Tensor, size, mode: str = "bilinear", layout: str = "auto") -> torch.Tensor:
+    """reni_resample: src resampled to size = (height, width) with mode "nearest" | "bilinear" | "bicubic" | "lanczos4"
+    (conventions: reni_amd/resample.py).  src is read in place through its strides, planar ([H,W], [C,H,W], [N,C,H,W]) or
+    channel-last ([H,W,C], [N,H,W,C] with layout="hwc"); the result is planar float32 of the same rank ([Hd,Wd], [C,Hd,Wd],
+    [N,C,Hd,Wd]).  An image's result is bit-identical alone and inside a batch."""
+    from .resample import TAPS, device_tables
+    _require_cuda(src)
+    if mode not in TAPS:
+        raise ValueError(f"mode must be one of {tuple(TAPS)}, got {mode!r}")
+    Hd, Wd = int(size[0]), int(size[1])
+    if Hd < 1 or Wd < 1:
+        raise ValueError(f"size must be (height >= 1, width >= 1), got {tuple(size)}")
+    if src.dtype != torch.float32:
+        src = src.float()
+    x, unview = _image_layout(src, layout)
+    N, C, Hs, Ws = x.shape
+    if min(N, C, Hs, Ws) < 1:
+        raise ValueError(f"empty image {tuple(src.shape)}")
+    dev = x.device
+    ri, rw = device_tables(Hs, Hd, mode, dev)
+    ci, cw = device_tables(Ws, Wd, mode, dev)
+    out = torch.empty(N, C, Hd, Wd, dtype=torch.float32, device=dev)
+    st = (ctypes.c_int64 * 4)(*x.stride())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().reni_resample(N, C, Hs, Ws, Hd, Wd, x.data_ptr(), st, ri.data_ptr(), rw.data_ptr(), TAPS[mode],
+                                             ci.data_ptr(), cw.data_ptr(), TAPS[mode], out.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream))
+    return unview(out)
+
+
+def gaussian_blur(img: torch.Tensor, sigma: float, layout: str = "auto") -> torch.Tensor:
+    """reni_gaussian_blur: scipy.ndimage.gaussian_filter(channel, sigma) of every channel of one image ([H,W], [H,W,C] or
+    [C,H,W]; layout as in ``resample``): truncate 4, `reflect` boundary, rows first.  The result has the input's shape and
+    layout, float32."""
+    from .resample import gaussian_weights
+    _require_cuda(img)
+    if img.dim() not in (2, 3):
+        raise ValueError(f"expected one image [H,W], [H,W,C] or [C,H,W], got {tuple(img.shape)}")
+    w, r = gaussian_weights(sigma)
+    x = img if img.dtype == torch.float32 else img.float()
+    out = torch.empty_like(x)
+    if out.stride() != x.stride():
+        x = x.contiguous()
+        out = torch.empty_like(x)
+    v, _ = _image_layout(x, layout)
+    _, C, H, W = v.shape
+    if min(C, H, W) < 1:
+        raise ValueError(f"empty image {tuple(img.shape)}")
+    dev = x.device
+    lib = _lib.load()
+    wt = torch.from_numpy(w.astype("float32")).to(dev)
+    st = (ctypes.c_int64 * 3)(*v.stride()[1:])
+    ws, wp, wn = _ws256(int(lib.reni_blur_workspace_bytes(C, H, W)), dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.reni_gaussian_blur(C, H, W, x.data_ptr(), st, wt.data_ptr(), r, out.data_ptr(), wp, wn,
+                                          torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 def launch_count(reset: bool = False) -> int:
     """Kernel launches the library has issued so far in this process (reni_launch_count)."""
     return int(_lib.load().reni_launch_count(1 if reset else 0))

@@ -65,6 +65,14 @@ def gather_latents(model, optimizer=None, rank=None, world=None):
                         rdist.merge_owned_rows_(st[k], rank, world)
 
 
+def _load_batch(dataset, idx):
+    """[B, 3, H, W]: one device gather when the dataset is resident on the GPU (reni_amd.data.ResidentDataset.batch), else the
+    images loaded one by one on the host."""
+    if hasattr(dataset, "batch"):
+        return dataset.batch(idx)
+    return torch.stack([dataset[i][0] for i in idx])
+
+
 def fit(module, max_epochs=None, device=None, batches=None, rank=0, world=1):
     """Run ``module`` (a reni_amd.lightning_module.RENI) for ``max_epochs`` epochs.
 
@@ -92,14 +100,12 @@ def fit(module, max_epochs=None, device=None, batches=None, rank=0, world=1):
                     bad = [i for i in idx if i % world != rank]
                     assert not bad, f"rank {rank} of {world} was given images {bad} it does not own (i % world == rank)"
             for idx in batches:
-                imgs = torch.stack([module.dataset[i][0] for i in idx])
-                it.append((imgs, torch.tensor(idx)))
+                it.append((_load_batch(module.dataset, idx), torch.tensor(idx)))
         else:
             # the same number of steps on every rank (a short rank's trailing batches are short or empty)
             it = []
             for idx in rdist.epoch_batches(len(module.dataset), module.batch_size, rank, world):
-                imgs = torch.stack([module.dataset[i][0] for i in idx]) if idx else None
-                it.append((imgs, torch.tensor(idx, dtype=torch.long)))
+                it.append((_load_batch(module.dataset, idx) if idx else None, torch.tensor(idx, dtype=torch.long)))
         for bi, (imgs, idx) in enumerate(it):
             opt.zero_grad(set_to_none=True)
             if imgs is not None:

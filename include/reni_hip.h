@@ -503,6 +503,33 @@ size_t reni_blur_workspace_bytes(int64_t C, int64_t H, int64_t W);
 int reni_gaussian_blur(int64_t C, int64_t H, int64_t W, const float* src, const int64_t strides[3], const float* weights,
                        int32_t radius, float* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- rotation of equirectangular environment maps (reni_tu_rotate.hip; reni_amd/rotation.py, ResidentDataset's augmentation) --
+ * No reference counterpart (the reference rotates latents, never images).  out[b] is source image b turned by R_b:
+ *     out[b](d) = src[b](R_b^T d)        so that, for an equivariant model f,  f(Z R^T, D) = rotate(f(Z, D), R).
+ * Grid: H rows, W columns, W even; pixel (r, c) has phi = pi (r + 1/2) / H, theta = pi ((c + 1/2) / (W / 2) - 1) and direction
+ * d = (sin phi sin theta, cos phi, -sin phi cos theta) (utils.get_directions when W = 2 H).  For output pixel (r, c):
+ *     s = R^T d,  phi_s = atan2(sqrt(s.x^2 + s.z^2), s.y),  theta_s = atan2(s.x, -s.z),
+ *     row = phi_s / pi H - 1/2,  col = (theta_s / pi + 1) W / 2 - 1/2.
+ * Sampling is on the sphere: tap (i, j) with i < 0 is row -1 - i, column j + W / 2; with i >= H row 2 H - 1 - i, column j + W / 2
+ * (the row beyond a pole is the same row seen from the other side); then the column modulo W.  RENI_ROTATE_BILINEAR: the four
+ * taps floor(row), floor(row) + 1 x floor(col), floor(col) + 1 with the usual weights; RENI_ROTATE_NEAREST: the tap at
+ * floor(row + 1/2), floor(col + 1/2) (masks).  fp32, one launch on `stream`, no atomics, no workspace, no host synchronisation:
+ * two calls give identical bits, and an image's result is the same alone, inside a batch and through src_index.
+ *   src, src_strides: as reni_resample (planar, channel-last, or a model output [B][P][3] = {3 H W, 1, 3 W, 3} read in place)
+ *   src_index: NULL (image b is source b) or a device array [B]: image b is source src_index[b] of n_src, clamped to
+ *              [0, n_src) on the device -- the gather of a batch out of a level tensor, in the same launch
+ *   rot, rot_stride: device array [B][9], row-major R per image (stride 9), or one shared R (stride 0).  Not checked for
+ *              orthogonality here (reni_amd/rotation.py does); s is used as it comes, atan2 needs no unit length
+ *   row_trig [H][2] = (sin phi, cos phi), col_trig [W][2] = (sin theta, cos theta) of the grid above: device arrays the host
+ *              builds in float64 and rounds to fp32 once.  sqrt and the two atan2f of a pixel run on the device: with a fresh
+ *              rotation per image and step, host tables of the SOURCE coordinates would be the bottleneck.
+ *   out: planar [B][C][H][W].  B, C <= 65535, H W < 2^30, src_strides[2] and [3] < 2^31. */
+#define RENI_ROTATE_NEAREST 0
+#define RENI_ROTATE_BILINEAR 1
+int reni_rotate_envmap(int64_t B, int64_t C, int64_t H, int64_t W, const float* src, const int64_t src_strides[4],
+                       const int64_t* src_index, int64_t n_src, const float* rot, int64_t rot_stride, const float* row_trig,
+                       const float* col_trig, int32_t mode, float* out, void* stream);
+
 /* ---- the data-parallel exchange step over RCCL -------------------------------
  * Replaces, for the flat decoder gradient, what Lightning's DDP wrapper does in the reference (run.py:97-110:
  * strategy="ddp" -> NCCL all-reduce of every parameter's gradient, mean over ranks): ONE in-place ncclAllReduce(sum) of

@@ -20,6 +20,7 @@ DTYPE = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 LOSS_MSE, LOSS_TEST = 0, 1
 NEED_DW, NEED_DZ, WEIGHT_SPARSE, WEIGHT_COMPACT, WEIGHT_COS_CONSTANT = 1, 2, 4, 8, 16
 COND_CONCAT, COND_FILM = 0, 1
+ROTATE_MODE = {"nearest": 0, "bilinear": 1}
 
 # every symbol include/reni_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -35,7 +36,7 @@ EXPORTS = (
     "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
     "reni_image_workspace_bytes", "reni_unnormalise_srgb", "reni_minmax_normalise",
     "reni_minmax_batch_workspace_bytes", "reni_minmax_normalise_batch",
-    "reni_resample", "reni_blur_workspace_bytes", "reni_gaussian_blur",
+    "reni_resample", "reni_blur_workspace_bytes", "reni_gaussian_blur", "reni_rotate_envmap",
     "reni_rccl_unique_id", "reni_rccl_comm_create", "reni_rccl_comm_destroy", "reni_allreduce_grads",
 )
 
@@ -222,6 +223,9 @@ def load():
     lib.reni_gaussian_blur.argtypes = [c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p, c_int32, c_void_p,
                                        c_void_p, c_size_t, c_void_p]
     lib.reni_gaussian_blur.restype = c_int32
+    lib.reni_rotate_envmap.argtypes = [c_int64, c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p, c_int64, c_void_p,
+                                       c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
+    lib.reni_rotate_envmap.restype = c_int32
     lib.reni_rccl_unique_id.argtypes = [c_void_p]
     lib.reni_rccl_unique_id.restype = c_int32
     lib.reni_rccl_comm_create.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]

@@ -133,11 +133,24 @@ class ResidentDataset(Dataset):
     missing files of one ``batch`` are decoded by up to ``workers`` (<= 16) threads.
 
     ``dataset[i] -> (img [3, H, W] on the device, i)``; ``batch(idx) -> [B, 3, H, W]``: one index_select, no host work for
-    cached images.  ``double_resolution()`` moves to the next level and rebuilds from the files only beyond ``levels``."""
+    cached images.  ``double_resolution()`` moves to the next level and rebuilds from the files only beyond ``levels``.
+
+    Rotation augmentation (not in the reference; conventions in reni_amd/rotation.py).  ``batch(idx, rotations=R)`` with R
+    [B, 3, 3] on the device returns the images turned by R: ONE reni_rotate_envmap launch that gathers from the level tensor
+    and rotates (no index_select in front of it).  ``rotate="SO2"`` (yaw) or ``"SO3"`` makes every ``batch`` call without
+    explicit rotations take a fresh one per image from the dataset's own device generator, seeded with ``rotate_seed`` and
+    the data-parallel rank (``rotate_rank``, default: the process's torch.distributed rank) so that ranks draw different
+    streams.  The matrices are drawn ``ROTATION_POOL`` at a time and handed out in order (a draw is some thirty small
+    launches, a step one slice), so the sequence depends on the seed, the rank and the batch sizes asked for, nothing else.
+    The rotation interpolates the STORED level bilinearly, i.e. normalised log radiance for an HDR dataset: that is the
+    tensor the loss sees, and a sun does not bleed across four pixels as it would in linear radiance.  ``dataset[i]`` is
+    never rotated (FIT_LATENT, FIT_INVERSE and the ground-truth renders use it), and with ``rotate=None`` and no
+    ``rotations`` ``batch`` is the plain gather."""
 
     MAX_WORKERS = 16
+    ROTATION_POOL = 4096
 
-    def __init__(self, dataset, levels=0, device=None, workers=8):
+    def __init__(self, dataset, levels=0, device=None, workers=8, rotate=None, rotate_seed=0, rotate_rank=None):
         super().__init__()
         if not torch.cuda.is_available():
             raise _lib.RENILibraryError("ResidentDataset keeps the images on a GPU device and none is available; "
@@ -164,6 +177,16 @@ class ResidentDataset(Dataset):
         self._resize = ts[0]
         self._post = [t for t in ts[1:] if not isinstance(t, ToTensor)]
         self._hdr = isinstance(dataset, RENIDatasetHDR)
+        if rotate not in (None, "SO2", "SO3"):
+            raise ValueError(f"rotate must be None, 'SO2' or 'SO3', got {rotate!r}")
+        self.rotate = rotate
+        if rotate is not None:
+            if rotate_rank is None:
+                import torch.distributed as dist
+                rotate_rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+            self._rotate_gen = torch.Generator(device=device)
+            self._rotate_gen.manual_seed((int(rotate_seed) * 1000003 + int(rotate_rank)) % (1 << 63))
+            self._rotate_pool, self._rotate_next = None, 0
         self._allocate([(self._resize.size[0] << j, self._resize.size[1] << j) for j in range(int(levels) + 1)])
 
     def _allocate(self, sizes):
@@ -250,12 +273,27 @@ class ResidentDataset(Dataset):
             self.fill([i])
         return self._store[self.level][i].clone(), i  # a copy: UnNormalise works in place on what it is given
 
-    def batch(self, idx):
-        """[B, 3, H, W] of the images ``idx`` (a list or an integer tensor) at the current level."""
+    def batch(self, idx, rotations=None):
+        """[B, 3, H, W] of the images ``idx`` (a list or an integer tensor) at the current level; turned by ``rotations``
+        [B, 3, 3] when given, else by a fresh draw per image when the dataset was built with ``rotate``."""
         if self._missing:
             self.fill(idx.tolist() if isinstance(idx, torch.Tensor) else idx)
         sel = torch.as_tensor(idx, dtype=torch.long).to(self.device)
-        return self._store[self.level].index_select(0, sel)
+        if rotations is None and self.rotate is None:
+            return self._store[self.level].index_select(0, sel)
+        from . import ops
+        if rotations is None:
+            rotations = self._next_rotations(sel.numel())
+        return ops.rotate_envmap(self._store[self.level], rotations.to(self.device), "bilinear", "chw", index=sel)
+
+    def _next_rotations(self, n):
+        """the next n matrices [n, 3, 3] of the dataset's stream (what is left of a pool that is too short is dropped)"""
+        if self._rotate_pool is None or self._rotate_next + n > self._rotate_pool.shape[0]:
+            from .rotation import random_rotations
+            self._rotate_pool = random_rotations(max(n, self.ROTATION_POOL), self.rotate, self._rotate_gen)
+            self._rotate_next = 0
+        self._rotate_next += n
+        return self._rotate_pool[self._rotate_next - n:self._rotate_next]
 
     def double_resolution(self):
         """Multi-resolution curriculum hook (src/lightning/callbacks.py:27): the next level; beyond the last one the cache is

@@ -253,6 +253,11 @@ class RENI(_Base):
         else:
             ds = self.config.DATASET
             name = getattr(ds, "NAME", None)
+            # (not in the reference) DATASET.ROTATE_AUGMENT = "SO2" | "SO3": a fresh rotation per image and step, on the device
+            augment = (getattr(ds, "ROTATE_AUGMENT", None) or None) if self.task == "FIT_DECODER" else None
+            if augment is not None and (name == "SYNTHETIC" or not getattr(ds, "RESIDENT", False)):
+                raise ValueError("DATASET.ROTATE_AUGMENT rotates the resident dataset on the GPU: it needs a dataset on disk and "
+                                 "DATASET.RESIDENT = True")
             if name == "SYNTHETIC":  # (not in the reference: the stand-in for boxes without the dataset)
                 n = ds.SYNTHETIC.N_TRAIN if self.task == "FIT_DECODER" else ds.SYNTHETIC.N_TEST
                 self.dataset = SyntheticEnvMapDataset(n, img_size[0], img_size[1])
@@ -264,7 +269,8 @@ class RENI(_Base):
                 self.dataset = get_dataset(name, dcfg.PATH + os.sep + split, transforms, self.is_hdr)
                 if getattr(ds, "RESIDENT", False):  # (not in the reference) decode every file once, keep all levels on the GPU
                     from .data import ResidentDataset
-                    self.dataset = ResidentDataset(self.dataset, levels=len(tcfg.CURRICULUM) if tcfg.MULTI_RES_TRAINING else 0)
+                    self.dataset = ResidentDataset(self.dataset, levels=len(tcfg.CURRICULUM) if tcfg.MULTI_RES_TRAINING else 0,
+                                                   rotate=augment, rotate_seed=getattr(ds, "ROTATE_SEED", 0))
         self.batch_size = tcfg.BATCH_SIZE
         self.dataloader = torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size)
 

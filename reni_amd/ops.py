@@ -983,6 +983,67 @@ def gaussian_blur(img: torch.Tensor, sigma: float, layout: str = "auto") -> torc
     return out
 
 
+_ROTATE_TRIG = {}
+
+
+def _rotate_trig(H: int, W: int, device):
+    """(row_trig [H, 2], col_trig [W, 2]) fp32 on ``device``: (sin, cos) of the grid's polar and azimuth angles (rotation.py)."""
+    key = (H, W, device)
+    t = _ROTATE_TRIG.get(key)
+    if t is None:
+        from .rotation import grid_trig
+        t = tuple(torch.from_numpy(x.astype("float32")).to(device) for x in grid_trig(H, W))
+        if len(_ROTATE_TRIG) >= 64:
+            _ROTATE_TRIG.clear()
+        _ROTATE_TRIG[key] = t
+    return t
+
+
+def rotate_envmap(src: torch.Tensor, rot: torch.Tensor, mode: str = "bilinear", layout: str = "auto", index=None) -> torch.Tensor:
+    """reni_rotate_envmap: the equirectangular maps ``src`` turned by ``rot``, out(d) = src(R^T d), sampled on the sphere
+    (wrap in longitude, pole crossings) with mode "bilinear" | "nearest" (conventions: reni_amd/rotation.py).  src is read in
+    place through its strides, in the shapes ``resample`` accepts (a model output [B, P, 3]: ``out.view(B, H, W, 3)`` with
+    layout="hwc"); the width must be even.  rot: [3, 3] shared, or [B, 3, 3] per image; it is NOT checked for orthogonality
+    here (rotation.rotate_envmap does, at the price of a host synchronisation).  index: optional integer tensor [B]: image b
+    of the result is src[index[b]] turned by rot[b] -- the gather and the rotation in one launch (src must be a batch).
+    The result is planar float32 [B, C, H, W] ([C, H, W] / [H, W] for one image)."""
+    _require_cuda(src, rot, index if isinstance(index, torch.Tensor) else None)
+    if mode not in _lib.ROTATE_MODE:
+        raise ValueError(f"mode must be one of {tuple(_lib.ROTATE_MODE)}, got {mode!r}")
+    if src.dtype != torch.float32:
+        src = src.float()
+    x, unview = _image_layout(src, layout)
+    N, C, H, W = x.shape
+    if min(N, C, H, W) < 1 or W % 2:
+        raise ValueError(f"expected non-empty maps of even width, got {tuple(src.shape)}")
+    dev = x.device
+    if index is not None:
+        if src.dim() != 4:
+            raise ValueError(f"index= gathers from a batch of maps, got {tuple(src.shape)}")
+        index = torch.as_tensor(index, dtype=torch.long).to(dev).contiguous()
+        if index.dim() != 1 or index.numel() < 1:
+            raise ValueError(f"index must be a non-empty 1-d integer tensor, got {tuple(index.shape)}")
+    B = N if index is None else index.numel()
+    rot = _f32c(rot)
+    if rot.device != dev:
+        raise ValueError(f"rot is on {rot.device}, the maps on {dev}")
+    if tuple(rot.shape) == (3, 3):
+        rot_stride = 0
+    elif tuple(rot.shape) == (B, 3, 3):
+        rot_stride = 9
+    else:
+        raise ValueError(f"rot must be [3, 3] or [{B}, 3, 3], got {tuple(rot.shape)}")
+    rt, ct = _rotate_trig(H, W, dev)
+    out = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
+    st = (ctypes.c_int64 * 4)(*x.stride())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().reni_rotate_envmap(B, C, H, W, x.data_ptr(), st, None if index is None else index.data_ptr(), N,
+                                                  rot.data_ptr(), rot_stride, rt.data_ptr(), ct.data_ptr(),
+                                                  _lib.ROTATE_MODE[mode], out.data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream))
+    return unview(out)
+
+
 def launch_count(reset: bool = False) -> int:
     """Kernel launches the library has issued so far in this process (reni_launch_count)."""
     return int(_lib.load().reni_launch_count(1 if reset else 0))

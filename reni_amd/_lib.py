@@ -18,6 +18,7 @@ EQ = {"None": 0, None: 0, "SO2": 1, "SO3": 2}
 ACT = {None: 0, "None": 0, "none": 0, "tanh": 1, "exp": 2}
 DTYPE = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
 LOSS_MSE, LOSS_TEST = 0, 1
+LOSS_KIND = {"mse": LOSS_MSE, "test": LOSS_TEST}
 NEED_DW, NEED_DZ, WEIGHT_SPARSE, WEIGHT_COMPACT, WEIGHT_COS_CONSTANT = 1, 2, 4, 8, 16
 COND_CONCAT, COND_FILM = 0, 1
 ROTATE_MODE = {"nearest": 0, "bilinear": 1}
@@ -70,6 +71,7 @@ def load():
         )
     lib = ctypes.CDLL(LIB_PATH)
     i64x3 = POINTER(c_int64)
+    lib.reni_last_error.argtypes = []
     lib.reni_last_error.restype = c_char_p
     lib.reni_plan_create.argtypes = [POINTER(reni_desc), POINTER(c_void_p)]
     lib.reni_plan_create.restype = c_int32
@@ -84,34 +86,23 @@ def load():
     lib.reni_forward.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                  c_void_p, c_size_t, c_void_p]
     lib.reni_forward.restype = c_int32
-    lib.reni_forward_loss_backward.argtypes = [
-        c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, i64x3, c_void_p, i64x3,
-        c_int32, c_float, c_float, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.reni_forward_loss_backward.restype = c_int32
-    lib.reni_forward_loss_backward_rows.argtypes = [
-        c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, i64x3, c_void_p, i64x3,
-        c_int32, c_float, c_float, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.reni_forward_loss_backward_rows.restype = c_int32
-    lib.reni_train_step_rows.argtypes = [
-        c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, i64x3, c_void_p, i64x3,
-        c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int64, c_float,
-        POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.reni_train_step_rows.restype = c_int32
-    lib.reni_train_step_rows_dp.argtypes = [
-        c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, i64x3, c_void_p, i64x3,
-        c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int64, c_float,
-        c_void_p, c_int32, POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.reni_train_step_rows_dp.restype = c_int32
-    lib.reni_latent_step_rows.argtypes = [
-        c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, i64x3, c_void_p, i64x3,
-        c_int32, c_float, c_float, c_uint32, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int64,
-        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.reni_latent_step_rows.restype = c_int32
-    lib.reni_latent_step_rows_cached.argtypes = [
-        c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, i64x3, c_void_p, i64x3,
-        c_int32, c_float, c_float, c_uint32, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int64,
-        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.reni_latent_step_rows_cached.restype = c_int32
+    # the twins' shared runs of parameters, in the header's order (tests/test_api_cpu.py holds every list against its prototype)
+    rows = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]  # plan, B, P, Z_table, n_rows, idx
+    loss = [c_void_p, c_int64, c_void_p, c_void_p, i64x3, c_void_p, i64x3, c_int32, c_float, c_float]  # D, dbs, params, target .. beta
+    grads = [c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]  # flags, out, loss_terms, dZ, dparams, ws ..
+    lib.reni_forward_loss_backward.argtypes = rows[:4] + loss + grads
+    lib.reni_forward_loss_backward_rows.argtypes = rows + loss + grads
+    adam = [c_float, c_float, c_float, c_float, c_int64]  # lr, b1, b2, eps, step
+    step_head = rows + [c_void_p] + loss + [c_void_p, c_void_p, c_void_p, c_void_p] + adam + [c_float]  # idx_next; m / v x 2; grad_scale
+    step_tail = [POINTER(c_uint32), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]  # stage_state, loss_terms, dZ, dparams, ws ..
+    lib.reni_train_step_rows.argtypes = step_head + step_tail
+    lib.reni_train_step_rows_dp.argtypes = step_head + [c_void_p, c_int32] + step_tail  # comm, overlap
+    latent_tail = [c_void_p, c_void_p] + adam + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]  # m, v; loss_terms, dZ, ws ..
+    lib.reni_latent_step_rows.argtypes = rows + loss + [c_uint32] + latent_tail
+    lib.reni_latent_step_rows_cached.argtypes = rows + loss + [c_uint32, c_void_p] + latent_tail  # flags, weight_lists
+    for fn in (lib.reni_forward_loss_backward, lib.reni_forward_loss_backward_rows, lib.reni_train_step_rows,
+               lib.reni_train_step_rows_dp, lib.reni_latent_step_rows, lib.reni_latent_step_rows_cached):
+        fn.restype = c_int32
     lib.reni_weight_lists_bytes.argtypes = [c_int64, c_int64]
     lib.reni_weight_lists_bytes.restype = c_size_t
     lib.reni_weight_lists_build.argtypes = [c_int64, c_int64, c_void_p, i64x3, c_uint32, c_void_p, c_size_t, POINTER(c_int32), c_void_p]
@@ -169,6 +160,8 @@ def load():
     lib.reni_profile_read_kind.restype = c_int32
     lib.reni_profile_minmax.argtypes = [c_int32, POINTER(ctypes.c_double), POINTER(ctypes.c_double)]
     lib.reni_profile_minmax.restype = c_int32
+    lib.reni_probe_tr.argtypes = [c_void_p, c_int32, c_void_p]
+    lib.reni_probe_tr.restype = c_int32
     lib.reni_envmap_shade_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
     lib.reni_envmap_shade_workspace_bytes.restype = c_size_t
     for fn in (lib.reni_envmap_shade, lib.reni_envmap_shade_backward):

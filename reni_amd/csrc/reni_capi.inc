@@ -623,14 +623,14 @@ int check_common(const reni_plan* p, int64_t B, int64_t P, const void* Z, const 
 
 // FiLM entry points: the caller owns the per-image glue (layer-0 affine map, mapping network)
 struct FilmIO {
-  const float* A;     // [B][H][8]
-  const float* film;  // [B][L][2][H]
-  float* dA;          // [B][H][8]
-  float* dfilm;       // [B][L][2][H]
-  const float* Zp;    // reni_film_model_*: latents for the prior term of RENITestLoss (else NULL)
-  float alpha;
-  int64_t nz;
-  int keep_first;     // reni_film_model_*: the caller fills the first layer's gradient slot itself
+  const float* A = nullptr;     // [B][H][8]
+  const float* film = nullptr;  // [B][L][2][H]
+  float* dA = nullptr;          // [B][H][8]
+  float* dfilm = nullptr;       // [B][L][2][H]
+  const float* Zp = nullptr;    // reni_film_model_*: latents for the prior term of RENITestLoss (else NULL)
+  float alpha = 0.f;
+  int64_t nz = 0;
+  int keep_first = 0;           // reni_film_model_*: the caller fills the first layer's gradient slot itself
 };
 
 int check_film(const reni_plan* p, const FilmIO* f, bool backward) {
@@ -668,6 +668,31 @@ ListLayout make_list_layout(int64_t B, int64_t P) {
   return l;
 }
 constexpr long long LIST_MAGIC = 0x52454e494c495354ll;  // "RENILIST"
+// where the lists live: in the call's workspace (Layout) or in the caller's buffer (ListLayout) -- the same member names in both
+struct ListDst { int *tflag, *imgcos, *tlist, *tcount, *pcnt, *pscan, *nlive, *plist; };
+template <class L>
+ListDst list_dst(char* base, const L& l) {
+  return {(int*)(base + l.o_tflag), (int*)(base + l.o_imgcos), (int*)(base + l.o_tlist), (int*)(base + l.o_tcount),
+          (int*)(base + l.o_pcnt), (int*)(base + l.o_pscan), (int*)(base + l.o_nlive), (int*)(base + l.o_plist)};
+}
+// ... and the ONE place that builds them (run_backward per call, reni_weight_lists_build once per mask: the cached latent step is
+// bit-equal to the rebuilding one because both issue these launches): tile flags -> the two tile lists and their counts
+// (-> RENI_WEIGHT_COMPACT: position -> pixel)
+int build_weight_lists(const float* weight, const int64_t* wst, int64_t P, int tpi, int n_tiles, bool compact, const ListDst& d,
+                       hipStream_t s) {
+  RENI_LAUNCH(reni::k_tile_flags, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, weight, (long long)wst[0], (long long)wst[1],
+              (long long)wst[2], (int)P, tpi, n_tiles, d.tflag, d.imgcos, compact ? d.pcnt : (int*)nullptr);
+  HIP_TRY(hipGetLastError());
+  RENI_LAUNCH(reni::k_tile_compact, dim3(1), dim3(1024), 0, s, d.tflag, (const int*)d.imgcos, tpi, n_tiles, d.tlist, d.tlist + n_tiles,
+              d.tcount, compact ? (const int*)d.pcnt : (const int*)nullptr, (int)P, d.pscan, d.nlive);
+  HIP_TRY(hipGetLastError());
+  if (compact) {
+    RENI_LAUNCH(reni::k_pix_scatter, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, weight, (long long)wst[0], (long long)wst[1],
+                (long long)wst[2], (int)P, tpi, n_tiles, (const int*)d.imgcos, (const int*)d.pscan, d.plist);
+    HIP_TRY(hipGetLastError());
+  }
+  return RENI_OK;
+}
 struct WeightLists { const char* buf; uint32_t flags; };   // handed to run_backward by reni_latent_step_rows_cached
 // What reni_weight_lists_build built where, on the HOST (ADVICE r05: the header in the buffer is device memory, a cached step cannot read
 // it without a synchronisation; lists built for another B, P or mode would be read out of bounds).  The last 64 builds, newest first.
@@ -699,119 +724,125 @@ struct StepFuse {
   uint32_t* state;                              // in / out: bit 0 = this call's prologue is staged, bit 1 = in which copy
 };
 
+// One backward call: what run_backward, run_backward_chunked and film_model_backward take.  Every member's initialiser is its
+// "absent" value, so an entry point names only what it has.
+constexpr int LOSS_DOUT = 2;  // internal loss_kind beside RENI_LOSS_MSE / RENI_LOSS_TEST: no loss, the caller passed d loss / d out (`dout`)
+struct BwdCall {
+  int64_t B = 0, P = 0;
+  const float *Z = nullptr, *D = nullptr, *params = nullptr;  // (Z: the latent TABLE when idx is set)
+  int64_t dbs = 0;
+  const float *target = nullptr, *weight = nullptr, *dout = nullptr;
+  const int64_t *ts = nullptr, *wst = nullptr;
+  int loss_kind = RENI_LOSS_MSE;
+  float alpha = 0.f, beta = 0.f;
+  uint32_t flags = 0;
+  float *out = nullptr, *loss_terms = nullptr, *dZ = nullptr, *dparams = nullptr;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  void* stream = nullptr;
+  const FilmIO* fio = nullptr;   // FiLM conditioning
+  const int64_t* idx = nullptr;  // the batch's rows of the table Z [n_rows][nd][3]
+  int64_t n_rows = 0;
+  const StepFuse* fuse = nullptr;
+  const WeightLists* lists = nullptr;
+};
+
 // everything after the prologue for the backward entry points (fio != NULL: FiLM conditioning)
-int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const float* D, int64_t dbs,
-                 const float* params, const float* target, const int64_t* ts, const float* weight,
-                 const int64_t* wst, const float* dout, int loss_kind, float alpha, float beta,
-                 uint32_t flags, float* out, float* loss_terms, float* dZ, float* dparams, void* ws_v,
-                 size_t ws_bytes, void* stream, const FilmIO* fio = nullptr, const int64_t* idx = nullptr, int64_t n_rows = 0,
-                 const StepFuse* fuse = nullptr, const WeightLists* lists = nullptr) {
-  int rc = fio ? check_film(p, fio, true) : RENI_OK;
+int run_backward(const reni_plan* p, const BwdCall& c) {
+  const float* Z = c.Z;
+  int rc = c.fio ? check_film(p, c.fio, true) : RENI_OK;
   if (rc) return rc;
-  if (!fio && p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use the reni_film_* entry points");
-  rc = check_common(p, B, P, fio ? fio->A : Z, D, params, ws_v);
+  if (!c.fio && p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use the reni_film_* entry points");
+  rc = check_common(p, c.B, c.P, c.fio ? c.fio->A : Z, c.D, c.params, c.ws);
   if (rc) return rc;
-  if ((flags & RENI_NEED_DW) && !dparams) return fail(RENI_EINVAL, "RENI_NEED_DW set but dparams is NULL");
-  if (!fio && (flags & RENI_NEED_DZ) && !dZ) return fail(RENI_EINVAL, "RENI_NEED_DZ set but dZ is NULL");
-  if (loss_kind == 2) {
-    if (!dout) return fail(RENI_EINVAL, "dout is NULL");
+  if ((c.flags & RENI_NEED_DW) && !c.dparams) return fail(RENI_EINVAL, "RENI_NEED_DW set but dparams is NULL");
+  if (!c.fio && (c.flags & RENI_NEED_DZ) && !c.dZ) return fail(RENI_EINVAL, "RENI_NEED_DZ set but dZ is NULL");
+  if (c.loss_kind == LOSS_DOUT) {
+    if (!c.dout) return fail(RENI_EINVAL, "dout is NULL");
   } else {
-    if (loss_kind != RENI_LOSS_MSE && loss_kind != RENI_LOSS_TEST) return fail(RENI_EINVAL, "unknown loss_kind %d", loss_kind);
-    if (!target || !weight || !ts || !wst) return fail(RENI_EINVAL, "target/weight (and their strides) must be non-NULL");
-    if (!loss_terms) return fail(RENI_EINVAL, "loss_terms is NULL");
+    if (c.loss_kind != RENI_LOSS_MSE && c.loss_kind != RENI_LOSS_TEST) return fail(RENI_EINVAL, "unknown loss_kind %d", c.loss_kind);
+    if (!c.target || !c.weight || !c.ts || !c.wst) return fail(RENI_EINVAL, "target/weight (and their strides) must be non-NULL");
+    if (!c.loss_terms) return fail(RENI_EINVAL, "loss_terms is NULL");
   }
   GeoRt g;
   if (!geo_for(p, &g)) return fail(RENI_EUNSUPPORTED, "hidden_features=%d unsupported", p->d.hidden_features);
   DeviceGuard dev_guard;
-  rc = dev_guard.enter(params);
+  rc = dev_guard.enter(c.params);
   if (rc) return rc;
-  const bool staged = fuse && (*fuse->state & 1u);          // this call's prologue was run by the previous call
-  const int stage = staged ? (int)((*fuse->state >> 1) & 1u) : 0;
-  const Layout l = make_layout(p, g, B, P, flags, true, true, stage);
-  if (ws_bytes < l.total) return fail(RENI_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", l.total, ws_bytes);
-  char* ws = (char*)ws_v;
-  hipStream_t s = (hipStream_t)stream;
+  const bool staged = c.fuse && (*c.fuse->state & 1u);          // this call's prologue was run by the previous call
+  const int stage = staged ? (int)((*c.fuse->state >> 1) & 1u) : 0;
+  const Layout l = make_layout(p, g, c.B, c.P, c.flags, true, true, stage);
+  if (c.ws_bytes < l.total) return fail(RENI_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", l.total, c.ws_bytes);
+  char* ws = (char*)c.ws;
+  hipStream_t s = (hipStream_t)c.stream;
   const int H = p->d.hidden_features;
-  if (fuse) *fuse->state = 0;  // (whatever happens below: nothing is staged until this call has staged it)
+  if (c.fuse) *c.fuse->state = 0;  // (whatever happens below: nothing is staged until this call has staged it)
   // the constants the weight-gradient partials carry when the W^T images are 8 x the forward images (Layout::consistent_bwd; derivation:
   // DESIGN.md section 4.2f): hidden layer l: (omega_hidden / omega_first) (8 / 2 pi)^l, head: 1 / gy_scale.  Ones otherwise.
   reni::LayerScale lsc;
   lsc.n_hid = H * H + H; lsc.L = p->d.hidden_layers;
   for (int i = 0; i <= reni::MAX_LAYERS; ++i) lsc.c[i] = 1.f;
-  if (l.consistent_bwd && (flags & RENI_NEED_DW)) {
-    double gy = (double)p->d.first_omega_0 / 8.0, c = (double)p->d.hidden_omega_0 / (double)p->d.first_omega_0;
+  if (l.consistent_bwd && (c.flags & RENI_NEED_DW)) {
+    double gy = (double)p->d.first_omega_0 / 8.0, cl = (double)p->d.hidden_omega_0 / (double)p->d.first_omega_0;
     for (int i = 0; i < p->d.hidden_layers; ++i) {
       gy *= 6.283185307179586 / 8.0;
-      c *= 8.0 / 6.283185307179586;
-      lsc.c[i] = (float)c;
+      cl *= 8.0 / 6.283185307179586;
+      lsc.c[i] = (float)cl;
     }
     lsc.c[p->d.hidden_layers] = (float)(1.0 / gy);
   }
 
   if (!staged) {
-    rc = run_prologue(p, g, l, B, Z, params, ws, true, s, idx, fio ? fio->A : nullptr, n_rows);
+    rc = run_prologue(p, g, l, c.B, Z, c.params, ws, true, s, c.idx, c.fio ? c.fio->A : nullptr, c.n_rows);
     if (rc) return rc;
   }
-  if (idx) Z = (const float*)(ws + l.o_Zc);  // from here on: the batch's rows, gathered by k_prep_image
+  if (c.idx) Z = (const float*)(ws + l.o_Zc);  // from here on: the batch's rows, gathered by k_prep_image
 
   reni::MainArgs a;
-  fill_main_args(a, p, l, B, P, Z, D, dbs, ws);
-  if (fio) { a.Apre = fio->A; a.film = fio->film; a.params = params; a.Z = nullptr; }
-  a.need_dw = (flags & RENI_NEED_DW) ? 1 : 0;
+  fill_main_args(a, p, l, c.B, c.P, Z, c.D, c.dbs, ws);
+  if (c.fio) { a.Apre = c.fio->A; a.film = c.fio->film; a.params = c.params; a.Z = nullptr; }
+  a.need_dw = (c.flags & RENI_NEED_DW) ? 1 : 0;
 #ifdef RENI_DEBUG  // diagnostic builds only (build.sh -DRENI_DEBUG): the ablation mask skips work, i.e. yields WRONG results
-  if (const char* e = getenv("RENI_DEBUG_MASK")) a.dbg = fio ? 0 : atoi(e);
+  if (const char* e = getenv("RENI_DEBUG_MASK")) a.dbg = c.fio ? 0 : atoi(e);
 #endif
 #if defined(RENI_TRACE) || defined(RENI_TRACE_DW1)  // cycle-trace builds only (profiles/tools/gpu_trace.py, gpu_trace_dw1.py)
   if (const char* e = getenv("RENI_TRACE_PTR")) a.trace = (long long*)strtoull(e, nullptr, 0);
 #endif
-  a.out = out; a.dout = dout; a.beta = beta;
-  if (loss_kind != 2) {
-    a.target = target; a.ts0 = ts[0]; a.ts1 = ts[1]; a.ts2 = ts[2];
-    a.weight = weight; a.ws0 = wst[0]; a.ws1 = wst[1]; a.ws2 = wst[2];
+  a.out = c.out; a.dout = c.dout; a.beta = c.beta;
+  if (c.loss_kind != LOSS_DOUT) {
+    a.target = c.target; a.ts0 = c.ts[0]; a.ts1 = c.ts[1]; a.ts2 = c.ts[2];
+    a.weight = c.weight; a.ws0 = c.wst[0]; a.ws1 = c.wst[1]; a.ws2 = c.wst[2];
   }
   float* img_loss = (float*)(ws + l.o_img_loss);
   float* stats = (float*)(ws + l.o_stats);
-  float* dA = fio ? fio->dA : (float*)(ws + l.o_dA);
+  float* dA = c.fio ? c.fio->dA : (float*)(ws + l.o_dA);
   float* part2 = (float*)(ws + l.o_part2);
-  const bool use_cos = (loss_kind == RENI_LOSS_TEST) && (beta != 0.f);
+  const bool use_cos = (c.loss_kind == RENI_LOSS_TEST) && (c.beta != 0.f);
   // RENI_WEIGHT_SPARSE with a frozen concat decoder: the tiles that can change the result, listed on the device from the
   // weight (k_tile_flags, k_tile_compact: two small launches); the statistics pass visits the images whose cosine term is not a
   // constant, the main pass the tiles with a non-zero weight and those images.  Same results (skipped records would be exact zeros).
   // (not when the output image is wanted: the tiles left out would leave holes in it)
-  const bool sparse = (flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT)) && !fio && !(flags & RENI_NEED_DW) && loss_kind != 2 &&
-                      weight != nullptr && out == nullptr;  // (every concat kernel with a frozen decoder: persistent and generic, fp32 and bf16)
-  const bool compact = sparse && (flags & RENI_WEIGHT_COMPACT);  // + the pixels with weight packed into each image's first tiles
-  int* tflag = sparse ? (int*)(ws + l.o_tflag) : nullptr;
-  int* imgcos = sparse ? (int*)(ws + l.o_imgcos) : nullptr;
-  if (sparse && lists) {
-    // the caller's lists (reni_weight_lists_build for this B, P and these flags): no launch, no read of the weight
-    const ListLayout ll = make_list_layout(B, P);
-    char* lb = const_cast<char*>(lists->buf);
-    tflag = (int*)(lb + ll.o_tflag); imgcos = (int*)(lb + ll.o_imgcos);
-    a.tlist = (const int*)(lb + ll.o_tlist); a.tcount = (const int*)(lb + ll.o_tcount);
-    if (compact) { a.plist = (const int*)(lb + ll.o_plist); a.nlive = (const int*)(lb + ll.o_nlive); }
-  } else if (sparse) {
-    int* const tl = (int*)(ws + l.o_tlist);
-    int* const tc = (int*)(ws + l.o_tcount);
-    RENI_LAUNCH(reni::k_tile_flags, dim3((unsigned)((l.n_tiles + 3) / 4)), dim3(256), 0, s, weight, (long long)wst[0], (long long)wst[1],
-                (long long)wst[2], (int)P, l.tpi, l.n_tiles, tflag, imgcos, compact ? (int*)(ws + l.o_pcnt) : (int*)nullptr);
-    HIP_TRY(hipGetLastError());
-    RENI_LAUNCH(reni::k_tile_compact, dim3(1), dim3(1024), 0, s, tflag, (const int*)imgcos, l.tpi, l.n_tiles, tl, tl + l.n_tiles, tc,
-                compact ? (const int*)(ws + l.o_pcnt) : (const int*)nullptr, (int)P, (int*)(ws + l.o_pscan), (int*)(ws + l.o_nlive));
-    HIP_TRY(hipGetLastError());
-    a.tlist = tl; a.tcount = tc;
-    if (compact) {
-      RENI_LAUNCH(reni::k_pix_scatter, dim3((unsigned)((l.n_tiles + 3) / 4)), dim3(256), 0, s, weight, (long long)wst[0], (long long)wst[1],
-                  (long long)wst[2], (int)P, l.tpi, l.n_tiles, (const int*)imgcos, (const int*)(ws + l.o_pscan), (int*)(ws + l.o_plist));
-      HIP_TRY(hipGetLastError());
-      a.plist = (const int*)(ws + l.o_plist); a.nlive = (const int*)(ws + l.o_nlive);
+  const bool sparse = (c.flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT)) && !c.fio && !(c.flags & RENI_NEED_DW) && c.loss_kind != LOSS_DOUT &&
+                      c.weight != nullptr && c.out == nullptr;  // (every concat kernel with a frozen decoder: persistent and generic, fp32 and bf16)
+  const bool compact = sparse && (c.flags & RENI_WEIGHT_COMPACT);  // + the pixels with weight packed into each image's first tiles
+  ListDst ld{};
+  if (sparse) {
+    if (c.lists) {
+      // the caller's lists (reni_weight_lists_build for this B, P and these flags): no launch, no read of the weight
+      ld = list_dst(const_cast<char*>(c.lists->buf), make_list_layout(c.B, c.P));
+    } else {
+      ld = list_dst(ws, l);
+      rc = build_weight_lists(c.weight, c.wst, c.P, l.tpi, l.n_tiles, compact, ld, s);
+      if (rc) return rc;
     }
+    a.tlist = ld.tlist; a.tcount = ld.tcount;
+    if (compact) { a.plist = ld.plist; a.nlive = ld.nlive; }
   }
   // RENI_WEIGHT_COS_CONSTANT (cached lists whose build reported NO image with a live cosine term -- every mask of data/Masks: pixel 0
   // is masked): the statistics instance would visit nothing and k_stats_image would write B rows of zero coefficients; both launches
   // are left out and the coefficients are the zeros the build left in the lists buffer.  Same bits.
-  const bool cos_const = sparse && lists && (lists->flags & RENI_WEIGHT_COS_CONSTANT);
-  if (cos_const) stats = (float*)(const_cast<char*>(lists->buf) + make_list_layout(B, P).o_zstats);
+  const bool cos_const = sparse && c.lists && (c.lists->flags & RENI_WEIGHT_COS_CONSTANT);
+  if (cos_const) stats = (float*)(const_cast<char*>(c.lists->buf) + make_list_layout(c.B, c.P).o_zstats);
   if (cos_const) a.stats = stats;
   if (use_cos && !cos_const) {
     reni::MainArgs st = a;
@@ -821,28 +852,28 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
     rc = l.persist ? launch_train(p, st, l.nwg, s, true) : launch_main(p, reni::MODE_STATS, st, l.nwg, s);
     if (rc) return rc;
     // the statistics of every image and their cosine coefficients: one launch (k_stats_image; it was three)
-    RENI_LAUNCH(reni::k_stats_image, dim3((unsigned)B), dim3(256), 0, s, (const float*)a.loss_part, l.tpi, weight, (long long)wst[0],
-                       (long long)wst[2], beta, img_loss, stats, (const int*)imgcos);
+    RENI_LAUNCH(reni::k_stats_image, dim3((unsigned)c.B), dim3(256), 0, s, (const float*)a.loss_part, l.tpi, c.weight, (long long)c.wst[0],
+                       (long long)c.wst[2], c.beta, img_loss, stats, (const int*)ld.imgcos);
     HIP_TRY(hipGetLastError());
   }
-  a.loss_kind = (loss_kind == 2) ? 2 : (use_cos ? 1 : 0);
-  const bool l0x = l.persist && !l.wide_train && (flags & RENI_NEED_DW) && !fio && l0x_ok(p, a);  // (decided once: the training kernel, the ring and the tail's order follow it)
+  a.loss_kind = (c.loss_kind == LOSS_DOUT) ? LOSS_DOUT : (use_cos ? 1 : 0);
+  const bool l0x = l.persist && !l.wide_train && (c.flags & RENI_NEED_DW) && !c.fio && l0x_ok(p, a);  // (decided once: the training kernel, the ring and the tail's order follow it)
   rc = l.persist ? launch_train(p, a, l.nwg, s, false, l0x) : launch_main(p, reni::MODE_FWD_BWD, a, l.nwg, s);
   if (rc) return rc;
   // persistent path: fork.  `s` continues with k_reni_dw1 -> weight-gradient reduction -> first-layer weight tail;
   // `se` (side stream) takes everything that only needs the per-tile partials; joined before returning.
   hipStream_t se = s;
-  const bool pdw = l.persist && !l.wide_train && (a.need_dw || fio);  // the training instance ran: image runs, g_1 stream, k_reni_dw1
+  const bool pdw = l.persist && !l.wide_train && (a.need_dw || c.fio);  // the training instance ran: image runs, g_1 stream, k_reni_dw1
   const bool dw1_ring = dw1_ring_ok(p, a);           // which dW_1 kernel (and how many partial slots its reduction sums)
   bool ev_rest_done = false;
   bool dp_early_done = false;                        // reni_train_step_rows_dp: the early slice's all-reduce is on the side stream
   bool rp_in_tail = false;                           // the partial reduction of layers >= 2 is part of k_tail_a's launch
-  const bool fused_tail0 = pdw && !fio;
+  const bool fused_tail0 = pdw && !c.fio;
   // (small problems -- fewer than eight tiles per workgroup: the multi-resolution curriculum's first stages -- stay on ONE stream:
   // k_reni_dw1 is then a few microseconds, and the fork's and the join's cross-stream edges (~12 us each) cost more than it hides)
   // (L0X: the per-image epilogue needs k_reni_l0_ring's dA runs, so it runs BEHIND it on the one stream -- that kernel leaves no
   // registers for a neighbour anyway -- and the partial reduction of layers >= 2 rides in k_tail_a's launch)
-  const bool fork = pdw && !l0x && !p->no_side_stream && (fio || l.n_tiles >= 8 * l.nwg);
+  const bool fork = pdw && !l0x && !p->no_side_stream && (c.fio || l.n_tiles >= 8 * l.nwg);
   SideStream* side = fork ? side_stream() : nullptr;
   std::unique_lock<std::mutex> side_lock(g_side_mu, std::defer_lock);  // (the events are per device: one fork/join is enqueued at a time)
   if (side) side_lock.lock();
@@ -862,20 +893,20 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
       se = side->s;
       side_join.side = side; side_join.s = s;
     }
-    if (!fio && (flags & RENI_NEED_DW) && p->d.hidden_layers >= 1) {
+    if (!c.fio && (c.flags & RENI_NEED_DW) && p->d.hidden_layers >= 1) {
       // The partials of layers >= 2 (85 MB at the BASELINE shape; final when the training kernel ends) are reduced HERE, alone on
       // the device for 18 us: beside k_reni_dw1 the reduction took 116 us and slowed it by 25, and behind the latent tails of the
       // side stream it was the end of the longer chain (profiles/r03_step_timeline_c2.txt).
       const int n_rest = (int)(p->n_params - p->n_first), n_l1 = H * H + H;
       // (one stream: the reduction's blocks ride in k_tail_a's launch, below)
-      const bool dp_early = fuse && fuse->comm && fuse->overlap;  // (its early slice is what this reduction produces)
+      const bool dp_early = c.fuse && c.fuse->comm && c.fuse->overlap;  // (its early slice is what this reduction produces)
       rp_in_tail = !side && fused_tail0 && n_rest > n_l1 && !g_ev_rest && !dp_early;
       if (n_rest > n_l1 && !rp_in_tail) {
         // (alone in front of k_reni_dw1, not beside it on a stream of its own: measured again in round 4 with the fused epilogue --
         // beside, everything crawls and the step is 30 us longer: profiles/r04_tail.md)
         hipStream_t sr = s;
         RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_rest - n_l1 + 63) / 64)), dim3(256), 0, sr,
-                           (const float*)a.dwp, l.dwp_per_wg, l.nwg, dparams + p->n_first, n_l1, n_rest, (const int*)nullptr, lsc);
+                           (const float*)a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, n_l1, n_rest, (const int*)nullptr, lsc);
         HIP_TRY(hipGetLastError());
         // the gradient of layers >= 2 and of the head is final HERE, a whole k_reni_dw1 before the call ends: a data-parallel caller
         // starts their all-reduce on another stream behind this event (TrainEngine(overlap_comm=True))
@@ -889,7 +920,7 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
           if (!side_lock.owns_lock()) side_lock.lock();
           HIP_TRY(hipEventRecord(cs->ev[1], sr));
           HIP_TRY(hipStreamWaitEvent(cs->s, cs->ev[1], 0));
-          rc = rccl_allreduce_inplace(fuse->comm, dparams + p->n_first + n_l1, (size_t)(n_rest - n_l1), cs->s);
+          rc = rccl_allreduce_inplace(c.fuse->comm, c.dparams + p->n_first + n_l1, (size_t)(n_rest - n_l1), cs->s);
           if (rc) return rc;
           if (!side_join.side) { side_join.side = cs; side_join.s = s; }  // (joined like the forked epilogue: whatever path leaves)
           dp_early_done = true;
@@ -909,7 +940,7 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(ev.b, s));
   }
-  if (l.wide_train && (flags & RENI_NEED_DW)) {  // the head's weight gradient from k_reni_wide256<2>'s g_y stream and phase stash (a frozen FiLM decoder: no partials to write)
+  if (l.wide_train && (c.flags & RENI_NEED_DW)) {  // the head's weight gradient from k_reni_wide256<2>'s g_y stream and phase stash (a frozen FiLM decoder: no partials to write)
     g_launches.fetch_add(1, std::memory_order_relaxed);
     EvPair ev;
     const bool timed = prof_begin(s, &ev, PROF_DWS);
@@ -920,7 +951,7 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
   if (l.stream) {  // hidden-layer weight gradients (and FiLM d(freq), d(phase)) from the operand stream
     static_assert(reni::Geo<reni::PolBF16, 256>::T_BYTES_AL == 36864 && reni::Geo<reni::PolBF16, 128>::T_BYTES_AL == 34816,
                   "stream record sizes (make_layout)");
-    const bool film = fio != nullptr;
+    const bool film = c.fio != nullptr;
     void (*fn)(const reni::MainArgs) = nullptr;
     if (H == 256) fn = film ? reni::k_dw_frag<256, true> : reni::k_dw_frag<256, false>;
     else fn = film ? reni::k_dw_stream<128, true> : reni::k_dw_stream<128, false>;
@@ -933,25 +964,25 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(ev.b, s));
   }
-  const bool fused_tail = pdw && !fio;  // concat decoder on the persistent path: the per-image epilogue is k_tail_a + k_tail_b, below
+  const bool fused_tail = pdw && !c.fio;  // concat decoder on the persistent path: the per-image epilogue is k_tail_a + k_tail_b, below
   // reni_train_step_rows on that path: layer 1's partial reduction is not launched -- it rides in the Adam launch behind the call's
   // work (k_adam2's layer-1 blocks)
   // (not with a data-parallel exchange inside the call: the collective needs layer 1's sum in the gradient buffer first)
-  const bool fuse_on = fuse && !fuse->comm && fused_tail && (flags & RENI_NEED_DW) && (flags & RENI_NEED_DZ) && p->d.hidden_layers >= 1;
+  const bool fuse_on = c.fuse && !c.fuse->comm && fused_tail && (c.flags & RENI_NEED_DW) && (c.flags & RENI_NEED_DZ) && p->d.hidden_layers >= 1;
   if (fused_tail) {
   } else if (pdw) {  // the training instance keeps the per-image sums on chip: a few image runs per image
-    RENI_LAUNCH(reni::k_reduce_runs, dim3((unsigned)B, B < 16 ? (unsigned)((H * 8 + 16 + 63) / 64) : 1u), dim3(256), 0, se, (const float*)a.pruns, (const int*)a.prun_image,
+    RENI_LAUNCH(reni::k_reduce_runs, dim3((unsigned)c.B, c.B < 16 ? (unsigned)((H * 8 + 16 + 63) / 64) : 1u), dim3(256), 0, se, (const float*)a.pruns, (const int*)a.prun_image,
                        l.nwg, l.pkmax, H, l.tpi, l.n_tiles, dA, img_loss);
     HIP_TRY(hipGetLastError());
   } else {
-    RENI_LAUNCH(reni::k_reduce_tiles_a, dim3((unsigned)B, (unsigned)l.nch), dim3(256), 0, se, (const float*)a.dA_part,
-                       (const float*)a.loss_part, l.tpi, H, part2, 1, l.rt_chunk, (const int*)tflag);
+    RENI_LAUNCH(reni::k_reduce_tiles_a, dim3((unsigned)c.B, (unsigned)l.nch), dim3(256), 0, se, (const float*)a.dA_part,
+                       (const float*)a.loss_part, l.tpi, H, part2, 1, l.rt_chunk, (const int*)ld.tflag);
     HIP_TRY(hipGetLastError());
-    RENI_LAUNCH(reni::k_reduce_tiles_b, dim3((unsigned)B, (unsigned)((H * 8 + 16 + 255) / 256)), dim3(256), 0, se, (const float*)part2, l.nch, H, dA, img_loss, 1);
+    RENI_LAUNCH(reni::k_reduce_tiles_b, dim3((unsigned)c.B, (unsigned)((H * 8 + 16 + 255) / 256)), dim3(256), 0, se, (const float*)part2, l.nch, H, dA, img_loss, 1);
     HIP_TRY(hipGetLastError());
   }
 
-  if (fio) {
+  if (c.fio) {
     // (persistent path: `s` carries k_reni_dw1 and what needs its runs -- d(freq) / d(phase), layer 1's weight gradient;
     // `se` what needs the training kernel only -- dA, the loss, the other layers' weight gradients)
     const int L = p->d.hidden_layers;
@@ -959,132 +990,120 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
     //  stream path's consumers, whose bookkeeping is the generic chain's)
     const bool fpers = l.persist && !l.wide_train;
     // persistent path with weight gradients: the runs' d(freq) / d(phase) sums and layer 1's tagged partials in one launch, below
-    const bool red2 = L > 0 && fpers && (flags & RENI_NEED_DW);
+    const bool red2 = L > 0 && fpers && (c.flags & RENI_NEED_DW);
     if (red2) {
     } else if (L > 0 && (l.stream || fpers)) {
-      RENI_LAUNCH(reni::k_reduce_film_runs, dim3((unsigned)B, (unsigned)((L * H + 255) / 256)), dim3(256), 0, s, a, H,
-                         fpers ? 3 * l.nwg * l.pkmax : l.nwg * l.kmax, fio->dfilm);
+      RENI_LAUNCH(reni::k_reduce_film_runs, dim3((unsigned)c.B, (unsigned)((L * H + 255) / 256)), dim3(256), 0, s, a, H,
+                         fpers ? 3 * l.nwg * l.pkmax : l.nwg * l.kmax, c.fio->dfilm);
       HIP_TRY(hipGetLastError());
     } else if (L > 0) {
-      RENI_LAUNCH(reni::k_reduce_film, dim3((unsigned)B, (unsigned)((L * 2 * H + 255) / 256)), dim3(256), 0, s,
-                         (const float*)a.dfp_part, l.tpi, L * 2 * H, fio->dfilm);
+      RENI_LAUNCH(reni::k_reduce_film, dim3((unsigned)c.B, (unsigned)((L * 2 * H + 255) / 256)), dim3(256), 0, s,
+                         (const float*)a.dfp_part, l.tpi, L * 2 * H, c.fio->dfilm);
       HIP_TRY(hipGetLastError());
     }
-    if (flags & RENI_NEED_DW) {
+    if (c.flags & RENI_NEED_DW) {
       // the first layer's gradient belongs to the glue (it is a function of dA): zero its slot unless the caller
       // (reni_film_model_*) fills it
-      if (!fio->keep_first) HIP_TRY(hipMemsetAsync(dparams, 0, (size_t)p->n_first * 4, s));
+      if (!c.fio->keep_first) HIP_TRY(hipMemsetAsync(c.dparams, 0, (size_t)p->n_first * 4, s));
       const int n_rest = (int)(p->n_params - p->n_first);
       if (fpers) {  // one partial slot per image run: layer 1 from k_reni_dw1's runs, the rest from the training kernel's
         const int n_l1 = H * H + H, nslot = l.nwg * l.pkmax;
         reni::FilmReduce2 r2;
-        r2.H = H; r2.nruns = 3 * l.nwg * l.pkmax; r2.B = (int)B; r2.gy = (L * H + 255) / 256; r2.dfilm = fio->dfilm;
-        r2.part = a.dw1p; r2.per_wg = (size_t)n_l1; r2.nslot = 2 * nslot; r2.dparams = dparams + p->n_first; r2.n = n_l1;
+        r2.H = H; r2.nruns = 3 * l.nwg * l.pkmax; r2.B = (int)c.B; r2.gy = (L * H + 255) / 256; r2.dfilm = c.fio->dfilm;
+        r2.part = a.dw1p; r2.per_wg = (size_t)n_l1; r2.nslot = 2 * nslot; r2.dparams = c.dparams + p->n_first; r2.n = n_l1;
         r2.valid = (const int*)a.prun_image + nslot;
         RENI_LAUNCH(reni::k_film_reduce2, dim3((unsigned)(r2.B * r2.gy + (n_l1 + 63) / 64)), dim3(256), 0, s, a, r2);
         HIP_TRY(hipGetLastError());
         RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_rest - n_l1 + 63) / 64)), dim3(256), 0, se,
-                           (const float*)a.dwp, l.dwp_per_wg, nslot, dparams + p->n_first, n_l1, n_rest, (const int*)a.prun_image, lsc);
+                           (const float*)a.dwp, l.dwp_per_wg, nslot, c.dparams + p->n_first, n_l1, n_rest, (const int*)a.prun_image, lsc);
         HIP_TRY(hipGetLastError());
       } else {
         RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_rest + 63) / 64)), dim3(256), 0, s,
-                           (const float*)a.dwp, l.dwp_per_wg, l.nwg, dparams + p->n_first, 0, n_rest, (const int*)nullptr, lsc);
+                           (const float*)a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, 0, n_rest, (const int*)nullptr, lsc);
         HIP_TRY(hipGetLastError());
       }
     }
-    if (loss_kind != 2) {
+    if (c.loss_kind != LOSS_DOUT) {
       RENI_LAUNCH(reni::k_finalize_loss, dim3(1), dim3(256), 0, se, (const float*)img_loss, (const float*)stats,
-                         fio->Zp, (int)B, (int)P, (int)fio->nz, use_cos ? 1 : 0,
-                         (fio->Zp != nullptr && loss_kind == RENI_LOSS_TEST) ? 1 : 0, fio->alpha, beta, loss_terms);
+                         c.fio->Zp, (int)c.B, (int)c.P, (int)c.fio->nz, use_cos ? 1 : 0,
+                         (c.fio->Zp != nullptr && c.loss_kind == RENI_LOSS_TEST) ? 1 : 0, c.fio->alpha, c.beta, c.loss_terms);
       HIP_TRY(hipGetLastError());
     }
     return RENI_OK;  // (joined by side_join)
   }
 
   reni::TailArgs t;
-  t.dA = dA; t.W0 = params; t.Z = Z; t.xconst = (const float*)(ws + l.o_xconst);
+  t.dA = dA; t.W0 = c.params; t.Z = Z; t.xconst = (const float*)(ws + l.o_xconst);
   t.mcol = (float*)(ws + l.o_mcol); t.ucol = (float*)(ws + l.o_ucol);
-  t.dZ = dZ; t.dW0 = dparams; t.db0 = dparams ? dparams + (size_t)H * p->F_in : nullptr;
-  t.alpha2 = (loss_kind == RENI_LOSS_TEST) ? alpha : 0.f;
-  t.eq = p->d.equivariance; t.nd = p->d.ndims; t.F_in = p->F_in; t.H = H; t.B = (int)B;
+  t.dZ = c.dZ; t.dW0 = c.dparams; t.db0 = c.dparams ? c.dparams + (size_t)H * p->F_in : nullptr;
+  t.alpha2 = (c.loss_kind == RENI_LOSS_TEST) ? c.alpha : 0.f;
+  t.eq = p->d.equivariance; t.nd = p->d.ndims; t.F_in = p->F_in; t.H = H; t.B = (int)c.B;
   auto reduce_l1 = [&]() -> int {
-  if (flags & RENI_NEED_DW) {
+  if (c.flags & RENI_NEED_DW) {
       const int n_rest = (int)(p->n_params - p->n_first);
       // persistent path: layer 1's H * H + H values come from k_reni_dw1's own partials (the rest was reduced in front of it)
       const int n_l1 = (l.persist && !l.wide_train && p->d.hidden_layers >= 1) ? H * H + H : 0;
       if (n_l1 > 0) {
         const int grid1 = dw1_slots(dw1_ring, l.nwg);
         RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_l1 + 63) / 64)), dim3(256), 0, s,
-                           (const float*)a.dw1p, (size_t)n_l1, grid1, dparams + p->n_first, 0, n_l1, (const int*)nullptr, lsc);
+                           (const float*)a.dw1p, (size_t)n_l1, grid1, c.dparams + p->n_first, 0, n_l1, (const int*)nullptr, lsc);
         HIP_TRY(hipGetLastError());
       }
     }
     return RENI_OK;
   };
   if (!fuse_on) { rc = reduce_l1(); if (rc) return rc; }
+  // what k_tail_b takes on either path: the per-image sums, the loss configuration, which outputs are wanted ...
+  reni::TailFusedArgs f;
+  memset(&f, 0, sizeof(f));
+  f.t = t;
+  f.img_loss = img_loss; f.stats = stats; f.P = (int)c.P; f.nz = (int)(c.B * p->d.ndims * 3); f.has_cos = use_cos ? 1 : 0;
+  f.has_prior = (c.loss_kind == RENI_LOSS_TEST) ? 1 : 0; f.alpha = c.alpha; f.beta = c.beta;
+  f.loss_terms = (c.loss_kind != LOSS_DOUT) ? c.loss_terms : nullptr;
+  f.need_dz = (c.flags & RENI_NEED_DZ) ? 1 : 0;
+  f.need_dw0 = (c.flags & RENI_NEED_DW) ? 1 : 0;
+  f.dw0_gx = (p->F_in + 1 + 255) / 256;
+  // ... and, for a staged step: the batch the previous call prepared must be the batch this call was given (else: NaN, loudly)
+  // (the staged-batch check of reni_train_step_rows on the generic kernels too: fp32, H = 32 / 64 / 256, RENI_NO_PERSIST -- ADVICE r04)
+  f.idx_now = staged ? (const long long*)c.idx : nullptr;
+  f.idx_staged = staged ? (const long long*)(ws + l.o_idxc) : nullptr;
+  f.skip_flag = c.fuse ? (int*)(ws + l.o_skip) : nullptr;
+  const unsigned nb = (unsigned)((f.need_dz ? c.B : 0) + 1 + (f.need_dw0 ? f.dw0_gx * H : 0));
   if (fused_tail) {
     // image runs -> dA_b, loss sums, m / u columns (k_tail_a); then dZ_b, loss terms, dW0 / db0 (k_tail_b): two launches, it was five
-    reni::TailFusedArgs f;
-    memset(&f, 0, sizeof(f));
-    f.t = t;
     f.pruns = a.pruns; f.prun_image = a.prun_image; f.nwg = l.nwg; f.kmax = l.pkmax; f.tpi = l.tpi; f.n_tiles = l.n_tiles;
-    f.dA_out = dA; f.img_loss = img_loss;
-    f.stats = stats; f.P = (int)P; f.nz = (int)(B * p->d.ndims * 3); f.has_cos = use_cos ? 1 : 0;
-    f.has_prior = (loss_kind == RENI_LOSS_TEST) ? 1 : 0; f.alpha = alpha; f.beta = beta;
-    f.loss_terms = (loss_kind != 2) ? loss_terms : nullptr;
-    f.need_dz = (flags & RENI_NEED_DZ) ? 1 : 0;
-    f.need_dw0 = (flags & RENI_NEED_DW) ? 1 : 0;
-    // a staged step: the batch the previous call prepared must be the batch this call was given (else: NaN, loudly)
-    f.idx_now = staged ? (const long long*)idx : nullptr;
-    f.idx_staged = staged ? (const long long*)(ws + l.o_idxc) : nullptr;
-    f.skip_flag = fuse ? (int*)(ws + l.o_skip) : nullptr;
-    f.dw0_gx = (p->F_in + 1 + 255) / 256;
+    f.dA_out = dA;
     const unsigned ny = f.need_dz ? (unsigned)((p->F_in + 63) / 64) : 1u;
-    unsigned gx = (unsigned)B;
+    unsigned gx = (unsigned)c.B;
     if (rp_in_tail) {
       const int n_rest = (int)(p->n_params - p->n_first), n_l1 = H * H + H;
-      f.rp_part = a.dwp; f.rp_per_wg = l.dwp_per_wg; f.rp_nwg = l.nwg; f.rp_out = dparams + p->n_first; f.rp_lo = n_l1; f.rp_n = n_rest; f.rp_ls = lsc;
+      f.rp_part = a.dwp; f.rp_per_wg = l.dwp_per_wg; f.rp_nwg = l.nwg; f.rp_out = c.dparams + p->n_first; f.rp_lo = n_l1; f.rp_n = n_rest; f.rp_ls = lsc;
       gx += ((unsigned)((n_rest - n_l1 + 63) / 64) + ny - 1) / ny;
     }
     RENI_LAUNCH(reni::k_tail_a, dim3(gx, ny), dim3(256), (size_t)reni::tail_a_lds_bytes(H), se, f);
     HIP_TRY(hipGetLastError());
     // dZ_b (B blocks), the loss terms (one block), dW0 / db0: all functions of k_tail_a's results alone -> one launch
-    const unsigned nb = (unsigned)((f.need_dz ? B : 0) + 1 + (f.need_dw0 ? f.dw0_gx * H : 0));
     RENI_LAUNCH(reni::k_tail_b, dim3(nb), dim3(256), 0, se, f);
     HIP_TRY(hipGetLastError());
   } else {
-    if (flags & RENI_NEED_DZ) {
-      RENI_LAUNCH(reni::k_tail_m, dim3((unsigned)B, (unsigned)((p->F_in + 63) / 64)), dim3(256), 0, se, t);
+    if (c.flags & RENI_NEED_DZ) {
+      RENI_LAUNCH(reni::k_tail_m, dim3((unsigned)c.B, (unsigned)((p->F_in + 63) / 64)), dim3(256), 0, se, t);
       HIP_TRY(hipGetLastError());
     }
     // dZ_b (from k_tail_m's columns), the loss terms, dW0 / db0 (from the per-image dA): one launch (k_tail_b; it was three)
-    reni::TailFusedArgs f;
-    memset(&f, 0, sizeof(f));
-    f.t = t;
-    f.img_loss = img_loss; f.stats = stats; f.P = (int)P; f.nz = (int)(B * p->d.ndims * 3); f.has_cos = use_cos ? 1 : 0;
-    f.has_prior = (loss_kind == RENI_LOSS_TEST) ? 1 : 0; f.alpha = alpha; f.beta = beta;
-    f.loss_terms = (loss_kind != 2) ? loss_terms : nullptr;
-    f.need_dz = (flags & RENI_NEED_DZ) ? 1 : 0;
-    f.need_dw0 = (flags & RENI_NEED_DW) ? 1 : 0;
-    f.dw0_gx = (p->F_in + 1 + 255) / 256;
-    // (the staged-batch check of reni_train_step_rows on the generic kernels too: fp32, H = 32 / 64 / 256, RENI_NO_PERSIST -- ADVICE r04)
-    f.idx_now = staged ? (const long long*)idx : nullptr;
-    f.idx_staged = staged ? (const long long*)(ws + l.o_idxc) : nullptr;
-    f.skip_flag = fuse ? (int*)(ws + l.o_skip) : nullptr;
-    const unsigned nb = (unsigned)((f.need_dz ? B : 0) + 1 + (f.need_dw0 ? f.dw0_gx * H : 0));
     RENI_LAUNCH(reni::k_tail_b, dim3(nb), dim3(256), 0, se, f);
     HIP_TRY(hipGetLastError());
   }
-  if ((flags & RENI_NEED_DW) && !fused_tail) {
+  if ((c.flags & RENI_NEED_DW) && !fused_tail) {
     const int n_rest = (int)(p->n_params - p->n_first);
     if (!(pdw && p->d.hidden_layers >= 1) && n_rest > 0) {  // (persistent path: reduced in front of k_reni_dw1, above)
       RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_rest + 63) / 64)), dim3(256), 0, s,
-                         (const float*)a.dwp, l.dwp_per_wg, l.nwg, dparams + p->n_first, 0, n_rest, (const int*)nullptr, lsc);
+                         (const float*)a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, 0, n_rest, (const int*)nullptr, lsc);
       HIP_TRY(hipGetLastError());
     }
   }
   if (g_ev_rest && !ev_rest_done) HIP_TRY(hipEventRecord(g_ev_rest, s));  // (paths without the early point: final at the end)
-  if (fuse) {
+  if (c.fuse) {
     // reni_train_step_rows: behind the call's work -- the side stream (if any) is joined first -- ONE launch takes the whole optimiser
     // step (decoder, latent table and, on the persistent path, layer 1's partial reduction with its Adam step), then the next
     // batch's prologue goes into the other stage copy.
@@ -1096,7 +1115,7 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
       HIP_TRY(hipStreamWaitEvent(s, side_join.side->ev[2], 0));
       side_join.side = nullptr;
     }
-    if (fuse->comm) {
+    if (c.fuse->comm) {
       // the data-parallel exchange (run.py:97-110: DDP's all-reduce of the shared decoder's gradients) INSIDE the step: an in-place
       // RCCL sum of the flat decoder gradient over the communicator's ranks on the caller's stream; the 1 / world of the mean rides on
       // Adam's grad_scale.  Latent rows need no exchange (every row has one owner: reni_amd/dist.py).
@@ -1106,19 +1125,19 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
       // (a staged step that met another batch than the one staged for it is skipped -- k_tail_b's flag, k_adam2 -- and that decision
       //  must be the same on every rank, or the replicas part: the flags' MAX first (4 bytes; ADVICE r05))
       // (unconditionally -- not only when THIS rank's step is staged: a collective every rank must enter)
-      rc = rccl_allreduce_max_i32(fuse->comm, (int*)(ws + l.o_skip), 1, s);
+      rc = rccl_allreduce_max_i32(c.fuse->comm, (int*)(ws + l.o_skip), 1, s);
       if (rc) return rc;
-      rc = rccl_allreduce_inplace(fuse->comm, dparams, (size_t)p->n_params - n_early, s);
+      rc = rccl_allreduce_inplace(c.fuse->comm, c.dparams, (size_t)p->n_params - n_early, s);
       if (rc) return rc;
       if (timed) HIP_TRY(hipEventRecord(ev.b, s));
     }
     reni::Adam2Args ad;
-    ad.p = fuse->params; ad.g = dparams; ad.m = fuse->m_dec; ad.v = fuse->v_dec; ad.n = p->n_params;
+    ad.p = c.fuse->params; ad.g = c.dparams; ad.m = c.fuse->m_dec; ad.v = c.fuse->v_dec; ad.n = p->n_params;
     ad.nb_dec = (int)((p->n_params + 255) / 256);
-    ad.tp = fuse->table; ad.g_rows = dZ; ad.idx = (const long long*)idx; ad.B = (int)B; ad.row_len = p->d.ndims * 3;
-    ad.tm = fuse->m_lat; ad.tv = fuse->v_lat; ad.tn = n_rows * ad.row_len;
-    ad.lr = fuse->lr; ad.b1 = fuse->b1; ad.b2 = fuse->b2; ad.eps = fuse->eps; ad.gscale = fuse->gscale;
-    ad.bc1 = fuse->bc1; ad.bc2_sqrt = fuse->bc2_sqrt;
+    ad.tp = c.fuse->table; ad.g_rows = c.dZ; ad.idx = (const long long*)c.idx; ad.B = (int)c.B; ad.row_len = p->d.ndims * 3;
+    ad.tm = c.fuse->m_lat; ad.tv = c.fuse->v_lat; ad.tn = c.n_rows * ad.row_len;
+    ad.lr = c.fuse->lr; ad.b1 = c.fuse->b1; ad.b2 = c.fuse->b2; ad.eps = c.fuse->eps; ad.gscale = c.fuse->gscale;
+    ad.bc1 = c.fuse->bc1; ad.bc2_sqrt = c.fuse->bc2_sqrt;
     ad.skip_lo = 0; ad.skip_hi = 0; ad.l1_part = nullptr; ad.l1_per_wg = 0; ad.l1_nwg = 0; ad.nb_l1 = 0; ad.l1_scale = lsc.c[0];
     ad.skip_step = (const int*)(ws + l.o_skip);  // (written by this call's k_tail_b, in front of this launch on every path)
     if (fuse_on) {
@@ -1128,11 +1147,11 @@ int run_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
     }
     RENI_LAUNCH(reni::k_adam2, dim3((unsigned)(ad.nb_dec + (ad.tn + 255) / 256 + ad.nb_l1)), dim3(256), 0, s, ad);
     HIP_TRY(hipGetLastError());
-    if (fuse->idx_next) {
-      const Layout ln = make_layout(p, g, B, P, flags, true, true, 1 - stage);
-      rc = run_prologue(p, g, ln, B, fuse->table, fuse->params, ws, true, s, fuse->idx_next, nullptr, n_rows);
+    if (c.fuse->idx_next) {
+      const Layout ln = make_layout(p, g, c.B, c.P, c.flags, true, true, 1 - stage);
+      rc = run_prologue(p, g, ln, c.B, c.fuse->table, c.fuse->params, ws, true, s, c.fuse->idx_next, nullptr, c.n_rows);
       if (rc) return rc;
-      *fuse->state = 1u | ((uint32_t)(1 - stage) << 1);
+      *c.fuse->state = 1u | ((uint32_t)(1 - stage) << 1);
     }
   }
   return RENI_OK;  // (joined by side_join)
@@ -1159,46 +1178,50 @@ int64_t frag_chunk_images(const reni_plan* p, int64_t B, int64_t P, uint32_t fla
   return (B + n_chunks - 1) / n_chunks;
 }
 
-int run_backward_chunked(const reni_plan* p, int64_t B, int64_t P, const float* Z, const float* D, int64_t dbs, const float* params,
-                         const float* target, const int64_t* ts, const float* weight, const int64_t* wst, const float* dout,
-                         int loss_kind, float alpha, float beta, uint32_t flags, float* out, float* loss_terms, float* dZ,
-                         float* dparams, void* ws_v, size_t ws_bytes, void* stream, const int64_t* idx = nullptr, int64_t n_rows = 0) {
-  const int64_t bc = (p && B >= 1 && P >= 1) ? frag_chunk_images(p, B, P, flags) : B;
-  if (bc >= B)
-    return run_backward(p, B, P, Z, D, dbs, params, target, ts, weight, wst, dout, loss_kind, alpha, beta, flags, out, loss_terms, dZ,
-                        dparams, ws_v, ws_bytes, stream, nullptr, idx, n_rows);
+int run_backward_chunked(const reni_plan* p, const BwdCall& c) {
+  const int64_t B = c.B, P = c.P;
+  const int64_t bc = (p && B >= 1 && P >= 1) ? frag_chunk_images(p, B, P, c.flags) : B;
+  if (bc >= B) return run_backward(p, c);
   // workspace: [chunk's own layout | dparams of the chunk | loss terms of the chunk]
   GeoRt g;
   geo_for(p, &g);
   // the chunk loop's own launches (k_add_into) run on the device that owns the buffers, like everything run_backward launches
   DeviceGuard dev_guard;
-  if (const int rcg = dev_guard.enter(params)) return rcg;
-  const size_t core = al256(make_layout(p, g, bc, P, flags | RENI_NEED_DZ, true, true).total);
-  if (B % bc != 0 && make_layout(p, g, B % bc, P, flags | RENI_NEED_DZ, true, true).total > core)
+  if (const int rcg = dev_guard.enter(c.params)) return rcg;
+  const size_t core = al256(make_layout(p, g, bc, P, c.flags | RENI_NEED_DZ, true, true).total);
+  if (B % bc != 0 && make_layout(p, g, B % bc, P, c.flags | RENI_NEED_DZ, true, true).total > core)
     return fail(RENI_EWORKSPACE, "internal: the last chunk's layout exceeds a full chunk's");
   const size_t extra = al256((size_t)p->n_params * 4) + 256;
-  if (!ws_v) return fail(RENI_EWORKSPACE, "workspace is NULL");
-  if (ws_bytes < core + extra) return fail(RENI_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", core + extra, ws_bytes);
-  float* dp_c = (float*)((char*)ws_v + core);
-  float* lt_c = (float*)((char*)ws_v + core + al256((size_t)p->n_params * 4));
-  hipStream_t s = (hipStream_t)stream;
+  if (!c.ws) return fail(RENI_EWORKSPACE, "workspace is NULL");
+  if (c.ws_bytes < core + extra) return fail(RENI_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", core + extra, c.ws_bytes);
+  float* dp_c = (float*)((char*)c.ws + core);
+  float* lt_c = (float*)((char*)c.ws + core + al256((size_t)p->n_params * 4));
+  hipStream_t s = (hipStream_t)c.stream;
   const int nd3 = p->d.ndims * 3;
   for (int64_t b0 = 0; b0 < B; b0 += bc) {
-    const int64_t nb = (B - b0 < bc) ? B - b0 : bc;
     const bool first = b0 == 0;
-    const int rc = run_backward(p, nb, P, (idx || !Z) ? Z : Z + b0 * nd3, D ? D + b0 * dbs : D, dbs, params,
-                                target ? target + b0 * ts[0] : nullptr, ts, weight ? weight + b0 * wst[0] : nullptr, wst,
-                                dout ? dout + b0 * P * 3 : nullptr, loss_kind, alpha, beta, flags, out ? out + b0 * P * 3 : nullptr,
-                                loss_terms ? (first ? loss_terms : lt_c) : nullptr, dZ ? dZ + b0 * nd3 : nullptr,
-                                dparams ? (first ? dparams : dp_c) : nullptr, ws_v, core, stream, nullptr, idx ? idx + b0 : nullptr, n_rows);
+    BwdCall k = c;  // the chunk: images [b0, b0 + k.B) of the call, every per-image buffer moved there
+    k.B = (B - b0 < bc) ? B - b0 : bc;
+    if (c.idx) k.idx = c.idx + b0;  // (Z stays the table)
+    else if (c.Z) k.Z = c.Z + b0 * nd3;
+    if (c.D) k.D = c.D + b0 * c.dbs;
+    if (c.target) k.target = c.target + b0 * c.ts[0];
+    if (c.weight) k.weight = c.weight + b0 * c.wst[0];
+    if (c.dout) k.dout = c.dout + b0 * P * 3;
+    if (c.out) k.out = c.out + b0 * P * 3;
+    if (c.dZ) k.dZ = c.dZ + b0 * nd3;
+    if (c.loss_terms && !first) k.loss_terms = lt_c;
+    if (c.dparams && !first) k.dparams = dp_c;
+    k.ws_bytes = core;
+    const int rc = run_backward(p, k);
     if (rc) return rc;
     if (!first) {
-      if (dparams) {
-        RENI_LAUNCH(reni::k_add_into, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, s, dparams, (const float*)dp_c, (size_t)p->n_params);
+      if (c.dparams) {
+        RENI_LAUNCH(reni::k_add_into, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, s, c.dparams, (const float*)dp_c, (size_t)p->n_params);
         HIP_TRY(hipGetLastError());
       }
-      if (loss_terms) {
-        RENI_LAUNCH(reni::k_add_into, dim3(1), dim3(256), 0, s, loss_terms, (const float*)lt_c, (size_t)4);
+      if (c.loss_terms) {
+        RENI_LAUNCH(reni::k_add_into, dim3(1), dim3(256), 0, s, c.loss_terms, (const float*)lt_c, (size_t)4);
         HIP_TRY(hipGetLastError());
       }
     }
@@ -1287,34 +1310,38 @@ size_t core_ws_bytes(const reni_plan* p, int64_t B, int64_t P, uint32_t flags) {
   return al256(make_layout(p, g, B, P, flags | RENI_NEED_DZ, true, true).total);  // (as reni_workspace_bytes sizes it)
 }
 
-int film_model_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const float* D, int64_t dbs,
-                        const float* params, const float* mparams, const float* target, const int64_t* ts,
-                        const float* weight, const int64_t* wst, const float* dout, int loss_kind, float alpha, float beta,
-                        uint32_t flags, float* out, float* loss_terms, float* dZ, float* dparams, float* dmparams,
-                        void* ws_v, size_t ws_bytes, void* stream) {
-  int rc = check_film_model(p, Z, mparams);
+// (c.Z: the latents; c.dparams / dmparams: the decoder's and the mapping network's gradients)
+int film_model_backward(const reni_plan* p, const BwdCall& c, const float* mparams, float* dmparams) {
+  const int64_t B = c.B;
+  const uint32_t flags = c.flags;
+  float* const dparams = c.dparams;
+  int rc = check_film_model(p, c.Z, mparams);
   if (rc) return rc;
   if ((flags & RENI_NEED_DW) && (!dparams || !dmparams)) return fail(RENI_EINVAL, "RENI_NEED_DW set but dparams / dmap_params is NULL");
-  if (!dZ) return fail(RENI_EINVAL, "dZ is NULL");
-  if (!ws_v) return fail(RENI_EWORKSPACE, "workspace is NULL");
-  const size_t core = core_ws_bytes(p, B, P, flags);
+  if (!c.dZ) return fail(RENI_EINVAL, "dZ is NULL");
+  if (!c.ws) return fail(RENI_EWORKSPACE, "workspace is NULL");
+  const size_t core = core_ws_bytes(p, B, c.P, flags);
   const GlueLayout gl = make_glue_layout(p, B);
-  if (core == 0 || ws_bytes < core + gl.total)
-    return fail(RENI_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", core + gl.total, ws_bytes);
+  if (core == 0 || c.ws_bytes < core + gl.total)
+    return fail(RENI_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", core + gl.total, c.ws_bytes);
   DeviceGuard dev_guard;
-  rc = dev_guard.enter(params);
+  rc = dev_guard.enter(c.params);
   if (rc) return rc;
-  char* gw = (char*)ws_v + core;
-  hipStream_t s = (hipStream_t)stream;
+  char* gw = (char*)c.ws + core;
+  hipStream_t s = (hipStream_t)c.stream;
   reni::FilmGlueArgs g;
-  fill_glue(g, p, gl, B, Z, params, mparams, gw);
-  g.dZ = dZ;
-  g.alpha2 = (loss_kind == RENI_LOSS_TEST) ? 2.f * alpha : 0.f;
+  fill_glue(g, p, gl, B, c.Z, c.params, mparams, gw);
+  g.dZ = c.dZ;
+  g.alpha2 = (c.loss_kind == RENI_LOSS_TEST) ? 2.f * c.alpha : 0.f;
   rc = run_film_glue_fwd(g, s);
   if (rc) return rc;
-  const FilmIO fio = {g.A, g.film, (float*)(gw + gl.o_dA), (float*)(gw + gl.o_dfilm), Z, alpha, B * p->d.ndims * 3, 1};
-  rc = run_backward(p, B, P, nullptr, D, dbs, params, target, ts, weight, wst, dout, loss_kind, 0.f, beta, flags & RENI_NEED_DW,
-                    out, loss_terms, nullptr, dparams, ws_v, core, stream, &fio);
+  FilmIO fio;
+  fio.A = g.A; fio.film = g.film; fio.dA = (float*)(gw + gl.o_dA); fio.dfilm = (float*)(gw + gl.o_dfilm);
+  fio.Zp = c.Z; fio.alpha = c.alpha; fio.nz = B * p->d.ndims * 3; fio.keep_first = 1;
+  BwdCall k = c;  // the per-sample core: the glue owns the latents, their prior and their gradient
+  k.Z = nullptr; k.dZ = nullptr; k.alpha = 0.f; k.flags = flags & RENI_NEED_DW;
+  k.ws_bytes = core; k.fio = &fio;
+  rc = run_backward(p, k);
   if (rc) return rc;
   RENI_LAUNCH(reni::k_film_dout, dim3((unsigned)B), dim3(256), 0, s, g);
   HIP_TRY(hipGetLastError());
@@ -1535,7 +1562,8 @@ int reni_forward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const
 
 int reni_film_forward(const reni_plan* p, int64_t B, int64_t P, const float* D, int64_t dbs, const float* A,
                       const float* film, const float* params, float* out, void* ws, size_t ws_bytes, void* stream) {
-  const FilmIO fio = {A, film, nullptr, nullptr, nullptr, 0.f, 0, 0};
+  FilmIO fio;
+  fio.A = A; fio.film = film;
   return forward_impl(p, B, P, nullptr, D, dbs, params, out, ws, ws_bytes, stream, &fio);
 }
 
@@ -1545,17 +1573,27 @@ int reni_film_forward_loss_backward(const reni_plan* p, int64_t B, int64_t P, co
                                     int32_t loss_kind, float beta, uint32_t flags, float* out, float* loss_terms,
                                     float* dA, float* dfilm, float* dparams, void* ws, size_t ws_bytes,
                                     void* stream) {
-  const FilmIO fio = {A, film, dA, dfilm, nullptr, 0.f, 0, 0};
-  return run_backward(p, B, P, nullptr, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, 0.f, beta, flags,
-                      out, loss_terms, nullptr, dparams, ws, ws_bytes, stream, &fio);
+  FilmIO fio;
+  fio.A = A; fio.film = film; fio.dA = dA; fio.dfilm = dfilm;
+  BwdCall c;
+  c.B = B; c.P = P; c.D = D; c.dbs = dbs; c.params = params;
+  c.target = target; c.ts = ts; c.weight = weight; c.wst = wst; c.loss_kind = loss_kind; c.beta = beta;
+  c.flags = flags; c.out = out; c.loss_terms = loss_terms; c.dparams = dparams;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream; c.fio = &fio;
+  return run_backward(p, c);
 }
 
 int reni_film_backward(const reni_plan* p, int64_t B, int64_t P, const float* D, int64_t dbs, const float* A,
                        const float* film, const float* params, const float* dout, uint32_t flags, float* dA,
                        float* dfilm, float* dparams, void* ws, size_t ws_bytes, void* stream) {
-  const FilmIO fio = {A, film, dA, dfilm, nullptr, 0.f, 0, 0};
-  return run_backward(p, B, P, nullptr, D, dbs, params, nullptr, nullptr, nullptr, nullptr, dout, 2, 0.f, 0.f, flags,
-                      nullptr, nullptr, nullptr, dparams, ws, ws_bytes, stream, &fio);
+  FilmIO fio;
+  fio.A = A; fio.film = film; fio.dA = dA; fio.dfilm = dfilm;
+  BwdCall c;
+  c.B = B; c.P = P; c.D = D; c.dbs = dbs; c.params = params;
+  c.dout = dout; c.loss_kind = LOSS_DOUT;
+  c.flags = flags; c.dparams = dparams;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream; c.fio = &fio;
+  return run_backward(p, c);
 }
 
 int reni_forward_loss_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const float* D,
@@ -1563,8 +1601,12 @@ int reni_forward_loss_backward(const reni_plan* p, int64_t B, int64_t P, const f
                                const float* weight, const int64_t wst[3], int32_t loss_kind, float alpha,
                                float beta, uint32_t flags, float* out, float* loss_terms, float* dZ,
                                float* dparams, void* ws, size_t ws_bytes, void* stream) {
-  return run_backward_chunked(p, B, P, Z, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, alpha, beta, flags,
-                              out, loss_terms, dZ, dparams, ws, ws_bytes, stream);
+  BwdCall c;
+  c.B = B; c.P = P; c.Z = Z; c.D = D; c.dbs = dbs; c.params = params;
+  c.target = target; c.ts = ts; c.weight = weight; c.wst = wst; c.loss_kind = loss_kind; c.alpha = alpha; c.beta = beta;
+  c.flags = flags; c.out = out; c.loss_terms = loss_terms; c.dZ = dZ; c.dparams = dparams;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  return run_backward_chunked(p, c);
 }
 
 int reni_forward_loss_backward_rows(const reni_plan* p, int64_t B, int64_t P, const float* Z_table, int64_t n_rows,
@@ -1575,8 +1617,51 @@ int reni_forward_loss_backward_rows(const reni_plan* p, int64_t B, int64_t P, co
   if (!idx) return fail(RENI_EINVAL, "idx is NULL");
   if (n_rows < 1) return fail(RENI_EINVAL, "n_rows=%lld must be >= 1", (long long)n_rows);
   if (p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use the reni_film_* entry points");
-  return run_backward_chunked(p, B, P, Z_table, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, alpha, beta, flags,
-                              out, loss_terms, dZ, dparams, ws, ws_bytes, stream, idx, n_rows);
+  BwdCall c;
+  c.B = B; c.P = P; c.Z = Z_table; c.idx = idx; c.n_rows = n_rows; c.D = D; c.dbs = dbs; c.params = params;
+  c.target = target; c.ts = ts; c.weight = weight; c.wst = wst; c.loss_kind = loss_kind; c.alpha = alpha; c.beta = beta;
+  c.flags = flags; c.out = out; c.loss_terms = loss_terms; c.dZ = dZ; c.dparams = dparams;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  return run_backward_chunked(p, c);
+}
+
+// reni_latent_step_rows (weight_lists == NULL: the lists are rebuilt by the call) and reni_latent_step_rows_cached
+static int latent_step_rows(const reni_plan* p, int64_t B, int64_t P, float* Z_table, int64_t n_rows, const int64_t* idx, const float* D,
+                            int64_t dbs, const float* params, const float* target, const int64_t ts[3], const float* weight,
+                            const int64_t wst[3], int32_t loss_kind, float alpha, float beta, uint32_t flags, const void* weight_lists,
+                            float* m_lat, float* v_lat, float lr, float b1, float b2, float eps, int64_t step, float* loss_terms,
+                            float* dZ, void* ws, size_t ws_bytes, void* stream) {
+  if (!idx) return fail(RENI_EINVAL, "idx is NULL");
+  if (n_rows < 1 || step < 1) return fail(RENI_EINVAL, "n_rows=%lld step=%lld", (long long)n_rows, (long long)step);
+  if (!m_lat || !v_lat || !dZ) return fail(RENI_EINVAL, "NULL optimiser state / output buffer");
+  if (p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use reni_film_model_forward_loss_backward + reni_adam_rows_step");
+  const uint32_t mode = flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT);
+  if (!weight_lists) {
+    if (flags & ~(uint32_t)(RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT)) return fail(RENI_EINVAL, "flags: RENI_WEIGHT_SPARSE / RENI_WEIGHT_COMPACT or 0");
+  } else {
+    if (!mode || (flags & ~(uint32_t)(RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT | RENI_WEIGHT_COS_CONSTANT)))
+      return fail(RENI_EINVAL, "flags: RENI_WEIGHT_SPARSE or RENI_WEIGHT_COMPACT (the mode the lists were built for) [| RENI_WEIGHT_COS_CONSTANT]");
+    if (((uintptr_t)weight_lists & 255) != 0) return fail(RENI_EINVAL, "weight_lists must be 256-byte aligned");
+    if (p && B >= 1 && P >= 1 && frag_chunk_images(p, B, P, flags | RENI_NEED_DZ) < B) return fail(RENI_EUNSUPPORTED, "chunked problems take reni_latent_step_rows");
+    // the lists must be the ones THIS library built for THIS shape and mode (their layout is a function of B and P)
+    ListRecord r{};
+    const int known = lists_check(weight_lists, B, P, mode, &r);
+    if (known == 1) return fail(RENI_EINVAL, "weight_lists: no reni_weight_lists_build is on record for this buffer");
+    if (known == 2) return fail(RENI_EINVAL, "weight_lists were built for B=%lld P=%lld mode=%u, this call has B=%lld P=%lld mode=%u",
+                                (long long)r.B, (long long)r.P, r.mode, (long long)B, (long long)P, mode);
+  }
+  // the frozen-decoder gradient call (the batch's rows are gathered into the workspace by its prologue: the table is free to move
+  // behind it), then the dense Adam step on the table -- the two calls this replaces, in their order, on the caller's stream
+  const WeightLists wl = {(const char*)weight_lists, flags};
+  BwdCall c;
+  c.B = B; c.P = P; c.Z = Z_table; c.idx = idx; c.n_rows = n_rows; c.D = D; c.dbs = dbs; c.params = params;
+  c.target = target; c.ts = ts; c.weight = weight; c.wst = wst; c.loss_kind = loss_kind; c.alpha = alpha; c.beta = beta;
+  c.flags = flags | RENI_NEED_DZ; c.loss_terms = loss_terms; c.dZ = dZ;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  if (weight_lists) c.lists = &wl;
+  const int rc = weight_lists ? run_backward(p, c) : run_backward_chunked(p, c);
+  if (rc) return rc;
+  return reni_adam_rows_step(Z_table, dZ, idx, B, (int64_t)p->d.ndims * 3, m_lat, v_lat, n_rows, lr, b1, b2, eps, step, 1.f, stream);
 }
 
 int reni_latent_step_rows(const reni_plan* p, int64_t B, int64_t P, float* Z_table, int64_t n_rows, const int64_t* idx, const float* D,
@@ -1584,17 +1669,18 @@ int reni_latent_step_rows(const reni_plan* p, int64_t B, int64_t P, float* Z_tab
                           const int64_t wst[3], int32_t loss_kind, float alpha, float beta, uint32_t flags, float* m_lat, float* v_lat,
                           float lr, float b1, float b2, float eps, int64_t step, float* loss_terms, float* dZ, void* ws, size_t ws_bytes,
                           void* stream) {
-  if (!idx) return fail(RENI_EINVAL, "idx is NULL");
-  if (n_rows < 1 || step < 1) return fail(RENI_EINVAL, "n_rows=%lld step=%lld", (long long)n_rows, (long long)step);
-  if (!m_lat || !v_lat || !dZ) return fail(RENI_EINVAL, "NULL optimiser state / output buffer");
-  if (p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use reni_film_model_forward_loss_backward + reni_adam_rows_step");
-  if (flags & ~(uint32_t)(RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT)) return fail(RENI_EINVAL, "flags: RENI_WEIGHT_SPARSE / RENI_WEIGHT_COMPACT or 0");
-  // the frozen-decoder gradient call (the batch's rows are gathered into the workspace by its prologue: the table is free to move
-  // behind it), then the dense Adam step on the table -- the two calls this replaces, in their order, on the caller's stream
-  int rc = run_backward_chunked(p, B, P, Z_table, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, alpha, beta,
-                                flags | RENI_NEED_DZ, nullptr, loss_terms, dZ, nullptr, ws, ws_bytes, stream, idx, n_rows);
-  if (rc) return rc;
-  return reni_adam_rows_step(Z_table, dZ, idx, B, (int64_t)p->d.ndims * 3, m_lat, v_lat, n_rows, lr, b1, b2, eps, step, 1.f, stream);
+  return latent_step_rows(p, B, P, Z_table, n_rows, idx, D, dbs, params, target, ts, weight, wst, loss_kind, alpha, beta, flags, nullptr,
+                          m_lat, v_lat, lr, b1, b2, eps, step, loss_terms, dZ, ws, ws_bytes, stream);
+}
+
+int reni_latent_step_rows_cached(const reni_plan* p, int64_t B, int64_t P, float* Z_table, int64_t n_rows, const int64_t* idx,
+                                 const float* D, int64_t dbs, const float* params, const float* target, const int64_t ts[3],
+                                 const float* weight, const int64_t wst[3], int32_t loss_kind, float alpha, float beta, uint32_t flags,
+                                 const void* weight_lists, float* m_lat, float* v_lat, float lr, float b1, float b2, float eps,
+                                 int64_t step, float* loss_terms, float* dZ, void* ws, size_t ws_bytes, void* stream) {
+  if (!weight_lists) return fail(RENI_EINVAL, "weight_lists is NULL (reni_weight_lists_build; without lists: reni_latent_step_rows)");
+  return latent_step_rows(p, B, P, Z_table, n_rows, idx, D, dbs, params, target, ts, weight, wst, loss_kind, alpha, beta, flags, weight_lists,
+                          m_lat, v_lat, lr, b1, b2, eps, step, loss_terms, dZ, ws, ws_bytes, stream);
 }
 
 size_t reni_weight_lists_bytes(int64_t B, int64_t P) {
@@ -1616,32 +1702,19 @@ int reni_weight_lists_build(int64_t B, int64_t P, const float* weight, const int
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   char* lb = (char*)lists;
-  const bool compact = (flags & RENI_WEIGHT_COMPACT) != 0;
-  const int tpi = (int)((P + 127) / 128), n_tiles = (int)(B * tpi);
-  int* tflag = (int*)(lb + ll.o_tflag);
-  int* imgcos = (int*)(lb + ll.o_imgcos);
-  int* tl = (int*)(lb + ll.o_tlist);
-  int* tc = (int*)(lb + ll.o_tcount);
-  RENI_LAUNCH(reni::k_tile_flags, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, weight, (long long)wst[0], (long long)wst[1],
-              (long long)wst[2], (int)P, tpi, n_tiles, tflag, imgcos, compact ? (int*)(lb + ll.o_pcnt) : (int*)nullptr);
-  HIP_TRY(hipGetLastError());
-  RENI_LAUNCH(reni::k_tile_compact, dim3(1), dim3(1024), 0, s, tflag, (const int*)imgcos, tpi, n_tiles, tl, tl + n_tiles, tc,
-              compact ? (const int*)(lb + ll.o_pcnt) : (const int*)nullptr, (int)P, (int*)(lb + ll.o_pscan), (int*)(lb + ll.o_nlive));
-  HIP_TRY(hipGetLastError());
-  if (compact) {
-    RENI_LAUNCH(reni::k_pix_scatter, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, weight, (long long)wst[0], (long long)wst[1],
-                (long long)wst[2], (int)P, tpi, n_tiles, (const int*)imgcos, (const int*)(lb + ll.o_pscan), (int*)(lb + ll.o_plist));
-    HIP_TRY(hipGetLastError());
-  }
+  const int tpi = (int)((P + 127) / 128);
+  const ListDst ld = list_dst(lb, ll);
+  rc = build_weight_lists(weight, wst, P, tpi, (int)(B * tpi), (flags & RENI_WEIGHT_COMPACT) != 0, ld, s);
+  if (rc) return rc;
   const long long hdr[4] = {(long long)B, (long long)P, (long long)(flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT)), LIST_MAGIC};
   HIP_TRY(hipMemcpyAsync(lb + ll.o_hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
   lists_remember(lists, B, P, flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT));
   HIP_TRY(hipMemsetAsync(lb + ll.o_zstats, 0, (size_t)B * 16 * 4, s));
   if (summary_host) {  // (one synchronisation, once per mask: what the lists hold -- the caller may then set RENI_WEIGHT_COS_CONSTANT)
     int cnt[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(cnt, tc, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cnt, ld.tcount, sizeof(cnt), hipMemcpyDeviceToHost, s));
     std::vector<int> ic((size_t)B);
-    HIP_TRY(hipMemcpyAsync(ic.data(), imgcos, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ic.data(), ld.imgcos, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     int live = 0;
     for (int64_t b = 0; b < B; ++b) live += ic[(size_t)b] != 0;
@@ -1650,33 +1723,44 @@ int reni_weight_lists_build(int64_t B, int64_t P, const float* weight, const int
   return RENI_OK;
 }
 
-int reni_latent_step_rows_cached(const reni_plan* p, int64_t B, int64_t P, float* Z_table, int64_t n_rows, const int64_t* idx,
-                                 const float* D, int64_t dbs, const float* params, const float* target, const int64_t ts[3],
-                                 const float* weight, const int64_t wst[3], int32_t loss_kind, float alpha, float beta, uint32_t flags,
-                                 const void* weight_lists, float* m_lat, float* v_lat, float lr, float b1, float b2, float eps,
-                                 int64_t step, float* loss_terms, float* dZ, void* ws, size_t ws_bytes, void* stream) {
-  if (!weight_lists) return fail(RENI_EINVAL, "weight_lists is NULL (reni_weight_lists_build; without lists: reni_latent_step_rows)");
+// reni_train_step_rows (comm == NULL: the single-process step) and reni_train_step_rows_dp
+static int train_step_rows(const reni_plan* p, int64_t B, int64_t P, float* Z_table, int64_t n_rows, const int64_t* idx,
+                           const int64_t* idx_next, const float* D, int64_t dbs, float* params, const float* target,
+                           const int64_t ts[3], const float* weight, const int64_t wst[3], int32_t loss_kind, float alpha, float beta,
+                           float* m_dec, float* v_dec, float* m_lat, float* v_lat, float lr, float b1, float b2, float eps,
+                           int64_t step, float grad_scale, void* comm, int32_t overlap, uint32_t* stage_state, float* loss_terms,
+                           float* dZ, float* dparams, void* ws, size_t ws_bytes, void* stream) {
   if (!idx) return fail(RENI_EINVAL, "idx is NULL");
   if (n_rows < 1 || step < 1) return fail(RENI_EINVAL, "n_rows=%lld step=%lld", (long long)n_rows, (long long)step);
-  if (!m_lat || !v_lat || !dZ) return fail(RENI_EINVAL, "NULL optimiser state / output buffer");
-  if (p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use reni_film_model_forward_loss_backward + reni_adam_rows_step");
-  if (!(flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT)) || (flags & ~(uint32_t)(RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT | RENI_WEIGHT_COS_CONSTANT)))
-    return fail(RENI_EINVAL, "flags: RENI_WEIGHT_SPARSE or RENI_WEIGHT_COMPACT (the mode the lists were built for) [| RENI_WEIGHT_COS_CONSTANT]");
-  if (((uintptr_t)weight_lists & 255) != 0) return fail(RENI_EINVAL, "weight_lists must be 256-byte aligned");
-  if (p && B >= 1 && P >= 1 && frag_chunk_images(p, B, P, flags | RENI_NEED_DZ) < B) return fail(RENI_EUNSUPPORTED, "chunked problems take reni_latent_step_rows");
-  {  // the lists must be the ones THIS library built for THIS shape and mode (their layout is a function of B and P)
-    ListRecord r{};
-    const int c = lists_check(weight_lists, B, P, flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT), &r);
-    if (c == 1) return fail(RENI_EINVAL, "weight_lists: no reni_weight_lists_build is on record for this buffer");
-    if (c == 2) return fail(RENI_EINVAL, "weight_lists were built for B=%lld P=%lld mode=%u, this call has B=%lld P=%lld mode=%u",
-                            (long long)r.B, (long long)r.P, r.mode, (long long)B, (long long)P,
-                            flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT));
+  if (!m_dec || !v_dec || !m_lat || !v_lat || !stage_state || !dZ || !dparams) return fail(RENI_EINVAL, "NULL optimiser state / output buffer");
+  if (p && p->d.conditioning != RENI_COND_CONCAT)
+    return fail(RENI_EINVAL, "FiLM plan: use reni_film_model_forward_loss_backward + %sreni_adam_step", comm ? "reni_allreduce_grads + " : "");
+  if (loss_kind != RENI_LOSS_MSE && loss_kind != RENI_LOSS_TEST) return fail(RENI_EINVAL, "unknown loss_kind %d", loss_kind);
+  StepFuse f;
+  f.comm = comm; f.overlap = overlap ? 1 : 0;
+  f.params = params; f.table = Z_table; f.m_dec = m_dec; f.v_dec = v_dec; f.m_lat = m_lat; f.v_lat = v_lat;
+  f.lr = lr; f.b1 = b1; f.b2 = b2; f.eps = eps; f.gscale = grad_scale;
+  f.bc1 = (float)(1.0 - std::pow((double)b1, (double)step));
+  f.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)b2, (double)step));
+  f.idx_next = idx_next; f.state = stage_state;
+  BwdCall c;
+  c.B = B; c.P = P; c.Z = Z_table; c.idx = idx; c.n_rows = n_rows; c.D = D; c.dbs = dbs; c.params = params;
+  c.target = target; c.ts = ts; c.weight = weight; c.wst = wst; c.loss_kind = loss_kind; c.alpha = alpha; c.beta = beta;
+  c.flags = RENI_NEED_DW | RENI_NEED_DZ; c.loss_terms = loss_terms; c.dZ = dZ; c.dparams = dparams;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  if (p && B >= 1 && P >= 1 && frag_chunk_images(p, B, P, c.flags) < B) {
+    // H = 256 in image chunks: the chunks' gradients are summed first, then ONE exchange (with a communicator) and ONE optimiser step;
+    // nothing is staged
+    *stage_state = 0;
+    int rc = run_backward_chunked(p, c);
+    if (rc) return rc;
+    if (comm) rc = reni_allreduce_grads(comm, dparams, (size_t)p->n_params, 1.f, stream);
+    if (rc) return rc;
+    return reni_adam_step2(params, dparams, m_dec, v_dec, p->n_params, Z_table, dZ, idx, B, (int64_t)p->d.ndims * 3, m_lat, v_lat,
+                           n_rows, lr, b1, b2, eps, step, grad_scale, stream);
   }
-  const WeightLists wl = {(const char*)weight_lists, flags};
-  int rc = run_backward(p, B, P, Z_table, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, alpha, beta,
-                        flags | RENI_NEED_DZ, nullptr, loss_terms, dZ, nullptr, ws, ws_bytes, stream, nullptr, idx, n_rows, nullptr, &wl);
-  if (rc) return rc;
-  return reni_adam_rows_step(Z_table, dZ, idx, B, (int64_t)p->d.ndims * 3, m_lat, v_lat, n_rows, lr, b1, b2, eps, step, 1.f, stream);
+  c.fuse = &f;
+  return run_backward(p, c);
 }
 
 int reni_train_step_rows(const reni_plan* p, int64_t B, int64_t P, float* Z_table, int64_t n_rows, const int64_t* idx,
@@ -1685,29 +1769,8 @@ int reni_train_step_rows(const reni_plan* p, int64_t B, int64_t P, float* Z_tabl
                          float* m_dec, float* v_dec, float* m_lat, float* v_lat, float lr, float b1, float b2, float eps,
                          int64_t step, float grad_scale, uint32_t* stage_state, float* loss_terms, float* dZ, float* dparams,
                          void* ws, size_t ws_bytes, void* stream) {
-  if (!idx) return fail(RENI_EINVAL, "idx is NULL");
-  if (n_rows < 1 || step < 1) return fail(RENI_EINVAL, "n_rows=%lld step=%lld", (long long)n_rows, (long long)step);
-  if (!m_dec || !v_dec || !m_lat || !v_lat || !stage_state || !dZ || !dparams) return fail(RENI_EINVAL, "NULL optimiser state / output buffer");
-  if (p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use reni_film_model_forward_loss_backward + reni_adam_step");
-  if (loss_kind != RENI_LOSS_MSE && loss_kind != RENI_LOSS_TEST) return fail(RENI_EINVAL, "unknown loss_kind %d", loss_kind);
-  StepFuse f;
-  f.params = params; f.table = Z_table; f.m_dec = m_dec; f.v_dec = v_dec; f.m_lat = m_lat; f.v_lat = v_lat;
-  f.lr = lr; f.b1 = b1; f.b2 = b2; f.eps = eps; f.gscale = grad_scale;
-  f.bc1 = (float)(1.0 - std::pow((double)b1, (double)step));
-  f.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)b2, (double)step));
-  f.idx_next = idx_next; f.state = stage_state;
-  const uint32_t flags = RENI_NEED_DW | RENI_NEED_DZ;
-  if (p && B >= 1 && P >= 1 && frag_chunk_images(p, B, P, flags) < B) {
-    // H = 256 in image chunks: the chunks' gradients are summed first, then ONE optimiser step; nothing is staged
-    *stage_state = 0;
-    int rc = run_backward_chunked(p, B, P, Z_table, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, alpha, beta, flags,
-                                  nullptr, loss_terms, dZ, dparams, ws, ws_bytes, stream, idx, n_rows);
-    if (rc) return rc;
-    return reni_adam_step2(params, dparams, m_dec, v_dec, p->n_params, Z_table, dZ, idx, B, (int64_t)p->d.ndims * 3, m_lat, v_lat,
-                           n_rows, lr, b1, b2, eps, step, grad_scale, stream);
-  }
-  return run_backward(p, B, P, Z_table, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, alpha, beta, flags, nullptr,
-                      loss_terms, dZ, dparams, ws, ws_bytes, stream, nullptr, idx, n_rows, &f);
+  return train_step_rows(p, B, P, Z_table, n_rows, idx, idx_next, D, dbs, params, target, ts, weight, wst, loss_kind, alpha, beta, m_dec, v_dec,
+                         m_lat, v_lat, lr, b1, b2, eps, step, grad_scale, nullptr, 0, stage_state, loss_terms, dZ, dparams, ws, ws_bytes, stream);
 }
 
 int reni_train_step_rows_dp(const reni_plan* p, int64_t B, int64_t P, float* Z_table, int64_t n_rows, const int64_t* idx,
@@ -1717,39 +1780,19 @@ int reni_train_step_rows_dp(const reni_plan* p, int64_t B, int64_t P, float* Z_t
                             int64_t step, float grad_scale, void* comm, int32_t overlap, uint32_t* stage_state, float* loss_terms,
                             float* dZ, float* dparams, void* ws, size_t ws_bytes, void* stream) {
   if (!comm) return fail(RENI_EINVAL, "comm is NULL (reni_rccl_comm_create; one process: reni_train_step_rows)");
-  if (!idx) return fail(RENI_EINVAL, "idx is NULL");
-  if (n_rows < 1 || step < 1) return fail(RENI_EINVAL, "n_rows=%lld step=%lld", (long long)n_rows, (long long)step);
-  if (!m_dec || !v_dec || !m_lat || !v_lat || !stage_state || !dZ || !dparams) return fail(RENI_EINVAL, "NULL optimiser state / output buffer");
-  if (p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use reni_film_model_forward_loss_backward + reni_allreduce_grads + reni_adam_step");
-  if (loss_kind != RENI_LOSS_MSE && loss_kind != RENI_LOSS_TEST) return fail(RENI_EINVAL, "unknown loss_kind %d", loss_kind);
-  StepFuse f;
-  f.comm = comm; f.overlap = overlap ? 1 : 0;
-  f.params = params; f.table = Z_table; f.m_dec = m_dec; f.v_dec = v_dec; f.m_lat = m_lat; f.v_lat = v_lat;
-  f.lr = lr; f.b1 = b1; f.b2 = b2; f.eps = eps; f.gscale = grad_scale;
-  f.bc1 = (float)(1.0 - std::pow((double)b1, (double)step));
-  f.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)b2, (double)step));
-  f.idx_next = idx_next; f.state = stage_state;
-  const uint32_t flags = RENI_NEED_DW | RENI_NEED_DZ;
-  if (p && B >= 1 && P >= 1 && frag_chunk_images(p, B, P, flags) < B) {
-    // H = 256 in image chunks: the chunks' gradients are summed first, then ONE exchange and ONE optimiser step; nothing is staged
-    *stage_state = 0;
-    int rc = run_backward_chunked(p, B, P, Z_table, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, alpha, beta, flags,
-                                  nullptr, loss_terms, dZ, dparams, ws, ws_bytes, stream, idx, n_rows);
-    if (rc) return rc;
-    rc = reni_allreduce_grads(comm, dparams, (size_t)p->n_params, 1.f, stream);
-    if (rc) return rc;
-    return reni_adam_step2(params, dparams, m_dec, v_dec, p->n_params, Z_table, dZ, idx, B, (int64_t)p->d.ndims * 3, m_lat, v_lat,
-                           n_rows, lr, b1, b2, eps, step, grad_scale, stream);
-  }
-  return run_backward(p, B, P, Z_table, D, dbs, params, target, ts, weight, wst, nullptr, loss_kind, alpha, beta, flags, nullptr,
-                      loss_terms, dZ, dparams, ws, ws_bytes, stream, nullptr, idx, n_rows, &f);
+  return train_step_rows(p, B, P, Z_table, n_rows, idx, idx_next, D, dbs, params, target, ts, weight, wst, loss_kind, alpha, beta, m_dec, v_dec,
+                         m_lat, v_lat, lr, b1, b2, eps, step, grad_scale, comm, overlap, stage_state, loss_terms, dZ, dparams, ws, ws_bytes, stream);
 }
 
 int reni_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const float* D, int64_t dbs,
                   const float* params, const float* dout, uint32_t flags, float* dZ, float* dparams, void* ws,
                   size_t ws_bytes, void* stream) {
-  return run_backward_chunked(p, B, P, Z, D, dbs, params, nullptr, nullptr, nullptr, nullptr, dout, 2, 0.f, 0.f, flags,
-                              nullptr, nullptr, dZ, dparams, ws, ws_bytes, stream);
+  BwdCall c;
+  c.B = B; c.P = P; c.Z = Z; c.D = D; c.dbs = dbs; c.params = params;
+  c.dout = dout; c.loss_kind = LOSS_DOUT;
+  c.flags = flags; c.dZ = dZ; c.dparams = dparams;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  return run_backward_chunked(p, c);
 }
 
 int64_t reni_film_map_param_count(const reni_plan* p) { return p ? p->n_map_params : 0; }
@@ -1772,7 +1815,8 @@ int reni_film_model_forward(const reni_plan* p, int64_t B, int64_t P, const floa
   fill_glue(g, p, gl, B, Z, params, mparams, gw);
   rc = run_film_glue_fwd(g, (hipStream_t)stream);
   if (rc) return rc;
-  const FilmIO fio = {g.A, g.film, nullptr, nullptr, nullptr, 0.f, 0, 0};
+  FilmIO fio;
+  fio.A = g.A; fio.film = g.film;
   return forward_impl(p, B, P, nullptr, D, dbs, params, out, ws_v, core, stream, &fio);
 }
 
@@ -1782,15 +1826,23 @@ int reni_film_model_forward_loss_backward(const reni_plan* p, int64_t B, int64_t
                                           int32_t loss_kind, float alpha, float beta, uint32_t flags, float* out,
                                           float* loss_terms, float* dZ, float* dparams, float* dmparams, void* ws,
                                           size_t ws_bytes, void* stream) {
-  return film_model_backward(p, B, P, Z, D, dbs, params, mparams, target, ts, weight, wst, nullptr, loss_kind, alpha, beta,
-                             flags, out, loss_terms, dZ, dparams, dmparams, ws, ws_bytes, stream);
+  BwdCall c;
+  c.B = B; c.P = P; c.Z = Z; c.D = D; c.dbs = dbs; c.params = params;
+  c.target = target; c.ts = ts; c.weight = weight; c.wst = wst; c.loss_kind = loss_kind; c.alpha = alpha; c.beta = beta;
+  c.flags = flags; c.out = out; c.loss_terms = loss_terms; c.dZ = dZ; c.dparams = dparams;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  return film_model_backward(p, c, mparams, dmparams);
 }
 
 int reni_film_model_backward(const reni_plan* p, int64_t B, int64_t P, const float* Z, const float* D, int64_t dbs,
                              const float* params, const float* mparams, const float* dout, uint32_t flags, float* dZ,
                              float* dparams, float* dmparams, void* ws, size_t ws_bytes, void* stream) {
-  return film_model_backward(p, B, P, Z, D, dbs, params, mparams, nullptr, nullptr, nullptr, nullptr, dout, 2, 0.f, 0.f,
-                             flags, nullptr, nullptr, dZ, dparams, dmparams, ws, ws_bytes, stream);
+  BwdCall c;
+  c.B = B; c.P = P; c.Z = Z; c.D = D; c.dbs = dbs; c.params = params;
+  c.dout = dout; c.loss_kind = LOSS_DOUT;
+  c.flags = flags; c.dZ = dZ; c.dparams = dparams;
+  c.ws = ws; c.ws_bytes = ws_bytes; c.stream = stream;
+  return film_model_backward(p, c, mparams, dmparams);
 }
 
 int reni_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,

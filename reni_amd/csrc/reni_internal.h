@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/reni_hip.h"
+
 namespace reni {
 
 constexpr int MAX_LAYERS = 15;  // hidden_layers <= MAX_LAYERS - 1
@@ -87,6 +89,11 @@ struct MainArgs {
 
 // sets reni_last_error()'s thread-local message and returns `code` (defined next to the C ABI, reni_capi.inc)
 int reni_set_error(int code, const char* msg);
+// the launches issued so far on this thread: hipGetLastError() as a RENI_* code, its text as reni_last_error()'s message
+inline int hip_status() {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? reni_set_error(RENI_EHIP, hipGetErrorString(e)) : RENI_OK;
+}
 
 // host launchers of the fused kernel, one per translation unit (reni_device.inc)
 hipError_t launch_main_f32(int H, int mode, const MainArgs& a, int nwg, hipStream_t s);

@@ -320,14 +320,10 @@ __global__ void __launch_bounds__(64) k_sh_reconstruct(const ShArgs a) {
 
 namespace {
 
+using reni::hip_status;
 using reni::reni_set_error;
 constexpr int64_t BL_MAX_ELEMS = 0x3fffffff;
 constexpr int64_t SH_MAX_W = 4096;  // keeps the reconstruction grid's y extent (H W / 128) under 65536
-
-int hip_status() {
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? reni_set_error(RENI_EHIP, hipGetErrorString(e)) : RENI_OK;
-}
 
 bool sg_shape_ok(int64_t N, int64_t K, int64_t H, int64_t W) {
   return N >= 1 && K >= 1 && K <= reni::SG_MAX_K && H >= 1 && W >= 1 && H <= BL_MAX_ELEMS / W &&

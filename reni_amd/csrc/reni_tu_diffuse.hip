@@ -186,15 +186,11 @@ __global__ void __launch_bounds__(256) k_sh_irradiance_l2(int64_t N, int64_t P, 
 
 namespace {
 
+using reni::hip_status;
 using reni::reni_set_error;
 constexpr int64_t DF_MAX_ELEMS = 0x3fffffff;
 constexpr int64_t DF_MIN_CHUNK = 2048;  // fewest i per split
 constexpr int64_t DF_TARGET_WGS = 256;  // workgroups per column group the split aims for (one per CU)
-
-int hip_status() {
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? reni_set_error(RENI_EHIP, hipGetErrorString(e)) : RENI_OK;
-}
 
 bool df_shape_ok(int64_t N, int64_t P, int64_t Q) {
   return N >= 1 && P >= 1 && Q >= 1 && P <= DF_MAX_ELEMS / 3 && Q <= DF_MAX_ELEMS / 3 && N <= DF_MAX_ELEMS / (3 * P) &&

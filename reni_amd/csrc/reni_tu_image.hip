@@ -251,9 +251,7 @@ int reni_unnormalise_srgb(int64_t B, int64_t H, int64_t W, const float* img, con
     const long long n = npix * 3;
     hipLaunchKernelGGL(reni::k_img_pass2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return reni_set_error(RENI_EHIP, hipGetErrorString(e));
-  return RENI_OK;
+  return reni::hip_status();
 }
 
 int reni_minmax_normalise(int64_t n, const float* img, double minmax0, double minmax1, float* out, void* ws, size_t ws_bytes,
@@ -269,9 +267,7 @@ int reni_minmax_normalise(int64_t n, const float* img, double minmax0, double mi
   hipLaunchKernelGGL(reni::k_img_minmax, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s, img, (long long)n, mm);
   hipLaunchKernelGGL(reni::k_img_normalise, dim3((unsigned)nb), dim3(256), 0, s, img, (long long)n, (const unsigned*)mm, (float)minmax0,
                      (float)(minmax1 - minmax0), out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return reni_set_error(RENI_EHIP, hipGetErrorString(e));
-  return RENI_OK;
+  return reni::hip_status();
 }
 
 size_t reni_minmax_batch_workspace_bytes(int64_t N) { return N < 1 || N > 65535 ? 0 : (size_t)N * 8 + 256; }
@@ -290,9 +286,7 @@ int reni_minmax_normalise_batch(int64_t N, int64_t n, const float* imgs, double 
   hipLaunchKernelGGL(reni::k_img_minmax_batch, dim3((unsigned)(nb < 128 ? nb : 128), (unsigned)N), dim3(256), 0, s, imgs, (long long)n, mm);
   hipLaunchKernelGGL(reni::k_img_normalise_batch, dim3((unsigned)nb, (unsigned)N), dim3(256), 0, s, imgs, (long long)n,
                      (const unsigned*)mm, (float)minmax0, (float)(minmax1 - minmax0), nan_to_num ? 1 : 0, out);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return reni_set_error(RENI_EHIP, hipGetErrorString(e));
-  return RENI_OK;
+  return reni::hip_status();
 }
 
 }  // extern "C"

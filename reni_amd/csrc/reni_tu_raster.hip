@@ -234,13 +234,9 @@ __global__ void __launch_bounds__(256) k_raster_tile(const RasterArgs a) {
 
 namespace {
 
+using reni::hip_status;
 using reni::reni_set_error;
 constexpr int64_t RS_MAX_ELEMS = 0x3fffffff;  // V, F; S * S
-
-int hip_status() {
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? reni_set_error(RENI_EHIP, hipGetErrorString(e)) : RENI_OK;
-}
 
 }  // namespace
 

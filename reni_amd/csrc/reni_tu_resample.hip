@@ -103,14 +103,10 @@ __global__ void __launch_bounds__(256) k_blur_axis(const float* __restrict__ in,
 
 namespace {
 
+using reni::hip_status;
 using reni::reni_set_error;
 constexpr int64_t RS_MAX_PIXELS = 0x3fffffff;
 constexpr int64_t RS_MAX_RADIUS = 1 << 20;
-
-int hip_status() {
-  hipError_t e = hipGetLastError();
-  return e != hipSuccess ? reni_set_error(RENI_EHIP, hipGetErrorString(e)) : RENI_OK;
-}
 
 bool blur_shape_ok(int64_t C, int64_t H, int64_t W) {
   return C >= 1 && C <= 65535 && H >= 1 && W >= 1 && H <= RS_MAX_PIXELS / W && C <= RS_MAX_PIXELS / (H * W);

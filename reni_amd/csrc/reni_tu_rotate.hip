@@ -144,6 +144,5 @@ extern "C" int reni_rotate_envmap(int64_t B, int64_t C, int64_t H, int64_t W, co
   hipStream_t s = (hipStream_t)stream;
   if (mode == RENI_ROTATE_BILINEAR) hipLaunchKernelGGL(reni::k_rotate_envmap<true>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(reni::k_rotate_envmap<false>, grid, dim3(256), 0, s, a);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? reni_set_error(RENI_EHIP, hipGetErrorString(e)) : RENI_OK;
+  return reni::hip_status();
 }

@@ -203,14 +203,12 @@ int shade_common(bool forward, int64_t B, int64_t NP, int64_t J, const float* no
       if (forward) hipLaunchKernelGGL((reni::k_envmap_shade<true, SHADE_BC>), grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL((reni::k_envmap_shade<false, SHADE_BC>), grid, dim3(256), 0, s, a);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return reni_set_error(RENI_EHIP, hipGetErrorString(e));
+    if (int rc = reni::hip_status()) return rc;
   }
   if (S > 1) {
     const size_t n = (size_t)B * n_own * 3;
     hipLaunchKernelGGL(reni::k_shade_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)ws, n, S, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return reni_set_error(RENI_EHIP, hipGetErrorString(e));
+    if (int rc = reni::hip_status()) return rc;
   }
   return RENI_OK;
 }

@@ -25,6 +25,25 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+def _loss_views(target, weight, B, P):
+    """target / weight as float32 [B,P,3] views (stride 0 broadcasts: nothing is materialised) and their stride arrays."""
+    target = (target if target.dtype == torch.float32 else target.float()).expand(B, P, 3)
+    weight = (weight if weight.dtype == torch.float32 else weight.float()).expand(B, P, 3)
+    return target, weight, (ctypes.c_int64 * 3)(*target.stride()), (ctypes.c_int64 * 3)(*weight.stride())
+
+
+def _sparse_flags(sparse_weight):
+    if sparse_weight not in (False, True, None, "tiles", "pixels"):
+        raise ValueError('sparse_weight must be False, True / "tiles", or "pixels"')
+    return _lib.WEIGHT_COMPACT if sparse_weight == "pixels" else _lib.WEIGHT_SPARSE if sparse_weight else 0
+
+
+def _call(fn, device, *args):
+    """fn(*args, stream) with `device` current and its current stream as the last argument; raises on a library error."""
+    with torch.cuda.device(device):
+        _lib.check(fn(*args, torch.cuda.current_stream(device).cuda_stream))
+
+
 class Plan:
     """Immutable kernel plan for one decoder architecture (reni_plan_create)."""
 
@@ -87,6 +106,11 @@ class Plan:
         ap = (p + 255) & ~255
         return ap, ws.numel() - (ap - p)
 
+    def _ws_args(self, B, P, flags, device):
+        """(aligned workspace pointer, bytes behind it, current stream) of one call -- through workspace(): every hand-out counts."""
+        wp, wn = self._aligned_ptr(self.workspace(B, P, flags, device))
+        return wp, wn, torch.cuda.current_stream(device).cuda_stream
+
     def launch_info(self, B: int, P: int):
         info = (ctypes.c_int32 * 4)()
         _lib.check(self.lib.reni_launch_info(self._h, B, P, info))
@@ -133,9 +157,7 @@ class Plan:
         self._check_zp(Z, params)
         B, P, Dc, dbs = self._grid_args(Z, D)
         out = torch.empty(B, P, 3, dtype=torch.float32, device=Z.device)
-        ws = self.workspace(B, P, 0, Z.device)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(Z.device).cuda_stream
+        wp, wn, stream = self._ws_args(B, P, 0, Z.device)
         _lib.check(self.lib.reni_forward(self._h, B, P, Z.data_ptr(), Dc.data_ptr(), dbs, params.data_ptr(),
                                          out.data_ptr(), wp, wn, stream))
         return out
@@ -161,27 +183,15 @@ class Plan:
             B, P, Dc, dbs = self._grid_args(Z[:1].expand(idx.numel(), -1, -1), D)  # (the batch's shape; Z stays the table)
         else:
             B, P, Dc, dbs = self._grid_args(Z, D)
-        if target.dtype != torch.float32:
-            target = target.float()
-        if weight.dtype != torch.float32:
-            weight = weight.float()
-        target = target.expand(B, P, 3)
-        weight = weight.expand(B, P, 3)
-        ts = (ctypes.c_int64 * 3)(*target.stride())
-        wst = (ctypes.c_int64 * 3)(*weight.stride())
-        if sparse_weight not in (False, True, None, "tiles", "pixels"):
-            raise ValueError('sparse_weight must be False, True / "tiles", or "pixels"')
-        flags = ((_lib.NEED_DW if need_dw else 0) | (_lib.NEED_DZ if need_dz else 0)
-                 | (_lib.WEIGHT_COMPACT if sparse_weight == "pixels" else _lib.WEIGHT_SPARSE if sparse_weight else 0))
+        target, weight, ts, wst = _loss_views(target, weight, B, P)
+        flags = (_lib.NEED_DW if need_dw else 0) | (_lib.NEED_DZ if need_dz else 0) | _sparse_flags(sparse_weight)
         dev = Z.device
         loss_terms = torch.empty(4, dtype=torch.float32, device=dev)
         dZ = torch.empty(B, self.ndims, 3, dtype=torch.float32, device=dev) if need_dz else None
         dparams = torch.empty(self.n_params, dtype=torch.float32, device=dev) if need_dw else None
         out = torch.empty(B, P, 3, dtype=torch.float32, device=dev) if want_out else None
-        ws = self.workspace(B, P, flags, dev)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        kind = {"mse": _lib.LOSS_MSE, "test": _lib.LOSS_TEST}[loss_kind]
+        wp, wn, stream = self._ws_args(B, P, flags, dev)
+        kind = _lib.LOSS_KIND[loss_kind]
         tail = (Dc.data_ptr(), dbs, params.data_ptr(), target.data_ptr(), ts, weight.data_ptr(), wst, kind, float(alpha),
                 float(beta), flags, out.data_ptr() if out is not None else None, loss_terms.data_ptr(),
                 dZ.data_ptr() if dZ is not None else None, dparams.data_ptr() if dparams is not None else None, wp, wn, stream)
@@ -209,10 +219,7 @@ class Plan:
             if ix is not None and (ix.dtype != torch.int64 or ix.dim() != 1 or ix.numel() != idx.numel() or not ix.is_contiguous()):
                 raise ValueError("idx / idx_next must be contiguous 1-D int64 tensors of the same length")
         B, P, Dc, dbs = self._grid_args(Z_table[:1].expand(idx.numel(), -1, -1), D)
-        target = (target if target.dtype == torch.float32 else target.float()).expand(B, P, 3)
-        weight = (weight if weight.dtype == torch.float32 else weight.float()).expand(B, P, 3)
-        ts = (ctypes.c_int64 * 3)(*target.stride())
-        wst = (ctypes.c_int64 * 3)(*weight.stride())
+        target, weight, ts, wst = _loss_views(target, weight, B, P)
         dev = Z_table.device
         loss_terms = torch.empty(4, dtype=torch.float32, device=dev)
         dZ = torch.empty(B, self.ndims, 3, dtype=torch.float32, device=dev)
@@ -220,16 +227,14 @@ class Plan:
         # a staged prologue is only good if NOTHING took the plan's workspace since the call that staged it (see workspace())
         if stage_state.value & 1 and getattr(self, "_stage_gen", None) != (getattr(self, "_ws_gen", 0), dev.index):
             stage_state.value = 0
-        ws = self.workspace(B, P, _lib.NEED_DW | _lib.NEED_DZ, dev)
+        wp, wn, stream = self._ws_args(B, P, _lib.NEED_DW | _lib.NEED_DZ, dev)
         self._stage_gen = (self._ws_gen, dev.index)
-        wp, wn = self._aligned_ptr(ws)
-        kind = {"mse": _lib.LOSS_MSE, "test": _lib.LOSS_TEST}[loss_kind]
+        kind = _lib.LOSS_KIND[loss_kind]
         head = (self._h, B, P, Z_table.data_ptr(), Z_table.shape[0], idx.data_ptr(), idx_next.data_ptr() if idx_next is not None else None,
                 Dc.data_ptr(), dbs, params.data_ptr(), target.data_ptr(), ts, weight.data_ptr(), wst, kind, float(alpha), float(beta),
                 m_dec.data_ptr(), v_dec.data_ptr(), m_lat.data_ptr(), v_lat.data_ptr(), float(lr), float(betas[0]), float(betas[1]),
                 float(eps), int(step), float(grad_scale))
-        tail = (ctypes.byref(stage_state), loss_terms.data_ptr(), dZ.data_ptr(), dparams.data_ptr(), wp, wn,
-                torch.cuda.current_stream(dev).cuda_stream)
+        tail = (ctypes.byref(stage_state), loss_terms.data_ptr(), dZ.data_ptr(), dparams.data_ptr(), wp, wn, stream)
         with torch.cuda.device(dev):
             if comm is not None:
                 _lib.check(self.lib.reni_train_step_rows_dp(*head, comm._comm, 1 if overlap else 0, *tail))
@@ -259,9 +264,8 @@ class Plan:
             lp = (buf.data_ptr() + 255) & ~255
             wst = (ctypes.c_int64 * 3)(*weight.stride())
             summary = (ctypes.c_int32 * 3)()
-            with torch.cuda.device(weight.device):
-                _lib.check(self.lib.reni_weight_lists_build(B, P, weight.data_ptr(), wst, int(mode), lp, buf.numel() - (lp - buf.data_ptr()),
-                                                            summary, torch.cuda.current_stream(weight.device).cuda_stream))
+            _call(self.lib.reni_weight_lists_build, weight.device, B, P, weight.data_ptr(), wst, int(mode), lp,
+                  buf.numel() - (lp - buf.data_ptr()), summary)
             # (one synchronisation per mask: no image with a live cosine term -> the steps leave the statistics launches out)
             cache.update(key=key, buf=buf, ptr=lp, weight=weight, cos_constant=summary[2] == 0,   # (the weight is kept alive: its
                          summary=tuple(summary))                                                  #  data_ptr is part of the key)
@@ -284,24 +288,18 @@ class Plan:
         self._check_zp(Z_table, params)
         if idx.dtype != torch.int64 or idx.dim() != 1 or idx.numel() < 1 or not idx.is_contiguous():
             raise ValueError("idx must be a non-empty contiguous 1-D int64 tensor")
-        if sparse_weight not in (False, True, None, "tiles", "pixels"):
-            raise ValueError('sparse_weight must be False, True / "tiles", or "pixels"')
+        flags = _sparse_flags(sparse_weight)
         B, P, Dc, dbs = self._grid_args(Z_table[:1].expand(idx.numel(), -1, -1), D)
-        target = (target if target.dtype == torch.float32 else target.float()).expand(B, P, 3)
-        weight = (weight if weight.dtype == torch.float32 else weight.float()).expand(B, P, 3)
-        ts = (ctypes.c_int64 * 3)(*target.stride())
-        wst = (ctypes.c_int64 * 3)(*weight.stride())
+        target, weight, ts, wst = _loss_views(target, weight, B, P)
         dev = Z_table.device
         loss_terms = torch.empty(4, dtype=torch.float32, device=dev)
         dZ = torch.empty(B, self.ndims, 3, dtype=torch.float32, device=dev)
-        flags = _lib.WEIGHT_COMPACT if sparse_weight == "pixels" else _lib.WEIGHT_SPARSE if sparse_weight else 0
-        ws = self.workspace(B, P, _lib.NEED_DZ | flags, dev)
-        wp, wn = self._aligned_ptr(ws)
-        kind = {"mse": _lib.LOSS_MSE, "test": _lib.LOSS_TEST}[loss_kind]
+        wp, wn, stream = self._ws_args(B, P, _lib.NEED_DZ | flags, dev)
+        kind = _lib.LOSS_KIND[loss_kind]
         head = (self._h, B, P, Z_table.data_ptr(), Z_table.shape[0], idx.data_ptr(), Dc.data_ptr(), dbs, params.data_ptr(),
                 target.data_ptr(), ts, weight.data_ptr(), wst, kind, float(alpha), float(beta), flags)
         tail = (m_lat.data_ptr(), v_lat.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
-                loss_terms.data_ptr(), dZ.data_ptr(), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+                loss_terms.data_ptr(), dZ.data_ptr(), wp, wn, stream)
         chunked = False
         if flags:  # (H = 256 problems that run in image chunks keep the rebuilding entry point; decided once per shape)
             cc = self.__dict__.setdefault("_chunk_cache", {})
@@ -331,9 +329,7 @@ class Plan:
         dev = Z.device
         dZ = torch.empty_like(Z) if need_dz else None
         dparams = torch.empty(self.n_params, dtype=torch.float32, device=dev) if need_dw else None
-        ws = self.workspace(B, P, flags, dev)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        wp, wn, stream = self._ws_args(B, P, flags, dev)
         _lib.check(self.lib.reni_backward(
             self._h, B, P, Z.data_ptr(), Dc.data_ptr(), dbs, params.data_ptr(), dout.data_ptr(), flags,
             dZ.data_ptr() if dZ is not None else None, dparams.data_ptr() if dparams is not None else None,
@@ -347,15 +343,7 @@ class Plan:
         H, L = self.hidden_features, self.hidden_layers
         assert A.shape == (B, H, 8), f"A must be [B,{H},8], got {tuple(A.shape)}"
         assert film.shape == (B, L, 2, H), f"film must be [B,{L},2,{H}], got {tuple(film.shape)}"
-        if D.dim() == 2:
-            D = D.unsqueeze(0)
-        if D.shape[0] not in (1, B):
-            raise ValueError(f"directions batch {D.shape[0]} does not match latent batch {B}")
-        P = D.shape[1]
-        dbs = 0 if D.shape[0] == 1 or D.stride(0) == 0 else P * 3
-        if dbs == 0:
-            D = D[:1]
-        return B, P, _f32c(D), dbs
+        return self._grid_args(A, D)
 
     def film_forward(self, A, film, D, params):
         _require_cuda(A, film, D, params)
@@ -363,9 +351,7 @@ class Plan:
         B, P, Dc, dbs = self._film_args(A, film, D)
         assert params.numel() == self.n_params
         out = torch.empty(B, P, 3, dtype=torch.float32, device=A.device)
-        ws = self.workspace(B, P, 0, A.device)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(A.device).cuda_stream
+        wp, wn, stream = self._ws_args(B, P, 0, A.device)
         _lib.check(self.lib.reni_film_forward(self._h, B, P, Dc.data_ptr(), dbs, A.data_ptr(), film.data_ptr(),
                                               params.data_ptr(), out.data_ptr(), wp, wn, stream))
         return out
@@ -376,14 +362,7 @@ class Plan:
         _require_cuda(A, film, D, params, target, weight)
         A = _f32c(A); film = _f32c(film); params = _f32c(params)
         B, P, Dc, dbs = self._film_args(A, film, D)
-        if target.dtype != torch.float32:
-            target = target.float()
-        if weight.dtype != torch.float32:
-            weight = weight.float()
-        target = target.expand(B, P, 3)
-        weight = weight.expand(B, P, 3)
-        ts = (ctypes.c_int64 * 3)(*target.stride())
-        wst = (ctypes.c_int64 * 3)(*weight.stride())
+        target, weight, ts, wst = _loss_views(target, weight, B, P)
         flags = _lib.NEED_DW if need_dw else 0
         dev = A.device
         loss_terms = torch.empty(4, dtype=torch.float32, device=dev)
@@ -391,10 +370,8 @@ class Plan:
         dfilm = torch.empty_like(film)
         dparams = torch.empty(self.n_params, dtype=torch.float32, device=dev) if need_dw else None
         out = torch.empty(B, P, 3, dtype=torch.float32, device=dev) if want_out else None
-        ws = self.workspace(B, P, flags, dev)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        kind = {"mse": _lib.LOSS_MSE, "test": _lib.LOSS_TEST}[loss_kind]
+        wp, wn, stream = self._ws_args(B, P, flags, dev)
+        kind = _lib.LOSS_KIND[loss_kind]
         _lib.check(self.lib.reni_film_forward_loss_backward(
             self._h, B, P, Dc.data_ptr(), dbs, A.data_ptr(), film.data_ptr(), params.data_ptr(), target.data_ptr(), ts,
             weight.data_ptr(), wst, kind, float(beta), flags, out.data_ptr() if out is not None else None,
@@ -411,9 +388,7 @@ class Plan:
         dA = torch.empty_like(A)
         dfilm = torch.empty_like(film)
         dparams = torch.empty(self.n_params, dtype=torch.float32, device=dev) if need_dw else None
-        ws = self.workspace(B, P, flags, dev)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        wp, wn, stream = self._ws_args(B, P, flags, dev)
         _lib.check(self.lib.reni_film_backward(
             self._h, B, P, Dc.data_ptr(), dbs, A.data_ptr(), film.data_ptr(), params.data_ptr(), dout.data_ptr(), flags,
             dA.data_ptr(), dfilm.data_ptr(), dparams.data_ptr() if dparams is not None else None, wp, wn, stream))
@@ -427,9 +402,7 @@ class Plan:
         self._check_zp(Z, params, map_params)
         B, P, Dc, dbs = self._grid_args(Z, D)
         out = torch.empty(B, P, 3, dtype=torch.float32, device=Z.device)
-        ws = self.workspace(B, P, 0, Z.device)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(Z.device).cuda_stream
+        wp, wn, stream = self._ws_args(B, P, 0, Z.device)
         _lib.check(self.lib.reni_film_model_forward(self._h, B, P, Z.data_ptr(), Dc.data_ptr(), dbs, params.data_ptr(),
                                                     map_params.data_ptr(), out.data_ptr(), wp, wn, stream))
         return out
@@ -443,14 +416,7 @@ class Plan:
         Z = _f32c(Z); params = _f32c(params); map_params = _f32c(map_params)
         self._check_zp(Z, params, map_params)
         B, P, Dc, dbs = self._grid_args(Z, D)
-        if target.dtype != torch.float32:
-            target = target.float()
-        if weight.dtype != torch.float32:
-            weight = weight.float()
-        target = target.expand(B, P, 3)
-        weight = weight.expand(B, P, 3)
-        ts = (ctypes.c_int64 * 3)(*target.stride())
-        wst = (ctypes.c_int64 * 3)(*weight.stride())
+        target, weight, ts, wst = _loss_views(target, weight, B, P)
         flags = (_lib.NEED_DW if need_dw else 0) | _lib.NEED_DZ
         dev = Z.device
         loss_terms = torch.empty(4, dtype=torch.float32, device=dev)
@@ -459,10 +425,8 @@ class Plan:
         dparams = gall[:self.n_params] if need_dw else None
         dmap = gall[self.n_params:] if need_dw else None
         out = torch.empty(B, P, 3, dtype=torch.float32, device=dev) if want_out else None
-        ws = self.workspace(B, P, flags, dev)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        kind = {"mse": _lib.LOSS_MSE, "test": _lib.LOSS_TEST}[loss_kind]
+        wp, wn, stream = self._ws_args(B, P, flags, dev)
+        kind = _lib.LOSS_KIND[loss_kind]
         _lib.check(self.lib.reni_film_model_forward_loss_backward(
             self._h, B, P, Z.data_ptr(), Dc.data_ptr(), dbs, params.data_ptr(), map_params.data_ptr(), target.data_ptr(), ts,
             weight.data_ptr(), wst, kind, float(alpha), float(beta), flags, out.data_ptr() if out is not None else None,
@@ -482,9 +446,7 @@ class Plan:
         dZ = torch.empty_like(Z)
         dparams = torch.empty(self.n_params, dtype=torch.float32, device=dev) if need_dw else None
         dmap = torch.empty(self.n_map_params, dtype=torch.float32, device=dev) if need_dw else None
-        ws = self.workspace(B, P, flags, dev)
-        wp, wn = self._aligned_ptr(ws)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        wp, wn, stream = self._ws_args(B, P, flags, dev)
         _lib.check(self.lib.reni_film_model_backward(
             self._h, B, P, Z.data_ptr(), Dc.data_ptr(), dbs, params.data_ptr(), map_params.data_ptr(), dout.data_ptr(), flags,
             dZ.data_ptr(), dparams.data_ptr() if need_dw else None, dmap.data_ptr() if need_dw else None, wp, wn, stream))
@@ -529,12 +491,9 @@ def adam_step2(p, g, m, v, table, g_rows, idx, tm, tv, step: int, lr: float, bet
     n_rows = table.shape[0]
     row_len = table.numel() // max(n_rows, 1)
     assert g_rows.numel() == idx.numel() * row_len
-    stream = torch.cuda.current_stream(p.device).cuda_stream
-    with torch.cuda.device(p.device):
-        _lib.check(lib.reni_adam_step2(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), table.data_ptr(),
-                                       g_rows.data_ptr(), idx.data_ptr(), idx.numel(), row_len, tm.data_ptr(), tv.data_ptr(),
-                                       n_rows, float(lr), float(betas[0]), float(betas[1]), float(eps), int(step),
-                                       float(grad_scale), stream))
+    _call(lib.reni_adam_step2, p.device, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), table.data_ptr(),
+          g_rows.data_ptr(), idx.data_ptr(), idx.numel(), row_len, tm.data_ptr(), tv.data_ptr(), n_rows, float(lr), float(betas[0]),
+          float(betas[1]), float(eps), int(step), float(grad_scale))
 
 
 def selftest_layouts():
@@ -593,12 +552,9 @@ def _shade_call(forward: bool, normals, positions, camera_center, light_dirs, sr
     out = torch.empty((B, NP, 3) if forward else (B, J, 3), dtype=f32, device=src.device)
     nbytes = int(lib.reni_envmap_shade_workspace_bytes(B, NP, J))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
-    stream = torch.cuda.current_stream(src.device).cuda_stream
-    fn = lib.reni_envmap_shade if forward else lib.reni_envmap_shade_backward
-    with torch.cuda.device(src.device):
-        _lib.check(fn(B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(),
-                      stride, src.data_ptr(), float(shininess), float(kd), float(ks), out.data_ptr(), ws.data_ptr(), nbytes,
-                      stream))
+    _call(lib.reni_envmap_shade if forward else lib.reni_envmap_shade_backward, src.device, B, NP, J, normals.data_ptr(),
+          positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride, src.data_ptr(), float(shininess), float(kd),
+          float(ks), out.data_ptr(), ws.data_ptr(), nbytes)
     return out
 
 
@@ -646,10 +602,8 @@ def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     if corners.numel() == 0:
         corners = torch.zeros(1, dtype=torch.int64, device=verts.device)  # (never read: every vertex's range is empty)
     out = torch.empty(V, 3, dtype=torch.float32, device=verts.device)
-    with torch.cuda.device(verts.device):
-        _lib.check(_lib.load().reni_mesh_vertex_normals(V, F, verts.data_ptr(), faces.data_ptr(), offsets.data_ptr(),
-                                                        corners.data_ptr(), out.data_ptr(),
-                                                        torch.cuda.current_stream(verts.device).cuda_stream))
+    _call(_lib.load().reni_mesh_vertex_normals, verts.device, V, F, verts.data_ptr(), faces.data_ptr(), offsets.data_ptr(),
+          corners.data_ptr(), out.data_ptr())
     return out
 
 
@@ -683,11 +637,8 @@ def rasterize_mesh(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch
     nrm = torch.empty(S * S, 3, dtype=torch.float32, device=dev)
     pos = torch.empty(S * S, 3, dtype=torch.float32, device=dev)
     ws, wp, wn = _ws256(int(lib.reni_raster_workspace_bytes(V, F, S, S)), dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.reni_rasterize_mesh(V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th,
-                                           float(tan_half_fov), S, S, p2f.data_ptr(), zbuf.data_ptr(), bary.data_ptr(),
-                                           dists.data_ptr(), nrm.data_ptr(), pos.data_ptr(), wp, wn,
-                                           torch.cuda.current_stream(dev).cuda_stream))
+    _call(lib.reni_rasterize_mesh, dev, V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th, float(tan_half_fov),
+          S, S, p2f.data_ptr(), zbuf.data_ptr(), bary.data_ptr(), dists.data_ptr(), nrm.data_ptr(), pos.data_ptr(), wp, wn)
     return p2f, zbuf, bary, dists, nrm, pos
 
 
@@ -706,10 +657,8 @@ def sg_render(params, theta_c, phi_c, theta_range: float, phi_range: float, H: i
     params, theta_c, phi_c, N, K, H, W = _sg_check(params, theta_c, phi_c, H, W)
     dev = params.device
     rec = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().reni_sg_render(N, K, H, W, params.data_ptr(), theta_c.data_ptr(), phi_c.data_ptr(),
-                                              float(theta_range), float(phi_range), rec.data_ptr(),
-                                              torch.cuda.current_stream(dev).cuda_stream))
+    _call(_lib.load().reni_sg_render, dev, N, K, H, W, params.data_ptr(), theta_c.data_ptr(), phi_c.data_ptr(), float(theta_range),
+          float(phi_range), rec.data_ptr())
     return rec
 
 
@@ -734,11 +683,9 @@ def sg_loss_grad(params, theta_c, phi_c, theta_range: float, phi_range: float, l
     grad = torch.empty(N, K, 6, dtype=torch.float32, device=dev)
     lib = _lib.load()
     ws, wp, wn = _ws256(int(lib.reni_sg_workspace_bytes(N, K, H, W)), dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.reni_sg_loss_grad(N, K, H, W, params.data_ptr(), theta_c.data_ptr(), phi_c.data_ptr(),
-                                         float(theta_range), float(phi_range), log_target.data_ptr(), weight.data_ptr(),
-                                         *[int(x) for x in weight.stride()], loss_map.data_ptr(), total.data_ptr(),
-                                         grad.data_ptr(), wp, wn, torch.cuda.current_stream(dev).cuda_stream))
+    _call(lib.reni_sg_loss_grad, dev, N, K, H, W, params.data_ptr(), theta_c.data_ptr(), phi_c.data_ptr(), float(theta_range),
+          float(phi_range), log_target.data_ptr(), weight.data_ptr(), *[int(x) for x in weight.stride()], loss_map.data_ptr(),
+          total.data_ptr(), grad.data_ptr(), wp, wn)
     return total, loss_map, grad
 
 
@@ -750,9 +697,7 @@ def _sh_call(project: bool, src, row_table, col_table, H: int, W: int, lmax: int
     dev = src.device
     out = torch.empty((N, T, 3) if project else (N, H, W, 3), dtype=torch.float32, device=dev)
     fn = _lib.load().reni_sh_project if project else _lib.load().reni_sh_reconstruct
-    with torch.cuda.device(dev):
-        _lib.check(fn(N, H, W, lmax, src.data_ptr(), _f32c(row_table).data_ptr(), _f32c(col_table).data_ptr(),
-                      out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    _call(fn, dev, N, H, W, lmax, src.data_ptr(), _f32c(row_table).data_ptr(), _f32c(col_table).data_ptr(), out.data_ptr())
     return out
 
 
@@ -797,10 +742,8 @@ def diffuse_convolve(src, in_dirs, in_weight, out_dirs, scale: float) -> torch.T
     out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
     lib = _lib.load()
     ws, wp, wn = _ws256(int(lib.reni_diffuse_workspace_bytes(N, P, Q)), dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.reni_diffuse_convolve(N, P, Q, out_dirs.data_ptr(), in_dirs.data_ptr(), in_weight.data_ptr(),
-                                             src.data_ptr(), sn, si, sc, float(scale), out.data_ptr(), wp, wn,
-                                             torch.cuda.current_stream(dev).cuda_stream))
+    _call(lib.reni_diffuse_convolve, dev, N, P, Q, out_dirs.data_ptr(), in_dirs.data_ptr(), in_weight.data_ptr(), src.data_ptr(),
+          sn, si, sc, float(scale), out.data_ptr(), wp, wn)
     return out
 
 
@@ -820,9 +763,7 @@ def sh_irradiance_l2(coeffs, normals) -> torch.Tensor:
         raise ValueError(f"normals must be [P, 3] or [N, P, 3], got {tuple(normals.shape)}")
     dev = coeffs.device
     out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().reni_sh_irradiance_l2(N, P, coeffs.data_ptr(), normals.data_ptr(), stride, out.data_ptr(),
-                                                     torch.cuda.current_stream(dev).cuda_stream))
+    _call(_lib.load().reni_sh_irradiance_l2, dev, N, P, coeffs.data_ptr(), normals.data_ptr(), stride, out.data_ptr())
     return out
 
 
@@ -852,11 +793,8 @@ def unnormalise_srgb(img: torch.Tensor, minmax=None, srgb: bool = True, want_lin
     lin = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if (want_linear or not srgb) else None
     ws, wp, wn = _ws256(int(lib.reni_image_workspace_bytes(B, H, W)), dev) if srgb else (None, None, 0)
     m0, m1 = (float(minmax[0]), float(minmax[1])) if minmax is not None else (0.0, 1.0)
-    with torch.cuda.device(dev):
-        _lib.check(lib.reni_unnormalise_srgb(B, H, W, img.data_ptr(), st, 0 if minmax is None else 1, m0, m1, 1 if srgb else 0,
-                                             out.data_ptr() if out is not None else None,
-                                             lin.data_ptr() if lin is not None else None, wp, wn,
-                                             torch.cuda.current_stream(dev).cuda_stream))
+    _call(lib.reni_unnormalise_srgb, dev, B, H, W, img.data_ptr(), st, 0 if minmax is None else 1, m0, m1, 1 if srgb else 0,
+          out.data_ptr() if out is not None else None, lin.data_ptr() if lin is not None else None, wp, wn)
     if srgb and want_linear:
         return out, lin
     return out if srgb else lin
@@ -869,9 +807,7 @@ def minmax_normalise(img: torch.Tensor, minmax):
     x = _f32c(img)
     out = torch.empty_like(x)
     ws, wp, wn = _ws256(256, x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.reni_minmax_normalise(x.numel(), x.data_ptr(), float(minmax[0]), float(minmax[1]), out.data_ptr(), wp, wn,
-                                             torch.cuda.current_stream(x.device).cuda_stream))
+    _call(lib.reni_minmax_normalise, x.device, x.numel(), x.data_ptr(), float(minmax[0]), float(minmax[1]), out.data_ptr(), wp, wn)
     return out
 
 
@@ -887,10 +823,8 @@ def minmax_normalise_batch(imgs: torch.Tensor, minmax, nan_to_num: bool = True):
     out = torch.empty_like(x)
     N = x.shape[0]
     ws, wp, wn = _ws256(int(lib.reni_minmax_batch_workspace_bytes(N)), x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.reni_minmax_normalise_batch(N, x[0].numel(), x.data_ptr(), float(minmax[0]), float(minmax[1]),
-                                                   1 if nan_to_num else 0, out.data_ptr(), wp, wn,
-                                                   torch.cuda.current_stream(x.device).cuda_stream))
+    _call(lib.reni_minmax_normalise_batch, x.device, N, x[0].numel(), x.data_ptr(), float(minmax[0]), float(minmax[1]),
+          1 if nan_to_num else 0, out.data_ptr(), wp, wn)
     return out
 
 
@@ -947,10 +881,8 @@ def resample(src: torch.Tensor, size, mode: str = "bilinear", layout: str = "aut
     ci, cw = device_tables(Ws, Wd, mode, dev)
     out = torch.empty(N, C, Hd, Wd, dtype=torch.float32, device=dev)
     st = (ctypes.c_int64 * 4)(*x.stride())
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().reni_resample(N, C, Hs, Ws, Hd, Wd, x.data_ptr(), st, ri.data_ptr(), rw.data_ptr(), TAPS[mode],
-                                             ci.data_ptr(), cw.data_ptr(), TAPS[mode], out.data_ptr(),
-                                             torch.cuda.current_stream(dev).cuda_stream))
+    _call(_lib.load().reni_resample, dev, N, C, Hs, Ws, Hd, Wd, x.data_ptr(), st, ri.data_ptr(), rw.data_ptr(), TAPS[mode],
+          ci.data_ptr(), cw.data_ptr(), TAPS[mode], out.data_ptr())
     return unview(out)
 
 
@@ -977,9 +909,7 @@ def gaussian_blur(img: torch.Tensor, sigma: float, layout: str = "auto") -> torc
     wt = torch.from_numpy(w.astype("float32")).to(dev)
     st = (ctypes.c_int64 * 3)(*v.stride()[1:])
     ws, wp, wn = _ws256(int(lib.reni_blur_workspace_bytes(C, H, W)), dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.reni_gaussian_blur(C, H, W, x.data_ptr(), st, wt.data_ptr(), r, out.data_ptr(), wp, wn,
-                                          torch.cuda.current_stream(dev).cuda_stream))
+    _call(lib.reni_gaussian_blur, dev, C, H, W, x.data_ptr(), st, wt.data_ptr(), r, out.data_ptr(), wp, wn)
     return out
 
 
@@ -1036,11 +966,8 @@ def rotate_envmap(src: torch.Tensor, rot: torch.Tensor, mode: str = "bilinear", 
     rt, ct = _rotate_trig(H, W, dev)
     out = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
     st = (ctypes.c_int64 * 4)(*x.stride())
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().reni_rotate_envmap(B, C, H, W, x.data_ptr(), st, None if index is None else index.data_ptr(), N,
-                                                  rot.data_ptr(), rot_stride, rt.data_ptr(), ct.data_ptr(),
-                                                  _lib.ROTATE_MODE[mode], out.data_ptr(),
-                                                  torch.cuda.current_stream(dev).cuda_stream))
+    _call(_lib.load().reni_rotate_envmap, dev, B, C, H, W, x.data_ptr(), st, None if index is None else index.data_ptr(), N,
+          rot.data_ptr(), rot_stride, rt.data_ptr(), ct.data_ptr(), _lib.ROTATE_MODE[mode], out.data_ptr())
     return unview(out)
 
 

@@ -30,6 +30,40 @@ def test_library_exports_every_declared_symbol():
         assert getattr(lib, name) is not None
 
 
+def test_binding_argtypes_are_the_headers_prototypes():
+    """Every prototype of include/reni_hip.h against the ctypes binding, position by position: ctypes converts what it is given to
+    the declared argtypes and checks nothing against the library, so a drifted list passes a pointer where a float belongs."""
+    import ctypes
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, "include", "reni_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    protos = re.findall(r"^([a-z_0-9 ]+?\*?)\s*\b(reni_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", header, flags=re.M)
+    assert {name for _, name, _ in protos} == set(_lib.EXPORTS) and len(protos) == len(_lib.EXPORTS)
+    scalars = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "int": ctypes.c_int32, "uint32_t": ctypes.c_uint32,
+               "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+
+    def agrees(ctype, decl, is_param):
+        if "*" in decl or "[" in decl:
+            return isinstance(ctype, type) and issubclass(ctype, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p))
+        words = [w for w in decl.split() if w != "const"]
+        base = " ".join(words[:-1] if is_param else words)   # (a parameter's last word is its name)
+        return ctype is None if base == "void" else ctype is scalars[base]
+
+    bad = []
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        want = [] if params.strip() == "void" else [x.strip() for x in params.split(",")]
+        if fn.argtypes is None or len(fn.argtypes) != len(want):
+            bad.append(f"{name}: argtypes {fn.argtypes!r} for {len(want)} parameters")
+            continue
+        bad += [f"{name}: parameter {i} `{d}` bound as {t.__name__}" for i, (t, d) in enumerate(zip(fn.argtypes, want))
+                if not agrees(t, d, True)]
+        if not agrees(fn.restype, ret.strip(), False):
+            bad.append(f"{name}: returns `{ret.strip()}`, restype {fn.restype!r}")
+    assert not bad, "\n".join(bad)
+
+
 def test_binding_constants_are_the_headers():
     """The flag / enum values the Python binding passes are the ones include/reni_hip.h defines (a drifted constant would select
     another behaviour silently: RENI_WEIGHT_SPARSE is a bit of the same word as RENI_NEED_DW / RENI_NEED_DZ)."""

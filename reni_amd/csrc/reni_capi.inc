@@ -46,7 +46,8 @@ thread_local std::string g_err;
 std::atomic<long long> g_launches{0};
 // reni_set_grad_ready_event: recorded on the call's stream once the gradient of everything behind layer 1 is final (see the header)
 thread_local hipEvent_t g_ev_rest = nullptr;
-#define RENI_LAUNCH(...) do { g_launches.fetch_add(1, std::memory_order_relaxed); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+// (... and its launch error is the enclosing function's return: HIP_TRY, below)
+#define RENI_LAUNCH(...) do { g_launches.fetch_add(1, std::memory_order_relaxed); hipLaunchKernelGGL(__VA_ARGS__); HIP_TRY(hipGetLastError()); } while (0)
 
 int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -126,6 +127,10 @@ bool geo_for(const reni_plan* p, GeoRt* g) {
 struct Layout {
   int tpi, n_tiles, nwg, persist, stream, kmax, frag;
   int wide_train;  // k_reni_wide256<2> runs the chain of this (H = 256, bf16, training) call: `persist` operands, the generic path's consumers
+  // The training instance of the persistent H = 128 kernel runs: image runs, g_1 stream, a dW_1 kernel behind it.  THE definition: run_backward
+  // and reni_path_info read it here.  (A call sees the same thing as `need_dw || fio`: a FiLM call always carries its FilmIO -- check_film,
+  // and run_backward refuses a FiLM plan without one -- and MainArgs::need_dw mirrors RENI_NEED_DW.)
+  int pdw;
   // Frozen-decoder call of a concat decoder on the persistent kernels (k_reni_train_bf16<128,false>, k_reni_wide256<1>): the packed W^T
   // images are 8 x the forward images' rounded weights, the rest of the factor rides on d loss / d y (MainArgs::gy_scale).  Why: with
   // the two images rounded independently -- bf16(W omega / 2 pi) forward, bf16(omega W) backward: the ratio 2 pi is no power of two --
@@ -159,7 +164,7 @@ Layout make_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uin
   // d(freq) / d(phase) need the same per-image weight-gradient sums
   l.wide_train = (backward && allow_persist && !p->no_persist && has_wide_train(p->d.dtype, H, L, flags, film)) ? 1 : 0;
   l.persist = (allow_persist && !p->no_persist && (has_persistent(p->d.dtype, H, L) || has_wide(p->d.dtype, H, L, flags, film, backward) || l.wide_train)) ? 1 : 0;
-  const bool pdw = l.persist && !l.wide_train && (film || (flags & RENI_NEED_DW));  // the training instance of the persistent kernel runs
+  l.pdw = (l.persist && !l.wide_train && (film || (flags & RENI_NEED_DW))) ? 1 : 0;
   // (every concat call on the persistent kernels: frozen-decoder and training calls at both widths -- the per-layer constants the weight
   //  gradients of a training call then carry are multiplied back where the per-workgroup partials are summed: reni::LayerScale; at
   //  H = 256 those partials are k_dw_frag's and k_wide_head_dw's, formed from the fragment stream the chain wrote with the same constants)
@@ -167,7 +172,7 @@ Layout make_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uin
   const int per_cu = (p->d.dtype == RENI_BF16 && !l.persist && H <= 128) ? 2 : 1;
   const int cap = device_cus() * per_cu;
   l.nwg = l.n_tiles < cap ? l.n_tiles : cap;
-  if (pdw && l.n_tiles > cap) {
+  if (l.pdw && l.n_tiles > cap) {
     // contiguous ranges: the longest range sets the time, so no more workgroups than give every one of them that length -- each
     // workgroup less is 0.33 MB of weight-gradient partials less to flush and to reduce (400 tiles: 200 x 2 instead of 256 x 1..2)
     const int rounds = (l.n_tiles + cap - 1) / cap;
@@ -202,7 +207,7 @@ Layout make_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uin
   l.o_stats = o; o += al256((size_t)B * 16 * 4);
   if (backward) {
     // (the frozen-decoder instance of the persistent kernel works on two tiles per workgroup)
-    l.stash_per_wg = (size_t)(L + 1) * g.stash_layer_bytes * ((l.persist && !pdw && !l.wide_train) ? 2 : 1);
+    l.stash_per_wg = (size_t)(L + 1) * g.stash_layer_bytes * ((l.persist && !l.pdw && !l.wide_train) ? 2 : 1);
     // (H = 256 bf16 training: the fragment stream -- every tile's phase stash stays for k_dw_frag)
     l.frag = (p->d.dtype == RENI_BF16 && H == 256 && L >= 1 && (film || (flags & RENI_NEED_DW))) ? 1 : 0;
     // (fp32, concat: k_dw_frag32 -- fp32 fragments; the per-tile += of a 256 x 256 partial it replaces ran at 8 M samples/s)
@@ -215,7 +220,7 @@ Layout make_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uin
     const size_t run_slots = (film && l.persist && !l.wide_train) ? (size_t)l.pkmax : 1;   // (wide_train: the stream path's bookkeeping, below)
     l.o_dwp = o; o += al256(l.dwp_per_wg * 4 * l.nwg * run_slots);
     // (the persistent training instance keeps layer-0 dA on chip: image runs below, no per-tile partials)
-    l.o_dA_part = o; if (!pdw) o += al256((size_t)l.n_tiles * H * 8 * 4);
+    l.o_dA_part = o; if (!l.pdw) o += al256((size_t)l.n_tiles * H * 8 * 4);
     l.o_tflag = l.o_tlist = l.o_tcount = l.o_imgcos = o;
     if (!film && !(flags & RENI_NEED_DW)) {  // frozen concat decoder (sized whether or not the call sets RENI_WEIGHT_SPARSE: the layout does not depend on it)
       l.o_tflag = o; o += al256((size_t)l.n_tiles * 4);
@@ -230,12 +235,12 @@ Layout make_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uin
     l.o_loss_part = o; o += al256((size_t)l.n_tiles * 4 * 16 * 4);
     l.o_dA = o; o += al256((size_t)B * H * 8 * 4);
     // k_reni_dw1 runs two workgroups per CU with partials of its own: [2 nwg][H * H + H]
-    l.o_dw1p = o; if (pdw && (flags & RENI_NEED_DW)) o += al256((size_t)2 * l.nwg * run_slots * ((size_t)H * H + H) * 4);
+    l.o_dw1p = o; if (l.pdw && (flags & RENI_NEED_DW)) o += al256((size_t)2 * l.nwg * run_slots * ((size_t)H * H + H) * 4);
     // (g_1 stream [position in a workgroup's tile range][workgroup][H / 16 x 4 KB]: ceil(n_tiles / nwg) positions)
-    l.o_g1 = o; if (pdw) o += al256((size_t)((l.n_tiles + l.nwg - 1) / l.nwg) * l.nwg * (H / 16) * 4096);
-    l.o_pruns = o; if (pdw) o += al256((size_t)l.nwg * l.pkmax * (H * 8 + 16) * 4);
+    l.o_g1 = o; if (l.pdw) o += al256((size_t)((l.n_tiles + l.nwg - 1) / l.nwg) * l.nwg * (H / 16) * 4096);
+    l.o_pruns = o; if (l.pdw) o += al256((size_t)l.nwg * l.pkmax * (H * 8 + 16) * 4);
     // (FiLM: + the run tags of k_reni_dw1's 2 nwg workgroups behind the training kernel's)
-    l.o_prunimg = o; if (pdw) o += al256((size_t)l.nwg * l.pkmax * (film ? 3 : 1) * 4);
+    l.o_prunimg = o; if (l.pdw) o += al256((size_t)l.nwg * l.pkmax * (film ? 3 : 1) * 4);
     // tiles per stage-A block of the per-image tile reduction.  Independent of the batch on purpose: an image's sums are then
     // formed in the same order whatever batch it is part of (its gradient does not depend on its neighbours, bit for bit).
     l.rt_chunk = reni::RT_CHUNK;
@@ -274,6 +279,11 @@ Layout make_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uin
   return l;
 }
 
+// the layout every backward call of this shape uses and reni_workspace_bytes sizes: RENI_NEED_DZ set, so that one buffer serves every call
+Layout backward_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uint32_t flags) {
+  return make_layout(p, g, B, P, flags | RENI_NEED_DZ, true, true);
+}
+
 // ---- optional HIP-event timing of the fused main kernel (reni_profile_*) --------------------
 // kind of the timed launch: the fused forward+loss+backward pass, RENITestLoss's statistics pass, or plain inference
 // (3: k_reni_l0_ring / k_reni_dw1_ring / k_reni_dw1 behind the training kernel; 4: the weight-gradient consumers of the fragment / operand
@@ -298,47 +308,53 @@ bool prof_begin(hipStream_t s, EvPair* out, int kind) {
   return hipEventRecord(out->a, s) == hipSuccess;
 }
 
-// the head / loss configuration of every shipped FIT_DECODER run (the SPEC instances' compile-time constants)
-bool train_spec(const reni::MainArgs& a, bool stats) {
-#ifndef RENI_AB_NO_SPEC  // (same-box A/B switch of profiles/tools/gpu_variants.sh; never defined in the shipped build)
-#define RENI_AB_NO_SPEC 0
+// One timed launch: the profile pair around whatever `go` enqueues on `s` (a kernel of this translation unit, or another unit's host
+// launcher), the launch count, the error check, the end event.
+template <class Go>
+int timed_launch(hipStream_t s, int kind, const char* what, Go go) {
+  EvPair ev;
+  const bool timed = prof_begin(s, &ev, kind);
+  g_launches.fetch_add(1, std::memory_order_relaxed);
+  const hipError_t e = go();
+  if (e != hipSuccess) return fail(RENI_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
+  if (timed) HIP_TRY(hipEventRecord(ev.b, s));
+  return RENI_OK;
+}
+// ... of a MainArgs kernel of this translation unit: the dynamic-LDS attribute first, when the kernel asks for any
+int timed_launch(void (*fn)(const reni::MainArgs), int grid, int block, int lds, hipStream_t s, const reni::MainArgs& a, int kind) {
+  if (lds) HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  return timed_launch(s, kind, "kernel", [&] { hipLaunchKernelGGL(fn, dim3(grid), dim3(block), lds, s, a); return hipGetLastError(); });
+}
+
+// the head / loss configuration of every shipped FIT_DECODER run (the SPEC instances' compile-time constants): linear head, tanh,
+// WeightedMSE, no output image.  spec_head: what the plan and the flags decide of it (reni_path_info reports from that part alone).
+#ifndef RENI_AB_NO_SPEC  // (same-box A/B switch of profiles/tools/gpu_variants.sh; never defined in the shipped build.  It covers the FiLM
+#define RENI_AB_NO_SPEC 0  //  training instance too: launch_train asks train_spec for both decoders)
 #endif
-  return !RENI_AB_NO_SPEC && !stats && a.need_dw && a.last_linear && a.act == RENI_ACT_TANH && a.loss_kind == 0 && a.out == nullptr;
+bool spec_head(bool need_dw, int last_linear, int act) { return !RENI_AB_NO_SPEC && need_dw && last_linear && act == RENI_ACT_TANH; }
+bool train_spec(const reni::MainArgs& a, bool stats) {
+  return !stats && spec_head(a.need_dw, a.last_linear, a.act) && a.loss_kind == 0 && a.out == nullptr;
 }
 
 int launch_train(const reni_plan* p, const reni::MainArgs& a, int nwg, hipStream_t s, bool stats = false, bool l0x = false) {
   using G = reni::GeoP<128>;
+  const int kind = !stats ? PROF_FWD_BWD : a.target ? PROF_STATS : PROF_FWD;
+  const bool film = p->d.conditioning == RENI_COND_FILM;
   if (p->d.hidden_features == 256) {  // k_reni_wide256: forward / statistics (stats), the frozen-decoder pass, or the training form
-    const bool wfilm = p->d.conditioning == RENI_COND_FILM;
-    if (wfilm && p->d.hidden_layers > (stats ? reni::wide256_film_max_layers() : reni::wide256_film_train_max_layers()))
+    if (film && p->d.hidden_layers > (stats ? reni::wide256_film_max_layers() : reni::wide256_film_train_max_layers()))
       return fail(RENI_EINVAL, "internal: k_reni_wide256's FiLM instances hold <= 5 (forward) / <= 4 (training form) hidden layers' tables");
-    if ((a.need_dw || wfilm) && !stats && a.gfs == nullptr) return fail(RENI_EINVAL, "internal: the training form of k_reni_wide256 needs the fragment stream");
-    EvPair ev;
-    const bool timed = prof_begin(s, &ev, !stats ? PROF_FWD_BWD : a.target ? PROF_STATS : PROF_FWD);
-    g_launches.fetch_add(1, std::memory_order_relaxed);
-    const hipError_t e = reni::launch_wide256(wfilm ? (stats ? 3 : 4) : stats ? 0 : a.need_dw ? 2 : 1, a, nwg, s);
-    if (e != hipSuccess) return fail(RENI_EHIP, "k_reni_wide256 launch failed: %s", hipGetErrorString(e));
-    if (timed) HIP_TRY(hipEventRecord(ev.b, s));
-    return RENI_OK;
+    if ((a.need_dw || film) && !stats && a.gfs == nullptr) return fail(RENI_EINVAL, "internal: the training form of k_reni_wide256 needs the fragment stream");
+    const int mode = film ? (stats ? 3 : 4) : stats ? 0 : a.need_dw ? 2 : 1;
+    return timed_launch(s, kind, "k_reni_wide256", [&] { return reni::launch_wide256(mode, a, nwg, s); });
   }
   if (!has_persistent(p->d.dtype, p->d.hidden_features, p->d.hidden_layers))
     return fail(RENI_EUNSUPPORTED, "no persistent training kernel for this configuration");
   if (p->d.hidden_layers >= 2 && (a.fwd_off[2] - a.fwd_off[1] != G::FWD_STRIDE || a.bwd_off[2] - a.bwd_off[1] != G::BWD_STRIDE))
     return fail(RENI_EINVAL, "packed weight images are not at the stride the persistent kernels assume");
-  if (p->d.conditioning == RENI_COND_FILM) {  // (the training instance also with a frozen decoder: see make_layout)
-    EvPair ev;
-    const bool timed = prof_begin(s, &ev, !stats ? PROF_FWD_BWD : a.target ? PROF_STATS : PROF_FWD);
-    const int pairs = (a.n_tiles + 1) / 2;
-    g_launches.fetch_add(1, std::memory_order_relaxed);
-    // (2: the SPEC form of the training instance -- linear head, tanh, WeightedMSE, no output image -- as for the concat decoder below)
-    const bool fspec = !stats && a.need_dw && a.last_linear && a.act == RENI_ACT_TANH && a.loss_kind == 0 && a.out == nullptr;
-    const hipError_t e = reni::launch_train_film(stats ? 1 : fspec ? 2 : 0, a, stats ? (nwg < pairs ? nwg : pairs) : nwg, s);
-    if (e != hipSuccess) return fail(RENI_EHIP, "FiLM persistent kernel launch failed: %s", hipGetErrorString(e));
-    if (timed) HIP_TRY(hipEventRecord(ev.b, s));
-    return RENI_OK;
-  }
-  // the head / loss configuration of every shipped FIT_DECODER run as compile-time constants (SPEC instance)
   const bool spec = train_spec(a, stats);
+  const int pairs = (a.n_tiles + 1) / 2, nwg2 = nwg < pairs ? nwg : pairs;  // (the forward-only instances: eight waves on two tiles)
+  if (film)  // (the training instance also with a frozen decoder: see make_layout; 2: its SPEC form, as for the concat decoder below)
+    return timed_launch(s, kind, "FiLM persistent kernel", [&] { return reni::launch_train_film(stats ? 1 : spec ? 2 : 0, a, stats ? nwg2 : nwg, s); });
   if (l0x && !spec) return fail(RENI_EINVAL, "internal: the L0X form exists for the SPEC instance only");
   void (*fn)(const reni::MainArgs) = stats ? reni::k_reni_train_bf16<128, false, true>
                                      : l0x ? reni::k_reni_train_bf16<128, true, false, false, true, true>
@@ -350,23 +366,17 @@ int launch_train(const reni_plan* p, const reni::MainArgs& a, int nwg, hipStream
 #else
   const int LDS = G::LDS_BYTES + lacc;
 #endif
-  HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-  EvPair ev;
-  const bool timed = prof_begin(s, &ev, !stats ? PROF_FWD_BWD : a.target ? PROF_STATS : PROF_FWD);
-  const int pairs = (a.n_tiles + 1) / 2;
-  if (a.need_dw && !stats) RENI_LAUNCH(fn, dim3(nwg), dim3(256), LDS, s, a);
-  else RENI_LAUNCH(fn, dim3(nwg < pairs ? nwg : pairs), dim3(512), LDS, s, a);  // eight waves on two tiles
-  HIP_TRY(hipGetLastError());
-  if (timed) HIP_TRY(hipEventRecord(ev.b, s));
-  return RENI_OK;
+  if (a.need_dw && !stats) return timed_launch(fn, nwg, 256, LDS, s, a, kind);
+  return timed_launch(fn, nwg2, 512, LDS, s, a, kind);
 }
 
 // k_reni_dw1_ring's preconditions (reni_dev_train.inc): concatenation decoder, whole tiles, a tile's directions one 16-byte
-// aligned run.  Decided ONCE per call (run_backward) and handed to both the launch and the layer-1 reduction, whose slot
+// aligned run.  Decided ONCE per call (bwd_path) and handed to both the launch and the layer-1 reduction, whose slot
 // count depends on it (ring: one partial per range, k_reni_dw1: two).
-bool dw1_ring_ok(const reni_plan* p, const reni::MainArgs& a) {
-  return !p->dw1_old && a.film == nullptr && a.P % 128 == 0 && (((uintptr_t)a.D | (uintptr_t)(a.d_bstride * 4)) & 15) == 0;
-}
+// Every run-time predicate here is two functions: *_plan_ok -- what the plan, the shape and the flags decide, all reni_path_info has --
+// and *_call_ok -- what the call's pointers and loss add.  run_backward takes plan && call.
+bool dw1_ring_plan_ok(const reni_plan* p, int64_t P) { return !p->dw1_old && p->d.conditioning != RENI_COND_FILM && P % 128 == 0; }
+bool dw1_ring_call_ok(const reni::MainArgs& a) { return (((uintptr_t)a.D | (uintptr_t)(a.d_bstride * 4)) & 15) == 0; }
 int dw1_slots(bool ring, int nwg) { return ring ? nwg : 2 * nwg; }
 // The L0X split (round 5): the training kernel ends a tile with layer 2's step and k_reni_l0_ring takes layer 1's dX GEMM, g_0, the
 // layer-0 dA and dW_1 from the g_1 stream.  Needs the ring's preconditions, the SPEC head / loss configuration and an odd number
@@ -377,63 +387,38 @@ bool l0x_rows_ok(const float* base, long long s0, long long s1, long long s2) {
   if (s1 == 3 && s2 == 1) return true;                     // interleaved: one 1536-byte run per tile
   return s1 == 1 && ((uintptr_t)(s2 * 4) & 15) == 0;      // planar: three 512-byte runs
 }
-bool l0x_ok(const reni_plan* p, const reni::MainArgs& a) {
+bool l0x_plan_ok(const reni_plan* p, const Layout& l, int64_t P, uint32_t flags) {
   const int L = p->d.hidden_layers;
-  return !p->no_l0x && dw1_ring_ok(p, a) && train_spec(a, false) && L >= 3 && (L & 1) == 1 &&
-         l0x_rows_ok(a.target, a.ts0, a.ts1, a.ts2) && l0x_rows_ok(a.weight, a.ws0, a.ws1, a.ws2);
+  return l.pdw && !p->no_l0x && dw1_ring_plan_ok(p, P) && spec_head(flags & RENI_NEED_DW, p->d.last_layer_linear, p->d.output_activation) &&
+         L >= 3 && (L & 1) == 1;
 }
+bool l0x_call_ok(const reni::MainArgs& a) {
+  return dw1_ring_call_ok(a) && train_spec(a, false) && l0x_rows_ok(a.target, a.ts0, a.ts1, a.ts2) && l0x_rows_ok(a.weight, a.ws0, a.ws1, a.ws2);
+}
+// "a side stream is allowed for this plan" -- not "this call forks": BwdPath::fork also needs !l0x and enough tiles per workgroup
+bool side_stream_plan_ok(const reni_plan* p, const Layout& l) { return l.pdw && !p->no_side_stream; }
 
 // dW_1 / db_1 from the stored g_1 stream (same grid: it fills the layer-1 slot of the same partials)
-int launch_dw1_impl(const reni::MainArgs& a, int nwg, bool ring, hipStream_t s, bool l0x);
 int launch_dw1(const reni::MainArgs& a, int nwg, bool ring, hipStream_t s, bool l0x = false) {
-  EvPair ev;
-  const bool timed = prof_begin(s, &ev, PROF_DW1);
-  const int rc = launch_dw1_impl(a, nwg, ring, s, l0x);
-  if (rc) return rc;
-  if (timed) HIP_TRY(hipEventRecord(ev.b, s));
-  return RENI_OK;
-}
-int launch_dw1_impl(const reni::MainArgs& a, int nwg, bool ring, hipStream_t s, bool l0x) {
-  if (l0x) {  // layer 0's backward + dW_1 (k_reni_l0_ring): one workgroup per range of the L0X training instance
-    void (*fr)(const reni::MainArgs) = reni::k_reni_l0_ring<128>;
 #ifdef RENI_TRACE_DW1
-    constexpr int LDSR = reni::L0Ring::LDS_BYTES + 8192;  // + the cycle trace's LDS words (build with -DRENI_L0_NSLOT=3)
+  constexpr int TRACE = 8192;  // + the cycle trace's LDS words (k_reni_l0_ring: build with -DRENI_L0_NSLOT=3)
 #else
-    constexpr int LDSR = reni::L0Ring::LDS_BYTES;
+  constexpr int TRACE = 0;
 #endif
-    HIP_TRY(hipFuncSetAttribute((const void*)fr, hipFuncAttributeMaxDynamicSharedMemorySize, LDSR));
-    RENI_LAUNCH(fr, dim3(nwg), dim3(reni::L0Ring::THREADS), LDSR, s, a);
-    HIP_TRY(hipGetLastError());
-    return RENI_OK;
-  }
-  if (a.film != nullptr) {
-    g_launches.fetch_add(1, std::memory_order_relaxed);
-    const hipError_t e = reni::launch_dw1_film(a, 2 * nwg, s);
-    if (e != hipSuccess) return fail(RENI_EHIP, "k_reni_dw1 (FiLM) launch failed: %s", hipGetErrorString(e));
-    return RENI_OK;
-  }
-  if (ring) {  // one workgroup per range, inputs through an LDS-DMA ring (k_reni_dw1_ring)
-    void (*fr)(const reni::MainArgs) = reni::k_reni_dw1_ring<128>;
-#ifdef RENI_TRACE_DW1
-    constexpr int LDSR = reni::Dw1Ring::LDS_BYTES + 8192;  // + the cycle trace's LDS words
-#else
-    constexpr int LDSR = reni::Dw1Ring::LDS_BYTES;
-#endif
-    HIP_TRY(hipFuncSetAttribute((const void*)fr, hipFuncAttributeMaxDynamicSharedMemorySize, LDSR));
-    RENI_LAUNCH(fr, dim3(nwg), dim3(reni::Dw1Ring::THREADS), LDSR, s, a);
-    HIP_TRY(hipGetLastError());
-    return RENI_OK;
-  }
-  void (*f1)(const reni::MainArgs) = reni::k_reni_dw1<128>;
-#ifdef RENI_TRACE_DW1
-  constexpr int LDS1 = 2 * reni::TS_BYTES + 8192;  // + the cycle trace's LDS words
-#else
-  constexpr int LDS1 = 2 * reni::TS_BYTES;
-#endif
-  HIP_TRY(hipFuncSetAttribute((const void*)f1, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1));
+  if (l0x)  // layer 0's backward + dW_1 (k_reni_l0_ring): one workgroup per range of the L0X training instance
+    return timed_launch(reni::k_reni_l0_ring<128>, nwg, reni::L0Ring::THREADS, reni::L0Ring::LDS_BYTES + TRACE, s, a, PROF_DW1);
+  if (a.film != nullptr) return timed_launch(s, PROF_DW1, "k_reni_dw1 (FiLM)", [&] { return reni::launch_dw1_film(a, 2 * nwg, s); });
+  if (ring)  // one workgroup per range, inputs through an LDS-DMA ring (k_reni_dw1_ring)
+    return timed_launch(reni::k_reni_dw1_ring<128>, nwg, reni::Dw1Ring::THREADS, reni::Dw1Ring::LDS_BYTES + TRACE, s, a, PROF_DW1);
   // two workgroups per range of the training kernel = two per CU (it is latency-bound at one)
-  RENI_LAUNCH(f1, dim3(2 * nwg), dim3(256), LDS1, s, a);
-  HIP_TRY(hipGetLastError());
+  return timed_launch(reni::k_reni_dw1<128>, 2 * nwg, 256, 2 * reni::TS_BYTES + TRACE, s, a, PROF_DW1);
+}
+
+// k_reduce_partials: elements [lo, hi) of `nslot` per-workgroup partials (`per_wg` floats apart; `valid`: a tag per slot, or NULL = every
+// slot counts) summed in a fixed order into out[lo .. hi)
+int reduce_partials(const float* part, size_t per_wg, int nslot, float* out, int lo, int hi, const int* valid, const reni::LayerScale& lsc,
+                    hipStream_t s) {
+  RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((hi - lo + 63) / 64)), dim3(256), 0, s, part, per_wg, nslot, out, lo, hi, valid, lsc);
   return RENI_OK;
 }
 
@@ -459,16 +444,11 @@ SideStream* side_stream() {
 
 int launch_main(const reni_plan* p, int mode, const reni::MainArgs& a, int nwg, hipStream_t s) {
   const int H = p->d.hidden_features;
-  const bool film = p->d.conditioning == RENI_COND_FILM;
-  EvPair ev;
-  const bool timed = prof_begin(s, &ev, mode == reni::MODE_FWD_BWD ? PROF_FWD_BWD : mode == reni::MODE_STATS ? PROF_STATS : PROF_FWD);
-  hipError_t e;
-  g_launches.fetch_add(1, std::memory_order_relaxed);
-  if (p->d.dtype == RENI_F32) e = film ? reni::launch_film_f32(H, mode, a, nwg, s) : reni::launch_main_f32(H, mode, a, nwg, s);
-  else e = film ? reni::launch_film_bf16(H, mode, a, nwg, s) : reni::launch_main_bf16(H, mode, a, nwg, s);
-  if (e != hipSuccess) return fail(RENI_EHIP, "fused kernel launch (H=%d) failed: %s", H, hipGetErrorString(e));
-  if (timed) HIP_TRY(hipEventRecord(ev.b, s));
-  return RENI_OK;
+  const bool film = p->d.conditioning == RENI_COND_FILM, f32 = p->d.dtype == RENI_F32;
+  return timed_launch(s, mode == reni::MODE_FWD_BWD ? PROF_FWD_BWD : mode == reni::MODE_STATS ? PROF_STATS : PROF_FWD, "fused kernel", [&] {
+    if (f32) return film ? reni::launch_film_f32(H, mode, a, nwg, s) : reni::launch_main_f32(H, mode, a, nwg, s);
+    return film ? reni::launch_film_bf16(H, mode, a, nwg, s) : reni::launch_main_bf16(H, mode, a, nwg, s);
+  });
 }
 
 // Every compute entry point runs on the device that owns its buffers and leaves the caller's current device as
@@ -558,12 +538,10 @@ int run_prologue(const reni_plan* p, const GeoRt& g, const Layout& l, int64_t B,
     const unsigned grid = (unsigned)(ga.n_prep + ga.pack_gx * n);
     if (f32) RENI_LAUNCH(reni::k_prologue<reni::PolF32>, dim3(grid), dim3(256), (size_t)p->F_in * 4, s, ga, ka);
     else RENI_LAUNCH(reni::k_prologue<reni::PolBF16>, dim3(grid), dim3(256), (size_t)p->F_in * 4, s, ga, ka);
-    HIP_TRY(hipGetLastError());
     return RENI_OK;
   }
   if (f32) RENI_LAUNCH(reni::k_pack<reni::PolF32>, dim3(16, n), dim3(256), 0, s, ka);
   else RENI_LAUNCH(reni::k_pack<reni::PolBF16>, dim3(8, n), dim3(256), 0, s, ka);
-  HIP_TRY(hipGetLastError());
   return RENI_OK;
 }
 
@@ -682,14 +660,11 @@ int build_weight_lists(const float* weight, const int64_t* wst, int64_t P, int t
                        hipStream_t s) {
   RENI_LAUNCH(reni::k_tile_flags, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, weight, (long long)wst[0], (long long)wst[1],
               (long long)wst[2], (int)P, tpi, n_tiles, d.tflag, d.imgcos, compact ? d.pcnt : (int*)nullptr);
-  HIP_TRY(hipGetLastError());
   RENI_LAUNCH(reni::k_tile_compact, dim3(1), dim3(1024), 0, s, d.tflag, (const int*)d.imgcos, tpi, n_tiles, d.tlist, d.tlist + n_tiles,
               d.tcount, compact ? (const int*)d.pcnt : (const int*)nullptr, (int)P, d.pscan, d.nlive);
-  HIP_TRY(hipGetLastError());
   if (compact) {
     RENI_LAUNCH(reni::k_pix_scatter, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, s, weight, (long long)wst[0], (long long)wst[1],
                 (long long)wst[2], (int)P, tpi, n_tiles, (const int*)d.imgcos, (const int*)d.pscan, d.plist);
-    HIP_TRY(hipGetLastError());
   }
   return RENI_OK;
 }
@@ -747,14 +722,100 @@ struct BwdCall {
   const WeightLists* lists = nullptr;
 };
 
-// everything after the prologue for the backward entry points (fio != NULL: FiLM conditioning)
-int run_backward(const reni_plan* p, const BwdCall& c) {
-  const float* Z = c.Z;
-  int rc = c.fio ? check_film(p, c.fio, true) : RENI_OK;
-  if (rc) return rc;
+// The decisions of one backward call, each taken in ONE place: bwd_path fills the record right after the layout and MainArgs exist, the
+// stages of run_backward only read it.  (Layout::pdw -- "the persistent training instance runs" -- is the layout's, see there.)
+struct BwdPath {
+  bool staged;      // this call's prologue was run by the previous call: no run_prologue, and k_tail_b checks the batch it was staged for
+  int stage;        // ... into this copy of the per-batch prologue results; the next batch goes into the other one
+  bool use_cos;     // RENITestLoss with beta != 0: the statistics pass runs (unless cos_const) and the main pass takes loss_kind 1
+  bool sparse;      // the statistics and main passes visit the listed tiles only (bwd_weight_lists binds or builds the lists)
+  bool compact;     // ... and the main pass reads each image's live pixels packed into its first tiles
+  bool cos_const;   // no statistics pass, no k_stats_image: the coefficients are the zeros the cached lists' build left
+  bool dw1_ring;    // which dW_1 kernel runs, and how many partial slots its reduction sums (dw1_slots)
+  bool l0x;         // the L0X training instance + k_reni_l0_ring: no fork, the per-image epilogue behind the ring on the one stream
+  bool fork;        // the per-image epilogue goes to the side stream, if one can be had (bwd_fork_dw1)
+  bool early_rest;  // layers >= 2 and the head are reduced apart from layer 1: alone in front of dW_1, or in k_tail_a's launch (rp_in_tail)
+  bool dp_early;    // the data-parallel step wants that early slice all-reduced on the communication stream, beside dW_1
+  bool fused_tail;  // concat decoder behind the training instance: the per-image epilogue is k_tail_a + k_tail_b
+  bool fuse_on;     // layer 1's partial reduction is not launched: it rides in k_adam2's launch (its layer-1 blocks)
+  bool fpers;       // FiLM on the H = 128 persistent instances: one partial slot per image run
+  bool red2;        // ... with weight gradients: the runs' d(freq) / d(phase) and layer 1's tagged partials in ONE launch (k_film_reduce2)
+  int n_rest;       // decoder parameters behind the first layer: what the per-workgroup partials hold
+  int n_l1;         // ... of which layer 1's (W_1 + b_1): the dW_1 kernel's own partials on the persistent path
+  // Resolved where the resource is acquired -- side_stream() can return NULL, an event or a collective is only then on record -- by
+  // bwd_fork_dw1; false until then:
+  bool rp_in_tail;     // the partial reduction of layers >= 2 is part of k_tail_a's launch
+  bool ev_rest_done;   // the caller's grad-ready event was recorded at the early point (else: at the call's end)
+  bool dp_early_done;  // reni_train_step_rows_dp: the early slice's all-reduce is on the side stream (the final exchange leaves it out)
+};
+
+// What the stages of run_backward share.
+struct Bwd {
+  const reni_plan* p;
+  const BwdCall& c;
+  GeoRt g; Layout l; reni::MainArgs a;
+  char* ws;                // the workspace base
+  hipStream_t s, se;       // the caller's stream; the side stream once forked (else = s)
+  const float* Z;          // the call's latents: the batch's rows, gathered by k_prep_image, when the call came with a table and indices
+  int stage_in;            // the copy the previous call staged this call's prologue into, -1: it staged none
+  float *img_loss, *stats, *dA, *part2;
+  ListDst ld;
+  reni::LayerScale lsc;
+  BwdPath path;
+};
+
+bool call_uses_cos(const BwdCall& c) { return c.loss_kind == RENI_LOSS_TEST && c.beta != 0.f; }  // RENITestLoss's cosine term is live
+
+BwdPath bwd_path(const reni_plan* p, const Layout& l, const BwdCall& c, const reni::MainArgs& a, int stage_in) {
+  BwdPath t{};
+  const int H = p->d.hidden_features, L = p->d.hidden_layers;
+  const bool need_dw = (c.flags & RENI_NEED_DW) != 0;
+  t.staged = stage_in >= 0;
+  t.stage = t.staged ? stage_in : 0;
+  t.n_rest = (int)(p->n_params - p->n_first);
+  t.n_l1 = H * H + H;
+  t.use_cos = call_uses_cos(c);
+  // RENI_WEIGHT_SPARSE with a frozen concat decoder: the tiles that can change the result, listed on the device from the
+  // weight (k_tile_flags, k_tile_compact: two small launches); the statistics pass visits the images whose cosine term is not a
+  // constant, the main pass the tiles with a non-zero weight and those images.  Same results (skipped records would be exact zeros).
+  // (not when the output image is wanted: the tiles left out would leave holes in it)
+  t.sparse = (c.flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT)) && !c.fio && !need_dw && c.loss_kind != LOSS_DOUT &&
+             c.weight != nullptr && c.out == nullptr;  // (every concat kernel with a frozen decoder: persistent and generic, fp32 and bf16)
+  t.compact = t.sparse && (c.flags & RENI_WEIGHT_COMPACT);  // + the pixels with weight packed into each image's first tiles
+  // RENI_WEIGHT_COS_CONSTANT (cached lists whose build reported NO image with a live cosine term -- every mask of data/Masks: pixel 0
+  // is masked): the statistics instance would visit nothing and k_stats_image would write B rows of zero coefficients; both launches
+  // are left out and the coefficients are the zeros the build left in the lists buffer.  Same bits.
+  t.cos_const = t.sparse && c.lists && (c.lists->flags & RENI_WEIGHT_COS_CONSTANT);
+  t.dw1_ring = dw1_ring_plan_ok(p, c.P) && dw1_ring_call_ok(a);
+  t.l0x = l0x_plan_ok(p, l, c.P, c.flags) && l0x_call_ok(a);  // (decided once: the training kernel, the ring and the tail's order follow it)
+  // persistent path: fork.  `s` continues with k_reni_dw1 -> weight-gradient reduction -> first-layer weight tail;
+  // `se` (side stream) takes everything that only needs the per-tile partials; joined before returning.
+  // (small problems -- fewer than eight tiles per workgroup: the multi-resolution curriculum's first stages -- stay on ONE stream:
+  // k_reni_dw1 is then a few microseconds, and the fork's and the join's cross-stream edges (~12 us each) cost more than it hides)
+  // (L0X: the per-image epilogue needs k_reni_l0_ring's dA runs, so it runs BEHIND it on the one stream -- that kernel leaves no
+  // registers for a neighbour anyway -- and the partial reduction of layers >= 2 rides in k_tail_a's launch)
+  t.fork = side_stream_plan_ok(p, l) && !t.l0x && (c.fio || l.n_tiles >= 8 * l.nwg);
+  t.early_rest = l.pdw && !c.fio && need_dw && L >= 1 && t.n_rest > t.n_l1;
+  t.dp_early = c.fuse && c.fuse->comm && c.fuse->overlap;  // (its early slice is what the early reduction produces)
+  t.fused_tail = l.pdw && !c.fio;
+  // reni_train_step_rows on that path: layer 1's partial reduction is not launched -- it rides in the Adam launch behind the call's
+  // work (k_adam2's layer-1 blocks)
+  // (not with a data-parallel exchange inside the call: the collective needs layer 1's sum in the gradient buffer first)
+  t.fuse_on = c.fuse && !c.fuse->comm && t.fused_tail && need_dw && (c.flags & RENI_NEED_DZ) && L >= 1;
+  // (fpers: the H = 128 persistent FiLM instances' bookkeeping -- one partial slot per image run; k_reni_wide256<2, FILM> feeds the
+  //  stream path's consumers, whose bookkeeping is the generic chain's)
+  t.fpers = l.persist && !l.wide_train;
+  // persistent path with weight gradients: the runs' d(freq) / d(phase) sums and layer 1's tagged partials in one launch
+  t.red2 = L > 0 && t.fpers && need_dw;
+  return t;
+}
+
+// the argument checks, and the kernels' geometry
+int bwd_validate(Bwd& x) {
+  const reni_plan* p = x.p; const BwdCall& c = x.c;
+  if (const int rc = c.fio ? check_film(p, c.fio, true) : RENI_OK) return rc;
   if (!c.fio && p && p->d.conditioning != RENI_COND_CONCAT) return fail(RENI_EINVAL, "FiLM plan: use the reni_film_* entry points");
-  rc = check_common(p, c.B, c.P, c.fio ? c.fio->A : Z, c.D, c.params, c.ws);
-  if (rc) return rc;
+  if (const int rc = check_common(p, c.B, c.P, c.fio ? c.fio->A : c.Z, c.D, c.params, c.ws)) return rc;
   if ((c.flags & RENI_NEED_DW) && !c.dparams) return fail(RENI_EINVAL, "RENI_NEED_DW set but dparams is NULL");
   if (!c.fio && (c.flags & RENI_NEED_DZ) && !c.dZ) return fail(RENI_EINVAL, "RENI_NEED_DZ set but dZ is NULL");
   if (c.loss_kind == LOSS_DOUT) {
@@ -764,25 +825,34 @@ int run_backward(const reni_plan* p, const BwdCall& c) {
     if (!c.target || !c.weight || !c.ts || !c.wst) return fail(RENI_EINVAL, "target/weight (and their strides) must be non-NULL");
     if (!c.loss_terms) return fail(RENI_EINVAL, "loss_terms is NULL");
   }
-  GeoRt g;
-  if (!geo_for(p, &g)) return fail(RENI_EUNSUPPORTED, "hidden_features=%d unsupported", p->d.hidden_features);
-  DeviceGuard dev_guard;
-  rc = dev_guard.enter(c.params);
-  if (rc) return rc;
+  if (!geo_for(p, &x.g)) return fail(RENI_EUNSUPPORTED, "hidden_features=%d unsupported", p->d.hidden_features);
+  return RENI_OK;
+}
+
+// the layout (in the stage copy a staged step's prologue went to), the workspace check, the per-image buffers
+int bwd_layout(Bwd& x) {
+  const BwdCall& c = x.c;
   const bool staged = c.fuse && (*c.fuse->state & 1u);          // this call's prologue was run by the previous call
-  const int stage = staged ? (int)((*c.fuse->state >> 1) & 1u) : 0;
-  const Layout l = make_layout(p, g, c.B, c.P, c.flags, true, true, stage);
+  x.stage_in = staged ? (int)((*c.fuse->state >> 1) & 1u) : -1;
+  x.l = make_layout(x.p, x.g, c.B, c.P, c.flags, true, true, staged ? x.stage_in : 0);
+  const Layout& l = x.l;
   if (c.ws_bytes < l.total) return fail(RENI_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", l.total, c.ws_bytes);
-  char* ws = (char*)c.ws;
-  hipStream_t s = (hipStream_t)c.stream;
-  const int H = p->d.hidden_features;
   if (c.fuse) *c.fuse->state = 0;  // (whatever happens below: nothing is staged until this call has staged it)
-  // the constants the weight-gradient partials carry when the W^T images are 8 x the forward images (Layout::consistent_bwd; derivation:
-  // DESIGN.md section 4.2f): hidden layer l: (omega_hidden / omega_first) (8 / 2 pi)^l, head: 1 / gy_scale.  Ones otherwise.
-  reni::LayerScale lsc;
-  lsc.n_hid = H * H + H; lsc.L = p->d.hidden_layers;
+  x.ws = (char*)c.ws;
+  x.s = x.se = (hipStream_t)c.stream;
+  x.Z = c.idx ? (const float*)(x.ws + l.o_Zc) : c.Z;  // behind the prologue: the batch's rows, gathered by k_prep_image
+  x.img_loss = (float*)(x.ws + l.o_img_loss); x.stats = (float*)(x.ws + l.o_stats);
+  x.dA = c.fio ? c.fio->dA : (float*)(x.ws + l.o_dA); x.part2 = (float*)(x.ws + l.o_part2);
+  return RENI_OK;
+}
+
+// the constants the weight-gradient partials carry when the W^T images are 8 x the forward images (Layout::consistent_bwd; derivation:
+// DESIGN.md section 4.2f): hidden layer l: (omega_hidden / omega_first) (8 / 2 pi)^l, head: 1 / gy_scale.  Ones otherwise.
+void bwd_layer_scales(Bwd& x) {
+  const reni_plan* p = x.p; reni::LayerScale& lsc = x.lsc;
+  lsc.n_hid = p->d.hidden_features * p->d.hidden_features + p->d.hidden_features; lsc.L = p->d.hidden_layers;
   for (int i = 0; i <= reni::MAX_LAYERS; ++i) lsc.c[i] = 1.f;
-  if (l.consistent_bwd && (c.flags & RENI_NEED_DW)) {
+  if (x.l.consistent_bwd && (x.c.flags & RENI_NEED_DW)) {
     double gy = (double)p->d.first_omega_0 / 8.0, cl = (double)p->d.hidden_omega_0 / (double)p->d.first_omega_0;
     for (int i = 0; i < p->d.hidden_layers; ++i) {
       gy *= 6.283185307179586 / 8.0;
@@ -791,15 +861,12 @@ int run_backward(const reni_plan* p, const BwdCall& c) {
     }
     lsc.c[p->d.hidden_layers] = (float)(1.0 / gy);
   }
+}
 
-  if (!staged) {
-    rc = run_prologue(p, g, l, c.B, Z, c.params, ws, true, s, c.idx, c.fio ? c.fio->A : nullptr, c.n_rows);
-    if (rc) return rc;
-  }
-  if (c.idx) Z = (const float*)(ws + l.o_Zc);  // from here on: the batch's rows, gathered by k_prep_image
-
-  reni::MainArgs a;
-  fill_main_args(a, p, l, c.B, c.P, Z, c.D, c.dbs, ws);
+// what the main pass takes (host work only: the pointers are the layout's), then the call's decisions from it
+void bwd_main_args(Bwd& x) {
+  const BwdCall& c = x.c; reni::MainArgs& a = x.a;
+  fill_main_args(a, x.p, x.l, c.B, c.P, x.Z, c.D, c.dbs, x.ws);
   if (c.fio) { a.Apre = c.fio->A; a.film = c.fio->film; a.params = c.params; a.Z = nullptr; }
   a.need_dw = (c.flags & RENI_NEED_DW) ? 1 : 0;
 #ifdef RENI_DEBUG  // diagnostic builds only (build.sh -DRENI_DEBUG): the ablation mask skips work, i.e. yields WRONG results
@@ -813,348 +880,306 @@ int run_backward(const reni_plan* p, const BwdCall& c) {
     a.target = c.target; a.ts0 = c.ts[0]; a.ts1 = c.ts[1]; a.ts2 = c.ts[2];
     a.weight = c.weight; a.ws0 = c.wst[0]; a.ws1 = c.wst[1]; a.ws2 = c.wst[2];
   }
-  float* img_loss = (float*)(ws + l.o_img_loss);
-  float* stats = (float*)(ws + l.o_stats);
-  float* dA = c.fio ? c.fio->dA : (float*)(ws + l.o_dA);
-  float* part2 = (float*)(ws + l.o_part2);
-  const bool use_cos = (c.loss_kind == RENI_LOSS_TEST) && (c.beta != 0.f);
-  // RENI_WEIGHT_SPARSE with a frozen concat decoder: the tiles that can change the result, listed on the device from the
-  // weight (k_tile_flags, k_tile_compact: two small launches); the statistics pass visits the images whose cosine term is not a
-  // constant, the main pass the tiles with a non-zero weight and those images.  Same results (skipped records would be exact zeros).
-  // (not when the output image is wanted: the tiles left out would leave holes in it)
-  const bool sparse = (c.flags & (RENI_WEIGHT_SPARSE | RENI_WEIGHT_COMPACT)) && !c.fio && !(c.flags & RENI_NEED_DW) && c.loss_kind != LOSS_DOUT &&
-                      c.weight != nullptr && c.out == nullptr;  // (every concat kernel with a frozen decoder: persistent and generic, fp32 and bf16)
-  const bool compact = sparse && (c.flags & RENI_WEIGHT_COMPACT);  // + the pixels with weight packed into each image's first tiles
-  ListDst ld{};
-  if (sparse) {
-    if (c.lists) {
-      // the caller's lists (reni_weight_lists_build for this B, P and these flags): no launch, no read of the weight
-      ld = list_dst(const_cast<char*>(c.lists->buf), make_list_layout(c.B, c.P));
-    } else {
-      ld = list_dst(ws, l);
-      rc = build_weight_lists(c.weight, c.wst, c.P, l.tpi, l.n_tiles, compact, ld, s);
+  a.loss_kind = (c.loss_kind == LOSS_DOUT) ? LOSS_DOUT : (call_uses_cos(c) ? 1 : 0);  // (the statistics pass takes a copy with its own)
+  x.path = bwd_path(x.p, x.l, c, a, x.stage_in);
+}
+
+// BwdPath::sparse: bind the caller's cached lists or build them in the workspace; BwdPath::cos_const: the cached zero coefficients
+int bwd_weight_lists(Bwd& x) {
+  const BwdCall& c = x.c; const BwdPath& path = x.path; reni::MainArgs& a = x.a;
+  if (!path.sparse) return RENI_OK;
+  if (c.lists) {
+    // the caller's lists (reni_weight_lists_build for this B, P and these flags): no launch, no read of the weight
+    x.ld = list_dst(const_cast<char*>(c.lists->buf), make_list_layout(c.B, c.P));
+  } else {
+    x.ld = list_dst(x.ws, x.l);
+    if (const int rc = build_weight_lists(c.weight, c.wst, c.P, x.l.tpi, x.l.n_tiles, path.compact, x.ld, x.s)) return rc;
+  }
+  a.tlist = x.ld.tlist; a.tcount = x.ld.tcount;
+  if (path.compact) { a.plist = x.ld.plist; a.nlive = x.ld.nlive; }
+  if (path.cos_const) a.stats = x.stats = (float*)(const_cast<char*>(c.lists->buf) + make_list_layout(c.B, c.P).o_zstats);
+  return RENI_OK;
+}
+
+// RENITestLoss's cosine term: the statistics of every image, then their coefficients
+int bwd_stats_pass(Bwd& x) {
+  const BwdCall& c = x.c; const Layout& l = x.l;
+  if (!x.path.use_cos || x.path.cos_const) return RENI_OK;
+  reni::MainArgs st = x.a;
+  st.out = nullptr; st.loss_kind = 0;
+  if (x.path.sparse) { st.tlist = x.a.tlist + l.n_tiles; st.tcount = x.a.tcount + 1; }
+  // persistent path: the forward-only statistics instance of the same kernel, on the same pre-scaled weight images
+  if (const int rc = l.persist ? launch_train(x.p, st, l.nwg, x.s, true) : launch_main(x.p, reni::MODE_STATS, st, l.nwg, x.s)) return rc;
+  // the statistics of every image and their cosine coefficients: one launch (k_stats_image; it was three)
+  RENI_LAUNCH(reni::k_stats_image, dim3((unsigned)c.B), dim3(256), 0, x.s, (const float*)x.a.loss_part, l.tpi, c.weight, (long long)c.wst[0],
+                     (long long)c.wst[2], c.beta, x.img_loss, x.stats, (const int*)x.ld.imgcos);
+  return RENI_OK;
+}
+
+// Whatever path leaves run_backward after the fork -- the joins at its end or an early error return -- the caller's stream waits for
+// the side stream: a forked stream left un-joined would let the caller's next launch overtake work that reads its buffers.
+struct SideJoin {
+  SideStream* side = nullptr;
+  hipStream_t s = nullptr;
+  ~SideJoin() { if (side && hipEventRecord(side->ev[2], side->s) == hipSuccess) (void)hipStreamWaitEvent(s, side->ev[2], 0); }
+};
+
+// Behind the persistent training instance: the fork (BwdPath::fork), the early reduction of layers >= 2 with what hangs on it, the dW_1
+// kernel.  Resolves rp_in_tail, ev_rest_done and dp_early_done.
+int bwd_fork_dw1(Bwd& x, std::unique_lock<std::mutex>& side_lock, SideJoin& side_join) {
+  const reni_plan* p = x.p; const BwdCall& c = x.c; const Layout& l = x.l; BwdPath& path = x.path; hipStream_t s = x.s;
+  if (!l.pdw) return RENI_OK;
+  SideStream* side = path.fork ? side_stream() : nullptr;
+  if (side) {
+    side_lock.lock();  // (the events are per device: one fork/join is enqueued at a time)
+    HIP_TRY(hipEventRecord(side->ev[0], s));
+    HIP_TRY(hipStreamWaitEvent(side->s, side->ev[0], 0));
+    x.se = side->s;
+    side_join.side = side; side_join.s = s;
+  }
+  // The partials of layers >= 2 (85 MB at the BASELINE shape; final when the training kernel ends) are reduced HERE, alone on
+  // the device for 18 us: beside k_reni_dw1 the reduction took 116 us and slowed it by 25, and behind the latent tails of the
+  // side stream it was the end of the longer chain (profiles/r03_step_timeline_c2.txt).
+  // (one stream: the reduction's blocks ride in k_tail_a's launch -- bwd_epilogue_concat)
+  path.rp_in_tail = path.early_rest && !side && !g_ev_rest && !path.dp_early;
+  if (path.early_rest && !path.rp_in_tail) {
+    // (alone in front of k_reni_dw1, not beside it on a stream of its own: measured again in round 4 with the fused epilogue --
+    // beside, everything crawls and the step is 30 us longer: profiles/r04_tail.md)
+    int rc = reduce_partials(x.a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, path.n_l1, path.n_rest, nullptr, x.lsc, s);
+    if (rc) return rc;
+    // the gradient of layers >= 2 and of the head is final HERE, a whole k_reni_dw1 before the call ends: a data-parallel caller
+    // starts their all-reduce on another stream behind this event (TrainEngine(overlap_comm=True))
+    if (g_ev_rest) { HIP_TRY(hipEventRecord(g_ev_rest, s)); path.ev_rest_done = true; }
+    if (path.dp_early) {
+      // reni_train_step_rows_dp(overlap): the slice [n_first + n_l1, n_params) -- layers >= 2 and the head, 28 % of the gradient at
+      // config 2 -- is final HERE: its all-reduce starts on the library's communication stream, beside the ring kernel and the
+      // per-image epilogue; the optimiser launch waits for it below.  (Same order of collectives on every rank: early slice, then rest.)
+      SideStream* cs = side_stream();
+      if (!cs) return fail(RENI_EHIP, "no communication stream");
+      if (!side_lock.owns_lock()) side_lock.lock();
+      HIP_TRY(hipEventRecord(cs->ev[1], s));
+      HIP_TRY(hipStreamWaitEvent(cs->s, cs->ev[1], 0));
+      rc = rccl_allreduce_inplace(c.fuse->comm, c.dparams + p->n_first + path.n_l1, (size_t)(path.n_rest - path.n_l1), cs->s);
       if (rc) return rc;
+      if (!side_join.side) { side_join.side = cs; side_join.s = s; }  // (joined like the forked epilogue: whatever path leaves)
+      path.dp_early_done = true;
     }
-    a.tlist = ld.tlist; a.tcount = ld.tcount;
-    if (compact) { a.plist = ld.plist; a.nlive = ld.nlive; }
   }
-  // RENI_WEIGHT_COS_CONSTANT (cached lists whose build reported NO image with a live cosine term -- every mask of data/Masks: pixel 0
-  // is masked): the statistics instance would visit nothing and k_stats_image would write B rows of zero coefficients; both launches
-  // are left out and the coefficients are the zeros the build left in the lists buffer.  Same bits.
-  const bool cos_const = sparse && c.lists && (c.lists->flags & RENI_WEIGHT_COS_CONSTANT);
-  if (cos_const) stats = (float*)(const_cast<char*>(c.lists->buf) + make_list_layout(c.B, c.P).o_zstats);
-  if (cos_const) a.stats = stats;
-  if (use_cos && !cos_const) {
-    reni::MainArgs st = a;
-    st.out = nullptr; st.loss_kind = 0;
-    if (sparse) { st.tlist = a.tlist + l.n_tiles; st.tcount = a.tcount + 1; }
-    // persistent path: the forward-only statistics instance of the same kernel, on the same pre-scaled weight images
-    rc = l.persist ? launch_train(p, st, l.nwg, s, true) : launch_main(p, reni::MODE_STATS, st, l.nwg, s);
-    if (rc) return rc;
-    // the statistics of every image and their cosine coefficients: one launch (k_stats_image; it was three)
-    RENI_LAUNCH(reni::k_stats_image, dim3((unsigned)c.B), dim3(256), 0, s, (const float*)a.loss_part, l.tpi, c.weight, (long long)c.wst[0],
-                       (long long)c.wst[2], c.beta, img_loss, stats, (const int*)ld.imgcos);
-    HIP_TRY(hipGetLastError());
-  }
-  a.loss_kind = (c.loss_kind == LOSS_DOUT) ? LOSS_DOUT : (use_cos ? 1 : 0);
-  const bool l0x = l.persist && !l.wide_train && (c.flags & RENI_NEED_DW) && !c.fio && l0x_ok(p, a);  // (decided once: the training kernel, the ring and the tail's order follow it)
-  rc = l.persist ? launch_train(p, a, l.nwg, s, false, l0x) : launch_main(p, reni::MODE_FWD_BWD, a, l.nwg, s);
-  if (rc) return rc;
-  // persistent path: fork.  `s` continues with k_reni_dw1 -> weight-gradient reduction -> first-layer weight tail;
-  // `se` (side stream) takes everything that only needs the per-tile partials; joined before returning.
-  hipStream_t se = s;
-  const bool pdw = l.persist && !l.wide_train && (a.need_dw || c.fio);  // the training instance ran: image runs, g_1 stream, k_reni_dw1
-  const bool dw1_ring = dw1_ring_ok(p, a);           // which dW_1 kernel (and how many partial slots its reduction sums)
-  bool ev_rest_done = false;
-  bool dp_early_done = false;                        // reni_train_step_rows_dp: the early slice's all-reduce is on the side stream
-  bool rp_in_tail = false;                           // the partial reduction of layers >= 2 is part of k_tail_a's launch
-  const bool fused_tail0 = pdw && !c.fio;
-  // (small problems -- fewer than eight tiles per workgroup: the multi-resolution curriculum's first stages -- stay on ONE stream:
-  // k_reni_dw1 is then a few microseconds, and the fork's and the join's cross-stream edges (~12 us each) cost more than it hides)
-  // (L0X: the per-image epilogue needs k_reni_l0_ring's dA runs, so it runs BEHIND it on the one stream -- that kernel leaves no
-  // registers for a neighbour anyway -- and the partial reduction of layers >= 2 rides in k_tail_a's launch)
-  const bool fork = pdw && !l0x && !p->no_side_stream && (c.fio || l.n_tiles >= 8 * l.nwg);
-  SideStream* side = fork ? side_stream() : nullptr;
-  std::unique_lock<std::mutex> side_lock(g_side_mu, std::defer_lock);  // (the events are per device: one fork/join is enqueued at a time)
-  if (side) side_lock.lock();
-  // Whatever path leaves this function after the fork -- the joins below or an early error return -- the caller's stream waits for
-  // the side stream: a forked stream left un-joined would let the caller's next launch overtake work that reads its buffers.
-  struct SideJoin {
-    SideStream* side = nullptr;
-    hipStream_t s = nullptr;
-    ~SideJoin() {
-      if (side && hipEventRecord(side->ev[2], side->s) == hipSuccess) (void)hipStreamWaitEvent(s, side->ev[2], 0);
-    }
-  } side_join;
-  if (pdw) {
-    if (side) {
-      HIP_TRY(hipEventRecord(side->ev[0], s));
-      HIP_TRY(hipStreamWaitEvent(side->s, side->ev[0], 0));
-      se = side->s;
-      side_join.side = side; side_join.s = s;
-    }
-    if (!c.fio && (c.flags & RENI_NEED_DW) && p->d.hidden_layers >= 1) {
-      // The partials of layers >= 2 (85 MB at the BASELINE shape; final when the training kernel ends) are reduced HERE, alone on
-      // the device for 18 us: beside k_reni_dw1 the reduction took 116 us and slowed it by 25, and behind the latent tails of the
-      // side stream it was the end of the longer chain (profiles/r03_step_timeline_c2.txt).
-      const int n_rest = (int)(p->n_params - p->n_first), n_l1 = H * H + H;
-      // (one stream: the reduction's blocks ride in k_tail_a's launch, below)
-      const bool dp_early = c.fuse && c.fuse->comm && c.fuse->overlap;  // (its early slice is what this reduction produces)
-      rp_in_tail = !side && fused_tail0 && n_rest > n_l1 && !g_ev_rest && !dp_early;
-      if (n_rest > n_l1 && !rp_in_tail) {
-        // (alone in front of k_reni_dw1, not beside it on a stream of its own: measured again in round 4 with the fused epilogue --
-        // beside, everything crawls and the step is 30 us longer: profiles/r04_tail.md)
-        hipStream_t sr = s;
-        RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_rest - n_l1 + 63) / 64)), dim3(256), 0, sr,
-                           (const float*)a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, n_l1, n_rest, (const int*)nullptr, lsc);
-        HIP_TRY(hipGetLastError());
-        // the gradient of layers >= 2 and of the head is final HERE, a whole k_reni_dw1 before the call ends: a data-parallel caller
-        // starts their all-reduce on another stream behind this event (TrainEngine(overlap_comm=True))
-        if (g_ev_rest) { HIP_TRY(hipEventRecord(g_ev_rest, sr)); ev_rest_done = true; }
-        if (dp_early) {
-          // reni_train_step_rows_dp(overlap): the slice [n_first + n_l1, n_params) -- layers >= 2 and the head, 28 % of the gradient at
-          // config 2 -- is final HERE: its all-reduce starts on the library's communication stream, beside the ring kernel and the
-          // per-image epilogue; the optimiser launch waits for it below.  (Same order of collectives on every rank: early slice, then rest.)
-          SideStream* cs = side_stream();
-          if (!cs) return fail(RENI_EHIP, "no communication stream");
-          if (!side_lock.owns_lock()) side_lock.lock();
-          HIP_TRY(hipEventRecord(cs->ev[1], sr));
-          HIP_TRY(hipStreamWaitEvent(cs->s, cs->ev[1], 0));
-          rc = rccl_allreduce_inplace(c.fuse->comm, c.dparams + p->n_first + n_l1, (size_t)(n_rest - n_l1), cs->s);
-          if (rc) return rc;
-          if (!side_join.side) { side_join.side = cs; side_join.s = s; }  // (joined like the forked epilogue: whatever path leaves)
-          dp_early_done = true;
-        }
-      }
-    }
-    rc = launch_dw1(a, l.nwg, dw1_ring, s, l0x);
-    if (rc) return rc;
-  }
+  return launch_dw1(x.a, l.nwg, path.dw1_ring, s, path.l0x);
+}
+
+// the weight-gradient consumers of the fragment / operand streams (the paths that do not keep the sums in registers)
+int bwd_dw_consumers(Bwd& x) {
+  const Layout& l = x.l; const reni::MainArgs& a = x.a; hipStream_t s = x.s;
+  const int H = x.p->d.hidden_features;
   if (l.frag == 2) {  // fp32, H = 256: hidden-layer weight gradients from the fp32 fragment stream
-    void (*fn)(const reni::MainArgs) = reni::k_dw_frag32<256>;
     const int lds = 4 * ((reni::Geo<reni::PolF32, 256>::T_BYTES + 1023) & ~1023);
-    HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    EvPair ev;
-    const bool timed = prof_begin(s, &ev, PROF_DWS);
-    RENI_LAUNCH(fn, dim3(l.nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    if (timed) HIP_TRY(hipEventRecord(ev.b, s));
+    if (const int rc = timed_launch(reni::k_dw_frag32<256>, l.nwg, 256, lds, s, a, PROF_DWS)) return rc;
   }
-  if (l.wide_train && (c.flags & RENI_NEED_DW)) {  // the head's weight gradient from k_reni_wide256<2>'s g_y stream and phase stash (a frozen FiLM decoder: no partials to write)
-    g_launches.fetch_add(1, std::memory_order_relaxed);
-    EvPair ev;
-    const bool timed = prof_begin(s, &ev, PROF_DWS);
-    const hipError_t e = reni::launch_wide_head_dw(a, l.nwg, s);
-    if (e != hipSuccess) return fail(RENI_EHIP, "k_wide_head_dw launch failed: %s", hipGetErrorString(e));
-    if (timed) HIP_TRY(hipEventRecord(ev.b, s));
+  if (l.wide_train && (x.c.flags & RENI_NEED_DW)) {  // the head's weight gradient from k_reni_wide256<2>'s g_y stream and phase stash (a frozen FiLM decoder: no partials to write)
+    if (const int rc = timed_launch(s, PROF_DWS, "k_wide_head_dw", [&] { return reni::launch_wide_head_dw(a, l.nwg, s); })) return rc;
   }
   if (l.stream) {  // hidden-layer weight gradients (and FiLM d(freq), d(phase)) from the operand stream
     static_assert(reni::Geo<reni::PolBF16, 256>::T_BYTES_AL == 36864 && reni::Geo<reni::PolBF16, 128>::T_BYTES_AL == 34816,
                   "stream record sizes (make_layout)");
-    const bool film = c.fio != nullptr;
+    const bool film = x.c.fio != nullptr;
     void (*fn)(const reni::MainArgs) = nullptr;
     if (H == 256) fn = film ? reni::k_dw_frag<256, true> : reni::k_dw_frag<256, false>;
     else fn = film ? reni::k_dw_stream<128, true> : reni::k_dw_stream<128, false>;
-    const int lds = 4 * (H == 256 ? 36864 : 34816);
     if (film) HIP_TRY(hipMemsetAsync(a.run_image, 0xff, (size_t)l.nwg * l.kmax * 4, s));
-    HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    EvPair ev;
-    const bool timed = prof_begin(s, &ev, PROF_DWS);
-    RENI_LAUNCH(fn, dim3(l.nwg), dim3(256), lds, s, a);
-    HIP_TRY(hipGetLastError());
-    if (timed) HIP_TRY(hipEventRecord(ev.b, s));
+    return timed_launch(fn, l.nwg, 256, 4 * (H == 256 ? 36864 : 34816), s, a, PROF_DWS);
   }
-  const bool fused_tail = pdw && !c.fio;  // concat decoder on the persistent path: the per-image epilogue is k_tail_a + k_tail_b, below
-  // reni_train_step_rows on that path: layer 1's partial reduction is not launched -- it rides in the Adam launch behind the call's
-  // work (k_adam2's layer-1 blocks)
-  // (not with a data-parallel exchange inside the call: the collective needs layer 1's sum in the gradient buffer first)
-  const bool fuse_on = c.fuse && !c.fuse->comm && fused_tail && (c.flags & RENI_NEED_DW) && (c.flags & RENI_NEED_DZ) && p->d.hidden_layers >= 1;
-  if (fused_tail) {
-  } else if (pdw) {  // the training instance keeps the per-image sums on chip: a few image runs per image
-    RENI_LAUNCH(reni::k_reduce_runs, dim3((unsigned)c.B, c.B < 16 ? (unsigned)((H * 8 + 16 + 63) / 64) : 1u), dim3(256), 0, se, (const float*)a.pruns, (const int*)a.prun_image,
-                       l.nwg, l.pkmax, H, l.tpi, l.n_tiles, dA, img_loss);
-    HIP_TRY(hipGetLastError());
-  } else {
-    RENI_LAUNCH(reni::k_reduce_tiles_a, dim3((unsigned)c.B, (unsigned)l.nch), dim3(256), 0, se, (const float*)a.dA_part,
-                       (const float*)a.loss_part, l.tpi, H, part2, 1, l.rt_chunk, (const int*)ld.tflag);
-    HIP_TRY(hipGetLastError());
-    RENI_LAUNCH(reni::k_reduce_tiles_b, dim3((unsigned)c.B, (unsigned)((H * 8 + 16 + 255) / 256)), dim3(256), 0, se, (const float*)part2, l.nch, H, dA, img_loss, 1);
-    HIP_TRY(hipGetLastError());
-  }
+  return RENI_OK;
+}
 
-  if (c.fio) {
-    // (persistent path: `s` carries k_reni_dw1 and what needs its runs -- d(freq) / d(phase), layer 1's weight gradient;
-    // `se` what needs the training kernel only -- dA, the loss, the other layers' weight gradients)
-    const int L = p->d.hidden_layers;
-    // (fpers: the H = 128 persistent FiLM instances' bookkeeping -- one partial slot per image run; k_reni_wide256<2, FILM> feeds the
-    //  stream path's consumers, whose bookkeeping is the generic chain's)
-    const bool fpers = l.persist && !l.wide_train;
-    // persistent path with weight gradients: the runs' d(freq) / d(phase) sums and layer 1's tagged partials in one launch, below
-    const bool red2 = L > 0 && fpers && (c.flags & RENI_NEED_DW);
-    if (red2) {
-    } else if (L > 0 && (l.stream || fpers)) {
-      RENI_LAUNCH(reni::k_reduce_film_runs, dim3((unsigned)c.B, (unsigned)((L * H + 255) / 256)), dim3(256), 0, s, a, H,
-                         fpers ? 3 * l.nwg * l.pkmax : l.nwg * l.kmax, c.fio->dfilm);
-      HIP_TRY(hipGetLastError());
-    } else if (L > 0) {
-      RENI_LAUNCH(reni::k_reduce_film, dim3((unsigned)c.B, (unsigned)((L * 2 * H + 255) / 256)), dim3(256), 0, s,
-                         (const float*)a.dfp_part, l.tpi, L * 2 * H, c.fio->dfilm);
-      HIP_TRY(hipGetLastError());
-    }
-    if (c.flags & RENI_NEED_DW) {
-      // the first layer's gradient belongs to the glue (it is a function of dA): zero its slot unless the caller
-      // (reni_film_model_*) fills it
-      if (!c.fio->keep_first) HIP_TRY(hipMemsetAsync(c.dparams, 0, (size_t)p->n_first * 4, s));
-      const int n_rest = (int)(p->n_params - p->n_first);
-      if (fpers) {  // one partial slot per image run: layer 1 from k_reni_dw1's runs, the rest from the training kernel's
-        const int n_l1 = H * H + H, nslot = l.nwg * l.pkmax;
-        reni::FilmReduce2 r2;
-        r2.H = H; r2.nruns = 3 * l.nwg * l.pkmax; r2.B = (int)c.B; r2.gy = (L * H + 255) / 256; r2.dfilm = c.fio->dfilm;
-        r2.part = a.dw1p; r2.per_wg = (size_t)n_l1; r2.nslot = 2 * nslot; r2.dparams = c.dparams + p->n_first; r2.n = n_l1;
-        r2.valid = (const int*)a.prun_image + nslot;
-        RENI_LAUNCH(reni::k_film_reduce2, dim3((unsigned)(r2.B * r2.gy + (n_l1 + 63) / 64)), dim3(256), 0, s, a, r2);
-        HIP_TRY(hipGetLastError());
-        RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_rest - n_l1 + 63) / 64)), dim3(256), 0, se,
-                           (const float*)a.dwp, l.dwp_per_wg, nslot, c.dparams + p->n_first, n_l1, n_rest, (const int*)a.prun_image, lsc);
-        HIP_TRY(hipGetLastError());
-      } else {
-        RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_rest + 63) / 64)), dim3(256), 0, s,
-                           (const float*)a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, 0, n_rest, (const int*)nullptr, lsc);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    if (c.loss_kind != LOSS_DOUT) {
-      RENI_LAUNCH(reni::k_finalize_loss, dim3(1), dim3(256), 0, se, (const float*)img_loss, (const float*)stats,
-                         c.fio->Zp, (int)c.B, (int)c.P, (int)c.fio->nz, use_cos ? 1 : 0,
-                         (c.fio->Zp != nullptr && c.loss_kind == RENI_LOSS_TEST) ? 1 : 0, c.fio->alpha, c.beta, c.loss_terms);
-      HIP_TRY(hipGetLastError());
-    }
-    return RENI_OK;  // (joined by side_join)
+// the per-image sums -- dA_b and the loss -- of every path but the fused tail's (whose k_tail_a forms them): on `se`
+int bwd_image_sums(Bwd& x) {
+  const BwdCall& c = x.c; const Layout& l = x.l; const reni::MainArgs& a = x.a;
+  const int H = x.p->d.hidden_features;
+  if (x.path.fused_tail) return RENI_OK;
+  if (l.pdw) {  // the training instance keeps the per-image sums on chip: a few image runs per image
+    RENI_LAUNCH(reni::k_reduce_runs, dim3((unsigned)c.B, c.B < 16 ? (unsigned)((H * 8 + 16 + 63) / 64) : 1u), dim3(256), 0, x.se, (const float*)a.pruns, (const int*)a.prun_image,
+                       l.nwg, l.pkmax, H, l.tpi, l.n_tiles, x.dA, x.img_loss);
+    return RENI_OK;
   }
+  RENI_LAUNCH(reni::k_reduce_tiles_a, dim3((unsigned)c.B, (unsigned)l.nch), dim3(256), 0, x.se, (const float*)a.dA_part,
+                     (const float*)a.loss_part, l.tpi, H, x.part2, 1, l.rt_chunk, (const int*)x.ld.tflag);
+  RENI_LAUNCH(reni::k_reduce_tiles_b, dim3((unsigned)c.B, (unsigned)((H * 8 + 16 + 255) / 256)), dim3(256), 0, x.se, (const float*)x.part2, l.nch, H, x.dA, x.img_loss, 1);
+  return RENI_OK;
+}
 
+// FiLM: d(freq) / d(phase), the decoder's weight gradient, the loss terms
+// (persistent path: `s` carries k_reni_dw1 and what needs its runs -- d(freq) / d(phase), layer 1's weight gradient;
+// `se` what needs the training kernel only -- dA, the loss, the other layers' weight gradients)
+int bwd_epilogue_film(Bwd& x) {
+  const reni_plan* p = x.p; const BwdCall& c = x.c; const Layout& l = x.l; const BwdPath& path = x.path; const reni::MainArgs& a = x.a;
+  hipStream_t s = x.s, se = x.se;
+  const int H = p->d.hidden_features, L = p->d.hidden_layers;
+  if (path.red2) {  // (in k_film_reduce2's launch, below)
+  } else if (L > 0 && (l.stream || path.fpers)) {
+    RENI_LAUNCH(reni::k_reduce_film_runs, dim3((unsigned)c.B, (unsigned)((L * H + 255) / 256)), dim3(256), 0, s, a, H,
+                       path.fpers ? 3 * l.nwg * l.pkmax : l.nwg * l.kmax, c.fio->dfilm);
+  } else if (L > 0) {
+    RENI_LAUNCH(reni::k_reduce_film, dim3((unsigned)c.B, (unsigned)((L * 2 * H + 255) / 256)), dim3(256), 0, s,
+                       (const float*)a.dfp_part, l.tpi, L * 2 * H, c.fio->dfilm);
+  }
+  if (c.flags & RENI_NEED_DW) {
+    // the first layer's gradient belongs to the glue (it is a function of dA): zero its slot unless the caller
+    // (reni_film_model_*) fills it
+    if (!c.fio->keep_first) HIP_TRY(hipMemsetAsync(c.dparams, 0, (size_t)p->n_first * 4, s));
+    if (path.fpers) {  // one partial slot per image run: layer 1 from k_reni_dw1's runs, the rest from the training kernel's
+      const int n_l1 = path.n_l1, nslot = l.nwg * l.pkmax;
+      reni::FilmReduce2 r2;
+      r2.H = H; r2.nruns = 3 * l.nwg * l.pkmax; r2.B = (int)c.B; r2.gy = (L * H + 255) / 256; r2.dfilm = c.fio->dfilm;
+      r2.part = a.dw1p; r2.per_wg = (size_t)n_l1; r2.nslot = 2 * nslot; r2.dparams = c.dparams + p->n_first; r2.n = n_l1;
+      r2.valid = (const int*)a.prun_image + nslot;
+      RENI_LAUNCH(reni::k_film_reduce2, dim3((unsigned)(r2.B * r2.gy + (n_l1 + 63) / 64)), dim3(256), 0, s, a, r2);
+      if (const int rc = reduce_partials(a.dwp, l.dwp_per_wg, nslot, c.dparams + p->n_first, n_l1, path.n_rest, a.prun_image, x.lsc, se)) return rc;
+    } else if (const int rc = reduce_partials(a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, 0, path.n_rest, nullptr, x.lsc, s)) {
+      return rc;
+    }
+  }
+  if (c.loss_kind != LOSS_DOUT) {
+    RENI_LAUNCH(reni::k_finalize_loss, dim3(1), dim3(256), 0, se, (const float*)x.img_loss, (const float*)x.stats,
+                       c.fio->Zp, (int)c.B, (int)c.P, (int)c.fio->nz, path.use_cos ? 1 : 0,
+                       (c.fio->Zp != nullptr && c.loss_kind == RENI_LOSS_TEST) ? 1 : 0, c.fio->alpha, c.beta, c.loss_terms);
+  }
+  return RENI_OK;
+}
+
+// concat decoder: layer 1's reduction, the latent tails, the loss terms, the first layer's weight gradient, the generic paths' reduction
+int bwd_epilogue_concat(Bwd& x) {
+  const reni_plan* p = x.p; const BwdCall& c = x.c; const Layout& l = x.l; const BwdPath& path = x.path; const reni::MainArgs& a = x.a;
+  hipStream_t s = x.s, se = x.se;
+  const int H = p->d.hidden_features;
+  const bool need_dw = (c.flags & RENI_NEED_DW) != 0;
   reni::TailArgs t;
-  t.dA = dA; t.W0 = c.params; t.Z = Z; t.xconst = (const float*)(ws + l.o_xconst);
-  t.mcol = (float*)(ws + l.o_mcol); t.ucol = (float*)(ws + l.o_ucol);
+  t.dA = x.dA; t.W0 = c.params; t.Z = x.Z; t.xconst = (const float*)(x.ws + l.o_xconst);
+  t.mcol = (float*)(x.ws + l.o_mcol); t.ucol = (float*)(x.ws + l.o_ucol);
   t.dZ = c.dZ; t.dW0 = c.dparams; t.db0 = c.dparams ? c.dparams + (size_t)H * p->F_in : nullptr;
   t.alpha2 = (c.loss_kind == RENI_LOSS_TEST) ? c.alpha : 0.f;
   t.eq = p->d.equivariance; t.nd = p->d.ndims; t.F_in = p->F_in; t.H = H; t.B = (int)c.B;
-  auto reduce_l1 = [&]() -> int {
-  if (c.flags & RENI_NEED_DW) {
-      const int n_rest = (int)(p->n_params - p->n_first);
-      // persistent path: layer 1's H * H + H values come from k_reni_dw1's own partials (the rest was reduced in front of it)
-      const int n_l1 = (l.persist && !l.wide_train && p->d.hidden_layers >= 1) ? H * H + H : 0;
-      if (n_l1 > 0) {
-        const int grid1 = dw1_slots(dw1_ring, l.nwg);
-        RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_l1 + 63) / 64)), dim3(256), 0, s,
-                           (const float*)a.dw1p, (size_t)n_l1, grid1, c.dparams + p->n_first, 0, n_l1, (const int*)nullptr, lsc);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    return RENI_OK;
-  };
-  if (!fuse_on) { rc = reduce_l1(); if (rc) return rc; }
+  // persistent path: layer 1's H * H + H values come from k_reni_dw1's own partials (the rest was reduced in front of it)
+  if (!path.fuse_on && need_dw && l.pdw && p->d.hidden_layers >= 1) {
+    if (const int rc = reduce_partials(a.dw1p, (size_t)path.n_l1, dw1_slots(path.dw1_ring, l.nwg), c.dparams + p->n_first, 0, path.n_l1, nullptr, x.lsc, s)) return rc;
+  }
   // what k_tail_b takes on either path: the per-image sums, the loss configuration, which outputs are wanted ...
   reni::TailFusedArgs f;
   memset(&f, 0, sizeof(f));
   f.t = t;
-  f.img_loss = img_loss; f.stats = stats; f.P = (int)c.P; f.nz = (int)(c.B * p->d.ndims * 3); f.has_cos = use_cos ? 1 : 0;
+  f.img_loss = x.img_loss; f.stats = x.stats; f.P = (int)c.P; f.nz = (int)(c.B * p->d.ndims * 3); f.has_cos = path.use_cos ? 1 : 0;
   f.has_prior = (c.loss_kind == RENI_LOSS_TEST) ? 1 : 0; f.alpha = c.alpha; f.beta = c.beta;
   f.loss_terms = (c.loss_kind != LOSS_DOUT) ? c.loss_terms : nullptr;
   f.need_dz = (c.flags & RENI_NEED_DZ) ? 1 : 0;
-  f.need_dw0 = (c.flags & RENI_NEED_DW) ? 1 : 0;
+  f.need_dw0 = need_dw ? 1 : 0;
   f.dw0_gx = (p->F_in + 1 + 255) / 256;
   // ... and, for a staged step: the batch the previous call prepared must be the batch this call was given (else: NaN, loudly)
   // (the staged-batch check of reni_train_step_rows on the generic kernels too: fp32, H = 32 / 64 / 256, RENI_NO_PERSIST -- ADVICE r04)
-  f.idx_now = staged ? (const long long*)c.idx : nullptr;
-  f.idx_staged = staged ? (const long long*)(ws + l.o_idxc) : nullptr;
-  f.skip_flag = c.fuse ? (int*)(ws + l.o_skip) : nullptr;
+  f.idx_now = path.staged ? (const long long*)c.idx : nullptr;
+  f.idx_staged = path.staged ? (const long long*)(x.ws + l.o_idxc) : nullptr;
+  f.skip_flag = c.fuse ? (int*)(x.ws + l.o_skip) : nullptr;
   const unsigned nb = (unsigned)((f.need_dz ? c.B : 0) + 1 + (f.need_dw0 ? f.dw0_gx * H : 0));
-  if (fused_tail) {
+  if (path.fused_tail) {
     // image runs -> dA_b, loss sums, m / u columns (k_tail_a); then dZ_b, loss terms, dW0 / db0 (k_tail_b): two launches, it was five
     f.pruns = a.pruns; f.prun_image = a.prun_image; f.nwg = l.nwg; f.kmax = l.pkmax; f.tpi = l.tpi; f.n_tiles = l.n_tiles;
-    f.dA_out = dA;
+    f.dA_out = x.dA;
     const unsigned ny = f.need_dz ? (unsigned)((p->F_in + 63) / 64) : 1u;
     unsigned gx = (unsigned)c.B;
-    if (rp_in_tail) {
-      const int n_rest = (int)(p->n_params - p->n_first), n_l1 = H * H + H;
-      f.rp_part = a.dwp; f.rp_per_wg = l.dwp_per_wg; f.rp_nwg = l.nwg; f.rp_out = c.dparams + p->n_first; f.rp_lo = n_l1; f.rp_n = n_rest; f.rp_ls = lsc;
-      gx += ((unsigned)((n_rest - n_l1 + 63) / 64) + ny - 1) / ny;
+    if (path.rp_in_tail) {
+      f.rp_part = a.dwp; f.rp_per_wg = l.dwp_per_wg; f.rp_nwg = l.nwg; f.rp_out = c.dparams + p->n_first; f.rp_lo = path.n_l1; f.rp_n = path.n_rest; f.rp_ls = x.lsc;
+      gx += ((unsigned)((path.n_rest - path.n_l1 + 63) / 64) + ny - 1) / ny;
     }
     RENI_LAUNCH(reni::k_tail_a, dim3(gx, ny), dim3(256), (size_t)reni::tail_a_lds_bytes(H), se, f);
-    HIP_TRY(hipGetLastError());
-    // dZ_b (B blocks), the loss terms (one block), dW0 / db0: all functions of k_tail_a's results alone -> one launch
-    RENI_LAUNCH(reni::k_tail_b, dim3(nb), dim3(256), 0, se, f);
-    HIP_TRY(hipGetLastError());
-  } else {
-    if (c.flags & RENI_NEED_DZ) {
-      RENI_LAUNCH(reni::k_tail_m, dim3((unsigned)c.B, (unsigned)((p->F_in + 63) / 64)), dim3(256), 0, se, t);
-      HIP_TRY(hipGetLastError());
-    }
-    // dZ_b (from k_tail_m's columns), the loss terms, dW0 / db0 (from the per-image dA): one launch (k_tail_b; it was three)
-    RENI_LAUNCH(reni::k_tail_b, dim3(nb), dim3(256), 0, se, f);
-    HIP_TRY(hipGetLastError());
+  } else if (c.flags & RENI_NEED_DZ) {
+    RENI_LAUNCH(reni::k_tail_m, dim3((unsigned)c.B, (unsigned)((p->F_in + 63) / 64)), dim3(256), 0, se, t);
   }
-  if ((c.flags & RENI_NEED_DW) && !fused_tail) {
-    const int n_rest = (int)(p->n_params - p->n_first);
-    if (!(pdw && p->d.hidden_layers >= 1) && n_rest > 0) {  // (persistent path: reduced in front of k_reni_dw1, above)
-      RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((n_rest + 63) / 64)), dim3(256), 0, s,
-                         (const float*)a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, 0, n_rest, (const int*)nullptr, lsc);
-      HIP_TRY(hipGetLastError());
-    }
+  // dZ_b (B blocks; from k_tail_a's or k_tail_m's columns), the loss terms (one block), dW0 / db0 (from the per-image dA): all functions
+  // of those results alone -> one launch (k_tail_b; it was three)
+  RENI_LAUNCH(reni::k_tail_b, dim3(nb), dim3(256), 0, se, f);
+  if (need_dw && !path.fused_tail && path.n_rest > 0) {  // (persistent path: reduced in front of k_reni_dw1, or in k_tail_a's launch)
+    if (const int rc = reduce_partials(a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, 0, path.n_rest, nullptr, x.lsc, s)) return rc;
   }
-  if (g_ev_rest && !ev_rest_done) HIP_TRY(hipEventRecord(g_ev_rest, s));  // (paths without the early point: final at the end)
-  if (c.fuse) {
-    // reni_train_step_rows: behind the call's work -- the side stream (if any) is joined first -- ONE launch takes the whole optimiser
-    // step (decoder, latent table and, on the persistent path, layer 1's partial reduction with its Adam step), then the next
-    // batch's prologue goes into the other stage copy.
-    // (Round 4 also tried the optimiser and the next prologue SPLIT around k_reni_dw1 -- everything but layer 1 beside it on the side
-    // stream, layer 1 behind it: beside that kernel the 23 us of Adam + prologue crawl for 80 and slow it by 10, and the extra
-    // cross-stream edge costs what is left: +-0 at config 2, +11 us at 64 x 128.  profiles/r04_tail.md.)
-    if (side_join.side) {
-      HIP_TRY(hipEventRecord(side_join.side->ev[2], side_join.side->s));
-      HIP_TRY(hipStreamWaitEvent(s, side_join.side->ev[2], 0));
-      side_join.side = nullptr;
-    }
-    if (c.fuse->comm) {
-      // the data-parallel exchange (run.py:97-110: DDP's all-reduce of the shared decoder's gradients) INSIDE the step: an in-place
-      // RCCL sum of the flat decoder gradient over the communicator's ranks on the caller's stream; the 1 / world of the mean rides on
-      // Adam's grad_scale.  Latent rows need no exchange (every row has one owner: reni_amd/dist.py).
-      const size_t n_early = dp_early_done ? (size_t)(p->n_params - p->n_first - ((size_t)H * H + H)) : 0;
-      EvPair ev;
-      const bool timed = prof_begin(s, &ev, PROF_COMM);
-      // (a staged step that met another batch than the one staged for it is skipped -- k_tail_b's flag, k_adam2 -- and that decision
-      //  must be the same on every rank, or the replicas part: the flags' MAX first (4 bytes; ADVICE r05))
-      // (unconditionally -- not only when THIS rank's step is staged: a collective every rank must enter)
-      rc = rccl_allreduce_max_i32(c.fuse->comm, (int*)(ws + l.o_skip), 1, s);
-      if (rc) return rc;
-      rc = rccl_allreduce_inplace(c.fuse->comm, c.dparams, (size_t)p->n_params - n_early, s);
-      if (rc) return rc;
-      if (timed) HIP_TRY(hipEventRecord(ev.b, s));
-    }
-    reni::Adam2Args ad;
-    ad.p = c.fuse->params; ad.g = c.dparams; ad.m = c.fuse->m_dec; ad.v = c.fuse->v_dec; ad.n = p->n_params;
-    ad.nb_dec = (int)((p->n_params + 255) / 256);
-    ad.tp = c.fuse->table; ad.g_rows = c.dZ; ad.idx = (const long long*)c.idx; ad.B = (int)c.B; ad.row_len = p->d.ndims * 3;
-    ad.tm = c.fuse->m_lat; ad.tv = c.fuse->v_lat; ad.tn = c.n_rows * ad.row_len;
-    ad.lr = c.fuse->lr; ad.b1 = c.fuse->b1; ad.b2 = c.fuse->b2; ad.eps = c.fuse->eps; ad.gscale = c.fuse->gscale;
-    ad.bc1 = c.fuse->bc1; ad.bc2_sqrt = c.fuse->bc2_sqrt;
-    ad.skip_lo = 0; ad.skip_hi = 0; ad.l1_part = nullptr; ad.l1_per_wg = 0; ad.l1_nwg = 0; ad.nb_l1 = 0; ad.l1_scale = lsc.c[0];
-    ad.skip_step = (const int*)(ws + l.o_skip);  // (written by this call's k_tail_b, in front of this launch on every path)
-    if (fuse_on) {
-      const int n_l1 = H * H + H;
-      ad.skip_lo = p->n_first; ad.skip_hi = p->n_first + n_l1;
-      ad.l1_part = a.dw1p; ad.l1_per_wg = (size_t)n_l1; ad.l1_nwg = dw1_slots(dw1_ring, l.nwg); ad.nb_l1 = (n_l1 + 63) / 64;
-    }
-    RENI_LAUNCH(reni::k_adam2, dim3((unsigned)(ad.nb_dec + (ad.tn + 255) / 256 + ad.nb_l1)), dim3(256), 0, s, ad);
-    HIP_TRY(hipGetLastError());
-    if (c.fuse->idx_next) {
-      const Layout ln = make_layout(p, g, c.B, c.P, c.flags, true, true, 1 - stage);
-      rc = run_prologue(p, g, ln, c.B, c.fuse->table, c.fuse->params, ws, true, s, c.fuse->idx_next, nullptr, c.n_rows);
-      if (rc) return rc;
-      *c.fuse->state = 1u | ((uint32_t)(1 - stage) << 1);
-    }
+  if (g_ev_rest && !path.ev_rest_done) HIP_TRY(hipEventRecord(g_ev_rest, s));  // (paths without the early point: final at the end)
+  return RENI_OK;
+}
+
+// reni_train_step_rows: behind the call's work -- the side stream (if any) is joined first -- ONE launch takes the whole optimiser
+// step (decoder, latent table and, on the persistent path, layer 1's partial reduction with its Adam step), then the next
+// batch's prologue goes into the other stage copy.
+// (Round 4 also tried the optimiser and the next prologue SPLIT around k_reni_dw1 -- everything but layer 1 beside it on the side
+// stream, layer 1 behind it: beside that kernel the 23 us of Adam + prologue crawl for 80 and slow it by 10, and the extra
+// cross-stream edge costs what is left: +-0 at config 2, +11 us at 64 x 128.  profiles/r04_tail.md.)
+int bwd_fused_step(Bwd& x, SideJoin& side_join) {
+  const reni_plan* p = x.p; const BwdCall& c = x.c; const Layout& l = x.l; const BwdPath& path = x.path; hipStream_t s = x.s;
+  const StepFuse& fu = *c.fuse;
+  if (side_join.side) {
+    HIP_TRY(hipEventRecord(side_join.side->ev[2], side_join.side->s));
+    HIP_TRY(hipStreamWaitEvent(s, side_join.side->ev[2], 0));
+    side_join.side = nullptr;
   }
-  return RENI_OK;  // (joined by side_join)
+  if (fu.comm) {
+    // the data-parallel exchange (run.py:97-110: DDP's all-reduce of the shared decoder's gradients) INSIDE the step: an in-place
+    // RCCL sum of the flat decoder gradient over the communicator's ranks on the caller's stream; the 1 / world of the mean rides on
+    // Adam's grad_scale.  Latent rows need no exchange (every row has one owner: reni_amd/dist.py).
+    const size_t n_early = path.dp_early_done ? (size_t)(path.n_rest - path.n_l1) : 0;
+    // (a staged step that met another batch than the one staged for it is skipped -- k_tail_b's flag, k_adam2 -- and that decision
+    //  must be the same on every rank, or the replicas part: the flags' MAX first (4 bytes; ADVICE r05))
+    // (unconditionally -- not only when THIS rank's step is staged: a collective every rank must enter)
+    EvPair ev;
+    const bool timed = prof_begin(s, &ev, PROF_COMM);
+    int rc = rccl_allreduce_max_i32(fu.comm, (int*)(x.ws + l.o_skip), 1, s);
+    if (rc) return rc;
+    rc = rccl_allreduce_inplace(fu.comm, c.dparams, (size_t)p->n_params - n_early, s);
+    if (rc) return rc;
+    if (timed) HIP_TRY(hipEventRecord(ev.b, s));
+  }
+  reni::Adam2Args ad;
+  ad.p = fu.params; ad.g = c.dparams; ad.m = fu.m_dec; ad.v = fu.v_dec; ad.n = p->n_params;
+  ad.nb_dec = (int)((p->n_params + 255) / 256);
+  ad.tp = fu.table; ad.g_rows = c.dZ; ad.idx = (const long long*)c.idx; ad.B = (int)c.B; ad.row_len = p->d.ndims * 3;
+  ad.tm = fu.m_lat; ad.tv = fu.v_lat; ad.tn = c.n_rows * ad.row_len;
+  ad.lr = fu.lr; ad.b1 = fu.b1; ad.b2 = fu.b2; ad.eps = fu.eps; ad.gscale = fu.gscale;
+  ad.bc1 = fu.bc1; ad.bc2_sqrt = fu.bc2_sqrt;
+  ad.skip_lo = 0; ad.skip_hi = 0; ad.l1_part = nullptr; ad.l1_per_wg = 0; ad.l1_nwg = 0; ad.nb_l1 = 0; ad.l1_scale = x.lsc.c[0];
+  ad.skip_step = (const int*)(x.ws + l.o_skip);  // (written by this call's k_tail_b, in front of this launch on every path)
+  if (path.fuse_on) {
+    ad.skip_lo = p->n_first; ad.skip_hi = p->n_first + path.n_l1;
+    ad.l1_part = x.a.dw1p; ad.l1_per_wg = (size_t)path.n_l1; ad.l1_nwg = dw1_slots(path.dw1_ring, l.nwg); ad.nb_l1 = (path.n_l1 + 63) / 64;
+  }
+  RENI_LAUNCH(reni::k_adam2, dim3((unsigned)(ad.nb_dec + (ad.tn + 255) / 256 + ad.nb_l1)), dim3(256), 0, s, ad);
+  if (fu.idx_next) {
+    const Layout ln = make_layout(p, x.g, c.B, c.P, c.flags, true, true, 1 - path.stage);
+    if (const int rc = run_prologue(p, x.g, ln, c.B, fu.table, fu.params, x.ws, true, s, fu.idx_next, nullptr, c.n_rows)) return rc;
+    *fu.state = 1u | ((uint32_t)(1 - path.stage) << 1);
+  }
+  return RENI_OK;
+}
+
+// Everything behind the entry points' own argument handling, for every backward call (fio != NULL: FiLM conditioning): a driver over
+// the stages above, in launch order.  The side stream's lock and join guard live in THIS frame, so every return below them -- an
+// error from any stage included -- joins the side stream and then lets go of the lock.
+int run_backward(const reni_plan* p, const BwdCall& c) {
+  Bwd x{p, c};
+  int rc = bwd_validate(x);
+  if (rc) return rc;
+  DeviceGuard dev_guard;
+  if ((rc = dev_guard.enter(c.params))) return rc;
+  if ((rc = bwd_layout(x))) return rc;
+  bwd_layer_scales(x);
+  bwd_main_args(x);  // (+ BwdPath: from here on every decision is on record)
+  if (!x.path.staged && (rc = run_prologue(p, x.g, x.l, c.B, c.Z, c.params, x.ws, true, x.s, c.idx, c.fio ? c.fio->A : nullptr, c.n_rows))) return rc;
+  if ((rc = bwd_weight_lists(x))) return rc;
+  if ((rc = bwd_stats_pass(x))) return rc;
+  rc = x.l.persist ? launch_train(p, x.a, x.l.nwg, x.s, false, x.path.l0x) : launch_main(p, reni::MODE_FWD_BWD, x.a, x.l.nwg, x.s);
+  if (rc) return rc;
+  std::unique_lock<std::mutex> side_lock(g_side_mu, std::defer_lock);
+  SideJoin side_join;
+  if ((rc = bwd_fork_dw1(x, side_lock, side_join))) return rc;
+  if ((rc = bwd_dw_consumers(x))) return rc;
+  if ((rc = bwd_image_sums(x))) return rc;
+  if (c.fio) return bwd_epilogue_film(x);
+  if ((rc = bwd_epilogue_concat(x))) return rc;
+  return c.fuse ? bwd_fused_step(x, side_join) : RENI_OK;
 }
 
 // ---- H = 256 training in image chunks ---------------------------------------------------------------------------------
@@ -1166,7 +1191,7 @@ int run_backward(const reni_plan* p, const BwdCall& c) {
 int64_t frag_chunk_images(const reni_plan* p, int64_t B, int64_t P, uint32_t flags) {
   GeoRt g;
   if (!p || p->d.conditioning != RENI_COND_CONCAT || p->d.hidden_features != 256 || !(flags & RENI_NEED_DW) || !geo_for(p, &g)) return B;
-  const Layout l = make_layout(p, g, 1, P, flags | RENI_NEED_DZ, true, true);
+  const Layout l = backward_layout(p, g, 1, P, flags);
   if (!l.frag) return B;
   const size_t per_image = (size_t)l.tpi * (size_t)(2 * p->d.hidden_layers + 1) * g.stash_layer_bytes;
   int64_t bc = (int64_t)(p->frag_ws_cap / (per_image ? per_image : 1));
@@ -1188,8 +1213,8 @@ int run_backward_chunked(const reni_plan* p, const BwdCall& c) {
   // the chunk loop's own launches (k_add_into) run on the device that owns the buffers, like everything run_backward launches
   DeviceGuard dev_guard;
   if (const int rcg = dev_guard.enter(c.params)) return rcg;
-  const size_t core = al256(make_layout(p, g, bc, P, c.flags | RENI_NEED_DZ, true, true).total);
-  if (B % bc != 0 && make_layout(p, g, B % bc, P, c.flags | RENI_NEED_DZ, true, true).total > core)
+  const size_t core = al256(backward_layout(p, g, bc, P, c.flags).total);
+  if (B % bc != 0 && backward_layout(p, g, B % bc, P, c.flags).total > core)
     return fail(RENI_EWORKSPACE, "internal: the last chunk's layout exceeds a full chunk's");
   const size_t extra = al256((size_t)p->n_params * 4) + 256;
   if (!c.ws) return fail(RENI_EWORKSPACE, "workspace is NULL");
@@ -1218,11 +1243,9 @@ int run_backward_chunked(const reni_plan* p, const BwdCall& c) {
     if (!first) {
       if (c.dparams) {
         RENI_LAUNCH(reni::k_add_into, dim3((unsigned)((p->n_params + 255) / 256)), dim3(256), 0, s, c.dparams, (const float*)dp_c, (size_t)p->n_params);
-        HIP_TRY(hipGetLastError());
       }
       if (c.loss_terms) {
         RENI_LAUNCH(reni::k_add_into, dim3(1), dim3(256), 0, s, c.loss_terms, (const float*)lt_c, (size_t)4);
-        HIP_TRY(hipGetLastError());
       }
     }
   }
@@ -1283,7 +1306,6 @@ void fill_glue(reni::FilmGlueArgs& g, const reni_plan* p, const GlueLayout& gl, 
 int run_film_glue_fwd(const reni::FilmGlueArgs& g, hipStream_t s) {
   const int B = g.B;
   RENI_LAUNCH(reni::k_film_minput, dim3((unsigned)B), dim3(256), 0, s, g);
-  HIP_TRY(hipGetLastError());
   for (int i = 0; i <= g.ML; ++i) {
     const int N = (i < g.ML) ? g.Hm : g.N_out, K = (i == 0) ? g.M_in : g.Hm;
     const float* x = (i == 0) ? g.mapm : g.mapx + (size_t)(i - 1) * g.Hm;
@@ -1296,10 +1318,8 @@ int run_film_glue_fwd(const reni::FilmGlueArgs& g, hipStream_t s) {
     else
       RENI_LAUNCH(reni::k_film_linear<1>, dim3((unsigned)((N + 3) / 4), (unsigned)B), dim3(256), 0, s, x, ldx,
                          g.mparams + g.mw_off[i], g.mparams + g.mb_off[i], y, ldy, N, K, i < g.ML ? 1 : 0);
-    HIP_TRY(hipGetLastError());
   }
   RENI_LAUNCH(reni::k_film_fold, dim3((unsigned)B), dim3(256), 0, s, g);
-  HIP_TRY(hipGetLastError());
   return RENI_OK;
 }
 
@@ -1307,7 +1327,7 @@ int run_film_glue_fwd(const reni::FilmGlueArgs& g, hipStream_t s) {
 size_t core_ws_bytes(const reni_plan* p, int64_t B, int64_t P, uint32_t flags) {
   GeoRt g;
   if (!geo_for(p, &g)) return 0;
-  return al256(make_layout(p, g, B, P, flags | RENI_NEED_DZ, true, true).total);  // (as reni_workspace_bytes sizes it)
+  return al256(backward_layout(p, g, B, P, flags).total);  // (as reni_workspace_bytes sizes it)
 }
 
 // (c.Z: the latents; c.dparams / dmparams: the decoder's and the mapping network's gradients)
@@ -1344,7 +1364,6 @@ int film_model_backward(const reni_plan* p, const BwdCall& c, const float* mpara
   rc = run_backward(p, k);
   if (rc) return rc;
   RENI_LAUNCH(reni::k_film_dout, dim3((unsigned)B), dim3(256), 0, s, g);
-  HIP_TRY(hipGetLastError());
   float* dm = (float*)(gw + gl.o_dm);
   for (int i = g.ML; i >= 0; --i) {  // delta of layer i-1's output (i = 0: of the mapping input) from layer i's
     const int N = (i < g.ML) ? g.Hm : g.N_out, K = (i == 0) ? g.M_in : g.Hm;
@@ -1352,7 +1371,6 @@ int film_model_backward(const reni_plan* p, const BwdCall& c, const float* mpara
     float* dx = (i == 0) ? dm : g.dly + gl.dly_off[i - 1];
     RENI_LAUNCH(reni::k_film_linear_t, dim3((unsigned)((K + 63) / 64), (unsigned)B), dim3(64 * reni::FLT_NG), 0, s,
                        (const float*)(g.dly + gl.dly_off[i]), N, g.mparams + g.mw_off[i], N, K, xact, g.ML * g.Hm, dx, K);
-    HIP_TRY(hipGetLastError());
   }
   // dZ (needs dm), the first FiLM layer's and every mapping-network layer's weight gradients (need the deltas): one launch
   reni::FilmWgradAll wa;
@@ -1380,7 +1398,6 @@ int film_model_backward(const reni_plan* p, const BwdCall& c, const float* mpara
     nblk += (unsigned)(fg.gx0 * H + nw);
   }
   RENI_LAUNCH(reni::k_film_grads, dim3(nblk), dim3(256), 0, s, g, wa, fg);
-  HIP_TRY(hipGetLastError());
   return RENI_OK;
 }
 
@@ -1484,9 +1501,9 @@ size_t reni_workspace_bytes(const reni_plan* p, int64_t B, int64_t P, uint32_t f
   // sized for the backward entry points so that one buffer serves every call.  The layout is the one the calls will use NOW:
   // RENI_NO_PERSIST is read here as it is there (sizing for both kernel choices made the headline path ask for 5.7 GB
   // instead of 0.7 GB); a caller that flips the variable between sizing and calling gets RENI_EWORKSPACE, not a wrong result.
-  size_t n = make_layout(p, g, B, P, flags | RENI_NEED_DZ, true, true).total;
+  size_t n = backward_layout(p, g, B, P, flags).total;
   const int64_t bc = frag_chunk_images(p, B, P, flags);  // (H = 256 training: in image chunks, see run_backward_chunked)
-  if (bc < B) n = al256(make_layout(p, g, bc, P, flags | RENI_NEED_DZ, true, true).total) + al256((size_t)p->n_params * 4) + 256;
+  if (bc < B) n = al256(backward_layout(p, g, bc, P, flags).total) + al256((size_t)p->n_params * 4) + 256;
   if (p->d.conditioning == RENI_COND_FILM && p->d.mapping_layers > 0) n = al256(n) + make_glue_layout(p, B).total;
   return n;
 }
@@ -1503,14 +1520,14 @@ int reni_path_info(const reni_plan* p, int64_t B, int64_t P, uint32_t flags, int
   GeoRt g;
   if (!p || !info8 || B < 1 || P < 1 || !geo_for(p, &g)) return fail(RENI_EINVAL, "bad argument");
   const Layout l = make_layout(p, g, B, P, flags, true);
-  const bool film = p->d.conditioning == RENI_COND_FILM;
-  const bool pdw = l.persist && !l.wide_train && (film || (flags & RENI_NEED_DW));
   info8[0] = l.persist;                                                    // register-persistent kernels (k_reni_train_bf16)
-  info8[1] = !pdw ? 0 : (!p->dw1_old && !film && P % 128 == 0) ? 1 : 2;    // dW_1: none / k_reni_dw1_ring (given aligned directions) / k_reni_dw1
+  // dW_1: none / k_reni_dw1_ring (given aligned directions) / k_reni_dw1 /
   // 3: k_reni_l0_ring behind the L0X training instance (layer 0's backward + dW_1; given, in addition, WeightedMSE and no output image)
-  if (info8[1] == 1 && !p->no_l0x && (flags & RENI_NEED_DW) && p->d.last_layer_linear && p->d.output_activation == RENI_ACT_TANH &&
-      p->d.hidden_layers >= 3 && (p->d.hidden_layers & 1)) info8[1] = 3;
-  info8[2] = (pdw && !p->no_side_stream) ? 1 : 0;                          // per-image epilogue on the forked side stream
+  // (the *_plan_ok halves of the predicates run_backward decides with: what a call's pointers and loss add is not known here)
+  info8[1] = !l.pdw ? 0 : l0x_plan_ok(p, l, P, flags) ? 3 : dw1_ring_plan_ok(p, P) ? 1 : 2;
+  // "a side stream is ALLOWED for this plan", not "this call forks": a call forks (BwdPath::fork) when, in addition, it is not an L0X call
+  // and -- concat decoder -- has at least eight tiles per workgroup.  bench.py records this value.
+  info8[2] = side_stream_plan_ok(p, l) ? 1 : 0;
   info8[3] = (int32_t)frag_chunk_images(p, B, P, flags);                   // images per chunk of the H = 256 training path (B = one pass)
   info8[4] = l.stream;                                                     // operand stream (k_dw_stream / k_dw_frag)
   info8[5] = l.frag;                                                       // fragment stream: 1 bf16, 2 fp32
@@ -1857,7 +1874,6 @@ int reni_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
   const double bc2 = 1.0 - std::pow((double)b2, (double)step);
   RENI_LAUNCH(reni::k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                      (long long)n, lr, b1, b2, eps, (float)bc1, (float)std::sqrt(bc2), grad_scale);
-  HIP_TRY(hipGetLastError());
   return RENI_OK;
 }
 
@@ -1877,7 +1893,6 @@ int reni_adam_rows_step(float* p, const float* g_rows, const int64_t* idx, int64
   RENI_LAUNCH(reni::k_adam_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g_rows,
                      (const long long*)idx, (int)B, (int)row_len, m, v, (long long)n, lr, b1, b2, eps, (float)bc1,
                      (float)std::sqrt(bc2), grad_scale);
-  HIP_TRY(hipGetLastError());
   return RENI_OK;
 }
 
@@ -1901,7 +1916,6 @@ int reni_adam_step2(float* p, const float* g, float* m, float* v, int64_t n, flo
   a.skip_lo = 0; a.skip_hi = 0; a.l1_part = nullptr; a.l1_per_wg = 0; a.l1_nwg = 0; a.nb_l1 = 0; a.l1_scale = 1.f; a.skip_step = nullptr;
   const long long nb = a.nb_dec + (a.tn + 255) / 256;
   RENI_LAUNCH(reni::k_adam2, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
   return RENI_OK;
 }
 
@@ -1989,7 +2003,6 @@ int reni_allreduce_grads(void* comm, float* flat, size_t n, float scale, void* s
   if (e) return rccl_fail(r, "ncclAllReduce", e);
   if (scale != 1.f) {
     RENI_LAUNCH(reni::k_scale, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, flat, n, scale);
-    HIP_TRY(hipGetLastError());
   }
   return RENI_OK;
 }
@@ -2044,7 +2057,6 @@ int reni_probe_tr(const int32_t* lane_addr_host, int32_t mode, uint16_t* out_hos
   HIP_TRY(hipMalloc(&da, 64 * sizeof(int)));
   if (lane_addr_host) HIP_TRY(hipMemcpy(da, lane_addr_host, 64 * sizeof(int), hipMemcpyHostToDevice));
   RENI_LAUNCH(reni::k_probe_tr, dim3(1), dim3(64), 0, 0, d, da, mode);
-  HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out_host, d, 256 * sizeof(unsigned short), hipMemcpyDeviceToHost));
   (void)hipFree(d); (void)hipFree(da);
   return RENI_OK;
@@ -2058,7 +2070,6 @@ int reni_selftest_layouts(int32_t* out_mismatch, int32_t n_probes) {
   for (int which = 0; which < 2; ++which) {
     HIP_TRY(hipMemset(d, 0xff, 32 * 32 * sizeof(float)));
     RENI_LAUNCH(reni::k_probe, dim3(1), dim3(64), 0, 0, d, which);
-    HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(h.data(), d, 32 * 32 * sizeof(float), hipMemcpyDeviceToHost));
     int bad = 0;
     for (int i = 0; i < 32; ++i)

@@ -4,7 +4,9 @@
  * is driven up to the point where it would touch the device -- NULL and out-of-range arguments, every supported width / depth /
  * conditioning through plan creation, workspace sizing, launch / path reports, the workspace-too-small returns behind the layout
  * computation.  ASan watches the plan's offset tables, the layout arrays and the info buffers (heap allocated at their exact size).
- * Prints "capi_args: N checks ok" and exits 0; any unexpected return code is a failure with the library's message. */
+ * Prints "capi_args: N checks ok" and exits 0; any unexpected return code is a failure with the library's message.
+ * With the argument `dump` it also prints one line per (plan, B, P, flags) of the sweep and of the FiLM plans -- workspace bytes, the four
+ * launch-info and the eight path-info values: two builds of the library whose dumps are equal size and report every call alike. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,6 +26,17 @@ static int n_checks = 0, n_bad = 0;
   } while (0)
 #define EXPECT_TRUE(expr) EXPECT(!!(expr), 1)
 
+static int g_dump = 0;
+static void dump_line(const char* kind, const reni_desc* d, const reni_plan* p, int64_t B, int64_t P, uint32_t fl) {
+  int32_t i4[4] = {0, 0, 0, 0}, i8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (!g_dump) return;
+  reni_launch_info(p, B, P, i4);
+  reni_path_info(p, B, P, fl, i8);
+  printf("%s eq=%d H=%d L=%d dt=%d ml=%d B=%lld P=%lld fl=%u ws=%zu launch=%d,%d,%d,%d path=%d,%d,%d,%d,%d,%d,%d,%d\n", kind, d->equivariance,
+         d->hidden_features, d->hidden_layers, d->dtype, d->mapping_layers, (long long)B, (long long)P, fl, reni_workspace_bytes(p, B, P, fl),
+         i4[0], i4[1], i4[2], i4[3], i8[0], i8[1], i8[2], i8[3], i8[4], i8[5], i8[6], i8[7]);
+}
+
 static int64_t g_st3[3] = {3 * 128, 3, 1};
 static const int64_t* st3(uint32_t unused) { (void)unused; return g_st3; }
 
@@ -36,8 +49,9 @@ static reni_desc desc(int eq, int nd, int H, int L, int dtype, int cond, int ml,
   return d;
 }
 
-int main(void) {
+int main(int argc, char** argv) {
   reni_plan* p = NULL;
+  g_dump = argc > 1 && strcmp(argv[1], "dump") == 0;
   reni_desc d = desc(RENI_EQ_SO2, 36, 128, 5, RENI_BF16, RENI_COND_CONCAT, 0, 0);
   /* ---- plan creation: argument errors */
   EXPECT(reni_plan_create(NULL, &p), RENI_EINVAL);
@@ -89,6 +103,7 @@ int main(void) {
                 EXPECT_TRUE(i4[0] >= 1 && i4[3] == Bs[bi] * ((Ps[pi] + 127) / 128) && i8[6] == 0 && i8[7] >= 1);
                 EXPECT_TRUE(i8[3] >= 1 && i8[3] <= Bs[bi]);
                 free(i4); free(i8);
+                dump_line("concat", &c, p, Bs[bi], Ps[pi], fl);
               }
           EXPECT(reni_workspace_bytes(p, 0, 128, 0), 0);
           EXPECT(reni_workspace_bytes(p, 1, 0, 0), 0);
@@ -106,6 +121,7 @@ int main(void) {
     const long long M_in = 36 * 36 + 36, N_out = 2 * 6 * 128;
     EXPECT(reni_film_map_param_count(p), (M_in * 128 + 128) + (long long)(ml - 1) * (128 * 128 + 128) + (128 * N_out + N_out));
     EXPECT_TRUE(reni_workspace_bytes(p, 64, 32768, 3) > 0);
+    for (uint32_t fl = 0; fl <= 3; ++fl) { dump_line("film", &c, p, 64, 32768, fl); dump_line("film", &c, p, 7, 129, fl); }
     reni_plan_destroy(p);
     p = NULL;
   }
@@ -212,6 +228,7 @@ int main(void) {
     EXPECT(reni_film_model_forward(p, 1, 128, NULL, fake, 0, fake, fake, fake, ws, 1 << 20, NULL), RENI_EINVAL);
     EXPECT(reni_film_model_forward(p, 1, 128, fake, fake, 0, fake, fake, fake, NULL, 0, NULL), RENI_EWORKSPACE);
     EXPECT(reni_film_model_forward(p, 1, 128, fake, fake, 0, fake, fake, fake, ws, 16, NULL), RENI_EWORKSPACE);
+    for (uint32_t fl = 0; fl <= 3; ++fl) { dump_line("film", &c, p, 64, 32768, fl); dump_line("film", &c, p, 7, 129, fl); }
     reni_plan_destroy(p); }
   /* H = 256 training in image chunks: sizing and the chunk count */
   { reni_desc c = desc(RENI_EQ_SO2, 36, 256, 5, RENI_BF16, RENI_COND_CONCAT, 0, 0);
@@ -225,6 +242,7 @@ int main(void) {
     EXPECT(reni_path_info(p, 256, 32768, 3, i8), RENI_OK);
     EXPECT_TRUE(i8[3] >= 64 && i8[3] <= 96);  /* (three chunks of 86, 86, 84 -- not 95 + 95 + 66) */
     EXPECT_TRUE(reni_workspace_bytes(p, 256, 32768, 3) < ((size_t)18 << 30));
+    for (uint32_t fl = 0; fl <= 3; ++fl) { dump_line("chunked", &c, p, 256, 32768, fl); dump_line("chunked", &c, p, 64, 32768, fl); }
     reni_plan_destroy(p); }
   /* optimiser / exchange / diagnostics */
   EXPECT(reni_adam_step(NULL, fake, fake, fake, 4, 1e-3f, .9f, .999f, 1e-8f, 1, 1.f, NULL), RENI_EINVAL);

@@ -530,6 +530,57 @@ int reni_rotate_envmap(int64_t B, int64_t C, int64_t H, int64_t W, const float* 
                        const int64_t* src_index, int64_t n_src, const float* rot, int64_t rot_stride, const float* row_trig,
                        const float* col_trig, int32_t mode, float* out, void* stream);
 
+/* ---- scores of environment-map pairs (reni_tu_metrics.hip; reni_amd/metrics.py) ------------------------------------------------
+ * No reference counterpart (the reference's evaluation composes these from tensor operations).  A prediction and a target, B images
+ * of 3 x H x W each, are read in place: element (b, c, h, w) of an image at ptr[b s[0] + c s[1] + h s[2] + w s[3]] (element strides
+ * >= 0, as reni_resample and reni_unnormalise_srgb take them: planar [B][3][H][W] is {3HW, HW, W, 1}, a model output [B][P][3] is
+ * {3HW, 1, 3W, 3}).  weight: element (b, h, w) at weight[b s[0] + h s[1] + w s[2]], any stride may be 0 (sin phi per row is an [H]
+ * array with {0, 1, 0}, a shared mask {0, W, 1}); NULL is weight 1.  Weights are expected >= 0; a pixel of weight 0 is not there.
+ * space: what is compared, mapped in registers (nothing mapped is written to memory), prediction and target alike:
+ *     RENI_SPACE_STORED   the numbers as given
+ *     RENI_SPACE_LINEAR   exp(0.5 (x + 1)(minmax1 - minmax0) + minmax0), UnMinMaxNormlise: the expression of reni_unnormalise_srgb
+ *     RENI_SPACE_SRGB     linear / exposure[b], clamped to [0, 1], the sRGB transfer curve (utils.sRGB's, reni_unnormalise_srgb's).
+ *                         exposure: device array [B] from the caller (metrics.exposure: the nested 0.98-quantile of the linear
+ *                         target), applied to BOTH images: a pair is judged under one exposure.
+ * minmax0 / minmax1 are read in the mapped spaces only (minmax1 > minmax0), exposure in RENI_SPACE_SRGB only.
+ * fp32 on the device, no float atomics, sums in an order that depends on (H, W) only, no host synchronisation, launches on `stream`
+ * only: two calls give identical bits; image b scores the same alone and inside a batch, planar and as a model output.
+ * ws (both calls): reni_pair_stats_workspace_bytes(B, H, W) bytes, 256-byte aligned.  1 <= B <= 65535, H W < 2^30.
+ *
+ * reni_pair_stats: one pass, every pixel read once; out[B][8], over pixels i (weight w_i) and channels c of mapped p, t:
+ *     [0] sum_i w_i                        [4] max of t over the pixels with w_i > 0   (-inf when there is none)
+ *     [1] sum_i w_i sum_c (p - t)^2        [5] min of t over the pixels with w_i > 0   (+inf when there is none)
+ *     [2] sum_i w_i sum_c |p - t|          [6] sum_i w_i sum_c t^2
+ *     [3] sum_i w_i cos(p_i, t_i)          [7] sum_i w_i sum_c t
+ *   cos is the RGB-vector cosine of F.cosine_similarity(dim = channel, eps = 1e-20).  Workgroups write fp32 partials to ws; a second
+ *   kernel adds an image's partials in double in a fixed order and rounds once.
+ *
+ * reni_ssim: the mean SSIM of Wang et al. 2004 per image, out[B]: an 11 x 11 Gaussian window, sigma 1.5, normalised (the host builds
+ *   the 11 weights in float64 and rounds them once), C1 = (0.01 L)^2, C2 = (0.03 L)^2, per channel of the mapped images
+ *       ssim = (2 mu_p mu_t + C1)(2 cov + C2) / ((mu_p^2 + mu_t^2 + C1)(var_p + var_t + C2)),
+ *   mu, var, cov from the five windowed moments E[p], E[t], E[p^2], E[t^2], E[p t]; the three channels are averaged.
+ *     RENI_SSIM_SPHERE  every pixel has a window; its taps are taken on the sphere by the rule of reni_rotate_envmap: row i < 0 is
+ *                       row -1 - i at column j + W / 2, row i >= H is row 2 H - 1 - i at column j + W / 2, then the column modulo W.
+ *                       W even, H >= 5.  out[b] = sum_i w_i ssim_i / sum_i w_i.
+ *     RENI_SSIM_PLANAR  the published image definition: only the windows that lie inside the image, an (H - 10) x (W - 10) map,
+ *                       unweighted mean.  weight must be NULL; H, W >= 11.
+ *   map_out: NULL, or [B][H][W]: the channel-mean SSIM of every pixel (planar mode: zero on the border of 5).
+ *   One kernel holds a 32 x 32 tile plus halo of both mapped images in LDS and forms the moments separably; the values go straight
+ *   into the workgroup's partial sum, no moment image is written to memory. */
+#define RENI_SPACE_STORED 0
+#define RENI_SPACE_LINEAR 1
+#define RENI_SPACE_SRGB 2
+#define RENI_SSIM_SPHERE 0
+#define RENI_SSIM_PLANAR 1
+size_t reni_pair_stats_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int reni_pair_stats(int64_t B, int64_t H, int64_t W, const float* pred, const int64_t pred_strides[4], const float* target,
+                    const int64_t target_strides[4], const float* weight, const int64_t weight_strides[3], int32_t space,
+                    double minmax0, double minmax1, const float* exposure, float* out, void* ws, size_t ws_bytes, void* stream);
+int reni_ssim(int64_t B, int64_t H, int64_t W, const float* pred, const int64_t pred_strides[4], const float* target,
+              const int64_t target_strides[4], const float* weight, const int64_t weight_strides[3], int32_t space,
+              double minmax0, double minmax1, const float* exposure, float L, int32_t mode, float* out, float* map_out, void* ws,
+              size_t ws_bytes, void* stream);
+
 /* ---- the data-parallel exchange step over RCCL -------------------------------
  * Replaces, for the flat decoder gradient, what Lightning's DDP wrapper does in the reference (run.py:97-110:
  * strategy="ddp" -> NCCL all-reduce of every parameter's gradient, mean over ranks): ONE in-place ncclAllReduce(sum) of

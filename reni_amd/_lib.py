@@ -22,6 +22,8 @@ LOSS_KIND = {"mse": LOSS_MSE, "test": LOSS_TEST}
 NEED_DW, NEED_DZ, WEIGHT_SPARSE, WEIGHT_COMPACT, WEIGHT_COS_CONSTANT = 1, 2, 4, 8, 16
 COND_CONCAT, COND_FILM = 0, 1
 ROTATE_MODE = {"nearest": 0, "bilinear": 1}
+SPACE = {"stored": 0, "linear": 1, "srgb": 2}
+SSIM_MODE = {"sphere": 0, "planar": 1}
 
 # every symbol include/reni_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -38,6 +40,7 @@ EXPORTS = (
     "reni_image_workspace_bytes", "reni_unnormalise_srgb", "reni_minmax_normalise",
     "reni_minmax_batch_workspace_bytes", "reni_minmax_normalise_batch",
     "reni_resample", "reni_blur_workspace_bytes", "reni_gaussian_blur", "reni_rotate_envmap",
+    "reni_pair_stats_workspace_bytes", "reni_pair_stats", "reni_ssim",
     "reni_rccl_unique_id", "reni_rccl_comm_create", "reni_rccl_comm_destroy", "reni_allreduce_grads",
 )
 
@@ -219,6 +222,14 @@ def load():
     lib.reni_rotate_envmap.argtypes = [c_int64, c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p, c_int64, c_void_p,
                                        c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
     lib.reni_rotate_envmap.restype = c_int32
+    lib.reni_pair_stats_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    lib.reni_pair_stats_workspace_bytes.restype = c_size_t
+    pair = [c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p, POINTER(c_int64), c_void_p, POINTER(c_int64), c_int32,
+            ctypes.c_double, ctypes.c_double, c_void_p]  # B, H, W, pred + strides, target + strides, weight + strides, space, minmax, exposure
+    lib.reni_pair_stats.argtypes = pair + [c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_pair_stats.restype = c_int32
+    lib.reni_ssim.argtypes = pair + [c_float, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]  # L, mode, out, map_out, ws ..
+    lib.reni_ssim.restype = c_int32
     lib.reni_rccl_unique_id.argtypes = [c_void_p]
     lib.reni_rccl_unique_id.restype = c_int32
     lib.reni_rccl_comm_create.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]

@@ -1406,6 +1406,7 @@ int film_model_backward(const reni_plan* p, const BwdCall& c, const float* mpara
 // error hook of the other translation units (reni_tu_shade.hip): same thread-local message as fail()
 namespace reni {
 int reni_set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+void note_launches(int n) { g_launches.fetch_add(n, std::memory_order_relaxed); }
 }  // namespace reni
 
 extern "C" {

@@ -89,6 +89,8 @@ struct MainArgs {
 
 // sets reni_last_error()'s thread-local message and returns `code` (defined next to the C ABI, reni_capi.inc)
 int reni_set_error(int code, const char* msg);
+// adds n to reni_launch_count()'s counter: for a translation unit that launches its own kernels and wants them counted
+void note_launches(int n);
 // the launches issued so far on this thread: hipGetLastError() as a RENI_* code, its text as reni_last_error()'s message
 inline int hip_status() {
   const hipError_t e = hipGetLastError();

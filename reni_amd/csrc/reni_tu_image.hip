@@ -22,6 +22,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_dev_image.inc"
 
 #define DEV __device__ __forceinline__
 
@@ -57,7 +58,7 @@ __global__ void __launch_bounds__(256) k_img_pass1(const ImgArgs a) {
   for (int c = 0; c < 3; ++c) {
     float x = a.in[b * a.sb + c * a.sc + h * a.sh + w * a.sw];
     // 0.5 * (img + 1) * (m1 - m0) + m0, rounded after every operation as the reference's tensor ops are
-    if (a.unnorm) x = expf(__fadd_rn(__fmul_rn(__fmul_rn(0.5f, __fadd_rn(x, 1.f)), a.range), a.m0));
+    if (a.unnorm) x = img_unnormalise(x, a.range, a.m0);
     v[c] = x;
     if (a.lin) a.lin[(((long long)b * 3 + c) * a.H + h) * a.W + w] = x;
   }
@@ -119,9 +120,7 @@ __global__ void __launch_bounds__(256) k_img_pass2(const ImgArgs a) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int b = (int)(i / per);
-  float x = a.lin[i] / a.q[b];
-  x = fminf(fmaxf(x, 0.f), 1.f);
-  a.out[i] = (x <= 0.0031308f) ? 12.92f * x : 1.055f * powf(fabsf(x), 1.f / 2.4f) - 0.055f;
+  a.out[i] = img_srgb(a.lin[i], a.q[b]);
 }
 
 // MinMaxNormalise: smallest positive and largest finite value of the tensor (positive floats order like their bits)

@@ -160,6 +160,13 @@ class RENI(_Base):
         directions, _ = self._grids(z)
         return self.model(z, directions)
 
+    # ------------------------------------------------------------------ evaluation (reni_amd/metrics.py)
+    def evaluate(self, idx=None, diffuse=False):
+        """(table, means) of ``metrics.evaluate``: the module's model scored against its dataset, with its mask (FIT_LATENT's
+        inpainting split) and the dataset's minmax."""
+        from . import metrics
+        return metrics.evaluate(self.model, self.dataset, idx=idx, mask=self.mask, diffuse=diffuse)
+
     # ------------------------------------------------------------------ the step (RENI_module.py:80-146)
     def training_step(self, batch, batch_idx):
         imgs, idx = batch

@@ -971,6 +971,134 @@ def rotate_envmap(src: torch.Tensor, rot: torch.Tensor, mode: str = "bilinear", 
     return unview(out)
 
 
+def _pair_args(pred, target, weight, size=None, check_weight=True):
+    """(pred, target as float32 views [B, 3, H, W], weight as a float32 view [B, H, W] or None) without copying a pixel, or
+    ValueError.  An image batch is [B, 3, H, W] with any strides or a model output [B, P, 3] (``size`` = (H, W); default: the
+    other operand's, else P = H x 2H); the weight is anything that broadcasts to [B, H, W] (sin(phi) per row: [H, 1]) or a
+    mask / sineweight [1 | B, P, 3] (channel 0 is read).  Negative weights raise (check_weight: one read-back per call)."""
+    import math
+    if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise ValueError("pred and target must be tensors")
+    if size is None:
+        for x in (pred, target):
+            if x.dim() == 4:
+                size = tuple(x.shape[-2:])
+    views = []
+    for name, x in (("pred", pred), ("target", target)):
+        if x.dim() == 4 and x.shape[1] == 3:
+            v = x
+        elif x.dim() == 3 and x.shape[2] == 3:
+            if size is None:
+                H = math.isqrt(x.shape[1] // 2)
+                if 2 * H * H != x.shape[1]:
+                    raise ValueError(f"{name}: {x.shape[1]} pixels are not H x 2H; pass size=(H, W)")
+                size = (H, 2 * H)
+            if int(size[0]) * int(size[1]) != x.shape[1]:
+                raise ValueError(f"{name}: {x.shape[1]} pixels are not {int(size[0])} x {int(size[1])}")
+            v = x.unflatten(1, (int(size[0]), int(size[1]))).permute(0, 3, 1, 2)
+        else:
+            raise ValueError(f"{name} must be [B, 3, H, W] or a model output [B, P, 3], got {tuple(x.shape)}")
+        views.append(v if v.dtype == torch.float32 else v.float())
+    p, t = views
+    if p.shape != t.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} are not the same batch of images")
+    B, _, H, W = p.shape
+    if min(B, H, W) < 1:
+        raise ValueError(f"empty images {tuple(pred.shape)}")
+    if p.device != t.device:
+        raise ValueError(f"pred is on {p.device}, target on {t.device}")
+    w = None
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor):
+            raise ValueError("weight must be a tensor or None")
+        w = weight if weight.dtype == torch.float32 else weight.float()
+        if w.dim() == 3 and w.shape[2] == 3 and w.shape[1] == H * W and w.shape[0] in (1, B) and (H, W) != (H * W, 3):
+            w = w[..., 0].unflatten(1, (H, W))
+        try:
+            w = torch.broadcast_to(w, (B, H, W))
+        except RuntimeError:
+            raise ValueError(f"weight {tuple(weight.shape)} does not broadcast to [{B}, {H}, {W}]") from None
+        if w.device != p.device:
+            raise ValueError(f"weight is on {w.device}, the images on {p.device}")
+        if check_weight and not bool((weight >= 0).all()):  # (a read-back; callers that built the weight from checked parts skip it)
+            raise ValueError("weights must be >= 0 (and not NaN)")
+    return p, t, w
+
+
+def _space_args(space, minmax, exposure, B, device):
+    if space not in _lib.SPACE:
+        raise ValueError(f"space must be one of {tuple(_lib.SPACE)}, got {space!r}")
+    if space != "stored":
+        if minmax is None:
+            raise ValueError(f"space={space!r} maps the stored numbers back to radiance and needs minmax")
+        if not float(minmax[1]) > float(minmax[0]):
+            raise ValueError(f"minmax[1] must exceed minmax[0], got {tuple(minmax)}")
+    if space == "srgb":
+        if not isinstance(exposure, torch.Tensor) or tuple(exposure.shape) != (B,):
+            raise ValueError(f"space='srgb' needs exposure, a tensor [{B}] (metrics.exposure(target, minmax))")
+        if exposure.device != device:
+            raise ValueError(f"exposure is on {exposure.device}, the images on {device}")
+        exposure = _f32c(exposure)
+    else:
+        exposure = None
+    m0, m1 = (float(minmax[0]), float(minmax[1])) if minmax is not None else (0.0, 1.0)
+    return m0, m1, exposure
+
+
+def _pair_call_head(p, t, w, space, m0, m1, exposure):
+    B, _, H, W = p.shape
+    return (B, H, W, p.data_ptr(), (ctypes.c_int64 * 4)(*p.stride()), t.data_ptr(), (ctypes.c_int64 * 4)(*t.stride()),
+            None if w is None else w.data_ptr(), None if w is None else (ctypes.c_int64 * 3)(*w.stride()), _lib.SPACE[space],
+            m0, m1, None if exposure is None else exposure.data_ptr())
+
+
+def pair_stats(pred, target, weight=None, space: str = "stored", minmax=None, exposure=None, size=None,
+               check_weight: bool = True) -> torch.Tensor:
+    """reni_pair_stats: [B, 8] float32 = (sum w, sum w (p - t)^2, sum w |p - t|, sum w cos(p, t), max t, min t, sum w t^2,
+    sum w t) per image, over pixels (weight w) and channels, of pred and target mapped into ``space`` ("stored" | "linear" |
+    "srgb"; include/reni_hip.h) in registers.  Shapes, strides and weights as ``_pair_args`` takes them: nothing is copied,
+    permuted or expanded.  "linear" and "srgb" need ``minmax``; "srgb" needs ``exposure`` [B].  check_weight=False skips the read-back that
+    looks for negative weights (for a caller that built the weight from checked parts)."""
+    p, t, w = _pair_args(pred, target, weight, size, check_weight)
+    m0, m1, exposure = _space_args(space, minmax, exposure, p.shape[0], p.device)
+    _require_cuda(p, t, w)
+    lib = _lib.load()
+    B, _, H, W = p.shape
+    out = torch.empty(B, 8, dtype=torch.float32, device=p.device)
+    ws, wp, wn = _ws256(int(lib.reni_pair_stats_workspace_bytes(B, H, W)), p.device)
+    _call(lib.reni_pair_stats, p.device, *_pair_call_head(p, t, w, space, m0, m1, exposure), out.data_ptr(), wp, wn)
+    return out
+
+
+def ssim(pred, target, weight=None, space: str = "stored", minmax=None, exposure=None, L: float = 1.0, sphere: bool = True,
+         return_map: bool = False, size=None, check_weight: bool = True):
+    """reni_ssim: mean SSIM per image [B] (11 x 11 Gaussian window, sigma 1.5, dynamic range ``L``) of pred and target mapped
+    into ``space``.  sphere=True: every pixel has a window, taken on the sphere (columns wrap, rows cross the poles; even
+    width), and the mean is weighted; sphere=False: the published image definition (windows inside the image, no weight).
+    return_map: also the per-pixel channel-mean map [B, H, W]."""
+    p, t, w = _pair_args(pred, target, weight, size, check_weight)
+    B, _, H, W = p.shape
+    m0, m1, exposure = _space_args(space, minmax, exposure, B, p.device)
+    if not float(L) > 0:
+        raise ValueError(f"L must be > 0, got {L}")
+    if sphere:
+        if W % 2 or H < 5:
+            raise ValueError(f"SSIM on the sphere needs an even width and H >= 5, got {H} x {W}")
+    else:
+        if w is not None:
+            raise ValueError("the planar SSIM is the unweighted published definition: pass no weight (or sphere=True)")
+        if H < 11 or W < 11:
+            raise ValueError(f"the planar SSIM needs H, W >= 11, got {H} x {W}")
+    _require_cuda(p, t, w)
+    lib = _lib.load()
+    out = torch.empty(B, dtype=torch.float32, device=p.device)
+    smap = torch.empty(B, H, W, dtype=torch.float32, device=p.device) if return_map else None
+    ws, wp, wn = _ws256(int(lib.reni_pair_stats_workspace_bytes(B, H, W)), p.device)
+    _call(lib.reni_ssim, p.device, *_pair_call_head(p, t, w, space, m0, m1, exposure), float(L),
+          _lib.SSIM_MODE["sphere" if sphere else "planar"], out.data_ptr(), None if smap is None else smap.data_ptr(), wp, wn)
+    return (out, smap) if return_map else out
+
+
 def launch_count(reset: bool = False) -> int:
     """Kernel launches the library has issued so far in this process (reni_launch_count)."""
     return int(_lib.load().reni_launch_count(1 if reset else 0))

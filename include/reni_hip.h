@@ -581,6 +581,52 @@ int reni_ssim(int64_t B, int64_t H, int64_t W, const float* pred, const int64_t 
               double minmax0, double minmax1, const float* exposure, float L, int32_t mode, float* out, float* map_out, void* ws,
               size_t ws_bytes, void* stream);
 
+/* ---- environment maps as importance-sampled light lists (reni_tu_lights.hip; reni_amd/lighting.py) ----------------------------
+ * No reference counterpart (the reference sums every texel of a map wherever it lights something).  B maps of 3 x H x W on RENI's
+ * grid (W even, H = W / 2, W <= 4096, 1 <= B <= 65535) are read in place through four element strides as reni_pair_stats reads
+ * them; space is RENI_SPACE_STORED (the numbers are radiance already) or RENI_SPACE_LINEAR (the expression of reni_unnormalise_srgb,
+ * in registers); RENI_SPACE_SRGB is RENI_EINVAL.  solid_angle [H] is the per-texel solid angle omega_i of row i, row_cos [H + 1]
+ * (double) is cos(i pi / H), dirs_table [H W][3] the texel-centre directions: host tables, so the library holds no grid convention.
+ * fp32 storage, no float atomics, no host synchronisation, launches on `stream` only; every sum runs in an order that depends on
+ * (H, W) or S only: two calls give identical bits, and image b's results are the same alone and inside a batch.
+ *
+ * reni_light_table_build: the sampling distribution.  Per texel f = max(0, 0.2126 r + 0.7152 g + 0.0722 b) omega_i mask, formed in
+ *   double and rounded to fp32 once (a NaN counts as 0); F_b = sum f.  mask: element (b, h, w) at mask[b s[0] + h s[1] + w s[2]], any
+ *   stride may be 0, NULL is 1, expected >= 0.  With eps = uniform_mix in [0, 1]
+ *       pmf  [B][H][W] = (1 - eps) f / F_b + eps omega_i / sum_i (W omega_i)      (F_b zero or not finite: eps = 1 for that image)
+ *       cond [B][H][W] = inclusive prefix sum of the row's pmf / the row's sum    (a row without mass: (j + 1) / W)
+ *       marg [B][H]    = inclusive prefix sum of the row sums / their total
+ *   Everything behind f is double arithmetic on the rounded f, rounded to fp32 once.  The prefix sums come from a parallel scan (a
+ *   fixed order, not the sequential one); each is divided by the scan's own value at the last entry with mass, and a running
+ *   maximum behind the division makes every CDF ascending, exactly flat over an entry whose pmf is 0, and exactly 1.0f from the
+ *   last entry with mass on.  ws: reni_light_table_workspace_bytes(B, H, W) bytes, 256-byte aligned.
+ *
+ * reni_light_sample: S lights per map by inverse-CDF sampling.  u: uniforms in [0, 1) (not checked), sample k of image b at
+ *   u[b u_stride_b + 2 k] (u_stride_b 0: one [S][2] set for all images; 2 S: [B][S][2]).  Row i = the number of entries of marg[b]
+ *   that are <= u0, at most H - 1; column j = the number of entries of cond[b][i] that are <= u1, at most W - 1 (numpy's
+ *   searchsorted(side = "right"): a texel without mass is never chosen).  Per sample, with t = i W + j:
+ *       index    [B][S]    = t                      pdf      [B][S]    = pmf[t] / omega_i   (per steradian)
+ *       radiance [B][S][3] = the mapped texel       colors   [B][S][3] = radiance texel_weight[t] / (S pmf[t])   (texel_weight NULL: 1)
+ *       dirs     [B][S][3] = dirs_table[t] (jitter 0), or (jitter 1) uniform in solid angle inside the texel: with t_r, t_c where u0,
+ *                            u1 lie between the CDF entries around i, j:  cos phi = row_cos[i] - t_r (row_cos[i] - row_cos[i + 1]),
+ *                            theta = 2 pi (j + t_c) / W - pi,  d = (sin phi sin theta, cos phi, -sin phi cos theta)   (in double)
+ *   so that sum_s colors_s g(dirs_s) estimates sum_t texel_weight_t L_t g(d_t).
+ *
+ * reni_lights_irradiance: out [B][P][3] = scale sum_s max(0, n_p . dirs_bs) colors_bs for normals [P][3] (normals_stride_b 0) or
+ *   [B][P][3] (3 P) and light lists dirs, colors [B][S][3]; lights are staged in LDS and added in ascending s, one fmaf chain per
+ *   output channel.  1 <= B <= 65535, B P < 2^28 and B S < 2^28 (reni_light_sample: B S < 2^28 as well). */
+size_t reni_light_table_workspace_bytes(int64_t B, int64_t H, int64_t W);
+int reni_light_table_build(int64_t B, int64_t H, int64_t W, const float* img, const int64_t img_strides[4], const float* mask,
+                           const int64_t mask_strides[3], int32_t space, double minmax0, double minmax1, const float* solid_angle,
+                           double uniform_mix, float* pmf, float* cond, float* marg, void* ws, size_t ws_bytes, void* stream);
+int reni_light_sample(int64_t B, int64_t H, int64_t W, int64_t S, const float* pmf, const float* cond, const float* marg,
+                      const float* img, const int64_t img_strides[4], int32_t space, double minmax0, double minmax1,
+                      const float* u, int64_t u_stride_b, const float* dirs_table, const float* solid_angle,
+                      const double* row_cos, const float* texel_weight, int32_t jitter, int32_t* index, float* dirs, float* pdf,
+                      float* radiance, float* colors, void* stream);
+int reni_lights_irradiance(int64_t B, int64_t P, int64_t S, const float* normals, int64_t normals_stride_b, const float* dirs,
+                           const float* colors, float scale, float* out, void* stream);
+
 /* ---- the data-parallel exchange step over RCCL -------------------------------
  * Replaces, for the flat decoder gradient, what Lightning's DDP wrapper does in the reference (run.py:97-110:
  * strategy="ddp" -> NCCL all-reduce of every parameter's gradient, mean over ranks): ONE in-place ncclAllReduce(sum) of

@@ -1,3 +1,5 @@
 """reni_amd -- MI355X-native RENI forward/training hot path (HIP kernels behind the reference's
 nn.Module surface).  See DESIGN.md."""
 __version__ = "0.1.0"
+
+from . import lighting  # noqa: E402,F401  (importance-sampled light lists: reni_amd.lighting.build_light_table, sample_lights, ...)

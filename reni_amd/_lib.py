@@ -41,6 +41,7 @@ EXPORTS = (
     "reni_minmax_batch_workspace_bytes", "reni_minmax_normalise_batch",
     "reni_resample", "reni_blur_workspace_bytes", "reni_gaussian_blur", "reni_rotate_envmap",
     "reni_pair_stats_workspace_bytes", "reni_pair_stats", "reni_ssim",
+    "reni_light_table_workspace_bytes", "reni_light_table_build", "reni_light_sample", "reni_lights_irradiance",
     "reni_rccl_unique_id", "reni_rccl_comm_create", "reni_rccl_comm_destroy", "reni_allreduce_grads",
 )
 
@@ -230,6 +231,19 @@ def load():
     lib.reni_pair_stats.restype = c_int32
     lib.reni_ssim.argtypes = pair + [c_float, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]  # L, mode, out, map_out, ws ..
     lib.reni_ssim.restype = c_int32
+    lib.reni_light_table_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    lib.reni_light_table_workspace_bytes.restype = c_size_t
+    image = [c_void_p, POINTER(c_int64)]  # img + strides
+    space = [c_int32, ctypes.c_double, ctypes.c_double]  # space, minmax
+    lib.reni_light_table_build.argtypes = ([c_int64, c_int64, c_int64] + image + [c_void_p, POINTER(c_int64)] + space +  # B, H, W .. mask + strides ..
+                                           [c_void_p, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p])  # solid_angle, uniform_mix, pmf, cond, marg, ws ..
+    lib.reni_light_table_build.restype = c_int32
+    lib.reni_light_sample.argtypes = ([c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p] + image + space +  # B, H, W, S, pmf, cond, marg ..
+                                      [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32] +  # u + stride, dirs_table, solid_angle, row_cos, texel_weight, jitter
+                                      [c_void_p] * 5 + [c_void_p])  # index, dirs, pdf, radiance, colors; stream
+    lib.reni_light_sample.restype = c_int32
+    lib.reni_lights_irradiance.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p]
+    lib.reni_lights_irradiance.restype = c_int32
     lib.reni_rccl_unique_id.argtypes = [c_void_p]
     lib.reni_rccl_unique_id.restype = c_int32
     lib.reni_rccl_comm_create.argtypes = [c_void_p, c_int32, c_int32, POINTER(c_void_p)]

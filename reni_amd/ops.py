@@ -1099,6 +1099,131 @@ def ssim(pred, target, weight=None, space: str = "stored", minmax=None, exposure
     return (out, smap) if return_map else out
 
 
+LIGHT_MAX_WIDTH = 4096
+_LIGHT_GRIDS = {}  # (W, device) -> light_grid's tables; the most recent LIGHT_GRIDS_KEPT keys only (a 4096-wide direction table is 100 MB)
+LIGHT_GRIDS_KEPT = 2
+
+
+def light_maps_view(maps, size=None):
+    """maps as a float32 view [B, 3, H, W] on RENI's grid (W even, H = W / 2, W <= 4096) without copying a texel, or ValueError.
+    maps: [B, H, W, 3], a model output [B, H W, 3] (``size`` = (H, W); default H x 2H) or planar [B, 3, H, W]."""
+    if not isinstance(maps, torch.Tensor):
+        raise ValueError("maps must be a tensor")
+    if maps.dim() == 4 and maps.shape[3] == 3 and (maps.shape[1] != 3 or maps.shape[2] == 6):  # ([B, 3, 6, 3] is 3 x 6 texels: no planar map is 3 wide)
+        maps = maps.permute(0, 3, 1, 2)
+    elif not (maps.dim() == 4 and maps.shape[1] == 3) and not (maps.dim() == 3 and maps.shape[2] == 3):
+        raise ValueError(f"maps must be [B, H, W, 3], a model output [B, H W, 3] or planar [B, 3, H, W], got {tuple(maps.shape)}")
+    v = _pair_args(maps, maps, None, size)[0]
+    H, W = int(v.shape[2]), int(v.shape[3])
+    if W % 2 or H != W // 2 or W > LIGHT_MAX_WIDTH:
+        raise ValueError(f"light tables live on RENI's grid: W even, H = W / 2 and W <= {LIGHT_MAX_WIDTH}, got {H} x {W}")
+    if v.shape[0] > 65535:
+        raise ValueError(f"at most 65535 maps per call, got {v.shape[0]}")
+    return v
+
+
+def _light_space(space, minmax):
+    if space not in ("stored", "linear"):
+        raise ValueError(f'space must be "stored" (the maps hold radiance) or "linear" (un-normalise with minmax), got {space!r}')
+    return _space_args(space, minmax, None, 0, None)[:2]
+
+
+def light_grid(W: int, device):
+    """(solid_angle [H] float32, row_cos [H + 1] float64, dirs_table [H W, 3] float32) of the W / 2 x W grid on ``device``: the
+    exact band solid angles of ``baselines.reni_grid_weights``, cos(i pi / H), and ``utils.get_directions(W)``."""
+    import numpy as np
+    from .baselines import reni_grid_weights
+    from .utils import get_directions
+    key = (int(W), str(device))
+    if key in _LIGHT_GRIDS:
+        _LIGHT_GRIDS[key] = _LIGHT_GRIDS.pop(key)  # (most recent last)
+    else:
+        while len(_LIGHT_GRIDS) >= LIGHT_GRIDS_KEPT:
+            _LIGHT_GRIDS.pop(next(iter(_LIGHT_GRIDS)))
+        H = int(W) // 2
+        sa = torch.from_numpy(reni_grid_weights(W)[::int(W)].astype(np.float32))
+        rc = torch.from_numpy(np.cos(np.arange(H + 1, dtype=np.float64) * np.pi / H))
+        _LIGHT_GRIDS[key] = (sa.to(device), rc.to(device), get_directions(int(W))[0].to(device, torch.float32).contiguous())
+    return _LIGHT_GRIDS[key]
+
+
+def light_table_build(maps, space: str = "linear", minmax=None, mask=None, uniform_mix: float = 0.0, size=None):
+    """reni_light_table_build: (pmf [B, H, W], cond [B, H, W], marg [B, H]) float32 of maps as ``light_maps_view`` takes them,
+    read in place.  mask: anything ``_pair_args`` takes as a weight (broadcasts to [B, H, W], or [1 | B, H W, 3])."""
+    v = light_maps_view(maps, size)
+    m0, m1 = _light_space(space, minmax)
+    if not 0.0 <= float(uniform_mix) <= 1.0:
+        raise ValueError(f"uniform_mix must lie in [0, 1], got {uniform_mix}")
+    w = _pair_args(v, v, mask, None, check_weight=False)[2]
+    _require_cuda(v, w)
+    lib = _lib.load()
+    B, _, H, W = v.shape
+    dev = v.device
+    sa = light_grid(W, dev)[0]
+    pmf = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    cond = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    marg = torch.empty(B, H, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_light_table_workspace_bytes(B, H, W)), dev)
+    _call(lib.reni_light_table_build, dev, B, H, W, v.data_ptr(), (ctypes.c_int64 * 4)(*v.stride()),
+          None if w is None else w.data_ptr(), None if w is None else (ctypes.c_int64 * 3)(*w.stride()), _lib.SPACE[space], m0, m1,
+          sa.data_ptr(), float(uniform_mix), pmf.data_ptr(), cond.data_ptr(), marg.data_ptr(), wp, wn)
+    return pmf, cond, marg
+
+
+def light_sample(pmf, cond, marg, maps, u, space: str = "linear", minmax=None, texel_weight=None, jitter: bool = False, size=None):
+    """reni_light_sample: (index [B, S] int32, dirs [B, S, 3], pdf [B, S], radiance [B, S, 3], colors [B, S, 3]) for uniforms u
+    [S, 2] (shared) or [B, S, 2]; texel_weight [H W] float32 or None (1)."""
+    v = light_maps_view(maps, size)
+    m0, m1 = _light_space(space, minmax)
+    B, _, H, W = v.shape
+    for name, t, shape in (("pmf", pmf, (B, H, W)), ("cond", cond, (B, H, W)), ("marg", marg, (B, H))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 tensor {list(shape)} (the table of these maps)")
+    if not isinstance(u, torch.Tensor) or u.dim() not in (2, 3) or u.shape[-1] != 2 or u.shape[-2] < 1 or (u.dim() == 3 and u.shape[0] != B):
+        raise ValueError(f"u must be [S, 2] or [{B}, S, 2] with S >= 1, got {tuple(u.shape) if isinstance(u, torch.Tensor) else u!r}")
+    S = int(u.shape[-2])
+    if texel_weight is not None and (not isinstance(texel_weight, torch.Tensor) or tuple(texel_weight.shape) != (H * W,)):
+        raise ValueError(f"texel_weight must be a tensor [{H * W}] or None")
+    _require_cuda(v, pmf, cond, marg, u, texel_weight)
+    pmf, cond, marg, u = pmf.contiguous(), cond.contiguous(), marg.contiguous(), _f32c(u)
+    tw = None if texel_weight is None else _f32c(texel_weight)
+    lib = _lib.load()
+    dev = v.device
+    sa, rc, dt = light_grid(W, dev)
+    index = torch.empty(B, S, dtype=torch.int32, device=dev)
+    dirs, radiance, colors = (torch.empty(B, S, 3, dtype=torch.float32, device=dev) for _ in range(3))
+    pdf = torch.empty(B, S, dtype=torch.float32, device=dev)
+    _call(lib.reni_light_sample, dev, B, H, W, S, pmf.data_ptr(), cond.data_ptr(), marg.data_ptr(), v.data_ptr(),
+          (ctypes.c_int64 * 4)(*v.stride()), _lib.SPACE[space], m0, m1, u.data_ptr(), 0 if u.dim() == 2 else 2 * S, dt.data_ptr(),
+          sa.data_ptr(), rc.data_ptr(), None if tw is None else tw.data_ptr(), 1 if jitter else 0, index.data_ptr(), dirs.data_ptr(),
+          pdf.data_ptr(), radiance.data_ptr(), colors.data_ptr())
+    return index, dirs, pdf, radiance, colors
+
+
+def lights_irradiance(normals, dirs, colors, scale: float) -> torch.Tensor:
+    """reni_lights_irradiance: out [B, P, 3] = scale sum_s max(0, normals[p] . dirs[b, s]) colors[b, s] for light lists dirs,
+    colors [B, S, 3] and normals [P, 3] (shared) or [B, P, 3] (per map); no [B, P, S] tensor exists."""
+    for name, t in (("dirs", dirs), ("colors", colors), ("normals", normals)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor")
+    if dirs.dim() != 3 or dirs.shape[2] != 3 or dirs.shape != colors.shape or min(dirs.shape[:2]) < 1:
+        raise ValueError(f"dirs and colors must both be [B, S, 3], got {tuple(dirs.shape)} and {tuple(colors.shape)}")
+    B, S = int(dirs.shape[0]), int(dirs.shape[1])
+    if normals.dim() == 2 and normals.shape[1] == 3 and normals.shape[0] >= 1:
+        P, stride = int(normals.shape[0]), 0
+    elif normals.dim() == 3 and normals.shape[0] == B and normals.shape[2] == 3 and normals.shape[1] >= 1:
+        P = int(normals.shape[1])
+        stride = 3 * P
+    else:
+        raise ValueError(f"normals must be [P, 3] or [{B}, P, 3], got {tuple(normals.shape)}")
+    _require_cuda(normals, dirs, colors)
+    normals, dirs, colors = _f32c(normals), _f32c(dirs), _f32c(colors)
+    out = torch.empty(B, P, 3, dtype=torch.float32, device=dirs.device)
+    _call(_lib.load().reni_lights_irradiance, dirs.device, B, P, S, normals.data_ptr(), stride, dirs.data_ptr(), colors.data_ptr(),
+          float(scale), out.data_ptr())
+    return out
+
+
 def launch_count(reset: bool = False) -> int:
     """Kernel launches the library has issued so far in this process (reni_launch_count)."""
     return int(_lib.load().reni_launch_count(1 if reset else 0))

@@ -466,8 +466,11 @@ int reni_sh_irradiance_l2(int64_t N, int64_t P, const float* coeffs, const float
  *   srgb       : 1 = produce out_srgb [B][3][H][W]; 0 = only the linear image
  *   out_linear : [B][3][H][W] linear HDR, or NULL when not wanted (then srgb must be 1)
  *   ws         : reni_image_workspace_bytes(B, H, W) bytes, 256-byte aligned (needed when srgb = 1); H, W <= 4096
+ *   NaN propagates as in torch: a NaN (or an infinite largest channel) in an image makes its exposure, and so its whole sRGB
+ *   image, NaN, and no other image's; an exposure of 0 gives 1 for lit pixels and NaN (0 / 0) for zero ones.
  * reni_minmax_normalise is the forward transform MinMaxNormalise (custom_transforms.py:4-12) over the n elements of one
- * image: clip to [smallest positive, largest finite value of the image] -> log -> 2 (. - m0) / (m1 - m0) - 1. */
+ * image: clip to [smallest positive, largest finite value of the image] -> log -> 2 (. - m0) / (m1 - m0) - 1.  A NaN enters
+ * neither bound and stays NaN; -0.0 is a zero, not a bound. */
 size_t reni_image_workspace_bytes(int64_t B, int64_t H, int64_t W);
 int reni_unnormalise_srgb(int64_t B, int64_t H, int64_t W, const float* img, const int64_t strides[4], int32_t unnormalise,
                           double minmax0, double minmax1, int32_t srgb, float* out_srgb, float* out_linear, void* ws,

@@ -4,6 +4,10 @@
 // Reference:
 //   UnMinMaxNormlise   src/utils/custom_transforms.py:14-21   y = exp(0.5 (x + 1)(m1 - m0) + m0)
 //   sRGB               src/utils/utils.py:30-42               x / q_b -> clamp [0,1] -> sRGB transfer curve
+//
+// Pinned semantics: NaN propagates as in torch (torch.clamp keeps a NaN; fminf / fmaxf would return the other operand and
+// turn it into black), so a NaN pixel, a NaN exposure and 0 / 0 under an exposure q == 0 all come out NaN; a lit pixel
+// under q == 0 is +inf before the clamp and 1 after it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -18,7 +22,7 @@ __device__ __forceinline__ float img_unnormalise(float x, float range, float m0)
 // linear radiance under exposure q (the image's nested 0.98-quantile): divide, clamp, sRGB transfer curve (utils.py:35-41)
 __device__ __forceinline__ float img_srgb(float lin, float q) {
   float x = lin / q;
-  x = fminf(fmaxf(x, 0.f), 1.f);
+  x = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);  // torch.clamp(x, 0, 1): both comparisons are false for a NaN, which stays
   return (x <= 0.0031308f) ? 12.92f * x : 1.055f * powf(fabsf(x), 1.f / 2.4f) - 0.055f;
 }
 

@@ -16,6 +16,17 @@
 // thread counts the elements smaller than its own, ties broken by index): exact, deterministic, O(n^2 / 256) per thread
 // and the grids are small (B*W columns of H values, then B rows of W values) -- HBM traffic is the two passes over the
 // image (12 + 12 B per pixel and channel), which is what bounds it.
+//
+// Pinned semantics at the edges (tests/test_gpu_image.py holds each against torch on the host):
+//   NaN propagates as in torch: a NaN in any channel, column or row makes that quantile NaN (torch.quantile), so one NaN
+//     pixel makes its image's exposure q, and with it the whole sRGB image, NaN; the other images of the batch do not see
+//     it.  torch.clamp keeps NaN and so does img_srgb.  The linear image is written before any of this and is unaffected.
+//   q == 0 (an image whose 0.98-quantile is black): x / 0 is +inf for a lit pixel, which clamps to 1, and NaN for a
+//     zero pixel, which stays NaN -- never a valid-looking black picture.  An infinite lerp end gives NaN (inf - inf), as
+//     ATen's lerp does.
+//   MinMaxNormalise: the clip bounds are the smallest value > 0 and the largest value < inf; NaN takes part in neither
+//     (torch's masks drop it) and stays NaN in the output.  -0.0 is a zero, not a bound: it is not positive, and as a
+//     maximum it is the zero the search starts from (its sign bit must not enter the integer ordering of the bits).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -69,7 +80,11 @@ __global__ void __launch_bounds__(256) k_img_pass1(const ImgArgs a) {
     if (s[0] > s[1]) { const float t = s[0]; s[0] = s[1]; s[1] = t; }
     const float rank = a.qf * 2.f;
     const float fl = floorf(rank);
-    a.q1[i] = lerp_aten(s[(int)fl], s[(int)ceilf(rank)], rank - fl);
+    const float ql = lerp_aten(s[(int)fl], s[(int)ceilf(rank)], rank - fl);
+    // torch.quantile: a NaN anywhere in the reduced axis gives NaN (the exchanges above leave a NaN where it was, so the
+    // lerp alone would take its two neighbours)
+    const bool has_nan = v[0] != v[0] || v[1] != v[1] || v[2] != v[2];
+    a.q1[i] = has_nan ? __builtin_nanf("") : ql;
   }
 }
 
@@ -129,8 +144,10 @@ __global__ void __launch_bounds__(256) k_img_minmax(const float* in, long long n
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const float x = in[i];
     if (x > 0.f) lo = min(lo, __float_as_uint(x));
-    if (x < INFINITY && x >= 0.f) hi = max(hi, __float_as_uint(x));  // (radiance is never negative: a finite maximum below
-  }                                                                    //  zero is not representable in this encoding)
+    // x > 0, not x >= 0: -0.0 passes x >= 0 and its bits (0x80000000) beat every positive float.  A zero of either sign is
+    // the identity hi starts from.  (Radiance is never negative: a finite maximum below zero is not representable here.)
+    if (x < INFINITY && x > 0.f) hi = max(hi, __float_as_uint(x));
+  }
   for (int d = 32; d >= 1; d >>= 1) {
     lo = min(lo, (unsigned)__shfl_xor((int)lo, d, 64));
     hi = max(hi, (unsigned)__shfl_xor((int)hi, d, 64));
@@ -167,7 +184,7 @@ __global__ void __launch_bounds__(256) k_img_minmax_batch(const float* in, long 
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const float x = in[i];
     if (x > 0.f) lo = min(lo, __float_as_uint(x));
-    if (x < INFINITY && x >= 0.f) hi = max(hi, __float_as_uint(x));
+    if (x < INFINITY && x > 0.f) hi = max(hi, __float_as_uint(x));  // x > 0: see k_img_minmax (-0.0 is a zero, not a bound)
   }
   for (int d = 32; d >= 1; d >>= 1) {
     lo = min(lo, (unsigned)__shfl_xor((int)lo, d, 64));
@@ -240,15 +257,19 @@ int reni_unnormalise_srgb(int64_t B, int64_t H, int64_t W, const float* img, con
   }
   const long long npix = (long long)B * H * W;
   hipLaunchKernelGGL(reni::k_img_pass1, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
+  reni::note_launches(1);
   if (srgb) {
     // over H (dim 1 of [B,H,W]) -> [B,W]; then over W (dim 1 of [B,W]) -> [B]
     hipLaunchKernelGGL(reni::k_img_quantile, dim3((unsigned)(B * W)), dim3(256), 0, s, (const float*)a.q1, (int)H, (long long)W,
                        (int)W, (long long)H * W, 1LL, a.qf, q2);
+    reni::note_launches(1);
     hipLaunchKernelGGL(reni::k_img_quantile, dim3((unsigned)B), dim3(256), 0, s, (const float*)q2, (int)W, 1LL, 1, (long long)W, 0LL,
                        a.qf, q3);
+    reni::note_launches(1);
     a.q = q3;
     const long long n = npix * 3;
     hipLaunchKernelGGL(reni::k_img_pass2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    reni::note_launches(1);
   }
   return reni::hip_status();
 }
@@ -262,10 +283,13 @@ int reni_minmax_normalise(int64_t n, const float* img, double minmax0, double mi
   hipStream_t s = (hipStream_t)stream;
   unsigned* mm = (unsigned*)ws;
   hipLaunchKernelGGL(reni::k_img_minmax_init, dim3(1), dim3(1), 0, s, mm);
+  reni::note_launches(1);
   const long long nb = (n + 255) / 256;
   hipLaunchKernelGGL(reni::k_img_minmax, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s, img, (long long)n, mm);
+  reni::note_launches(1);
   hipLaunchKernelGGL(reni::k_img_normalise, dim3((unsigned)nb), dim3(256), 0, s, img, (long long)n, (const unsigned*)mm, (float)minmax0,
                      (float)(minmax1 - minmax0), out);
+  reni::note_launches(1);
   return reni::hip_status();
 }
 
@@ -281,10 +305,13 @@ int reni_minmax_normalise_batch(int64_t N, int64_t n, const float* imgs, double 
   hipStream_t s = (hipStream_t)stream;
   unsigned* mm = (unsigned*)ws;
   hipLaunchKernelGGL(reni::k_img_minmax_init_batch, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, mm, (int)N);
+  reni::note_launches(1);
   const long long nb = (n + 255) / 256;
   hipLaunchKernelGGL(reni::k_img_minmax_batch, dim3((unsigned)(nb < 128 ? nb : 128), (unsigned)N), dim3(256), 0, s, imgs, (long long)n, mm);
+  reni::note_launches(1);
   hipLaunchKernelGGL(reni::k_img_normalise_batch, dim3((unsigned)nb, (unsigned)N), dim3(256), 0, s, imgs, (long long)n,
                      (const unsigned*)mm, (float)minmax0, (float)(minmax1 - minmax0), nan_to_num ? 1 : 0, out);
+  reni::note_launches(1);
   return reni::hip_status();
 }
 

@@ -452,6 +452,45 @@ int reni_diffuse_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs
 int reni_sh_irradiance_l2(int64_t N, int64_t P, const float* coeffs, const float* normals, int64_t normals_stride_n, float* out,
                           void* stream);
 
+/* ---- glossy lighting: zonal-lobe convolution and lookup at arbitrary directions (reni_tu_glossy.hip; reni_amd/glossy.py) ----
+ * No reference counterpart.  fp32, deterministic (no float atomics; fixed summation order that depends on (P, Q) only): two
+ * calls give identical bits, map n's results are the same alone or inside a batch, and lobe l's results are the same alone
+ * or among other lobes.
+ * reni_lobe_convolve: for output directions o (out_dirs [P][3]), input directions d_i with weights w_i (in_dirs [Q][3],
+ *   in_w [Q]), N maps (src, addressed as in reni_diffuse_convolve) and n_lobes lobes (1..16),
+ *       t            = o . d_i                          (fp32: ox dx, then two fma, reni_diffuse_convolve's order)
+ *       num[n,l,o,c] = sum_i f_l(t) w_i src(n, i, c)    den[l,o] = sum_i f_l(t) w_i
+ *       out[n][l][o][c] = normalise ? (den > 0 ? num / den : 0) : scale num               out is [N][n_lobes][P][3]
+ *   With m = clamp((1 + t) / 2, 0, 1) and tc = clamp(t, 0, 1), lobe l is kinds[l] with the one parameter params[l] (HOST
+ *   arrays of n_lobes entries):
+ *       RENI_LOBE_PHONG  f = tc^n                                 n > 0
+ *       RENI_LOBE_BLINN  f = m^(s / 2)                            s > 0: (n . h)^s of the shader for view = normal
+ *       RENI_LOBE_GGX    f = tc a^2 / (m (a^2 - 1) + 1)^2         1e-9 <= a <= 1, a = roughness^2: D(h) (n . l) of the split-sum
+ *                                                                 prefilter under n = v = r, without 1 / pi
+ *   A power is exp2(p log2(b)); b = 0 gives 0.  PHONG(1) and GGX(1) are the clamped cosine.  den is one more column of the
+ *   same product (against ones), computed once per (lobe, o).  scale is ignored when normalising.
+ *   ws: reni_lobe_workspace_bytes(N, P, Q, n_lobes) bytes, 256-byte aligned (always needed: the partial sums of the i split,
+ *   which the library decides from (P, Q), and the division's operands).  n_lobes (3 N + 1) P and 3 Q < 2^30.
+ * reni_envmap_lookup: out [N][P][3] = the bilinear sample, on the sphere, of map n's level at direction p.  src element
+ *   (n, level, y, x, c) at src[n s[0] + level s[1] + y s[2] + x s[3] + c s[4]] (element strides >= 0, s[2] and s[3] < 2^31;
+ *   Lv = 1 with s[1] = 0 reads plain maps).  Direction p of map n is dirs[n dirs_stride_n + 3 p + 0..2], dirs_stride_n 0
+ *   (shared [P][3]) or 3 P (per map); it need not have unit length, and the zero vector samples the first row.  The
+ *   coordinate chain is reni_rotate_envmap's from s on (phi = atan2f(sqrtf(s.x^2 + s.z^2), s.y), theta = atan2f(s.x, -s.z),
+ *   the same row / col maps, clamps, pole and seam taps).  The level is level_const when level is NULL, else
+ *   level[n level_stride_n + p] (level_stride_n 0 or P); it is clamped to [0, Lv - 1] and the result mixes floor(level) and
+ *   the next level linearly, as one more lerp.  One launch, no workspace.  N, Lv <= 65535, H W < 2^30, W even, 3 N P < 2^30. */
+#define RENI_LOBE_PHONG 0
+#define RENI_LOBE_BLINN 1
+#define RENI_LOBE_GGX 2
+size_t reni_lobe_workspace_bytes(int64_t N, int64_t P, int64_t Q, int64_t n_lobes);
+int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, const float* in_dirs, const float* in_w,
+                       const float* src, int64_t src_stride_n, int64_t src_stride_i, int64_t src_stride_c, int n_lobes,
+                       const int32_t* kinds, const float* params, int normalise, float scale, float* out, void* ws,
+                       size_t ws_bytes, void* stream);
+int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* src, const int64_t src_strides[5],
+                       const float* dirs, int64_t dirs_stride_n, const float* level, int64_t level_stride_n, float level_const,
+                       float* out, void* stream);
+
 /* ---- HDR image epilogue / prologue ------------------------------------------------
  * reni_unnormalise_srgb replaces, on the device and in one call, the reference's viewing chain
  *   UnMinMaxNormlise(minmax)   src/utils/custom_transforms.py:14-21   y = exp(0.5 (x + 1)(m1 - m0) + m0)

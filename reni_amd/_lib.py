@@ -22,6 +22,7 @@ LOSS_KIND = {"mse": LOSS_MSE, "test": LOSS_TEST}
 NEED_DW, NEED_DZ, WEIGHT_SPARSE, WEIGHT_COMPACT, WEIGHT_COS_CONSTANT = 1, 2, 4, 8, 16
 COND_CONCAT, COND_FILM = 0, 1
 ROTATE_MODE = {"nearest": 0, "bilinear": 1}
+LOBE_KIND = {"phong": 0, "blinn": 1, "ggx": 2}  # RENI_LOBE_*
 SPACE = {"stored": 0, "linear": 1, "srgb": 2}
 SSIM_MODE = {"sphere": 0, "planar": 1}
 
@@ -37,6 +38,7 @@ EXPORTS = (
     "reni_raster_workspace_bytes", "reni_mesh_vertex_normals", "reni_rasterize_mesh",
     "reni_sg_workspace_bytes", "reni_sg_render", "reni_sg_loss_grad", "reni_sh_project", "reni_sh_reconstruct",
     "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
+    "reni_lobe_workspace_bytes", "reni_lobe_convolve", "reni_envmap_lookup",
     "reni_image_workspace_bytes", "reni_unnormalise_srgb", "reni_minmax_normalise",
     "reni_minmax_batch_workspace_bytes", "reni_minmax_normalise_batch",
     "reni_resample", "reni_blur_workspace_bytes", "reni_gaussian_blur", "reni_rotate_envmap",
@@ -199,6 +201,15 @@ def load():
     lib.reni_diffuse_convolve.restype = c_int32
     lib.reni_sh_irradiance_l2.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
     lib.reni_sh_irradiance_l2.restype = c_int32
+    lib.reni_lobe_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int64]
+    lib.reni_lobe_workspace_bytes.restype = c_size_t
+    lib.reni_lobe_convolve.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                       c_int64, c_int32, POINTER(c_int32), POINTER(c_float), c_int32, c_float, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]
+    lib.reni_lobe_convolve.restype = c_int32
+    lib.reni_envmap_lookup.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p,
+                                       c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p]
+    lib.reni_envmap_lookup.restype = c_int32
     lib.reni_image_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
     lib.reni_image_workspace_bytes.restype = c_size_t
     lib.reni_unnormalise_srgb.argtypes = [c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_int32, ctypes.c_double,

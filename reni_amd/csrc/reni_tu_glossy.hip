@@ -1,0 +1,419 @@
+// translation unit of libreni_hip.so: environment maps as glossy lighting -- the convolution of maps with a chain of zonal
+// specular lobes, and the lookup of maps or of such a chain at arbitrary directions (reni_amd/glossy.py).  No reference
+// counterpart: the reference lights glossy surfaces with its per-pixel Blinn-Phong shader only (reni_tu_shade.hip).
+//
+// fp32 throughout, no float atomics: every sum runs in a fixed order that depends on (P, Q) only, so two calls give identical
+// bits, a map's results do not depend on the batch around it, and a lobe's results do not depend on the lobes that share the
+// call.  Contraction is off for the whole unit: what is written is what runs.
+//
+//   k_lobe_convolve<KIND, CT>  part[s][l][col][o] = sum_(i in chunk s) f_l(o . d_i) (w_i scale) B[i][col], the GEMM of
+//                       k_diffuse_convolve (reni_tu_diffuse.hip: same tiles, same i split, same v_mfma_f32_32x32x2_f32 chain)
+//                       with another A generator: t = fma(oz, dz, fma(oy, dy, ox dx)), then the lobe, one straight-line
+//                       generator per KIND with the lobe's parameter a uniform argument.  B's columns are the batch's 3 N
+//                       colour columns and, when the call normalises, ONE column of ones behind them: the denominator
+//                       sum_i f_l w_i comes out of the same chain once per (lobe, o), not once per map.  blockIdx.z is
+//                       (lobe of this kind, split): a lobe never shares a workgroup with another.
+//   k_lobe_finish       out[n][l][o][c] = ((part_0 + part_1) + ...) of column 3 n + c, divided by the same sum of the
+//                       column of ones when normalising (0 where that sum is not positive).  The division sits here and
+//                       not behind the MFMAs: arithmetic on the accumulators makes hipcc copy them ahead of the drain pad.
+//   k_envmap_lookup     out[n][p][c] = the bilinear sample of src[n][level][.][.][c] at direction dirs[p] (or dirs[n][p]),
+//                       mixed linearly between floor(level) and the next level.  The coordinate chain is k_rotate_envmap's
+//                       (reni_tu_rotate.hip) from s on, COPIED here so that unit's bits cannot move: one lane per direction
+//                       computes the coordinate once and serves the channels and both levels with it.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "reni_hip.h"
+#include "reni_internal.h"
+
+#pragma clang fp contract(off)
+
+#define DEV __device__ __forceinline__
+
+namespace reni {
+
+typedef float lb_f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int LB_OT = 2;     // 32-row output tiles per wave
+constexpr int LB_WAVES = 4;  // waves per workgroup, each its own output rows
+constexpr int LB_ROWS = 32 * LB_OT * LB_WAVES;
+constexpr int LB_MAX_LOBES = 16;
+
+DEV constexpr int lb_rowmap(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }  // 32x32 MFMA result row
+
+DEV void lb_mfma_drain() {  // wait out the last MFMA's write-back (18 states) before its result is read
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_nop 15\n\ts_nop 3");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+struct LbArgs {
+  int N, P, Q;
+  int ncol;               // 3 N, plus the column of ones when normalising
+  const float* out_dirs;  // [P][3]
+  const float* in_dirs;   // [Q][3]
+  const float* in_w;      // [Q]
+  const float* src;       // element (n, i, c) at n sn + i si + c sc
+  int64_t sn, si, sc;
+  float scale;
+  int chunk;  // i per split (even)
+  int S;      // splits
+  int Lv;     // lobes of the call
+  int nl;     // lobes of this launch (one kind)
+  int lobe[LB_MAX_LOBES];   // their index in the call
+  float par[LB_MAX_LOBES];  // PHONG: n; BLINN: s / 2; GGX: alpha^2
+  float* ws;                // [S][Lv][ncol][P] partial sums
+};
+
+DEV float lb_clamp01(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, 1.f); }
+// b^p = exp2(p log2 b) on the hardware's v_log_f32 / v_exp_f32 (1 ulp each); b = 0: log2 = -inf, p > 0, exp2 = 0
+DEV float lb_pow(float b, float p) { return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(b)); }
+
+template <int KIND>
+DEV float lb_lobe(float t, float p);
+template <>
+DEV float lb_lobe<RENI_LOBE_PHONG>(float t, float p) { return lb_pow(lb_clamp01(t), p); }
+template <>
+DEV float lb_lobe<RENI_LOBE_BLINN>(float t, float p) { return lb_pow(lb_clamp01(fmaf(t, 0.5f, 0.5f)), p); }
+template <>
+DEV float lb_lobe<RENI_LOBE_GGX>(float t, float p) {
+  // m (a2 - 1) + 1 written as fma(m, a2, 1 - m): 1 - m is exact for m >= 1/2, where the sum cancels.  a2 / d^2 as
+  // ((a2 r) r) with r = 1 / d <= 1 / a2, so that no intermediate leaves the normal range for a2 >= 2^-60
+  const float m = lb_clamp01(fmaf(t, 0.5f, 0.5f));
+  const float r = __builtin_amdgcn_rcpf(fmaf(m, p, 1.f - m));
+  return ((p * r) * r) * lb_clamp01(t);
+}
+
+template <int KIND, int CT>
+__global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hi = lane >> 5;
+  const int ll = (int)blockIdx.z / a.S, sp = (int)blockIdx.z - ll * a.S;  // lobe of this launch, split
+  const float par = a.par[ll];
+  const int64_t o0 = (int64_t)blockIdx.x * LB_ROWS + wave * (32 * LB_OT);
+  float ox[LB_OT], oy[LB_OT], oz[LB_OT];
+#pragma unroll
+  for (int u = 0; u < LB_OT; ++u) {
+    const int64_t o = o0 + u * 32 + j;
+    const bool ok = o < a.P;
+    ox[u] = ok ? a.out_dirs[3 * o] : 0.f;
+    oy[u] = ok ? a.out_dirs[3 * o + 1] : 0.f;
+    oz[u] = ok ? a.out_dirs[3 * o + 2] : 0.f;
+  }
+  const float* colp[CT];
+  bool cok[CT], img[CT];
+  float fill[CT];  // what a lane feeds in place of a map's value: 1 in the column of ones, 0 beyond the last column
+#pragma unroll
+  for (int v = 0; v < CT; ++v) {
+    const int64_t col = (int64_t)blockIdx.y * (32 * CT) + v * 32 + j;
+    cok[v] = col < a.ncol;
+    img[v] = col < 3 * (int64_t)a.N;
+    fill[v] = cok[v] && !img[v] ? 1.f : 0.f;  // (col == 3 N < ncol only when normalising)
+    const int64_t n = img[v] ? col / 3 : 0;
+    const int64_t c = img[v] ? col - 3 * n : 0;
+    colp[v] = a.src + n * a.sn + c * a.sc;
+  }
+  lb_f32x16 acc[LB_OT][CT];
+#pragma unroll
+  for (int u = 0; u < LB_OT; ++u)
+#pragma unroll
+    for (int v = 0; v < CT; ++v)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[u][v][r] = 0.f;
+  // i = i0 + hi: lanes 0..31 feed k = 0 of the MFMA, lanes 32..63 k = 1.  The scale is folded into the weight, so the
+  // accumulators are stored as they are.
+  const int ilo = sp * a.chunk;
+  const int ihi = ilo + a.chunk < a.Q ? ilo + a.chunk : a.Q;
+  const float* dp = a.in_dirs + 3 * (int64_t)(ilo + hi);
+  const float* wp = a.in_w + ilo + hi;
+  const int64_t bstep = 2 * a.si;
+#pragma unroll
+  for (int v = 0; v < CT; ++v) colp[v] += (int64_t)(ilo + hi) * a.si;
+  // one k-step; iok false zeroes both operands of the lanes of i == ihi (the tail of an odd range)
+  auto step = [&](const bool iok) __attribute__((always_inline)) {
+    const float dx = dp[0], dy = dp[1], dz = dp[2];
+    const float w = iok ? wp[0] * a.scale : 0.f;
+    float b[CT];
+#pragma unroll
+    for (int v = 0; v < CT; ++v) {
+      const float x = *colp[v];
+      b[v] = iok ? (img[v] ? x : fill[v]) : 0.f;  // (every lane loads: map 0 where there is no map, the value dropped)
+    }
+#pragma unroll
+    for (int u = 0; u < LB_OT; ++u) {
+      float t = ox[u] * dx;
+      t = fmaf(oy[u], dy, t);
+      t = fmaf(oz[u], dz, t);
+      const float av = lb_lobe<KIND>(t, par) * w;
+#pragma unroll
+      for (int v = 0; v < CT; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[v], acc[u][v], 0, 0, 0);
+    }
+  };
+  int i0 = ilo;
+  for (; i0 + 1 < ihi; i0 += 2) {
+    step(true);
+    dp += 6;
+    wp += 2;
+#pragma unroll
+    for (int v = 0; v < CT; ++v) colp[v] += bstep;
+  }
+  if (i0 < ihi) {  // odd range: the lanes of i0 + 1 re-read i0 and contribute zero
+    dp -= 3 * hi;
+    wp -= hi;
+#pragma unroll
+    for (int v = 0; v < CT; ++v) colp[v] -= hi * a.si;
+    step(hi == 0);
+  }
+  lb_mfma_drain();
+  float* dst = a.ws + ((int64_t)sp * a.Lv + a.lobe[ll]) * a.ncol * a.P;
+#pragma unroll
+  for (int v = 0; v < CT; ++v) {
+    if (!cok[v]) continue;
+    const int64_t col = (int64_t)blockIdx.y * (32 * CT) + v * 32 + j;
+    float* op = dst + col * a.P;
+#pragma unroll
+    for (int u = 0; u < LB_OT; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t o = o0 + u * 32 + lb_rowmap(r, hi);
+        if (o < a.P) op[o] = acc[u][v][r];
+      }
+  }
+}
+
+// one lane per (lobe, map, o): the partial sums of a column in split order, then the division
+__global__ void __launch_bounds__(256) k_lobe_finish(const float* __restrict__ ws, int N, int Lv, int P, int ncol, int S,
+                                                     int normalise, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)Lv * N * P) return;
+  const int64_t o = e % P, ln = e / P;
+  const int64_t n = ln % N, l = ln / N;
+  const int64_t slab = (int64_t)Lv * ncol * P;
+  const float* base = ws + l * ncol * P + o;
+  float v[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* p = base + (3 * n + c) * P;
+    float x = p[0];
+    for (int s = 1; s < S; ++s) x += p[(int64_t)s * slab];
+    v[c] = x;
+  }
+  if (normalise) {
+    const float* p = base + 3 * (int64_t)N * P;
+    float den = p[0];
+    for (int s = 1; s < S; ++s) den += p[(int64_t)s * slab];
+    const bool ok = den > 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = ok ? v[c] / den : 0.f;
+  }
+  float* q = out + ((n * Lv + l) * P + o) * 3;
+  q[0] = v[0];
+  q[1] = v[1];
+  q[2] = v[2];
+}
+
+struct LkArgs {
+  const float* src;  // element (n, level, y, x, c) at n sn + level sl + y sy + x sx + c sc
+  int64_t sn, sl, sc;
+  int sy, sx;  // (< 2^31, checked, as in reni_rotate_envmap)
+  const float* dirs;  // direction p of map n at dirs + n dn + 3 p
+  int64_t dn;
+  const float* level;  // NULL: level_const for every direction; else level[n ln + p]
+  int64_t ln;
+  float level_const;
+  float* out;  // [N][P][3]
+  int Lv, H, W, P;
+  float row_scale, col_scale, col_bias;  // fp32(H / pi), fp32(W / 2 pi), W/2 - 1/2
+};
+
+__global__ void __launch_bounds__(256) k_envmap_lookup(const LkArgs a) {
+  const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;  // P < 2^30
+  if (p >= a.P) return;
+  const int64_t n = blockIdx.y;
+  const float* d = a.dirs + n * a.dn + 3 * (int64_t)p;
+  const float sx = d[0], sy = d[1], sz = d[2];
+  // ---- k_rotate_envmap's chain from s on (a copy: see the header).  atan2f needs no unit length; the zero vector gives
+  // phi = atan2f(0, 0) = 0, a finite theta and so the first row
+  const float phi = atan2f(sqrtf(fmaf(sz, sz, sx * sx)), sy);
+  const float theta = atan2f(sx, -sz);
+  // the clamps change nothing for finite directions; they keep a NaN or an overflow from becoming an address
+  const float row = fminf(fmaxf(fmaf(phi, a.row_scale, -0.5f), -1.f), (float)a.H);
+  const float col = fminf(fmaxf(fmaf(theta, a.col_scale, a.col_bias), -1.f), (float)a.W);
+  const float fi = floorf(row), fj = floorf(col);
+  const int i = (int)fi, j = (int)fj;
+  const float fr = row - fi, fc = col - fj;
+  const float gr = 1.f - fr, gc = 1.f - fc;
+  const int half = a.W >> 1;
+  int i0 = i, i1 = i + 1;
+  const bool x0 = i0 < 0 || i0 >= a.H, x1 = i1 >= a.H;  // beyond a pole: the far side
+  if (i0 < 0) i0 = -1 - i0;
+  if (i0 >= a.H) i0 = 2 * a.H - 1 - i0;
+  if (i1 >= a.H) i1 = 2 * a.H - 1 - i1;
+  i0 = min(max(i0, 0), a.H - 1);
+  i1 = min(max(i1, 0), a.H - 1);
+  int j0 = j < 0 ? j + a.W : (j >= a.W ? j - a.W : j);
+  int j1 = j + 1 >= a.W ? j + 1 - a.W : j + 1;
+  if (j1 >= a.W) j1 -= a.W;
+  const int j0f = j0 + half >= a.W ? j0 - half : j0 + half, j1f = j1 + half >= a.W ? j1 - half : j1 + half;
+  const int64_t r0 = (int64_t)i0 * (int64_t)a.sy, r1 = (int64_t)i1 * (int64_t)a.sy;
+  const int64_t o00 = r0 + (int64_t)(x0 ? j0f : j0) * (int64_t)a.sx, o01 = r0 + (int64_t)(x0 ? j1f : j1) * (int64_t)a.sx;
+  const int64_t o10 = r1 + (int64_t)(x1 ? j0f : j0) * (int64_t)a.sx, o11 = r1 + (int64_t)(x1 ? j1f : j1) * (int64_t)a.sx;
+  // ---- the level: clamped to [0, Lv - 1] (fmaxf drops a NaN), one more lerp in the same fma order
+  float lv = a.level ? a.level[n * a.ln + p] : a.level_const;
+  lv = fminf(fmaxf(lv, 0.f), (float)(a.Lv - 1));
+  const float fl0 = floorf(lv);
+  const int l0 = (int)fl0, l1 = min(l0 + 1, a.Lv - 1);
+  const float fl = lv - fl0, gl = 1.f - fl;
+  const float* b0 = a.src + n * a.sn + (int64_t)l0 * a.sl;
+  const float* b1 = a.src + n * a.sn + (int64_t)l1 * a.sl;
+  float* o = a.out + (n * a.P + p) * 3;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch, b0 += a.sc, b1 += a.sc) {
+    const float top = fmaf(fc, b0[o01], gc * b0[o00]);
+    const float bot = fmaf(fc, b0[o11], gc * b0[o10]);
+    float v = fmaf(fr, bot, gr * top);
+    if (fl > 0.f) {  // (fl == 0 would give the same bits for finite maps: fma(0, v1, 1 v))
+      const float top1 = fmaf(fc, b1[o01], gc * b1[o00]);
+      const float bot1 = fmaf(fc, b1[o11], gc * b1[o10]);
+      v = fmaf(fl, fmaf(fr, bot1, gr * top1), gl * v);
+    }
+    o[ch] = v;
+  }
+}
+
+}  // namespace reni
+
+namespace {
+
+using reni::hip_status;
+using reni::reni_set_error;
+constexpr int64_t LB_MAX_ELEMS = 0x3fffffff;
+constexpr int64_t LB_MIN_CHUNK = 2048;  // fewest i per split
+constexpr int64_t LB_TARGET_WGS = 256;  // workgroups per (column group, lobe) the split aims for (one per CU)
+
+bool lb_shape_ok(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
+  return N >= 1 && P >= 1 && Q >= 1 && Lv >= 1 && Lv <= reni::LB_MAX_LOBES && P <= LB_MAX_ELEMS / 3 && Q <= LB_MAX_ELEMS / 3 &&
+         N <= (LB_MAX_ELEMS / (3 * P) - 1) / Lv && (3 * N + 1 + 31) / 32 <= 65535;
+}
+
+// the i split: reni_diffuse_convolve's rule, a function of (P, Q) only -- not of N, and not of the lobes
+void lb_split(int64_t P, int64_t Q, int64_t& S, int64_t& chunk) {
+  const int64_t wgs = (P + reni::LB_ROWS - 1) / reni::LB_ROWS;
+  int64_t s = (LB_TARGET_WGS + wgs - 1) / wgs;
+  const int64_t smax = Q / LB_MIN_CHUNK > 1 ? Q / LB_MIN_CHUNK : 1;
+  if (s > smax) s = smax;
+  chunk = (Q + s - 1) / s;
+  chunk += chunk & 1;
+  S = (Q + chunk - 1) / chunk;
+}
+
+int64_t lb_ws_bytes(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
+  int64_t S, chunk;
+  lb_split(P, Q, S, chunk);
+  return S * Lv * (3 * N + 1) * P * (int64_t)sizeof(float);
+}
+
+template <int KIND>
+void lb_launch(const reni::LbArgs& a, hipStream_t s) {
+  const unsigned gx = (unsigned)((a.P + reni::LB_ROWS - 1) / reni::LB_ROWS), gz = (unsigned)(a.nl * a.S);
+  if (a.ncol <= 32) {
+    hipLaunchKernelGGL((reni::k_lobe_convolve<KIND, 1>), dim3(gx, 1, gz), dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((reni::k_lobe_convolve<KIND, 2>), dim3(gx, (unsigned)((a.ncol + 63) / 64), gz), dim3(256), 0, s, a);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t reni_lobe_workspace_bytes(int64_t N, int64_t P, int64_t Q, int64_t n_lobes) {
+  if (!lb_shape_ok(N, P, Q, n_lobes)) return 0;
+  return (size_t)lb_ws_bytes(N, P, Q, n_lobes) + 256;
+}
+
+int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, const float* in_dirs, const float* in_w,
+                       const float* src, int64_t src_stride_n, int64_t src_stride_i, int64_t src_stride_c, int n_lobes,
+                       const int32_t* kinds, const float* params, int normalise, float scale, float* out, void* ws,
+                       size_t ws_bytes, void* stream) {
+  if (n_lobes < 1 || n_lobes > reni::LB_MAX_LOBES) return reni_set_error(RENI_EINVAL, "lobe convolve: need 1 <= n_lobes <= 16");
+  if (!lb_shape_ok(N, P, Q, n_lobes))
+    return reni_set_error(RENI_EINVAL, "lobe convolve: need N, P, Q >= 1 and n_lobes N P, Q < 2^28");
+  if (!out_dirs || !in_dirs || !in_w || !src || !out || !kinds || !params)
+    return reni_set_error(RENI_EINVAL, "lobe convolve: NULL argument");
+  for (int l = 0; l < n_lobes; ++l) {
+    const float p = params[l];
+    if (kinds[l] != RENI_LOBE_PHONG && kinds[l] != RENI_LOBE_BLINN && kinds[l] != RENI_LOBE_GGX)
+      return reni_set_error(RENI_EINVAL, "lobe convolve: unknown lobe kind");
+    if (!(p > 0.f) || !(p <= 3.0e38f))
+      return reni_set_error(RENI_EINVAL, "lobe convolve: a lobe's parameter must be positive and finite");
+    if (kinds[l] == RENI_LOBE_GGX && !(p <= 1.f && p >= 1e-9f))
+      return reni_set_error(RENI_EINVAL, "lobe convolve: GGX needs 1e-9 <= alpha <= 1");
+  }
+  if (src_stride_n < 0 || src_stride_i < 0 || src_stride_c < 0)
+    return reni_set_error(RENI_EINVAL, "lobe convolve: src strides must be >= 0");
+  const size_t need = (size_t)lb_ws_bytes(N, P, Q, n_lobes);
+  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
+    return reni_set_error(RENI_EWORKSPACE, "lobe convolve: workspace missing, too small or not 256-byte aligned");
+  reni::LbArgs a = {};
+  a.N = (int)N; a.P = (int)P; a.Q = (int)Q;
+  a.ncol = (int)(3 * N + (normalise ? 1 : 0));
+  a.out_dirs = out_dirs; a.in_dirs = in_dirs; a.in_w = in_w;
+  a.src = src; a.sn = src_stride_n; a.si = src_stride_i; a.sc = src_stride_c;
+  a.scale = normalise ? 1.f : scale;  // a normalised result does not depend on the scale
+  int64_t S, chunk;
+  lb_split(P, Q, S, chunk);
+  a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
+  a.ws = (float*)ws;
+  hipStream_t s = (hipStream_t)stream;
+  for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind) {  // one launch per kind present, its lobes along z
+    a.nl = 0;
+    for (int l = 0; l < n_lobes; ++l) {
+      if (kinds[l] != kind) continue;
+      a.lobe[a.nl] = l;
+      a.par[a.nl] = kind == RENI_LOBE_BLINN ? 0.5f * params[l] : kind == RENI_LOBE_GGX ? params[l] * params[l] : params[l];
+      ++a.nl;
+    }
+    if (!a.nl) continue;
+    if (kind == RENI_LOBE_PHONG) lb_launch<RENI_LOBE_PHONG>(a, s);
+    else if (kind == RENI_LOBE_BLINN) lb_launch<RENI_LOBE_BLINN>(a, s);
+    else lb_launch<RENI_LOBE_GGX>(a, s);
+    if (int rc = hip_status()) return rc;
+  }
+  const int64_t total = (int64_t)n_lobes * N * P;
+  hipLaunchKernelGGL(reni::k_lobe_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)a.ws, (int)N,
+                     n_lobes, (int)P, a.ncol, (int)S, normalise ? 1 : 0, out);
+  return hip_status();
+}
+
+int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* src, const int64_t src_strides[5],
+                       const float* dirs, int64_t dirs_stride_n, const float* level, int64_t level_stride_n, float level_const,
+                       float* out, void* stream) {
+  if (N < 1 || Lv < 1 || H < 1 || W < 1 || P < 1) return reni_set_error(RENI_EINVAL, "lookup: sizes must be >= 1");
+  if (W & 1) return reni_set_error(RENI_EINVAL, "lookup: W must be even (the far side of a pole is W / 2 columns away)");
+  if (N > 65535 || Lv > 65535 || H > 0x3fffffff / W || P > 0x3fffffff / 3 || N > 0x3fffffff / (3 * P))
+    return reni_set_error(RENI_EINVAL, "lookup: need N, Lv <= 65535, H W < 2^30 and N P < 2^28");
+  if (!src || !src_strides || !dirs || !out) return reni_set_error(RENI_EINVAL, "lookup: NULL argument");
+  for (int k = 0; k < 5; ++k)
+    if (src_strides[k] < 0) return reni_set_error(RENI_EINVAL, "lookup: src strides must be >= 0");
+  if (src_strides[2] > 0x7fffffff || src_strides[3] > 0x7fffffff)
+    return reni_set_error(RENI_EINVAL, "lookup: the row and column strides must be < 2^31 elements");
+  if (dirs_stride_n != 0 && dirs_stride_n != 3 * P)
+    return reni_set_error(RENI_EINVAL, "lookup: dirs_stride_n must be 0 (shared) or 3 P (per map)");
+  if (level && level_stride_n != 0 && level_stride_n != P)
+    return reni_set_error(RENI_EINVAL, "lookup: level_stride_n must be 0 (shared) or P (per map)");
+  reni::LkArgs a = {};
+  a.src = src; a.sn = src_strides[0]; a.sl = src_strides[1]; a.sy = (int)src_strides[2]; a.sx = (int)src_strides[3];
+  a.sc = src_strides[4];
+  a.dirs = dirs; a.dn = dirs_stride_n; a.level = level; a.ln = level ? level_stride_n : 0; a.level_const = level_const;
+  a.out = out;
+  a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
+  const double pi = 3.14159265358979323846;
+  a.row_scale = (float)((double)H / pi);
+  a.col_scale = (float)((double)W / (2.0 * pi));
+  a.col_bias = (float)(0.5 * (double)W - 0.5);
+  hipLaunchKernelGGL(reni::k_envmap_lookup, dim3((unsigned)((P + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream, a);
+  return reni::hip_status();
+}
+
+}  // extern "C"

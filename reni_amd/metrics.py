@@ -227,13 +227,14 @@ def _dataset_info(dataset):
     return int(H), int(W), getattr(un, "minmax", None)
 
 
-def evaluate(model, dataset, idx=None, batch_size=16, mask=None, diffuse=False, minmax="dataset"):
+def evaluate(model, dataset, idx=None, batch_size=16, mask=None, diffuse=False, minmax="dataset", glossy=None):
     """Score the model's reconstruction of dataset images: a forward pass at the dataset's resolution, ``score_maps`` against
     the dataset's images (``ResidentDataset.batch`` where the dataset is resident, ``dataset[i]`` otherwise).  idx: the
     images (default: all); latent i belongs to image i.  minmax: "dataset" takes ``dataset.unnormalise.minmax`` (None when
     the dataset has none: stored-space scores only).  diffuse=True adds ``diffuse_psnr``: psnr_linear (solid-angle weighted,
     peak = the target's largest irradiance) of ``baselines.irradiance_map`` of the linear prediction against that of the
-    linear target.  Returns (table, means): dicts of [N] tensors and of 0-d tensors, on the model's device."""
+    linear target.  glossy: a list of lobes (``glossy.phong / blinn / ggx``) adds ``glossy_psnr_<k>`` for lobe k, the same score
+    of ``glossy.prefilter`` of the two.  Returns (table, means): dicts of [N] tensors and of 0-d tensors, on the model's device."""
     from .utils import get_directions
     H, W, ds_minmax = _dataset_info(dataset)
     if minmax == "dataset":
@@ -244,6 +245,9 @@ def evaluate(model, dataset, idx=None, batch_size=16, mask=None, diffuse=False, 
         raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     if diffuse and minmax is None:
         raise ValueError("diffuse=True compares irradiance, which needs linear radiance: no minmax to un-normalise with")
+    glossy = list(glossy) if glossy is not None else []
+    if glossy and minmax is None:
+        raise ValueError("glossy= compares prefiltered radiance, which needs linear radiance: no minmax to un-normalise with")
     idx = list(range(len(dataset))) if idx is None else [int(i) for i in (idx.tolist() if isinstance(idx, torch.Tensor) else idx)]
     if not idx:
         raise ValueError("no images to evaluate")
@@ -269,6 +273,15 @@ def evaluate(model, dataset, idx=None, batch_size=16, mask=None, diffuse=False, 
                 it = irradiance_map(lt.permute(0, 2, 3, 1).reshape(len(chunk), H * W, 3))
                 s = ops.pair_stats(ip, it, solid_angle_weight(H, dev), "stored", size=(H, W))
                 row["diffuse_psnr"] = psnr_from_stats(s, "target_max")
+            if glossy:
+                from .glossy import prefilter
+                lp = ops.unnormalise_srgb(pred.unflatten(1, (H, W)).permute(0, 3, 1, 2), minmax, srgb=False)
+                lt = ops.unnormalise_srgb(target, minmax, srgb=False)
+                gp = prefilter(lp.permute(0, 2, 3, 1).reshape(len(chunk), H * W, 3), glossy)  # [B, Lv, H W, 3]
+                gt = prefilter(lt.permute(0, 2, 3, 1).reshape(len(chunk), H * W, 3), glossy)
+                for j in range(len(glossy)):
+                    s = ops.pair_stats(gp[:, j], gt[:, j], solid_angle_weight(H, dev), "stored", size=(H, W))
+                    row[f"glossy_psnr_{j}"] = psnr_from_stats(s, "target_max")
             rows.append(row)
     table = {k: torch.cat([r[k] for r in rows]) for k in rows[0]}
     return table, {k: v.mean() for k, v in table.items()}

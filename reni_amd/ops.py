@@ -716,11 +716,9 @@ def sh_reconstruct(coeffs, row_table, col_table, H: int, W: int, lmax: int) -> t
     return _sh_call(False, coeffs, row_table, col_table, int(H), int(W), int(lmax))
 
 
-def diffuse_convolve(src, in_dirs, in_weight, out_dirs, scale: float) -> torch.Tensor:
-    """reni_diffuse_convolve: out [N, P, 3] = scale sum_i max(0, out_dirs[o] . in_dirs[i]) in_weight[i] src[n, i, c].
-    src is [N, Q, 3] or channel-planar [N, 3, Q], read through its own strides (any float32 view of those shapes);
-    in_dirs [Q, 3], in_weight [Q], out_dirs [P, 3] are shared by the N maps."""
-    _require_cuda(src, in_dirs, in_weight, out_dirs)
+def _convolve_args(src, in_dirs, in_weight, out_dirs):
+    """The operands the convolutions over the sphere share: (src float32, in_dirs, in_weight, out_dirs contiguous float32,
+    N, P, Q, src's element strides (map, texel, channel)) for src [N, Q, 3] or channel-planar [N, 3, Q]."""
     in_dirs, in_weight, out_dirs = _f32c(in_dirs), _f32c(in_weight), _f32c(out_dirs)
     if in_dirs.dim() != 2 or in_dirs.shape[1] != 3 or out_dirs.dim() != 2 or out_dirs.shape[1] != 3:
         raise ValueError("in_dirs and out_dirs must be [Q, 3] and [P, 3]")
@@ -738,6 +736,15 @@ def diffuse_convolve(src, in_dirs, in_weight, out_dirs, scale: float) -> torch.T
         sn, sc, si = src.stride()
     else:
         raise ValueError(f"src must be [N, Q, 3] or [N, 3, Q] with Q = {Q}, got {tuple(src.shape)}")
+    return src, in_dirs, in_weight, out_dirs, N, P, Q, sn, si, sc
+
+
+def diffuse_convolve(src, in_dirs, in_weight, out_dirs, scale: float) -> torch.Tensor:
+    """reni_diffuse_convolve: out [N, P, 3] = scale sum_i max(0, out_dirs[o] . in_dirs[i]) in_weight[i] src[n, i, c].
+    src is [N, Q, 3] or channel-planar [N, 3, Q], read through its own strides (any float32 view of those shapes);
+    in_dirs [Q, 3], in_weight [Q], out_dirs [P, 3] are shared by the N maps."""
+    _require_cuda(src, in_dirs, in_weight, out_dirs)
+    src, in_dirs, in_weight, out_dirs, N, P, Q, sn, si, sc = _convolve_args(src, in_dirs, in_weight, out_dirs)
     dev = src.device
     out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
     lib = _lib.load()
@@ -772,6 +779,81 @@ def _ws256(nbytes, device):
     p = ws.data_ptr()
     ap = (p + 255) & ~255
     return ws, ap, ws.numel() - (ap - p)
+
+
+def lobe_convolve(src, in_dirs, in_weight, out_dirs, kinds, params, normalise: bool = True, scale: float = 1.0) -> torch.Tensor:
+    """reni_lobe_convolve: out [N, Lv, P, 3] = the maps convolved with Lv zonal lobes f_l(out_dirs[o] . in_dirs[i]) weighted
+    by in_weight[i]; divided by sum_i f_l in_weight[i] when normalise (0 where that sum is not positive), else times scale.
+    kinds: Lv names of _lib.LOBE_KIND ("phong": tc^n, "blinn": m^(s/2), "ggx": tc a^2 / (m (a^2 - 1) + 1)^2 with
+    tc = clamp(t, 0, 1), m = clamp((1 + t) / 2, 0, 1)); params: their one parameter each (n, s, a).  src, in_dirs, in_weight,
+    out_dirs as in ``diffuse_convolve``."""
+    _require_cuda(src, in_dirs, in_weight, out_dirs)
+    kinds, params = list(kinds), [float(p) for p in params]
+    Lv = len(kinds)
+    if not 1 <= Lv <= 16 or len(params) != Lv:
+        raise ValueError(f"need 1..16 lobes and one parameter each, got {Lv} kinds and {len(params)} parameters")
+    for k in kinds:
+        if k not in _lib.LOBE_KIND:
+            raise ValueError(f"lobe kind must be one of {tuple(_lib.LOBE_KIND)}, got {k!r}")
+    src, in_dirs, in_weight, out_dirs, N, P, Q, sn, si, sc = _convolve_args(src, in_dirs, in_weight, out_dirs)
+    dev = src.device
+    out = torch.empty(N, Lv, P, 3, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws, wp, wn = _ws256(int(lib.reni_lobe_workspace_bytes(N, P, Q, Lv)), dev)
+    ck = (ctypes.c_int32 * Lv)(*[_lib.LOBE_KIND[k] for k in kinds])
+    cp = (ctypes.c_float * Lv)(*params)
+    _call(lib.reni_lobe_convolve, dev, N, P, Q, out_dirs.data_ptr(), in_dirs.data_ptr(), in_weight.data_ptr(), src.data_ptr(),
+          sn, si, sc, Lv, ck, cp, 1 if normalise else 0, float(scale), out.data_ptr(), wp, wn)
+    return out
+
+
+def envmap_lookup(maps, dirs, level=None) -> torch.Tensor:
+    """reni_envmap_lookup: the bilinear sample, on the sphere, of equirectangular maps [N, H, W, 3] or chains of maps
+    [N, Lv, H, W, 3] (any strides, read in place) at directions dirs [P, 3] (shared) or [N, P, 3] (per map), which need not
+    have unit length -> [N, P, 3].  level: None (level 0), a number, or a float tensor [P] / [N, P]; it is clamped to
+    [0, Lv - 1] and the result mixes floor(level) and the next level linearly."""
+    _require_cuda(maps, dirs, level if isinstance(level, torch.Tensor) and level.dim() > 0 else None)
+    if maps.dtype != torch.float32:
+        maps = maps.float()
+    if maps.dim() == 4:
+        maps = maps.unsqueeze(1)
+    if maps.dim() != 5 or maps.shape[4] != 3:
+        raise ValueError(f"maps must be [N, H, W, 3] or [N, Lv, H, W, 3], got {tuple(maps.shape)}")
+    N, Lv, H, W, _ = maps.shape
+    if min(N, Lv, H, W) < 1 or W % 2:
+        raise ValueError(f"expected non-empty maps of even width, got {tuple(maps.shape)}")
+    dirs = _f32c(dirs)
+    if dirs.dim() == 2 and dirs.shape[1] == 3:
+        P, dn = dirs.shape[0], 0
+    elif dirs.dim() == 3 and dirs.shape[0] == N and dirs.shape[2] == 3:
+        P = dirs.shape[1]
+        dn = 3 * P
+    else:
+        raise ValueError(f"dirs must be [P, 3] or [{N}, P, 3], got {tuple(dirs.shape)}")
+    if P < 1:
+        raise ValueError("no directions")
+    dev = maps.device
+    lp, ln, lc = None, 0, 0.0
+    if isinstance(level, torch.Tensor) and level.dim() > 0:
+        level = _f32c(level)
+        if tuple(level.shape) == (P,):
+            ln = 0
+        elif tuple(level.shape) == (N, P):
+            ln = P
+        else:
+            raise ValueError(f"level must be a number, [P] or [N, P], got {tuple(level.shape)}")
+        if level.device != dev:
+            raise ValueError(f"level is on {level.device}, the maps on {dev}")
+        lp = level.data_ptr()
+    elif level is not None:
+        lc = float(level)
+    if dirs.device != dev:
+        raise ValueError(f"dirs are on {dirs.device}, the maps on {dev}")
+    out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
+    st = (ctypes.c_int64 * 5)(*maps.stride())
+    _call(_lib.load().reni_envmap_lookup, dev, N, Lv, H, W, P, maps.data_ptr(), st, dirs.data_ptr(), dn, lp, ln, lc,
+          out.data_ptr())
+    return out
 
 
 def unnormalise_srgb(img: torch.Tensor, minmax=None, srgb: bool = True, want_linear: bool = False):

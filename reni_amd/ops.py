@@ -741,7 +741,8 @@ def _convolve_args(src, in_dirs, in_weight, out_dirs):
 
 def diffuse_convolve(src, in_dirs, in_weight, out_dirs, scale: float) -> torch.Tensor:
     """reni_diffuse_convolve: out [N, P, 3] = scale sum_i max(0, out_dirs[o] . in_dirs[i]) in_weight[i] src[n, i, c].
-    src is [N, Q, 3] or channel-planar [N, 3, Q], read through its own strides (any float32 view of those shapes);
+    src is [N, Q, 3] or channel-planar [N, 3, Q], read through its own strides (any float32 view of those shapes; at
+    Q = 3 the two shapes coincide and src is taken as [N, Q, 3]);
     in_dirs [Q, 3], in_weight [Q], out_dirs [P, 3] are shared by the N maps."""
     _require_cuda(src, in_dirs, in_weight, out_dirs)
     src, in_dirs, in_weight, out_dirs, N, P, Q, sn, si, sc = _convolve_args(src, in_dirs, in_weight, out_dirs)

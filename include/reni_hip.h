@@ -595,7 +595,9 @@ int reni_rotate_envmap(int64_t B, int64_t C, int64_t H, int64_t W, const float* 
  *     [2] sum_i w_i sum_c |p - t|          [6] sum_i w_i sum_c t^2
  *     [3] sum_i w_i cos(p_i, t_i)          [7] sum_i w_i sum_c t
  *   cos is the RGB-vector cosine of F.cosine_similarity(dim = channel, eps = 1e-20).  Workgroups write fp32 partials to ws; a second
- *   kernel adds an image's partials in double in a fixed order and rounds once.
+ *   kernel adds an image's partials in double in a fixed order and rounds once.  A pixel of weight 0 is skipped, not multiplied by 0:
+ *   a NaN, an infinity or an overflowing exponential there changes no bit of any entry.  With no pixel of weight > 0 the six sums
+ *   are exactly 0, [4] is -inf and [5] is +inf.
  *
  * reni_ssim: the mean SSIM of Wang et al. 2004 per image, out[B]: an 11 x 11 Gaussian window, sigma 1.5, normalised (the host builds
  *   the 11 weights in float64 and rounds them once), C1 = (0.01 L)^2, C2 = (0.03 L)^2, per channel of the mapped images
@@ -607,6 +609,12 @@ int reni_rotate_envmap(int64_t B, int64_t C, int64_t H, int64_t W, const float* 
  *     RENI_SSIM_PLANAR  the published image definition: only the windows that lie inside the image, an (H - 10) x (W - 10) map,
  *                       unweighted mean.  weight must be NULL; H, W >= 11.
  *   map_out: NULL, or [B][H][W]: the channel-mean SSIM of every pixel (planar mode: zero on the border of 5).
+ *   A weight acts on the MEAN only; a window has no per-tap weight.  A pixel of weight 0 is left out of out[b], but its value is a
+ *   tap of the 11 x 11 window of every pixel around it (on the sphere by the tap rule above, across a pole and around the seam).
+ *   If that value is not finite once mapped (a NaN; an infinity in RENI_SPACE_STORED; +inf or an overflowing exponential in
+ *   RENI_SPACE_LINEAR -- exp(-inf) is 0, and the clamp of RENI_SPACE_SRGB turns an infinite radiance into 1), map_out is NaN on
+ *   exactly the pixels whose window holds it and unchanged everywhere else, and out[b] is unchanged once every pixel of that set has
+ *   weight 0; otherwise out[b] is NaN.  With no pixel of weight > 0, out[b] is 0 / 0 = NaN.
  *   One kernel holds a 32 x 32 tile plus halo of both mapped images in LDS and forms the moments separably; the values go straight
  *   into the workgroup's partial sum, no moment image is written to memory. */
 #define RENI_SPACE_STORED 0

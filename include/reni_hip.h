@@ -491,6 +491,52 @@ int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, c
                        const float* dirs, int64_t dirs_stride_n, const float* level, int64_t level_stride_n, float level_const,
                        float* out, void* stream);
 
+/* ---- glossy lighting, backward: the transposes of the two operators above (reni_tu_glossy_bwd.hip; the autograd functions of
+ * reni_amd/glossy.py).  Both operators are linear in the maps, so d loss / d map is their transpose applied to the upstream
+ * gradient; directions, weights, levels and lobe parameters are constants.  fp32, deterministic (no float atomics, fixed
+ * summation orders): two calls give identical bits and map n's gradient is the same alone or inside a batch.
+ * reni_lobe_denominators: den[l][o] = sum_i f_l(o . d_i) w_i, [n_lobes][P] -- the denominators reni_lobe_convolve divides by
+ *   when it normalises, bit for bit: the forward's own launch with no maps, only its column of ones (the split depends on
+ *   (P, Q) only, and a column's sums do not depend on the columns beside it).  Equal to the unnormalised convolution, scale 1,
+ *   of a map of ones.  ws: reni_lobe_denominators_workspace_bytes(P, Q, n_lobes) bytes, 256-byte aligned.
+ * reni_lobe_convolve_backward: for grad_out [N][n_lobes][P][3], the upstream gradient of the forward's out,
+ *       r[l][o]       = normalise ? (den[l][o] > 0 ? 1 / den[l][o] : 0) : scale
+ *       dsrc(n, i, c) = w_i sum_l sum_o f_l(o . d_i) r[l][o] grad_out[n][l][o][c]
+ *   written to grad_src[n grad_stride_n + i grad_stride_i + c grad_stride_c] (element strides >= 0; [N][Q][3] and planar
+ *   [N][3][Q] both work; every element is written).  The same GEMM as the forward with rows and reduction swapped: t is built
+ *   in the forward's fp32 order, the o range is split by the forward's rule with P and Q exchanged, the lobes of a kind are
+ *   summed inside one launch, and the (kind, split) partial sums are added in that order.  den [n_lobes][P] (device, from
+ *   the denominators entry above) is required iff normalise; scale is ignored when normalising.  The argument checks and
+ *   error codes are the forward's.  ws: reni_lobe_backward_workspace_bytes(N, P, Q, n_lobes) bytes, 256-byte aligned.
+ * reni_envmap_lookup_taps: for each direction the 8 texels the lookup reads -- 4 on floor(level), 4 on the next level, each
+ *   as the element index level H W + y W + x of a contiguous [Lv][H][W] map -- and their effective weights
+ *   {gr gc, gr fc, fr gc, fr fc} x {gl, fl} from the lookup's own coordinate chain (a copy).  The next level weighs 0 unless
+ *   fl > 0, as the forward reads it only then; a tap that is not used has weight 0 (and a valid index).  tap_index (int32) and
+ *   tap_weight are [n_tables][P][8]; n_tables is 1 when directions and level are shared (both strides 0) and N otherwise.
+ *   Lv H W < 2^31; the other limits are the lookup's.
+ * reni_envmap_lookup_backward: grad_src [N][Lv][H][W][3] (contiguous, ALL of it written: 0 where nobody sampled) from
+ *   grad_out [N][P][3], the tap weights, tap_order [n_tables][8 P] (int64: the taps' positions p 8 + k of a table in
+ *   ascending order of their element index, ties in ascending position -- a stable sort) and offsets [n_tables][Lv H W + 1]
+ *   (int64: element e owns tap_order[offsets[e] .. offsets[e + 1])).  One lane per (map, element) adds weight x upstream
+ *   over its range in that order, for the three channels: a gather, no atomics.  n_tables = 1 serves all N maps.  A texel
+ *   sampled by very many directions is summed by ONE lane: a known limit (a map's pole rows under a narrow field of view).
+ *   An order entry outside [0, 8 P) is skipped and a range is clipped to the table, so a malformed table cannot become an
+ *   address. */
+size_t reni_lobe_denominators_workspace_bytes(int64_t P, int64_t Q, int64_t n_lobes);
+int reni_lobe_denominators(int64_t P, int64_t Q, const float* out_dirs, const float* in_dirs, const float* in_w, int n_lobes,
+                           const int32_t* kinds, const float* params, float* den, void* ws, size_t ws_bytes, void* stream);
+size_t reni_lobe_backward_workspace_bytes(int64_t N, int64_t P, int64_t Q, int64_t n_lobes);
+int reni_lobe_convolve_backward(int64_t N, int64_t P, int64_t Q, const float* out_dirs, const float* in_dirs, const float* in_w,
+                                const float* grad_out, int n_lobes, const int32_t* kinds, const float* params, int normalise,
+                                float scale, const float* den, float* grad_src, int64_t grad_stride_n, int64_t grad_stride_i,
+                                int64_t grad_stride_c, void* ws, size_t ws_bytes, void* stream);
+int reni_envmap_lookup_taps(int64_t n_tables, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* dirs, int64_t dirs_stride_n,
+                            const float* level, int64_t level_stride_n, float level_const, int32_t* tap_index, float* tap_weight,
+                            void* stream);
+int reni_envmap_lookup_backward(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* grad_out, int64_t n_tables,
+                                const float* tap_weight, const int64_t* tap_order, const int64_t* offsets, float* grad_src,
+                                void* stream);
+
 /* ---- HDR image epilogue / prologue ------------------------------------------------
  * reni_unnormalise_srgb replaces, on the device and in one call, the reference's viewing chain
  *   UnMinMaxNormlise(minmax)   src/utils/custom_transforms.py:14-21   y = exp(0.5 (x + 1)(m1 - m0) + m0)

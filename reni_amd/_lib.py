@@ -39,6 +39,8 @@ EXPORTS = (
     "reni_sg_workspace_bytes", "reni_sg_render", "reni_sg_loss_grad", "reni_sh_project", "reni_sh_reconstruct",
     "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
     "reni_lobe_workspace_bytes", "reni_lobe_convolve", "reni_envmap_lookup",
+    "reni_lobe_denominators_workspace_bytes", "reni_lobe_denominators", "reni_lobe_backward_workspace_bytes",
+    "reni_lobe_convolve_backward", "reni_envmap_lookup_taps", "reni_envmap_lookup_backward",
     "reni_image_workspace_bytes", "reni_unnormalise_srgb", "reni_minmax_normalise",
     "reni_minmax_batch_workspace_bytes", "reni_minmax_normalise_batch",
     "reni_resample", "reni_blur_workspace_bytes", "reni_gaussian_blur", "reni_rotate_envmap",
@@ -210,6 +212,23 @@ def load():
     lib.reni_envmap_lookup.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p,
                                        c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p]
     lib.reni_envmap_lookup.restype = c_int32
+    lib.reni_lobe_denominators_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    lib.reni_lobe_denominators_workspace_bytes.restype = c_size_t
+    lib.reni_lobe_denominators.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_int32),
+                                           POINTER(c_float), c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_lobe_denominators.restype = c_int32
+    lib.reni_lobe_backward_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int64]
+    lib.reni_lobe_backward_workspace_bytes.restype = c_size_t
+    lib.reni_lobe_convolve_backward.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                                POINTER(c_int32), POINTER(c_float), c_int32, c_float, c_void_p, c_void_p,
+                                                c_int64, c_int64, c_int64, c_void_p, c_size_t, c_void_p]
+    lib.reni_lobe_convolve_backward.restype = c_int32
+    lib.reni_envmap_lookup_taps.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                            c_float, c_void_p, c_void_p, c_void_p]
+    lib.reni_envmap_lookup_taps.restype = c_int32
+    lib.reni_envmap_lookup_backward.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.reni_envmap_lookup_backward.restype = c_int32
     lib.reni_image_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
     lib.reni_image_workspace_bytes.restype = c_size_t
     lib.reni_unnormalise_srgb.argtypes = [c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_int32, ctypes.c_double,

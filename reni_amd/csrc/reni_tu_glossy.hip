@@ -16,6 +16,9 @@
 //   k_lobe_finish       out[n][l][o][c] = ((part_0 + part_1) + ...) of column 3 n + c, divided by the same sum of the
 //                       column of ones when normalising (0 where that sum is not positive).  The division sits here and
 //                       not behind the MFMAs: arithmetic on the accumulators makes hipcc copy them ahead of the drain pad.
+//   k_lobe_den_finish   den[l][o] = the same sum of the column of ones of a call WITHOUT maps (reni_lobe_denominators: the
+//                       forward's own launch, so the bits the forward divided by), for the transpose in
+//                       reni_tu_glossy_bwd.hip.
 //   k_envmap_lookup     out[n][p][c] = the bilinear sample of src[n][level][.][.][c] at direction dirs[p] (or dirs[n][p]),
 //                       mixed linearly between floor(level) and the next level.  The coordinate chain is k_rotate_envmap's
 //                       (reni_tu_rotate.hip) from s on, COPIED here so that unit's bits cannot move: one lane per direction
@@ -31,22 +34,9 @@
 
 #define DEV __device__ __forceinline__
 
+#include "reni_lobe.inc"  // tiles, lobe generators, drain, split rule: shared with the transpose (reni_tu_glossy_bwd.hip)
+
 namespace reni {
-
-typedef float lb_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int LB_OT = 2;     // 32-row output tiles per wave
-constexpr int LB_WAVES = 4;  // waves per workgroup, each its own output rows
-constexpr int LB_ROWS = 32 * LB_OT * LB_WAVES;
-constexpr int LB_MAX_LOBES = 16;
-
-DEV constexpr int lb_rowmap(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }  // 32x32 MFMA result row
-
-DEV void lb_mfma_drain() {  // wait out the last MFMA's write-back (18 states) before its result is read
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 15\n\ts_nop 3");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 struct LbArgs {
   int N, P, Q;
@@ -65,25 +55,6 @@ struct LbArgs {
   float par[LB_MAX_LOBES];  // PHONG: n; BLINN: s / 2; GGX: alpha^2
   float* ws;                // [S][Lv][ncol][P] partial sums
 };
-
-DEV float lb_clamp01(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, 1.f); }
-// b^p = exp2(p log2 b) on the hardware's v_log_f32 / v_exp_f32 (1 ulp each); b = 0: log2 = -inf, p > 0, exp2 = 0
-DEV float lb_pow(float b, float p) { return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(b)); }
-
-template <int KIND>
-DEV float lb_lobe(float t, float p);
-template <>
-DEV float lb_lobe<RENI_LOBE_PHONG>(float t, float p) { return lb_pow(lb_clamp01(t), p); }
-template <>
-DEV float lb_lobe<RENI_LOBE_BLINN>(float t, float p) { return lb_pow(lb_clamp01(fmaf(t, 0.5f, 0.5f)), p); }
-template <>
-DEV float lb_lobe<RENI_LOBE_GGX>(float t, float p) {
-  // m (a2 - 1) + 1 written as fma(m, a2, 1 - m): 1 - m is exact for m >= 1/2, where the sum cancels.  a2 / d^2 as
-  // ((a2 r) r) with r = 1 / d <= 1 / a2, so that no intermediate leaves the normal range for a2 >= 2^-60
-  const float m = lb_clamp01(fmaf(t, 0.5f, 0.5f));
-  const float r = __builtin_amdgcn_rcpf(fmaf(m, p, 1.f - m));
-  return ((p * r) * r) * lb_clamp01(t);
-}
 
 template <int KIND, int CT>
 __global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
@@ -212,6 +183,16 @@ __global__ void __launch_bounds__(256) k_lobe_finish(const float* __restrict__ w
   q[2] = v[2];
 }
 
+// one lane per (lobe, o): the partial sums of the column of ones of a call without maps, in split order
+__global__ void __launch_bounds__(256) k_lobe_den_finish(const float* __restrict__ ws, int Lv, int P, int S, float* __restrict__ den) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t slab = (int64_t)Lv * P;
+  if (e >= slab) return;
+  float x = ws[e];
+  for (int s = 1; s < S; ++s) x += ws[(int64_t)s * slab + e];
+  den[e] = x;
+}
+
 struct LkArgs {
   const float* src;  // element (n, level, y, x, c) at n sn + level sl + y sy + x sx + c sc
   int64_t sn, sl, sc;
@@ -287,26 +268,6 @@ namespace {
 
 using reni::hip_status;
 using reni::reni_set_error;
-constexpr int64_t LB_MAX_ELEMS = 0x3fffffff;
-constexpr int64_t LB_MIN_CHUNK = 2048;  // fewest i per split
-constexpr int64_t LB_TARGET_WGS = 256;  // workgroups per (column group, lobe) the split aims for (one per CU)
-
-bool lb_shape_ok(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
-  return N >= 1 && P >= 1 && Q >= 1 && Lv >= 1 && Lv <= reni::LB_MAX_LOBES && P <= LB_MAX_ELEMS / 3 && Q <= LB_MAX_ELEMS / 3 &&
-         N <= (LB_MAX_ELEMS / (3 * P) - 1) / Lv && (3 * N + 1 + 31) / 32 <= 65535;
-}
-
-// the i split: reni_diffuse_convolve's rule, a function of (P, Q) only -- not of N, and not of the lobes
-void lb_split(int64_t P, int64_t Q, int64_t& S, int64_t& chunk) {
-  const int64_t wgs = (P + reni::LB_ROWS - 1) / reni::LB_ROWS;
-  int64_t s = (LB_TARGET_WGS + wgs - 1) / wgs;
-  const int64_t smax = Q / LB_MIN_CHUNK > 1 ? Q / LB_MIN_CHUNK : 1;
-  if (s > smax) s = smax;
-  chunk = (Q + s - 1) / s;
-  chunk += chunk & 1;
-  S = (Q + chunk - 1) / chunk;
-}
-
 int64_t lb_ws_bytes(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
   int64_t S, chunk;
   lb_split(P, Q, S, chunk);
@@ -321,6 +282,30 @@ void lb_launch(const reni::LbArgs& a, hipStream_t s) {
   } else {
     hipLaunchKernelGGL((reni::k_lobe_convolve<KIND, 2>), dim3(gx, (unsigned)((a.ncol + 63) / 64), gz), dim3(256), 0, s, a);
   }
+}
+
+// one launch per kind present, its lobes along z
+int lb_launch_kinds(reni::LbArgs& a, int n_lobes, const int32_t* kinds, const float* params, hipStream_t s) {
+  for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind) {
+    a.nl = 0;
+    for (int l = 0; l < n_lobes; ++l) {
+      if (kinds[l] != kind) continue;
+      a.lobe[a.nl] = l;
+      a.par[a.nl] = lb_kernel_param(kind, params[l]);
+      ++a.nl;
+    }
+    if (!a.nl) continue;
+    if (kind == RENI_LOBE_PHONG) lb_launch<RENI_LOBE_PHONG>(a, s);
+    else if (kind == RENI_LOBE_BLINN) lb_launch<RENI_LOBE_BLINN>(a, s);
+    else lb_launch<RENI_LOBE_GGX>(a, s);
+    if (int rc = hip_status()) return rc;
+  }
+  return RENI_OK;
+}
+
+bool lb_den_shape_ok(int64_t P, int64_t Q, int64_t Lv) {
+  return P >= 1 && Q >= 1 && Lv >= 1 && Lv <= reni::LB_MAX_LOBES && P <= LB_MAX_ELEMS / 3 && Q <= LB_MAX_ELEMS / 3 &&
+         P <= LB_MAX_ELEMS / (3 * Lv);
 }
 
 }  // namespace
@@ -341,15 +326,7 @@ int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, c
     return reni_set_error(RENI_EINVAL, "lobe convolve: need N, P, Q >= 1 and n_lobes N P, Q < 2^28");
   if (!out_dirs || !in_dirs || !in_w || !src || !out || !kinds || !params)
     return reni_set_error(RENI_EINVAL, "lobe convolve: NULL argument");
-  for (int l = 0; l < n_lobes; ++l) {
-    const float p = params[l];
-    if (kinds[l] != RENI_LOBE_PHONG && kinds[l] != RENI_LOBE_BLINN && kinds[l] != RENI_LOBE_GGX)
-      return reni_set_error(RENI_EINVAL, "lobe convolve: unknown lobe kind");
-    if (!(p > 0.f) || !(p <= 3.0e38f))
-      return reni_set_error(RENI_EINVAL, "lobe convolve: a lobe's parameter must be positive and finite");
-    if (kinds[l] == RENI_LOBE_GGX && !(p <= 1.f && p >= 1e-9f))
-      return reni_set_error(RENI_EINVAL, "lobe convolve: GGX needs 1e-9 <= alpha <= 1");
-  }
+  if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
   if (src_stride_n < 0 || src_stride_i < 0 || src_stride_c < 0)
     return reni_set_error(RENI_EINVAL, "lobe convolve: src strides must be >= 0");
   const size_t need = (size_t)lb_ws_bytes(N, P, Q, n_lobes);
@@ -366,23 +343,53 @@ int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, c
   a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
   a.ws = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
-  for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind) {  // one launch per kind present, its lobes along z
-    a.nl = 0;
-    for (int l = 0; l < n_lobes; ++l) {
-      if (kinds[l] != kind) continue;
-      a.lobe[a.nl] = l;
-      a.par[a.nl] = kind == RENI_LOBE_BLINN ? 0.5f * params[l] : kind == RENI_LOBE_GGX ? params[l] * params[l] : params[l];
-      ++a.nl;
-    }
-    if (!a.nl) continue;
-    if (kind == RENI_LOBE_PHONG) lb_launch<RENI_LOBE_PHONG>(a, s);
-    else if (kind == RENI_LOBE_BLINN) lb_launch<RENI_LOBE_BLINN>(a, s);
-    else lb_launch<RENI_LOBE_GGX>(a, s);
-    if (int rc = hip_status()) return rc;
-  }
+  if (int rc = lb_launch_kinds(a, n_lobes, kinds, params, s)) return rc;
   const int64_t total = (int64_t)n_lobes * N * P;
   hipLaunchKernelGGL(reni::k_lobe_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)a.ws, (int)N,
                      n_lobes, (int)P, a.ncol, (int)S, normalise ? 1 : 0, out);
+  return hip_status();
+}
+
+size_t reni_lobe_denominators_workspace_bytes(int64_t P, int64_t Q, int64_t n_lobes) {
+  if (!lb_den_shape_ok(P, Q, n_lobes)) return 0;
+  int64_t S, chunk;
+  lb_split(P, Q, S, chunk);
+  return (size_t)(S * n_lobes * P * (int64_t)sizeof(float)) + 256;
+}
+
+int reni_lobe_denominators(int64_t P, int64_t Q, const float* out_dirs, const float* in_dirs, const float* in_w, int n_lobes,
+                           const int32_t* kinds, const float* params, float* den, void* ws, size_t ws_bytes, void* stream) {
+  if (n_lobes < 1 || n_lobes > reni::LB_MAX_LOBES) return reni_set_error(RENI_EINVAL, "lobe convolve: need 1 <= n_lobes <= 16");
+  if (!lb_den_shape_ok(P, Q, n_lobes))
+    return reni_set_error(RENI_EINVAL, "lobe denominators: need P, Q >= 1 and n_lobes P, Q < 2^28");
+  if (!out_dirs || !in_dirs || !in_w || !den || !kinds || !params)
+    return reni_set_error(RENI_EINVAL, "lobe denominators: NULL argument");
+  if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
+  int64_t S, chunk;
+  lb_split(P, Q, S, chunk);
+  const size_t need = (size_t)(S * n_lobes * P * (int64_t)sizeof(float));
+  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
+    return reni_set_error(RENI_EWORKSPACE, "lobe denominators: workspace missing, too small or not 256-byte aligned");
+  // the forward's own launch without maps: the column of ones is column 0 of one 32-column group, and a column's sums do not
+  // depend on the columns beside it.  The kernel loads a map's value in every lane and drops it where there is no map: in_w
+  // stands in for the maps it reads ([Q] floats, texel stride 1).
+  reni::LbArgs a = {};
+  a.N = 0; a.P = (int)P; a.Q = (int)Q;
+  a.ncol = 1;
+  a.out_dirs = out_dirs; a.in_dirs = in_dirs; a.in_w = in_w;
+  a.src = in_w; a.sn = 0; a.si = 1; a.sc = 0;
+  a.scale = 1.f;
+  a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
+  a.ws = (float*)ws;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = lb_launch_kinds(a, n_lobes, kinds, params, s)) return rc;
+  int present = 0;
+  for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind)
+    for (int l = 0; l < n_lobes; ++l)
+      if (kinds[l] == kind) { ++present; break; }
+  reni::note_launches(present + 1);
+  hipLaunchKernelGGL(reni::k_lobe_den_finish, dim3((unsigned)((n_lobes * P + 255) / 256)), dim3(256), 0, s, (const float*)a.ws,
+                     n_lobes, (int)P, (int)S, den);
   return hip_status();
 }
 

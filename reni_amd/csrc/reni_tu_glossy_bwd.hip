@@ -1,0 +1,428 @@
+// translation unit of libreni_hip.so: the transposes of glossy lighting's two linear operators (reni_tu_glossy.hip) -- what
+// d loss / d map needs behind a prefiltered render (reni_amd/glossy.py's autograd functions).
+//
+// fp32 throughout, no float atomics: every sum runs in a fixed order, so two calls give identical bits and a map's gradient
+// does not depend on the batch around it.  Contraction is off for the whole unit: what is written is what runs.
+//
+//   k_lobe_recip        r[l][o] = normalise ? (den[l][o] > 0 ? 1 / den[l][o] : 0) : scale -- what the forward multiplied
+//                       num[.][l][o][.] by, once per (lobe, o).
+//   k_lobe_convolve_t<KIND, CT>  part[s][col][i] = sum_(l of KIND) sum_(o in chunk s) f_l(o . d_i) r[l][o] g[o][col of lobe l]:
+//                       k_lobe_convolve with the roles swapped.  Rows are the Q texels (the same 32-row tiles, LB_OT a
+//                       wave, 4 waves), the reduction runs over o, two a step with lanes 32..63 feeding k = 1, and t is
+//                       built in the forward's order (ox dx, then two fma), so both directions use one kernel matrix up to
+//                       the lobe's rounding.  r sits where the forward has w_i, a per-k scalar.  The lobes of a kind are
+//                       looped INSIDE the workgroup into the same accumulators; the o range is split by the forward's rule
+//                       with P and Q exchanged.
+//   k_lobe_finish_t     dsrc(n, i, c) = w_i ((slab_0 + slab_1) + ...) of column 3 n + c over the (kind, split) slabs in that
+//                       order, written through element strides: every element is written.
+//   k_envmap_lookup_taps  per direction the 8 texels k_envmap_lookup reads (4 on floor(level), 4 on the next level) as
+//                       element indices level H W + y W + x, and their effective weights {gr gc, gr fc, fr gc, fr fc} x
+//                       {gl, fl}; the second level weighs 0 unless fl > 0, as the forward reads it only then.  The coordinate
+//                       chain is k_envmap_lookup's, COPIED here so that unit's bits cannot move.
+//   k_envmap_lookup_bwd one lane per (map, element): the sum of weight x upstream over the element's taps, in the order a
+//                       stable sort of the indices left them -- the scatter as a gather (as reni_mesh_vertex_normals does
+//                       with the faces of a vertex).  A texel sampled by very many directions is summed by ONE lane.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "reni_hip.h"
+#include "reni_internal.h"
+
+#pragma clang fp contract(off)
+
+#define DEV __device__ __forceinline__
+
+#include "reni_lobe.inc"
+
+namespace reni {
+
+struct LbtArgs {
+  int P, Q;
+  int ncol;               // 3 N
+  const float* out_dirs;  // [P][3]
+  const float* in_dirs;   // [Q][3]
+  const float* g;         // upstream [N][Lv][P][3]: element (o, col = 3 n + c) of lobe l at ((n Lv + l) P + o) 3 + c
+  const float* r;         // [Lv][P]
+  int chunk;  // o per split (even)
+  int S;      // splits
+  int Lv;     // lobes of the call
+  int nl;     // lobes of this launch (one kind)
+  int lobe[LB_MAX_LOBES];   // their index in the call
+  float par[LB_MAX_LOBES];  // PHONG: n; BLINN: s / 2; GGX: alpha^2
+  float* ws;                // this kind's slabs [S][ncol][Q]
+};
+
+__global__ void __launch_bounds__(256) k_lobe_recip(const float* __restrict__ den, int64_t total, float scale,
+                                                    float* __restrict__ r) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  float v = scale;
+  if (den) {  // (the largest finite number where 1 / den overflows: 0 f stays 0)
+    const float d = den[e];
+    v = d > 0.f ? fminf(1.f / d, 3.4028234664e38f) : 0.f;
+  }
+  r[e] = v;
+}
+
+// lb_mfma_drain with the accumulators tied to the pad: behind the loop over the lobes hipcc would otherwise copy them out of
+// the AGPRs ahead of it, one wait state short of the write-back on the path that leaves the loop
+template <int CT>
+DEV void lbt_mfma_drain(lb_f32x16 (&acc)[LB_OT][CT]) {
+  static_assert(LB_OT == 2 && (CT == 1 || CT == 2), "one operand per accumulator tile");
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (CT == 1) {
+    asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[0][0]), "+a"(acc[1][0]));
+  } else {
+    asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[1][0]), "+a"(acc[1][1]));
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+template <int KIND, int CT>
+__global__ void __launch_bounds__(256) k_lobe_convolve_t(const LbtArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hi = lane >> 5;
+  const int sp = (int)blockIdx.z;  // split
+  const int64_t i0 = (int64_t)blockIdx.x * LB_ROWS + wave * (32 * LB_OT);
+  float dx[LB_OT], dy[LB_OT], dz[LB_OT];
+#pragma unroll
+  for (int u = 0; u < LB_OT; ++u) {
+    const int64_t i = i0 + u * 32 + j;
+    const bool ok = i < a.Q;
+    dx[u] = ok ? a.in_dirs[3 * i] : 0.f;
+    dy[u] = ok ? a.in_dirs[3 * i + 1] : 0.f;
+    dz[u] = ok ? a.in_dirs[3 * i + 2] : 0.f;
+  }
+  const float* colp[CT];  // column (n, c) of lobe 0 at o = olo + hi
+  bool cok[CT];
+  const int olo = sp * a.chunk;
+  const int ohi = olo + a.chunk < a.P ? olo + a.chunk : a.P;
+#pragma unroll
+  for (int v = 0; v < CT; ++v) {
+    const int64_t col = (int64_t)blockIdx.y * (32 * CT) + v * 32 + j;
+    cok[v] = col < a.ncol;
+    const int64_t n = cok[v] ? col / 3 : 0;  // (every lane loads: column 0 beyond the last column, the value dropped)
+    const int64_t c = cok[v] ? col - 3 * n : 0;
+    colp[v] = a.g + (n * a.Lv * a.P + olo + hi) * 3 + c;
+  }
+  lb_f32x16 acc[LB_OT][CT];
+#pragma unroll
+  for (int u = 0; u < LB_OT; ++u)
+#pragma unroll
+    for (int v = 0; v < CT; ++v)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[u][v][r] = 0.f;
+  int ll = 0;
+  do {  // (nl >= 1: a loop that may run zero times makes hipcc merge the accumulators with their zeros ahead of the drain pad)
+    const float par = a.par[ll];
+    const int64_t lo = (int64_t)a.lobe[ll] * a.P;
+    // o = o0 + hi: lanes 0..31 feed k = 0 of the MFMA, lanes 32..63 k = 1
+    const float* dp = a.out_dirs + 3 * (int64_t)(olo + hi);
+    const float* rp = a.r + lo + olo + hi;
+    const float* bp[CT];
+#pragma unroll
+    for (int v = 0; v < CT; ++v) bp[v] = colp[v] + 3 * lo;
+    // one k-step; ook false zeroes both operands of the lanes of o == ohi (the tail of an odd range)
+    auto step = [&](const bool ook) __attribute__((always_inline)) {
+      const float ox = dp[0], oy = dp[1], oz = dp[2];
+      const float rv = ook ? rp[0] : 0.f;
+      float b[CT];
+#pragma unroll
+      for (int v = 0; v < CT; ++v) {
+        const float x = *bp[v];
+        b[v] = ook && cok[v] ? x : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < LB_OT; ++u) {
+        float t = ox * dx[u];
+        t = fmaf(oy, dy[u], t);
+        t = fmaf(oz, dz[u], t);
+        const float av = lb_lobe<KIND>(t, par) * rv;
+#pragma unroll
+        for (int v = 0; v < CT; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[v], acc[u][v], 0, 0, 0);
+      }
+    };
+    int o0 = olo;
+    for (; o0 + 1 < ohi; o0 += 2) {
+      step(true);
+      dp += 6;
+      rp += 2;
+#pragma unroll
+      for (int v = 0; v < CT; ++v) bp[v] += 6;
+    }
+    if (o0 < ohi) {  // odd range: the lanes of o0 + 1 re-read o0 and contribute zero
+      dp -= 3 * hi;
+      rp -= hi;
+#pragma unroll
+      for (int v = 0; v < CT; ++v) bp[v] -= 3 * hi;
+      step(hi == 0);
+    }
+  } while (++ll < a.nl);
+  lbt_mfma_drain<CT>(acc);
+  float* dst = a.ws + (int64_t)sp * a.ncol * a.Q;
+#pragma unroll
+  for (int v = 0; v < CT; ++v) {
+    if (!cok[v]) continue;
+    const int64_t col = (int64_t)blockIdx.y * (32 * CT) + v * 32 + j;
+    float* op = dst + col * a.Q;
+#pragma unroll
+    for (int u = 0; u < LB_OT; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t i = i0 + u * 32 + lb_rowmap(r, hi);
+        if (i < a.Q) op[i] = acc[u][v][r];
+      }
+  }
+}
+
+// one lane per (map, i): the slabs of its three columns in (kind, split) order, then the texel's weight
+__global__ void __launch_bounds__(256) k_lobe_finish_t(const float* __restrict__ ws, const float* __restrict__ in_w, int N, int Q,
+                                                       int slabs, float* __restrict__ dsrc, int64_t sn, int64_t si, int64_t sc) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)N * Q) return;
+  const int64_t i = e % Q, n = e / Q;
+  const int64_t slab = 3 * (int64_t)N * Q;
+  const float w = in_w[i];
+  float* q = dsrc + n * sn + i * si;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* p = ws + (3 * n + c) * Q + i;
+    float x = p[0];
+    for (int s = 1; s < slabs; ++s) x += p[(int64_t)s * slab];
+    q[c * sc] = w * x;
+  }
+}
+
+struct LtArgs {
+  const float* dirs;  // direction p of table t at dirs + t dn + 3 p
+  int64_t dn;
+  const float* level;  // NULL: level_const for every direction; else level[t ln + p]
+  int64_t ln;
+  float level_const;
+  int32_t* idx;  // [T][P][8]
+  float* wgt;    // [T][P][8]
+  int Lv, H, W, P;
+  float row_scale, col_scale, col_bias;  // fp32(H / pi), fp32(W / 2 pi), W/2 - 1/2
+};
+
+__global__ void __launch_bounds__(256) k_envmap_lookup_taps(const LtArgs a) {
+  const int p = (int)blockIdx.x * 256 + (int)threadIdx.x;  // P < 2^28
+  if (p >= a.P) return;
+  const int64_t n = blockIdx.y;
+  const float* d = a.dirs + n * a.dn + 3 * (int64_t)p;
+  const float sx = d[0], sy = d[1], sz = d[2];
+  // ---- k_envmap_lookup's chain (a copy: see the header)
+  const float phi = atan2f(sqrtf(fmaf(sz, sz, sx * sx)), sy);
+  const float theta = atan2f(sx, -sz);
+  const float row = fminf(fmaxf(fmaf(phi, a.row_scale, -0.5f), -1.f), (float)a.H);
+  const float col = fminf(fmaxf(fmaf(theta, a.col_scale, a.col_bias), -1.f), (float)a.W);
+  const float fi = floorf(row), fj = floorf(col);
+  const int i = (int)fi, j = (int)fj;
+  const float fr = row - fi, fc = col - fj;
+  const float gr = 1.f - fr, gc = 1.f - fc;
+  const int half = a.W >> 1;
+  int i0 = i, i1 = i + 1;
+  const bool x0 = i0 < 0 || i0 >= a.H, x1 = i1 >= a.H;  // beyond a pole: the far side
+  if (i0 < 0) i0 = -1 - i0;
+  if (i0 >= a.H) i0 = 2 * a.H - 1 - i0;
+  if (i1 >= a.H) i1 = 2 * a.H - 1 - i1;
+  i0 = min(max(i0, 0), a.H - 1);
+  i1 = min(max(i1, 0), a.H - 1);
+  int j0 = j < 0 ? j + a.W : (j >= a.W ? j - a.W : j);
+  int j1 = j + 1 >= a.W ? j + 1 - a.W : j + 1;
+  if (j1 >= a.W) j1 -= a.W;
+  const int j0f = j0 + half >= a.W ? j0 - half : j0 + half, j1f = j1 + half >= a.W ? j1 - half : j1 + half;
+  const int r0 = i0 * a.W, r1 = i1 * a.W;
+  const int c00 = x0 ? j0f : j0, c01 = x0 ? j1f : j1, c10 = x1 ? j0f : j0, c11 = x1 ? j1f : j1;
+  const int e4[4] = {r0 + c00, r0 + c01, r1 + c10, r1 + c11};
+  const float w4[4] = {gr * gc, gr * fc, fr * gc, fr * fc};
+  // ---- the level, as the forward: the next level is read, and so weighs, only when fl > 0
+  float lv = a.level ? a.level[n * a.ln + p] : a.level_const;
+  lv = fminf(fmaxf(lv, 0.f), (float)(a.Lv - 1));
+  const float fl0 = floorf(lv);
+  const int l0 = (int)fl0, l1 = min(l0 + 1, a.Lv - 1);
+  const float fl = lv - fl0, gl = 1.f - fl;
+  const bool two = fl > 0.f;
+  const int hw = a.H * a.W;
+  int32_t* ip = a.idx + (n * a.P + p) * 8;
+  float* wp = a.wgt + (n * a.P + p) * 8;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    ip[k] = l0 * hw + e4[k];
+    wp[k] = two ? w4[k] * gl : w4[k];
+    ip[4 + k] = l1 * hw + e4[k];
+    wp[4 + k] = two ? w4[k] * fl : 0.f;
+  }
+}
+
+// T == 1: one table serves every map
+__global__ void __launch_bounds__(256) k_envmap_lookup_bwd(const float* __restrict__ g, const float* __restrict__ wgt,
+                                                           const int64_t* __restrict__ order, const int64_t* __restrict__ offsets,
+                                                           int64_t E, int64_t P, int T, float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  const int64_t n = blockIdx.y, t = T == 1 ? 0 : n, taps = 8 * P;
+  const int64_t* off = offsets + t * (E + 1) + e;
+  int64_t k0 = off[0], k1 = off[1];
+  k0 = k0 < 0 ? 0 : k0;  // (a table that is not what ops builds must not become an address)
+  k1 = k1 > taps ? taps : k1;
+  const int64_t* ord = order + t * taps;
+  const float* w = wgt + t * taps;
+  const float* gn = g + n * P * 3;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  for (int64_t k = k0; k < k1; ++k) {
+    const int64_t tap = ord[k];
+    if ((uint64_t)tap >= (uint64_t)taps) continue;
+    const float wv = w[tap];
+    if (wv == 0.f) continue;
+    const float* gp = gn + (tap >> 3) * 3;
+    s0 += wv * gp[0];
+    s1 += wv * gp[1];
+    s2 += wv * gp[2];
+  }
+  float* q = out + (n * E + e) * 3;
+  q[0] = s0;
+  q[1] = s1;
+  q[2] = s2;
+}
+
+}  // namespace reni
+
+namespace {
+
+using reni::hip_status;
+using reni::reni_set_error;
+
+size_t lbt_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// r [Lv][P] (rounded up to 256 bytes), then 3 kinds x S slabs [3 N][Q]
+size_t lbt_ws_bytes(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
+  int64_t S, chunk;
+  lb_split(Q, P, S, chunk);
+  return lbt_align((size_t)(Lv * P) * sizeof(float)) + (size_t)(3 * S * 3 * N * Q) * sizeof(float);
+}
+
+template <int KIND>
+void lbt_launch(const reni::LbtArgs& a, hipStream_t s) {
+  const unsigned gx = (unsigned)((a.Q + reni::LB_ROWS - 1) / reni::LB_ROWS);
+  if (a.ncol <= 32) {
+    hipLaunchKernelGGL((reni::k_lobe_convolve_t<KIND, 1>), dim3(gx, 1, (unsigned)a.S), dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((reni::k_lobe_convolve_t<KIND, 2>), dim3(gx, (unsigned)((a.ncol + 63) / 64), (unsigned)a.S), dim3(256), 0,
+                       s, a);
+  }
+  reni::note_launches(1);
+}
+
+int lk_check_sizes(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, int64_t T) {
+  if (N < 1 || Lv < 1 || H < 1 || W < 1 || P < 1) return reni_set_error(RENI_EINVAL, "lookup backward: sizes must be >= 1");
+  if (W & 1) return reni_set_error(RENI_EINVAL, "lookup backward: W must be even");
+  if (N > 65535 || Lv > 65535 || H > 0x3fffffff / W || Lv > 0x7ffffffe / (H * W) || P > 0x3fffffff / 3 || N > 0x3fffffff / (3 * P))
+    return reni_set_error(RENI_EINVAL, "lookup backward: need N, Lv <= 65535, H W < 2^30, Lv H W < 2^31 and N P < 2^28");
+  if (T != 1 && T != N) return reni_set_error(RENI_EINVAL, "lookup backward: n_tables must be 1 (shared) or N (per map)");
+  return RENI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t reni_lobe_backward_workspace_bytes(int64_t N, int64_t P, int64_t Q, int64_t n_lobes) {
+  if (!lb_shape_ok(N, P, Q, n_lobes)) return 0;
+  return lbt_ws_bytes(N, P, Q, n_lobes) + 256;
+}
+
+int reni_lobe_convolve_backward(int64_t N, int64_t P, int64_t Q, const float* out_dirs, const float* in_dirs, const float* in_w,
+                                const float* grad_out, int n_lobes, const int32_t* kinds, const float* params, int normalise,
+                                float scale, const float* den, float* grad_src, int64_t grad_stride_n, int64_t grad_stride_i,
+                                int64_t grad_stride_c, void* ws, size_t ws_bytes, void* stream) {
+  if (n_lobes < 1 || n_lobes > reni::LB_MAX_LOBES) return reni_set_error(RENI_EINVAL, "lobe convolve: need 1 <= n_lobes <= 16");
+  if (!lb_shape_ok(N, P, Q, n_lobes))
+    return reni_set_error(RENI_EINVAL, "lobe convolve backward: need N, P, Q >= 1 and n_lobes N P, Q < 2^28");
+  if (!out_dirs || !in_dirs || !in_w || !grad_out || !grad_src || !kinds || !params)
+    return reni_set_error(RENI_EINVAL, "lobe convolve backward: NULL argument");
+  if (normalise && !den)
+    return reni_set_error(RENI_EINVAL, "lobe convolve backward: NULL den (the denominators are required when normalising)");
+  if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
+  if (grad_stride_n < 0 || grad_stride_i < 0 || grad_stride_c < 0)
+    return reni_set_error(RENI_EINVAL, "lobe convolve backward: grad_src strides must be >= 0");
+  const size_t need = lbt_ws_bytes(N, P, Q, n_lobes);
+  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
+    return reni_set_error(RENI_EWORKSPACE, "lobe convolve backward: workspace missing, too small or not 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  float* r = (float*)ws;
+  float* slabs = (float*)((char*)ws + lbt_align((size_t)(n_lobes * P) * sizeof(float)));
+  const int64_t rtotal = (int64_t)n_lobes * P;
+  hipLaunchKernelGGL(reni::k_lobe_recip, dim3((unsigned)((rtotal + 255) / 256)), dim3(256), 0, s, normalise ? den : nullptr, rtotal,
+                     scale, r);
+  reni::note_launches(1);
+  if (int rc = hip_status()) return rc;
+  reni::LbtArgs a = {};
+  a.P = (int)P; a.Q = (int)Q;
+  a.ncol = (int)(3 * N);
+  a.out_dirs = out_dirs; a.in_dirs = in_dirs;
+  a.g = grad_out; a.r = r;
+  int64_t S, chunk;
+  lb_split(Q, P, S, chunk);
+  a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
+  int nslab = 0;
+  for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind) {  // one launch per kind present, its lobes inside
+    a.nl = 0;
+    for (int l = 0; l < n_lobes; ++l) {
+      if (kinds[l] != kind) continue;
+      a.lobe[a.nl] = l;
+      a.par[a.nl] = lb_kernel_param(kind, params[l]);
+      ++a.nl;
+    }
+    if (!a.nl) continue;
+    a.ws = slabs + (int64_t)nslab * (3 * N) * Q;
+    if (kind == RENI_LOBE_PHONG) lbt_launch<RENI_LOBE_PHONG>(a, s);
+    else if (kind == RENI_LOBE_BLINN) lbt_launch<RENI_LOBE_BLINN>(a, s);
+    else lbt_launch<RENI_LOBE_GGX>(a, s);
+    if (int rc = hip_status()) return rc;
+    nslab += (int)S;
+  }
+  const int64_t total = N * Q;
+  hipLaunchKernelGGL(reni::k_lobe_finish_t, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)slabs, in_w, (int)N,
+                     (int)Q, nslab, grad_src, grad_stride_n, grad_stride_i, grad_stride_c);
+  reni::note_launches(1);
+  return hip_status();
+}
+
+int reni_envmap_lookup_taps(int64_t n_tables, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* dirs, int64_t dirs_stride_n,
+                            const float* level, int64_t level_stride_n, float level_const, int32_t* tap_index, float* tap_weight,
+                            void* stream) {
+  if (int rc = lk_check_sizes(n_tables, Lv, H, W, P, n_tables)) return rc;
+  if (!dirs || !tap_index || !tap_weight) return reni_set_error(RENI_EINVAL, "lookup taps: NULL argument");
+  if (dirs_stride_n != 0 && dirs_stride_n != 3 * P)
+    return reni_set_error(RENI_EINVAL, "lookup taps: dirs_stride_n must be 0 (shared) or 3 P (per map)");
+  if (level && level_stride_n != 0 && level_stride_n != P)
+    return reni_set_error(RENI_EINVAL, "lookup taps: level_stride_n must be 0 (shared) or P (per map)");
+  reni::LtArgs a = {};
+  a.dirs = dirs; a.dn = dirs_stride_n; a.level = level; a.ln = level ? level_stride_n : 0; a.level_const = level_const;
+  a.idx = tap_index; a.wgt = tap_weight;
+  a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
+  const double pi = 3.14159265358979323846;
+  a.row_scale = (float)((double)H / pi);
+  a.col_scale = (float)((double)W / (2.0 * pi));
+  a.col_bias = (float)(0.5 * (double)W - 0.5);
+  hipLaunchKernelGGL(reni::k_envmap_lookup_taps, dim3((unsigned)((P + 255) / 256), (unsigned)n_tables), dim3(256), 0,
+                     (hipStream_t)stream, a);
+  reni::note_launches(1);
+  return reni::hip_status();
+}
+
+int reni_envmap_lookup_backward(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* grad_out, int64_t n_tables,
+                                const float* tap_weight, const int64_t* tap_order, const int64_t* offsets, float* grad_src,
+                                void* stream) {
+  if (int rc = lk_check_sizes(N, Lv, H, W, P, n_tables)) return rc;
+  if (!grad_out || !grad_src) return reni_set_error(RENI_EINVAL, "lookup backward: NULL argument");
+  if (!tap_weight || !tap_order || !offsets) return reni_set_error(RENI_EINVAL, "lookup backward: NULL tap table, order or offsets");
+  const int64_t E = Lv * H * W;
+  hipLaunchKernelGGL(reni::k_envmap_lookup_bwd, dim3((unsigned)((E + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream,
+                     grad_out, tap_weight, tap_order, offsets, E, P, (int)n_tables, grad_src);
+  reni::note_launches(1);
+  return reni::hip_status();
+}
+
+}  // extern "C"

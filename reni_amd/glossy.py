@@ -72,14 +72,80 @@ def lobe_value(lobe: Lobe, t):
     raise ValueError(f"unknown lobe kind {lobe.kind!r}")
 
 
+def _constant(**tensors):
+    """Directions, weights and levels are constants of these operators, as mesh and camera are of the shader: one that asks for
+    a gradient gets an error, not silence."""
+    for name, t in tensors.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError(f"{name} requires grad, but glossy lighting is differentiable with respect to the maps only: "
+                             f"{name} is a constant here (detach it)")
+
+
+def _wants_grad(t) -> bool:
+    return torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad
+
+
+class _LobeConvolveFn(torch.autograd.Function):
+    """``ops.lobe_convolve`` with its transpose ``ops.lobe_convolve_backward`` behind it.  den: the cached denominators of
+    these operands, or None -- they are then computed in backward, and only there."""
+
+    @staticmethod
+    def forward(ctx, src, in_dirs, in_weight, out_dirs, kinds, params, normalise, scale, den):
+        ctx.save_for_backward(in_dirs, in_weight, out_dirs, *(() if den is None else (den,)))
+        ctx.consts = (kinds, params, bool(normalise), float(scale))
+        ctx.planar = not (src.shape[1] == in_dirs.shape[0] and src.shape[2] == 3)  # (ops._convolve_args' reading of src)
+        return ops.lobe_convolve(src, in_dirs, in_weight, out_dirs, kinds, params, normalise, scale)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        in_dirs, in_weight, out_dirs, *den = ctx.saved_tensors
+        kinds, params, normalise, scale = ctx.consts
+        g = ops.lobe_convolve_backward(grad_out, in_dirs, in_weight, out_dirs, kinds, params, normalise, scale,
+                                       den=den[0] if den else None, planar=ctx.planar)
+        return g, None, None, None, None, None, None, None, None
+
+
+class _LookupFn(torch.autograd.Function):
+    """``ops.envmap_lookup`` with its transpose ``ops.envmap_lookup_backward`` behind it; the tap table is built in backward."""
+
+    @staticmethod
+    def forward(ctx, maps, dirs, level):
+        ctx.save_for_backward(dirs, *((level,) if isinstance(level, torch.Tensor) else ()))
+        ctx.level = None if isinstance(level, torch.Tensor) else level
+        ctx.shape = tuple(maps.shape)
+        return ops.envmap_lookup(maps, dirs, level)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dirs, *level = ctx.saved_tensors
+        Lv, H, W = (1,) + ctx.shape[1:3] if len(ctx.shape) == 4 else ctx.shape[1:4]
+        g = ops.envmap_lookup_backward(grad_out, Lv, H, W, dirs, level[0] if level else ctx.level)
+        return g.view(ctx.shape), None, None
+
+
+def _lobe_convolve(src, in_dirs, in_weight, out_dirs, lobes, normalise, scale, den=None):
+    """den: None, or a function that returns the cached denominators (called only when src requires grad)"""
+    lobes = _lobes(lobes)
+    kinds, params = [l.kind for l in lobes], [l.param for l in lobes]
+    _constant(in_dirs=in_dirs, in_weight=in_weight, out_dirs=out_dirs)
+    if not _wants_grad(src):
+        return ops.lobe_convolve(src, in_dirs, in_weight, out_dirs, kinds, params, normalise, scale)
+    ops._require_cuda(src, in_dirs, in_weight, out_dirs)
+    if src.dtype != torch.float32:
+        src = src.float()
+    return _LobeConvolveFn.apply(src, in_dirs, in_weight, out_dirs, kinds, params, normalise, scale,
+                                 den() if den is not None and normalise else None)
+
+
 def lobe_convolve(src, in_dirs, in_weight, out_dirs, lobes, normalise: bool = True, scale: float = 1.0) -> torch.Tensor:
     """out[n, l, o, c] = sum_i f_l(out_dirs[o] . in_dirs[i]) in_weight[i] src[n, i, c], divided by sum_i f_l in_weight[i]
     when normalise (0 where no texel lies in the lobe), else times scale.  src [N, Q, 3] or planar [N, 3, Q] (any strides);
     in_dirs [Q, 3], in_weight [Q], out_dirs [P, 3] -> [N, Lv, P, 3] float32.  Deterministic: a map's bits do not depend on
-    the batch, a lobe's not on the other lobes of the call."""
-    lobes = _lobes(lobes)
-    return ops.lobe_convolve(src, in_dirs, in_weight, out_dirs, [l.kind for l in lobes], [l.param for l in lobes],
-                             normalise, scale)
+    the batch, a lobe's not on the other lobes of the call.
+
+    Differentiable with respect to src (the transposed convolution, ``ops.lobe_convolve_backward``; the denominators of a
+    normalised call are computed in backward).  Directions, weights and lobes are constants: one that requires grad raises."""
+    return _lobe_convolve(src, in_dirs, in_weight, out_dirs, lobes, normalise, scale)
 
 
 def _grid_width(envmaps):
@@ -96,7 +162,8 @@ def _grid_width(envmaps):
 def prefilter(envmaps: torch.Tensor, lobes, out_width=None) -> torch.Tensor:
     """The normalised convolution of maps on RENI's own grid (``utils.get_directions``, texels weighted by their exact band
     solid angles) with each lobe: envmaps [N, H W, 3] or [N, H, W, 3] on the GPU -> [N, Lv, Ho Wo, 3] or [N, Lv, Ho, Wo, 3]
-    at out_width (default: the input width).  A constant map stays that constant under every lobe."""
+    at out_width (default: the input width).  A constant map stays that constant under every lobe.  Differentiable with
+    respect to envmaps; the denominators the backward needs are cached with the grids, per (width, out_width, lobes)."""
     from .utils import get_directions
     W = _grid_width(envmaps)
     Wo = W if out_width is None else int(out_width)
@@ -106,15 +173,31 @@ def prefilter(envmaps: torch.Tensor, lobes, out_width=None) -> torch.Tensor:
     src = envmaps.reshape(envmaps.shape[0], -1, 3)
     dirs, w = _diffuse_device_tables(("reni", W), lambda: (get_directions(W)[0], reni_grid_weights(W)), envmaps.device)
     (odirs,) = _diffuse_device_tables(("reni_out", Wo), lambda: (get_directions(Wo)[0],), envmaps.device)
-    out = lobe_convolve(src, dirs, w, odirs, lobes, normalise=True)
+    lobes = _lobes(lobes)
+
+    def den():  # kept with the grids: a fit loop pays for the denominators once
+        return _diffuse_device_tables(("reni_den", W, Wo) + tuple(lobes), lambda: (ops.lobe_denominators(
+            dirs, w, odirs, [l.kind for l in lobes], [l.param for l in lobes]),), envmaps.device)[0]
+
+    out = _lobe_convolve(src, dirs, w, odirs, lobes, True, 1.0, den)
     return out.view(out.shape[0], out.shape[1], Wo // 2, Wo, 3) if envmaps.dim() == 4 else out
 
 
 def lookup(maps_or_chain: torch.Tensor, dirs: torch.Tensor, level=None) -> torch.Tensor:
     """Maps [N, H, W, 3] or chains [N, Lv, H, W, 3] on RENI's grid, sampled bilinearly on the sphere at dirs [P, 3] (shared)
     or [N, P, 3] (per map; no unit length needed, a zero vector gives a finite value) -> [N, P, 3].  level: None, a number, or
-    a float tensor [P] / [N, P], clamped to [0, Lv - 1]; the result mixes the two nearest levels linearly."""
-    return ops.envmap_lookup(maps_or_chain, dirs, level)
+    a float tensor [P] / [N, P], clamped to [0, Lv - 1]; the result mixes the two nearest levels linearly.
+
+    Differentiable with respect to the maps (``ops.envmap_lookup_backward``: a deterministic gather per texel, its table built
+    in backward).  dirs and level are constants: one that requires grad raises."""
+    _constant(dirs=dirs, level=level)
+    if not _wants_grad(maps_or_chain):
+        return ops.envmap_lookup(maps_or_chain, dirs, level)
+    ops._require_cuda(maps_or_chain, dirs)
+    maps = maps_or_chain if maps_or_chain.dtype == torch.float32 else maps_or_chain.float()
+    if maps.dim() not in (4, 5):
+        raise ValueError(f"maps must be [N, H, W, 3] or [N, Lv, H, W, 3], got {tuple(maps.shape)}")
+    return _LookupFn.apply(maps, dirs, level)
 
 
 # ------------------------------------------------------------------------------------------ SH domain
@@ -198,7 +281,10 @@ def shade_prefiltered(envmap, normals, positions, camera_center, shininess, kd, 
     What it is: the diffuse term is the shader's own sum up to the bilinear lookup on the out_width grid; the specular term
     uses the n = v = r approximation (the lobe around the mirrored direction as if the surface were seen along its normal),
     so it differs from the shader at grazing angles whatever out_width is.  It is cheaper than ``ops.envmap_shade`` only when
-    the chain is reused across views or meshes, or when out_width^2 / 2 is small against the number of pixels."""
+    the chain is reused across views or meshes, or when out_width^2 / 2 is small against the number of pixels.
+
+    Differentiable with respect to ``envmap.environment_map`` through ``lobe_convolve`` and ``lookup``: the backward costs
+    one transposed two-lobe convolution and two gathers, not pixels x texels."""
     from .envmap_shader import _shared_grid
     from .utils import get_directions
     Wo = int(out_width)
@@ -219,3 +305,48 @@ def shade_prefiltered(envmap, normals, positions, camera_center, shininess, kd, 
     diffuse = lookup(chain, n, 0.0)
     specular = lookup(chain, r, 1.0)
     return (float(kd) * diffuse + (blinn_phong_norm(s) * float(ks)) * specular) * mask
+
+
+class PrefilteredRenderer(torch.nn.Module):
+    """``renderer(envmap=..., **kwargs) -> (colors [B, S, S, 3], pixel_normals [B, S, S, 3])`` -- the call shape
+    ``RENI.set_renderer`` expects -- shading with ``shade_prefiltered`` instead of the per-pixel sum over texels, forward and
+    backward.  The first argument is a ``mesh.MeshRasterizer`` (then the call takes ``meshes_world``, ``R``, ``T`` as
+    ``mesh.HipMeshRenderer`` does, and the G-buffer is the rasteriser's cached one) or an ``envmap_shader.GBuffer``.
+
+    ks defaults to 1 - kd.  camera_center defaults to what ``HipMeshRenderer`` uses -- the rasteriser's camera asked WITHOUT
+    R and T, the reference's quirk -- or to the G-buffer's own; with kd = 1 the two renderers differ only by the lookup's
+    interpolation on the out_width grid."""
+
+    def __init__(self, rasterizer_or_gbuffer, kd: float, shininess: float = 500.0, out_width: int = 64, ks=None,
+                 camera_center=None):
+        super().__init__()
+        from .envmap_shader import GBuffer
+        self.gbuffer = rasterizer_or_gbuffer if isinstance(rasterizer_or_gbuffer, GBuffer) else None
+        self.rasterizer = None if self.gbuffer is not None else rasterizer_or_gbuffer
+        if self.gbuffer is None and not hasattr(self.rasterizer, "gbuffer"):
+            raise ValueError("PrefilteredRenderer needs a mesh.MeshRasterizer or an envmap_shader.GBuffer")
+        self.kd = float(kd)
+        self.ks = 1.0 - self.kd if ks is None else float(ks)
+        self.shininess = float(shininess)
+        self.out_width = int(out_width)
+        if self.out_width < 2 or self.out_width % 2:
+            raise ValueError(f"out_width must be even and >= 2, got {out_width}")
+        if camera_center is None:
+            camera_center = (self.gbuffer.camera_center if self.gbuffer is not None
+                             else self.rasterizer.cameras.get_camera_center())
+        self.camera_center = torch.as_tensor(camera_center, dtype=torch.float32).detach().reshape(-1)[:3].cpu()
+
+    def forward(self, meshes_world=None, R=None, T=None, envmap=None, **kwargs):
+        dev = envmap.environment_map.device
+        if self.gbuffer is not None:
+            g = self.gbuffer
+            if g.pixel_normals.device != dev and dev.type == "cuda":
+                g.to(dev)
+            nrm, pos, (Hr, Wr) = g.pixel_normals, g.pixel_positions, g.image_size
+        else:
+            _, nrm, pos = self.rasterizer.gbuffer(meshes_world, R, T)
+            Hr = Wr = self.rasterizer.raster_settings.image_size
+        B = envmap.environment_map.shape[0]
+        colors = shade_prefiltered(envmap, nrm, pos, self.camera_center, self.shininess, self.kd, self.ks, self.out_width)
+        normals = torch.nn.functional.normalize(nrm, p=2, dim=-1, eps=1e-6).reshape(1, Hr, Wr, 3).repeat(B, 1, 1, 1)
+        return colors.reshape(B, Hr, Wr, 3), normals

@@ -782,13 +782,8 @@ def _ws256(nbytes, device):
     return ws, ap, ws.numel() - (ap - p)
 
 
-def lobe_convolve(src, in_dirs, in_weight, out_dirs, kinds, params, normalise: bool = True, scale: float = 1.0) -> torch.Tensor:
-    """reni_lobe_convolve: out [N, Lv, P, 3] = the maps convolved with Lv zonal lobes f_l(out_dirs[o] . in_dirs[i]) weighted
-    by in_weight[i]; divided by sum_i f_l in_weight[i] when normalise (0 where that sum is not positive), else times scale.
-    kinds: Lv names of _lib.LOBE_KIND ("phong": tc^n, "blinn": m^(s/2), "ggx": tc a^2 / (m (a^2 - 1) + 1)^2 with
-    tc = clamp(t, 0, 1), m = clamp((1 + t) / 2, 0, 1)); params: their one parameter each (n, s, a).  src, in_dirs, in_weight,
-    out_dirs as in ``diffuse_convolve``."""
-    _require_cuda(src, in_dirs, in_weight, out_dirs)
+def _lobe_args(kinds, params):
+    """(Lv, kinds as int32[Lv], params as float[Lv]) of a call's lobes, checked"""
     kinds, params = list(kinds), [float(p) for p in params]
     Lv = len(kinds)
     if not 1 <= Lv <= 16 or len(params) != Lv:
@@ -796,16 +791,57 @@ def lobe_convolve(src, in_dirs, in_weight, out_dirs, kinds, params, normalise: b
     for k in kinds:
         if k not in _lib.LOBE_KIND:
             raise ValueError(f"lobe kind must be one of {tuple(_lib.LOBE_KIND)}, got {k!r}")
+    return Lv, (ctypes.c_int32 * Lv)(*[_lib.LOBE_KIND[k] for k in kinds]), (ctypes.c_float * Lv)(*params)
+
+
+def lobe_convolve(src, in_dirs, in_weight, out_dirs, kinds, params, normalise: bool = True, scale: float = 1.0) -> torch.Tensor:
+    """reni_lobe_convolve: out [N, Lv, P, 3] = the maps convolved with Lv zonal lobes f_l(out_dirs[o] . in_dirs[i]) weighted
+    by in_weight[i]; divided by sum_i f_l in_weight[i] when normalise (0 where that sum is not positive), else times scale.
+    kinds: Lv names of _lib.LOBE_KIND ("phong": tc^n, "blinn": m^(s/2), "ggx": tc a^2 / (m (a^2 - 1) + 1)^2 with
+    tc = clamp(t, 0, 1), m = clamp((1 + t) / 2, 0, 1)); params: their one parameter each (n, s, a).  src, in_dirs, in_weight,
+    out_dirs as in ``diffuse_convolve``."""
+    _require_cuda(src, in_dirs, in_weight, out_dirs)
+    Lv, ck, cp = _lobe_args(kinds, params)
     src, in_dirs, in_weight, out_dirs, N, P, Q, sn, si, sc = _convolve_args(src, in_dirs, in_weight, out_dirs)
     dev = src.device
     out = torch.empty(N, Lv, P, 3, dtype=torch.float32, device=dev)
     lib = _lib.load()
     ws, wp, wn = _ws256(int(lib.reni_lobe_workspace_bytes(N, P, Q, Lv)), dev)
-    ck = (ctypes.c_int32 * Lv)(*[_lib.LOBE_KIND[k] for k in kinds])
-    cp = (ctypes.c_float * Lv)(*params)
     _call(lib.reni_lobe_convolve, dev, N, P, Q, out_dirs.data_ptr(), in_dirs.data_ptr(), in_weight.data_ptr(), src.data_ptr(),
           sn, si, sc, Lv, ck, cp, 1 if normalise else 0, float(scale), out.data_ptr(), wp, wn)
     return out
+
+
+def _lookup_dirs_level(N, dirs, level, dev):
+    """The directions and the level of a lookup of N maps on dev, checked: (dirs float32 contiguous, P, the directions' map
+    stride, the level tensor or None, its pointer or None, its map stride, the constant level)."""
+    dirs = _f32c(dirs)
+    if dirs.dim() == 2 and dirs.shape[1] == 3:
+        P, dn = dirs.shape[0], 0
+    elif dirs.dim() == 3 and dirs.shape[0] == N and dirs.shape[2] == 3:
+        P = dirs.shape[1]
+        dn = 3 * P
+    else:
+        raise ValueError(f"dirs must be [P, 3] or [{N}, P, 3], got {tuple(dirs.shape)}")
+    if P < 1:
+        raise ValueError("no directions")
+    lp, ln, lc = None, 0, 0.0
+    if isinstance(level, torch.Tensor) and level.dim() > 0:
+        level = _f32c(level)
+        if tuple(level.shape) == (P,):
+            ln = 0
+        elif tuple(level.shape) == (N, P):
+            ln = P
+        else:
+            raise ValueError(f"level must be a number, [P] or [N, P], got {tuple(level.shape)}")
+        if level.device != dev:
+            raise ValueError(f"level is on {level.device}, the maps on {dev}")
+        lp = level.data_ptr()
+    elif level is not None:
+        lc = float(level)
+    if dirs.device != dev:
+        raise ValueError(f"dirs are on {dirs.device}, the maps on {dev}")
+    return dirs, P, dn, level if lp is not None else None, lp, ln, lc
 
 
 def envmap_lookup(maps, dirs, level=None) -> torch.Tensor:
@@ -823,37 +859,117 @@ def envmap_lookup(maps, dirs, level=None) -> torch.Tensor:
     N, Lv, H, W, _ = maps.shape
     if min(N, Lv, H, W) < 1 or W % 2:
         raise ValueError(f"expected non-empty maps of even width, got {tuple(maps.shape)}")
-    dirs = _f32c(dirs)
-    if dirs.dim() == 2 and dirs.shape[1] == 3:
-        P, dn = dirs.shape[0], 0
-    elif dirs.dim() == 3 and dirs.shape[0] == N and dirs.shape[2] == 3:
-        P = dirs.shape[1]
-        dn = 3 * P
-    else:
-        raise ValueError(f"dirs must be [P, 3] or [{N}, P, 3], got {tuple(dirs.shape)}")
-    if P < 1:
-        raise ValueError("no directions")
     dev = maps.device
-    lp, ln, lc = None, 0, 0.0
-    if isinstance(level, torch.Tensor) and level.dim() > 0:
-        level = _f32c(level)
-        if tuple(level.shape) == (P,):
-            ln = 0
-        elif tuple(level.shape) == (N, P):
-            ln = P
-        else:
-            raise ValueError(f"level must be a number, [P] or [N, P], got {tuple(level.shape)}")
-        if level.device != dev:
-            raise ValueError(f"level is on {level.device}, the maps on {dev}")
-        lp = level.data_ptr()
-    elif level is not None:
-        lc = float(level)
-    if dirs.device != dev:
-        raise ValueError(f"dirs are on {dirs.device}, the maps on {dev}")
+    dirs, P, dn, level, lp, ln, lc = _lookup_dirs_level(N, dirs, level, dev)
     out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
     st = (ctypes.c_int64 * 5)(*maps.stride())
     _call(_lib.load().reni_envmap_lookup, dev, N, Lv, H, W, P, maps.data_ptr(), st, dirs.data_ptr(), dn, lp, ln, lc,
           out.data_ptr())
+    return out
+
+
+def lobe_denominators(in_dirs, in_weight, out_dirs, kinds, params) -> torch.Tensor:
+    """reni_lobe_denominators: den [Lv, P] = sum_i f_l(out_dirs[o] . in_dirs[i]) in_weight[i], the denominators
+    ``lobe_convolve`` divides by when it normalises, bit for bit (the forward's own launch without maps)."""
+    _require_cuda(in_dirs, in_weight, out_dirs)
+    Lv, ck, cp = _lobe_args(kinds, params)
+    in_dirs, in_weight, out_dirs = _f32c(in_dirs), _f32c(in_weight), _f32c(out_dirs)
+    if in_dirs.dim() != 2 or in_dirs.shape[1] != 3 or out_dirs.dim() != 2 or out_dirs.shape[1] != 3:
+        raise ValueError("in_dirs and out_dirs must be [Q, 3] and [P, 3]")
+    Q, P = in_dirs.shape[0], out_dirs.shape[0]
+    if tuple(in_weight.shape) != (Q,):
+        raise ValueError(f"in_weight must be [Q] = [{Q}], got {tuple(in_weight.shape)}")
+    dev = in_dirs.device
+    den = torch.empty(Lv, P, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    ws, wp, wn = _ws256(int(lib.reni_lobe_denominators_workspace_bytes(P, Q, Lv)), dev)
+    _call(lib.reni_lobe_denominators, dev, P, Q, out_dirs.data_ptr(), in_dirs.data_ptr(), in_weight.data_ptr(), Lv, ck, cp,
+          den.data_ptr(), wp, wn)
+    return den
+
+
+def lobe_convolve_backward(grad_out, in_dirs, in_weight, out_dirs, kinds, params, normalise: bool = True, scale: float = 1.0,
+                           den=None, planar: bool = False) -> torch.Tensor:
+    """reni_lobe_convolve_backward: d loss / d src of ``lobe_convolve`` for the upstream grad_out [N, Lv, P, 3] -- the
+    transposed convolution, as [N, Q, 3] or, with planar, [N, 3, Q] (the same bits).  den: the [Lv, P] of
+    ``lobe_denominators`` for these operands (computed here when None and normalising; not needed otherwise)."""
+    _require_cuda(grad_out, in_dirs, in_weight, out_dirs, den)
+    Lv, ck, cp = _lobe_args(kinds, params)
+    in_dirs, in_weight, out_dirs, grad_out = _f32c(in_dirs), _f32c(in_weight), _f32c(out_dirs), _f32c(grad_out)
+    if in_dirs.dim() != 2 or in_dirs.shape[1] != 3 or out_dirs.dim() != 2 or out_dirs.shape[1] != 3:
+        raise ValueError("in_dirs and out_dirs must be [Q, 3] and [P, 3]")
+    Q, P = in_dirs.shape[0], out_dirs.shape[0]
+    if tuple(in_weight.shape) != (Q,):
+        raise ValueError(f"in_weight must be [Q] = [{Q}], got {tuple(in_weight.shape)}")
+    if grad_out.dim() != 4 or tuple(grad_out.shape[1:]) != (Lv, P, 3) or grad_out.shape[0] < 1:
+        raise ValueError(f"grad_out must be [N, {Lv}, {P}, 3], got {tuple(grad_out.shape)}")
+    N = grad_out.shape[0]
+    dev = grad_out.device
+    dp = None
+    if normalise:
+        den = lobe_denominators(in_dirs, in_weight, out_dirs, kinds, params) if den is None else _f32c(den)
+        if tuple(den.shape) != (Lv, P) or den.device != dev:
+            raise ValueError(f"den must be [{Lv}, {P}] on {dev}, got {tuple(den.shape)} on {den.device}")
+        dp = den.data_ptr()
+    out = torch.empty((N, 3, Q) if planar else (N, Q, 3), dtype=torch.float32, device=dev)
+    sn, si, sc = (3 * Q, 1, Q) if planar else (3 * Q, 3, 1)
+    lib = _lib.load()
+    ws, wp, wn = _ws256(int(lib.reni_lobe_backward_workspace_bytes(N, P, Q, Lv)), dev)
+    _call(lib.reni_lobe_convolve_backward, dev, N, P, Q, out_dirs.data_ptr(), in_dirs.data_ptr(), in_weight.data_ptr(),
+          grad_out.data_ptr(), Lv, ck, cp, 1 if normalise else 0, float(scale), dp, out.data_ptr(), sn, si, sc, wp, wn)
+    return out
+
+
+def envmap_lookup_table(N: int, Lv: int, H: int, W: int, dirs, level=None):
+    """What ``envmap_lookup_backward`` gathers through, for a lookup of N maps [Lv, H, W, 3] at dirs / level (as in
+    ``envmap_lookup``): (tap weights [T, P, 8], tap order [T, 8 P] int64, offsets [T, Lv H W + 1] int64) with T = 1 when
+    directions and level are shared by the maps, else N.  reni_envmap_lookup_taps writes the 8 texels and weights of every
+    direction; a stable sort of the texel indices and a searchsorted bin them per texel (as ``_vertex_face_csr`` does the
+    faces of a vertex).  It depends on the directions and the level only: a caller whose geometry is fixed may keep it."""
+    N, Lv, H, W = int(N), int(Lv), int(H), int(W)
+    if min(N, Lv, H, W) < 1 or W % 2 or Lv * H * W >= 2 ** 31:
+        raise ValueError(f"expected N, Lv, H, W >= 1, an even width and Lv H W < 2^31, got {(N, Lv, H, W)}")
+    _require_cuda(dirs, level if isinstance(level, torch.Tensor) and level.dim() > 0 else None)
+    dev = dirs.device
+    dirs, P, dn, level, lp, ln, lc = _lookup_dirs_level(N, dirs, level, dev)
+    T = 1 if dn == 0 and ln == 0 else N
+    idx = torch.empty(T, 8 * P, dtype=torch.int32, device=dev)
+    wgt = torch.empty(T, P, 8, dtype=torch.float32, device=dev)
+    _call(_lib.load().reni_envmap_lookup_taps, dev, T, Lv, H, W, P, dirs.data_ptr(), dn, lp, ln, lc, idx.data_ptr(),
+          wgt.data_ptr())
+    keys, order = torch.sort(idx, dim=1, stable=True)
+    bounds = torch.arange(Lv * H * W + 1, device=dev, dtype=torch.int32).expand(T, -1).contiguous()
+    offsets = torch.searchsorted(keys, bounds)
+    return wgt, order.contiguous(), offsets.contiguous()
+
+
+def envmap_lookup_backward(grad_out, Lv: int, H: int, W: int, dirs=None, level=None, table=None) -> torch.Tensor:
+    """reni_envmap_lookup_backward: d loss / d maps [N, Lv, H, W, 3] (contiguous; 0 where nobody sampled) of
+    ``envmap_lookup`` for the upstream grad_out [N, P, 3] -- the scatter of the lookup's 8 weights per direction, done as a
+    deterministic gather per texel.  table: ``envmap_lookup_table(N, Lv, H, W, dirs, level)`` (built here when None)."""
+    _require_cuda(grad_out, dirs)
+    grad_out = _f32c(grad_out)
+    if grad_out.dim() != 3 or grad_out.shape[2] != 3 or grad_out.shape[0] < 1 or grad_out.shape[1] < 1:
+        raise ValueError(f"grad_out must be [N, P, 3], got {tuple(grad_out.shape)}")
+    N, P, _ = grad_out.shape
+    Lv, H, W = int(Lv), int(H), int(W)
+    if table is None:
+        if dirs is None:
+            raise ValueError("need the lookup's dirs (and level), or its table")
+        table = envmap_lookup_table(N, Lv, H, W, dirs, level)
+    wgt, order, offsets = table
+    _require_cuda(wgt, order, offsets)
+    T = wgt.shape[0]
+    E = Lv * H * W
+    if (T not in (1, N) or tuple(wgt.shape) != (T, P, 8) or tuple(order.shape) != (T, 8 * P) or tuple(offsets.shape) != (T, E + 1)
+            or wgt.dtype != torch.float32 or order.dtype != torch.int64 or offsets.dtype != torch.int64):
+        raise ValueError(f"the table is not one of {N} maps [{Lv}, {H}, {W}, 3] looked up at {P} directions")
+    dev = grad_out.device
+    if wgt.device != dev or order.device != dev or offsets.device != dev:
+        raise ValueError(f"the table is not on {dev}")
+    out = torch.empty(N, Lv, H, W, 3, dtype=torch.float32, device=dev)
+    _call(_lib.load().reni_envmap_lookup_backward, dev, N, Lv, H, W, P, grad_out.data_ptr(), T, wgt.contiguous().data_ptr(),
+          order.contiguous().data_ptr(), offsets.contiguous().data_ptr(), out.data_ptr())
     return out
 
 

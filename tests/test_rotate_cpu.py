@@ -73,9 +73,10 @@ def fetch(img, i, j):
     """img [..., H, W] at integer taps i, j [h, w] of the sphere: a row beyond a pole is the same row seen from the other side"""
     H, W = img.shape[-2:]
     i, j = np.array(i), np.array(j)
-    lo, hi = i < 0, i >= H
-    j = np.where(lo | hi, j + W // 2, j)
-    i = np.where(lo, -1 - i, np.where(hi, 2 * H - 1 - i, i))
+    k = np.mod(i, 2 * H)  # (rows repeat with period 2 H: at H = 1 a tap two rows beyond a pole is back on the near side)
+    far = k >= H
+    j = np.where(far, j + W // 2, j)
+    i = np.where(far, 2 * H - 1 - k, k)
     return img[..., i, np.mod(j, W)]
 
 

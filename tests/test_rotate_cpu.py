@@ -145,27 +145,32 @@ def rotate_bound(img, R):
     return dr * Sr + dc * Sc + K_SUM * EPS32 * mag, keep
 
 
-def emulate_kernel_fp32(img, R):
-    """the kernel's chain with numpy's fp32 functions (each operation rounded to fp32; numpy's sqrt is correctly rounded and
-    its arctan2 within an ulp or so): what the derivation of rotate_bound is checked against without a GPU"""
+def _fma32(a, b, c):  # one rounding
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def emulate_coordinates_fp32(H, W, R):
+    """(row, col) [H, W] float32: the source coordinate as the kernel's chain computes it, with numpy's fp32 functions"""
     from reni_amd.rotation import grid_trig
     f = np.float32
-    img = np.asarray(img, f)
-    H, W = img.shape[-2:]
     rt, ct = (t.astype(f) for t in grid_trig(H, W))
     R = np.asarray(R, f)
     sp, cp, st, cth = rt[:, 0][:, None], rt[:, 1][:, None], ct[:, 0][None, :], ct[:, 1][None, :]
     dx, dy, dz = sp * st, cp * np.ones_like(st), -(sp * cth)
-
-    def fma(a, b, c):  # one rounding
-        return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(f)
-
-    s = [fma(R[2, k], dz, fma(R[1, k], dy, R[0, k] * dx)) for k in range(3)]
-    phi = np.arctan2(np.sqrt(fma(s[2], s[2], s[0] * s[0])), s[1])
+    s = [_fma32(R[2, k], dz, _fma32(R[1, k], dy, R[0, k] * dx)) for k in range(3)]
+    phi = np.arctan2(np.sqrt(_fma32(s[2], s[2], s[0] * s[0])), s[1])
     theta = np.arctan2(s[0], -s[2])
     assert phi.dtype == f and theta.dtype == f
-    row = fma(phi, f(H / np.pi), f(-0.5))
-    col = fma(theta, f(W / (2 * np.pi)), f(W / 2 - 0.5))
+    return _fma32(phi, f(H / np.pi), f(-0.5)), _fma32(theta, f(W / (2 * np.pi)), f(W / 2 - 0.5))
+
+
+def emulate_kernel_fp32(img, R):
+    """the kernel's chain with numpy's fp32 functions (each operation rounded to fp32; numpy's sqrt is correctly rounded and
+    its arctan2 within an ulp or so): what the derivation of rotate_bound is checked against without a GPU"""
+    f, fma = np.float32, _fma32
+    img = np.asarray(img, f)
+    H, W = img.shape[-2:]
+    row, col = emulate_coordinates_fp32(H, W, R)
     fi, fj = np.floor(row), np.floor(col)
     i, j = fi.astype(np.int64), fj.astype(np.int64)
     fr, fc = row - fi, col - fj

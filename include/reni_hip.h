@@ -400,6 +400,47 @@ int reni_rasterize_mesh(int64_t V, int64_t F, const float* verts, const int64_t*
                         float* zbuf, float* bary, float* dists, float* pixel_normals, float* pixel_positions, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- cast shadows: visibility masks of the mesh for the shader (reni_tu_visibility.hip, the MASKED shader instances) ----
+ * The shader above lets light pass through the mesh: M(p, j) knows the pixel's own normal and nothing else.  The lights are at
+ * infinity, so whether texel direction j reaches pixel p is a constant of (mesh, camera, directions), as the G-buffer is.
+ * Definition.  Pixel p has the origin o = pixel_positions[p] and its own face pix_to_face[p]; d is a unit direction; face f has
+ * the vertices v0, v1, v2 (a face with an index outside [0, V) is skipped, as in the rasteriser):
+ *     e1 = v1 - v0, e2 = v2 - v0, h = d x e2, a = e1 . h;          |a| <= 1e-12: miss
+ *     s = o - v0, u = (s . h) / a, q = s x e1, v = (d . q) / a, t = (e2 . q) / a
+ *     hit  <=>  f != own face  and  u >= 0  and  v >= 0  and  u + v <= 1  and  t > t_min
+ *   Two-sided, no culling (as the rasteriser).  Bit (p, j) is 1 ("visible") iff no face hits; a background pixel
+ *   (pix_to_face < 0) has every bit 0.  fp32; the pass is deterministic (an any-hit query: two calls give identical bits).
+ *   vis : uint32 [NB][NP][JW], JW = ceil(J / 32); bit j & 31 of word j >> 5; bits at j >= J are 0.  NB = 1 when the directions
+ *         are shared (dirs_batch_stride == 0), else NB = B.
+ * reni_mesh_visibility_prepare: the acceleration record of (verts [V][3], faces [F][3] int64) in the caller's buffer accel
+ *   (reni_mesh_visibility_accel_bytes(F) bytes, 16-byte aligned; 0 for an F outside [1, 2^30)): per slot k the face order[k]
+ *   (order [F] int64, a permutation that puts nearby faces next to each other, e.g. the argsort of the centroids' Morton codes;
+ *   NULL: the given order) as v0, e1, e2 and its id, and one bounding box per cluster of 64 consecutive slots, grown by 2^-10 of
+ *   its extent and position so that the fp32 slab test stays conservative.  The record is opaque and holds no pointer.
+ * reni_mesh_visibility: positions [NP][3], pix_to_face [NP] int64 (the rasteriser's), dirs [J][3] of image b at
+ *   dirs + b * dirs_batch_stride (floats; 0 = shared), 0 <= t_min finite (hits nearer than this are the surface itself).
+ *   flags: RENI_VIS_NO_CULL visits every cluster of every ray (no box test, no early exit): brute force, the same bits. */
+#define RENI_VIS_NO_CULL 1u
+size_t reni_mesh_visibility_accel_bytes(int64_t F);
+int reni_mesh_visibility_prepare(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int64_t* order,
+                                 void* accel, size_t accel_bytes, void* stream);
+int reni_mesh_visibility(int64_t B, int64_t NP, int64_t J, const float* positions, const int64_t* pix_to_face,
+                         const float* dirs, int64_t dirs_batch_stride, const void* accel, float t_min, uint32_t flags,
+                         uint32_t* vis, void* stream);
+/* The shader with a mask: colors[b,p] = sum_j vis(p,j) M(p,j) C[b,j], dC[b,j] = sum_p vis(p,j) M(p,j) dcolors[b,p]; every other
+ * argument, the workspace, the splits and the summation order are reni_envmap_shade's, so an all-ones mask gives its bits.
+ *   vis : [NB][NP][ceil(J/32)] as above, image b's at vis + b * vis_batch_stride (words; 0 = one mask for all images, required
+ *         when dirs_batch_stride == 0). */
+int reni_envmap_shade_masked(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                             float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                             const float* light_colors, float shininess, float kd, float ks, const uint32_t* vis,
+                             int64_t vis_batch_stride, float* colors, void* ws, size_t ws_bytes, void* stream);
+int reni_envmap_shade_masked_backward(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions,
+                                      float cam_x, float cam_y, float cam_z, const float* light_dirs,
+                                      int64_t dirs_batch_stride, const float* dcolors, float shininess, float kd, float ks,
+                                      const uint32_t* vis, int64_t vis_batch_stride, float* dlight_colors, void* ws,
+                                      size_t ws_bytes, void* stream);
+
 /* ---- environment-map baselines: spherical Gaussians and spherical harmonics ----------------------------------------
  * What RENI is compared against.  fp32, deterministic (no float atomics; fixed summation order: two calls give identical
  * bits, and map n's results are the same alone or inside a batch).

@@ -25,6 +25,7 @@ ROTATE_MODE = {"nearest": 0, "bilinear": 1}
 LOBE_KIND = {"phong": 0, "blinn": 1, "ggx": 2}  # RENI_LOBE_*
 SPACE = {"stored": 0, "linear": 1, "srgb": 2}
 SSIM_MODE = {"sphere": 0, "planar": 1}
+VIS_NO_CULL = 1  # RENI_VIS_NO_CULL
 
 # every symbol include/reni_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -36,6 +37,8 @@ EXPORTS = (
     "reni_film_model_backward",
     "reni_envmap_shade_workspace_bytes", "reni_envmap_shade", "reni_envmap_shade_backward",
     "reni_raster_workspace_bytes", "reni_mesh_vertex_normals", "reni_rasterize_mesh",
+    "reni_mesh_visibility_accel_bytes", "reni_mesh_visibility_prepare", "reni_mesh_visibility",
+    "reni_envmap_shade_masked", "reni_envmap_shade_masked_backward",
     "reni_sg_workspace_bytes", "reni_sg_render", "reni_sg_loss_grad", "reni_sh_project", "reni_sh_reconstruct",
     "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
     "reni_lobe_workspace_bytes", "reni_lobe_convolve", "reni_envmap_lookup",
@@ -184,6 +187,17 @@ def load():
                                         c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_void_p]
     lib.reni_rasterize_mesh.restype = c_int32
+    lib.reni_mesh_visibility_accel_bytes.argtypes = [c_int64]
+    lib.reni_mesh_visibility_accel_bytes.restype = c_size_t
+    lib.reni_mesh_visibility_prepare.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_mesh_visibility_prepare.restype = c_int32
+    lib.reni_mesh_visibility.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_float,
+                                         c_uint32, c_void_p, c_void_p]
+    lib.reni_mesh_visibility.restype = c_int32
+    for fn in (lib.reni_envmap_shade_masked, lib.reni_envmap_shade_masked_backward):  # the shader's list + vis, vis_batch_stride
+        fn.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int64,
+                       c_void_p, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
+        fn.restype = c_int32
     lib.reni_sg_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int64]
     lib.reni_sg_workspace_bytes.restype = c_size_t
     lib.reni_sg_render.argtypes = [c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,

@@ -36,6 +36,8 @@ struct ShadeArgs {
   float shin, kd, ksn;     // ksn = ks * (s + 2) / (4 (2 - exp(-s / 2)))     (:112-114)
   int B, NP, J, b0, nb;    // images b0 .. b0 + nb - 1 are handled by this launch (nb <= BC)
   int per_split;           // elements of the other axis per blockIdx.y
+  const uint32_t* vis;     // MASKED: [NP][JW] visibility bits of the chunk's first image (bit j & 31 of word j >> 5)
+  int JW;                  // words per pixel, ceil(J / 32)
 };
 
 DEV void normalize3(float (&v)[3]) {  // F.normalize(p=2, eps=1e-6): v / max(|v|, eps)      (:82,:93,:107)
@@ -56,12 +58,17 @@ DEV float shade_coeff(const float (&N)[3], const float (&V)[3], const float (&L)
 
 constexpr int SH_TILE = 128;  // elements of the other axis per LDS stage
 
-// OWN_PIXEL: a thread owns pixel p and sums over texels j (forward); else it owns texel j and sums over pixels
-template <bool OWN_PIXEL, int BC>
+// OWN_PIXEL: a thread owns pixel p and sums over texels j (forward); else it owns texel j and sums over pixels.
+// MASKED: M(p, j) counts only where bit (p, j) of a.vis is set (cast shadows, reni_tu_visibility.hip) -- a select on the
+// coefficient, so the sums keep their order and an all-ones mask gives the unmasked instance's bits.  Forward: the pixel's
+// four words of a 128-texel stage are one 16-byte load (four guarded loads when JW is no multiple of 4: the rows are then
+// not 16-byte aligned).  Backward: the stage's 128 pixels x the workgroup's 8 words (its 256 texels) go through LDS.
+template <bool OWN_PIXEL, int BC, bool MASKED = false>
 __global__ void __launch_bounds__(256) k_envmap_shade(const ShadeArgs a) {
   __shared__ float4 g0[SH_TILE];       // other axis geometry: texel (Lx, Ly, Lz, -) | pixel (Nx, Ny, Nz, Vx)
   __shared__ float4 g1[SH_TILE];       //                                            | pixel (Vy, Vz, -, -)
   __shared__ float4 sv[SH_TILE][(3 * BC + 3) / 4];  // source rows of the BC images
+  __shared__ uint32_t mw[MASKED && !OWN_PIXEL ? SH_TILE : 1][8];  // backward: mask words of the stage's pixels
   const int tid = threadIdx.x;
   const int n_own = OWN_PIXEL ? a.NP : a.J, n_oth = OWN_PIXEL ? a.J : a.NP;
   const int o = blockIdx.x * 256 + tid;
@@ -111,8 +118,53 @@ __global__ void __launch_bounds__(256) k_envmap_shade(const ShadeArgs a) {
         svf[e * ROW + r] = x;
       }
     }
+    if constexpr (MASKED && !OWN_PIXEL) {
+      for (int i = tid; i < SH_TILE * 8; i += 256) {
+        const int e = i >> 3, w = blockIdx.x * 8 + (i & 7), t = t0 + e;
+        mw[e][i & 7] = (t < t_end && w < a.JW) ? a.vis[(size_t)t * a.JW + w] : 0u;
+      }
+    }
     __syncthreads();
     const int cnt = min(SH_TILE, t_end - t0);
+    if constexpr (MASKED) {
+      uint32_t wv[4] = {0u, 0u, 0u, 0u};
+      if (OWN_PIXEL && live) {  // (t0 is a multiple of SH_TILE: per_split is)
+        const uint32_t* row = a.vis + (size_t)o * a.JW;
+        const int w0 = t0 >> 5;
+        if ((a.JW & 3) == 0) {
+          const uint4 q = *(const uint4*)(row + w0);
+          wv[0] = q.x; wv[1] = q.y; wv[2] = q.z; wv[3] = q.w;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) wv[k] = w0 + k < a.JW ? row[w0 + k] : 0u;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {  // the same ascending walk as below, 32 elements per mask word
+        const int e_end = min(cnt, 32 * k + 32);
+        for (int e = 32 * k; e < e_end; ++e) {
+          const float4 q0 = g0[e];
+          float m;
+          bool on;
+          if (OWN_PIXEL) {
+            const float Lo[3] = {q0.x, q0.y, q0.z};
+            m = shade_coeff(N, V, Lo, a.shin, a.kd, a.ksn);
+            on = (wv[k] >> (e & 31)) & 1u;
+          } else {
+            const float4 q1 = g1[e];
+            const float No[3] = {q0.x, q0.y, q0.z}, Vo[3] = {q0.w, q1.x, q1.y};
+            m = shade_coeff(No, Vo, L, a.shin, a.kd, a.ksn);
+            on = (mw[e][tid >> 5] >> (tid & 31)) & 1u;
+          }
+          m = on ? m : 0.f;
+          const float* s = (const float*)sv[e];
+#pragma unroll
+          for (int b = 0; b < BC; ++b) {
+            acc[b][0] += m * s[3 * b]; acc[b][1] += m * s[3 * b + 1]; acc[b][2] += m * s[3 * b + 2];
+          }
+        }
+      }
+    } else
     for (int e = 0; e < cnt; ++e) {
       const float4 q0 = g0[e];
       float m;
@@ -170,12 +222,20 @@ int n_splits(int64_t n_own, int64_t n_oth) {  // enough workgroups for 256 CUs, 
 
 int shade_common(bool forward, int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions,
                  float cx, float cy, float cz, const float* light_dirs, int64_t dirs_bstride, const float* src,
-                 float shininess, float kd, float ks, float* out, void* ws, size_t ws_bytes, void* stream) {
+                 float shininess, float kd, float ks, float* out, void* ws, size_t ws_bytes, void* stream,
+                 bool masked = false, const uint32_t* vis = nullptr, int64_t vis_bstride = 0) {
   if (B < 1 || NP < 1 || J < 1) return reni_set_error(RENI_EINVAL, "envmap shade: B, NP and J must be >= 1");
   if (NP > 0x3fffffff || J > 0x3fffffff || B > 0xffff) return reni_set_error(RENI_EINVAL, "envmap shade: problem too large");
   if (!normals || !positions || !light_dirs || !src || !out) return reni_set_error(RENI_EINVAL, "envmap shade: NULL argument");
   if (dirs_bstride != 0 && dirs_bstride < J * 3) return reni_set_error(RENI_EINVAL, "envmap shade: direction batch stride must be 0 or >= 3 J");
   if (!(shininess > 0.f)) return reni_set_error(RENI_EINVAL, "envmap shade: shininess must be positive");
+  const int64_t JW = (J + 31) / 32;
+  if (masked) {
+    if (!vis || ((uintptr_t)vis & 15) != 0) return reni_set_error(RENI_EINVAL, "envmap shade: the mask must be non-NULL and 16-byte aligned");
+    // (rows of JW % 4 == 0 words are read 16 bytes at a time: every image's mask must then start on such a boundary)
+    if (vis_bstride != 0 && (dirs_bstride == 0 || vis_bstride < NP * JW || ((JW & 3) == 0 && (vis_bstride & 3) != 0)))
+      return reni_set_error(RENI_EINVAL, "envmap shade: mask batch stride must be 0 (required with shared directions) or >= NP ceil(J/32) words");
+  }
   const int64_t n_own = forward ? NP : J, n_oth = forward ? J : NP;
   const int S = n_splits(n_own, n_oth);
   const size_t need = S > 1 ? (size_t)S * B * n_own * 3 * sizeof(float) : 0;
@@ -190,13 +250,23 @@ int shade_common(bool forward, int64_t B, int64_t NP, int64_t J, const float* no
   a.B = (int)B; a.NP = (int)NP; a.J = (int)J;
   const int64_t tiles = (n_oth + reni::SH_TILE - 1) / reni::SH_TILE;
   a.per_split = (int)((tiles + S - 1) / S) * reni::SH_TILE;
+  a.vis = nullptr; a.JW = (int)JW;
   const dim3 grid((unsigned)((n_own + 255) / 256), (unsigned)S);
   // images that share their texel directions share M: chunks of SHADE_BC; otherwise one image per launch
   const int step = dirs_bstride == 0 ? SHADE_BC : 1;
   for (int64_t b0 = 0; b0 < B; b0 += step) {
     a.b0 = (int)b0; a.nb = (int)((B - b0) < step ? (B - b0) : step);
     a.ldir = light_dirs + (size_t)b0 * dirs_bstride;
-    if (step == 1) {
+    if (masked) {
+      a.vis = vis + (size_t)b0 * vis_bstride;
+      if (step == 1) {
+        if (forward) hipLaunchKernelGGL((reni::k_envmap_shade<true, 1, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((reni::k_envmap_shade<false, 1, true>), grid, dim3(256), 0, s, a);
+      } else {
+        if (forward) hipLaunchKernelGGL((reni::k_envmap_shade<true, SHADE_BC, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((reni::k_envmap_shade<false, SHADE_BC, true>), grid, dim3(256), 0, s, a);
+      }
+    } else if (step == 1) {
       if (forward) hipLaunchKernelGGL((reni::k_envmap_shade<true, 1>), grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL((reni::k_envmap_shade<false, 1>), grid, dim3(256), 0, s, a);
     } else {
@@ -238,6 +308,23 @@ int reni_envmap_shade_backward(int64_t B, int64_t NP, int64_t J, const float* no
                                size_t ws_bytes, void* stream) {
   return shade_common(false, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, dcolors,
                       shininess, kd, ks, dlight_colors, ws, ws_bytes, stream);
+}
+
+int reni_envmap_shade_masked(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                             float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                             const float* light_colors, float shininess, float kd, float ks, const uint32_t* vis,
+                             int64_t vis_batch_stride, float* colors, void* ws, size_t ws_bytes, void* stream) {
+  return shade_common(true, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, light_colors,
+                      shininess, kd, ks, colors, ws, ws_bytes, stream, true, vis, vis_batch_stride);
+}
+
+int reni_envmap_shade_masked_backward(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions,
+                                      float cam_x, float cam_y, float cam_z, const float* light_dirs,
+                                      int64_t dirs_batch_stride, const float* dcolors, float shininess, float kd, float ks,
+                                      const uint32_t* vis, int64_t vis_batch_stride, float* dlight_colors, void* ws,
+                                      size_t ws_bytes, void* stream) {
+  return shade_common(false, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, dcolors,
+                      shininess, kd, ks, dlight_colors, ws, ws_bytes, stream, true, vis, vis_batch_stride);
 }
 
 }  // extern "C"

@@ -49,16 +49,27 @@ def interpolate_face_attributes(pix_to_face: torch.Tensor, bary_coords: torch.Te
 
 class _ShadeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, light_colors, normals, positions, camera_center, light_dirs, shininess, kd, ks):
+    def forward(ctx, light_colors, normals, positions, camera_center, light_dirs, shininess, kd, ks, vis=None):
         ctx.save_for_backward(normals, positions, camera_center, light_dirs)
         ctx.consts = (float(shininess), float(kd), float(ks))
-        return ops.envmap_shade(normals, positions, camera_center, light_dirs, light_colors, *ctx.consts)
+        ctx.vis = vis  # a constant of (mesh, camera, directions): see _constant_mask
+        return ops.envmap_shade(normals, positions, camera_center, light_dirs, light_colors, *ctx.consts, vis=vis)
 
     @staticmethod
     def backward(ctx, dcolors):
         normals, positions, camera_center, light_dirs = ctx.saved_tensors
-        g = ops.envmap_shade_backward(normals, positions, camera_center, light_dirs, dcolors.contiguous(), *ctx.consts)
-        return g, None, None, None, None, None, None, None
+        g = ops.envmap_shade_backward(normals, positions, camera_center, light_dirs, dcolors.contiguous(), *ctx.consts,
+                                      vis=ctx.vis)
+        return g, None, None, None, None, None, None, None, None
+
+
+def _constant_mask(vis, NP, directions):
+    """A visibility mask rides through the shader as a constant (it depends on the geometry alone, and gradients with
+    respect to geometry are out of scope): one that requires grad is an error, not a silently dropped gradient."""
+    if vis is None:
+        return None
+    ops.check_visibility(vis, NP, directions.shape[-2])
+    return vis
 
 
 def _shared_grid(directions: torch.Tensor) -> torch.Tensor:
@@ -72,12 +83,14 @@ def _shared_grid(directions: torch.Tensor) -> torch.Tensor:
 
 
 def blinn_phong_shading_gbuffer(pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap,
-                                shininess, kd, ks) -> torch.Tensor:
-    """colors [B, NP, 3] from interpolated (not normalised) normals / positions [NP, 3] (reference :75-115)."""
+                                shininess, kd, ks, vis=None) -> torch.Tensor:
+    """colors [B, NP, 3] from interpolated (not normalised) normals / positions [NP, 3] (reference :75-115).  ``vis``: a
+    visibility mask of the envmap's directions (``MeshRasterizer.visibility``) -- only the texels a pixel sees light it."""
     s = float(torch.as_tensor(shininess).reshape(-1)[0])
     cam = torch.as_tensor(camera_center, dtype=torch.float32).reshape(-1)[:3].cpu()
-    return _ShadeFn.apply(envmap.environment_map, pixel_normals, pixel_positions, cam, _shared_grid(envmap.directions),
-                          s, kd, ks)
+    dirs = _shared_grid(envmap.directions)
+    return _ShadeFn.apply(envmap.environment_map, pixel_normals, pixel_positions, cam, dirs, s, kd, ks,
+                          _constant_mask(vis, pixel_normals.shape[0], dirs))
 
 
 def blinn_phong_shading_env_map(device, meshes, fragments, envmap, cameras, materials, kd, ks):

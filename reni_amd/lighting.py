@@ -6,6 +6,7 @@ map from it by inverse-CDF sampling, and the result -- directions and colours [B
 
     sampled_irradiance(samples, normals)      diffuse: scale sum_s max(0, n . d_s) colors_s       (reni_lights_irradiance)
     shade_sampled(samples, normals, ...)      Blinn-Phong: ``ops.envmap_shade`` with per-image light lists
+    light_visibility(rasterizer, mesh, ...)   which pixels each sampled light reaches past the mesh (cast shadows)
 
 All three steps are HIP calls of reni_tu_lights.hip (include/reni_hip.h has the definitions); nothing here touches a texel.
 
@@ -37,7 +38,7 @@ import torch
 
 from . import ops
 
-__all__ = ["LightTable", "LightSamples", "build_light_table", "uniforms", "texel_weights", "sample_lights", "sampled_irradiance", "shade_sampled"]
+__all__ = ["LightTable", "LightSamples", "build_light_table", "uniforms", "texel_weights", "sample_lights", "sampled_irradiance", "shade_sampled", "light_visibility", "ambient_occlusion"]
 
 
 @dataclass
@@ -176,9 +177,39 @@ def sampled_irradiance(samples: LightSamples, normals, scale: float = 1.0 / math
     return ops.lights_irradiance(normals, samples.dirs, samples.colors, scale)
 
 
-def shade_sampled(samples: LightSamples, normals, positions, camera_center, shininess, kd, ks) -> torch.Tensor:
+def shade_sampled(samples: LightSamples, normals, positions, camera_center, shininess, kd, ks, visibility=None) -> torch.Tensor:
     """[B, NP, 3]: the Blinn-Phong environment-map shader (``ops.envmap_shade``) lit by the S sampled lights of each map
-    instead of its H W texels; sample with texel_weight "sineweight" to estimate what the shader gives for the whole map."""
+    instead of its H W texels; sample with texel_weight "sineweight" to estimate what the shader gives for the whole map.
+    ``visibility``: the mask of ``light_visibility`` for these samples -- a light lights only the pixels that see it."""
     if not isinstance(samples, LightSamples):
         raise ValueError("samples must be LightSamples (sample_lights)")
-    return ops.envmap_shade(normals, positions, camera_center, samples.dirs, samples.colors, shininess, kd, ks)
+    return ops.envmap_shade(normals, positions, camera_center, samples.dirs, samples.colors, shininess, kd, ks, vis=visibility)
+
+
+def light_visibility(rasterizer, mesh, R, T, samples: LightSamples, t_min=None) -> torch.Tensor:
+    """The visibility mask [B, NP, ceil(S/32)] of each map's S sampled lights over ``rasterizer``'s G-buffer of ``mesh`` seen
+    with (R, T) (``mesh.MeshRasterizer.visibility`` with per-image direction lists): sampled point lights that cast shadows."""
+    if not isinstance(samples, LightSamples):
+        raise ValueError("samples must be LightSamples (sample_lights)")
+    return rasterizer.visibility(mesh, R, T, samples.dirs, t_min=t_min)
+
+
+def ambient_occlusion(vis, normals, dirs, weights) -> torch.Tensor:
+    """[NP] = sum_j w_j max(0, n . d_j) vis(p, j) / sum_j w_j max(0, n . d_j), and 0 where the denominator is 0: the
+    cosine-weighted share of the directions ``dirs`` [J, 3] (weights [J], e.g. solid angles) that pixel p sees past the mesh.
+    vis is the mask [1, NP, ceil(J/32)] of a shared grid; normals [NP, 3] need not be normalised.  Two calls of the shader
+    (kd = 1, ks = 0, colours w), masked and unmasked -- no kernel of its own."""
+    if not isinstance(dirs, torch.Tensor) or dirs.dim() != 2 or dirs.shape[1] != 3:
+        raise ValueError("dirs must be [J, 3] (a shared grid)")
+    J = dirs.shape[0]
+    if not isinstance(normals, torch.Tensor) or normals.dim() != 2 or normals.shape[1] != 3:
+        raise ValueError("normals must be [NP, 3]")
+    if not isinstance(weights, torch.Tensor) or weights.numel() != J:
+        raise ValueError(f"weights must hold {J} values")
+    ops.check_visibility(vis, normals.shape[0], J, NB=1)
+    w = weights.reshape(1, J, 1).to(torch.float32).expand(1, J, 3).contiguous()
+    pos = torch.zeros_like(normals, dtype=torch.float32)
+    cam = torch.tensor([0.0, 0.0, 1.0])
+    num = ops.envmap_shade(normals, pos, cam, dirs, w, 1.0, 1.0, 0.0, vis=vis)[0, :, 0]
+    den = ops.envmap_shade(normals, pos, cam, dirs, w, 1.0, 1.0, 0.0)[0, :, 0]
+    return torch.where(den > 0, num / den.clamp_min(1e-30), torch.zeros_like(den))

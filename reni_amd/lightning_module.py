@@ -103,6 +103,14 @@ class RENI(_Base):
         if not os.path.isfile(obj_path):
             raise FileNotFoundError(f"RENI.FIT_INVERSE.OBJECT_PATH: OBJ file not found: {obj_path!r}")
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        # optional RENI.FIT_INVERSE.SHADOWS (absent = False): the mesh casts shadows on itself; a capability of the HIP
+        # renderer alone (reni_amd.mesh), which is then used whether or not pytorch3d is importable
+        shadows = bool(t.get("SHADOWS", False) if isinstance(t, dict) else getattr(t, "SHADOWS", False))
+        if shadows:
+            from .mesh import build_hip_renderer
+            renderer, R, T, mesh = build_hip_renderer(obj_path, 0, t.RENDER_RESOLUTION, t.KD_VALUE, device, shadows=True)
+            self.set_renderer(renderer, dict(meshes_world=mesh, R=R, T=T))
+            return
         try:
             import pytorch3d  # noqa: F401
             from .envmap_shader import build_renderer

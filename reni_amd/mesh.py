@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .envmap_shader import EnvironmentMap, _Materials, blinn_phong_shading_gbuffer
+from .envmap_shader import EnvironmentMap, _Materials, _shared_grid, blinn_phong_shading_gbuffer
 
 Fragments = namedtuple("Fragments", ["pix_to_face", "zbuf", "bary_coords", "dists"])
 
@@ -166,6 +166,8 @@ class MeshRasterizer(nn.Module):
         self.cameras = cameras if cameras is not None else FoVPerspectiveCameras()
         self.raster_settings = raster_settings if raster_settings is not None else RasterizationSettings()
         self._cache = None
+        self._accel_cache = None
+        self._vis_cache = None
 
     def gbuffer(self, meshes_world: Meshes, R=None, T=None):
         """-> (Fragments, pixel_normals [S*S,3], pixel_positions [S*S,3]) (interpolated, not normalised)."""
@@ -182,6 +184,33 @@ class MeshRasterizer(nn.Module):
         self._cache = (key, (v, f, R, T), out)  # (the tensors are held so that their ids stay theirs)
         return out
 
+    def visibility(self, meshes_world: Meshes, R=None, T=None, dirs=None, t_min=None, no_cull: bool = False):
+        """-> the int32 visibility mask [NB, S*S, ceil(J/32)] of ``dirs`` ([J,3] shared, NB = 1, or [B,J,3], NB = B) over the
+        cached G-buffer: bit (p, j) is 1 where no face of the mesh but the pixel's own blocks direction j from the pixel's
+        surface point (``ops.mesh_visibility``; ``unpack_visibility`` turns it into booleans).  t_min defaults to 1e-4 x
+        the diagonal of the mesh's bounding box.  The lights are at infinity, so the mask is a constant of (mesh, camera,
+        directions): the acceleration record is kept per mesh and the mask per (G-buffer key, the directions' memory, shape
+        and in-place version, t_min), like the G-buffer itself."""
+        if not isinstance(dirs, torch.Tensor):
+            raise ValueError("dirs must be a tensor [J, 3] or [B, J, 3]")
+        frags, _, pos = self.gbuffer(meshes_world, R, T)
+        gkey = self._cache[0]
+        v, f = meshes_world.verts_packed(), meshes_world.faces_packed()
+        akey = tuple((id(t), t._version) for t in (v, f))
+        if self._accel_cache is None or self._accel_cache[0] != akey:
+            diag = float((v.max(dim=0).values - v.min(dim=0).values).norm())
+            self._accel_cache = (akey, (v, f), ops.mesh_visibility_prepare(v, f), diag)
+        _, _, accel, diag = self._accel_cache
+        t_min = 1e-4 * diag if t_min is None else float(t_min)
+        # a view of the same memory (directions.expand(B, -1, -1)[0], a fresh Python object every step) is the same grid
+        dkey = (dirs.data_ptr(), tuple(dirs.shape), tuple(dirs.stride()), dirs._version, str(dirs.device))
+        key = (gkey, dkey, t_min, bool(no_cull))
+        if self._vis_cache is not None and self._vis_cache[0] == key:
+            return self._vis_cache[2]
+        vis = ops.mesh_visibility(pos, frags.pix_to_face, dirs, accel, t_min, no_cull=no_cull)
+        self._vis_cache = (key, dirs, vis)  # (dirs is held so that its memory stays its own)
+        return vis
+
     def forward(self, meshes_world: Meshes, R=None, T=None, **kwargs) -> Fragments:
         return self.gbuffer(meshes_world, R, T)[0]
 
@@ -194,11 +223,16 @@ class HipMeshRenderer(nn.Module):
     Reference quirk kept: the reference's shader asks ``cameras.get_camera_center()`` WITHOUT R and T
     (pytorch3d_envmap_shader.py:78; MeshRenderer hands R and T to the rasteriser only as keyword arguments), so its
     specular term uses the centre of the default camera -- the world origin -- not the rendering camera's (0, 0, 2).  The
-    same is done here.  With the default KD_VALUE = 1 (no specular term) it has no effect."""
+    same is done here.  With the default KD_VALUE = 1 (no specular term) it has no effect.
 
-    def __init__(self, rasterizer: MeshRasterizer, kd: float, ks: float = None, materials=None, shader_cameras=None):
+    ``shadows=True``: the mesh blocks light (``MeshRasterizer.visibility`` of the envmap's directions, cached; the shader
+    then counts only the texels a pixel sees).  The default, False, renders what the reference renders."""
+
+    def __init__(self, rasterizer: MeshRasterizer, kd: float, ks: float = None, materials=None, shader_cameras=None,
+                 shadows: bool = False):
         super().__init__()
         self.rasterizer = rasterizer
+        self.shadows = bool(shadows)  # cast shadows: the mesh blocks the texels it hides from a pixel
         self.kd = float(kd)
         self.ks = 1.0 - self.kd if ks is None else float(ks)
         self.materials = materials if materials is not None else _Materials(500.0)
@@ -210,15 +244,33 @@ class HipMeshRenderer(nn.Module):
         _, nrm, pos = self.rasterizer.gbuffer(meshes_world, R, T)
         S = self.rasterizer.raster_settings.image_size
         B = envmap.environment_map.shape[0]
-        colors = blinn_phong_shading_gbuffer(nrm, pos, self.camera_center, envmap, self.materials.shininess, self.kd, self.ks)
+        vis = None
+        if self.shadows:  # the mask of the envmap's directions: one for a shared grid, one per image for per-image lists
+            vis = self.rasterizer.visibility(meshes_world, R, T, _shared_grid(envmap.directions))
+        colors = blinn_phong_shading_gbuffer(nrm, pos, self.camera_center, envmap, self.materials.shininess, self.kd, self.ks,
+                                             vis=vis)
         normals = torch.nn.functional.normalize(nrm, p=2, dim=-1, eps=1e-6).reshape(1, S, S, 3).repeat(B, 1, 1, 1)
         return colors.reshape(B, S, S, 3), normals
 
 
-def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device):
+def unpack_visibility(vis: torch.Tensor, J: int) -> torch.Tensor:
+    """The packed mask of ``MeshRasterizer.visibility`` / ``ops.mesh_visibility`` (int32 [NB, NP, ceil(J/32)], bit j & 31 of
+    word j >> 5) as booleans [NB, NP, J].  Plain torch: works on any device."""
+    if not isinstance(vis, torch.Tensor) or vis.dtype != torch.int32 or vis.dim() != 3:
+        raise ValueError("vis must be an int32 tensor [NB, NP, JW]")
+    J = int(J)
+    if J < 1 or (J + 31) // 32 != vis.shape[2]:
+        raise ValueError(f"{J} directions need {(J + 31) // 32} words per pixel, the mask has {vis.shape[2]}")
+    shifts = torch.arange(32, dtype=torch.int32, device=vis.device)
+    bits = (vis.unsqueeze(-1) >> shifts) & 1  # (an arithmetic shift: the sign bit's copies are masked off)
+    return bits.reshape(vis.shape[0], vis.shape[1], -1)[:, :, :J].to(torch.bool)
+
+
+def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device, shadows: bool = False):
     """Same arguments and return value as the reference's ``build_renderer`` (:177-217) -- ``(renderer, R, T, mesh)`` with
     ``renderer(meshes_world=mesh, R=R, T=T, envmap=...)`` -- without pytorch3d: Materials(shininess=500), ks = 1 - kd, the
-    camera at look_at_view_transform(2, 0, 0).  ``device`` must be a GPU device (there is no CPU path)."""
+    camera at look_at_view_transform(2, 0, 0).  ``device`` must be a GPU device (there is no CPU path).  ``shadows=True``:
+    the mesh casts shadows on itself (``HipMeshRenderer(shadows=True)``); the default renders what the reference does."""
     verts, faces = load_obj(obj_path)
     verts = rotate_axis_angle_y(verts, obj_rotation)
     if torch.device(device).type != "cuda":
@@ -227,6 +279,6 @@ def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device):
     mesh.verts_normals_packed()
     cameras = FoVPerspectiveCameras(device=device)
     raster = MeshRasterizer(cameras=cameras, raster_settings=RasterizationSettings(image_size=int(img_size)))
-    renderer = HipMeshRenderer(raster, kd=kd, materials=_Materials(500.0))
+    renderer = HipMeshRenderer(raster, kd=kd, materials=_Materials(500.0), shadows=shadows)
     R, T = look_at_view_transform(2.0, 0.0, 0.0, degrees=True, device=device)
     return renderer, R, T, mesh

@@ -527,10 +527,39 @@ def profile_read(reset: bool = True, kind: int = PROF_FWD_BWD):
     return tot.value, n.value
 
 
-def _shade_call(forward: bool, normals, positions, camera_center, light_dirs, src, shininess, kd, ks):
-    """reni_envmap_shade / reni_envmap_shade_backward (include/reni_hip.h).  normals, positions [NP,3];
-    light_dirs [J,3] (shared grid) or [B,J,3]; src = light colours [B,J,3] (forward) or d colours [B,NP,3] (backward)."""
-    _require_cuda(normals, positions, light_dirs, src)
+def _dirs_dims(light_dirs, what="light_dirs"):
+    if not isinstance(light_dirs, torch.Tensor) or light_dirs.dim() not in (2, 3) or light_dirs.shape[-1] != 3 or min(light_dirs.shape) < 1:
+        raise ValueError(f"{what} must be [J, 3] (a shared grid) or [B, J, 3], got "
+                         f"{tuple(light_dirs.shape) if isinstance(light_dirs, torch.Tensor) else type(light_dirs).__name__}")
+
+
+def check_visibility(vis, NP: int, J: int, NB=None):
+    """The checks every consumer of a visibility mask makes before the library is touched: int32 (the bit pattern of the
+    header's uint32 words) [NB, NP, ceil(J/32)], a constant (no gradient).  NB None: any."""
+    if isinstance(vis, torch.Tensor) and vis.requires_grad:
+        raise ValueError("the visibility mask is a constant: it cannot require grad")
+    if not isinstance(vis, torch.Tensor) or vis.dtype != torch.int32:
+        raise ValueError(f"the visibility mask must be an int32 tensor (32 directions per word), got "
+                         f"{vis.dtype if isinstance(vis, torch.Tensor) else type(vis).__name__}")
+    JW = (int(J) + 31) // 32
+    if vis.dim() != 3 or vis.shape[1] != NP or vis.shape[2] != JW or (NB is not None and vis.shape[0] != NB):
+        raise ValueError(f"the visibility mask must be [{'NB' if NB is None else NB}, {NP}, {JW}] for {NP} pixels and {J} "
+                         f"directions, got {tuple(vis.shape)}")
+
+
+def _shade_call(forward: bool, normals, positions, camera_center, light_dirs, src, shininess, kd, ks, vis=None):
+    """reni_envmap_shade / reni_envmap_shade_backward and their _masked forms (include/reni_hip.h).  normals, positions [NP,3];
+    light_dirs [J,3] (shared grid) or [B,J,3]; src = light colours [B,J,3] (forward) or d colours [B,NP,3] (backward);
+    vis = None or the int32 mask [1,NP,JW] (shared grid; also accepted with per-image directions) / [B,NP,JW]."""
+    if vis is not None:  # argument errors of the new argument come before the library, as everywhere else
+        _dirs_dims(light_dirs)
+        if not isinstance(normals, torch.Tensor) or normals.dim() != 2:
+            raise ValueError("normals and positions must be [NP, 3]")
+        J_ = light_dirs.shape[-2]
+        check_visibility(vis, normals.shape[0], J_)
+        if vis.shape[0] != 1 and (light_dirs.dim() == 2 or vis.shape[0] != light_dirs.shape[0]):
+            raise ValueError(f"a mask of {vis.shape[0]} images needs per-image directions [{vis.shape[0]}, J, 3]")
+    _require_cuda(normals, positions, light_dirs, src, vis)
     lib = _lib.load()
     f32 = torch.float32
     normals = normals.to(f32).contiguous(); positions = positions.to(f32).contiguous()
@@ -552,20 +581,28 @@ def _shade_call(forward: bool, normals, positions, camera_center, light_dirs, sr
     out = torch.empty((B, NP, 3) if forward else (B, J, 3), dtype=f32, device=src.device)
     nbytes = int(lib.reni_envmap_shade_workspace_bytes(B, NP, J))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
-    _call(lib.reni_envmap_shade if forward else lib.reni_envmap_shade_backward, src.device, B, NP, J, normals.data_ptr(),
-          positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride, src.data_ptr(), float(shininess), float(kd),
-          float(ks), out.data_ptr(), ws.data_ptr(), nbytes)
+    head = (B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride,
+            src.data_ptr(), float(shininess), float(kd), float(ks))
+    if vis is None:
+        _call(lib.reni_envmap_shade if forward else lib.reni_envmap_shade_backward, src.device, *head, out.data_ptr(),
+              ws.data_ptr(), nbytes)
+    else:
+        vis = vis.contiguous()
+        vstride = 0 if vis.shape[0] == 1 else NP * vis.shape[2]
+        _call(lib.reni_envmap_shade_masked if forward else lib.reni_envmap_shade_masked_backward, src.device, *head,
+              vis.data_ptr(), vstride, out.data_ptr(), ws.data_ptr(), nbytes)
     return out
 
 
-def envmap_shade(normals, positions, camera_center, light_dirs, light_colors, shininess, kd, ks):
-    """colors [B,NP,3] of the Blinn-Phong environment-map shader (pytorch3d_envmap_shader.py:75-115)."""
-    return _shade_call(True, normals, positions, camera_center, light_dirs, light_colors, shininess, kd, ks)
+def envmap_shade(normals, positions, camera_center, light_dirs, light_colors, shininess, kd, ks, vis=None):
+    """colors [B,NP,3] of the Blinn-Phong environment-map shader (pytorch3d_envmap_shader.py:75-115); with ``vis`` (a mask of
+    ``mesh_visibility``) only the directions a pixel sees count: cast shadows."""
+    return _shade_call(True, normals, positions, camera_center, light_dirs, light_colors, shininess, kd, ks, vis)
 
 
-def envmap_shade_backward(normals, positions, camera_center, light_dirs, dcolors, shininess, kd, ks):
-    """d loss / d light_colors [B,J,3] for an upstream d loss / d colors [B,NP,3]."""
-    return _shade_call(False, normals, positions, camera_center, light_dirs, dcolors, shininess, kd, ks)
+def envmap_shade_backward(normals, positions, camera_center, light_dirs, dcolors, shininess, kd, ks, vis=None):
+    """d loss / d light_colors [B,J,3] for an upstream d loss / d colors [B,NP,3] (``vis``: as in the forward call)."""
+    return _shade_call(False, normals, positions, camera_center, light_dirs, dcolors, shininess, kd, ks, vis)
 
 
 def _vertex_face_csr(faces: torch.Tensor, V: int):
@@ -640,6 +677,83 @@ def rasterize_mesh(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch
     _call(lib.reni_rasterize_mesh, dev, V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th, float(tan_half_fov),
           S, S, p2f.data_ptr(), zbuf.data_ptr(), bary.data_ptr(), dists.data_ptr(), nrm.data_ptr(), pos.data_ptr(), wp, wn)
     return p2f, zbuf, bary, dists, nrm, pos
+
+
+def _morton_order(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """A permutation of the faces that keeps neighbours together: the stable argsort of the 30-bit Morton codes of the
+    centroids (10 bits per axis over the mesh's bounding box).  Faces with an index outside [0, V) sort last."""
+    V = verts.shape[0]
+    ok = ((faces >= 0) & (faces < V)).all(dim=1)
+    c = verts[faces.clamp(0, V - 1)].mean(dim=1)
+    lo, hi = verts.min(dim=0).values, verts.max(dim=0).values
+    g = ((c - lo) / (hi - lo).clamp_min(1e-30) * 1023.0).clamp(0, 1023).to(torch.int64)
+
+    def spread(x):  # 10 bits -> every third bit
+        x = (x | (x << 16)) & 0x030000FF
+        x = (x | (x << 8)) & 0x0300F00F
+        x = (x | (x << 4)) & 0x030C30C3
+        return (x | (x << 2)) & 0x09249249
+
+    code = spread(g[:, 0]) | (spread(g[:, 1]) << 1) | (spread(g[:, 2]) << 2)
+    code = torch.where(ok, code, torch.full_like(code, 1 << 30))
+    return torch.sort(code, stable=True).indices.contiguous()
+
+
+def mesh_visibility_prepare(verts: torch.Tensor, faces: torch.Tensor, order=None) -> torch.Tensor:
+    """reni_mesh_visibility_prepare: the acceleration record of one mesh for ``mesh_visibility`` -- a uint8 tensor (opaque;
+    the faces in Morton order of their centroids unless ``order`` [F] int64 is given, and one inflated bounding box per
+    cluster of 64).  One-off per mesh."""
+    for name, t in (("verts", verts), ("faces", faces)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError(f"{name} must be a tensor [N, 3] with N >= 1")
+    verts, faces = _mesh_inputs(verts, faces)
+    V, F = verts.shape[0], faces.shape[0]
+    if order is None:
+        order = _morton_order(verts, faces)
+    else:
+        if not isinstance(order, torch.Tensor) or tuple(order.shape) != (F,):
+            raise ValueError(f"order must be an int64 tensor [{F}]")
+        _require_cuda(order)
+        order = order.to(torch.int64).contiguous()
+    lib = _lib.load()
+    nbytes = int(lib.reni_mesh_visibility_accel_bytes(F))
+    if nbytes == 0:
+        raise ValueError(f"too many faces ({F})")
+    accel = torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
+    _call(lib.reni_mesh_visibility_prepare, verts.device, V, F, verts.data_ptr(), faces.data_ptr(), order.data_ptr(),
+          accel.data_ptr(), nbytes)
+    return accel
+
+
+def mesh_visibility(positions, pix_to_face, dirs, accel, t_min: float, no_cull: bool = False) -> torch.Tensor:
+    """reni_mesh_visibility: which directions each pixel sees past the mesh.  positions [NP,3] and pix_to_face (NP int64
+    entries, any shape: the rasteriser's) are the G-buffer, dirs [J,3] (shared) or [B,J,3], accel the record of
+    ``mesh_visibility_prepare``, t_min >= 0 the distance below which a hit is the surface itself.  Returns the int32 mask
+    [NB, NP, ceil(J/32)] (NB = 1 for shared directions, else B): bit j & 31 of word j >> 5 is 1 where direction j is
+    unoccluded; background pixels and the bits at j >= J are 0.  ``no_cull`` runs the brute-force path (the same bits)."""
+    _dirs_dims(dirs, "dirs")
+    if not isinstance(positions, torch.Tensor) or positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 1:
+        raise ValueError("positions must be [NP, 3]")
+    NP = positions.shape[0]
+    if not isinstance(pix_to_face, torch.Tensor) or pix_to_face.dtype != torch.int64 or pix_to_face.numel() != NP:
+        raise ValueError(f"pix_to_face must hold {NP} int64 entries")
+    if not isinstance(accel, torch.Tensor) or accel.dtype != torch.uint8 or accel.dim() != 1:
+        raise ValueError("accel must be the uint8 tensor of mesh_visibility_prepare")
+    t_min = float(t_min)
+    if not (t_min >= 0.0 and t_min < float("inf")):
+        raise ValueError("t_min must be finite and >= 0")
+    _require_cuda(positions, pix_to_face, dirs, accel)
+    positions, dirs = _f32c(positions), _f32c(dirs)
+    p2f = pix_to_face.reshape(-1).contiguous()
+    if dirs.dim() == 2:
+        B, J, stride, NB = 1, dirs.shape[0], 0, 1
+    else:
+        B, J = dirs.shape[0], dirs.shape[1]
+        stride, NB = 3 * J, B
+    vis = torch.empty(NB, NP, (J + 31) // 32, dtype=torch.int32, device=positions.device)
+    _call(_lib.load().reni_mesh_visibility, positions.device, B, NP, J, positions.data_ptr(), p2f.data_ptr(), dirs.data_ptr(),
+          stride, accel.data_ptr(), t_min, _lib.VIS_NO_CULL if no_cull else 0, vis.data_ptr())
+    return vis
 
 
 def _sg_check(params, theta_c, phi_c, H, W):

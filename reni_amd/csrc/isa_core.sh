@@ -1,6 +1,15 @@
 #!/bin/bash
-# emit the gfx950 ISA of the core translation unit (build.sh's flags) to $1 and print the training kernel's spill / register summary
+# Emit the gfx950 ISA of one kernel translation unit, with build.sh's flags.
+# Usage: isa_core.sh UNIT OUT.s [extra hipcc flags]
+#   UNIT is one of: core main_f32 main_bf16 film_f32 film_bf16 train_film wide
+# Two builds compare with
+#   sed -E 's/__hip_cuid_[0-9a-f]+/__hip_cuid_X/g' OUT.s | sha256sum
+# (the cuid symbol is a hash of the source text, everything else is the code object).
+set -e
+out="$(realpath -m "${2:-}")"
 cd "$(dirname "$0")"
-hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-spill-vgpr-to-agpr=0 -I../../include "${@:2}" -S --cuda-device-only reni_tu_core.hip -o "$1" 2>&1 | grep -E "error" 
-awk '/^_ZN4reni17k_reni_train_bf16ILi128ELb1ELb0EEEvNS_8MainArgsE:/{p=1} p&&/scratch_/{print NR": "$0} p&&/^\.Lfunc_end0/{exit}' "$1" | head
-grep -n "; ScratchSize\|; NumVgprs" "$1" | head -6
+case "$1" in
+  core|main_f32|main_bf16|film_f32|film_bf16|train_film|wide) ;;
+  *) echo "usage: $0 {core|main_f32|main_bf16|film_f32|film_bf16|train_film|wide} OUT.s [hipcc flags]" >&2; exit 2 ;;
+esac
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -mllvm -amdgpu-spill-vgpr-to-agpr=0 -I../../include "${@:3}" -S --cuda-device-only "reni_tu_$1.hip" -o "$out"

@@ -328,10 +328,7 @@ int timed_launch(void (*fn)(const reni::MainArgs), int grid, int block, int lds,
 
 // the head / loss configuration of every shipped FIT_DECODER run (the SPEC instances' compile-time constants): linear head, tanh,
 // WeightedMSE, no output image.  spec_head: what the plan and the flags decide of it (reni_path_info reports from that part alone).
-#ifndef RENI_AB_NO_SPEC  // (same-box A/B switch of profiles/tools/gpu_variants.sh; never defined in the shipped build.  It covers the FiLM
-#define RENI_AB_NO_SPEC 0  //  training instance too: launch_train asks train_spec for both decoders)
-#endif
-bool spec_head(bool need_dw, int last_linear, int act) { return !RENI_AB_NO_SPEC && need_dw && last_linear && act == RENI_ACT_TANH; }
+bool spec_head(bool need_dw, int last_linear, int act) { return need_dw && last_linear && act == RENI_ACT_TANH; }
 bool train_spec(const reni::MainArgs& a, bool stats) {
   return !stats && spec_head(a.need_dw, a.last_linear, a.act) && a.loss_kind == 0 && a.out == nullptr;
 }
@@ -517,9 +514,7 @@ int run_prologue(const reni_plan* p, const GeoRt& g, const Layout& l, int64_t B,
       d.scale = !l.persist ? 1.f : film ? ((i == 1 || H == 256) ? 1.f : 6.283185307179586f) : (i == 1 ? p->d.first_omega_0 : p->d.hidden_omega_0);
       // frozen-decoder calls (Layout::consistent_bwd): 8 x the scale of the FORWARD image -- the same fp32 product times a power of two,
       // so the bf16 rounding gives the same mantissas and the W^T image is exactly 8 x the transpose of the forward image
-#if !(RENI_ABL & 16)   // (16: the round-5 images, for the A/B of profiles/r06_trajectory.md)
       if (l.consistent_bwd) d.scale = (head ? 1.f : p->d.hidden_omega_0 * 0.15915494309189535f) * 8.f;
-#endif
       ka.d[n++] = d;
     }
   }
@@ -552,13 +547,11 @@ void fill_main_args(reni::MainArgs& a, const reni_plan* p, const Layout& l, int6
   a.L = p->d.hidden_layers; a.last_linear = p->d.last_layer_linear; a.act = p->d.output_activation;
   a.w_first = p->d.first_omega_0; a.w_hidden = p->d.hidden_omega_0;
   a.gy_scale = 1.f;
-#if !(RENI_ABL & 16)
   if (l.consistent_bwd) {  // (2 pi)^L omega_first / 8^(L+1): see Layout::consistent_bwd (L = 5, omega = 30: 1.1207)
     double sc = (double)p->d.first_omega_0 / 8.0;
     for (int i = 0; i < p->d.hidden_layers; ++i) sc *= 6.283185307179586 / 8.0;
     a.gy_scale = (float)sc;
   }
-#endif
   a.Z = Z; a.D = D; a.d_bstride = dbs;
   a.Apre = (const float*)(ws + l.o_A);
   a.afrag = ws + l.o_afrag;

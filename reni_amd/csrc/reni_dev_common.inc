@@ -229,19 +229,7 @@ DEV float phase_hi(unsigned w) { return (float)__builtin_bit_cast(f16x2, w)[1]; 
 // v_fma_mix_f32 multiplies the fp16 cosine into the fp32 gradient -- no unpacking conversion (hipcc turns the plain
 // C++ form into cos, cvt, pk_mul).  One instruction sits between each cosine and its use: a transcendental result
 // needs one wait state before a VALU reads it, and hipcc does not look into asm statements.
-// RENI_ABL: numerics ablations of the bf16 persistent kernels for the G14 trajectory study (profiles/r06_trajectory.md; never defined in
-// the shipped build): 1 = the concat instances reduce a sine argument to [0, 1) before v_sin_f32 and the stash (as the FiLM instances do);
-// 2 = the backward cosine in fp32 (v_cvt_f32_f16 + v_cos_f32 + v_mul_f32) instead of v_cos_f16 + v_fma_mix; 4 = the stashed fp16 phase
-// loses its three lowest mantissa bits (a SENSITIVITY probe: an 8 x coarser stash)
-#ifndef RENI_ABL
-#define RENI_ABL 0
-#endif
 DEV void cos_mul2(unsigned w, float g0, float g1, float& r0, float& r1) {
-  if constexpr (RENI_ABL & 2) {
-    r0 = g0 * __builtin_amdgcn_cosf(phase_lo(w));
-    r1 = g1 * __builtin_amdgcn_cosf(phase_hi(w));
-    return;
-  }
   unsigned c0, c1;
   asm("v_cos_f16_e32 %0, %4\n\t"
       "v_cos_f16_sdwa %1, %4 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1\n\t"
@@ -254,14 +242,6 @@ DEV void cos_mul2(unsigned w, float g0, float g1, float& r0, float& r1) {
 // the packing converts sink to the MFMA that reads the operand, inside the two wait states a VALU write needs in front of it
 // (tests/isa_audit.py::valu_to_mfma)
 DEV unsigned cos_mul2_pk(unsigned w, float g0, float g1) {
-  if constexpr (RENI_ABL & 2) {
-    float r0, r1;
-    cos_mul2(w, g0, g1, r0, r1);
-    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-    unsigned pk2;
-    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2\n\ts_nop 1" : "=v"(pk2) : "v"(r0), "v"(r1));
-    return pk2;
-  }
   unsigned c0, c1, pk;
   asm volatile("v_cos_f16_e32 %0, %3\n\t"
                "v_cos_f16_sdwa %1, %3 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1\n\t"
@@ -455,14 +435,7 @@ enum { DW_HIDDEN = 0, DW_HEAD = 1, DW_L0 = 2 };
 // wait states behind the LAST MFMA of a chain before anything reads its result: an 8-pass XDL op on gfx950 needs 12
 // (LLVM's GFX940_XDL_N_PassWriteVgprVALUReadWaitStates: passes + 3 + 1; the figure hipcc pads its own MFMAs with, and the
 // one tests/isa_audit.py enforces).  Twenty, as first written, cost 8 dead states on each of ~60 chains per tile.
-#define RENI_STR2(x) #x
-#define RENI_STR(x) RENI_STR2(x)
-#ifdef RENI_MFMA_TAIL_N  // (timing probes only: gpu_variants.sh "-DRENI_MFMA_TAIL_N=3" -- fewer states than 11 is WRONG in general)
-#define RENI_MFMA_TAIL "s_nop " RENI_STR(RENI_MFMA_TAIL_N)
-#endif
-#ifndef RENI_MFMA_TAIL
 #define RENI_MFMA_TAIL "s_nop 11"
-#endif
 // TAILN >= 0: a SHORTER pad, `s_nop TAILN`, at a site where the instructions that follow on every path are independent of the
 // result and make up the rest of the twelve states -- each such site is proven by tests/isa_audit.py on the emitted ISA (the pads
 // cost 0.5 % of the kernel per four states over the ~45 chains of a tile: profiles/r04_variants.md)

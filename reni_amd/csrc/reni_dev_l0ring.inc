@@ -98,9 +98,6 @@ __global__ void __launch_bounds__(512, 1) k_reni_l0_ring(const MainArgs a) {
   const int n = t_hi - t_lo + 1;
   const int b_lo = t_lo / a.tiles_per_image;
 
-#ifndef RENI_EXP_L0  // timing-only ablations (results WRONG): 1 no compute, 2 no LDS-DMA, 4 no barrier
-#define RENI_EXP_L0 0
-#endif
   // The walk's coordinates are carried from tile to tile (this kernel is bound by the number of instructions its two waves per SIMD
   // issue -- ~5 cycles apiece whatever their kind: two integer divisions and the 64-bit address products per tile were ~90 scalar
   // instructions of a 485-instruction tile).  Issue side: the tile NSLOT - 1 ahead of the one being computed.
@@ -122,7 +119,6 @@ __global__ void __launch_bounds__(512, 1) k_reni_l0_ring(const MainArgs a) {
                  : "=&s"(keep) : "v"(lane_off), "s"(gsrc_uniform), "s"(lds_dst_uniform) : "memory");
   };
   auto issue_part = [&](int part) {  // this wave's share of the next tile of the walk into the next slot: VM_PER_TILE instructions in all
-    if constexpr (RENI_EXP_L0 & 2) return;
     if (part == 0) { glds16x2(is_g, lane16, is_dst + (unsigned)wave * 4096); return; }
     if (part == 1) { glds16x2(is_g + 2048, lane16, is_dst + (unsigned)wave * 4096 + 2048); return; }
     if (wave < 4) {  // the image's layer-0 operands (k_prep_image's afrag), one row block
@@ -305,10 +301,8 @@ __global__ void __launch_bounds__(512, 1) k_reni_l0_ring(const MainArgs a) {
   };
 
   // ---- the ring
-  if constexpr (!(RENI_EXP_L0 & 2)) {
 #pragma unroll
-    for (int i = 0; i < R::NSLOT - 1; ++i) { if (i < n) issue(); }
-  }
+  for (int i = 0; i < R::NSLOT - 1; ++i) { if (i < n) issue(); }
   int b_prev = t_hi / a.tiles_per_image, cs_tin = t_hi - b_prev * a.tiles_per_image;  // compute side: image / position of tile i
   unsigned cs_base = ring;                                                              // its slot
 #pragma unroll 1
@@ -318,13 +312,11 @@ __global__ void __launch_bounds__(512, 1) k_reni_l0_ring(const MainArgs a) {
     if (i + R::NSLOT - 2 < n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R::NSLOT - 2) * R::VM_PER_TILE) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     TRACE1(2);
-    if constexpr (!(RENI_EXP_L0 & 4))
     __syncthreads();  // everybody's pieces of tile i are there, and everybody is done with tile i - 1: its slot is free
     TRACE1(3);
     const bool do_issue = i + R::NSLOT - 1 < n;
-    if constexpr (RENI_EXP_L0 & 1) { if (do_issue) issue(); }
     TRACE1(4);
-    if constexpr (!(RENI_EXP_L0 & 1)) tile_compute(cs_base, do_issue);
+    tile_compute(cs_base, do_issue);
     TRACE1(6);
     // the next tile of the walk: one position down; behind position 0 the image run ends and its dA leaves (the slot just used is free)
     if (--cs_tin < 0 && i + 1 < n) {

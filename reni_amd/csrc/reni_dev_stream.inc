@@ -161,17 +161,11 @@ __global__ void __launch_bounds__(256, 1) k_dw_frag(const MainArgs a) {
   const int nrec = a.n_tiles * NROUND;
   const int r0 = (int)((long long)blockIdx.x * nrec / gridDim.x), r1 = (int)((long long)(blockIdx.x + 1) * nrec / gridDim.x);
   const int rec_per_image = a.tiles_per_image * NROUND;
-#ifndef RENI_DWFRAG_NTLOAD
-#define RENI_DWFRAG_NTLOAD 1
-#endif
-#ifndef RENI_DWFRAG_PIPE
-#define RENI_DWFRAG_PIPE 1
-#endif
   // The builder (round 6).  Work is split by ROW BLOCKS, not by operand: thread (half, pt) places the g values AND computes / places the
   // sines of row blocks 4 half .. 4 half + 3 of chain thread pt, in eight UNITS of two 16-byte words (unit u: chunk u of its row blocks'
   // g fragments -> raw[u], of their phases -> raw[NRB + u]).  (Round 2 gave threads 0..127 all of g and threads 128..255 all of the sines:
   // 128 v_sin_f32 + 128 converts per record on two of the four waves, and a barrier per record at which the other two waited.)
-  // RENI_DWFRAG_PIPE: the units of record r + 1 are placed BETWEEN the MFMA groups of record r (into the other slot), and each unit's
+  // Pipelined: the units of record r + 1 are placed BETWEEN the MFMA groups of record r (into the other slot), and each unit's
   // registers are reloaded with record r + 2's words as soon as they have been placed: the ~460 VALU / LDS / transcendental instructions of
   // a record's build run under the 64 MFMAs of the record before instead of in front of them.  Same LDS images, same bits.
   u32x4 raw[NRB * 2];
@@ -181,18 +175,11 @@ __global__ void __launch_bounds__(256, 1) k_dw_frag(const MainArgs a) {
     sp = a.stash + (size_t)tile * a.stash_per_wg + (size_t)(l - 1) * G::STASH_LAYER_BYTES + (round * 128 + pt) * 16 + half * (NRB * 4096);
   };
   auto load_unit = [&](const char* sg, const char* sp, int u) __attribute__((always_inline)) {
-#if RENI_DWFRAG_NTLOAD   // (the fragments are read once: non-temporal loads, -1.0 % on the step)
+    // (the fragments are read once: non-temporal loads, -1.0 % on the step)
     raw[u] = __builtin_nontemporal_load((const u32x4*)(sg + u * 4096));
     raw[NRB + u] = __builtin_nontemporal_load((const u32x4*)(sp + u * 4096));
-#else
-    raw[u] = *(const u32x4*)(sg + u * 4096);
-    raw[NRB + u] = *(const u32x4*)(sp + u * 4096);
-#endif
   };
-#ifndef RENI_DWFRAG_W32
-#define RENI_DWFRAG_W32 1
-#endif
-  // RENI_DWFRAG_W32: the kernel is bound by its LDS pipe (counters: an LDS instruction in flight 20 % of every wave's time x four waves
+  // Dword stores: the kernel is bound by its LDS pipe (counters: an LDS instruction in flight 20 % of every wave's time x four waves
   // per CU; 128 two-byte stores per wave and record) -- neighbouring lanes (samples 2 k, 2 k + 1: adjacent columns of the images) swap
   // their words through DPP, the even lane stores BOTH samples' row-r values as one dword, the odd lane both row-(r + 1) values: 64
   // four-byte stores instead of 128 two-byte ones for two more VALU instructions per word.  Same LDS images, same bits.
@@ -200,13 +187,13 @@ __global__ void __launch_bounds__(256, 1) k_dw_frag(const MainArgs a) {
   auto build_unit = [&](int slot, int u) __attribute__((always_inline)) {
     const int rq = u >> 1, c = u & 1;
     const u32x4 wg = raw[u], wp = raw[NRB + u];
-#if RENI_DWFRAG_W32
     char* const TAw = smem + slot * REC + (pw * 32 + (pj & ~1)) * 2 + (half * (NRB / 2) * 32 + (pj & 1)) * G::T_ROWB;   // (rowmap(r + 1) = rowmap(r) + 1 for even r)
     char* const TBw = TAw + G::T_BYTES_AL;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       const int r = 8 * c + 2 * d;
       static_assert(rowmap(1, 0) == rowmap(0, 0) + 1 && rowmap(7, 1) == rowmap(6, 1) + 1, "rows r, r + 1 of a word are adjacent");
+      // (the two sines of a word converted by ONE v_cvt_pk_bf16_f32 -- converted one at a time hipcc issued a packed convert per value)
       typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
       const unsigned hp = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{__builtin_amdgcn_sinf(phase_lo(wp[d])), __builtin_amdgcn_sinf(phase_hi(wp[d]))}, bf16x2_t));
       const unsigned gx = (unsigned)__builtin_amdgcn_update_dpp(0, (int)wg[d], 0xB1, 0xf, 0xf, true);   // quad_perm [1, 0, 3, 2]
@@ -214,21 +201,6 @@ __global__ void __launch_bounds__(256, 1) k_dw_frag(const MainArgs a) {
       *(unsigned*)(TAw + (32 * rq + rowmap(r, phi)) * G::T_ROWB) = __builtin_amdgcn_perm(gx, wg[d], w32_sel);
       *(unsigned*)(TBw + (32 * rq + rowmap(r, phi)) * G::T_ROWB) = __builtin_amdgcn_perm(hx, hp, w32_sel);
     }
-#else
-    char* const TAw = smem + slot * REC + (pw * 32 + pj) * 2 + (half * (NRB / 2) * 32) * G::T_ROWB;
-    char* const TBw = TAw + G::T_BYTES_AL;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const int r = 8 * c + 2 * d;
-      *(unsigned short*)(TAw + (32 * rq + rowmap(r, phi)) * G::T_ROWB) = (unsigned short)(wg[d] & 0xffffu);
-      *(unsigned short*)(TAw + (32 * rq + rowmap(r + 1, phi)) * G::T_ROWB) = (unsigned short)(wg[d] >> 16);
-      // (the two sines of a word converted by ONE v_cvt_pk_bf16_f32 -- converted one at a time hipcc issued a packed convert per value)
-      typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-      const unsigned hp = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{__builtin_amdgcn_sinf(phase_lo(wp[d])), __builtin_amdgcn_sinf(phase_hi(wp[d]))}, bf16x2_t));
-      *(unsigned short*)(TBw + (32 * rq + rowmap(r, phi)) * G::T_ROWB) = (unsigned short)(hp & 0xffffu);
-      *(unsigned short*)(TBw + (32 * rq + rowmap(r + 1, phi)) * G::T_ROWB) = (unsigned short)(hp >> 16);
-    }
-#endif
   };
 #pragma unroll 1
   for (int l = 1; l <= a.L; ++l) {
@@ -356,7 +328,6 @@ __global__ void __launch_bounds__(256, 1) k_dw_frag(const MainArgs a) {
       ptrs(l, rs, sg, sp);
 #pragma unroll
       for (int u = 0; u < NRB; ++u) load_unit(sg, sp, u);
-#if RENI_DWFRAG_PIPE
 #pragma unroll
       for (int u = 0; u < NRB; ++u) build_unit(slot, u);   // the run's first record: placed in front of its MFMAs
       if (rs + 1 < re) {
@@ -379,20 +350,6 @@ __global__ void __launch_bounds__(256, 1) k_dw_frag(const MainArgs a) {
       }
       mma(slot, M0{}, sg, sp);
       slot ^= 1;
-#else
-#pragma unroll 1
-      for (int rec = rs; rec < re; ++rec, slot ^= 1) {
-#pragma unroll
-        for (int u = 0; u < NRB; ++u) build_unit(slot, u);   // (its fragments arrived while the previous record was multiplied)
-        if (rec + 1 < re) {
-          ptrs(l, rec + 1, sg, sp);
-#pragma unroll
-          for (int u = 0; u < NRB; ++u) load_unit(sg, sp, u);
-        }
-        __syncthreads();                     // the images are complete; every wave is past the other slot's MFMAs of rec - 1
-        mma(slot, M0{}, sg, sp);
-      }
-#endif
       flush(image);
       rs = re;
     }

@@ -1,8 +1,3 @@
-// RENI_G1_NT (round-6 experiment, off): non-temporal stores for the g_1 stream.  k_reni_l0_ring reads it straight behind this kernel, out of the
-// Infinity Cache: +1.3 % on the step with them (the H = 256 chain's fragment stream, read much later, gains 12 %: RENI_WIDE_NT).
-#ifndef RENI_G1_NT
-#define RENI_G1_NT 0
-#endif
 // reni_dev_train.inc -- the register-persistent bf16 kernels (H = 128, L <= 5): k_reni_train_bf16 (training / frozen / statistics / FiLM instances) and k_reni_dw1
 // Part of reni_device.inc (included there, inside namespace reni; never compiled on its own).
 
@@ -23,17 +18,14 @@
 //    profiles/r03_parity_numbers.txt).  FiLM keeps the reduction: its angles freq (W h + b) + phase reach tens of revolutions.
 // pads behind the LAST MFMA of a chain at the sites where independent instructions follow on every path (see mfma_bf16_pin_v's TAILN):
 // the values are the smallest the audit (tests/isa_audit.py, every instance, every path) accepts
-#ifndef RENI_TAIL_RB2
-#define RENI_TAIL_RB2 1
-#endif
-#ifndef RENI_TAIL_RB1
-#define RENI_TAIL_RB1 3
-#endif
-#ifndef RENI_TAIL_DWDX
-#define RENI_TAIL_DWDX 1
-#endif
-#ifndef RENI_TAIL_DWDX_A
-#define RENI_TAIL_DWDX_A 1
+constexpr int TAIL_RB2 = 1, TAIL_DWDX = 1, TAIL_DWDX_A = 1;
+#ifdef RENI_TU_TRAIN_FILM
+// (the pads are proven per translation unit on the emitted instruction streams: the FiLM instances interleave other fillers behind the
+// forward GEMMs' first accumulator -- tests/isa_audit.py finds 10 / 11 states there with the concat instances' pad of three, twelve
+// with five -- and take the concat values at the other three sites)
+constexpr int TAIL_RB1 = 5;
+#else
+constexpr int TAIL_RB1 = 3;
 #endif
 template <int N, class F>
 DEV void static_for_down(F&& f) {
@@ -111,9 +103,6 @@ DEV void glds16x3(const char* gsrc_uniform, unsigned lane_off, unsigned lds_dst_
 }
 // group g of this wave (the waves take the groups round-robin); the GEMM loops issue one group per k-step
 DEV void dma_group(const DmaJob& jb, int g, int wave, int nwaves = 4) {
-#if defined(RENI_EXP) && (RENI_EXP & 8)
-  return;
-#endif
   const int gi = g * nwaves + wave;
   if (gi < jb.ng) glds16x3(jb.src + gi * 3072, jb.lane_off, jb.dst + gi * 3072);
 }
@@ -168,7 +157,7 @@ DEV void gemm_rb2(const char* wb, int rbo0, const bf16x8 (&bop)[NKS], f32x16& ac
     fill(ks, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (ks == 0 && ZERO) mfma_bf16_zero_v<NKS == 1>(acc1, a1, bop[ks]);
-    else if (ks == NKS - 1) mfma_bf16_pin_v<true, NKS == 1, NKS == 1 ? -1 : RENI_TAIL_RB2>(acc1, a1, bop[ks]);
+    else if (ks == NKS - 1) mfma_bf16_pin_v<true, NKS == 1, NKS == 1 ? -1 : TAIL_RB2>(acc1, a1, bop[ks]);
     else if (ks == 0) mfma_bf16_pin_v<false, true>(acc1, a1, bop[ks]);
     else mfma_bf16_pin_v<false, false>(acc1, a1, bop[ks]);
     fill(ks, 1);
@@ -190,7 +179,7 @@ DEV void gemm_rb1(const char* wb, int rbo, const bf16x8 (&bop)[NKS], f32x16& acc
     const bf16x8 a = q[ks % D];
     if (ks + D < NKS) q[ks % D] = fa(ks + D);
     if (ks == 0 && ZERO) mfma_bf16_zero_v<NKS == 1>(acc, a, bop[ks]);
-    else if (ks == NKS - 1) mfma_bf16_pin_v<true, NKS == 1, NKS == 1 ? -1 : RENI_TAIL_RB1>(acc, a, bop[ks]);
+    else if (ks == NKS - 1) mfma_bf16_pin_v<true, NKS == 1, NKS == 1 ? -1 : TAIL_RB1>(acc, a, bop[ks]);
     else if (ks == 0) mfma_bf16_pin_v<false, true>(acc, a, bop[ks]);
     else mfma_bf16_pin_v<false, false>(acc, a, bop[ks]);
     fill(ks);
@@ -329,45 +318,6 @@ DEV void dw_gemm_s(const char* TA, const char* TB, f32x16 (&acc)[NBC], float& db
   }
 }
 
-// hidden-layer dW into the hand-owned AGPR tiles BASE..BASE+3 (rows = this wave's block, 4 column blocks)
-template <int BASE, class F = NoFill>
-DEV void dw_gemm_s_agpr(const char* TA, const char* TB, float& dbacc, int wave, int lane, const F& fill = F()) {
-  const TsBase bA = ts_base(TA, lane), bB = ts_base(TB, lane);
-  // the fragments of a k-step are fetched one k-step ahead (two: no faster, measured)
-  constexpr int PF = 1;
-  bf16x8 fa[PF], f0[PF], f1[PF], f2[PF], f3[PF];
-#pragma unroll
-  for (int d = 0; d < PF; ++d) {
-    fa[d] = ts_read(bA, wave, d);
-    f0[d] = ts_read(bB, 0, d); f1[d] = ts_read(bB, 1, d); f2[d] = ts_read(bB, 2, d); f3[d] = ts_read(bB, 3, d);
-  }
-  // The bias-gradient sums (v_dot2c_f32_bf16 x 4 per k-step) are issued one k-step LATE, behind the next k-step's ten
-  // LDS reads: a dot2c straight behind an MFMA waits ~17 cycles for the matrix pipe (it shares the dot unit:
-  // profiles/r02_mfma_shadow.md, k_a2_dot2c*), behind the read block the pipe has drained.
-  bf16x8 a_prev;
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) {
-    const int c = ks % PF;
-    const bf16x8 a = fa[c], b0 = f0[c], b1 = f1[c], b2 = f2[c], b3 = f3[c];
-    if (ks + PF < 8) {
-      fa[c] = ts_read(bA, wave, ks + PF);
-      f0[c] = ts_read(bB, 0, ks + PF); f1[c] = ts_read(bB, 1, ks + PF);
-      f2[c] = ts_read(bB, 2, ks + PF); f3[c] = ts_read(bB, 3, ks + PF);
-    }
-    if (ks > 0) dbacc = frag_sum<PolBF16>(a_prev, dbacc);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_bf16_agpr_tile<BASE + 0, false>(a, b0);
-    mfma_bf16_agpr_tile<BASE + 1, false>(a, b1);
-    mfma_bf16_agpr_tile<BASE + 2, false>(a, b2);
-    if (ks == 7) mfma_bf16_agpr_tile<BASE + 3, true>(a, b3);
-    else mfma_bf16_agpr_tile<BASE + 3, false>(a, b3);
-    a_prev = a;
-    fill(ks);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  dbacc = frag_sum<PolBF16>(a_prev, dbacc);
-}
-
 // ==========================================================================================
 // bf16 TRAINING kernel with register-persistent weight-gradient accumulators (H = 128, L <= 5)
 // ==========================================================================================
@@ -445,25 +395,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
 #else
 #define TRACE(tag) do {} while (0)
 #endif
-  // (64 no stash stores, 128 no stash loads, 256 no transposition-image writes, 512 no dW GEMMs, 1024 no activation VALU in the
-  //  forward fillers)
-  // (2048 no vmcnt(0) in front of the layer / step barriers, 4096 no forward-layer barrier, 8192 no B1, 16384 no B2)
-  // RENI_EXP: timing-only ablations (results are WRONG with any bit set): 1 no barriers, 2 one stash slot for
-  // all layers (L2-resident), 8 no weight DMA, 16 no target loads, 32 no g1 stores
-#ifndef RENI_FILM_PLAIN_LOOP
-#define RENI_FILM_PLAIN_LOOP 0
-#endif
-#ifndef RENI_EXP
-#define RENI_EXP 0
-#endif
-#define TSYNC() do { if constexpr (!(RENI_EXP & 1)) __syncthreads(); } while (0)
-  // RENI_ALT (TIMING-ONLY experiment, results are wrong: profiles/r06_frozen_alternation.txt): strict alternation of the two halves of
-  // an eight-wave workgroup -- a second barrier behind every GEMM phase and the second half one barrier late, so that at any time
-  // only ONE half is inside a GEMM (the weight buffers' hand-over and the dA phase's turns are NOT adapted)
-#ifndef RENI_ALT
-#define RENI_ALT 0
-#endif
-#define EBAR() do { if constexpr (RENI_ALT && !DW) __builtin_amdgcn_s_barrier(); } while (0)
   const int tid = threadIdx.x;
   // The frozen instance runs EIGHT waves (two per SIMD: it has no accumulator tiles to hold and is latency-bound at one)
   // on two 128-sample tiles at a time: waves 0-3 = half 0, waves 4-7 = half 1.  Both halves share the weight buffers
@@ -473,12 +404,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wq = wave & 3, half = wave >> 2;
   const int lane = tid & 63, hi = lane >> 5, j = lane & 31;
-#ifndef RENI_PRIO  // (same-box A/B switch: static issue priority for the second-dispatched half of an eight-wave workgroup -- MI355X_MICROARCH.md,
-#define RENI_PRIO 0  //  "Two waves per SIMD", item 4; 1: waves 4-7 at priority 1, 2: waves 0-3)
-#endif
-  if constexpr (NW == 8 && RENI_PRIO != 0) {
-    if ((RENI_PRIO == 1) == (half == 1)) __builtin_amdgcn_s_setprio(1);
-  }
   // stash layout [layer][workgroup][32 KB (x 2 halves)]: the workgroups run in step, so at any moment all of them store (or load) the
   // SAME layer -- layer-major, those accesses cover one contiguous 8 MB region, spread evenly over the memory channels; workgroup-major
   // (stride = 6 layers x 32 KB) the cost of a layer's eight stores varied between 150 and 650 cycles with the layer's slot (cycle trace)
@@ -502,10 +427,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
   // wave sums = 56 DPP instructions with their wait states, two LDS read-modify-writes on lane 0): every owner lane adds its four
   // values to a slot of its own in LDS (one ds_read_b128, two packed adds, one ds_write_b128); the loss leaves with the image run, the
   // db_out sums once per launch.  SPEC instance only.
-#ifndef RENI_AB_NO_LACC  // (same-box A/B switch of profiles/tools/gpu_variants.sh; never defined in the shipped build)
-#define RENI_AB_NO_LACC 0
-#endif
-  constexpr bool LACC = SPEC && !RENI_AB_NO_LACC;  // (in the generic instance, at 256 registers, the same change costs 1.2 %: profiles/r04_variants.md)
+  constexpr bool LACC = SPEC;  // (in the generic instance, at 256 registers, the same change costs 1.2 %: profiles/r04_variants.md)
   f32x4* const lacc = (f32x4*)(dAacc + H * 8 + (FILM ? FT_FLOATS : 0));  // [4 waves][32 owner lanes] (FiLM: behind the tables)
   float* const hdb = hdw + 3 * H + 16;      // [4 waves][4] db_out, each wave's own samples
   float* const loss_run = hdw + 3 * H + 8;  // [4] each wave's weighted squared error over the current image run (LDS: the
@@ -575,10 +497,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
   float d3_n[3];
   // Concat training instance: the tile's image and its position in the image are carried from tile to tile (the range is
   // contiguous, one tile per step) -- three integer divisions by a run-time value per tile (~30 instructions each) otherwise.
-#ifndef RENI_AB_NO_INCR  // (same-box A/B switch; never defined in the shipped build)
-#define RENI_AB_NO_INCR 0
-#endif
-  constexpr bool INCR = DW && (!FILM || SPEC) && !RENI_AB_NO_INCR;  // (FiLM: its SPEC form has the two registers)
+  constexpr bool INCR = DW && (!FILM || SPEC);  // (FiLM: its SPEC form has the two registers)
   int cur_b = 0, cur_tin = 0;  // image of tile0, tile0's index within it (INCR)
   if constexpr (INCR) { cur_b = t_first / a.tiles_per_image; cur_tin = t_first - cur_b * a.tiles_per_image; }
   int tile_pref = 0;  // (strided walk) the tile prefetch_tile looked up for the next iteration: the list is read once per tile, a tile ahead
@@ -603,11 +522,8 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     for (int rbo = 0; rbo < NRB; ++rbo) aop0_n[rbo] = *(const bf16x8*)(a.afrag + ((size_t)(bi * NRB + rbo) * 64) * 16 + (unsigned)(lane * 16));
     d3_n[0] = dp[0]; d3_n[1] = dp[1]; d3_n[2] = dp[2];
   };
-#ifndef RENI_AB_NO_FILM_PREF  // (same-box A/B switch of profiles/tools/gpu_variants.sh; never defined in the shipped build)
-#define RENI_AB_NO_FILM_PREF 0
-#endif
   // (the generic FiLM training instance has no registers to carry them across the dA phase; its SPEC form has: 239 VGPRs with them)
-  constexpr bool PREF = !(FILM && DW) || (SPEC && !RENI_AB_NO_FILM_PREF);
+  constexpr bool PREF = !(FILM && DW) || SPEC;
   if constexpr (PREF) prefetch_tile(t_first);
   // L0X: a tile's directions come through LDS -- every wave fetches ITS 32 samples' 384 bytes with one LDS-DMA instruction during the
   // previous tile's last step (no cross-wave dependency: the wave's own counted wait at the end of that tile covers it) and reads them
@@ -620,7 +536,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(dnext + wq * 384));
     if (lane < 24) glds16(src, (unsigned)lane16, dst);
   };
-  // The tile's TARGET and WEIGHT rows come the same way (round 5: with them off -- RENI_EXP 16 -- the kernel ran 9.5 % faster.  They
+  // The tile's TARGET and WEIGHT rows come the same way (round 5, profiles/r05_l0ring.md: with them off the kernel ran 9.5 % faster.  They
   // were six strided dword loads per owner lane at the top of the tile, the OLDEST vector-memory operations in flight, so the first
   // vmcnt(0) of the forward pass -- for a weight image issued long after them -- waited out their trip to HBM, every tile).  Each
   // wave fetches its own 32 samples' rows of the NEXT tile at the start of the first backward step, a whole step ahead of the next
@@ -648,7 +564,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     dma_rows(a.weight, a.ws0, a.ws2, w_planar, wnext, bi, tin);
   };
   if constexpr (L0X) { dma_dirs(cur_b, cur_tin); dma_tw(cur_b, cur_tin); dma_wait(); }
-  if constexpr (RENI_ALT && !DW) { if (half == 1) __builtin_amdgcn_s_barrier(); }
 #pragma unroll 1
   for (int tile0 = t_first; tile0 < t_stop; tile0 += t_step) {
     const bool last_tile = tile0 + t_step >= t_stop;
@@ -673,7 +588,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       const int i0 = INCR ? cur_b : tile0 / a.tiles_per_image;
       const int i1 = (tile0 + 1 < t_stop ? tile0 + 1 : t_stop - 1) / a.tiles_per_image;
       if (i0 != ft_img0 || (NHALF == 2 && i1 != ft_img1)) {
-        TSYNC();  // nobody reads the old tables any more
+        __syncthreads();  // nobody reads the old tables any more
         int t0 = tid;  // (opaque here: the copy loops' trip counts are otherwise computed outside the tile loop and kept -- spilled -- for it)
         asm volatile("" : "+v"(t0));
         for (int hsel = 0; hsel < NHALF; ++hsel) {
@@ -685,7 +600,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
 #pragma unroll 1
           for (int i = t0; i < L * 2 * H; i += NW * 64) ft[2 * H + i] = src[i] * 0.15915494309189535f;
         }
-        TSYNC();
+        __syncthreads();
         ft_img0 = i0; ft_img1 = i1;
       }
     }
@@ -739,7 +654,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     asm volatile("" : "+v"(bop0) :: "memory");  // D is consumed (and waited for) before the target loads are issued
     const bool owner = valid && (hi == 0);
     float tgt[3] = {0.f, 0.f, 0.f}, swt[3] = {0.f, 0.f, 0.f};
-    if (!L0X && owner && !(RENI_EXP & 16) && (!STATS || a.target != nullptr)) {  // target / weight: issued behind the first barrier (whose vmcnt(0) would expose
+    if (!L0X && owner && (!STATS || a.target != nullptr)) {  // target / weight: issued behind the first barrier (whose vmcnt(0) would expose
                              // them), consumed after the forward pass
       if (loss_kind == 2) {
 #pragma unroll
@@ -763,18 +678,12 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     // sc < 0: the pre-activation already is the angle in revolutions (hidden layers: omega / 2 pi is folded
     // into the packed weight image and bias by k_pack, PackDesc::scale)
     // (FiLM: tp = the layer's table slot [freq / 2 pi | phase / 2 pi], angle = acc . freq + phase; nullptr = plain)
-    auto red = [](float x) { if constexpr (!FILM && !(RENI_ABL & 1)) return x; else return __builtin_amdgcn_fractf(x); };  // (see the list above)
+    auto red = [](float x) { if constexpr (!FILM) return x; else return __builtin_amdgcn_fractf(x); };  // (see the list above)
     // the same for elements 2q, 2q+1 only (hidden layers): fine-grained filler between another row block's MFMAs
     // FiLM: tp = the layer's table slot; the four (freq, phase) values of pairs q (even) and q + 1 are fetched at the even pair
     // (two ds_read_b128) and kept in `fs` for the odd one
     struct FilmQ { f32x4 fq, ph; };
     auto act_pair = [&](const f32x16& acc, int rb, int q, bf16x8 (&dst)[NKS], const float* tp = nullptr, FilmQ* fs = nullptr) {
-      if constexpr (RENI_EXP & 1024) {  // timing only: no fract / sin / phase packing
-        dst[2 * rb + (q >> 2)][(2 * q) & 7] = (__bf16)acc[2 * q];
-        dst[2 * rb + (q >> 2)][(2 * q + 1) & 7] = (__bf16)acc[2 * q + 1];
-        qst[2 * rb + (q >> 2)][q & 3] = __builtin_bit_cast(unsigned, acc[2 * q]);
-        return;
-      }
       float v0 = acc[2 * q], v1 = acc[2 * q + 1];
       if constexpr (FILM) {
         if ((q & 1) == 0) {
@@ -795,7 +704,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       u32x4 d4 = __builtin_bit_cast(u32x4, dst[2 * rb + (q >> 2)]);
       d4[q & 3] = pk;
       dst[2 * rb + (q >> 2)] = __builtin_bit_cast(bf16x8, d4);
-      if constexpr (RENI_ABL & 4) ph &= 0xfff8fff8u;
       qst[2 * rb + (q >> 2)][q & 3] = ph;
     };
     // a whole finished row block (layer 0; the last layer's pending row blocks)
@@ -808,7 +716,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       float th[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        if constexpr (RENI_EXP & 1024) { th[r] = acc[r]; dst[2 * rb + (r >> 3)][r & 7] = (__bf16)acc[r]; continue; }
         float v = acc[r];
         if constexpr (FILM) { if (tp != nullptr) { const int f = 32 * rb + rowmap(r, hi); v = __builtin_fmaf(v, tp[f], tp[H + f]); } }
         if constexpr (std::is_same<decltype(sc), float>::value) th[r] = red(v * sc);
@@ -834,7 +741,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       const unsigned off = ((unsigned)tid16 & 0x1f0u) | (((unsigned)tid16 >> 9) << 12);
       // (the layer's base as an opaque SCALAR: hipcc otherwise derives one layer's address from another's in 64-bit VALU
       // arithmetic -- two adds and a wait state in front of every store of the forward loop's second layer)
-      unsigned long long base = (unsigned long long)(stash + (size_t)((RENI_EXP & 2) ? 0 : layer) * stash_layer_stride);
+      unsigned long long base = (unsigned long long)(stash + (size_t)layer * stash_layer_stride);
       base = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
              (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)base);  // (wave-uniform by construction; says so to hipcc)
       asm volatile("" : "+s"(base));
@@ -870,11 +777,11 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         // in the dA phase; before the loop for the first tile).  No dma_wait here: its vmcnt(0) would also wait out
         // this tile's target / weight loads, issued a moment ago -- a full HBM latency per tile
         asm volatile("" ::: "memory");
-        if constexpr (!(RENI_EXP & 1)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       } else {
-        if constexpr (!(RENI_EXP & 2048)) dma_wait();
-        if constexpr (!(RENI_EXP & 4096)) TSYNC();  // image of this step landed; the other buffer is free
+        dma_wait();
+        __syncthreads();  // image of this step landed; the other buffer is free
       }
       TRACE(10 + l);
       DmaJob jb = make_job(l);  // next step's image: one group per k-step of the first GEMM below
@@ -894,10 +801,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         if (part == 0 && ks < DG) dma_group(jb, ks, wave, NW);
         // the bias values the second GEMM's accumulators start from are requested here (two quads per k-step once the pending
         // row blocks are done): loaded between the GEMMs, their LDS round trip stood in front of the second GEMM's first MFMA
-#ifndef RENI_AB_FWD_OLD  // (same-box A/B switch of profiles/tools/gpu_variants.sh; never defined in the shipped build)
-#define RENI_AB_FWD_OLD 0
-#endif
-        constexpr bool SPREAD = (!FILM || SPEC) && !RENI_AB_FWD_OLD;  // (FiLM: the SPEC instance has the registers for the two live table quads)
+        constexpr bool SPREAD = !FILM || SPEC;  // (FiLM: the SPEC instance has the registers for the two live table quads)
         if constexpr (SPREAD) {
           // The sixteen pending pairs spread over twelve MFMA slots instead of packed into the first eight (four pairs = 16 VALU
           // behind every MFMA pair there, nothing behind the last eight: the first half of the GEMM was VALU-bound, the second idle).
@@ -930,7 +834,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
           else { act_pair(pib, 3, 2 * ks, hin, tp_prev, &fs); act_pair(pib, 3, 2 * ks + 1, hin, tp_prev, &fs); }
         }
         }
-        if constexpr (!STATS && !(RENI_EXP & 64)) {
+        if constexpr (!STATS) {
           if constexpr (KEEP1) {  // (frozen instance: layer L - 1's phases stay in registers; layer 0's are rebuilt in backward)
             if (part == 1) {
               if (l == L) wB[ks] = qst[ks];
@@ -960,9 +864,8 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         }
       });
       TRACE(120 + l);
-      EBAR();
       if (STATS && l == L && (L & 1) && !last_tile) {
-        TSYNC();  // every wave is done reading buffer 0
+        __syncthreads();  // every wave is done reading buffer 0
         issue_dma(0);
       }
     };
@@ -1036,7 +939,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       if constexpr (PREF) prefetch_tile(tile0 + t_step);
       continue;
     }
-    if constexpr (L0X && !(RENI_EXP & 16)) {  // this tile's target / weight rows: fetched by this wave's LDS-DMA a tile ago (dma_tw)
+    if constexpr (L0X) {  // this tile's target / weight rows: fetched by this wave's LDS-DMA a tile ago (dma_tw)
       typedef __attribute__((address_space(3))) float* lfp;
       const int sl = wq * 32 + j;
       const unsigned to = lds_u32(tnext) + (unsigned)(t_planar ? sl * 4 : sl * 12), ts = t_planar ? 512u : 4u;
@@ -1176,7 +1079,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     auto dwdx_layer = [&](auto base_tag, const char* wb, const bf16x8 (&bop)[NKS], const DmaJob& jb, const u32x4 (&w)[NRB * 2],
                           bf16x8 (&ghb)[NKS], const float* tq, float& dbacc) {
       constexpr int BASE = decltype(base_tag)::value;
-      constexpr bool G1ST = L0X && BASE == 0 && !(RENI_EXP & 32);
+      constexpr bool G1ST = L0X && BASE == 0;
       // layout: [tile within the workgroup's range][workgroup][8 chunks x 4 KB], cells swizzled (kernel header).  The base is an opaque
       // SCALAR and the lane's cell is re-derived from tid16 at every store (hi = bit 9 of tid16): nothing per-lane lives across the stream
       unsigned long long g1b = 0;
@@ -1192,11 +1095,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         unsigned t = (unsigned)tid16;
         asm volatile("" : "+v"(t));
         const unsigned off = ((t ^ ((t >> 3) & 64u)) ^ (unsigned)((c & 1) << 7)) + (unsigned)(c * 4096);
-#if RENI_G1_NT   // (experiment: the g_1 stream is written once and read by k_reni_l0_ring only -- non-temporal stores)
-        asm volatile("global_store_dwordx4 %0, %1, %2 nt" :: "v"(off), "v"(ghb[c]), "s"(g1b) : "memory");
-#else
         asm volatile("global_store_dwordx4 %0, %1, %2" :: "v"(off), "v"(ghb[c]), "s"(g1b) : "memory");
-#endif
       };
       const TsBase bA = ts_base(TA, lane), bB = ts_base(TB, lane);
       auto fx = [&](int i) { return *(const bf16x8*)(wb + (((i >> 3) * NKS + (i & 7)) * 64 + lane) * 16); };
@@ -1210,29 +1109,22 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       auto slot = [&](auto ic, f32x16& acc, const f32x16& accp) {
         constexpr int i = decltype(ic)::value, rb = i >> 3, ks = i & 7, kk = i >> 2, m = i & 3;
         const bf16x8 ax = q[i % D];
-        if constexpr (!(RENI_EXP & 262144)) { if (i + D < 32) q[i % D] = fx(i + D); }
+        if (i + D < 32) q[i % D] = fx(i + D);
         if (ks == 0) mfma_bf16_zero_v<false>(acc, ax, bop[ks]);
-        else if (ks == 7) mfma_bf16_pin_v<true, false, RENI_TAIL_DWDX>(acc, ax, bop[ks]);
+        else if (ks == 7) mfma_bf16_pin_v<true, false, TAIL_DWDX>(acc, ax, bop[ks]);
         else mfma_bf16_pin_v<false, false>(acc, ax, bop[ks]);
-        if constexpr (rb >= 1 && !(RENI_EXP & 32768)) epi_pair(accp, rb - 1, ks, w, ghb, tq, fq4);
-        if constexpr ((RENI_EXP & 524288) != 0) {  // timing experiment: one quarter chunk of an h build (2 cvt, 2 sin, 1 pack) per slot
-          unsigned t0_, t1_, pk_;
-          asm volatile("v_cvt_f32_f16_e32 %0, %3\n\tv_cvt_f32_f16_sdwa %1, %3 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1\n\t"
-                       "v_sin_f32 %0, %0\n\tv_sin_f32 %1, %1\n\ts_nop 0\n\tv_cvt_pk_bf16_f32 %2, %0, %1"
-                       : "=&v"(t0_), "=&v"(t1_), "=&v"(pk_) : "v"(w[i & 7][i & 3]));
-          asm volatile("" :: "v"(pk_));
-        }
+        if constexpr (rb >= 1) epi_pair(accp, rb - 1, ks, w, ghb, tq, fq4);
         __builtin_amdgcn_sched_barrier(0);
         const bf16x8 bx = m == 0 ? fb0 : m == 1 ? fb1 : m == 2 ? fb2 : fb3;
-        if (i == 31) mfma_bf16_agpr_tile<BASE + m, true, RENI_TAIL_DWDX_A>(fa, bx);
+        if (i == 31) mfma_bf16_agpr_tile<BASE + m, true, TAIL_DWDX_A>(fa, bx);
         else mfma_bf16_agpr_tile<BASE + m, false>(fa, bx);
-        if constexpr (kk < 7 && !(RENI_EXP & 131072)) {  // the next k-step's fragments: B fragment m behind its use, the A fragment behind the k-step's first MFMA
+        if constexpr (kk < 7) {  // the next k-step's fragments: B fragment m behind its use, the A fragment behind the k-step's first MFMA
           if (m == 0) { fb0 = ts_read(bB, 0, kk + 1); fan = ts_read(bA, wave, kk + 1); }
           else if (m == 1) fb1 = ts_read(bB, 1, kk + 1);
           else if (m == 2) fb2 = ts_read(bB, 2, kk + 1);
           else fb3 = ts_read(bB, 3, kk + 1);
         }
-        if constexpr (m == 3) { if constexpr (!(RENI_EXP & 65536)) dbacc = frag_sum<PolBF16>(fa, dbacc); fa = fan; }  // (bias-gradient sums of the k-step)
+        if constexpr (m == 3) { dbacc = frag_sum<PolBF16>(fa, dbacc); fa = fan; }  // (bias-gradient sums of the k-step)
         if constexpr (i % 4 == 2 && i / 4 < DG) dma_group(jb, i / 4, wave, NW);  // next step's image, one group per dW k-step
         if constexpr (G1ST && i >= 12 && i % 4 == 0) g1_store((i - 12) / 4);     // (chunks 0..4 behind slots 12, 16, .. 28)
         __builtin_amdgcn_sched_barrier(0);
@@ -1250,8 +1142,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     auto load_phases = [&](const StashAt& sl, u32x4 (&w)[NRB * 2]) {  // all loads in flight together
 #pragma unroll
       for (int c = 0; c < NRB * 2; ++c) {
-        if constexpr (!(RENI_EXP & 128)) w[c] = *stash_chunk(sl, c);
-        else { w[c] = u32x4{0x3c003800u + (unsigned)c, 0x38003400u, 0x30003a00u, 0x39003100u}; asm volatile("" : "+v"(w[c])); }
+        w[c] = *stash_chunk(sl, c);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -1294,7 +1185,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         ts_write<1>(TB, gyb, wq * 32 + jx, hix);
       }
       dma_wait();  // the stash stores of the forward pass are complete before the first read-back below
-      if constexpr (DW) TSYNC();  // the operand images are complete (frozen instance: nothing is shared here)
+      if constexpr (DW) __syncthreads();  // the operand images are complete (frozen instance: nothing is shared here)
       TRACE(7);
       if constexpr (!KEEP1) load_phases(stash_mid(L - 1), wB);  // for step L (KEEP1: wB already holds them)
       if constexpr (DW) {
@@ -1357,25 +1248,19 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         char* gp = a.g1 + ((size_t)(tile - t_first) * gridDim.x + blockIdx.x) * (NKS * 4096);  // (layout: see fillv below)
 #pragma unroll
         for (int c = 0; c < NKS; ++c) {
-          if constexpr (!(RENI_EXP & 32)) {
-#if RENI_G1_NT
-            __builtin_nontemporal_store(gb[c], (bf16x8*)(gp + c * 4096 + (unsigned)tid16));
-#else
-            *(bf16x8*)(gp + c * 4096 + (unsigned)tid16) = gb[c];
-#endif
-          }
+          *(bf16x8*)(gp + c * 4096 + (unsigned)tid16) = gb[c];
         }
       }
       TRACE(30 + l);
       if (DW && l >= 2) {  // (layer 1 has no in-kernel dW GEMM: nothing to transpose, one barrier for the weight image)
-        if constexpr (!(RENI_EXP & 8192)) TSYNC();  // B1: every wave finished the previous step's LDS reads
+        __syncthreads();  // B1: every wave finished the previous step's LDS reads
         TRACE(40 + l);
-        if constexpr (!(RENI_EXP & 256)) ts_write<NRB>(TA, gb, wave * 32 + jx, hix);
+        ts_write<NRB>(TA, gb, wave * 32 + jx, hix);
         TRACE(80 + l);
         // h_{l-1} = sin(phase_{l-1}) straight into the transposed image (dW_l's column operand)
         const unsigned hbase = ts_write_base(TB, wave * 32 + jx, hix);
 #pragma unroll
-        for (int c = 0; c < ((RENI_EXP & 256) ? 0 : NRB * 2); ++c) {
+        for (int c = 0; c < NRB * 2; ++c) {
           bf16x8 hv;
 #pragma unroll
           for (int d = 0; d < 4; ++d) {
@@ -1386,8 +1271,8 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         }
       }
       TRACE(50 + l);
-      if constexpr (!(RENI_EXP & 2048)) dma_wait();       // this step's W^T image (issued one step ago)
-      if constexpr (!(RENI_EXP & 16384)) TSYNC();  // B2
+      dma_wait();       // this step's W^T image (issued one step ago)
+      __syncthreads();  // B2
       TRACE(60 + l);
       if (!DW && l >= 2) {  // behind the vmcnt(0) above: a whole step to land
         if constexpr (!FILM) {
@@ -1399,19 +1284,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       // next step's image (or the next tile's first): one LDS-DMA group per k-step of the GEMM below
       DmaJob jb = make_job(k + 1 < nstep ? k + 1 : 0, LASTSTEP);  // (L0X: k + 1 == nstep in the last step)
       if (k + 1 >= nstep && last_tile) jb.ng = 0;
-      auto fill = [&](int ks) { if (ks < DG) dma_group(jb, ks, wave, NW); };
-#ifndef RENI_FILM_DWDX  // (1 from round 5: with the FiLM table addresses formed per tile the training instances have the registers for the
-#define RENI_FILM_DWDX 1  // interleaved dW / dX stream's second fragment set -- 512 registers, no scratch; 0 = rounds 2-4's separate dW GEMM)
-#endif
-      if constexpr (DW && FILM && !RENI_FILM_DWDX && !(RENI_EXP & 512)) {  // (FiLM training instance: the dW GEMM on its own; concat: dwdx_layer below)
-        switch (l) {  // one static register set per layer
-          case 5: dw_gemm_s_agpr<12>(TA, TB, pdb[4], wave, lane, fill); break;
-          case 4: dw_gemm_s_agpr<8>(TA, TB, pdb[3], wave, lane, fill); break;
-          case 3: dw_gemm_s_agpr<4>(TA, TB, pdb[2], wave, lane, fill); break;
-          case 2: dw_gemm_s_agpr<0>(TA, TB, pdb[1], wave, lane, fill); break;
-          default: break;  // layer 1: handled by k_reni_dw1 from the g_1 stream stored above
-        }
-      }
       TRACE(70 + l);
       // (l == 2: instead of layer 0's phases, the image's layer-0 A operands, through the SAME eight loads -- no second
       // code path: with the 512-byte chunk stride and the lane offset, chunk 2r is operand r of this lane; the odd chunks are
@@ -1428,7 +1300,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       if constexpr (DW) load_phases(sl_nx, wnx);
       if constexpr (!L0X) { if (l == 1) load_d(dre); }  // for the dA phase after the loop; in flight during the dX GEMM
       if constexpr (L0X) { if (l == 2) dma_dirs(last_tile ? cur_b : nxt_b, last_tile ? cur_tin : nxt_tin); }  // the next tile's directions
-      if constexpr (L0X && !(RENI_EXP & 16)) { if (l == L) dma_tw(last_tile ? cur_b : nxt_b, last_tile ? cur_tin : nxt_tin); }  // ... target / weight rows
+      if constexpr (L0X) { if (l == L) dma_tw(last_tile ? cur_b : nxt_b, last_tile ? cur_tin : nxt_tin); }  // ... target / weight rows
       const char* wb = smem + ((k ^ (L0X ? wpar_v : 0)) & 1) * GP::WBSZ;
       const float* const tq_prev = FILM ? ftab + (l - 1) * 2 * H : nullptr;  // frequencies of layer l - 1 (slot 0: ones)
       {
@@ -1436,22 +1308,18 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         // vector-memory fillers of the dX GEMM's 32 MFMA slots
         auto fillv = [&](int rb, int ks) {
           if (!had_dw && rb == 0 && ks < DG) dma_group(jb, ks, wave, NW);
-          if constexpr (DW && !FILM && !(RENI_EXP & 32)) {  // the g_1 stream (dW_1 is finished by k_reni_dw1)
+          if constexpr (DW && !FILM) {  // the g_1 stream (dW_1 is finished by k_reni_dw1)
             if (l == 1 && (ks & 3) == 2) {
               const int c = 2 * rb + (ks >> 2);
               // g_1 stream layout [tile within the workgroup's range][workgroup][32 KB]: the workgroups run in step, so at any moment they
               // write (and k_reni_dw1's read) the same position of their ranges -- range-major these are 256 blocks 2 MB apart,
               // interleaved like this one contiguous 8 MB region, spread evenly over the memory channels
-#if RENI_G1_NT
-              __builtin_nontemporal_store(gb[c], (bf16x8*)(a.g1 + ((size_t)(tile - t_first) * gridDim.x + blockIdx.x) * (NKS * 4096) + (size_t)((unsigned)tid16 + (unsigned)(c * 4096))));
-#else
               *(bf16x8*)(a.g1 + ((size_t)(tile - t_first) * gridDim.x + blockIdx.x) * (NKS * 4096) + (size_t)((unsigned)tid16 + (unsigned)(c * 4096))) = gb[c];
-#endif
             }
           }
         };
         TRACE(190 + l);
-        if constexpr (DW && (!FILM || RENI_FILM_DWDX)) {  // (FiLM: see RENI_FILM_DWDX)
+        if constexpr (DW) {
           switch (l) {  // one static AGPR tile set per layer
             case 5: dwdx_layer(std::integral_constant<int, 12>{}, wb, gb, jb, wph, ghb, tq_prev, pdb[4]); break;
             case 4: dwdx_layer(std::integral_constant<int, 8>{}, wb, gb, jb, wph, ghb, tq_prev, pdb[3]); break;
@@ -1461,7 +1329,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
           }
         } else {
           dx_layer(wb, gb, fillv, wph, ghb, tq_prev, l);
-          EBAR();
         }
       }
     };
@@ -1471,17 +1338,8 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       // conditional g_1 stores, weight-image groups and branches around them -- +10 % on every second dX GEMM (cycle trace).  An even
       // layer count takes its first step ahead of the loop (and pays the 64 copies that put the arrays back in their roles).
       // (round 5: the FiLM training instances take the paired loop too -- with the table addresses formed per tile, above, they no longer
-      // spill with one more copy of the step; -DRENI_FILM_PLAIN_LOOP=1 keeps rounds 2-4's loop for the A/B)
-      if constexpr (FILM && DW && RENI_FILM_PLAIN_LOOP) {
-      int l = L;
-#pragma unroll 1
-      for (; l >= 2; l -= 2) { step(l, gA, gB, wB, wA); step(l - 1, gB, gA, wA, wB); }
-      if (l == 1) step(1, gA, gB, wB, wA);
-      else {
-#pragma unroll
-        for (int c = 0; c < NKS; ++c) gB[c] = gA[c];  // even L: g_0 ended up in gA
-      }
-      } else if constexpr (L0X) {
+      // spill with one more copy of the step)
+      if constexpr (L0X) {
         // odd L >= 3 (launch_train): pairs down to (3, 2) -- layer 2's is the LAST step: g_1 ends in gA, the next tile's layer-0 A
         // operands in wB[0, 2, 4, 6]
         // (do-while: the instance is only launched with L >= 3 -- l0x_ok -- and a loop that may run zero times gives the counted wait
@@ -1537,7 +1395,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       for (int hsel = 0; hsel < NHALF; ++hsel) {  // the halves take turns on the one pair of transposition images
         // (first turn: the images' last readers -- step 2's dW GEMM, or the previous tile's dA GEMM in the frozen
         // instance -- already lie behind a later barrier of every wave)
-        if (hsel > 0) TSYNC();
+        if (hsel > 0) __syncthreads();
         if (half == hsel) {
           ts_write<NRB>(TA, gb, wq * 32 + j, hi);
           ts_write<1>(TB, xcb, wq * 32 + j, hi);
@@ -1554,7 +1412,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
           } else if constexpr (PREF) prefetch_tile(tile0 + t_step);  // the next tile's first inputs: a barrier, the dA GEMM and the loop's tail to land in
         }
         TRACE(94);
-        TSYNC();
+        __syncthreads();
         TRACE(95);
         if (half == hsel) {
           f32x16 accA[1];
@@ -1674,7 +1532,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     if constexpr (INCR) { cur_b = nxt_b; cur_tin = nxt_tin; }
     TRACE(9);
   }
-  if constexpr (RENI_ALT && !DW) { if (half == 0) __builtin_amdgcn_s_barrier(); }
 #ifdef RENI_TRACE
   if (trace_on) {
     for (int i = lane; i < trace_n; i += 64) a.trace[i] = (long long)trace_lds[i];
@@ -1695,7 +1552,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         const float s0 = wave_sum(v[1]), s1 = wave_sum(v[2]), s2 = wave_sum(v[3]);
         if ((tid_e & 63) == 0) { float* o = hdb + 4 * (tid_e >> 6); o[0] = s0; o[1] = s1; o[2] = s2; }
       }
-      TSYNC();
+      __syncthreads();
       float* const dw0 = a.dwp + (size_t)blockIdx.x * a.pkmax * a.dwp_per_wg;
       for (int i = tid_e; i < 3 * H; i += 256) dw0[a.p_off_w[L + 1] + i] = hdw[i];
       if (tid_e < 3) dw0[a.p_off_b[L + 1] + tid_e] = (hdb[tid_e] + hdb[4 + tid_e]) + (hdb[8 + tid_e] + hdb[12 + tid_e]);
@@ -1707,7 +1564,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       const float s0 = wave_sum(v[1]), s1 = wave_sum(v[2]), s2 = wave_sum(v[3]);
       if ((tid_e & 63) == 0) { float* o = hdb + 4 * (tid_e >> 6); o[0] = s0; o[1] = s1; o[2] = s2; }
     }
-    TSYNC();
+    __syncthreads();
     for (int i = tid_e; i < 3 * H; i += 256) dwp[a.p_off_w[L + 1] + i] = hdw[i];
     if (tid_e < 3) dwp[a.p_off_b[L + 1] + tid_e] = (hdb[tid_e] + hdb[4 + tid_e]) + (hdb[8 + tid_e] + hdb[12 + tid_e]);
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
@@ -1789,9 +1646,6 @@ __global__ void __launch_bounds__(256, 2) k_reni_dw1(const MainArgs a) {
     const char* gp = a.g1 + ((size_t)(tile - t_lo) * G_ + g_) * (NKS * 4096);  // ([position in the range][range]: k_reni_train_bf16)
 #pragma unroll
     for (int c = 0; c < NKS; ++c) {
-#if defined(RENI_EXP_DW1) && (RENI_EXP_DW1 & 1)
-      if (c > 0) { gbN[c] = gbN[0]; continue; }
-#endif
       gbN[c] = *(const bf16x8*)(gp + c * 4096 + tid * 16);
     }
     if (b != imgN) {
@@ -1873,11 +1727,7 @@ __global__ void __launch_bounds__(256, 2) k_reni_dw1(const MainArgs a) {
         a0 = PolBF16::mfma(aop[rbo], bop, a0);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-#if defined(RENI_EXP_DW1) && (RENI_EXP_DW1 & 4)
-          hb[2 * rbo + (r >> 3)][r & 7] = (__bf16)a0[r];
-#else
           hb[2 * rbo + (r >> 3)][r & 7] = (__bf16)__builtin_amdgcn_sinf(!FILM ? a0[r] : __builtin_amdgcn_fractf(a0[r]));  // (as the training kernel's forward)
-#endif
       }
     }
     TRACE1(4);
@@ -1888,11 +1738,7 @@ __global__ void __launch_bounds__(256, 2) k_reni_dw1(const MainArgs a) {
     TRACE1(6);
     __syncthreads();
     TRACE1(7);
-#if defined(RENI_EXP_DW1) && (RENI_EXP_DW1 & 2)
-    acc[0][0] += TA[tid] + TB[tid];
-#else
     dw_gemm_s<NRB, DW_HIDDEN, 0>(TA, TB, acc, db, wave, lane);
-#endif
     TRACE1(8);
     if constexpr (FILM) {  // end of an image run of the walk (the next tile, two below, belongs to another image or to nobody)
       const int b_now = tile / a.tiles_per_image;

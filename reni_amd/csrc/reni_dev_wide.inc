@@ -16,7 +16,7 @@
 //     fragments as A operands and the W_1^T image's fragments as B operands, theta_0^T = X . A_b^T the same way, so that
 //     g_0^T (.) cos(theta_0^T), packed, IS the A operand of dA = g_0 X^T -- no transposition image of g_0 (64 KB this kernel's LDS
 //     does not have), only the 9-component X^T operand goes through a private LDS region.
-// One workgroup = RENI_WIDE_WAVES (8) waves on TWO 128-sample tiles (waves 0..3: tile 2 it, waves 4..7: tile 2 it + 1; 4 waves x 32
+// One workgroup = eight waves on TWO 128-sample tiles (waves 0..3: tile 2 it, waves 4..7: tile 2 it + 1; 4 waves x 32
 // samples each), one workgroup per CU, two waves per SIMD: the two tiles share the weight stream (half the L2 -> LDS traffic, barriers
 // and DMA issue per sample) and one wave's MFMAs run under the other's activation epilogue.  256 registers per wave: the backward GEMMs
 // run in QUARTERS of two row blocks (two accumulator chains).  Tile pairs walked with stride gridDim.x (or MainArgs::tlist:
@@ -28,12 +28,9 @@
 // they are held in (MainArgs::gfs: the same [chunk][thread] layout), and the head's g_y goes to a small fp32 stream behind the
 // fragments ([tile][128 samples][4]) from which k_wide_head_dw forms dW_out / db_out (the generic chain transposes for them in LDS
 // this kernel does not have).
-#ifndef RENI_WIDE_WAVES
-#define RENI_WIDE_WAVES 8
-#endif
 struct Wide256 {
   static constexpr int H = 256, NRB = 8, NKS = 16;
-  static constexpr int NWAVE = RENI_WIDE_WAVES, NT = NWAVE / 4;   // waves per workgroup, tiles per workgroup
+  static constexpr int NWAVE = 8, NT = NWAVE / 4;   // waves per workgroup, tiles per workgroup
   static constexpr int HALF = 4 * NKS * 1024;                    // four row blocks of a hidden image: 64 KB
   static constexpr int BIAS_B = 1024;                            // a layer's 256 biases
   static constexpr int XT_ROW = 72, XT_BYTES = 9 * XT_ROW + 8;   // per wave: (x_hi | 1 | x_lo) component-major, 32 samples
@@ -43,13 +40,9 @@ struct Wide256 {
   static constexpr int FT_LMAX = (NWAVE * XT_BYTES + DAS_BYTES) / (NT * 2 * 256 * 4);
   // FiLM training form: the tables alias the dA exchange alone (the X^T operands are written at the top of the tile and live to its end)
   static constexpr int FT_LMAX2 = DAS_BYTES / (NT * 2 * 256 * 4);
-  static_assert(NWAVE == 4 || NWAVE == 8, "one or two tiles per workgroup");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 };
 
-#ifndef RENI_WIDE_DBG  // diagnostics only (never defined in the shipped build): 1 synchronous chunk fetch, 2 no cosine in the epilogues, 4 C++ cosine
-#define RENI_WIDE_DBG 0
-#endif
 // FILM = true (round 6; MODE 0 only): the forward / statistics pass of the reference's DEFAULT model at its shipped width
 // (configs/default.py:9,13: FiLM conditioning, 256 features; src/models/RENI.py:508-519, 565-586, 665-676) -- hidden layer l of image b
 // applies sin(freq_bl . (W_l h + b_l) + phase_bl).  The forward images stay plain (as for the H = 128 FiLM instances), the per-image
@@ -64,15 +57,13 @@ struct Wide256 {
 // generic chain writes: g_theta = cos(theta) . g_h goes to the stream (k_dw_frag applies the frequency where its sums need it), the
 // chain goes on with g_a = freq . g_theta.  Its tables (<= FT_LMAX2 = 4 hidden
 // layers: the default model's) sit in the dA-exchange region, which only the tile's LAST step uses: staged at the top of every tile pair.
-// RENI_WIDE_NT (round 6, default on): the training form's fragment stream -- g_l (k_dw_frag's operand, 64 KB per layer and tile), the head's g_y --
+// The training form's fragment stream -- g_l (k_dw_frag's operand, 64 KB per layer and tile), the head's g_y --
 // leaves through NON-TEMPORAL stores: written once, read by another kernel much later.  With plain stores the stream pushed the tile's own phase
 // stash -- which this kernel reads back in its backward pass -- out of the L2 / Infinity Cache: chain 4.38 -> 3.84 ms, config 2 at 256 features
-// 6.79 -> 6.26 ms same box.  (The H = 128 kernel's g_1 stream, RENI_G1_NT in reni_dev_train.inc, is read by k_reni_l0_ring straight away: +1.3 %, off.)
-#ifndef RENI_WIDE_NT
-#define RENI_WIDE_NT 1
-#endif
+// 6.79 -> 6.26 ms same box.  (The H = 128 kernel's g_1 stream is read by k_reni_l0_ring straight away, out of the Infinity Cache: plain stores,
+// non-temporal ones cost +1.3 % on the step.)
 template <int MODE, bool FILM = false>
-__global__ void __launch_bounds__(64 * RENI_WIDE_WAVES, 1) k_reni_wide256(const MainArgs a) {
+__global__ void __launch_bounds__(64 * Wide256::NWAVE, 1) k_reni_wide256(const MainArgs a) {
   static_assert(!FILM || MODE == 0 || MODE == 2, "FiLM: the forward / statistics instance and the training form (which also serves a frozen decoder)");
   using W = Wide256;
   using G = Geo<PolBF16, 256>;
@@ -258,14 +249,6 @@ __global__ void __launch_bounds__(64 * RENI_WIDE_WAVES, 1) k_reni_wide256(const 
     };
     int k = 0;  // chunk of the tile
     auto chunk_begin = [&]() -> const char* {
-      if constexpr (RENI_WIDE_DBG & 1) {  // (diagnostic: no prefetch -- every chunk fetched synchronously into buffer 0)
-        __syncthreads();
-        dma_chunk(k, k & 1);   // ((k ^ (k & 1)) & 1 == 0: buffer 0)
-        dma_wait();
-        __syncthreads();
-        ++k;
-        return smem;
-      }
       dma_wait();        // this chunk (requested a chunk ago) and everything else this wave has in flight
       __syncthreads();   // every wave's pieces are there; every wave is done with the other buffer
       if (k + 1 < nch) dma_chunk(k + 1, kpar);
@@ -402,21 +385,13 @@ __global__ void __launch_bounds__(64 * RENI_WIDE_WAVES, 1) k_reni_wide256(const 
         if (active) {
 #pragma unroll
           for (int c = 0; c < NKS; ++c) {
-#if RENI_WIDE_NT
             __builtin_nontemporal_store(g[c], (u32x4*)(gp + (size_t)c * 4096));
-#else
-            *(u32x4*)(gp + (size_t)c * 4096) = g[c];
-#endif
           }
         }
       };
       if constexpr (MODE == 2) {
         if (hi == 0 && active)
-#if RENI_WIDE_NT
           __builtin_nontemporal_store(f32x4{gy[0], gy[1], gy[2], 0.f}, (f32x4*)(a.gfs + (size_t)L * a.n_tiles * (size_t)G::STASH_LAYER_BYTES + ((size_t)tile * 128 + ((tl16 >> 10) * 32 + ((tl16 >> 4) & 31))) * 16));  // (sample = 32 wq + j, from the opaque offset)
-#else
-          *(f32x4*)(a.gfs + (size_t)L * a.n_tiles * (size_t)G::STASH_LAYER_BYTES + ((size_t)tile * 128 + ((tl16 >> 10) * 32 + ((tl16 >> 4) & 31))) * 16) = f32x4{gy[0], gy[1], gy[2], 0.f};  // (sample = 32 wq + j, from the opaque offset)
-#endif
       }
       // phases of layer `l`, row blocks 4 h .. 4 h + 3 (eight 16-byte words per lane), requested at the top of the half that uses them
       // (per QUARTER: row blocks 2 qt, 2 qt + 1 -- four words)
@@ -455,9 +430,7 @@ __global__ void __launch_bounds__(64 * RENI_WIDE_WAVES, 1) k_reni_wide256(const 
         for (int r = 0; r < 16; r += 2) {
           const unsigned w = (r < 8 ? w0 : w1)[(r & 7) >> 1];
           float r0, r1;
-          if constexpr (RENI_WIDE_DBG & 2) { r0 = acc[r]; r1 = acc[r + 1]; }
-          else if constexpr (RENI_WIDE_DBG & 4) { r0 = acc[r] * __builtin_amdgcn_cosf(phase_lo(w)); r1 = acc[r + 1] * __builtin_amdgcn_cosf(phase_hi(w)); }
-          else cos_mul2(w, acc[r], acc[r + 1], r0, r1);
+          cos_mul2(w, acc[r], acc[r + 1], r0, r1);
           if constexpr (FILM) {
             // (the W^T image carries 2 pi for the chain's g_a = (freq / 2 pi) . (2 pi W^T g): the stream's g_theta is the plain one)
             // (in 8-byte pieces as they are made: two live words, not eight -- the instance is at its register limit.  The W^T images
@@ -472,11 +445,7 @@ __global__ void __launch_bounds__(64 * RENI_WIDE_WAVES, 1) k_reni_wide256(const 
               asm volatile("" : "+v"(off));
               off += (unsigned)(gofs + (r >> 3) * 4096 + ((r & 7) >> 2) * 8);
               typedef __attribute__((address_space(1))) u32x2 gu32x2;
-#if RENI_WIDE_NT
               __builtin_nontemporal_store(u32x2{sprev, sw}, (gu32x2*)((__attribute__((address_space(1))) char*)gst + off));
-#else
-              *(gu32x2*)((__attribute__((address_space(1))) char*)gst + off) = u32x2{sprev, sw};
-#endif
             }
             if ((r & 3) == 0) fq4 = *(const f32x4*)(tq + 8 * (r >> 2));
             r0 *= fq4[r & 3]; r1 *= fq4[(r & 3) + 1];

@@ -91,9 +91,6 @@ int train_film_lds_bytes(int which) {
   return GeoP<128>::LDS_BYTES + (which != 1 ? (5 + 1) * 2 * 128 * 4 : 0) + (which == 2 ? GeoP<128>::LACC_BYTES : 0);
 }
 hipError_t launch_train_film(int which, const MainArgs& a, int grid, hipStream_t s) {
-#ifdef RENI_AB_NO_FSPEC  // (same-box A/B switch of profiles/tools/gpu_variants.sh; never defined in the shipped build)
-  if (which == 2) which = 0;
-#endif
   void (*fn)(const MainArgs) = which == 0 ? k_reni_train_bf16<128, true, false, true>
                                : which == 2 ? k_reni_train_bf16<128, true, false, true, true> : k_reni_train_bf16<128, false, true, true>;
   const int lds = train_film_lds_bytes(which);

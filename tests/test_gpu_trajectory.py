@@ -137,7 +137,7 @@ def test_c4_latent_trajectory_bf16_g14():
     # network than the one the forward pass evaluates, and the loop's fixed point -- where THAT gradient vanishes -- is not a minimum of
     # the loss the forward pass measures: a first-order image error.  With the W^T images 8 x the forward images (and the rest of the
     # factor on d loss / d y): 48.9 / 47.6 dB.  None of the approximations VERDICT r05 listed (fp16 phase stash, v_cos_f16, unreduced
-    # v_sin_f32 arguments) moved the result by more than 1.3 dB in either direction (RENI_ABL 1, 2, 4 in reni_dev_common.inc).
+    # v_sin_f32 arguments) moved the result by more than 1.3 dB in either direction (profiles/r06_trajectory.md).
     masked_out = (g["mask"].reshape(-1, 3) == 0).all(1)
     ref_img, ac_img = g["img_after_200"], g["img_after_200_autocast_bf16"].astype(np.float32)
     for name, sel in (("masked-out", masked_out), ("kept", ~masked_out)):

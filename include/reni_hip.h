@@ -551,7 +551,7 @@ int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, c
  *   error codes are the forward's.  ws: reni_lobe_backward_workspace_bytes(N, P, Q, n_lobes) bytes, 256-byte aligned.
  * reni_envmap_lookup_taps: for each direction the 8 texels the lookup reads -- 4 on floor(level), 4 on the next level, each
  *   as the element index level H W + y W + x of a contiguous [Lv][H][W] map -- and their effective weights
- *   {gr gc, gr fc, fr gc, fr fc} x {gl, fl} from the lookup's own coordinate chain (a copy).  The next level weighs 0 unless
+ *   {gr gc, gr fc, fr gc, fr fc} x {gl, fl} from the lookup's own coordinate chain (a copy of its four taps).  The next level weighs 0 unless
  *   fl > 0, as the forward reads it only then; a tap that is not used has weight 0 (and a valid index).  tap_index (int32) and
  *   tap_weight are [n_tables][P][8]; n_tables is 1 when directions and level are shared (both strides 0) and N otherwise.
  *   Lv H W < 2^31; the other limits are the lookup's.

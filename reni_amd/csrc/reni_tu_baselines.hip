@@ -25,11 +25,9 @@
 #include "reni_hip.h"
 #include "reni_internal.h"
 
-#define DEV __device__ __forceinline__
+#include "reni_sphere.inc"  // the MFMA result-row map and the drain pad
 
 namespace reni {
-
-typedef float bl_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int SG_WAVES = 4;            // maps per workgroup (one wave each)
 constexpr int SG_MAX_K = 64;           // lobes per map
@@ -208,14 +206,6 @@ __global__ void __launch_bounds__(256) k_sg_total(const float* __restrict__ loss
 }
 
 // ---- spherical harmonics -----------------------------------------------------------------------------------------------
-DEV constexpr int sh_rowmap(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }  // 32x32 MFMA result row
-
-DEV void mfma_drain() {  // wait out the last MFMA's write-back (18 states) before its result is read
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 15\n\ts_nop 3");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 struct ShArgs {
   int N, H, W, T;
   const float* row;  // [H][T]  K P (sqrt 2 for m != 0), times dOmega(y) for the projection
@@ -235,7 +225,7 @@ __global__ void __launch_bounds__(64) k_sh_project(const ShArgs a) {
   const int c = cok ? (int)(col - 3 * n) : 0;
   const int Q = a.H * a.W, T = a.T;
   const float* xp = a.in + n * 3 * (int64_t)Q + c;
-  bl_f32x16 acc[MT];
+  mfma_f32x16 acc[MT];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -262,7 +252,7 @@ __global__ void __launch_bounds__(64) k_sh_project(const ShArgs a) {
   for (int m = 0; m < MT; ++m)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int t = m * 32 + sh_rowmap(r, hi);
+      const int t = m * 32 + mfma_rowmap(r, hi);
       if (t < T) o[3 * t] = acc[m][r];
     }
 }
@@ -282,7 +272,7 @@ __global__ void __launch_bounds__(64) k_sh_reconstruct(const ShArgs a) {
   const float* rowp[SH_QT];
   const float* colp[SH_QT];
   bool qok[SH_QT];
-  bl_f32x16 acc[SH_QT];
+  mfma_f32x16 acc[SH_QT];
 #pragma unroll
   for (int u = 0; u < SH_QT; ++u) {
     const int q = q0 + u * 32 + j;
@@ -311,7 +301,7 @@ __global__ void __launch_bounds__(64) k_sh_reconstruct(const ShArgs a) {
   for (int u = 0; u < SH_QT; ++u)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int q = q0 + u * 32 + sh_rowmap(r, hi);
+      const int q = q0 + u * 32 + mfma_rowmap(r, hi);
       if (q < Q) o[3 * (int64_t)q] = acc[u][r];
     }
 }

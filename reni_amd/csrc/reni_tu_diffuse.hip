@@ -7,10 +7,12 @@
 //
 //   k_diffuse_convolve  out[(o)][(n, c)] = sum_i A[o][i] src[n][i][c], A[o][i] = max(0, n_o . d_i) (w_i scale): a GEMM whose A operand
 //                       is generated on the VALU (one fixed fmaf order) and never stored.  fp32 MFMA v_mfma_f32_32x32x2_f32,
-//                       whose result is bitwise a k-ordered fmaf chain.  A wave owns DF_OT x 32 output rows and CT x 32
+//                       whose result is bitwise a k-ordered fmaf chain.  A wave owns DG_OT x 32 output rows and CT x 32
 //                       (n, c) columns; the four waves of a workgroup share the columns (their src reads hit the same lines).
-//                       blockIdx.z splits the i range into S chunks, S a function of (P, Q) only (df_split); with S > 1 the
+//                       blockIdx.z splits the i range into S chunks, S a function of (P, Q) only (dg_split); with S > 1 the
 //                       partial sums go to the workspace and k_diffuse_reduce adds them in split order.
+//                       Tile constants, result-row map, drain and split rule are reni_sphere.inc's, shared with the lobe
+//                       convolution and its transpose; the body is written out here as it is there.
 //   k_diffuse_reduce    out = ((part_0 + part_1) + part_2) + ...
 //   k_sh_irradiance_l2  shRenderL2 per (map, pixel), the reference's term order and constants, then / pi.
 #include <hip/hip_runtime.h>
@@ -20,23 +22,9 @@
 #include "reni_hip.h"
 #include "reni_internal.h"
 
-#define DEV __device__ __forceinline__
+#include "reni_sphere.inc"  // tile constants, result-row map, drain, split rule, workspace check
 
 namespace reni {
-
-typedef float df_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int DF_OT = 2;     // 32-row output tiles per wave
-constexpr int DF_WAVES = 4;  // waves per workgroup, each its own output rows
-constexpr int DF_ROWS = 32 * DF_OT * DF_WAVES;
-
-DEV constexpr int df_rowmap(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }  // 32x32 MFMA result row
-
-DEV void df_mfma_drain() {  // wait out the last MFMA's write-back (18 states) before its result is read
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 15\n\ts_nop 3");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 struct DfArgs {
   int N, P, Q;  // N P, Q < 2^28
@@ -55,10 +43,10 @@ template <int CT>
 __global__ void __launch_bounds__(256) k_diffuse_convolve(const DfArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hi = lane >> 5;
   const int64_t ncol = 3 * a.N;
-  const int64_t o0 = (int64_t)blockIdx.x * DF_ROWS + wave * (32 * DF_OT);
-  float ox[DF_OT], oy[DF_OT], oz[DF_OT];
+  const int64_t o0 = (int64_t)blockIdx.x * DG_ROWS + wave * (32 * DG_OT);
+  float ox[DG_OT], oy[DG_OT], oz[DG_OT];
 #pragma unroll
-  for (int u = 0; u < DF_OT; ++u) {
+  for (int u = 0; u < DG_OT; ++u) {
     const int64_t o = o0 + u * 32 + j;
     const bool ok = o < a.P;
     ox[u] = ok ? a.out_dirs[3 * o] : 0.f;
@@ -75,9 +63,9 @@ __global__ void __launch_bounds__(256) k_diffuse_convolve(const DfArgs a) {
     const int64_t c = cok[v] ? col - 3 * n : 0;
     colp[v] = a.src + n * a.sn + c * a.sc;
   }
-  df_f32x16 acc[DF_OT][CT];
+  mfma_f32x16 acc[DG_OT][CT];
 #pragma unroll
-  for (int u = 0; u < DF_OT; ++u)
+  for (int u = 0; u < DG_OT; ++u)
 #pragma unroll
     for (int v = 0; v < CT; ++v)
 #pragma unroll
@@ -102,7 +90,7 @@ __global__ void __launch_bounds__(256) k_diffuse_convolve(const DfArgs a) {
       b[v] = cok[v] && iok ? x : 0.f;
     }
 #pragma unroll
-    for (int u = 0; u < DF_OT; ++u) {
+    for (int u = 0; u < DG_OT; ++u) {
       float t = ox[u] * dx;
       t = fmaf(oy[u], dy, t);
       t = fmaf(oz[u], dz, t);
@@ -126,7 +114,7 @@ __global__ void __launch_bounds__(256) k_diffuse_convolve(const DfArgs a) {
     for (int v = 0; v < CT; ++v) colp[v] -= hi * a.si;
     step(hi == 0);
   }
-  df_mfma_drain();
+  mfma_drain();
   const bool split = gridDim.z > 1;
   float* dst = split ? a.ws + (int64_t)blockIdx.z * ncol * a.P : a.out;
 #pragma unroll
@@ -136,10 +124,10 @@ __global__ void __launch_bounds__(256) k_diffuse_convolve(const DfArgs a) {
     const int64_t n = col / 3, c = col - 3 * n;
     float* op = dst + n * 3 * a.P + c;
 #pragma unroll
-    for (int u = 0; u < DF_OT; ++u)
+    for (int u = 0; u < DG_OT; ++u)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t o = o0 + u * 32 + df_rowmap(r, hi);
+        const int64_t o = o0 + u * 32 + mfma_rowmap(r, hi);
         if (o < a.P) op[3 * o] = acc[u][v][r];
       }
   }
@@ -188,29 +176,15 @@ namespace {
 
 using reni::hip_status;
 using reni::reni_set_error;
-constexpr int64_t DF_MAX_ELEMS = 0x3fffffff;
-constexpr int64_t DF_MIN_CHUNK = 2048;  // fewest i per split
-constexpr int64_t DF_TARGET_WGS = 256;  // workgroups per column group the split aims for (one per CU)
 
 bool df_shape_ok(int64_t N, int64_t P, int64_t Q) {
-  return N >= 1 && P >= 1 && Q >= 1 && P <= DF_MAX_ELEMS / 3 && Q <= DF_MAX_ELEMS / 3 && N <= DF_MAX_ELEMS / (3 * P) &&
+  return N >= 1 && P >= 1 && Q >= 1 && P <= DG_MAX_ELEMS / 3 && Q <= DG_MAX_ELEMS / 3 && N <= DG_MAX_ELEMS / (3 * P) &&
          (3 * N + 31) / 32 <= 65535;
-}
-
-// the i split: a function of (P, Q) only, so a map's sums run in the same order in every batch
-void df_split(int64_t P, int64_t Q, int64_t& S, int64_t& chunk) {
-  const int64_t wgs = (P + reni::DF_ROWS - 1) / reni::DF_ROWS;
-  int64_t s = (DF_TARGET_WGS + wgs - 1) / wgs;
-  const int64_t smax = Q / DF_MIN_CHUNK > 1 ? Q / DF_MIN_CHUNK : 1;
-  if (s > smax) s = smax;
-  chunk = (Q + s - 1) / s;
-  chunk += chunk & 1;
-  S = (Q + chunk - 1) / chunk;
 }
 
 int64_t df_ws_bytes(int64_t N, int64_t P, int64_t Q) {
   int64_t S, chunk;
-  df_split(P, Q, S, chunk);
+  dg_split(P, Q, S, chunk);
   return S > 1 ? S * 3 * N * P * (int64_t)sizeof(float) : 0;
 }
 
@@ -237,16 +211,14 @@ int reni_diffuse_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs
   a.src = src; a.sn = src_stride_n; a.si = src_stride_i; a.sc = src_stride_c;
   a.scale = scale; a.out = out;
   int64_t S, chunk;
-  df_split(P, Q, S, chunk);
+  dg_split(P, Q, S, chunk);
   a.chunk = (int)chunk;
   if (S > 1) {
-    const size_t need = (size_t)df_ws_bytes(N, P, Q);
-    if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
-      return reni_set_error(RENI_EWORKSPACE, "diffuse convolve: workspace missing, too small or not 256-byte aligned");
+    if (int rc = dg_check_ws("diffuse convolve", ws, ws_bytes, (size_t)df_ws_bytes(N, P, Q))) return rc;
     a.ws = (float*)ws;
   }
   hipStream_t s = (hipStream_t)stream;
-  const unsigned gx = (unsigned)((P + reni::DF_ROWS - 1) / reni::DF_ROWS);
+  const unsigned gx = (unsigned)((P + reni::DG_ROWS - 1) / reni::DG_ROWS);
   if (3 * N <= 32) {
     hipLaunchKernelGGL(reni::k_diffuse_convolve<1>, dim3(gx, (unsigned)((3 * N + 31) / 32), (unsigned)S), dim3(256), 0, s, a);
   } else {
@@ -264,7 +236,7 @@ int reni_diffuse_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs
 
 int reni_sh_irradiance_l2(int64_t N, int64_t P, const float* coeffs, const float* normals, int64_t normals_stride_n, float* out,
                           void* stream) {
-  if (N < 1 || P < 1 || P > DF_MAX_ELEMS / 3 || N > DF_MAX_ELEMS / (3 * P))
+  if (N < 1 || P < 1 || P > DG_MAX_ELEMS / 3 || N > DG_MAX_ELEMS / (3 * P))
     return reni_set_error(RENI_EINVAL, "sh irradiance: need N, P >= 1 and N P < 2^28");
   if (normals_stride_n != 0 && normals_stride_n != 3 * P)
     return reni_set_error(RENI_EINVAL, "sh irradiance: the normals' map stride must be 0 (shared) or 3 P (per map)");

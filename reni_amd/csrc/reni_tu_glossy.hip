@@ -7,7 +7,8 @@
 // call.  Contraction is off for the whole unit: what is written is what runs.
 //
 //   k_lobe_convolve<KIND, CT>  part[s][l][col][o] = sum_(i in chunk s) f_l(o . d_i) (w_i scale) B[i][col], the GEMM of
-//                       k_diffuse_convolve (reni_tu_diffuse.hip: same tiles, same i split, same v_mfma_f32_32x32x2_f32 chain)
+//                       k_diffuse_convolve (reni_tu_diffuse.hip: same tiles, same i split, same v_mfma_f32_32x32x2_f32 chain;
+//                       tiles, split, row map and drain are reni_sphere.inc's, the body is written out again)
 //                       with another A generator: t = fma(oz, dz, fma(oy, dy, ox dx)), then the lobe, one straight-line
 //                       generator per KIND with the lobe's parameter a uniform argument.  B's columns are the batch's 3 N
 //                       colour columns and, when the call normalises, ONE column of ones behind them: the denominator
@@ -20,9 +21,10 @@
 //                       forward's own launch, so the bits the forward divided by), for the transpose in
 //                       reni_tu_glossy_bwd.hip.
 //   k_envmap_lookup     out[n][p][c] = the bilinear sample of src[n][level][.][.][c] at direction dirs[p] (or dirs[n][p]),
-//                       mixed linearly between floor(level) and the next level.  The coordinate chain is k_rotate_envmap's
-//                       (reni_tu_rotate.hip) from s on, COPIED here so that unit's bits cannot move: one lane per direction
-//                       computes the coordinate once and serves the channels and both levels with it.
+//                       mixed linearly between floor(level) and the next level.  Direction -> (row, col) and the level are
+//                       reni_sphere.inc's (sph_rowcol, sph_level), the functions k_rotate_envmap and k_envmap_lookup_taps
+//                       call; the four taps are k_rotate_envmap's, written out again.  One lane per direction computes the
+//                       coordinate once and serves the channels and both levels with it.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -32,9 +34,7 @@
 
 #pragma clang fp contract(off)
 
-#define DEV __device__ __forceinline__
-
-#include "reni_lobe.inc"  // tiles, lobe generators, drain, split rule: shared with the transpose (reni_tu_glossy_bwd.hip)
+#include "reni_sphere.inc"  // tiles, lobes, drain, split rule, (row, col) and level: shared with reni_tu_glossy_bwd.hip
 
 namespace reni {
 
@@ -61,10 +61,10 @@ __global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hi = lane >> 5;
   const int ll = (int)blockIdx.z / a.S, sp = (int)blockIdx.z - ll * a.S;  // lobe of this launch, split
   const float par = a.par[ll];
-  const int64_t o0 = (int64_t)blockIdx.x * LB_ROWS + wave * (32 * LB_OT);
-  float ox[LB_OT], oy[LB_OT], oz[LB_OT];
+  const int64_t o0 = (int64_t)blockIdx.x * DG_ROWS + wave * (32 * DG_OT);
+  float ox[DG_OT], oy[DG_OT], oz[DG_OT];
 #pragma unroll
-  for (int u = 0; u < LB_OT; ++u) {
+  for (int u = 0; u < DG_OT; ++u) {
     const int64_t o = o0 + u * 32 + j;
     const bool ok = o < a.P;
     ox[u] = ok ? a.out_dirs[3 * o] : 0.f;
@@ -84,9 +84,9 @@ __global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
     const int64_t c = img[v] ? col - 3 * n : 0;
     colp[v] = a.src + n * a.sn + c * a.sc;
   }
-  lb_f32x16 acc[LB_OT][CT];
+  mfma_f32x16 acc[DG_OT][CT];
 #pragma unroll
-  for (int u = 0; u < LB_OT; ++u)
+  for (int u = 0; u < DG_OT; ++u)
 #pragma unroll
     for (int v = 0; v < CT; ++v)
 #pragma unroll
@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
       b[v] = iok ? (img[v] ? x : fill[v]) : 0.f;  // (every lane loads: map 0 where there is no map, the value dropped)
     }
 #pragma unroll
-    for (int u = 0; u < LB_OT; ++u) {
+    for (int u = 0; u < DG_OT; ++u) {
       float t = ox[u] * dx;
       t = fmaf(oy[u], dy, t);
       t = fmaf(oz[u], dz, t);
@@ -135,7 +135,7 @@ __global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
     for (int v = 0; v < CT; ++v) colp[v] -= hi * a.si;
     step(hi == 0);
   }
-  lb_mfma_drain();
+  mfma_drain();
   float* dst = a.ws + ((int64_t)sp * a.Lv + a.lobe[ll]) * a.ncol * a.P;
 #pragma unroll
   for (int v = 0; v < CT; ++v) {
@@ -143,10 +143,10 @@ __global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
     const int64_t col = (int64_t)blockIdx.y * (32 * CT) + v * 32 + j;
     float* op = dst + col * a.P;
 #pragma unroll
-    for (int u = 0; u < LB_OT; ++u)
+    for (int u = 0; u < DG_OT; ++u)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t o = o0 + u * 32 + lb_rowmap(r, hi);
+        const int64_t o = o0 + u * 32 + mfma_rowmap(r, hi);
         if (o < a.P) op[o] = acc[u][v][r];
       }
   }
@@ -213,13 +213,9 @@ __global__ void __launch_bounds__(256) k_envmap_lookup(const LkArgs a) {
   const int64_t n = blockIdx.y;
   const float* d = a.dirs + n * a.dn + 3 * (int64_t)p;
   const float sx = d[0], sy = d[1], sz = d[2];
-  // ---- k_rotate_envmap's chain from s on (a copy: see the header).  atan2f needs no unit length; the zero vector gives
-  // phi = atan2f(0, 0) = 0, a finite theta and so the first row
-  const float phi = atan2f(sqrtf(fmaf(sz, sz, sx * sx)), sy);
-  const float theta = atan2f(sx, -sz);
-  // the clamps change nothing for finite directions; they keep a NaN or an overflow from becoming an address
-  const float row = fminf(fmaxf(fmaf(phi, a.row_scale, -0.5f), -1.f), (float)a.H);
-  const float col = fminf(fmaxf(fmaf(theta, a.col_scale, a.col_bias), -1.f), (float)a.W);
+  // ---- k_rotate_envmap's four taps (written out again: see the header)
+  float row, col;
+  sph_rowcol(sx, sy, sz, a.H, a.W, a.row_scale, a.col_scale, a.col_bias, row, col);
   const float fi = floorf(row), fj = floorf(col);
   const int i = (int)fi, j = (int)fj;
   const float fr = row - fi, fc = col - fj;
@@ -240,11 +236,9 @@ __global__ void __launch_bounds__(256) k_envmap_lookup(const LkArgs a) {
   const int64_t o00 = r0 + (int64_t)(x0 ? j0f : j0) * (int64_t)a.sx, o01 = r0 + (int64_t)(x0 ? j1f : j1) * (int64_t)a.sx;
   const int64_t o10 = r1 + (int64_t)(x1 ? j0f : j0) * (int64_t)a.sx, o11 = r1 + (int64_t)(x1 ? j1f : j1) * (int64_t)a.sx;
   // ---- the level: clamped to [0, Lv - 1] (fmaxf drops a NaN), one more lerp in the same fma order
-  float lv = a.level ? a.level[n * a.ln + p] : a.level_const;
-  lv = fminf(fmaxf(lv, 0.f), (float)(a.Lv - 1));
-  const float fl0 = floorf(lv);
-  const int l0 = (int)fl0, l1 = min(l0 + 1, a.Lv - 1);
-  const float fl = lv - fl0, gl = 1.f - fl;
+  const SphLevel L = sph_level(a.level ? a.level[n * a.ln + p] : a.level_const, a.Lv);
+  const int l0 = L.l0, l1 = L.l1;
+  const float fl = L.fl, gl = L.gl;
   const float* b0 = a.src + n * a.sn + (int64_t)l0 * a.sl;
   const float* b1 = a.src + n * a.sn + (int64_t)l1 * a.sl;
   float* o = a.out + (n * a.P + p) * 3;
@@ -270,13 +264,13 @@ using reni::hip_status;
 using reni::reni_set_error;
 int64_t lb_ws_bytes(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
   int64_t S, chunk;
-  lb_split(P, Q, S, chunk);
+  dg_split(P, Q, S, chunk);
   return S * Lv * (3 * N + 1) * P * (int64_t)sizeof(float);
 }
 
 template <int KIND>
 void lb_launch(const reni::LbArgs& a, hipStream_t s) {
-  const unsigned gx = (unsigned)((a.P + reni::LB_ROWS - 1) / reni::LB_ROWS), gz = (unsigned)(a.nl * a.S);
+  const unsigned gx = (unsigned)((a.P + reni::DG_ROWS - 1) / reni::DG_ROWS), gz = (unsigned)(a.nl * a.S);
   if (a.ncol <= 32) {
     hipLaunchKernelGGL((reni::k_lobe_convolve<KIND, 1>), dim3(gx, 1, gz), dim3(256), 0, s, a);
   } else {
@@ -304,8 +298,8 @@ int lb_launch_kinds(reni::LbArgs& a, int n_lobes, const int32_t* kinds, const fl
 }
 
 bool lb_den_shape_ok(int64_t P, int64_t Q, int64_t Lv) {
-  return P >= 1 && Q >= 1 && Lv >= 1 && Lv <= reni::LB_MAX_LOBES && P <= LB_MAX_ELEMS / 3 && Q <= LB_MAX_ELEMS / 3 &&
-         P <= LB_MAX_ELEMS / (3 * Lv);
+  return P >= 1 && Q >= 1 && Lv >= 1 && Lv <= reni::LB_MAX_LOBES && P <= DG_MAX_ELEMS / 3 && Q <= DG_MAX_ELEMS / 3 &&
+         P <= DG_MAX_ELEMS / (3 * Lv);
 }
 
 }  // namespace
@@ -329,9 +323,7 @@ int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, c
   if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
   if (src_stride_n < 0 || src_stride_i < 0 || src_stride_c < 0)
     return reni_set_error(RENI_EINVAL, "lobe convolve: src strides must be >= 0");
-  const size_t need = (size_t)lb_ws_bytes(N, P, Q, n_lobes);
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
-    return reni_set_error(RENI_EWORKSPACE, "lobe convolve: workspace missing, too small or not 256-byte aligned");
+  if (int rc = dg_check_ws("lobe convolve", ws, ws_bytes, (size_t)lb_ws_bytes(N, P, Q, n_lobes))) return rc;
   reni::LbArgs a = {};
   a.N = (int)N; a.P = (int)P; a.Q = (int)Q;
   a.ncol = (int)(3 * N + (normalise ? 1 : 0));
@@ -339,7 +331,7 @@ int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, c
   a.src = src; a.sn = src_stride_n; a.si = src_stride_i; a.sc = src_stride_c;
   a.scale = normalise ? 1.f : scale;  // a normalised result does not depend on the scale
   int64_t S, chunk;
-  lb_split(P, Q, S, chunk);
+  dg_split(P, Q, S, chunk);
   a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
   a.ws = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
@@ -353,7 +345,7 @@ int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, c
 size_t reni_lobe_denominators_workspace_bytes(int64_t P, int64_t Q, int64_t n_lobes) {
   if (!lb_den_shape_ok(P, Q, n_lobes)) return 0;
   int64_t S, chunk;
-  lb_split(P, Q, S, chunk);
+  dg_split(P, Q, S, chunk);
   return (size_t)(S * n_lobes * P * (int64_t)sizeof(float)) + 256;
 }
 
@@ -366,10 +358,8 @@ int reni_lobe_denominators(int64_t P, int64_t Q, const float* out_dirs, const fl
     return reni_set_error(RENI_EINVAL, "lobe denominators: NULL argument");
   if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
   int64_t S, chunk;
-  lb_split(P, Q, S, chunk);
-  const size_t need = (size_t)(S * n_lobes * P * (int64_t)sizeof(float));
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
-    return reni_set_error(RENI_EWORKSPACE, "lobe denominators: workspace missing, too small or not 256-byte aligned");
+  dg_split(P, Q, S, chunk);
+  if (int rc = dg_check_ws("lobe denominators", ws, ws_bytes, (size_t)(S * n_lobes * P * (int64_t)sizeof(float)))) return rc;
   // the forward's own launch without maps: the column of ones is column 0 of one 32-column group, and a column's sums do not
   // depend on the columns beside it.  The kernel loads a map's value in every lane and drops it where there is no map: in_w
   // stands in for the maps it reads ([Q] floats, texel stride 1).
@@ -415,10 +405,7 @@ int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, c
   a.dirs = dirs; a.dn = dirs_stride_n; a.level = level; a.ln = level ? level_stride_n : 0; a.level_const = level_const;
   a.out = out;
   a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
-  const double pi = 3.14159265358979323846;
-  a.row_scale = (float)((double)H / pi);
-  a.col_scale = (float)((double)W / (2.0 * pi));
-  a.col_bias = (float)(0.5 * (double)W - 0.5);
+  sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
   hipLaunchKernelGGL(reni::k_envmap_lookup, dim3((unsigned)((P + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream, a);
   return reni::hip_status();
 }

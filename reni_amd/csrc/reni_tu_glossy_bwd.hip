@@ -7,7 +7,7 @@
 //   k_lobe_recip        r[l][o] = normalise ? (den[l][o] > 0 ? 1 / den[l][o] : 0) : scale -- what the forward multiplied
 //                       num[.][l][o][.] by, once per (lobe, o).
 //   k_lobe_convolve_t<KIND, CT>  part[s][col][i] = sum_(l of KIND) sum_(o in chunk s) f_l(o . d_i) r[l][o] g[o][col of lobe l]:
-//                       k_lobe_convolve with the roles swapped.  Rows are the Q texels (the same 32-row tiles, LB_OT a
+//                       k_lobe_convolve with the roles swapped.  Rows are the Q texels (the same 32-row tiles, DG_OT a
 //                       wave, 4 waves), the reduction runs over o, two a step with lanes 32..63 feeding k = 1, and t is
 //                       built in the forward's order (ox dx, then two fma), so both directions use one kernel matrix up to
 //                       the lobe's rounding.  r sits where the forward has w_i, a per-k scalar.  The lobes of a kind are
@@ -17,8 +17,9 @@
 //                       order, written through element strides: every element is written.
 //   k_envmap_lookup_taps  per direction the 8 texels k_envmap_lookup reads (4 on floor(level), 4 on the next level) as
 //                       element indices level H W + y W + x, and their effective weights {gr gc, gr fc, fr gc, fr fc} x
-//                       {gl, fl}; the second level weighs 0 unless fl > 0, as the forward reads it only then.  The coordinate
-//                       chain is k_envmap_lookup's, COPIED here so that unit's bits cannot move.
+//                       {gl, fl}; the second level weighs 0 unless fl > 0, as the forward reads it only then.  (row, col)
+//                       and the level come from the functions k_envmap_lookup calls (sph_rowcol, sph_level); the four taps
+//                       are k_envmap_lookup's, written out again.
 //   k_envmap_lookup_bwd one lane per (map, element): the sum of weight x upstream over the element's taps, in the order a
 //                       stable sort of the indices left them -- the scatter as a gather (as reni_mesh_vertex_normals does
 //                       with the faces of a vertex).  A texel sampled by very many directions is summed by ONE lane.
@@ -31,9 +32,7 @@
 
 #pragma clang fp contract(off)
 
-#define DEV __device__ __forceinline__
-
-#include "reni_lobe.inc"
+#include "reni_sphere.inc"  // tiles, lobes, drains, split rule, (row, col) and level: shared with reni_tu_glossy.hip
 
 namespace reni {
 
@@ -65,28 +64,14 @@ __global__ void __launch_bounds__(256) k_lobe_recip(const float* __restrict__ de
   r[e] = v;
 }
 
-// lb_mfma_drain with the accumulators tied to the pad: behind the loop over the lobes hipcc would otherwise copy them out of
-// the AGPRs ahead of it, one wait state short of the write-back on the path that leaves the loop
-template <int CT>
-DEV void lbt_mfma_drain(lb_f32x16 (&acc)[LB_OT][CT]) {
-  static_assert(LB_OT == 2 && (CT == 1 || CT == 2), "one operand per accumulator tile");
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (CT == 1) {
-    asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[0][0]), "+a"(acc[1][0]));
-  } else {
-    asm volatile("s_nop 15\n\ts_nop 3" : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[1][0]), "+a"(acc[1][1]));
-  }
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 template <int KIND, int CT>
 __global__ void __launch_bounds__(256) k_lobe_convolve_t(const LbtArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hi = lane >> 5;
   const int sp = (int)blockIdx.z;  // split
-  const int64_t i0 = (int64_t)blockIdx.x * LB_ROWS + wave * (32 * LB_OT);
-  float dx[LB_OT], dy[LB_OT], dz[LB_OT];
+  const int64_t i0 = (int64_t)blockIdx.x * DG_ROWS + wave * (32 * DG_OT);
+  float dx[DG_OT], dy[DG_OT], dz[DG_OT];
 #pragma unroll
-  for (int u = 0; u < LB_OT; ++u) {
+  for (int u = 0; u < DG_OT; ++u) {
     const int64_t i = i0 + u * 32 + j;
     const bool ok = i < a.Q;
     dx[u] = ok ? a.in_dirs[3 * i] : 0.f;
@@ -105,9 +90,9 @@ __global__ void __launch_bounds__(256) k_lobe_convolve_t(const LbtArgs a) {
     const int64_t c = cok[v] ? col - 3 * n : 0;
     colp[v] = a.g + (n * a.Lv * a.P + olo + hi) * 3 + c;
   }
-  lb_f32x16 acc[LB_OT][CT];
+  mfma_f32x16 acc[DG_OT][CT];
 #pragma unroll
-  for (int u = 0; u < LB_OT; ++u)
+  for (int u = 0; u < DG_OT; ++u)
 #pragma unroll
     for (int v = 0; v < CT; ++v)
 #pragma unroll
@@ -133,7 +118,7 @@ __global__ void __launch_bounds__(256) k_lobe_convolve_t(const LbtArgs a) {
         b[v] = ook && cok[v] ? x : 0.f;
       }
 #pragma unroll
-      for (int u = 0; u < LB_OT; ++u) {
+      for (int u = 0; u < DG_OT; ++u) {
         float t = ox * dx[u];
         t = fmaf(oy, dy[u], t);
         t = fmaf(oz, dz[u], t);
@@ -158,7 +143,7 @@ __global__ void __launch_bounds__(256) k_lobe_convolve_t(const LbtArgs a) {
       step(hi == 0);
     }
   } while (++ll < a.nl);
-  lbt_mfma_drain<CT>(acc);
+  mfma_drain_tied(acc);
   float* dst = a.ws + (int64_t)sp * a.ncol * a.Q;
 #pragma unroll
   for (int v = 0; v < CT; ++v) {
@@ -166,10 +151,10 @@ __global__ void __launch_bounds__(256) k_lobe_convolve_t(const LbtArgs a) {
     const int64_t col = (int64_t)blockIdx.y * (32 * CT) + v * 32 + j;
     float* op = dst + col * a.Q;
 #pragma unroll
-    for (int u = 0; u < LB_OT; ++u)
+    for (int u = 0; u < DG_OT; ++u)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t i = i0 + u * 32 + lb_rowmap(r, hi);
+        const int64_t i = i0 + u * 32 + mfma_rowmap(r, hi);
         if (i < a.Q) op[i] = acc[u][v][r];
       }
   }
@@ -211,11 +196,9 @@ __global__ void __launch_bounds__(256) k_envmap_lookup_taps(const LtArgs a) {
   const int64_t n = blockIdx.y;
   const float* d = a.dirs + n * a.dn + 3 * (int64_t)p;
   const float sx = d[0], sy = d[1], sz = d[2];
-  // ---- k_envmap_lookup's chain (a copy: see the header)
-  const float phi = atan2f(sqrtf(fmaf(sz, sz, sx * sx)), sy);
-  const float theta = atan2f(sx, -sz);
-  const float row = fminf(fmaxf(fmaf(phi, a.row_scale, -0.5f), -1.f), (float)a.H);
-  const float col = fminf(fmaxf(fmaf(theta, a.col_scale, a.col_bias), -1.f), (float)a.W);
+  // ---- k_envmap_lookup's four taps (written out again: see the header)
+  float row, col;
+  sph_rowcol(sx, sy, sz, a.H, a.W, a.row_scale, a.col_scale, a.col_bias, row, col);
   const float fi = floorf(row), fj = floorf(col);
   const int i = (int)fi, j = (int)fj;
   const float fr = row - fi, fc = col - fj;
@@ -237,11 +220,9 @@ __global__ void __launch_bounds__(256) k_envmap_lookup_taps(const LtArgs a) {
   const int e4[4] = {r0 + c00, r0 + c01, r1 + c10, r1 + c11};
   const float w4[4] = {gr * gc, gr * fc, fr * gc, fr * fc};
   // ---- the level, as the forward: the next level is read, and so weighs, only when fl > 0
-  float lv = a.level ? a.level[n * a.ln + p] : a.level_const;
-  lv = fminf(fmaxf(lv, 0.f), (float)(a.Lv - 1));
-  const float fl0 = floorf(lv);
-  const int l0 = (int)fl0, l1 = min(l0 + 1, a.Lv - 1);
-  const float fl = lv - fl0, gl = 1.f - fl;
+  const SphLevel L = sph_level(a.level ? a.level[n * a.ln + p] : a.level_const, a.Lv);
+  const int l0 = L.l0, l1 = L.l1;
+  const float fl = L.fl, gl = L.gl;
   const bool two = fl > 0.f;
   const int hw = a.H * a.W;
   int32_t* ip = a.idx + (n * a.P + p) * 8;
@@ -298,13 +279,13 @@ size_t lbt_align(size_t x) { return (x + 255) & ~(size_t)255; }
 // r [Lv][P] (rounded up to 256 bytes), then 3 kinds x S slabs [3 N][Q]
 size_t lbt_ws_bytes(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
   int64_t S, chunk;
-  lb_split(Q, P, S, chunk);
+  dg_split(Q, P, S, chunk);
   return lbt_align((size_t)(Lv * P) * sizeof(float)) + (size_t)(3 * S * 3 * N * Q) * sizeof(float);
 }
 
 template <int KIND>
 void lbt_launch(const reni::LbtArgs& a, hipStream_t s) {
-  const unsigned gx = (unsigned)((a.Q + reni::LB_ROWS - 1) / reni::LB_ROWS);
+  const unsigned gx = (unsigned)((a.Q + reni::DG_ROWS - 1) / reni::DG_ROWS);
   if (a.ncol <= 32) {
     hipLaunchKernelGGL((reni::k_lobe_convolve_t<KIND, 1>), dim3(gx, 1, (unsigned)a.S), dim3(256), 0, s, a);
   } else {
@@ -346,9 +327,7 @@ int reni_lobe_convolve_backward(int64_t N, int64_t P, int64_t Q, const float* ou
   if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
   if (grad_stride_n < 0 || grad_stride_i < 0 || grad_stride_c < 0)
     return reni_set_error(RENI_EINVAL, "lobe convolve backward: grad_src strides must be >= 0");
-  const size_t need = lbt_ws_bytes(N, P, Q, n_lobes);
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
-    return reni_set_error(RENI_EWORKSPACE, "lobe convolve backward: workspace missing, too small or not 256-byte aligned");
+  if (int rc = dg_check_ws("lobe convolve backward", ws, ws_bytes, lbt_ws_bytes(N, P, Q, n_lobes))) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* r = (float*)ws;
   float* slabs = (float*)((char*)ws + lbt_align((size_t)(n_lobes * P) * sizeof(float)));
@@ -363,7 +342,7 @@ int reni_lobe_convolve_backward(int64_t N, int64_t P, int64_t Q, const float* ou
   a.out_dirs = out_dirs; a.in_dirs = in_dirs;
   a.g = grad_out; a.r = r;
   int64_t S, chunk;
-  lb_split(Q, P, S, chunk);
+  dg_split(Q, P, S, chunk);
   a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
   int nslab = 0;
   for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind) {  // one launch per kind present, its lobes inside
@@ -402,10 +381,7 @@ int reni_envmap_lookup_taps(int64_t n_tables, int64_t Lv, int64_t H, int64_t W, 
   a.dirs = dirs; a.dn = dirs_stride_n; a.level = level; a.ln = level ? level_stride_n : 0; a.level_const = level_const;
   a.idx = tap_index; a.wgt = tap_weight;
   a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
-  const double pi = 3.14159265358979323846;
-  a.row_scale = (float)((double)H / pi);
-  a.col_scale = (float)((double)W / (2.0 * pi));
-  a.col_bias = (float)(0.5 * (double)W - 0.5);
+  sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
   hipLaunchKernelGGL(reni::k_envmap_lookup_taps, dim3((unsigned)((P + 255) / 256), (unsigned)n_tables), dim3(256), 0,
                      (hipStream_t)stream, a);
   reni::note_launches(1);

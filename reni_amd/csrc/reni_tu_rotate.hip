@@ -30,6 +30,8 @@
 
 #pragma clang fp contract(off)
 
+#include "reni_sphere.inc"  // direction -> (row, col) and the three constants: shared with the lookup (reni_tu_glossy.hip)
+
 namespace reni {
 
 struct RotArgs {
@@ -48,7 +50,7 @@ struct RotArgs {
 };
 
 // element offset of the tap (i, j) of the sphere: -1 <= i <= H, -1 <= j <= W + 1
-__device__ __forceinline__ int64_t tap_offset(int i, int j, const RotArgs& a) {
+DEV int64_t tap_offset(int i, int j, const RotArgs& a) {
   if (i < 0) { i = -1 - i; j += a.W >> 1; }
   if (i >= a.H) { i = 2 * a.H - 1 - i; j += a.W >> 1; }
   if (j < 0) j += a.W;
@@ -71,12 +73,8 @@ __global__ void __launch_bounds__(256) k_rotate_envmap(const RotArgs a) {
   const float sx = fmaf(R[6], dz, fmaf(R[3], dy, R[0] * dx));
   const float sy = fmaf(R[7], dz, fmaf(R[4], dy, R[1] * dx));
   const float sz = fmaf(R[8], dz, fmaf(R[5], dy, R[2] * dx));
-  const float phi = atan2f(sqrtf(fmaf(sz, sz, sx * sx)), sy);
-  const float theta = atan2f(sx, -sz);
-  // the clamps change nothing for finite R (0 <= phi <= fp32(pi), |theta| <= fp32(pi)); they keep a NaN or an overflow in a
-  // caller's matrix from becoming an address
-  const float row = fminf(fmaxf(fmaf(phi, a.row_scale, -0.5f), -1.f), (float)a.H);
-  const float col = fminf(fmaxf(fmaf(theta, a.col_scale, a.col_bias), -1.f), (float)a.W);
+  float row, col;
+  sph_rowcol(sx, sy, sz, a.H, a.W, a.row_scale, a.col_scale, a.col_bias, row, col);
   int64_t n = b;
   if (a.src_index) n = min(max(a.src_index[b], (int64_t)0), a.n_src - 1);
   const float* base = a.src + n * a.sn;
@@ -136,10 +134,7 @@ extern "C" int reni_rotate_envmap(int64_t B, int64_t C, int64_t H, int64_t W, co
   a.src_index = src_index; a.n_src = n_src; a.rot = rot; a.rot_stride = rot_stride;
   a.row_trig = row_trig; a.col_trig = col_trig; a.out = out;
   a.C = (int)C; a.H = (int)H; a.W = (int)W;
-  const double pi = 3.14159265358979323846;
-  a.row_scale = (float)((double)H / pi);
-  a.col_scale = (float)((double)W / (2.0 * pi));
-  a.col_bias = (float)(0.5 * (double)W - 0.5);
+  sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
   const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)B);
   hipStream_t s = (hipStream_t)stream;
   if (mode == RENI_ROTATE_BILINEAR) hipLaunchKernelGGL(reni::k_rotate_envmap<true>, grid, dim3(256), 0, s, a);

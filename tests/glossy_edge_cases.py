@@ -15,7 +15,7 @@ the texels either side of each chunk boundary, the others walk the texels cyclic
 there every row, the last one, the first one and those at the chunk boundaries among them, lies next to a texel, and the
 indicator gradients sit at those rows.
 
-A builder restates its case in fp32 (each operation rounded once, the kernel's dot order, the lobes of reni_lobe.inc, ONE
+A builder restates its case in fp32 (each operation rounded once, the kernel's dot order, the lobes of reni_sphere.inc, ONE
 sequential chain over the reduction: a harsher order than the kernel's pairs and splits) and moves to its next seed until
 that restatement stays within ROOM = 0.75 of every budget and every float64 denominator is above 0.1 of its lobe's
 largest; the budgets themselves (tests/test_glossy_cpu.py::lobe_tol) are never widened."""
@@ -52,7 +52,7 @@ LOBE_SETS = {"nine": tuple(LOBES), "phong16": PHONG16, "mix16": MIX16}
 
 # ---------------------------------------------------------------------------------------------- the split rule
 def lb_split(rows, red):
-    """(S, chunk) of reni_lobe.inc's lb_split: the forward calls it with (P, Q), the transpose with (Q, P)"""
+    """(S, chunk) of reni_sphere.inc's dg_split: the forwards call it with (P, Q), the transpose with (Q, P)"""
     wgs = (rows + 255) // 256
     s = min((256 + wgs - 1) // wgs, max(red // 2048, 1))
     chunk = (red + s - 1) // s
@@ -101,7 +101,7 @@ def t_fp32(out_dirs, in_dirs):
 
 
 def lobe_fp32(lobe, t):
-    """reni_lobe.inc's generators in numpy fp32, every operation rounded once (log2 / exp2 / the reciprocal correctly rounded
+    """reni_sphere.inc's generators in numpy fp32, every operation rounded once (log2 / exp2 / the reciprocal correctly rounded
     where the hardware's are within 1 ulp)"""
     kind, p = lobe
     t = np.asarray(t, f32)

@@ -1,6 +1,6 @@
 """CPU check of the glossy edge-shape case lists (tests/glossy_edge_cases.py): the lists hold the shapes they name, the library
 splits them as the names say, every output row lies next to its texel, every float64 denominator is well away from zero,
-and an fp32 restatement of each kernel -- the kernel's dot order, the lobes of reni_lobe.inc, every operation rounded once,
+and an fp32 restatement of each kernel -- the kernel's dot order, the lobes of reni_sphere.inc, every operation rounded once,
 ONE sequential chain over the reduction -- stays within 0.75 of the budget tests/test_gpu_glossy_edges.py applies against
 float64 (tests/test_glossy_cpu.py::lobe_tol; twice it for the normalised transpose).  A case that plain fp32 arithmetic
 already pushed to its bound would make the GPU comparison say nothing about the kernel; it fails here first.

@@ -801,8 +801,12 @@ int reni_path_info(const reni_plan* plan, int64_t B, int64_t P, uint32_t flags, 
  * rest behind the call as before.  `hip_event` is a hipEvent_t created by the caller on the buffers' device. */
 int reni_set_grad_ready_event(void* hip_event);
 
-/* Kernel launches the library has issued in this process (all entry points, all streams); reset != 0 returns the count and
- * sets it to zero.  bench.py reports launches per step: at small problems a step costs its dependent launches. */
+/* Kernel launches counted so far in this process, on all streams; reset != 0 returns the count and sets it to zero.  Counted:
+ * every launch of the model's entry points (forward, backward, training and latent steps, optimisers, weight lists), of the
+ * image, metrics, lights and visibility entry points, and of reni_lobe_denominators, reni_lobe_convolve_backward,
+ * reni_envmap_lookup_taps and reni_envmap_lookup_backward.  NOT counted: the shader, raster, baseline (SG, SH), diffuse,
+ * resample, blur and rotate entry points, reni_lobe_convolve and reni_envmap_lookup.
+ * bench.py reports launches per step: at small problems a step costs its dependent launches. */
 int64_t reni_launch_count(int32_t reset);
 
 #ifdef __cplusplus

@@ -41,8 +41,9 @@ namespace {
 
 thread_local std::string g_err;
 
-// Every kernel launch of the library is counted (reni_launch_count): bench.py reports launches per step beside ms_per_step -- at small
-// problems a step is its dependent launches, not its FLOPs (DESIGN.md section 5).
+// Every kernel launch of the core (RENI_LAUNCH and timed_launch below) is counted (reni_launch_count): bench.py reports launches per step beside ms_per_step -- at small
+// problems a step is its dependent launches, not its FLOPs (DESIGN.md section 5).  Of the utility units only some count theirs
+// (note_launches, through tu_launch(TU_COUNTED, ...) of reni_tu_host.inc): DESIGN.md section 4.4i has the table.
 std::atomic<long long> g_launches{0};
 // reni_set_grad_ready_event: recorded on the call's stream once the gradient of everything behind layer 1 is final (see the header)
 thread_local hipEvent_t g_ev_rest = nullptr;

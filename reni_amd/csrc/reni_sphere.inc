@@ -1,14 +1,13 @@
 // reni_sphere.inc -- the ONE definition of what the environment-map units share without a change to their generated code:
 //   * the 32x32 MFMA result-row map and the drain pads (the SH kernels of reni_tu_baselines.hip and the direction GEMMs);
 //   * of the direction GEMM (k_diffuse_convolve, k_lobe_convolve, k_lobe_convolve_t): tile constants, lobe generators, split
-//     rule, limits, workspace check, the lobes' argument checks.  The body (row load, clear, k-step, k-pair loop, store) stays
+//     rule, limits, the lobes' argument checks.  The body (row load, clear, k-step, k-pair loop, store) stays
 //     written out in each kernel: every shared form of it changed the generated code (DESIGN 4.4h);
 //   * of the equirectangular lookup (k_rotate_envmap, k_envmap_lookup, k_envmap_lookup_taps): direction -> (row, col), the
 //     level interpolation, the host's three constants.  The four taps stay written out in each kernel, for the same reason.
 // Included at file scope, outside every namespace.  Every function here that rounds switches contraction off for itself, so
 // what is written is what runs whatever the including unit compiles with (the lobe generators hold no a * b + c outside fmaf).
 #pragma once
-#include <stdio.h>
 
 #ifndef DEV
 #define DEV __device__ __forceinline__
@@ -119,14 +118,6 @@ inline void dg_split(int64_t rows, int64_t red, int64_t& S, int64_t& chunk) {
   chunk = (red + s - 1) / s;
   chunk += chunk & 1;
   S = (red + chunk - 1) / chunk;
-}
-
-// RENI_OK, or "<who>: workspace missing, too small or not 256-byte aligned" set
-inline int dg_check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need) {
-  if (ws && !((uintptr_t)ws & 255) && ws_bytes >= need) return RENI_OK;
-  char msg[96];
-  snprintf(msg, sizeof msg, "%s: workspace missing, too small or not 256-byte aligned", who);
-  return reni::reni_set_error(RENI_EWORKSPACE, msg);
 }
 
 // the constants of sph_rowcol, rounded once from float64: fp32(H / pi), fp32(W / 2 pi), W/2 - 1/2

@@ -24,6 +24,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
 #include "reni_sphere.inc"  // the MFMA result-row map and the drain pad
 
@@ -310,7 +311,6 @@ __global__ void __launch_bounds__(64) k_sh_reconstruct(const ShArgs a) {
 
 namespace {
 
-using reni::hip_status;
 using reni::reni_set_error;
 constexpr int64_t BL_MAX_ELEMS = 0x3fffffff;
 constexpr int64_t SH_MAX_W = 4096;  // keeps the reconstruction grid's y extent (H W / 128) under 65536
@@ -336,11 +336,10 @@ reni::SgArgs sg_args(int64_t N, int64_t K, int64_t H, int64_t W, const float* pa
   return a;
 }
 
-int sh_check(const char* what, int64_t N, int64_t H, int64_t W, int64_t lmax) {
+int sh_check(int64_t N, int64_t H, int64_t W, int64_t lmax) {
   if (lmax < 0 || lmax > reni::SH_MAX_LMAX) return reni_set_error(RENI_EINVAL, "sh: lmax must be in [0, 15]");
   if (N < 1 || W < 2 || (W & 1) || H != W / 2) return reni_set_error(RENI_EINVAL, "sh: need N >= 1, W even, H == W / 2");
   if (W > SH_MAX_W || N > BL_MAX_ELEMS / (3 * H * W)) return reni_set_error(RENI_EINVAL, "sh: W > 4096 or too many elements");
-  (void)what;
   return RENI_OK;
 }
 
@@ -361,8 +360,7 @@ int reni_sg_render(int64_t N, int64_t K, int64_t H, int64_t W, const float* para
   reni::SgArgs a = sg_args(N, K, H, W, params, theta_c, phi_c, theta_range, phi_range);
   a.rec = rec;
   const unsigned blocks = (unsigned)((N + reni::SG_WAVES - 1) / reni::SG_WAVES);
-  hipLaunchKernelGGL(reni::k_sg_render, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
-  return hip_status();
+  return tu_launch(TU_PLAIN, reni::k_sg_render, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 int reni_sg_loss_grad(int64_t N, int64_t K, int64_t H, int64_t W, const float* params, const float* theta_c, const float* phi_c,
@@ -382,46 +380,40 @@ int reni_sg_loss_grad(int64_t N, int64_t K, int64_t H, int64_t W, const float* p
   const int64_t P = H * W;
   if (sg_uses_lds(H, W)) {
     const unsigned blocks = (unsigned)((N + reni::SG_WAVES - 1) / reni::SG_WAVES);
-    hipLaunchKernelGGL(reni::k_sg_loss_grad<true>, dim3(blocks), dim3(256), (size_t)15 * P * sizeof(float), s, a);
+    if (int rc = tu_launch(TU_PLAIN, reni::k_sg_loss_grad<true>, dim3(blocks), dim3(256), (size_t)15 * P * sizeof(float), s, a)) return rc;
   } else {
-    const size_t need = (size_t)sg_ws_blocks(N) * 15 * (size_t)P * sizeof(float);
-    if (!ws || ((uintptr_t)ws & 255) || ws_bytes < need)
-      return reni_set_error(RENI_EWORKSPACE, "sg loss: workspace missing, too small or not 256-byte aligned");
+    if (int rc = tu_check_ws("sg loss", ws, ws_bytes, (size_t)sg_ws_blocks(N) * 15 * (size_t)P * sizeof(float))) return rc;
     a.ws = (float*)ws;
-    hipLaunchKernelGGL(reni::k_sg_loss_grad<false>, dim3((unsigned)sg_ws_blocks(N)), dim3(256), 0, s, a);
+    if (int rc = tu_launch(TU_PLAIN, reni::k_sg_loss_grad<false>, dim3((unsigned)sg_ws_blocks(N)), dim3(256), 0, s, a)) return rc;
   }
-  if (int rc = hip_status()) return rc;
-  hipLaunchKernelGGL(reni::k_sg_total, dim3(1), dim3(256), 0, s, loss_per_map, (int)N, loss_total);
-  return hip_status();
+  return tu_launch(TU_PLAIN, reni::k_sg_total, dim3(1), dim3(256), 0, s, loss_per_map, (int)N, loss_total);
 }
 
 int reni_sh_project(int64_t N, int64_t H, int64_t W, int64_t lmax, const float* img, const float* row_table,
                     const float* col_table, float* coeffs, void* stream) {
-  if (int rc = sh_check("project", N, H, W, lmax)) return rc;
+  if (int rc = sh_check(N, H, W, lmax)) return rc;
   if (!img || !row_table || !col_table || !coeffs) return reni_set_error(RENI_EINVAL, "sh project: NULL argument");
   reni::ShArgs a;
   a.N = (int)N; a.H = (int)H; a.W = (int)W; a.T = (int)((lmax + 1) * (lmax + 1));
   a.row = row_table; a.col = col_table; a.in = img; a.out = coeffs;
   const dim3 grid((unsigned)((3 * N + 31) / 32));
   hipStream_t s = (hipStream_t)stream;
-  if (a.T <= 32) hipLaunchKernelGGL(reni::k_sh_project<1>, grid, dim3(64), 0, s, a);
-  else if (a.T <= 64) hipLaunchKernelGGL(reni::k_sh_project<2>, grid, dim3(64), 0, s, a);
-  else if (a.T <= 128) hipLaunchKernelGGL(reni::k_sh_project<4>, grid, dim3(64), 0, s, a);
-  else hipLaunchKernelGGL(reni::k_sh_project<8>, grid, dim3(64), 0, s, a);
-  return hip_status();
+  if (a.T <= 32) return tu_launch(TU_PLAIN, reni::k_sh_project<1>, grid, dim3(64), 0, s, a);
+  if (a.T <= 64) return tu_launch(TU_PLAIN, reni::k_sh_project<2>, grid, dim3(64), 0, s, a);
+  if (a.T <= 128) return tu_launch(TU_PLAIN, reni::k_sh_project<4>, grid, dim3(64), 0, s, a);
+  return tu_launch(TU_PLAIN, reni::k_sh_project<8>, grid, dim3(64), 0, s, a);
 }
 
 int reni_sh_reconstruct(int64_t N, int64_t H, int64_t W, int64_t lmax, const float* coeffs, const float* row_table,
                         const float* col_table, float* out, void* stream) {
-  if (int rc = sh_check("reconstruct", N, H, W, lmax)) return rc;
+  if (int rc = sh_check(N, H, W, lmax)) return rc;
   if (!coeffs || !row_table || !col_table || !out) return reni_set_error(RENI_EINVAL, "sh reconstruct: NULL argument");
   reni::ShArgs a;
   a.N = (int)N; a.H = (int)H; a.W = (int)W; a.T = (int)((lmax + 1) * (lmax + 1));
   a.row = row_table; a.col = col_table; a.in = coeffs; a.out = out;
   const int64_t Q = H * W;
   const dim3 grid((unsigned)((3 * N + 31) / 32), (unsigned)((Q + 32 * reni::SH_QT - 1) / (32 * reni::SH_QT)));
-  hipLaunchKernelGGL(reni::k_sh_reconstruct, grid, dim3(64), 0, (hipStream_t)stream, a);
-  return hip_status();
+  return tu_launch(TU_PLAIN, reni::k_sh_reconstruct, grid, dim3(64), 0, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

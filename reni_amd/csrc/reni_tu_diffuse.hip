@@ -21,8 +21,9 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
-#include "reni_sphere.inc"  // tile constants, result-row map, drain, split rule, workspace check
+#include "reni_sphere.inc"  // tile constants, result-row map, drain, split rule
 
 namespace reni {
 
@@ -174,7 +175,6 @@ __global__ void __launch_bounds__(256) k_sh_irradiance_l2(int64_t N, int64_t P, 
 
 namespace {
 
-using reni::hip_status;
 using reni::reni_set_error;
 
 bool df_shape_ok(int64_t N, int64_t P, int64_t Q) {
@@ -214,24 +214,17 @@ int reni_diffuse_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs
   dg_split(P, Q, S, chunk);
   a.chunk = (int)chunk;
   if (S > 1) {
-    if (int rc = dg_check_ws("diffuse convolve", ws, ws_bytes, (size_t)df_ws_bytes(N, P, Q))) return rc;
+    if (int rc = tu_check_ws("diffuse convolve", ws, ws_bytes, (size_t)df_ws_bytes(N, P, Q))) return rc;
     a.ws = (float*)ws;
   }
   hipStream_t s = (hipStream_t)stream;
   const unsigned gx = (unsigned)((P + reni::DG_ROWS - 1) / reni::DG_ROWS);
-  if (3 * N <= 32) {
-    hipLaunchKernelGGL(reni::k_diffuse_convolve<1>, dim3(gx, (unsigned)((3 * N + 31) / 32), (unsigned)S), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(reni::k_diffuse_convolve<2>, dim3(gx, (unsigned)((3 * N + 63) / 64), (unsigned)S), dim3(256), 0, s, a);
-  }
-  if (int rc = hip_status()) return rc;
-  if (S > 1) {
-    const int64_t total = 3 * N * P;
-    hipLaunchKernelGGL(reni::k_diffuse_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)a.ws, total,
-                       (int)S, out);
-    return hip_status();
-  }
-  return RENI_OK;
+  const bool one = 3 * N <= 32;  // one 32-column group per workgroup, else two
+  const dim3 grid(gx, (unsigned)(one ? (3 * N + 31) / 32 : (3 * N + 63) / 64), (unsigned)S);
+  if (int rc = tu_launch(TU_PLAIN, one ? reni::k_diffuse_convolve<1> : reni::k_diffuse_convolve<2>, grid, dim3(256), 0, s, a)) return rc;
+  if (S == 1) return RENI_OK;
+  const int64_t total = 3 * N * P;
+  return tu_launch(TU_PLAIN, reni::k_diffuse_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.ws, total, (int)S, out);
 }
 
 int reni_sh_irradiance_l2(int64_t N, int64_t P, const float* coeffs, const float* normals, int64_t normals_stride_n, float* out,
@@ -241,9 +234,8 @@ int reni_sh_irradiance_l2(int64_t N, int64_t P, const float* coeffs, const float
   if (normals_stride_n != 0 && normals_stride_n != 3 * P)
     return reni_set_error(RENI_EINVAL, "sh irradiance: the normals' map stride must be 0 (shared) or 3 P (per map)");
   if (!coeffs || !normals || !out) return reni_set_error(RENI_EINVAL, "sh irradiance: NULL argument");
-  hipLaunchKernelGGL(reni::k_sh_irradiance_l2, dim3((unsigned)((N * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, P,
-                     coeffs, normals, normals_stride_n, out);
-  return hip_status();
+  return tu_launch(TU_PLAIN, reni::k_sh_irradiance_l2, dim3((unsigned)((N * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, P,
+                   coeffs, normals, normals_stride_n, out);
 }
 
 }  // extern "C"

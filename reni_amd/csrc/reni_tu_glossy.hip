@@ -31,6 +31,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
 #pragma clang fp contract(off)
 
@@ -260,8 +261,8 @@ __global__ void __launch_bounds__(256) k_envmap_lookup(const LkArgs a) {
 
 namespace {
 
-using reni::hip_status;
 using reni::reni_set_error;
+
 int64_t lb_ws_bytes(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
   int64_t S, chunk;
   dg_split(P, Q, S, chunk);
@@ -269,17 +270,14 @@ int64_t lb_ws_bytes(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
 }
 
 template <int KIND>
-void lb_launch(const reni::LbArgs& a, hipStream_t s) {
+int lb_launch(TuCount count, const reni::LbArgs& a, hipStream_t s) {
   const unsigned gx = (unsigned)((a.P + reni::DG_ROWS - 1) / reni::DG_ROWS), gz = (unsigned)(a.nl * a.S);
-  if (a.ncol <= 32) {
-    hipLaunchKernelGGL((reni::k_lobe_convolve<KIND, 1>), dim3(gx, 1, gz), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((reni::k_lobe_convolve<KIND, 2>), dim3(gx, (unsigned)((a.ncol + 63) / 64), gz), dim3(256), 0, s, a);
-  }
+  if (a.ncol <= 32) return tu_launch(count, reni::k_lobe_convolve<KIND, 1>, dim3(gx, 1, gz), dim3(256), 0, s, a);
+  return tu_launch(count, reni::k_lobe_convolve<KIND, 2>, dim3(gx, (unsigned)((a.ncol + 63) / 64), gz), dim3(256), 0, s, a);
 }
 
-// one launch per kind present, its lobes along z
-int lb_launch_kinds(reni::LbArgs& a, int n_lobes, const int32_t* kinds, const float* params, hipStream_t s) {
+// one launch per kind present, its lobes along z; counted or not as the caller's other launches are
+int lb_launch_kinds(TuCount count, reni::LbArgs& a, int n_lobes, const int32_t* kinds, const float* params, hipStream_t s) {
   for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind) {
     a.nl = 0;
     for (int l = 0; l < n_lobes; ++l) {
@@ -289,10 +287,10 @@ int lb_launch_kinds(reni::LbArgs& a, int n_lobes, const int32_t* kinds, const fl
       ++a.nl;
     }
     if (!a.nl) continue;
-    if (kind == RENI_LOBE_PHONG) lb_launch<RENI_LOBE_PHONG>(a, s);
-    else if (kind == RENI_LOBE_BLINN) lb_launch<RENI_LOBE_BLINN>(a, s);
-    else lb_launch<RENI_LOBE_GGX>(a, s);
-    if (int rc = hip_status()) return rc;
+    const int rc = kind == RENI_LOBE_PHONG   ? lb_launch<RENI_LOBE_PHONG>(count, a, s)
+                   : kind == RENI_LOBE_BLINN ? lb_launch<RENI_LOBE_BLINN>(count, a, s)
+                                             : lb_launch<RENI_LOBE_GGX>(count, a, s);
+    if (rc) return rc;
   }
   return RENI_OK;
 }
@@ -323,7 +321,7 @@ int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, c
   if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
   if (src_stride_n < 0 || src_stride_i < 0 || src_stride_c < 0)
     return reni_set_error(RENI_EINVAL, "lobe convolve: src strides must be >= 0");
-  if (int rc = dg_check_ws("lobe convolve", ws, ws_bytes, (size_t)lb_ws_bytes(N, P, Q, n_lobes))) return rc;
+  if (int rc = tu_check_ws("lobe convolve", ws, ws_bytes, (size_t)lb_ws_bytes(N, P, Q, n_lobes))) return rc;
   reni::LbArgs a = {};
   a.N = (int)N; a.P = (int)P; a.Q = (int)Q;
   a.ncol = (int)(3 * N + (normalise ? 1 : 0));
@@ -335,11 +333,10 @@ int reni_lobe_convolve(int64_t N, int64_t P, int64_t Q, const float* out_dirs, c
   a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
   a.ws = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = lb_launch_kinds(a, n_lobes, kinds, params, s)) return rc;
+  if (int rc = lb_launch_kinds(TU_PLAIN, a, n_lobes, kinds, params, s)) return rc;
   const int64_t total = (int64_t)n_lobes * N * P;
-  hipLaunchKernelGGL(reni::k_lobe_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)a.ws, (int)N,
-                     n_lobes, (int)P, a.ncol, (int)S, normalise ? 1 : 0, out);
-  return hip_status();
+  return tu_launch(TU_PLAIN, reni::k_lobe_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a.ws, (int)N, n_lobes, (int)P,
+                   a.ncol, (int)S, normalise ? 1 : 0, out);
 }
 
 size_t reni_lobe_denominators_workspace_bytes(int64_t P, int64_t Q, int64_t n_lobes) {
@@ -359,7 +356,7 @@ int reni_lobe_denominators(int64_t P, int64_t Q, const float* out_dirs, const fl
   if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
   int64_t S, chunk;
   dg_split(P, Q, S, chunk);
-  if (int rc = dg_check_ws("lobe denominators", ws, ws_bytes, (size_t)(S * n_lobes * P * (int64_t)sizeof(float)))) return rc;
+  if (int rc = tu_check_ws("lobe denominators", ws, ws_bytes, (size_t)(S * n_lobes * P * (int64_t)sizeof(float)))) return rc;
   // the forward's own launch without maps: the column of ones is column 0 of one 32-column group, and a column's sums do not
   // depend on the columns beside it.  The kernel loads a map's value in every lane and drops it where there is no map: in_w
   // stands in for the maps it reads ([Q] floats, texel stride 1).
@@ -372,15 +369,9 @@ int reni_lobe_denominators(int64_t P, int64_t Q, const float* out_dirs, const fl
   a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
   a.ws = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = lb_launch_kinds(a, n_lobes, kinds, params, s)) return rc;
-  int present = 0;
-  for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind)
-    for (int l = 0; l < n_lobes; ++l)
-      if (kinds[l] == kind) { ++present; break; }
-  reni::note_launches(present + 1);
-  hipLaunchKernelGGL(reni::k_lobe_den_finish, dim3((unsigned)((n_lobes * P + 255) / 256)), dim3(256), 0, s, (const float*)a.ws,
-                     n_lobes, (int)P, (int)S, den);
-  return hip_status();
+  if (int rc = lb_launch_kinds(TU_COUNTED, a, n_lobes, kinds, params, s)) return rc;
+  return tu_launch(TU_COUNTED, reni::k_lobe_den_finish, dim3((unsigned)((n_lobes * P + 255) / 256)), dim3(256), 0, s, a.ws, n_lobes,
+                   (int)P, (int)S, den);
 }
 
 int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* src, const int64_t src_strides[5],
@@ -391,8 +382,7 @@ int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, c
   if (N > 65535 || Lv > 65535 || H > 0x3fffffff / W || P > 0x3fffffff / 3 || N > 0x3fffffff / (3 * P))
     return reni_set_error(RENI_EINVAL, "lookup: need N, Lv <= 65535, H W < 2^30 and N P < 2^28");
   if (!src || !src_strides || !dirs || !out) return reni_set_error(RENI_EINVAL, "lookup: NULL argument");
-  for (int k = 0; k < 5; ++k)
-    if (src_strides[k] < 0) return reni_set_error(RENI_EINVAL, "lookup: src strides must be >= 0");
+  if (int rc = tu_check_strides("lookup", "src strides", src_strides, 5)) return rc;
   if (src_strides[2] > 0x7fffffff || src_strides[3] > 0x7fffffff)
     return reni_set_error(RENI_EINVAL, "lookup: the row and column strides must be < 2^31 elements");
   if (dirs_stride_n != 0 && dirs_stride_n != 3 * P)
@@ -406,8 +396,7 @@ int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, c
   a.out = out;
   a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
   sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
-  hipLaunchKernelGGL(reni::k_envmap_lookup, dim3((unsigned)((P + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream, a);
-  return reni::hip_status();
+  return tu_launch(TU_PLAIN, reni::k_envmap_lookup, dim3((unsigned)((P + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

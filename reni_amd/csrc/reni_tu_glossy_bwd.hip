@@ -29,6 +29,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
 #pragma clang fp contract(off)
 
@@ -271,7 +272,6 @@ __global__ void __launch_bounds__(256) k_envmap_lookup_bwd(const float* __restri
 
 namespace {
 
-using reni::hip_status;
 using reni::reni_set_error;
 
 size_t lbt_align(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -284,15 +284,10 @@ size_t lbt_ws_bytes(int64_t N, int64_t P, int64_t Q, int64_t Lv) {
 }
 
 template <int KIND>
-void lbt_launch(const reni::LbtArgs& a, hipStream_t s) {
+int lbt_launch(TuCount count, const reni::LbtArgs& a, hipStream_t s) {
   const unsigned gx = (unsigned)((a.Q + reni::DG_ROWS - 1) / reni::DG_ROWS);
-  if (a.ncol <= 32) {
-    hipLaunchKernelGGL((reni::k_lobe_convolve_t<KIND, 1>), dim3(gx, 1, (unsigned)a.S), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((reni::k_lobe_convolve_t<KIND, 2>), dim3(gx, (unsigned)((a.ncol + 63) / 64), (unsigned)a.S), dim3(256), 0,
-                       s, a);
-  }
-  reni::note_launches(1);
+  if (a.ncol <= 32) return tu_launch(count, reni::k_lobe_convolve_t<KIND, 1>, dim3(gx, 1, (unsigned)a.S), dim3(256), 0, s, a);
+  return tu_launch(count, reni::k_lobe_convolve_t<KIND, 2>, dim3(gx, (unsigned)((a.ncol + 63) / 64), (unsigned)a.S), dim3(256), 0, s, a);
 }
 
 int lk_check_sizes(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, int64_t T) {
@@ -327,15 +322,14 @@ int reni_lobe_convolve_backward(int64_t N, int64_t P, int64_t Q, const float* ou
   if (int rc = lb_check_lobes(n_lobes, kinds, params)) return rc;
   if (grad_stride_n < 0 || grad_stride_i < 0 || grad_stride_c < 0)
     return reni_set_error(RENI_EINVAL, "lobe convolve backward: grad_src strides must be >= 0");
-  if (int rc = dg_check_ws("lobe convolve backward", ws, ws_bytes, lbt_ws_bytes(N, P, Q, n_lobes))) return rc;
+  if (int rc = tu_check_ws("lobe convolve backward", ws, ws_bytes, lbt_ws_bytes(N, P, Q, n_lobes))) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* r = (float*)ws;
   float* slabs = (float*)((char*)ws + lbt_align((size_t)(n_lobes * P) * sizeof(float)));
   const int64_t rtotal = (int64_t)n_lobes * P;
-  hipLaunchKernelGGL(reni::k_lobe_recip, dim3((unsigned)((rtotal + 255) / 256)), dim3(256), 0, s, normalise ? den : nullptr, rtotal,
-                     scale, r);
-  reni::note_launches(1);
-  if (int rc = hip_status()) return rc;
+  if (int rc = tu_launch(TU_COUNTED, reni::k_lobe_recip, dim3((unsigned)((rtotal + 255) / 256)), dim3(256), 0, s,
+                         normalise ? den : nullptr, rtotal, scale, r))
+    return rc;
   reni::LbtArgs a = {};
   a.P = (int)P; a.Q = (int)Q;
   a.ncol = (int)(3 * N);
@@ -355,17 +349,15 @@ int reni_lobe_convolve_backward(int64_t N, int64_t P, int64_t Q, const float* ou
     }
     if (!a.nl) continue;
     a.ws = slabs + (int64_t)nslab * (3 * N) * Q;
-    if (kind == RENI_LOBE_PHONG) lbt_launch<RENI_LOBE_PHONG>(a, s);
-    else if (kind == RENI_LOBE_BLINN) lbt_launch<RENI_LOBE_BLINN>(a, s);
-    else lbt_launch<RENI_LOBE_GGX>(a, s);
-    if (int rc = hip_status()) return rc;
+    const int rc = kind == RENI_LOBE_PHONG   ? lbt_launch<RENI_LOBE_PHONG>(TU_COUNTED, a, s)
+                   : kind == RENI_LOBE_BLINN ? lbt_launch<RENI_LOBE_BLINN>(TU_COUNTED, a, s)
+                                             : lbt_launch<RENI_LOBE_GGX>(TU_COUNTED, a, s);
+    if (rc) return rc;
     nslab += (int)S;
   }
   const int64_t total = N * Q;
-  hipLaunchKernelGGL(reni::k_lobe_finish_t, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)slabs, in_w, (int)N,
-                     (int)Q, nslab, grad_src, grad_stride_n, grad_stride_i, grad_stride_c);
-  reni::note_launches(1);
-  return hip_status();
+  return tu_launch(TU_COUNTED, reni::k_lobe_finish_t, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, slabs, in_w, (int)N, (int)Q,
+                   nslab, grad_src, grad_stride_n, grad_stride_i, grad_stride_c);
 }
 
 int reni_envmap_lookup_taps(int64_t n_tables, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* dirs, int64_t dirs_stride_n,
@@ -382,10 +374,8 @@ int reni_envmap_lookup_taps(int64_t n_tables, int64_t Lv, int64_t H, int64_t W, 
   a.idx = tap_index; a.wgt = tap_weight;
   a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
   sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
-  hipLaunchKernelGGL(reni::k_envmap_lookup_taps, dim3((unsigned)((P + 255) / 256), (unsigned)n_tables), dim3(256), 0,
-                     (hipStream_t)stream, a);
-  reni::note_launches(1);
-  return reni::hip_status();
+  return tu_launch(TU_COUNTED, reni::k_envmap_lookup_taps, dim3((unsigned)((P + 255) / 256), (unsigned)n_tables), dim3(256), 0,
+                   (hipStream_t)stream, a);
 }
 
 int reni_envmap_lookup_backward(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* grad_out, int64_t n_tables,
@@ -395,10 +385,8 @@ int reni_envmap_lookup_backward(int64_t N, int64_t Lv, int64_t H, int64_t W, int
   if (!grad_out || !grad_src) return reni_set_error(RENI_EINVAL, "lookup backward: NULL argument");
   if (!tap_weight || !tap_order || !offsets) return reni_set_error(RENI_EINVAL, "lookup backward: NULL tap table, order or offsets");
   const int64_t E = Lv * H * W;
-  hipLaunchKernelGGL(reni::k_envmap_lookup_bwd, dim3((unsigned)((E + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream,
-                     grad_out, tap_weight, tap_order, offsets, E, P, (int)n_tables, grad_src);
-  reni::note_launches(1);
-  return reni::hip_status();
+  return tu_launch(TU_COUNTED, reni::k_envmap_lookup_bwd, dim3((unsigned)((E + 255) / 256), (unsigned)N), dim3(256), 0,
+                   (hipStream_t)stream, grad_out, tap_weight, tap_order, offsets, E, P, (int)n_tables, grad_src);
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@
 #include "reni_hip.h"
 #include "reni_internal.h"
 #include "reni_dev_image.inc"
+#include "reni_tu_host.inc"
 
 #define DEV __device__ __forceinline__
 
@@ -234,8 +235,8 @@ int reni_unnormalise_srgb(int64_t B, int64_t H, int64_t W, const float* img, con
   if (srgb && !out_srgb) return reni_set_error(RENI_EINVAL, "image: sRGB requested but out_srgb is NULL");
   if (!srgb && !out_linear) return reni_set_error(RENI_EINVAL, "image: nothing to compute");
   if (srgb && (H > reni::QMAX || W > reni::QMAX)) return reni_set_error(RENI_EUNSUPPORTED, "image: quantile axis longer than 4096");
-  if (srgb && (!ws || ws_bytes < reni_image_workspace_bytes(B, H, W) || ((uintptr_t)ws & 255)))
-    return reni_set_error(RENI_EWORKSPACE, "image: workspace missing, too small or not 256-byte aligned");
+  if (srgb)
+    if (int rc = tu_check_ws("image", ws, ws_bytes, reni_image_workspace_bytes(B, H, W))) return rc;
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)ws;
   reni::ImgArgs a;
@@ -256,22 +257,18 @@ int reni_unnormalise_srgb(int64_t B, int64_t H, int64_t W, const float* img, con
     q3 = (float*)(w + o);
   }
   const long long npix = (long long)B * H * W;
-  hipLaunchKernelGGL(reni::k_img_pass1, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a);
-  reni::note_launches(1);
-  if (srgb) {
-    // over H (dim 1 of [B,H,W]) -> [B,W]; then over W (dim 1 of [B,W]) -> [B]
-    hipLaunchKernelGGL(reni::k_img_quantile, dim3((unsigned)(B * W)), dim3(256), 0, s, (const float*)a.q1, (int)H, (long long)W,
-                       (int)W, (long long)H * W, 1LL, a.qf, q2);
-    reni::note_launches(1);
-    hipLaunchKernelGGL(reni::k_img_quantile, dim3((unsigned)B), dim3(256), 0, s, (const float*)q2, (int)W, 1LL, 1, (long long)W, 0LL,
-                       a.qf, q3);
-    reni::note_launches(1);
-    a.q = q3;
-    const long long n = npix * 3;
-    hipLaunchKernelGGL(reni::k_img_pass2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-    reni::note_launches(1);
-  }
-  return reni::hip_status();
+  if (int rc = tu_launch(TU_COUNTED, reni::k_img_pass1, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, a)) return rc;
+  if (!srgb) return RENI_OK;
+  // over H (dim 1 of [B,H,W]) -> [B,W]; then over W (dim 1 of [B,W]) -> [B]
+  if (int rc = tu_launch(TU_COUNTED, reni::k_img_quantile, dim3((unsigned)(B * W)), dim3(256), 0, s, a.q1, (int)H, (long long)W,
+                         (int)W, (long long)H * W, 1LL, a.qf, q2))
+    return rc;
+  if (int rc = tu_launch(TU_COUNTED, reni::k_img_quantile, dim3((unsigned)B), dim3(256), 0, s, q2, (int)W, 1LL, 1, (long long)W, 0LL,
+                         a.qf, q3))
+    return rc;
+  a.q = q3;
+  const long long n = npix * 3;
+  return tu_launch(TU_COUNTED, reni::k_img_pass2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
 }
 
 int reni_minmax_normalise(int64_t n, const float* img, double minmax0, double minmax1, float* out, void* ws, size_t ws_bytes,
@@ -282,15 +279,12 @@ int reni_minmax_normalise(int64_t n, const float* img, double minmax0, double mi
   if (!(minmax1 > minmax0)) return reni_set_error(RENI_EINVAL, "normalise: minmax[1] must exceed minmax[0]");
   hipStream_t s = (hipStream_t)stream;
   unsigned* mm = (unsigned*)ws;
-  hipLaunchKernelGGL(reni::k_img_minmax_init, dim3(1), dim3(1), 0, s, mm);
-  reni::note_launches(1);
+  if (int rc = tu_launch(TU_COUNTED, reni::k_img_minmax_init, dim3(1), dim3(1), 0, s, mm)) return rc;
   const long long nb = (n + 255) / 256;
-  hipLaunchKernelGGL(reni::k_img_minmax, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s, img, (long long)n, mm);
-  reni::note_launches(1);
-  hipLaunchKernelGGL(reni::k_img_normalise, dim3((unsigned)nb), dim3(256), 0, s, img, (long long)n, (const unsigned*)mm, (float)minmax0,
-                     (float)(minmax1 - minmax0), out);
-  reni::note_launches(1);
-  return reni::hip_status();
+  if (int rc = tu_launch(TU_COUNTED, reni::k_img_minmax, dim3((unsigned)(nb < 2048 ? nb : 2048)), dim3(256), 0, s, img, (long long)n, mm))
+    return rc;
+  return tu_launch(TU_COUNTED, reni::k_img_normalise, dim3((unsigned)nb), dim3(256), 0, s, img, (long long)n, mm, (float)minmax0,
+                   (float)(minmax1 - minmax0), out);
 }
 
 size_t reni_minmax_batch_workspace_bytes(int64_t N) { return N < 1 || N > 65535 ? 0 : (size_t)N * 8 + 256; }
@@ -300,19 +294,17 @@ int reni_minmax_normalise_batch(int64_t N, int64_t n, const float* imgs, double 
   if (N < 1 || N > 65535 || n < 1 || n > 0x3fffffffLL) return reni_set_error(RENI_EINVAL, "normalise batch: need 1 <= N <= 65535, 1 <= n < 2^30");
   if (!imgs || !out) return reni_set_error(RENI_EINVAL, "normalise batch: NULL argument");
   if (!(minmax1 > minmax0)) return reni_set_error(RENI_EINVAL, "normalise batch: minmax[1] must exceed minmax[0]");
-  if (!ws || ws_bytes < (size_t)N * 8 || ((uintptr_t)ws & 255))
-    return reni_set_error(RENI_EWORKSPACE, "normalise batch: workspace missing, too small or not 256-byte aligned");
+  if (int rc = tu_check_ws("normalise batch", ws, ws_bytes, (size_t)N * 8)) return rc;
   hipStream_t s = (hipStream_t)stream;
   unsigned* mm = (unsigned*)ws;
-  hipLaunchKernelGGL(reni::k_img_minmax_init_batch, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, mm, (int)N);
-  reni::note_launches(1);
+  if (int rc = tu_launch(TU_COUNTED, reni::k_img_minmax_init_batch, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, mm, (int)N))
+    return rc;
   const long long nb = (n + 255) / 256;
-  hipLaunchKernelGGL(reni::k_img_minmax_batch, dim3((unsigned)(nb < 128 ? nb : 128), (unsigned)N), dim3(256), 0, s, imgs, (long long)n, mm);
-  reni::note_launches(1);
-  hipLaunchKernelGGL(reni::k_img_normalise_batch, dim3((unsigned)nb, (unsigned)N), dim3(256), 0, s, imgs, (long long)n,
-                     (const unsigned*)mm, (float)minmax0, (float)(minmax1 - minmax0), nan_to_num ? 1 : 0, out);
-  reni::note_launches(1);
-  return reni::hip_status();
+  if (int rc = tu_launch(TU_COUNTED, reni::k_img_minmax_batch, dim3((unsigned)(nb < 128 ? nb : 128), (unsigned)N), dim3(256), 0, s, imgs,
+                         (long long)n, mm))
+    return rc;
+  return tu_launch(TU_COUNTED, reni::k_img_normalise_batch, dim3((unsigned)nb, (unsigned)N), dim3(256), 0, s, imgs, (long long)n, mm,
+                   (float)minmax0, (float)(minmax1 - minmax0), nan_to_num ? 1 : 0, out);
 }
 
 }  // extern "C"

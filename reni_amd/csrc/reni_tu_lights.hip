@@ -23,11 +23,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "reni_hip.h"
 #include "reni_internal.h"
 #include "reni_dev_image.inc"
+#include "reni_tu_host.inc"
 
 #pragma clang fp contract(off)
 
@@ -378,7 +378,6 @@ __global__ void __launch_bounds__(256) k_lights_irradiance(int P, int S, const f
 
 namespace {
 
-using reni::hip_status;
 using reni::reni_set_error;
 
 constexpr int64_t LT_MAX_ELEMS = (int64_t)1 << 28;  // B S and B P stay below this (3 B S fits an int with room to spare)
@@ -389,17 +388,12 @@ bool lt_shape_ok(int64_t B, int64_t H, int64_t W) {
 
 // the checks of an image argument that the table and the sampler share
 int lt_check_image(const char* what, const float* img, const int64_t* st, int32_t space, double m0, double m1) {
-  static thread_local char msg[160];
-  auto fail = [&](const char* text) {
-    snprintf(msg, sizeof msg, "%s: %s", what, text);
-    return reni_set_error(RENI_EINVAL, msg);
-  };
-  if (!img || !st) return fail("NULL argument");
-  for (int k = 0; k < 4; ++k)
-    if (st[k] < 0) return fail("image strides must be >= 0");
-  if (space == RENI_SPACE_SRGB) return fail("RENI_SPACE_SRGB is a display space, not radiance: use RENI_SPACE_STORED or RENI_SPACE_LINEAR");
-  if (space != RENI_SPACE_STORED && space != RENI_SPACE_LINEAR) return fail("unknown space");
-  if (space == RENI_SPACE_LINEAR && !(m1 > m0)) return fail("minmax[1] must exceed minmax[0] in RENI_SPACE_LINEAR");
+  if (!img || !st) return tu_fail(RENI_EINVAL, what, "NULL argument");
+  if (int rc = tu_check_strides(what, "image strides", st, 4)) return rc;
+  if (space == RENI_SPACE_SRGB)
+    return tu_fail(RENI_EINVAL, what, "RENI_SPACE_SRGB is a display space, not radiance: use RENI_SPACE_STORED or RENI_SPACE_LINEAR");
+  if (space != RENI_SPACE_STORED && space != RENI_SPACE_LINEAR) return tu_fail(RENI_EINVAL, what, "unknown space");
+  if (space == RENI_SPACE_LINEAR && !(m1 > m0)) return tu_fail(RENI_EINVAL, what, "minmax[1] must exceed minmax[0] in RENI_SPACE_LINEAR");
   return RENI_OK;
 }
 
@@ -422,11 +416,9 @@ int reni_light_table_build(int64_t B, int64_t H, int64_t W, const float* img, co
   if (int rc = lt_check_image("light table", img, img_strides, space, minmax0, minmax1)) return rc;
   if (!solid_angle || !pmf || !cond || !marg) return reni_set_error(RENI_EINVAL, "light table: NULL argument");
   if (mask && !mask_strides) return reni_set_error(RENI_EINVAL, "light table: NULL argument (a mask needs its strides)");
-  for (int k = 0; mask && k < 3; ++k)
-    if (mask_strides[k] < 0) return reni_set_error(RENI_EINVAL, "light table: mask strides must be >= 0");
+  if (int rc = tu_check_strides("light table", "mask strides", mask_strides, mask ? 3 : 0)) return rc;
   if (!(uniform_mix >= 0.0 && uniform_mix <= 1.0)) return reni_set_error(RENI_EINVAL, "light table: uniform_mix must lie in [0, 1]");
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < (size_t)lt_ws_doubles(B, H) * sizeof(double))
-    return reni_set_error(RENI_EWORKSPACE, "light table: workspace missing, too small or not 256-byte aligned");
+  if (int rc = tu_check_ws("light table", ws, ws_bytes, (size_t)lt_ws_doubles(B, H) * sizeof(double))) return rc;
   reni::LtArgs a = {};
   a.img = img;
   for (int k = 0; k < 4; ++k) a.s[k] = img_strides[k];
@@ -441,17 +433,10 @@ int reni_light_table_build(int64_t B, int64_t H, int64_t W, const float* img, co
   a.par = a.rowf + B * H;
   hipStream_t s = (hipStream_t)stream;
   const dim3 rows((unsigned)H, (unsigned)B);
-  if (space == RENI_SPACE_STORED) hipLaunchKernelGGL(reni::k_lt_rows<RENI_SPACE_STORED>, rows, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(reni::k_lt_rows<RENI_SPACE_LINEAR>, rows, dim3(256), 0, s, a);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  hipLaunchKernelGGL(reni::k_lt_image, dim3((unsigned)B), dim3(256), 0, s, a);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  hipLaunchKernelGGL(reni::k_lt_cdf, rows, dim3(256), 0, s, a);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  return RENI_OK;
+  const auto k = space == RENI_SPACE_STORED ? reni::k_lt_rows<RENI_SPACE_STORED> : reni::k_lt_rows<RENI_SPACE_LINEAR>;
+  if (int rc = tu_launch(TU_COUNTED, k, rows, dim3(256), 0, s, a)) return rc;
+  if (int rc = tu_launch(TU_COUNTED, reni::k_lt_image, dim3((unsigned)B), dim3(256), 0, s, a)) return rc;
+  return tu_launch(TU_COUNTED, reni::k_lt_cdf, rows, dim3(256), 0, s, a);
 }
 
 int reni_light_sample(int64_t B, int64_t H, int64_t W, int64_t S, const float* pmf, const float* cond, const float* marg,
@@ -481,11 +466,8 @@ int reni_light_sample(int64_t B, int64_t H, int64_t W, int64_t S, const float* p
   a.index = index; a.dirs = dirs; a.pdf = pdf; a.radiance = radiance; a.colors = colors;
   const dim3 grid((unsigned)((S + 255) / 256), (unsigned)B);
   hipStream_t s = (hipStream_t)stream;
-  if (space == RENI_SPACE_STORED) hipLaunchKernelGGL(reni::k_light_sample<RENI_SPACE_STORED>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(reni::k_light_sample<RENI_SPACE_LINEAR>, grid, dim3(256), 0, s, a);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  return RENI_OK;
+  const auto k = space == RENI_SPACE_STORED ? reni::k_light_sample<RENI_SPACE_STORED> : reni::k_light_sample<RENI_SPACE_LINEAR>;
+  return tu_launch(TU_COUNTED, k, grid, dim3(256), 0, s, a);
 }
 
 int reni_lights_irradiance(int64_t B, int64_t P, int64_t S, const float* normals, int64_t normals_stride_b, const float* dirs,
@@ -495,11 +477,8 @@ int reni_lights_irradiance(int64_t B, int64_t P, int64_t S, const float* normals
   if (normals_stride_b != 0 && normals_stride_b != 3 * P)
     return reni_set_error(RENI_EINVAL, "lights irradiance: the normals' image stride must be 0 (shared) or 3 P (per image)");
   if (!normals || !dirs || !colors || !out) return reni_set_error(RENI_EINVAL, "lights irradiance: NULL argument");
-  hipLaunchKernelGGL(reni::k_lights_irradiance, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                     (int)P, (int)S, normals, normals_stride_b, dirs, colors, scale, out);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  return RENI_OK;
+  return tu_launch(TU_COUNTED, reni::k_lights_irradiance, dim3((unsigned)((P + 255) / 256), (unsigned)B), dim3(256), 0,
+                   (hipStream_t)stream, (int)P, (int)S, normals, normals_stride_b, dirs, colors, scale, out);
 }
 
 }  // extern "C"

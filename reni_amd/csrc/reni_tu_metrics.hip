@@ -21,11 +21,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "reni_hip.h"
 #include "reni_internal.h"
 #include "reni_dev_image.inc"
+#include "reni_tu_host.inc"
 
 #pragma clang fp contract(off)
 
@@ -311,7 +311,6 @@ __global__ void __launch_bounds__(64) k_finish(const float* __restrict__ part, i
 
 namespace {
 
-using reni::hip_status;
 using reni::reni_set_error;
 
 int64_t ps_blocks(int64_t H, int64_t W) { return (H * W + reni::PS_CHUNK - 1) / reni::PS_CHUNK; }
@@ -323,21 +322,16 @@ bool met_shape_ok(int64_t B, int64_t H, int64_t W) { return B >= 1 && B <= 65535
 int met_check(const char* what, int64_t B, int64_t H, int64_t W, const float* pred, const int64_t* ps, const float* target,
               const int64_t* ts, const float* weight, const int64_t* wst, int32_t space, double m0, double m1,
               const float* exposure, const void* out) {
-  static thread_local char msg[160];
-  auto fail = [&](const char* text) {
-    snprintf(msg, sizeof msg, "%s: %s", what, text);
-    return reni_set_error(RENI_EINVAL, msg);
-  };
-  if (!met_shape_ok(B, H, W)) return fail("need 1 <= B <= 65535, H, W >= 1 and H W < 2^30");
-  if (!pred || !ps || !target || !ts || !out) return fail("NULL argument");
-  if (weight && !wst) return fail("NULL argument (a weight needs its strides)");
-  for (int k = 0; k < 4; ++k)
-    if (ps[k] < 0 || ts[k] < 0) return fail("image strides must be >= 0");
-  for (int k = 0; weight && k < 3; ++k)
-    if (wst[k] < 0) return fail("weight strides must be >= 0");
-  if (space != RENI_SPACE_STORED && space != RENI_SPACE_LINEAR && space != RENI_SPACE_SRGB) return fail("unknown space");
-  if (space != RENI_SPACE_STORED && !(m1 > m0)) return fail("minmax[1] must exceed minmax[0] in a mapped space");
-  if (space == RENI_SPACE_SRGB && !exposure) return fail("NULL argument (RENI_SPACE_SRGB needs the exposures)");
+  if (!met_shape_ok(B, H, W)) return tu_fail(RENI_EINVAL, what, "need 1 <= B <= 65535, H, W >= 1 and H W < 2^30");
+  if (!pred || !ps || !target || !ts || !out) return tu_fail(RENI_EINVAL, what, "NULL argument");
+  if (weight && !wst) return tu_fail(RENI_EINVAL, what, "NULL argument (a weight needs its strides)");
+  if (int rc = tu_check_strides(what, "image strides", ps, 4)) return rc;
+  if (int rc = tu_check_strides(what, "image strides", ts, 4)) return rc;
+  if (int rc = tu_check_strides(what, "weight strides", wst, weight ? 3 : 0)) return rc;
+  if (space != RENI_SPACE_STORED && space != RENI_SPACE_LINEAR && space != RENI_SPACE_SRGB)
+    return tu_fail(RENI_EINVAL, what, "unknown space");
+  if (space != RENI_SPACE_STORED && !(m1 > m0)) return tu_fail(RENI_EINVAL, what, "minmax[1] must exceed minmax[0] in a mapped space");
+  if (space == RENI_SPACE_SRGB && !exposure) return tu_fail(RENI_EINVAL, what, "NULL argument (RENI_SPACE_SRGB needs the exposures)");
   return RENI_OK;
 }
 
@@ -369,23 +363,18 @@ int reni_pair_stats(int64_t B, int64_t H, int64_t W, const float* pred, const in
                          minmax0, minmax1, exposure, out))
     return rc;
   const int64_t nblk = ps_blocks(H, W);
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < (size_t)(B * nblk * 8) * sizeof(float))
-    return reni_set_error(RENI_EWORKSPACE, "pair stats: workspace missing, too small or not 256-byte aligned");
+  if (int rc = tu_check_ws("pair stats", ws, ws_bytes, (size_t)(B * nblk * 8) * sizeof(float))) return rc;
   reni::MetArgs a = {};
   met_fill(a, H, W, pred, pred_strides, target, target_strides, weight, weight_strides, minmax0, minmax1, exposure);
   a.nblk = (int)nblk;
   a.part = (float*)ws;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)nblk, (unsigned)B);
-  if (space == RENI_SPACE_STORED) hipLaunchKernelGGL(reni::k_pair_stats<RENI_SPACE_STORED>, grid, dim3(256), 0, s, a);
-  else if (space == RENI_SPACE_LINEAR) hipLaunchKernelGGL(reni::k_pair_stats<RENI_SPACE_LINEAR>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(reni::k_pair_stats<RENI_SPACE_SRGB>, grid, dim3(256), 0, s, a);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  hipLaunchKernelGGL(reni::k_finish<8>, dim3((unsigned)B), dim3(64), 0, s, (const float*)a.part, a.nblk, out);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  return RENI_OK;
+  auto k = reni::k_pair_stats<RENI_SPACE_STORED>;
+  if (space == RENI_SPACE_LINEAR) k = reni::k_pair_stats<RENI_SPACE_LINEAR>;
+  if (space == RENI_SPACE_SRGB) k = reni::k_pair_stats<RENI_SPACE_SRGB>;
+  if (int rc = tu_launch(TU_COUNTED, k, grid, dim3(256), 0, s, a)) return rc;
+  return tu_launch(TU_COUNTED, reni::k_finish<8>, dim3((unsigned)B), dim3(64), 0, s, a.part, a.nblk, out);
 }
 
 int reni_ssim(int64_t B, int64_t H, int64_t W, const float* pred, const int64_t pred_strides[4], const float* target,
@@ -406,8 +395,7 @@ int reni_ssim(int64_t B, int64_t H, int64_t W, const float* pred, const int64_t 
     if (H < win || W < win) return reni_set_error(RENI_EINVAL, "ssim: the planar mode needs H, W >= 11 (one whole window)");
   }
   const int64_t tx = ss_tiles(W), nblk = tx * ss_tiles(H);
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < (size_t)(B * nblk * 2) * sizeof(float))
-    return reni_set_error(RENI_EWORKSPACE, "ssim: workspace missing, too small or not 256-byte aligned");
+  if (int rc = tu_check_ws("ssim", ws, ws_bytes, (size_t)(B * nblk * 2) * sizeof(float))) return rc;
   reni::MetArgs a = {};
   met_fill(a, H, W, pred, pred_strides, target, target_strides, weight, weight_strides, minmax0, minmax1, exposure);
   a.nblk = (int)nblk;
@@ -427,15 +415,11 @@ int reni_ssim(int64_t B, int64_t H, int64_t W, const float* pred, const int64_t 
   a.C2 = (float)((0.03 * (double)L) * (0.03 * (double)L));
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)nblk, (unsigned)B);
-  if (space == RENI_SPACE_STORED) hipLaunchKernelGGL(reni::k_ssim<RENI_SPACE_STORED>, grid, dim3(256), 0, s, a);
-  else if (space == RENI_SPACE_LINEAR) hipLaunchKernelGGL(reni::k_ssim<RENI_SPACE_LINEAR>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(reni::k_ssim<RENI_SPACE_SRGB>, grid, dim3(256), 0, s, a);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  hipLaunchKernelGGL(reni::k_finish<2>, dim3((unsigned)B), dim3(64), 0, s, (const float*)a.part, a.nblk, out);
-  if (int rc = hip_status()) return rc;
-  reni::note_launches(1);
-  return RENI_OK;
+  auto k = reni::k_ssim<RENI_SPACE_STORED>;
+  if (space == RENI_SPACE_LINEAR) k = reni::k_ssim<RENI_SPACE_LINEAR>;
+  if (space == RENI_SPACE_SRGB) k = reni::k_ssim<RENI_SPACE_SRGB>;
+  if (int rc = tu_launch(TU_COUNTED, k, grid, dim3(256), 0, s, a)) return rc;
+  return tu_launch(TU_COUNTED, reni::k_finish<2>, dim3((unsigned)B), dim3(64), 0, s, a.part, a.nblk, out);
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
 #define DEV __device__ __forceinline__
 
@@ -234,7 +235,6 @@ __global__ void __launch_bounds__(256) k_raster_tile(const RasterArgs a) {
 
 namespace {
 
-using reni::hip_status;
 using reni::reni_set_error;
 constexpr int64_t RS_MAX_ELEMS = 0x3fffffff;  // V, F; S * S
 
@@ -251,9 +251,8 @@ int reni_mesh_vertex_normals(int64_t V, int64_t F, const float* verts, const int
                              const int64_t* vf_corners, float* normals, void* stream) {
   if (V < 1 || F < 1 || V > RS_MAX_ELEMS || F > RS_MAX_ELEMS) return reni_set_error(RENI_EINVAL, "vertex normals: bad V / F");
   if (!verts || !faces || !vf_offsets || !vf_corners || !normals) return reni_set_error(RENI_EINVAL, "vertex normals: NULL argument");
-  hipLaunchKernelGGL(reni::k_vertex_normals, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)V, (int)F,
-                     verts, faces, vf_offsets, vf_corners, normals);
-  return hip_status();
+  return tu_launch(TU_PLAIN, reni::k_vertex_normals, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)V,
+                   (int)F, verts, faces, vf_offsets, vf_corners, normals);
 }
 
 int reni_rasterize_mesh(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* vert_normals,
@@ -266,25 +265,22 @@ int reni_rasterize_mesh(int64_t V, int64_t F, const float* verts, const int64_t*
       !pixel_positions)
     return reni_set_error(RENI_EINVAL, "rasterize: NULL argument");
   if (!(tan_half_fov > 0.f) || !isfinite(tan_half_fov)) return reni_set_error(RENI_EINVAL, "rasterize: tan_half_fov must be positive");
-  const size_t need = (size_t)F * sizeof(reni::FaceRec);
-  const uintptr_t wp = (uintptr_t)ws;
-  if (!ws || (wp & 255) || ws_bytes < need)
-    return reni_set_error(RENI_EWORKSPACE, "rasterize: workspace missing, too small or not 256-byte aligned");
+  if (int rc = tu_check_ws("rasterize", ws, ws_bytes, (size_t)F * sizeof(reni::FaceRec))) return rc;
   hipStream_t s = (hipStream_t)stream;
   reni::Camera cam;
   for (int i = 0; i < 9; ++i) cam.R[i] = R[i];
   for (int i = 0; i < 3; ++i) cam.T[i] = T[i];
   cam.tan_half_fov = tan_half_fov;
   reni::FaceRec* rec = (reni::FaceRec*)ws;
-  hipLaunchKernelGGL(reni::k_face_setup, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, (int)V, (int)F, verts, faces, cam, rec);
-  if (int rc = hip_status()) return rc;
+  if (int rc = tu_launch(TU_PLAIN, reni::k_face_setup, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, (int)V, (int)F, verts, faces,
+                         cam, rec))
+    return rc;
   reni::RasterArgs a;
   a.rec = rec; a.verts = verts; a.vnrm = vert_normals; a.faces = faces;
   a.pix_to_face = pix_to_face; a.zbuf = zbuf; a.bary = bary; a.dists = dists; a.gnrm = pixel_normals; a.gpos = pixel_positions;
   a.F = (int)F; a.S = (int)H;
   const unsigned tiles = (unsigned)((H + reni::RS_TILE - 1) / reni::RS_TILE);
-  hipLaunchKernelGGL(reni::k_raster_tile, dim3(tiles, tiles), dim3(256), 0, s, a);
-  return hip_status();
+  return tu_launch(TU_PLAIN, reni::k_raster_tile, dim3(tiles, tiles), dim3(256), 0, s, a);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
 #define DEV __device__ __forceinline__
 
@@ -103,7 +104,6 @@ __global__ void __launch_bounds__(256) k_blur_axis(const float* __restrict__ in,
 
 namespace {
 
-using reni::hip_status;
 using reni::reni_set_error;
 constexpr int64_t RS_MAX_PIXELS = 0x3fffffff;
 constexpr int64_t RS_MAX_RADIUS = 1 << 20;
@@ -126,8 +126,7 @@ int reni_resample(int64_t N, int64_t C, int64_t Hs, int64_t Ws, int64_t Hd, int6
     return reni_set_error(RENI_EINVAL, "resample: taps per axis must be 1..8");
   if (!src || !src_strides || !row_idx || !row_w || !col_idx || !col_w || !out)
     return reni_set_error(RENI_EINVAL, "resample: NULL argument");
-  for (int k = 0; k < 4; ++k)
-    if (src_strides[k] < 0) return reni_set_error(RENI_EINVAL, "resample: src strides must be >= 0");
+  if (int rc = tu_check_strides("resample", "src strides", src_strides, 4)) return rc;
   reni::RsArgs a = {};
   a.src = src; a.sn = src_strides[0]; a.sc = src_strides[1]; a.sy = src_strides[2]; a.sx = src_strides[3];
   a.out = out; a.row_idx = row_idx; a.row_w = row_w; a.col_idx = col_idx; a.col_w = col_w;
@@ -135,13 +134,12 @@ int reni_resample(int64_t N, int64_t C, int64_t Hs, int64_t Ws, int64_t Hd, int6
   const dim3 grid((unsigned)((Hd * Wd + 255) / 256), (unsigned)C, (unsigned)N);
   hipStream_t s = (hipStream_t)stream;
   switch (col_taps) {
-    case 1: hipLaunchKernelGGL(reni::k_resample<1>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(reni::k_resample<2>, grid, dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL(reni::k_resample<4>, grid, dim3(256), 0, s, a); break;
-    case 8: hipLaunchKernelGGL(reni::k_resample<8>, grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(reni::k_resample<0>, grid, dim3(256), 0, s, a); break;
+    case 1: return tu_launch(TU_PLAIN, reni::k_resample<1>, grid, dim3(256), 0, s, a);
+    case 2: return tu_launch(TU_PLAIN, reni::k_resample<2>, grid, dim3(256), 0, s, a);
+    case 4: return tu_launch(TU_PLAIN, reni::k_resample<4>, grid, dim3(256), 0, s, a);
+    case 8: return tu_launch(TU_PLAIN, reni::k_resample<8>, grid, dim3(256), 0, s, a);
+    default: return tu_launch(TU_PLAIN, reni::k_resample<0>, grid, dim3(256), 0, s, a);
   }
-  return hip_status();
 }
 
 size_t reni_blur_workspace_bytes(int64_t C, int64_t H, int64_t W) {
@@ -154,19 +152,16 @@ int reni_gaussian_blur(int64_t C, int64_t H, int64_t W, const float* src, const 
   if (!blur_shape_ok(C, H, W)) return reni_set_error(RENI_EINVAL, "blur: need C, H, W >= 1, C <= 65535 and C H W < 2^30");
   if (radius < 0 || radius > RS_MAX_RADIUS) return reni_set_error(RENI_EINVAL, "blur: radius must be 0..2^20");
   if (!src || !strides || !weights || !out) return reni_set_error(RENI_EINVAL, "blur: NULL argument");
-  for (int k = 0; k < 3; ++k)
-    if (strides[k] < 0) return reni_set_error(RENI_EINVAL, "blur: strides must be >= 0");
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < (size_t)C * H * W * sizeof(float))
-    return reni_set_error(RENI_EWORKSPACE, "blur: workspace missing, too small or not 256-byte aligned");
+  if (int rc = tu_check_strides("blur", "strides", strides, 3)) return rc;
+  if (int rc = tu_check_ws("blur", ws, ws_bytes, (size_t)C * H * W * sizeof(float))) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* mid = (float*)ws;  // [C][H][W]
   const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)C);
-  hipLaunchKernelGGL(reni::k_blur_axis, grid, dim3(256), 0, s, src, strides[0], strides[1], strides[2], mid, H * W, W, (int64_t)1,
-                     (int)H, (int)W, 0, weights, (int)radius);
-  if (int rc = hip_status()) return rc;
-  hipLaunchKernelGGL(reni::k_blur_axis, grid, dim3(256), 0, s, (const float*)mid, H * W, W, (int64_t)1, out, strides[0],
-                     strides[1], strides[2], (int)H, (int)W, 1, weights, (int)radius);
-  return hip_status();
+  if (int rc = tu_launch(TU_PLAIN, reni::k_blur_axis, grid, dim3(256), 0, s, src, strides[0], strides[1], strides[2], mid, H * W, W,
+                         (int64_t)1, (int)H, (int)W, 0, weights, (int)radius))
+    return rc;
+  return tu_launch(TU_PLAIN, reni::k_blur_axis, grid, dim3(256), 0, s, mid, H * W, W, (int64_t)1, out, strides[0], strides[1],
+                   strides[2], (int)H, (int)W, 1, weights, (int)radius);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
 #pragma clang fp contract(off)
 
@@ -122,8 +123,7 @@ extern "C" int reni_rotate_envmap(int64_t B, int64_t C, int64_t H, int64_t W, co
   if (W & 1) return reni_set_error(RENI_EINVAL, "rotate: W must be even (the far side of a pole is W / 2 columns away)");
   if (B > 65535 || C > 65535 || H > 0x3fffffff / W) return reni_set_error(RENI_EINVAL, "rotate: need B, C <= 65535 and H W < 2^30");
   if (!src || !src_strides || !rot || !row_trig || !col_trig || !out) return reni_set_error(RENI_EINVAL, "rotate: NULL argument");
-  for (int k = 0; k < 4; ++k)
-    if (src_strides[k] < 0) return reni_set_error(RENI_EINVAL, "rotate: src strides must be >= 0");
+  if (int rc = tu_check_strides("rotate", "src strides", src_strides, 4)) return rc;
   if (src_strides[2] > 0x7fffffff || src_strides[3] > 0x7fffffff)
     return reni_set_error(RENI_EINVAL, "rotate: the row and column strides must be < 2^31 elements");
   if (rot_stride != 0 && rot_stride != 9) return reni_set_error(RENI_EINVAL, "rotate: rot_stride must be 9 (per image) or 0 (shared)");
@@ -137,7 +137,6 @@ extern "C" int reni_rotate_envmap(int64_t B, int64_t C, int64_t H, int64_t W, co
   sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
   const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)B);
   hipStream_t s = (hipStream_t)stream;
-  if (mode == RENI_ROTATE_BILINEAR) hipLaunchKernelGGL(reni::k_rotate_envmap<true>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(reni::k_rotate_envmap<false>, grid, dim3(256), 0, s, a);
-  return reni::hip_status();
+  const auto k = mode == RENI_ROTATE_BILINEAR ? reni::k_rotate_envmap<true> : reni::k_rotate_envmap<false>;
+  return tu_launch(TU_PLAIN, k, grid, dim3(256), 0, s, a);
 }

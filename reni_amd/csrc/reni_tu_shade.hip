@@ -21,6 +21,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
 #define DEV __device__ __forceinline__
 
@@ -254,33 +255,20 @@ int shade_common(bool forward, int64_t B, int64_t NP, int64_t J, const float* no
   const dim3 grid((unsigned)((n_own + 255) / 256), (unsigned)S);
   // images that share their texel directions share M: chunks of SHADE_BC; otherwise one image per launch
   const int step = dirs_bstride == 0 ? SHADE_BC : 1;
+  using reni::k_envmap_shade;
+  const auto k = masked ? (step == 1 ? (forward ? k_envmap_shade<true, 1, true> : k_envmap_shade<false, 1, true>)
+                                     : (forward ? k_envmap_shade<true, SHADE_BC, true> : k_envmap_shade<false, SHADE_BC, true>))
+                        : (step == 1 ? (forward ? k_envmap_shade<true, 1> : k_envmap_shade<false, 1>)
+                                     : (forward ? k_envmap_shade<true, SHADE_BC> : k_envmap_shade<false, SHADE_BC>));
   for (int64_t b0 = 0; b0 < B; b0 += step) {
     a.b0 = (int)b0; a.nb = (int)((B - b0) < step ? (B - b0) : step);
     a.ldir = light_dirs + (size_t)b0 * dirs_bstride;
-    if (masked) {
-      a.vis = vis + (size_t)b0 * vis_bstride;
-      if (step == 1) {
-        if (forward) hipLaunchKernelGGL((reni::k_envmap_shade<true, 1, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((reni::k_envmap_shade<false, 1, true>), grid, dim3(256), 0, s, a);
-      } else {
-        if (forward) hipLaunchKernelGGL((reni::k_envmap_shade<true, SHADE_BC, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((reni::k_envmap_shade<false, SHADE_BC, true>), grid, dim3(256), 0, s, a);
-      }
-    } else if (step == 1) {
-      if (forward) hipLaunchKernelGGL((reni::k_envmap_shade<true, 1>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((reni::k_envmap_shade<false, 1>), grid, dim3(256), 0, s, a);
-    } else {
-      if (forward) hipLaunchKernelGGL((reni::k_envmap_shade<true, SHADE_BC>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((reni::k_envmap_shade<false, SHADE_BC>), grid, dim3(256), 0, s, a);
-    }
-    if (int rc = reni::hip_status()) return rc;
+    if (masked) a.vis = vis + (size_t)b0 * vis_bstride;
+    if (int rc = tu_launch(TU_PLAIN, k, grid, dim3(256), 0, s, a)) return rc;
   }
-  if (S > 1) {
-    const size_t n = (size_t)B * n_own * 3;
-    hipLaunchKernelGGL(reni::k_shade_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)ws, n, S, out);
-    if (int rc = reni::hip_status()) return rc;
-  }
-  return RENI_OK;
+  if (S == 1) return RENI_OK;
+  const size_t n = (size_t)B * n_own * 3;
+  return tu_launch(TU_PLAIN, reni::k_shade_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)ws, n, S, out);
 }
 
 }  // namespace

@@ -22,6 +22,7 @@
 
 #include "reni_hip.h"
 #include "reni_internal.h"
+#include "reni_tu_host.inc"
 
 #define DEV __device__ __forceinline__
 
@@ -241,10 +242,8 @@ int reni_mesh_visibility_prepare(int64_t V, int64_t F, const float* verts, const
   if (((uintptr_t)accel & 15) != 0) return reni_set_error(RENI_EINVAL, "visibility prepare: accel must be 16-byte aligned");
   if (accel_bytes_given < accel_bytes(F)) return reni_set_error(RENI_EWORKSPACE, "visibility prepare: accel buffer too small");
   const unsigned NC = (unsigned)((F + reni::VIS_CLUSTER - 1) / reni::VIS_CLUSTER);
-  hipLaunchKernelGGL(reni::k_vis_prepare, dim3(NC), dim3(reni::VIS_CLUSTER), 0, (hipStream_t)stream, (int)V, (int)F, verts,
-                     faces, order, accel);
-  reni::note_launches(1);
-  return reni::hip_status();
+  return tu_launch(TU_COUNTED, reni::k_vis_prepare, dim3(NC), dim3(reni::VIS_CLUSTER), 0, (hipStream_t)stream, (int)V, (int)F, verts,
+                   faces, order, accel);
 }
 
 int reni_mesh_visibility(int64_t B, int64_t NP, int64_t J, const float* positions, const int64_t* pix_to_face,
@@ -263,9 +262,7 @@ int reni_mesh_visibility(int64_t B, int64_t NP, int64_t J, const float* position
   a.NP = (int)NP; a.J = (int)J; a.JW = (int)((J + 31) / 32); a.no_cull = (flags & RENI_VIS_NO_CULL) ? 1 : 0;
   const int NB = dirs_batch_stride == 0 ? 1 : (int)B;
   const dim3 grid((unsigned)NP, (unsigned)((J + 255) / 256), (unsigned)NB);
-  hipLaunchKernelGGL(reni::k_mesh_visibility, grid, dim3(reni::VIS_WAVES * 64), 0, (hipStream_t)stream, a);
-  reni::note_launches(1);
-  return reni::hip_status();
+  return tu_launch(TU_COUNTED, reni::k_mesh_visibility, grid, dim3(reni::VIS_WAVES * 64), 0, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

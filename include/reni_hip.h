@@ -441,6 +441,35 @@ int reni_envmap_shade_masked_backward(int64_t B, int64_t NP, int64_t J, const fl
                                       const uint32_t* vis, int64_t vis_batch_stride, float* dlight_colors, void* ws,
                                       size_t ws_bytes, void* stream);
 
+/* ---- per-pixel materials: the shader's terms, for an albedo, a ks and a shininess per pixel and their gradients ----
+ * With nl, nh as in reni_envmap_shade (nl = clamp(N.L, 0, 1), nh = clamp(N.normalize(V + L), 0, 1)), s_p the pixel's
+ * shininess and v(p,j) the visibility bit (1 when vis is NULL):
+ *     diffuse[b,p,:]      = sum_j v nl                C[b,j,:]
+ *     specular[b,p,:]     = sum_j v nh^s_p            C[b,j,:]     (no norm(s), no ks: the caller applies the material,
+ *                                                                   colors = albedo diffuse + ks norm(s_p) specular)
+ *     dspecular_ds[b,p,:] = sum_j v nh^s_p ln nh      C[b,j,:]     (d specular / d s_p; a pair with nh = 0 adds exactly 0;
+ *                                                                   NULL: not wanted, not computed)
+ *     dlight_colors[b,j,:] = sum_p v ( nl d_diffuse[b,p,:] + nh^s_p d_specular[b,p,:] )
+ * normals .. light_colors, vis, vis_batch_stride: as for reni_envmap_shade[_masked]; the three outputs and the two upstream
+ * gradients are [B][NP][3].  shininess: device, s_p = shininess[p * shininess_stride], shininess_stride 0 (one value for all
+ * pixels) or 1 ([NP]).  Every s_p must be > 0: a value <= 0 or NaN gives unspecified values for that pixel (and, backward,
+ * for the texels it lights), never an access outside the buffers.  Deterministic (fixed-order partial sums, no float
+ * atomics); an all-ones mask gives the bits of vis = NULL.
+ * ws: reni_envmap_shade_terms_workspace_bytes(B, NP, J, flags) bytes, flags = RENI_SHADE_TERMS_DS when dspecular_ds is
+ * wanted, else 0 (0 is returned for a size < 1 or an unknown flag); one buffer of that size serves both calls. */
+#define RENI_SHADE_TERMS_DS 1u
+size_t reni_envmap_shade_terms_workspace_bytes(int64_t B, int64_t NP, int64_t J, uint32_t flags);
+int reni_envmap_shade_terms(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                            float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                            const float* light_colors, const float* shininess, int64_t shininess_stride, const uint32_t* vis,
+                            int64_t vis_batch_stride, float* diffuse, float* specular, float* dspecular_ds, void* ws,
+                            size_t ws_bytes, void* stream);
+int reni_envmap_shade_terms_backward(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions,
+                                     float cam_x, float cam_y, float cam_z, const float* light_dirs,
+                                     int64_t dirs_batch_stride, const float* shininess, int64_t shininess_stride,
+                                     const uint32_t* vis, int64_t vis_batch_stride, const float* d_diffuse,
+                                     const float* d_specular, float* dlight_colors, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- environment-map baselines: spherical Gaussians and spherical harmonics ----------------------------------------
  * What RENI is compared against.  fp32, deterministic (no float atomics; fixed summation order: two calls give identical
  * bits, and map n's results are the same alone or inside a batch).

@@ -26,6 +26,7 @@ LOBE_KIND = {"phong": 0, "blinn": 1, "ggx": 2}  # RENI_LOBE_*
 SPACE = {"stored": 0, "linear": 1, "srgb": 2}
 SSIM_MODE = {"sphere": 0, "planar": 1}
 VIS_NO_CULL = 1  # RENI_VIS_NO_CULL
+SHADE_TERMS_DS = 1  # RENI_SHADE_TERMS_DS
 
 # every symbol include/reni_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -39,6 +40,7 @@ EXPORTS = (
     "reni_raster_workspace_bytes", "reni_mesh_vertex_normals", "reni_rasterize_mesh",
     "reni_mesh_visibility_accel_bytes", "reni_mesh_visibility_prepare", "reni_mesh_visibility",
     "reni_envmap_shade_masked", "reni_envmap_shade_masked_backward",
+    "reni_envmap_shade_terms_workspace_bytes", "reni_envmap_shade_terms", "reni_envmap_shade_terms_backward",
     "reni_sg_workspace_bytes", "reni_sg_render", "reni_sg_loss_grad", "reni_sh_project", "reni_sh_reconstruct",
     "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
     "reni_lobe_workspace_bytes", "reni_lobe_convolve", "reni_envmap_lookup",
@@ -198,6 +200,14 @@ def load():
         fn.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int64,
                        c_void_p, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]
         fn.restype = c_int32
+    lib.reni_envmap_shade_terms_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_uint32]
+    lib.reni_envmap_shade_terms_workspace_bytes.restype = c_size_t
+    terms = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int64]  # B, NP, J .. dirs_batch_stride
+    mats = [c_void_p, c_int64, c_void_p, c_int64]  # shininess + stride, vis + stride
+    lib.reni_envmap_shade_terms.argtypes = terms + [c_void_p] + mats + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_envmap_shade_terms.restype = c_int32
+    lib.reni_envmap_shade_terms_backward.argtypes = terms + mats + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_envmap_shade_terms_backward.restype = c_int32
     lib.reni_sg_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int64]
     lib.reni_sg_workspace_bytes.restype = c_size_t
     lib.reni_sg_render.argtypes = [c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,

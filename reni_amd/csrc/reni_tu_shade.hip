@@ -204,6 +204,209 @@ __global__ void __launch_bounds__(256) k_shade_reduce(const float* part, size_t 
   out[i] = s;
 }
 
+// ---- per-pixel materials: the shader's TERMS ------------------------------------------------------------
+// With an albedo per pixel and channel, and gradients with respect to the material, one coefficient M(p, j) no longer
+// serves: the diffuse and the specular sums are kept apart, without kd, ks and norm(s) (those are applied behind the
+// kernel, O(B NP) work), and the shininess s_p is the pixel's own.  v(p, j) is the visibility bit (1 without a mask):
+//
+//   D[b,p,:]  = sum_j v nl(p,j)                 C[b,j,:]
+//   S[b,p,:]  = sum_j v nh(p,j)^s_p             C[b,j,:]
+//   T[b,p,:]  = sum_j v nh(p,j)^s_p ln nh(p,j)  C[b,j,:]      = dS / ds_p; a pair with nh = 0 adds exactly 0   (WANT_T)
+//   dC[b,j,:] = sum_p v ( nl(p,j) gD[b,p,:] + nh(p,j)^s_p gS[b,p,:] )
+//
+// Same structure as k_envmap_shade: a thread owns an element of one axis and walks the other through LDS, the other axis
+// is split over blockIdx.y, the partial sums are combined in a fixed order.  The transcendentals per pair are the same
+// three (rsq, log, exp2): T reuses the log.
+struct TermsArgs {
+  const float* nrm;        // [NP][3]
+  const float* pos;        // [NP][3]
+  const float* ldir;       // [J][3] texel directions of the image chunk's first image
+  const float* src0;       // forward: C [B][J][3]; backward: gD [B][NP][3]
+  const float* src1;       // backward: gS [B][NP][3]
+  const float* shin;       // s_p = shin[p * shin_stride]
+  float* out[3];           // forward: D, S, T (partial sums of split 0 when there are splits); backward: out[0] = dC
+  size_t split_stride;     // floats from one split's partial sums to the next split's
+  float cam[3];
+  int shin_stride;         // 0: one value for all pixels, 1: per pixel
+  int B, NP, J, b0, nb;
+  int per_split;
+  const uint32_t* vis;     // MASKED: as ShadeArgs::vis
+  int JW;
+};
+
+struct PairTerms { float nl, nh, lg; };  // clamp(N.L), clamp(N.H), log2 of the latter (-inf at 0)
+
+// shade_coeff's geometry.  The multiply-adds are written out (here and at the accumulators): which products the compiler
+// fuses then does not depend on the instance, so the MASKED and WANT_T instances give the plain instance's bits.
+DEV PairTerms shade_pair(const float (&N)[3], const float (&V)[3], const float (&L)[3]) {
+  PairTerms t;
+  t.nl = fminf(fmaxf(fmaf(N[2], L[2], fmaf(N[1], L[1], N[0] * L[0])), 0.f), 1.f);
+  const float hx = V[0] + L[0], hy = V[1] + L[1], hz = V[2] + L[2];
+  const float inv = __builtin_amdgcn_rsqf(fmaxf(fmaf(hz, hz, fmaf(hy, hy, hx * hx)), 1e-12f));  // 1 / max(|h|, 1e-6)
+  // normalise first, then dot, as the reference does
+  t.nh = fminf(fmaxf(fmaf(N[2], hz * inv, fmaf(N[1], hy * inv, N[0] * (hx * inv))), 0.f), 1.f);
+  t.lg = __builtin_amdgcn_logf(t.nh);
+  return t;
+}
+
+// OWN_PIXEL: forward (a thread owns pixel p: its N, V, s_p and 6 BC accumulators, 9 BC with WANT_T); else backward (a thread
+// owns texel j; the stage holds per pixel N, V, s_p and the rows gD, gS: 6 BC floats).  MASKED: as in k_envmap_shade, a
+// select on the pair's terms, read from the same packed words in the same way.
+template <bool OWN_PIXEL, int BC, bool MASKED, bool WANT_T>
+__global__ void __launch_bounds__(256) k_envmap_terms(const TermsArgs a) {
+  static_assert(OWN_PIXEL || !WANT_T, "T is a forward output");
+  constexpr int NSRC = OWN_PIXEL ? 3 * BC : 6 * BC;  // source floats per staged element
+  constexpr int ROW = 4 * ((NSRC + 3) / 4);
+  constexpr int NT = OWN_PIXEL ? (WANT_T ? 3 : 2) : 1;
+  constexpr float LN2 = 0.6931471805599453f;
+  __shared__ float4 g0[SH_TILE];                      // texel (Lx, Ly, Lz, -) | pixel (Nx, Ny, Nz, Vx)
+  __shared__ float4 g1[OWN_PIXEL ? 1 : SH_TILE];      //                       | pixel (Vy, Vz, s, -)
+  __shared__ float4 sv[SH_TILE][ROW / 4];             // forward: C rows of the BC images; backward: gD rows, then gS rows
+  __shared__ uint32_t mw[MASKED && !OWN_PIXEL ? SH_TILE : 1][8];
+  const int tid = threadIdx.x;
+  const int n_own = OWN_PIXEL ? a.NP : a.J, n_oth = OWN_PIXEL ? a.J : a.NP;
+  const int o = blockIdx.x * 256 + tid;
+  const bool live = o < n_own;
+  float N[3] = {0.f, 0.f, 0.f}, V[3] = {0.f, 0.f, 0.f}, L[3] = {0.f, 0.f, 0.f}, shin = 1.f;
+  auto load_pixel = [&](int p, float (&n)[3], float (&v)[3]) {
+    n[0] = a.nrm[(size_t)p * 3]; n[1] = a.nrm[(size_t)p * 3 + 1]; n[2] = a.nrm[(size_t)p * 3 + 2];
+    normalize3(n);
+    v[0] = a.cam[0] - a.pos[(size_t)p * 3]; v[1] = a.cam[1] - a.pos[(size_t)p * 3 + 1]; v[2] = a.cam[2] - a.pos[(size_t)p * 3 + 2];
+    normalize3(v);
+  };
+  if (live) {
+    if (OWN_PIXEL) { load_pixel(o, N, V); shin = a.shin[(size_t)o * a.shin_stride]; }
+    else { L[0] = a.ldir[(size_t)o * 3]; L[1] = a.ldir[(size_t)o * 3 + 1]; L[2] = a.ldir[(size_t)o * 3 + 2]; }
+  }
+  float acc[NT][BC][3];
+#pragma unroll
+  for (int k = 0; k < NT; ++k)
+#pragma unroll
+    for (int b = 0; b < BC; ++b) { acc[k][b][0] = 0.f; acc[k][b][1] = 0.f; acc[k][b][2] = 0.f; }
+
+  // one (p, j) pair: element e of the stage against the thread's own element; `on` is its visibility bit
+  auto pair = [&](int e, bool on) {
+    const float4 q0 = g0[e];
+    PairTerms t;
+    float s;
+    if (OWN_PIXEL) {
+      const float Lo[3] = {q0.x, q0.y, q0.z};
+      t = shade_pair(N, V, Lo);
+      s = shin;
+    } else {
+      const float4 q1 = g1[e];
+      const float No[3] = {q0.x, q0.y, q0.z}, Vo[3] = {q0.w, q1.x, q1.y};
+      t = shade_pair(No, Vo, L);
+      s = q1.z;
+    }
+    float nl = t.nl;
+    float sp = __builtin_amdgcn_exp2f(s * t.lg);             // nh^s; nh = 0: exp2(-inf) = 0
+    float dsp = 0.f;
+    if (WANT_T) dsp = t.nh > 0.f ? sp * (t.lg * LN2) : 0.f;  // nh^s ln nh, and 0 (not 0 * -inf) at nh = 0
+    if (MASKED) { nl = on ? nl : 0.f; sp = on ? sp : 0.f; dsp = on ? dsp : 0.f; }
+    const float* r = (const float*)sv[e];
+#pragma unroll
+    for (int b = 0; b < BC; ++b) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        if (OWN_PIXEL) {
+          acc[0][b][c] = fmaf(nl, r[3 * b + c], acc[0][b][c]);
+          acc[1][b][c] = fmaf(sp, r[3 * b + c], acc[1][b][c]);
+          if (WANT_T) acc[NT - 1][b][c] = fmaf(dsp, r[3 * b + c], acc[NT - 1][b][c]);
+        } else {
+          acc[0][b][c] = fmaf(sp, r[3 * BC + 3 * b + c], fmaf(nl, r[3 * b + c], acc[0][b][c]));
+        }
+      }
+    }
+  };
+
+  const int t_begin = blockIdx.y * a.per_split, t_end = min(n_oth, t_begin + a.per_split);
+  for (int t0 = t_begin; t0 < t_end; t0 += SH_TILE) {
+    __syncthreads();
+    if (tid < SH_TILE) {
+      const int t = t0 + tid;
+      float4 q0 = {0.f, 0.f, 0.f, 0.f}, q1 = {0.f, 0.f, 1.f, 0.f};
+      if (t < t_end) {
+        if (OWN_PIXEL) {
+          q0.x = a.ldir[(size_t)t * 3]; q0.y = a.ldir[(size_t)t * 3 + 1]; q0.z = a.ldir[(size_t)t * 3 + 2];
+        } else {
+          float n[3], v[3];
+          load_pixel(t, n, v);
+          q0 = float4{n[0], n[1], n[2], v[0]};
+          q1 = float4{v[1], v[2], a.shin[(size_t)t * a.shin_stride], 0.f};
+        }
+      }
+      g0[tid] = q0;
+      if (!OWN_PIXEL) g1[tid] = q1;
+    }
+    {  // source rows, zero beyond the range / the chunk's images
+      float* svf = (float*)sv;
+      for (int i = tid; i < SH_TILE * NSRC; i += 256) {
+        const int e = i / NSRC, r = i - e * NSRC, h = r / (3 * BC), rr = r - h * (3 * BC), b = rr / 3, c = rr - b * 3;
+        const int t = t0 + e;
+        const float* src = h == 0 ? a.src0 : a.src1;
+        float x = 0.f;
+        if (t < t_end && b < a.nb) x = src[((size_t)(a.b0 + b) * n_oth + t) * 3 + c];
+        svf[e * ROW + r] = x;
+      }
+    }
+    if constexpr (MASKED && !OWN_PIXEL) {
+      for (int i = tid; i < SH_TILE * 8; i += 256) {
+        const int e = i >> 3, w = blockIdx.x * 8 + (i & 7), t = t0 + e;
+        mw[e][i & 7] = (t < t_end && w < a.JW) ? a.vis[(size_t)t * a.JW + w] : 0u;
+      }
+    }
+    __syncthreads();
+    const int cnt = min(SH_TILE, t_end - t0);
+    if constexpr (MASKED) {
+      uint32_t wv[4] = {0u, 0u, 0u, 0u};
+      if (OWN_PIXEL && live) {  // (t0 is a multiple of SH_TILE: per_split is)
+        const uint32_t* row = a.vis + (size_t)o * a.JW;
+        const int w0 = t0 >> 5;
+        if ((a.JW & 3) == 0) {
+          const uint4 q = *(const uint4*)(row + w0);
+          wv[0] = q.x; wv[1] = q.y; wv[2] = q.z; wv[3] = q.w;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) wv[k] = w0 + k < a.JW ? row[w0 + k] : 0u;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {  // the ascending walk of the unmasked instance, 32 elements per mask word
+        const int e_end = min(cnt, 32 * k + 32);
+        for (int e = 32 * k; e < e_end; ++e)
+          pair(e, OWN_PIXEL ? (wv[k] >> (e & 31)) & 1u : (mw[e][tid >> 5] >> (tid & 31)) & 1u);
+      }
+    } else {
+      for (int e = 0; e < cnt; ++e) pair(e, true);
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+#pragma unroll
+      for (int b = 0; b < BC; ++b) {
+        if (b < a.nb) {
+          float* dst = a.out[k] + (size_t)blockIdx.y * a.split_stride + ((size_t)(a.b0 + b) * n_own + o) * 3;
+          dst[0] = acc[k][b][0]; dst[1] = acc[k][b][1]; dst[2] = acc[k][b][2];
+        }
+      }
+    }
+  }
+}
+
+// out[k][i] = sum_s part[(s * NT + k) * n + i], s ascending; blockIdx.y = k
+struct TermsReduceArgs { const float* part; float* out[3]; size_t n; int S, NT; };
+__global__ void __launch_bounds__(256) k_terms_reduce(const TermsReduceArgs a) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const int k = blockIdx.y;
+  float s = 0.f;
+  for (int q = 0; q < a.S; ++q) s += a.part[((size_t)q * a.NT + k) * a.n + i];
+  float* out = k == 0 ? a.out[0] : k == 1 ? a.out[1] : a.out[2];
+  out[i] = s;
+}
+
 }  // namespace reni
 
 namespace {
@@ -271,6 +474,79 @@ int shade_common(bool forward, int64_t B, int64_t NP, int64_t J, const float* no
   return tu_launch(TU_PLAIN, reni::k_shade_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)ws, n, S, out);
 }
 
+// floats of partial sums the terms pair needs: NT terms forward, one gradient backward (0 when there is one split)
+size_t terms_partials(bool forward, int64_t B, int64_t NP, int64_t J, int NT) {
+  const int64_t n_own = forward ? NP : J, n_oth = forward ? J : NP;
+  const int S = n_splits(n_own, n_oth);
+  return S > 1 ? (size_t)S * (forward ? NT : 1) * B * n_own * 3 : 0;
+}
+
+// forward: src0 = C, out = (D, S, T | NULL); backward: src0 = gD, src1 = gS, out0 = dC
+int terms_common(bool forward, int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cx,
+                 float cy, float cz, const float* light_dirs, int64_t dirs_bstride, const float* src0, const float* src1,
+                 const float* shininess, int64_t shin_stride, const uint32_t* vis, int64_t vis_bstride, float* out0,
+                 float* out1, float* out2, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 1 || NP < 1 || J < 1) return reni_set_error(RENI_EINVAL, "envmap shade terms: B, NP and J must be >= 1");
+  if (NP > 0x3fffffff || J > 0x3fffffff || B > 0xffff) return reni_set_error(RENI_EINVAL, "envmap shade terms: problem too large");
+  if (!normals || !positions || !light_dirs || !src0 || !shininess || !out0 || (forward ? !out1 : !src1))
+    return reni_set_error(RENI_EINVAL, "envmap shade terms: NULL argument");
+  if (dirs_bstride != 0 && dirs_bstride < J * 3)
+    return reni_set_error(RENI_EINVAL, "envmap shade terms: direction batch stride must be 0 or >= 3 J");
+  if (shin_stride != 0 && shin_stride != 1)
+    return reni_set_error(RENI_EINVAL, "envmap shade terms: shininess stride must be 0 (one value) or 1 (per pixel)");
+  const int64_t JW = (J + 31) / 32;
+  const bool masked = vis != nullptr;
+  if (masked) {
+    if (((uintptr_t)vis & 15) != 0) return reni_set_error(RENI_EINVAL, "envmap shade terms: the mask must be 16-byte aligned");
+    if (vis_bstride != 0 && (dirs_bstride == 0 || vis_bstride < NP * JW || ((JW & 3) == 0 && (vis_bstride & 3) != 0)))
+      return reni_set_error(RENI_EINVAL, "envmap shade terms: mask batch stride must be 0 (required with shared directions) or >= NP ceil(J/32) words");
+  }
+  const bool want_t = forward && out2 != nullptr;
+  const int NT = forward ? (want_t ? 3 : 2) : 1;
+  const int64_t n_own = forward ? NP : J, n_oth = forward ? J : NP;
+  const int S = n_splits(n_own, n_oth);
+  const size_t need = terms_partials(forward, B, NP, J, NT) * sizeof(float);
+  if (need > 0 && (!ws || ws_bytes < need)) return reni_set_error(RENI_EWORKSPACE, "envmap shade terms: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)B * n_own * 3;
+  reni::TermsArgs a;
+  a.nrm = normals; a.pos = positions; a.src0 = src0; a.src1 = src1;
+  a.shin = shininess; a.shin_stride = (int)shin_stride;
+  float* const outs[3] = {out0, out1, out2};
+  for (int k = 0; k < 3; ++k) a.out[k] = k >= NT ? nullptr : S > 1 ? (float*)ws + (size_t)k * n : outs[k];
+  a.split_stride = (size_t)NT * n;
+  a.cam[0] = cx; a.cam[1] = cy; a.cam[2] = cz;
+  a.B = (int)B; a.NP = (int)NP; a.J = (int)J;
+  const int64_t tiles = (n_oth + reni::SH_TILE - 1) / reni::SH_TILE;
+  a.per_split = (int)((tiles + S - 1) / S) * reni::SH_TILE;
+  a.vis = nullptr; a.JW = (int)JW;
+  const dim3 grid((unsigned)((n_own + 255) / 256), (unsigned)S);
+  const int step = dirs_bstride == 0 ? SHADE_BC : 1;  // as in shade_common
+  using reni::k_envmap_terms;
+  void (*k)(const reni::TermsArgs);
+  if (!forward) {
+    k = step == 1 ? (masked ? k_envmap_terms<false, 1, true, false> : k_envmap_terms<false, 1, false, false>)
+                  : (masked ? k_envmap_terms<false, SHADE_BC, true, false> : k_envmap_terms<false, SHADE_BC, false, false>);
+  } else if (step == 1) {
+    k = masked ? (want_t ? k_envmap_terms<true, 1, true, true> : k_envmap_terms<true, 1, true, false>)
+               : (want_t ? k_envmap_terms<true, 1, false, true> : k_envmap_terms<true, 1, false, false>);
+  } else {
+    k = masked ? (want_t ? k_envmap_terms<true, SHADE_BC, true, true> : k_envmap_terms<true, SHADE_BC, true, false>)
+               : (want_t ? k_envmap_terms<true, SHADE_BC, false, true> : k_envmap_terms<true, SHADE_BC, false, false>);
+  }
+  for (int64_t b0 = 0; b0 < B; b0 += step) {
+    a.b0 = (int)b0; a.nb = (int)((B - b0) < step ? (B - b0) : step);
+    a.ldir = light_dirs + (size_t)b0 * dirs_bstride;
+    if (masked) a.vis = vis + (size_t)b0 * vis_bstride;
+    if (int rc = tu_launch(TU_PLAIN, k, grid, dim3(256), 0, s, a)) return rc;
+  }
+  if (S == 1) return RENI_OK;
+  reni::TermsReduceArgs r;
+  r.part = (const float*)ws; r.n = n; r.S = S; r.NT = NT;
+  for (int k2 = 0; k2 < 3; ++k2) r.out[k2] = k2 < NT ? outs[k2] : nullptr;
+  return tu_launch(TU_PLAIN, reni::k_terms_reduce, dim3((unsigned)((n + 255) / 256), (unsigned)NT), dim3(256), 0, s, r);
+}
+
 }  // namespace
 
 extern "C" {
@@ -313,6 +589,33 @@ int reni_envmap_shade_masked_backward(int64_t B, int64_t NP, int64_t J, const fl
                                       size_t ws_bytes, void* stream) {
   return shade_common(false, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, dcolors,
                       shininess, kd, ks, dlight_colors, ws, ws_bytes, stream, true, vis, vis_batch_stride);
+}
+
+size_t reni_envmap_shade_terms_workspace_bytes(int64_t B, int64_t NP, int64_t J, uint32_t flags) {
+  if (B < 1 || NP < 1 || J < 1 || (flags & ~RENI_SHADE_TERMS_DS) != 0) return 0;
+  const size_t f = terms_partials(true, B, NP, J, (flags & RENI_SHADE_TERMS_DS) ? 3 : 2) * sizeof(float);
+  const size_t g = terms_partials(false, B, NP, J, 1) * sizeof(float);
+  return (f > g ? f : g) + 256;
+}
+
+int reni_envmap_shade_terms(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                            float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                            const float* light_colors, const float* shininess, int64_t shininess_stride, const uint32_t* vis,
+                            int64_t vis_batch_stride, float* diffuse, float* specular, float* dspecular_ds, void* ws,
+                            size_t ws_bytes, void* stream) {
+  return terms_common(true, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, light_colors,
+                      nullptr, shininess, shininess_stride, vis, vis_batch_stride, diffuse, specular, dspecular_ds, ws,
+                      ws_bytes, stream);
+}
+
+int reni_envmap_shade_terms_backward(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions,
+                                     float cam_x, float cam_y, float cam_z, const float* light_dirs,
+                                     int64_t dirs_batch_stride, const float* shininess, int64_t shininess_stride,
+                                     const uint32_t* vis, int64_t vis_batch_stride, const float* d_diffuse,
+                                     const float* d_specular, float* dlight_colors, void* ws, size_t ws_bytes, void* stream) {
+  return terms_common(false, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, d_diffuse,
+                      d_specular, shininess, shininess_stride, vis, vis_batch_stride, dlight_colors, nullptr, nullptr, ws,
+                      ws_bytes, stream);
 }
 
 }  // extern "C"

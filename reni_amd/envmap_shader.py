@@ -93,6 +93,145 @@ def blinn_phong_shading_gbuffer(pixel_normals, pixel_positions, camera_center, e
                           _constant_mask(vis, pixel_normals.shape[0], dirs))
 
 
+class _ShadeTermsFn(torch.autograd.Function):
+    """(D, S) of ``ops.envmap_shade_terms``.  Gradients: the light colours through the backward kernel, the shininess as
+    ds_p = sum_{b,c} gS T with T = dS/ds_p from the forward kernel (computed only when the shininess needs a gradient)."""
+
+    @staticmethod
+    def forward(ctx, light_colors, shininess, normals, positions, camera_center, light_dirs, vis, need_ds):
+        D, S, T = ops.envmap_shade_terms(normals, positions, camera_center, light_dirs, light_colors, shininess, vis=vis,
+                                         need_ds=need_ds)
+        ctx.save_for_backward(normals, positions, camera_center, light_dirs, shininess, T)
+        ctx.vis = vis  # a constant of (mesh, camera, directions): see _constant_mask
+        return D, S
+
+    @staticmethod
+    def backward(ctx, gD, gS):
+        normals, positions, camera_center, light_dirs, shininess, T = ctx.saved_tensors
+        gC = gs = None
+        if ctx.needs_input_grad[0]:
+            gC = ops.envmap_shade_terms_backward(normals, positions, camera_center, light_dirs, gD.contiguous(),
+                                                 gS.contiguous(), shininess, vis=ctx.vis)
+        if ctx.needs_input_grad[1] and T is not None:
+            gs = (gS * T).sum(dim=(0, 2))
+            gs = (gs.sum() if shininess.numel() == 1 else gs).reshape(shininess.shape).to(shininess.dtype)
+        return gC, gs, None, None, None, None, None, None
+
+
+def _constant(what, t):
+    if isinstance(t, torch.Tensor) and t.requires_grad:
+        raise ValueError(f"{what} are constants of the shader (gradients with respect to geometry and camera are out of "
+                         "scope): they cannot require grad")
+    return t
+
+
+def _shade_terms(light_colors, light_dirs, pixel_normals, pixel_positions, camera_center, shininess, vis=None):
+    _constant("the pixel normals", pixel_normals)
+    _constant("the pixel positions", pixel_positions)
+    _constant("the light directions", light_dirs)
+    cam = torch.as_tensor(_constant("the camera centre", camera_center), dtype=torch.float32).reshape(-1)[:3].cpu()
+    NP = pixel_normals.shape[0] if isinstance(pixel_normals, torch.Tensor) and pixel_normals.dim() == 2 else -1
+    if not isinstance(shininess, torch.Tensor):
+        shininess = torch.as_tensor(float(shininess), dtype=torch.float32, device=light_colors.device)
+    if shininess.numel() != 1 and tuple(shininess.shape) != (NP,):
+        raise ValueError(f"shininess must be a float, one value or [{NP}] (one per pixel), got {tuple(shininess.shape)}")
+    dirs = _shared_grid(light_dirs)
+    need_ds = bool(shininess.requires_grad and torch.is_grad_enabled())  # T = dS/ds only when somebody will ask for it
+    return _ShadeTermsFn.apply(light_colors, shininess, pixel_normals, pixel_positions, cam, dirs,
+                               _constant_mask(vis, NP, dirs), need_ds)
+
+
+def shade_terms(pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap, shininess, vis=None):
+    """(D, S), each [B, NP, 3]: the diffuse sum D = sum_j nl C and the specular sum S = sum_j nh^s_p C of the shader, kept
+    apart and without kd, ks and norm(s), for a shininess per pixel (a float, one value or [NP]; every value > 0).
+    ``compose_materials`` turns them into colours.  Differentiable with respect to ``envmap.environment_map`` and
+    ``shininess``; normals, positions, camera, directions and the mask are constants (one that requires grad raises)."""
+    return _shade_terms(envmap.environment_map, envmap.directions, pixel_normals, pixel_positions, camera_center, shininess, vis)
+
+
+def specular_norm(shininess: torch.Tensor) -> torch.Tensor:
+    """norm(s) = (s + 2) / (4 (2 - exp(-s / 2))), the reference's energy normalisation of the lobe (:112-114)."""
+    return (shininess + 2.0) / (4.0 * (2.0 - torch.exp(-shininess / 2.0)))
+
+
+def compose_materials(D: torch.Tensor, S: torch.Tensor, albedo, ks, shininess) -> torch.Tensor:
+    """colours [B, NP, 3] = albedo D + ks norm(s) S from the terms of ``shade_terms``.  albedo: a float, [3] or [NP, 3];
+    ks and shininess: a float, one value or [NP].  Plain torch (any device, any float dtype): its autograd gives the
+    gradients of albedo and ks and the norm'(s) part of the shininess's."""
+    if not isinstance(D, torch.Tensor) or D.dim() != 3 or D.shape[-1] != 3 or S.shape != D.shape:
+        raise ValueError("D and S must be [B, NP, 3]")
+    NP = D.shape[1]
+
+    def per_pixel(x, name):
+        x = torch.as_tensor(x, dtype=D.dtype, device=D.device) if not isinstance(x, torch.Tensor) else x.to(D.dtype)
+        if x.numel() == 1:
+            return x.reshape(1, 1)
+        if tuple(x.shape) != (NP,):
+            raise ValueError(f"{name} must be a float, one value or [{NP}] (one per pixel), got {tuple(x.shape)}")
+        return x.reshape(NP, 1)
+
+    a = torch.as_tensor(albedo, dtype=D.dtype, device=D.device) if not isinstance(albedo, torch.Tensor) else albedo.to(D.dtype)
+    if a.numel() != 1 and tuple(a.shape) not in ((3,), (NP, 3)):
+        raise ValueError(f"albedo must be a float, [3] or [{NP}, 3], got {tuple(a.shape)}")
+    if a.numel() == 1:
+        a = a.reshape(1)
+    return a * D + (per_pixel(ks, "ks") * specular_norm(per_pixel(shininess, "shininess"))) * S
+
+
+def blinn_phong_shading_materials(pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap, albedo, ks,
+                                  shininess, vis=None) -> torch.Tensor:
+    """colours [B, NP, 3] with a material per pixel: ``compose_materials(*shade_terms(...), albedo, ks, shininess)``.
+    Differentiable with respect to the environment map, albedo, ks and shininess."""
+    D, S = shade_terms(pixel_normals, pixel_positions, camera_center, envmap, shininess, vis=vis)
+    return compose_materials(D, S, albedo, ks, shininess)
+
+
+class SpatialMaterials(nn.Module):
+    """A Blinn-Phong material per render pixel.  albedo: a float, [3], [NP, 3] or [S, S, 3]; ks and shininess: a float,
+    [NP] or [S, S].  The names in ``learn`` become Parameters (the caller owns their optimiser), the others buffers.  The
+    shininess is clamped to [shininess_min, shininess_max] before use, so an optimiser cannot walk it out of the kernels'
+    precondition s > 0.  ``values()`` -> (albedo, ks, shininess) flattened over the pixels, as the shading functions take
+    them.  A per-vertex albedo needs no more than ``interpolate_face_attributes(frags.pix_to_face, frags.bary_coords,
+    vertex_albedo[faces])`` as the albedo of ``compose_materials``."""
+
+    NAMES = ("albedo", "ks", "shininess")
+
+    def __init__(self, albedo=1.0, ks=0.0, shininess=500.0, learn=(), shininess_min: float = 1.0, shininess_max: float = 2000.0):
+        super().__init__()
+        learn = (learn,) if isinstance(learn, str) else tuple(learn)
+        for name in learn:
+            if name not in self.NAMES:
+                raise ValueError(f"learn names must be among {self.NAMES}, got {name!r}")
+        if not 0.0 < float(shininess_min) <= float(shininess_max):
+            raise ValueError("0 < shininess_min <= shininess_max is required")
+        self.shininess_min, self.shininess_max = float(shininess_min), float(shininess_max)
+        a = torch.as_tensor(albedo, dtype=torch.float32).detach().clone()
+        if a.dim() == 3 and a.shape[0] == a.shape[1] and a.shape[2] == 3:
+            a = a.reshape(-1, 3)
+        if a.dim() > 2 or (a.dim() == 1 and a.shape[0] != 3) or (a.dim() == 2 and a.shape[1] != 3):
+            raise ValueError(f"albedo must be a float, [3], [NP, 3] or [S, S, 3], got {tuple(a.shape)}")
+        vals = {"albedo": a}
+        for name, x in (("ks", ks), ("shininess", shininess)):
+            x = torch.as_tensor(x, dtype=torch.float32).detach().clone()
+            if x.dim() == 2 and x.shape[0] == x.shape[1]:
+                x = x.reshape(-1)
+            if x.dim() > 1:
+                raise ValueError(f"{name} must be a float, [NP] or [S, S], got {tuple(x.shape)}")
+            vals[name] = x
+        sizes = {a.shape[0]} if a.dim() == 2 else set()
+        sizes |= {vals[k].shape[0] for k in ("ks", "shininess") if vals[k].numel() > 1}
+        if len(sizes) > 1:
+            raise ValueError(f"the per-pixel materials disagree about the number of pixels: {sorted(sizes)}")
+        for name, x in vals.items():
+            if name in learn:
+                setattr(self, name, nn.Parameter(x))
+            else:
+                self.register_buffer(name, x)
+
+    def values(self):
+        return self.albedo, self.ks, self.shininess.clamp(self.shininess_min, self.shininess_max)
+
+
 def blinn_phong_shading_env_map(device, meshes, fragments, envmap, cameras, materials, kd, ks):
     """Reference signature (:46-48).  Returns (colors [B,H,W,3], pixel_normals [B,H,W,3])."""
     verts = meshes.verts_packed()

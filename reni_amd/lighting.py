@@ -177,12 +177,24 @@ def sampled_irradiance(samples: LightSamples, normals, scale: float = 1.0 / math
     return ops.lights_irradiance(normals, samples.dirs, samples.colors, scale)
 
 
-def shade_sampled(samples: LightSamples, normals, positions, camera_center, shininess, kd, ks, visibility=None) -> torch.Tensor:
+def shade_sampled(samples: LightSamples, normals, positions, camera_center, shininess=None, kd=None, ks=None, visibility=None,
+                  materials=None) -> torch.Tensor:
     """[B, NP, 3]: the Blinn-Phong environment-map shader (``ops.envmap_shade``) lit by the S sampled lights of each map
     instead of its H W texels; sample with texel_weight "sineweight" to estimate what the shader gives for the whole map.
-    ``visibility``: the mask of ``light_visibility`` for these samples -- a light lights only the pixels that see it."""
+    ``visibility``: the mask of ``light_visibility`` for these samples -- a light lights only the pixels that see it.
+    ``materials``: an ``envmap_shader.SpatialMaterials`` of NP pixels instead of the scalars shininess, kd, ks (the shader's
+    terms path with per-image light lists; differentiable with respect to ``samples.colors`` and the materials)."""
     if not isinstance(samples, LightSamples):
         raise ValueError("samples must be LightSamples (sample_lights)")
+    if materials is not None:
+        from .envmap_shader import SpatialMaterials, _shade_terms, compose_materials
+        if not isinstance(materials, SpatialMaterials):
+            raise ValueError("materials must be an envmap_shader.SpatialMaterials")
+        albedo, ks_p, s_p = materials.values()
+        D, S = _shade_terms(samples.colors, samples.dirs, normals, positions, camera_center, s_p, vis=visibility)
+        return compose_materials(D, S, albedo, ks_p, s_p)
+    if shininess is None or kd is None or ks is None:
+        raise ValueError("shininess, kd and ks are required without materials")
     return ops.envmap_shade(normals, positions, camera_center, samples.dirs, samples.colors, shininess, kd, ks, vis=visibility)
 
 

@@ -20,7 +20,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .envmap_shader import EnvironmentMap, _Materials, _shared_grid, blinn_phong_shading_gbuffer
+from .envmap_shader import (EnvironmentMap, SpatialMaterials, _Materials, _shared_grid, blinn_phong_shading_gbuffer,
+                            blinn_phong_shading_materials)
 
 Fragments = namedtuple("Fragments", ["pix_to_face", "zbuf", "bary_coords", "dists"])
 
@@ -226,14 +227,22 @@ class HipMeshRenderer(nn.Module):
     same is done here.  With the default KD_VALUE = 1 (no specular term) it has no effect.
 
     ``shadows=True``: the mesh blocks light (``MeshRasterizer.visibility`` of the envmap's directions, cached; the shader
-    then counts only the texels a pixel sees).  The default, False, renders what the reference renders."""
+    then counts only the texels a pixel sees).  The default, False, renders what the reference renders.
 
-    def __init__(self, rasterizer: MeshRasterizer, kd: float, ks: float = None, materials=None, shader_cameras=None,
+    ``materials=SpatialMaterials(...)``: an albedo, a ks and a shininess per render pixel (S*S of them) instead of the
+    scalars kd, ks and ``materials.shininess``; the render is then differentiable with respect to them as well (the shader's
+    terms path, ``envmap_shader.blinn_phong_shading_materials``), and kd / ks are not used.  With any other ``materials``
+    the call and its bits are the scalar shader's."""
+
+    def __init__(self, rasterizer: MeshRasterizer, kd: float = None, ks: float = None, materials=None, shader_cameras=None,
                  shadows: bool = False):
         super().__init__()
         self.rasterizer = rasterizer
         self.shadows = bool(shadows)  # cast shadows: the mesh blocks the texels it hides from a pixel
-        self.kd = float(kd)
+        self.spatial = isinstance(materials, SpatialMaterials)
+        if kd is None and not self.spatial:
+            raise ValueError("kd is required unless materials is a SpatialMaterials")
+        self.kd = 1.0 if kd is None else float(kd)
         self.ks = 1.0 - self.kd if ks is None else float(ks)
         self.materials = materials if materials is not None else _Materials(500.0)
         shader_cameras = shader_cameras if shader_cameras is not None else rasterizer.cameras
@@ -247,8 +256,13 @@ class HipMeshRenderer(nn.Module):
         vis = None
         if self.shadows:  # the mask of the envmap's directions: one for a shared grid, one per image for per-image lists
             vis = self.rasterizer.visibility(meshes_world, R, T, _shared_grid(envmap.directions))
-        colors = blinn_phong_shading_gbuffer(nrm, pos, self.camera_center, envmap, self.materials.shininess, self.kd, self.ks,
-                                             vis=vis)
+        if self.spatial:
+            if self.materials.ks.device != nrm.device:
+                self.materials.to(nrm.device)
+            colors = blinn_phong_shading_materials(nrm, pos, self.camera_center, envmap, *self.materials.values(), vis=vis)
+        else:
+            colors = blinn_phong_shading_gbuffer(nrm, pos, self.camera_center, envmap, self.materials.shininess, self.kd,
+                                                 self.ks, vis=vis)
         normals = torch.nn.functional.normalize(nrm, p=2, dim=-1, eps=1e-6).reshape(1, S, S, 3).repeat(B, 1, 1, 1)
         return colors.reshape(B, S, S, 3), normals
 
@@ -266,11 +280,12 @@ def unpack_visibility(vis: torch.Tensor, J: int) -> torch.Tensor:
     return bits.reshape(vis.shape[0], vis.shape[1], -1)[:, :, :J].to(torch.bool)
 
 
-def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device, shadows: bool = False):
+def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device, shadows: bool = False, materials=None):
     """Same arguments and return value as the reference's ``build_renderer`` (:177-217) -- ``(renderer, R, T, mesh)`` with
     ``renderer(meshes_world=mesh, R=R, T=T, envmap=...)`` -- without pytorch3d: Materials(shininess=500), ks = 1 - kd, the
     camera at look_at_view_transform(2, 0, 0).  ``device`` must be a GPU device (there is no CPU path).  ``shadows=True``:
-    the mesh casts shadows on itself (``HipMeshRenderer(shadows=True)``); the default renders what the reference does."""
+    the mesh casts shadows on itself (``HipMeshRenderer(shadows=True)``); the default renders what the reference does.
+    ``materials``: a ``SpatialMaterials`` of img_size x img_size pixels (then kd is not used); None: Materials(shininess=500)."""
     verts, faces = load_obj(obj_path)
     verts = rotate_axis_angle_y(verts, obj_rotation)
     if torch.device(device).type != "cuda":
@@ -279,6 +294,9 @@ def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device, shadows: bo
     mesh.verts_normals_packed()
     cameras = FoVPerspectiveCameras(device=device)
     raster = MeshRasterizer(cameras=cameras, raster_settings=RasterizationSettings(image_size=int(img_size)))
-    renderer = HipMeshRenderer(raster, kd=kd, materials=_Materials(500.0), shadows=shadows)
+    if materials is not None and not isinstance(materials, SpatialMaterials):
+        raise ValueError("materials must be a SpatialMaterials or None")
+    renderer = HipMeshRenderer(raster, kd=kd, materials=_Materials(500.0) if materials is None else materials.to(device),
+                               shadows=shadows)
     R, T = look_at_view_transform(2.0, 0.0, 0.0, degrees=True, device=device)
     return renderer, R, T, mesh

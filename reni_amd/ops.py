@@ -605,6 +605,79 @@ def envmap_shade_backward(normals, positions, camera_center, light_dirs, dcolors
     return _shade_call(False, normals, positions, camera_center, light_dirs, dcolors, shininess, kd, ks, vis)
 
 
+def _terms_call(forward: bool, normals, positions, camera_center, light_dirs, srcs, shininess, vis, need_ds=False):
+    """reni_envmap_shade_terms / reni_envmap_shade_terms_backward (include/reni_hip.h) behind the checks of ``_shade_call``.
+    srcs: (light colours [B,J,3],) forward, (gD, gS) [B,NP,3] backward; shininess: a float, a one-element tensor or [NP]."""
+    _dirs_dims(light_dirs)
+    if not isinstance(normals, torch.Tensor) or normals.dim() != 2:
+        raise ValueError("normals and positions must be [NP, 3]")
+    NP = normals.shape[0]
+    if isinstance(shininess, torch.Tensor):
+        if shininess.numel() != 1 and tuple(shininess.shape) != (NP,):
+            raise ValueError(f"shininess must be a float, one value or [{NP}] (one per pixel), got {tuple(shininess.shape)}")
+    elif not isinstance(shininess, (int, float)):
+        raise ValueError(f"shininess must be a float, one value or [{NP}] (one per pixel), got {type(shininess).__name__}")
+    if vis is not None:
+        check_visibility(vis, NP, light_dirs.shape[-2])
+        if vis.shape[0] != 1 and (light_dirs.dim() == 2 or vis.shape[0] != light_dirs.shape[0]):
+            raise ValueError(f"a mask of {vis.shape[0]} images needs per-image directions [{vis.shape[0]}, J, 3]")
+    _require_cuda(normals, positions, light_dirs, *srcs, vis, shininess if isinstance(shininess, torch.Tensor) else None)
+    lib = _lib.load()
+    f32 = torch.float32
+    normals = normals.to(f32).contiguous(); positions = positions.to(f32).contiguous()
+    light_dirs = light_dirs.to(f32).contiguous()
+    srcs = [x.to(f32).contiguous() for x in srcs]
+    dev = srcs[0].device
+    if normals.shape != (NP, 3) or positions.shape != (NP, 3):
+        raise ValueError("normals and positions must be [NP, 3]")
+    B = srcs[0].shape[0]
+    if light_dirs.dim() == 2:
+        J, stride = light_dirs.shape[0], 0
+    else:
+        if light_dirs.shape[0] != B:
+            raise ValueError("light_dirs batch size must match the colours'")
+        J, stride = light_dirs.shape[1], light_dirs.shape[1] * 3
+    want = (B, J, 3) if forward else (B, NP, 3)
+    for x in srcs:
+        if tuple(x.shape) != want:
+            raise ValueError(f"expected a {want} tensor, got {tuple(x.shape)}")
+    if isinstance(shininess, torch.Tensor):
+        shin = shininess.detach().to(device=dev, dtype=f32).reshape(-1).contiguous()
+    else:
+        shin = torch.full((1,), float(shininess), dtype=f32, device=dev)
+    cam = [float(x) for x in torch.as_tensor(camera_center).reshape(-1)[:3].tolist()]
+    nbytes = int(lib.reni_envmap_shade_terms_workspace_bytes(B, NP, J, _lib.SHADE_TERMS_DS if need_ds else 0))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    vptr, vstride = None, 0
+    if vis is not None:
+        vis = vis.contiguous()
+        vptr, vstride = vis.data_ptr(), (0 if vis.shape[0] == 1 else NP * vis.shape[2])
+    head = (B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride)
+    mats = (shin.data_ptr(), 0 if shin.numel() == 1 else 1, vptr, vstride)
+    if forward:
+        outs = [torch.empty((B, NP, 3), dtype=f32, device=dev) for _ in range(3 if need_ds else 2)]
+        _call(lib.reni_envmap_shade_terms, dev, *head, srcs[0].data_ptr(), *mats, outs[0].data_ptr(), outs[1].data_ptr(),
+              outs[2].data_ptr() if need_ds else None, ws.data_ptr(), nbytes)
+        return outs[0], outs[1], (outs[2] if need_ds else None)
+    out = torch.empty((B, J, 3), dtype=f32, device=dev)
+    _call(lib.reni_envmap_shade_terms_backward, dev, *head, *mats, srcs[0].data_ptr(), srcs[1].data_ptr(), out.data_ptr(),
+          ws.data_ptr(), nbytes)
+    return out
+
+
+def envmap_shade_terms(normals, positions, camera_center, light_dirs, light_colors, shininess, vis=None, need_ds=False):
+    """The shader's terms for per-pixel materials -> (D, S, T | None), each [B,NP,3]: D = sum_j nl C, S = sum_j nh^s_p C
+    (no ks, no norm(s): ``envmap_shader.compose_materials`` applies the material) and, with need_ds, T = dS / ds_p =
+    sum_j nh^s_p ln nh C.  shininess: a float, a one-element tensor or [NP]; every value must be > 0 (anything else gives
+    unspecified values for that pixel).  ``vis``: as for ``envmap_shade``."""
+    return _terms_call(True, normals, positions, camera_center, light_dirs, (light_colors,), shininess, vis, need_ds)
+
+
+def envmap_shade_terms_backward(normals, positions, camera_center, light_dirs, gD, gS, shininess, vis=None):
+    """d loss / d light_colors [B,J,3] for upstream gradients gD, gS [B,NP,3] of ``envmap_shade_terms``' D and S."""
+    return _terms_call(False, normals, positions, camera_center, light_dirs, (gD, gS), shininess, vis)
+
+
 def _vertex_face_csr(faces: torch.Tensor, V: int):
     """The faces of every vertex as corner indices 3 f + k, ascending per vertex (a stable sort of the flattened index list on
     the device), and the [V+1] offsets into that list.  Corners whose index lies outside [0, V) are left out."""

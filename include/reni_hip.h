@@ -607,6 +607,62 @@ int reni_envmap_lookup_backward(int64_t N, int64_t Lv, int64_t H, int64_t W, int
                                 const float* tap_weight, const int64_t* tap_order, const int64_t* offsets, float* grad_src,
                                 void* stream);
 
+/* ---- UV-space textures: a material that lives on the surface (reni_tu_texture.hip; reni_amd/textures.py) --
+ * A texture in the mesh's UV space is looked up per render pixel through the G-buffer, with a mip pyramid, and its gradient is
+ * gathered back per texel.  No reference counterpart.  fp32, deterministic (no float atomics, fixed summation orders).
+ * Mesh UVs: verts_uvs [Tn][2], faces_uvs [F][3] (int64, its own indexing); an entry outside [0, Tn) marks a face without UVs.
+ * reni_mesh_pixel_uv: for pixel p of the S x S G-buffer with f = pix_to_face[p],
+ *       uv[p]  = fmaf(b2, t2, fmaf(b1, t1, b0 t0)),  t_k = verts_uvs[faces_uvs[f][k]],  b = bary[p] (the rasteriser's own, NDC)
+ *       jac[p] = (du/dcol, dv/dcol, du/drow, dv/drow) per pixel step: a constant of the face, from its NDC vertices with the
+ *                rasteriser's chain (p R + T, / (z tan_half_fov), area edge(v2, v0, v1) + 1e-8, one pixel = -2 / S in NDC x and y)
+ *   The pixel is INVALID when f is outside [0, F), a vertex or UV index of the face is out of range or uv is not finite: then
+ *   uv = 0, jac = 0 and pix_valid[p] = -1 (else f).  pix_valid (int64 [S S]) may be NULL.  R [9], T [3] are host arrays.
+ * The pyramid: level l is H_l x W_l = max(1, H0 >> l) x max(1, W0 >> l); L levels, 1 <= L <= 1 + log2(max(H0, W0)), L > 1 only
+ *   for powers of two; stored back to back as [E][C], E = sum H_l W_l < 2^31, channels innermost, 1 <= C <= 8.
+ * reni_texture_pyramid: fills levels 1 .. L - 1 from level 0, in place: texel (y, x) of level l + 1 is
+ *   ((a(2y, 2x) + a(2y, 2x+1)) + (a(2y+1, 2x) + a(2y+1, 2x+1))) / 4 of level l, or (a0 + a1) / 2 of the two that exist where
+ *   level l is one texel high or wide.  reni_texture_pyramid_backward: the transpose, in place on a gradient [E][C], from the
+ *   coarsest level down: g_l(y, x) += r g_{l+1}(y >> 1, x >> 1), r = 1/4 or 1/2, for l = L - 2 .. 0; level 0 then holds
+ *   d loss / d level 0 (the other levels hold partial sums and are of no further use).
+ * reni_texture_taps: the 8 (element index into [E], weight) pairs of every pixel, tap_index int32 [P][8], tap_weight [P][8]:
+ *       rho    = max(|(jac0 W0, jac1 H0)|, |(jac2 W0, jac3 H0)|) (hypotf: the squares neither overflow nor underflow),
+ *                lambda = clamp(log2 rho + lod_bias, 0, L - 1); rho = 0 or not finite (a jac entry, or rho itself in fp32):
+ *                lambda = 0; jac = NULL: lambda = clamp(lod_bias, 0, L - 1) for all pixels
+ *       l0 = floor(lambda), fl = lambda - l0; the next level weighs 0 (and l1 = l0) when fl = 0 or l0 = L - 1
+ *       RENI_TEX_CLAMP, align_corners 0:  x = clamp(u W_l - 1/2, 0, W_l - 1), y = clamp((1 - v) H_l - 1/2, 0, H_l - 1),
+ *                x0 = floor x, x1 = min(x0 + 1, W_l - 1), fx = x - x0, likewise y      (grid_sample, border, at (2u - 1, 1 - 2v))
+ *       RENI_TEX_REPEAT:  u' = u - floor u, x = u' W_l - 1/2, taps x0 = floor x and x0 + 1, both modulo W_l; y from 1 - v'
+ *       align_corners 1 (L = 1 and RENI_TEX_CLAMP only):  x = clamp(u, 0, 1) (W0 - 1), y = (1 - clamp(v, 0, 1)) (H0 - 1)
+ *       taps k = 0 .. 3 on l0: {gy gx, gy fx, fy gx, fy fx} (1 - fl) at (y0,x0) (y0,x1) (y1,x0) (y1,x1); k = 4 .. 7 on l1, x fl
+ *   An unused tap has weight 0 and a valid index.  A pixel with pix_valid[p] < 0 (pix_valid may be NULL: none) or a uv that is not
+ *   finite has all weights exactly 0 (index 0), so it fetches exactly 0.  uv [P][2] need not come from a mesh.
+ * reni_texture_fetch: out[p][c] = sum_k w[p][k] tex[idx[p][k]][c], an fmaf chain over k = 0 .. 7 from 0; a tap of weight 0 is
+ *   not read.  An index is clamped to [0, E): a table is trusted for weights, never for addresses.
+ * reni_texture_fetch_backward: grad_tex [E][C] (ALL of it written: 0 where nobody sampled), grad_tex[e][c] = sum over the taps
+ *   (p, k) with index e of w[p][k] grad_out[p][c], gathered through tap_order [8 P] (int64: the positions p 8 + k in ascending
+ *   order of their element index, ties in ascending position -- a stable sort) and offsets [E + 1] (int64: element e owns
+ *   tap_order[offsets[e] .. offsets[e + 1])).  A range of at most 128 entries is summed by one lane in that order.  A longer
+ *   one is cut into chunks of 64 consecutive entries that the 64 lanes of a wave sum together -- lane j adds entry j of every
+ *   chunk, in chunk order -- and the lane sums are combined by a fixed butterfly; the cut depends on offsets only, so two calls
+ *   give identical bits, and a 1 x 1 top level costs 8 P / 64 steps per lane, not 8 P.  plain = 1: every range by one lane (kept
+ *   for measurements).  An order entry outside [0, 8 P) is skipped and a range is clipped to the table: a malformed table cannot
+ *   become an address.  Entries behind offsets[E] are never read: ops.texture_table sorts the taps of weight 0 there (every tap of
+ *   an invalid pixel names element 0; left in the table they would make its range the longest).
+ * Limits: P, S S < 2^28; V, F, Tn < 2^30; tap_index and tap_weight 16-byte aligned.  None of these launches is counted. */
+#define RENI_TEX_CLAMP 0
+#define RENI_TEX_REPEAT 1
+int reni_mesh_pixel_uv(int64_t V, int64_t F, int64_t Tn, const float* verts, const int64_t* faces, const float* verts_uvs,
+                       const int64_t* faces_uvs, const float* R, const float* T, float tan_half_fov, int64_t S,
+                       const int64_t* pix_to_face, const float* bary, float* uv, float* jac, int64_t* pix_valid, void* stream);
+int reni_texture_taps(int64_t P, const float* uv, const float* jac, const int64_t* pix_valid, int64_t L, int64_t H0, int64_t W0,
+                      float lod_bias, int32_t wrap, int32_t align_corners, int32_t* tap_index, float* tap_weight, void* stream);
+int reni_texture_pyramid(int64_t L, int64_t H0, int64_t W0, int64_t C, float* tex, void* stream);
+int reni_texture_pyramid_backward(int64_t L, int64_t H0, int64_t W0, int64_t C, float* grad_tex, void* stream);
+int reni_texture_fetch(int64_t P, int64_t E, int64_t C, const float* tex, const int32_t* tap_index, const float* tap_weight,
+                       float* out, void* stream);
+int reni_texture_fetch_backward(int64_t P, int64_t E, int64_t C, const float* grad_out, const float* tap_weight,
+                                const int64_t* tap_order, const int64_t* offsets, int32_t plain, float* grad_tex, void* stream);
+
 /* ---- HDR image epilogue / prologue ------------------------------------------------
  * reni_unnormalise_srgb replaces, on the device and in one call, the reference's viewing chain
  *   UnMinMaxNormlise(minmax)   src/utils/custom_transforms.py:14-21   y = exp(0.5 (x + 1)(m1 - m0) + m0)
@@ -834,7 +890,7 @@ int reni_set_grad_ready_event(void* hip_event);
  * every launch of the model's entry points (forward, backward, training and latent steps, optimisers, weight lists), of the
  * image, metrics, lights and visibility entry points, and of reni_lobe_denominators, reni_lobe_convolve_backward,
  * reni_envmap_lookup_taps and reni_envmap_lookup_backward.  NOT counted: the shader, raster, baseline (SG, SH), diffuse,
- * resample, blur and rotate entry points, reni_lobe_convolve and reni_envmap_lookup.
+ * resample, blur, rotate and texture entry points, reni_lobe_convolve and reni_envmap_lookup.
  * bench.py reports launches per step: at small problems a step costs its dependent launches. */
 int64_t reni_launch_count(int32_t reset);
 

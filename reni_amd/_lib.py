@@ -27,6 +27,7 @@ SPACE = {"stored": 0, "linear": 1, "srgb": 2}
 SSIM_MODE = {"sphere": 0, "planar": 1}
 VIS_NO_CULL = 1  # RENI_VIS_NO_CULL
 SHADE_TERMS_DS = 1  # RENI_SHADE_TERMS_DS
+TEX_WRAP = {"clamp": 0, "repeat": 1}  # RENI_TEX_*
 
 # every symbol include/reni_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -46,6 +47,8 @@ EXPORTS = (
     "reni_lobe_workspace_bytes", "reni_lobe_convolve", "reni_envmap_lookup",
     "reni_lobe_denominators_workspace_bytes", "reni_lobe_denominators", "reni_lobe_backward_workspace_bytes",
     "reni_lobe_convolve_backward", "reni_envmap_lookup_taps", "reni_envmap_lookup_backward",
+    "reni_mesh_pixel_uv", "reni_texture_taps", "reni_texture_pyramid", "reni_texture_pyramid_backward", "reni_texture_fetch",
+    "reni_texture_fetch_backward",
     "reni_image_workspace_bytes", "reni_unnormalise_srgb", "reni_minmax_normalise",
     "reni_minmax_batch_workspace_bytes", "reni_minmax_normalise_batch",
     "reni_resample", "reni_blur_workspace_bytes", "reni_gaussian_blur", "reni_rotate_envmap",
@@ -253,6 +256,20 @@ def load():
     lib.reni_envmap_lookup_backward.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_void_p]
     lib.reni_envmap_lookup_backward.restype = c_int32
+    lib.reni_mesh_pixel_uv.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_float),
+                                       POINTER(c_float), c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.reni_mesh_pixel_uv.restype = c_int32
+    lib.reni_texture_taps.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_int32, c_int32,
+                                      c_void_p, c_void_p, c_void_p]
+    lib.reni_texture_taps.restype = c_int32
+    for fn in (lib.reni_texture_pyramid, lib.reni_texture_pyramid_backward):
+        fn.argtypes = [c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]
+        fn.restype = c_int32
+    lib.reni_texture_fetch.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.reni_texture_fetch.restype = c_int32
+    lib.reni_texture_fetch_backward.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                                c_void_p]
+    lib.reni_texture_fetch_backward.restype = c_int32
     lib.reni_image_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
     lib.reni_image_workspace_bytes.restype = c_size_t
     lib.reni_unnormalise_srgb.argtypes = [c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_int32, ctypes.c_double,

@@ -19,9 +19,10 @@ from collections import namedtuple
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, ops, textures
 from .envmap_shader import (EnvironmentMap, SpatialMaterials, _Materials, _shared_grid, blinn_phong_shading_gbuffer,
                             blinn_phong_shading_materials)
+from .textures import TexturedMaterials
 
 Fragments = namedtuple("Fragments", ["pix_to_face", "zbuf", "bary_coords", "dists"])
 
@@ -57,6 +58,54 @@ def load_obj(path, device="cpu"):
     v = torch.tensor(verts, dtype=torch.float32).reshape(-1, 3)
     f = torch.tensor(faces, dtype=torch.int64).reshape(-1, 3)
     return v.to(device), f.to(device)
+
+
+def load_obj_uv(path, device="cpu"):
+    """``v``, ``vt`` and ``f`` lines of a Wavefront OBJ file -> (verts float32 [V,3], faces int64 [F,3], verts_uvs float32
+    [Tn,2], faces_uvs int64 [F,3]), with ``load_obj``'s rules: 1-based indices, a negative one counts back from the last
+    ``v`` (``vt``) read so far, a polygon becomes the fan (0, i, i+1).  A corner written ``a`` or ``a//c`` has no texture
+    coordinate: its faces_uvs entry is -1 (a face with such a corner is not textured).  The third value of a ``vt`` line, if
+    any, is ignored.  The UVs have their own indexing: Tn differs from V wherever a seam duplicates a vertex."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"OBJ file not found: {path}")
+    verts, uvs, faces, faces_uv = [], [], [], []
+    with open(path, "r") as fh:
+        for ln, line in enumerate(fh, 1):
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{ln}: a vertex needs three coordinates")
+                verts.append([float(t) for t in tok[1:4]])
+            elif tok[0] == "vt":
+                if len(tok) < 3:
+                    raise ValueError(f"{path}:{ln}: a texture coordinate needs two values")
+                uvs.append([float(t) for t in tok[1:3]])
+            elif tok[0] == "f":
+                idx, tidx = [], []
+                for t in tok[1:]:
+                    part = t.split("/")
+                    i = int(part[0])
+                    if i == 0:
+                        raise ValueError(f"{path}:{ln}: OBJ indices start at 1")
+                    idx.append(i - 1 if i > 0 else len(verts) + i)
+                    if len(part) > 1 and part[1] != "":
+                        j = int(part[1])
+                        if j == 0:
+                            raise ValueError(f"{path}:{ln}: OBJ indices start at 1")
+                        tidx.append(j - 1 if j > 0 else len(uvs) + j)
+                    else:
+                        tidx.append(-1)
+                if len(idx) < 3:
+                    raise ValueError(f"{path}:{ln}: a face needs at least three vertices")
+                faces.extend([idx[0], idx[i], idx[i + 1]] for i in range(1, len(idx) - 1))
+                faces_uv.extend([tidx[0], tidx[i], tidx[i + 1]] for i in range(1, len(tidx) - 1))
+    v = torch.tensor(verts, dtype=torch.float32).reshape(-1, 3)
+    f = torch.tensor(faces, dtype=torch.int64).reshape(-1, 3)
+    vt = torch.tensor(uvs, dtype=torch.float32).reshape(-1, 2)
+    ft = torch.tensor(faces_uv, dtype=torch.int64).reshape(-1, 3)
+    return v.to(device), f.to(device), vt.to(device), ft.to(device)
 
 
 def rotate_axis_angle_y(verts: torch.Tensor, degrees: float) -> torch.Tensor:
@@ -118,14 +167,28 @@ class FoVPerspectiveCameras:
 
 class Meshes:
     """One triangle mesh in pytorch3d's packed form: ``Meshes(verts=[v], faces=[f])``; the vertex normals come from the
-    HIP kernel (a device tensor is needed for them) and are computed once."""
+    HIP kernel (a device tensor is needed for them) and are computed once.  ``verts_uvs=[vt], faces_uvs=[ft]`` (both or
+    neither; ``load_obj_uv``) give the mesh texture coordinates: vt [Tn,2], ft [F,3] with its own indexing, an entry
+    outside [0, Tn) marking a face without them."""
 
-    def __init__(self, verts, faces):
+    def __init__(self, verts, faces, verts_uvs=None, faces_uvs=None):
         if len(verts) != 1 or len(faces) != 1:
             raise ValueError("one mesh per Meshes (several meshes per batch are not supported)")
         self._verts = verts[0].to(torch.float32).contiguous()
         self._faces = faces[0].to(torch.int64).contiguous()
         self._normals = None
+        self._verts_uvs = self._faces_uvs = None
+        if (verts_uvs is None) != (faces_uvs is None):
+            raise ValueError("verts_uvs and faces_uvs come together")
+        if verts_uvs is not None:
+            if len(verts_uvs) != 1 or len(faces_uvs) != 1:
+                raise ValueError("one mesh per Meshes (several meshes per batch are not supported)")
+            vt, ft = verts_uvs[0].to(torch.float32).contiguous(), faces_uvs[0].to(torch.int64).contiguous()
+            if vt.dim() != 2 or vt.shape[1] != 2 or vt.shape[0] < 1:
+                raise ValueError(f"verts_uvs must be [Tn, 2] with Tn >= 1, got {tuple(vt.shape)}")
+            if tuple(ft.shape) != tuple(self._faces.shape):
+                raise ValueError(f"faces_uvs must be [F, 3] like faces, got {tuple(ft.shape)}")
+            self._verts_uvs, self._faces_uvs = vt, ft
 
     def verts_packed(self) -> torch.Tensor:
         return self._verts
@@ -137,6 +200,12 @@ class Meshes:
         if self._normals is None:
             self._normals = ops.vertex_normals(self._verts, self._faces)
         return self._normals
+
+    def verts_uvs_packed(self):
+        return self._verts_uvs
+
+    def faces_uvs_packed(self):
+        return self._faces_uvs
 
     @property
     def device(self):
@@ -162,6 +231,8 @@ class MeshRasterizer(nn.Module):
     training step then costs only the shader (same output).  The key is the identity and in-place version of the mesh's
     tensors and of R, T, so modifying any of them in place re-rasterises."""
 
+    MAX_TAPS_RECORDS = 8  # texture_taps records kept per scene (albedo, ks and shininess textures of a few sizes)
+
     def __init__(self, cameras=None, raster_settings=None):
         super().__init__()
         self.cameras = cameras if cameras is not None else FoVPerspectiveCameras()
@@ -169,6 +240,8 @@ class MeshRasterizer(nn.Module):
         self._cache = None
         self._accel_cache = None
         self._vis_cache = None
+        self._uv_cache = None
+        self._taps_cache = None
 
     def gbuffer(self, meshes_world: Meshes, R=None, T=None):
         """-> (Fragments, pixel_normals [S*S,3], pixel_positions [S*S,3]) (interpolated, not normalised)."""
@@ -212,6 +285,50 @@ class MeshRasterizer(nn.Module):
         self._vis_cache = (key, dirs, vis)  # (dirs is held so that its memory stays its own)
         return vis
 
+    def _uv_key(self, meshes_world: Meshes, R, T):
+        vt, ft = meshes_world.verts_uvs_packed(), meshes_world.faces_uvs_packed()
+        if vt is None:
+            raise ValueError("the mesh has no texture coordinates (Meshes(verts_uvs=, faces_uvs=); load_obj_uv reads them)")
+        self.gbuffer(meshes_world, R, T)
+        return (self._cache[0], tuple((id(t), t._version) for t in (vt, ft)))
+
+    def pixel_uv(self, meshes_world: Meshes, R=None, T=None):
+        """-> (uv [S*S,2], jac [S*S,4], pix_valid [S*S] int64) of the cached G-buffer (``ops.mesh_pixel_uv``): the pixel's
+        texture coordinate, its per-face footprint derivative, and the pixel's face or -1 where nothing textured is seen.
+        Kept beside the G-buffer under its key and the identity and in-place version of the mesh's UV tensors."""
+        key = self._uv_key(meshes_world, R, T)
+        if self._uv_cache is not None and self._uv_cache[0] == key:
+            return self._uv_cache[2]
+        frags = self._cache[2][0]
+        _, (v, f, Rk, Tk), _ = self._cache
+        vt, ft = meshes_world.verts_uvs_packed(), meshes_world.faces_uvs_packed()
+        out = ops.mesh_pixel_uv(v, f, vt, ft, Rk, Tk, self.raster_settings.image_size, frags.pix_to_face, frags.bary_coords,
+                                self.cameras.tan_half_fov())
+        self._uv_cache = (key, (vt, ft), out)
+        return out
+
+    def texture_taps(self, meshes_world: Meshes, R=None, T=None, size=None, levels=None, wrap: str = "clamp",
+                     align_corners: bool = False, lod_bias: float = 0.0):
+        """-> the ``textures.Taps`` of a texture of ``size`` = (H, W) seen through the cached G-buffer: the level per pixel
+        from its footprint, 8 (element, weight) pairs, and the sorted table the gradient is gathered through.  One record is
+        kept per (size, levels, wrap, align_corners, lod_bias) under the key of ``pixel_uv``, the MAX_TAPS_RECORDS newest; a
+        new G-buffer or new UVs drop them all."""
+        if size is None or len(tuple(size)) != 2:
+            raise ValueError("size must be (H, W), the texture's size")
+        key = self._uv_key(meshes_world, R, T)
+        if self._taps_cache is None or self._taps_cache[0] != key:
+            self._taps_cache = (key, {})
+        sub = (int(size[0]), int(size[1]), None if levels is None else int(levels), wrap, bool(align_corners), float(lod_bias))
+        found = self._taps_cache[1].get(sub)
+        if found is None:
+            uv, jac, valid = self.pixel_uv(meshes_world, R, T)
+            found = textures.make_taps(uv, sub[:2], sub[2], jac=jac, pix_valid=valid, wrap=wrap, align_corners=bool(align_corners),
+                                       lod_bias=float(lod_bias))
+            if len(self._taps_cache[1]) >= self.MAX_TAPS_RECORDS:  # (a lod_bias sweep must not keep every table: oldest out)
+                self._taps_cache[1].pop(next(iter(self._taps_cache[1])))
+            self._taps_cache[1][sub] = found
+        return found
+
     def forward(self, meshes_world: Meshes, R=None, T=None, **kwargs) -> Fragments:
         return self.gbuffer(meshes_world, R, T)[0]
 
@@ -232,7 +349,12 @@ class HipMeshRenderer(nn.Module):
     ``materials=SpatialMaterials(...)``: an albedo, a ks and a shininess per render pixel (S*S of them) instead of the
     scalars kd, ks and ``materials.shininess``; the render is then differentiable with respect to them as well (the shader's
     terms path, ``envmap_shader.blinn_phong_shading_materials``), and kd / ks are not used.  With any other ``materials``
-    the call and its bits are the scalar shader's."""
+    the call and its bits are the scalar shader's.
+
+    ``materials=TexturedMaterials(...)``: the material lives in the mesh's UV space (``reni_amd.textures``): the taps come
+    from the rasteriser's cache, the textures are fetched per pixel and go down the same terms path; the render is
+    differentiable with respect to the textures.  Several renderers -- each with its own rasteriser, camera and, through
+    ``shader_cameras=FoVPerspectiveCameras(R=R, T=T)``, its true camera centre -- may share one such object."""
 
     def __init__(self, rasterizer: MeshRasterizer, kd: float = None, ks: float = None, materials=None, shader_cameras=None,
                  shadows: bool = False):
@@ -240,8 +362,9 @@ class HipMeshRenderer(nn.Module):
         self.rasterizer = rasterizer
         self.shadows = bool(shadows)  # cast shadows: the mesh blocks the texels it hides from a pixel
         self.spatial = isinstance(materials, SpatialMaterials)
-        if kd is None and not self.spatial:
-            raise ValueError("kd is required unless materials is a SpatialMaterials")
+        self.textured = isinstance(materials, TexturedMaterials)
+        if kd is None and not self.spatial and not self.textured:
+            raise ValueError("kd is required unless materials is a SpatialMaterials or a TexturedMaterials")
         self.kd = 1.0 if kd is None else float(kd)
         self.ks = 1.0 - self.kd if ks is None else float(ks)
         self.materials = materials if materials is not None else _Materials(500.0)
@@ -260,6 +383,11 @@ class HipMeshRenderer(nn.Module):
             if self.materials.ks.device != nrm.device:
                 self.materials.to(nrm.device)
             colors = blinn_phong_shading_materials(nrm, pos, self.camera_center, envmap, *self.materials.values(), vis=vis)
+        elif self.textured:
+            if self.materials.ks.device != nrm.device:
+                self.materials.to(nrm.device)
+            colors = blinn_phong_shading_materials(nrm, pos, self.camera_center, envmap,
+                                                   *self.materials.values(self.rasterizer, meshes_world, R, T), vis=vis)
         else:
             colors = blinn_phong_shading_gbuffer(nrm, pos, self.camera_center, envmap, self.materials.shininess, self.kd,
                                                  self.ks, vis=vis)
@@ -285,17 +413,27 @@ def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device, shadows: bo
     ``renderer(meshes_world=mesh, R=R, T=T, envmap=...)`` -- without pytorch3d: Materials(shininess=500), ks = 1 - kd, the
     camera at look_at_view_transform(2, 0, 0).  ``device`` must be a GPU device (there is no CPU path).  ``shadows=True``:
     the mesh casts shadows on itself (``HipMeshRenderer(shadows=True)``); the default renders what the reference does.
-    ``materials``: a ``SpatialMaterials`` of img_size x img_size pixels (then kd is not used); None: Materials(shininess=500)."""
-    verts, faces = load_obj(obj_path)
+    ``materials``: a ``SpatialMaterials`` of img_size x img_size pixels, or a ``TexturedMaterials`` (the OBJ's ``vt`` are then
+    read, ``load_obj_uv``); kd is not used with either; None: Materials(shininess=500)."""
+    textured = isinstance(materials, TexturedMaterials)
+    if textured:
+        verts, faces, vt, ft = load_obj_uv(obj_path)
+        if vt.shape[0] < 1:
+            raise ValueError(f"{obj_path} has no texture coordinates (vt lines): TexturedMaterials needs them")
+    else:
+        verts, faces = load_obj(obj_path)
     verts = rotate_axis_angle_y(verts, obj_rotation)
     if torch.device(device).type != "cuda":
         raise _lib.RENILibraryError(f"build_hip_renderer renders on a GPU device, got {device!r}; there is no CPU path")
-    mesh = Meshes(verts=[verts.to(device)], faces=[faces.to(device)])
+    if textured:
+        mesh = Meshes(verts=[verts.to(device)], faces=[faces.to(device)], verts_uvs=[vt.to(device)], faces_uvs=[ft.to(device)])
+    else:
+        mesh = Meshes(verts=[verts.to(device)], faces=[faces.to(device)])
     mesh.verts_normals_packed()
     cameras = FoVPerspectiveCameras(device=device)
     raster = MeshRasterizer(cameras=cameras, raster_settings=RasterizationSettings(image_size=int(img_size)))
-    if materials is not None and not isinstance(materials, SpatialMaterials):
-        raise ValueError("materials must be a SpatialMaterials or None")
+    if materials is not None and not isinstance(materials, (SpatialMaterials, TexturedMaterials)):
+        raise ValueError("materials must be a SpatialMaterials, a TexturedMaterials or None")
     renderer = HipMeshRenderer(raster, kd=kd, materials=_Materials(500.0) if materials is None else materials.to(device),
                                shadows=shadows)
     R, T = look_at_view_transform(2.0, 0.0, 0.0, degrees=True, device=device)

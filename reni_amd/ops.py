@@ -1160,6 +1160,200 @@ def envmap_lookup_backward(grad_out, Lv: int, H: int, W: int, dirs=None, level=N
     return out
 
 
+def texture_levels(H0: int, W0: int, levels=None):
+    """(L, E, sizes): the number of levels of an H0 x W0 texture's pyramid (``levels=None``: the full one, 1 + log2(max(H0, W0))
+    for powers of two and 1 otherwise), the element count E = sum H_l W_l and the [(H_l, W_l)] list.  Raises on a pyramid
+    include/reni_hip.h does not define (L > 1 on a size that is no power of two, L beyond the full pyramid, E >= 2^31)."""
+    H0, W0 = int(H0), int(W0)
+    if H0 < 1 or W0 < 1:
+        raise ValueError(f"a texture needs H0, W0 >= 1, got {(H0, W0)}")
+    pow2 = H0 & (H0 - 1) == 0 and W0 & (W0 - 1) == 0
+    full = max(H0, W0).bit_length() if pow2 else 1
+    L = full if levels is None else int(levels)
+    if L < 1 or L > full:
+        raise ValueError(f"levels must be 1..{full} for a {H0} x {W0} texture (more than one level needs powers of two), got {L}")
+    sizes = [(max(1, H0 >> l), max(1, W0 >> l)) for l in range(L)]
+    E = sum(h * w for h, w in sizes)
+    if E >= 2 ** 31:
+        raise ValueError(f"the pyramid has {E} elements, the limit is 2^31 - 1")
+    return L, E, sizes
+
+
+def mesh_pixel_uv(verts, faces, verts_uvs, faces_uvs, R, T, image_size: int, pix_to_face, bary,
+                  tan_half_fov: float = 0.5773502691896258):
+    """reni_mesh_pixel_uv: (uv [P, 2], jac [P, 4], pix_valid [P] int64) of the P = S^2 pixels of a G-buffer
+    (``rasterize_mesh``'s pix_to_face and bary, any shape with S^2 / 3 S^2 elements): the interpolated texture coordinate, its
+    constant per-face derivative (du/dcol, dv/dcol, du/drow, dv/drow) per pixel step, and the pixel's face, -1 where the pixel
+    is background, its face has no UVs (a faces_uvs entry outside [0, Tn)) or its uv is not finite (then uv = jac = 0)."""
+    verts, faces = _mesh_inputs(verts, faces)
+    _require_cuda(verts_uvs, faces_uvs, pix_to_face, bary)
+    dev = verts.device
+    verts_uvs = verts_uvs.to(torch.float32).contiguous()
+    faces_uvs = faces_uvs.to(torch.int64).contiguous()
+    if verts_uvs.dim() != 2 or verts_uvs.shape[1] != 2 or verts_uvs.shape[0] < 1:
+        raise ValueError(f"verts_uvs must be [Tn, 2] with Tn >= 1, got {tuple(verts_uvs.shape)}")
+    if tuple(faces_uvs.shape) != tuple(faces.shape):
+        raise ValueError(f"faces_uvs must be [F, 3] like faces, got {tuple(faces_uvs.shape)}")
+    S = int(image_size)
+    if S < 1:
+        raise ValueError("image_size must be >= 1")
+    p2f = pix_to_face.to(torch.int64).contiguous()
+    bary = bary.to(torch.float32).contiguous()
+    if p2f.numel() != S * S or bary.numel() != 3 * S * S:
+        raise ValueError(f"pix_to_face and bary must hold {S * S} pixels (and 3 barycentrics each)")
+    if any(t.device != dev for t in (verts_uvs, faces_uvs, p2f, bary)):
+        raise ValueError("the mesh, its UVs and the G-buffer must be on the same device")
+    Rv = [float(x) for x in torch.as_tensor(R).reshape(-1).tolist()]
+    Tv = [float(x) for x in torch.as_tensor(T).reshape(-1).tolist()]
+    if len(Rv) != 9 or len(Tv) != 3:
+        raise ValueError("R must hold 9 values ([1,3,3] or [3,3]) and T 3 ([1,3] or [3])")
+    Rh, Th = (ctypes.c_float * 9)(*Rv), (ctypes.c_float * 3)(*Tv)
+    uv = torch.empty(S * S, 2, dtype=torch.float32, device=dev)
+    jac = torch.empty(S * S, 4, dtype=torch.float32, device=dev)
+    valid = torch.empty(S * S, dtype=torch.int64, device=dev)
+    _call(_lib.load().reni_mesh_pixel_uv, dev, verts.shape[0], faces.shape[0], verts_uvs.shape[0], verts.data_ptr(), faces.data_ptr(),
+          verts_uvs.data_ptr(), faces_uvs.data_ptr(), Rh, Th, float(tan_half_fov), S, p2f.data_ptr(), bary.data_ptr(), uv.data_ptr(),
+          jac.data_ptr(), valid.data_ptr())
+    return uv, jac, valid
+
+
+def texture_taps(uv, size, levels=None, jac=None, pix_valid=None, wrap: str = "clamp", align_corners: bool = False,
+                 lod_bias: float = 0.0):
+    """reni_texture_taps: (tap_index int32 [P, 8], tap_weight [P, 8]) of a lookup at uv [P, 2] into a texture of
+    ``size`` = (H0, W0) with ``levels`` levels (None: the full pyramid): the trilinear fetch's 8 element indices into the
+    [E] pyramid and their weights.  jac [P, 4] (``mesh_pixel_uv``'s) chooses the level per pixel; without it every pixel
+    uses clamp(lod_bias, 0, L - 1).  pix_valid [P] int64: < 0 marks a pixel that fetches exactly 0.  uv, jac and pix_valid
+    are constants (one that requires grad raises)."""
+    H0, W0 = (int(x) for x in size)
+    L, _, _ = texture_levels(H0, W0, levels)
+    if wrap not in _lib.TEX_WRAP:
+        raise ValueError(f'wrap must be "clamp" or "repeat", got {wrap!r}')
+    if align_corners and (L > 1 or wrap != "clamp"):
+        raise ValueError('align_corners=True needs levels=1 and wrap="clamp"')
+    lod_bias = float(lod_bias)
+    if lod_bias != lod_bias or lod_bias in (float("inf"), float("-inf")):
+        raise ValueError("lod_bias must be finite")
+    if not isinstance(uv, torch.Tensor) or uv.dim() != 2 or uv.shape[1] != 2 or uv.shape[0] < 1:
+        raise ValueError(f"uv must be [P, 2] with P >= 1, got {tuple(uv.shape) if isinstance(uv, torch.Tensor) else uv!r}")
+    P = uv.shape[0]
+    for name, t, shape in (("jac", jac, (P, 4)), ("pix_valid", pix_valid, (P,))):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape):
+            raise ValueError(f"{name} must be a tensor {list(shape)}")
+    for name, t in (("uv", uv), ("jac", jac)):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"{name} is a constant of the lookup and must not require grad (only the texture carries a gradient)")
+    _require_cuda(uv, jac, pix_valid)
+    dev = uv.device
+    uv = _f32c(uv)
+    jac = None if jac is None else _f32c(jac)
+    pix_valid = None if pix_valid is None else pix_valid.to(torch.int64).contiguous()
+    if any(t is not None and t.device != dev for t in (jac, pix_valid)):
+        raise ValueError(f"jac and pix_valid must be on {dev}")
+    idx = torch.empty(P, 8, dtype=torch.int32, device=dev)
+    wgt = torch.empty(P, 8, dtype=torch.float32, device=dev)
+    _call(_lib.load().reni_texture_taps, dev, P, uv.data_ptr(), None if jac is None else jac.data_ptr(),
+          None if pix_valid is None else pix_valid.data_ptr(), L, H0, W0, lod_bias, _lib.TEX_WRAP[wrap], 1 if align_corners else 0,
+          idx.data_ptr(), wgt.data_ptr())
+    return idx, wgt
+
+
+def texture_table(tap_index, E: int, tap_weight=None):
+    """What ``texture_fetch_backward`` gathers through: (tap_order [8 P] int64, offsets [E + 1] int64) from tap_index
+    [P, 8] -- a stable sort of the element indices and a searchsorted that bins them per texel, as ``envmap_lookup_table``
+    does.  With tap_weight [P, 8] the taps of weight 0 (the unused next level, every tap of an invalid pixel -- all of which
+    name element 0) are sorted behind offsets[E], outside every texel's range: they add nothing, and a background of
+    invalid pixels would otherwise make element 0's range the longest of the table.  It depends on the taps only: once per
+    (scene, texture size)."""
+    if not isinstance(tap_index, torch.Tensor) or tap_index.dim() != 2 or tap_index.shape[1] != 8 or tap_index.dtype != torch.int32:
+        raise ValueError("tap_index must be an int32 tensor [P, 8]")
+    E = int(E)
+    if E < 1 or E >= 2 ** 31:
+        raise ValueError(f"E must be in [1, 2^31), got {E}")
+    keys = tap_index.reshape(-1).to(torch.int64)
+    if tap_weight is not None:
+        if not isinstance(tap_weight, torch.Tensor) or tuple(tap_weight.shape) != tuple(tap_index.shape) or tap_weight.device != tap_index.device:
+            raise ValueError("tap_weight must be [P, 8] like tap_index, on its device")
+        keys = torch.where(tap_weight.reshape(-1) == 0, torch.full_like(keys, E), keys)
+    keys, order = torch.sort(keys, stable=True)
+    bounds = torch.arange(E + 1, device=tap_index.device, dtype=keys.dtype)
+    offsets = torch.searchsorted(keys, bounds)
+    return order.contiguous(), offsets.to(torch.int64).contiguous()
+
+
+def _texture_buffer(tex, L, H0, W0, what):
+    if not isinstance(tex, torch.Tensor) or tex.dim() != 2 or tex.dtype != torch.float32 or not tex.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor [E, C]")
+    L, E, _ = texture_levels(H0, W0, L)
+    if tex.shape[0] != E or not 1 <= tex.shape[1] <= 8:
+        raise ValueError(f"{what} must be [{E}, C] with 1 <= C <= 8 for {L} levels of {H0} x {W0}, got {tuple(tex.shape)}")
+    _require_cuda(tex)
+    return L
+
+
+def texture_pyramid(tex, levels: int, H0: int, W0: int):
+    """reni_texture_pyramid: fills levels 1 .. L - 1 of the pyramid buffer tex [E, C] from its level 0, IN PLACE (box rule);
+    returns tex."""
+    L = _texture_buffer(tex, levels, int(H0), int(W0), "tex")
+    _call(_lib.load().reni_texture_pyramid, tex.device, L, int(H0), int(W0), tex.shape[1], tex.data_ptr())
+    return tex
+
+
+def texture_pyramid_backward(grad_tex, levels: int, H0: int, W0: int):
+    """reni_texture_pyramid_backward: folds the gradients of levels L - 1 .. 1 of grad_tex [E, C] into level 0, IN PLACE;
+    returns grad_tex, whose first H0 W0 rows are then d loss / d level 0."""
+    L = _texture_buffer(grad_tex, levels, int(H0), int(W0), "grad_tex")
+    _call(_lib.load().reni_texture_pyramid_backward, grad_tex.device, L, int(H0), int(W0), grad_tex.shape[1], grad_tex.data_ptr())
+    return grad_tex
+
+
+def _tap_pair(tap_index, tap_weight):
+    if (not isinstance(tap_weight, torch.Tensor) or tap_weight.dim() != 2 or tap_weight.shape[1] != 8 or tap_weight.dtype != torch.float32):
+        raise ValueError("tap_weight must be a float32 tensor [P, 8]")
+    if tap_index is not None and (not isinstance(tap_index, torch.Tensor) or tap_index.dtype != torch.int32
+                                  or tuple(tap_index.shape) != tuple(tap_weight.shape)):
+        raise ValueError("tap_index must be an int32 tensor [P, 8] like tap_weight")
+    return tap_weight.shape[0]
+
+
+def texture_fetch(tex, tap_index, tap_weight) -> torch.Tensor:
+    """reni_texture_fetch: out [P, C] = sum_k tap_weight[p, k] tex[tap_index[p, k]] for the pyramid buffer tex [E, C]."""
+    P = _tap_pair(tap_index, tap_weight)
+    if not isinstance(tex, torch.Tensor) or tex.dim() != 2 or not 1 <= tex.shape[1] <= 8 or tex.shape[0] < 1:
+        raise ValueError("tex must be [E, C] with 1 <= C <= 8")
+    _require_cuda(tex, tap_index, tap_weight)
+    tex = _f32c(tex)
+    dev = tex.device
+    if tap_index.device != dev or tap_weight.device != dev:
+        raise ValueError(f"the taps are not on {dev}")
+    out = torch.empty(P, tex.shape[1], dtype=torch.float32, device=dev)
+    _call(_lib.load().reni_texture_fetch, dev, P, tex.shape[0], tex.shape[1], tex.data_ptr(), tap_index.contiguous().data_ptr(),
+          tap_weight.contiguous().data_ptr(), out.data_ptr())
+    return out
+
+
+def texture_fetch_backward(grad_out, tap_weight, table, E: int, plain: bool = False) -> torch.Tensor:
+    """reni_texture_fetch_backward: grad_tex [E, C] (0 where nobody sampled) of ``texture_fetch`` for the upstream grad_out
+    [P, C], gathered per texel through table = ``texture_table(tap_index, E, tap_weight)``.  Deterministic; a texel with a long range
+    is summed by the lanes of a wave (plain=True: by one lane, kept for measurements)."""
+    P = _tap_pair(None, tap_weight)
+    if not isinstance(grad_out, torch.Tensor) or grad_out.dim() != 2 or grad_out.shape[0] != P or not 1 <= grad_out.shape[1] <= 8:
+        raise ValueError(f"grad_out must be [{P}, C] with 1 <= C <= 8")
+    order, offsets = table
+    E = int(E)
+    if (not isinstance(order, torch.Tensor) or not isinstance(offsets, torch.Tensor) or tuple(order.shape) != (8 * P,)
+            or tuple(offsets.shape) != (E + 1,) or order.dtype != torch.int64 or offsets.dtype != torch.int64):
+        raise ValueError(f"the table is not one of {P} pixels looked up in {E} elements")
+    _require_cuda(grad_out, tap_weight, order, offsets)
+    grad_out = _f32c(grad_out)
+    dev = grad_out.device
+    if tap_weight.device != dev or order.device != dev or offsets.device != dev:
+        raise ValueError(f"the table is not on {dev}")
+    out = torch.empty(E, grad_out.shape[1], dtype=torch.float32, device=dev)
+    _call(_lib.load().reni_texture_fetch_backward, dev, P, E, grad_out.shape[1], grad_out.data_ptr(), tap_weight.contiguous().data_ptr(),
+          order.contiguous().data_ptr(), offsets.contiguous().data_ptr(), 1 if plain else 0, out.data_ptr())
+    return out
+
+
 def unnormalise_srgb(img: torch.Tensor, minmax=None, srgb: bool = True, want_linear: bool = False):
     """reni_unnormalise_srgb: UnMinMaxNormlise(minmax) (skipped when minmax is None) -> sRGB view, on the device.
     img: [B,3,H,W] or [3,H,W], ANY strides (e.g. a model output viewed as ``out.view(B,H,W,3).permute(0,3,1,2)`` is read

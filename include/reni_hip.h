@@ -469,6 +469,25 @@ int reni_envmap_shade_terms_backward(int64_t B, int64_t NP, int64_t J, const flo
                                      int64_t dirs_batch_stride, const float* shininess, int64_t shininess_stride,
                                      const uint32_t* vis, int64_t vis_batch_stride, const float* d_diffuse,
                                      const float* d_specular, float* dlight_colors, void* ws, size_t ws_bytes, void* stream);
+/* Normal-mapped materials: d loss / d normals of the two sums above, for upstream gradients d_diffuse, d_specular.  With
+ * n_p the given normal, N = n_p / max(|n_p|, 1e-6), H = normalize(V + L), x_l = N.L and x_h = N.H (before their clamps),
+ * a(b,p,j) = sum_c d_diffuse[b,p,c] C[b,j,c] and b'(b,p,j) = sum_c d_specular[b,p,c] C[b,j,c]:
+ *     gN[p]        = sum_b sum_j v ( [x_l > 0] a L_j + [x_h > 0] s_p nh^(s_p - 1) b' H )
+ *     d_normals[p] = (gN - N (N.gN)) / |n_p|  for |n_p| >= 1e-6,  gN / 1e-6 below it (F.normalize's eps branch)
+ * The gates are strict and the clamps at 1 are ignored (x <= 1, and at x = 1 the projection removes the term); a pixel with
+ * a zero normal (background) gets exactly 0 -- torch autograd on a zero normal gives L a / 1e-6 instead, clamp's backward
+ * passing the boundary.  Arguments as for reni_envmap_shade_terms; d_normals is [NP][3].  Each image has its own L when
+ * dirs_batch_stride != 0; the sum over images is taken in image order.  s_p <= 0 or NaN gives unspecified values for that
+ * pixel only, never an access outside the buffers.  Deterministic (fixed-order partial sums, no float atomics); an
+ * all-ones mask gives the bits of vis = NULL.
+ * ws: reni_envmap_shade_terms_dnormals_workspace_bytes(B, NP, J) bytes (0 is returned for a size < 1); always needed. */
+size_t reni_envmap_shade_terms_dnormals_workspace_bytes(int64_t B, int64_t NP, int64_t J);
+int reni_envmap_shade_terms_dnormals(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions,
+                                     float cam_x, float cam_y, float cam_z, const float* light_dirs,
+                                     int64_t dirs_batch_stride, const float* light_colors, const float* shininess,
+                                     int64_t shininess_stride, const uint32_t* vis, int64_t vis_batch_stride,
+                                     const float* d_diffuse, const float* d_specular, float* d_normals, void* ws,
+                                     size_t ws_bytes, void* stream);
 
 /* ---- environment-map baselines: spherical Gaussians and spherical harmonics ----------------------------------------
  * What RENI is compared against.  fp32, deterministic (no float atomics; fixed summation order: two calls give identical

@@ -42,6 +42,7 @@ EXPORTS = (
     "reni_mesh_visibility_accel_bytes", "reni_mesh_visibility_prepare", "reni_mesh_visibility",
     "reni_envmap_shade_masked", "reni_envmap_shade_masked_backward",
     "reni_envmap_shade_terms_workspace_bytes", "reni_envmap_shade_terms", "reni_envmap_shade_terms_backward",
+    "reni_envmap_shade_terms_dnormals_workspace_bytes", "reni_envmap_shade_terms_dnormals",
     "reni_sg_workspace_bytes", "reni_sg_render", "reni_sg_loss_grad", "reni_sh_project", "reni_sh_reconstruct",
     "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
     "reni_lobe_workspace_bytes", "reni_lobe_convolve", "reni_envmap_lookup",
@@ -211,6 +212,11 @@ def load():
     lib.reni_envmap_shade_terms.restype = c_int32
     lib.reni_envmap_shade_terms_backward.argtypes = terms + mats + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.reni_envmap_shade_terms_backward.restype = c_int32
+    lib.reni_envmap_shade_terms_dnormals_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    lib.reni_envmap_shade_terms_dnormals_workspace_bytes.restype = c_size_t
+    lib.reni_envmap_shade_terms_dnormals.argtypes = (terms + [c_void_p] + mats +  # .. light_colors, materials, gD, gS, d_normals, ws ..
+                                                     [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p])
+    lib.reni_envmap_shade_terms_dnormals.restype = c_int32
     lib.reni_sg_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int64]
     lib.reni_sg_workspace_bytes.restype = c_size_t
     lib.reni_sg_render.argtypes = [c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,

@@ -407,6 +407,173 @@ __global__ void __launch_bounds__(256) k_terms_reduce(const TermsReduceArgs a) {
   out[i] = s;
 }
 
+// ---- normal-mapped materials: d loss / d normals of the terms --------------------------------------------
+// With x_l = N.L, x_h = N.H before their clamps, a = sum_c gD[b,p,c] C[b,j,c] and b' = sum_c gS[b,p,c] C[b,j,c]:
+//
+//   gN[p]        = sum_b sum_j v ( [x_l > 0] a L + [x_h > 0] s_p nh^(s_p - 1) b' H )       (d loss / d N, N the unit normal)
+//   d_normals[p] = (gN - N (N.gN)) / |n_p|,   gN / 1e-6 where |n_p| < 1e-6                  (F.normalize's Jacobian)
+//
+// The gates are strict and the clamps at 1 are ignored (x <= 1, and at x = 1 the projection removes the term), so a
+// background pixel (n_p = 0: x_l = x_h = 0) gets exactly 0.  A sibling of the OWN_PIXEL forward: a thread owns pixel p -- N,
+// V, s_p and the rows gD[b,p,:], gS[b,p,:] of the chunk's BC images in registers -- and walks the texels through the
+// forward's stage (L and the C rows of the BC images).  Per pair shade_pair's three transcendentals (s nh^(s-1) =
+// s exp2((s - 1) log2 nh), selected to 0 where nh = 0), 6 BC multiply-adds for a and b', 6 for the accumulators.  The texel
+// axis is split over blockIdx.y; every (chunk, split) writes its own partial slot and k_terms_dn_reduce sums them in a
+// fixed order and applies the Jacobian once.
+struct TermsDnArgs {
+  const float* nrm;        // [NP][3]
+  const float* pos;        // [NP][3]
+  const float* ldir;       // [J][3] texel directions of the image chunk's first image
+  const float* col;        // C [B][J][3]
+  const float* gD;         // [B][NP][3]
+  const float* gS;         // [B][NP][3]
+  const float* shin;       // s_p = shin[p * shin_stride]
+  float* part;             // [S][NP][3] partial sums of this chunk
+  float cam[3];
+  int shin_stride;
+  int B, NP, J, b0, nb;
+  int per_split;
+  const uint32_t* vis;     // MASKED: as ShadeArgs::vis
+  int JW;
+};
+
+template <int BC, bool MASKED>
+__global__ void __launch_bounds__(256) k_envmap_terms_dn(const TermsDnArgs a) {
+  constexpr int NSRC = 3 * BC;
+  constexpr int ROW = 4 * ((NSRC + 3) / 4);
+  __shared__ float4 g0[SH_TILE];           // texel (Lx, Ly, Lz, -)
+  __shared__ float4 sv[SH_TILE][ROW / 4];  // C rows of the BC images
+  const int tid = threadIdx.x;
+  const int o = blockIdx.x * 256 + tid;
+  const bool live = o < a.NP;
+  float N[3] = {0.f, 0.f, 0.f}, V[3] = {0.f, 0.f, 0.f}, shin = 1.f;
+  float gd[BC][3], gs[BC][3];
+#pragma unroll
+  for (int b = 0; b < BC; ++b)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { gd[b][c] = 0.f; gs[b][c] = 0.f; }
+  if (live) {
+    N[0] = a.nrm[(size_t)o * 3]; N[1] = a.nrm[(size_t)o * 3 + 1]; N[2] = a.nrm[(size_t)o * 3 + 2];
+    normalize3(N);
+    V[0] = a.cam[0] - a.pos[(size_t)o * 3]; V[1] = a.cam[1] - a.pos[(size_t)o * 3 + 1]; V[2] = a.cam[2] - a.pos[(size_t)o * 3 + 2];
+    normalize3(V);
+    shin = a.shin[(size_t)o * a.shin_stride];
+#pragma unroll
+    for (int b = 0; b < BC; ++b) {
+      if (b < a.nb) {  // (beyond the chunk's images the rows stay 0, as the stage's do: they add nothing)
+        const size_t i = ((size_t)(a.b0 + b) * a.NP + o) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { gd[b][c] = a.gD[i + c]; gs[b][c] = a.gS[i + c]; }
+      }
+    }
+  }
+  const float sm1 = shin - 1.f;
+  float acc[3] = {0.f, 0.f, 0.f};
+
+  auto pair = [&](int e, bool on) {
+    const float4 q0 = g0[e];
+    const float Lo[3] = {q0.x, q0.y, q0.z};
+    const PairTerms t = shade_pair(N, V, Lo);
+    // H, in shade_pair's own expressions: inlined, they are the same values, computed once (one rsq per pair)
+    const float hx = V[0] + Lo[0], hy = V[1] + Lo[1], hz = V[2] + Lo[2];
+    const float inv = __builtin_amdgcn_rsqf(fmaxf(fmaf(hz, hz, fmaf(hy, hy, hx * hx)), 1e-12f));
+    const float Hv[3] = {hx * inv, hy * inv, hz * inv};
+    const float* r = (const float*)sv[e];
+    float ad = 0.f, as = 0.f;
+#pragma unroll
+    for (int b = 0; b < BC; ++b) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        ad = fmaf(gd[b][c], r[3 * b + c], ad);
+        as = fmaf(gs[b][c], r[3 * b + c], as);
+      }
+    }
+    // the clamp maps x <= 0 to 0, so nl > 0 is x_l > 0 and nh > 0 is x_h > 0; at nh = 0 the power is 0, inf or NaN: selected away
+    const float w = shin * __builtin_amdgcn_exp2f(sm1 * t.lg);
+    float cl = t.nl > 0.f ? ad : 0.f;
+    float ch = t.nh > 0.f ? w * as : 0.f;
+    if (MASKED) { cl = on ? cl : 0.f; ch = on ? ch : 0.f; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] = fmaf(ch, Hv[k], fmaf(cl, Lo[k], acc[k]));
+  };
+
+  const int t_begin = blockIdx.y * a.per_split, t_end = min(a.J, t_begin + a.per_split);
+  for (int t0 = t_begin; t0 < t_end; t0 += SH_TILE) {
+    __syncthreads();
+    if (tid < SH_TILE) {
+      const int t = t0 + tid;
+      float4 q0 = {0.f, 0.f, 0.f, 0.f};
+      if (t < t_end) { q0.x = a.ldir[(size_t)t * 3]; q0.y = a.ldir[(size_t)t * 3 + 1]; q0.z = a.ldir[(size_t)t * 3 + 2]; }
+      g0[tid] = q0;
+    }
+    {  // source rows, zero beyond the range / the chunk's images
+      float* svf = (float*)sv;
+      for (int i = tid; i < SH_TILE * NSRC; i += 256) {
+        const int e = i / NSRC, r = i - e * NSRC, b = r / 3, c = r - b * 3;
+        const int t = t0 + e;
+        float x = 0.f;
+        if (t < t_end && b < a.nb) x = a.col[((size_t)(a.b0 + b) * a.J + t) * 3 + c];
+        svf[e * ROW + r] = x;
+      }
+    }
+    __syncthreads();
+    const int cnt = min(SH_TILE, t_end - t0);
+    if constexpr (MASKED) {
+      uint32_t wv[4] = {0u, 0u, 0u, 0u};
+      if (live) {  // (t0 is a multiple of SH_TILE: per_split is)
+        const uint32_t* row = a.vis + (size_t)o * a.JW;
+        const int w0 = t0 >> 5;
+        if ((a.JW & 3) == 0) {
+          const uint4 q = *(const uint4*)(row + w0);
+          wv[0] = q.x; wv[1] = q.y; wv[2] = q.z; wv[3] = q.w;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) wv[k] = w0 + k < a.JW ? row[w0 + k] : 0u;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {  // the ascending walk of the unmasked instance, 32 elements per mask word
+        const int e_end = min(cnt, 32 * k + 32);
+        for (int e = 32 * k; e < e_end; ++e) pair(e, (wv[k] >> (e & 31)) & 1u);
+      }
+    } else {
+      for (int e = 0; e < cnt; ++e) pair(e, true);
+    }
+  }
+  if (live) {
+    float* dst = a.part + ((size_t)blockIdx.y * a.NP + o) * 3;
+    dst[0] = acc[0]; dst[1] = acc[1]; dst[2] = acc[2];
+  }
+}
+
+// gN[p] = sum over the image chunks (ascending) of the chunk's sum over its splits (ascending) of part[chunk][split][p],
+// then d_normals[p] = (gN - N (N.gN)) / |n_p|, or gN / 1e-6 under F.normalize's eps
+struct TermsDnReduceArgs { const float* part; const float* nrm; float* out; int NP, S, NCH; };
+__global__ void __launch_bounds__(256) k_terms_dn_reduce(const TermsDnReduceArgs a) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.NP) return;
+  float g[3] = {0.f, 0.f, 0.f};
+  for (int ch = 0; ch < a.NCH; ++ch) {
+    float cs[3] = {0.f, 0.f, 0.f};
+    for (int q = 0; q < a.S; ++q) {
+      const float* src = a.part + (((size_t)ch * a.S + q) * a.NP + p) * 3;
+      cs[0] += src[0]; cs[1] += src[1]; cs[2] += src[2];
+    }
+    g[0] += cs[0]; g[1] += cs[1]; g[2] += cs[2];
+  }
+  const float n[3] = {a.nrm[(size_t)p * 3], a.nrm[(size_t)p * 3 + 1], a.nrm[(size_t)p * 3 + 2]};
+  const float len = sqrtf(fmaf(n[2], n[2], fmaf(n[1], n[1], n[0] * n[0])));
+  const float inv = 1.f / fmaxf(len, 1e-6f);
+  float* out = a.out + (size_t)p * 3;
+  if (len >= 1e-6f) {
+    const float N[3] = {n[0] * inv, n[1] * inv, n[2] * inv};
+    const float d = fmaf(N[2], g[2], fmaf(N[1], g[1], N[0] * g[0]));
+    out[0] = fmaf(-N[0], d, g[0]) * inv; out[1] = fmaf(-N[1], d, g[1]) * inv; out[2] = fmaf(-N[2], d, g[2]) * inv;
+  } else {
+    out[0] = g[0] * inv; out[1] = g[1] * inv; out[2] = g[2] * inv;
+  }
+}
+
 }  // namespace reni
 
 namespace {
@@ -547,6 +714,58 @@ int terms_common(bool forward, int64_t B, int64_t NP, int64_t J, const float* no
   return tu_launch(TU_PLAIN, reni::k_terms_reduce, dim3((unsigned)((n + 255) / 256), (unsigned)NT), dim3(256), 0, s, r);
 }
 
+// d loss / d normals of the terms: one launch per image chunk into its own partial slots, then the fixed-order reduce
+int terms_dnormals_common(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cx, float cy,
+                          float cz, const float* light_dirs, int64_t dirs_bstride, const float* light_colors,
+                          const float* shininess, int64_t shin_stride, const uint32_t* vis, int64_t vis_bstride,
+                          const float* gD, const float* gS, float* d_normals, void* ws, size_t ws_bytes, void* stream) {
+  if (B < 1 || NP < 1 || J < 1) return reni_set_error(RENI_EINVAL, "envmap shade terms dnormals: B, NP and J must be >= 1");
+  if (NP > 0x3fffffff || J > 0x3fffffff || B > 0xffff)
+    return reni_set_error(RENI_EINVAL, "envmap shade terms dnormals: problem too large");
+  if (!normals || !positions || !light_dirs || !light_colors || !shininess || !gD || !gS || !d_normals)
+    return reni_set_error(RENI_EINVAL, "envmap shade terms dnormals: NULL argument");
+  if (dirs_bstride != 0 && dirs_bstride < J * 3)
+    return reni_set_error(RENI_EINVAL, "envmap shade terms dnormals: direction batch stride must be 0 or >= 3 J");
+  if (shin_stride != 0 && shin_stride != 1)
+    return reni_set_error(RENI_EINVAL, "envmap shade terms dnormals: shininess stride must be 0 (one value) or 1 (per pixel)");
+  const int64_t JW = (J + 31) / 32;
+  const bool masked = vis != nullptr;
+  if (masked) {
+    if (((uintptr_t)vis & 15) != 0) return reni_set_error(RENI_EINVAL, "envmap shade terms dnormals: the mask must be 16-byte aligned");
+    if (vis_bstride != 0 && (dirs_bstride == 0 || vis_bstride < NP * JW || ((JW & 3) == 0 && (vis_bstride & 3) != 0)))
+      return reni_set_error(RENI_EINVAL, "envmap shade terms dnormals: mask batch stride must be 0 (required with shared directions) or >= NP ceil(J/32) words");
+  }
+  const int step = dirs_bstride == 0 ? SHADE_BC : 1;  // as in shade_common
+  const int64_t n_chunks = (B + step - 1) / step;
+  const int S = n_splits(NP, J);
+  const size_t need = (size_t)n_chunks * S * NP * 3 * sizeof(float);
+  if (!ws || ws_bytes < need) return reni_set_error(RENI_EWORKSPACE, "envmap shade terms dnormals: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  reni::TermsDnArgs a;
+  a.nrm = normals; a.pos = positions; a.col = light_colors; a.gD = gD; a.gS = gS;
+  a.shin = shininess; a.shin_stride = (int)shin_stride;
+  a.cam[0] = cx; a.cam[1] = cy; a.cam[2] = cz;
+  a.B = (int)B; a.NP = (int)NP; a.J = (int)J;
+  const int64_t tiles = (J + reni::SH_TILE - 1) / reni::SH_TILE;
+  a.per_split = (int)((tiles + S - 1) / S) * reni::SH_TILE;
+  a.vis = nullptr; a.JW = (int)JW;
+  const dim3 grid((unsigned)((NP + 255) / 256), (unsigned)S);
+  using reni::k_envmap_terms_dn;
+  const auto k = step == 1 ? (masked ? k_envmap_terms_dn<1, true> : k_envmap_terms_dn<1, false>)
+                           : (masked ? k_envmap_terms_dn<SHADE_BC, true> : k_envmap_terms_dn<SHADE_BC, false>);
+  int64_t chunk = 0;
+  for (int64_t b0 = 0; b0 < B; b0 += step, ++chunk) {
+    a.b0 = (int)b0; a.nb = (int)((B - b0) < step ? (B - b0) : step);
+    a.ldir = light_dirs + (size_t)b0 * dirs_bstride;
+    if (masked) a.vis = vis + (size_t)b0 * vis_bstride;
+    a.part = (float*)ws + (size_t)chunk * S * NP * 3;
+    if (int rc = tu_launch(TU_PLAIN, k, grid, dim3(256), 0, s, a)) return rc;
+  }
+  reni::TermsDnReduceArgs r;
+  r.part = (const float*)ws; r.nrm = normals; r.out = d_normals; r.NP = (int)NP; r.S = S; r.NCH = (int)n_chunks;
+  return tu_launch(TU_PLAIN, reni::k_terms_dn_reduce, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, r);
+}
+
 }  // namespace
 
 extern "C" {
@@ -616,6 +835,23 @@ int reni_envmap_shade_terms_backward(int64_t B, int64_t NP, int64_t J, const flo
   return terms_common(false, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, d_diffuse,
                       d_specular, shininess, shininess_stride, vis, vis_batch_stride, dlight_colors, nullptr, nullptr, ws,
                       ws_bytes, stream);
+}
+
+size_t reni_envmap_shade_terms_dnormals_workspace_bytes(int64_t B, int64_t NP, int64_t J) {
+  if (B < 1 || NP < 1 || J < 1) return 0;
+  // one slot per (image chunk, split): per-image directions make every image a chunk
+  return (size_t)B * n_splits(NP, J) * NP * 3 * sizeof(float) + 256;
+}
+
+int reni_envmap_shade_terms_dnormals(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions,
+                                     float cam_x, float cam_y, float cam_z, const float* light_dirs,
+                                     int64_t dirs_batch_stride, const float* light_colors, const float* shininess,
+                                     int64_t shininess_stride, const uint32_t* vis, int64_t vis_batch_stride,
+                                     const float* d_diffuse, const float* d_specular, float* d_normals, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  return terms_dnormals_common(B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, light_colors,
+                               shininess, shininess_stride, vis, vis_batch_stride, d_diffuse, d_specular, d_normals, ws,
+                               ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -125,8 +125,38 @@ def _constant(what, t):
     return t
 
 
-def _shade_terms(light_colors, light_dirs, pixel_normals, pixel_positions, camera_center, shininess, vis=None):
-    _constant("the pixel normals", pixel_normals)
+class _ShadeTermsNormalsFn(torch.autograd.Function):
+    """``_ShadeTermsFn`` with one more differentiable input, the (un-normalised) pixel normals: their gradient comes from
+    ``ops.envmap_shade_terms_dnormals``, and only when somebody asks for it.  The forward call is the same kernel."""
+
+    @staticmethod
+    def forward(ctx, light_colors, shininess, normals, positions, camera_center, light_dirs, vis, need_ds):
+        D, S, T = ops.envmap_shade_terms(normals, positions, camera_center, light_dirs, light_colors, shininess, vis=vis,
+                                         need_ds=need_ds)
+        ctx.save_for_backward(normals, positions, camera_center, light_dirs, shininess, T, light_colors)
+        ctx.vis = vis
+        return D, S
+
+    @staticmethod
+    def backward(ctx, gD, gS):
+        normals, positions, camera_center, light_dirs, shininess, T, light_colors = ctx.saved_tensors
+        gC = gs = gn = None
+        gD, gS = gD.contiguous(), gS.contiguous()
+        if ctx.needs_input_grad[0]:
+            gC = ops.envmap_shade_terms_backward(normals, positions, camera_center, light_dirs, gD, gS, shininess, vis=ctx.vis)
+        if ctx.needs_input_grad[1] and T is not None:
+            gs = (gS * T).sum(dim=(0, 2))
+            gs = (gs.sum() if shininess.numel() == 1 else gs).reshape(shininess.shape).to(shininess.dtype)
+        if ctx.needs_input_grad[2]:
+            gn = ops.envmap_shade_terms_dnormals(normals, positions, camera_center, light_dirs, light_colors, gD, gS,
+                                                 shininess, vis=ctx.vis).to(normals.dtype)
+        return gC, gs, gn, None, None, None, None, None
+
+
+def _shade_terms(light_colors, light_dirs, pixel_normals, pixel_positions, camera_center, shininess, vis=None,
+                 differentiable_normals=False):
+    if not differentiable_normals:
+        _constant("the pixel normals", pixel_normals)
     _constant("the pixel positions", pixel_positions)
     _constant("the light directions", light_dirs)
     cam = torch.as_tensor(_constant("the camera centre", camera_center), dtype=torch.float32).reshape(-1)[:3].cpu()
@@ -137,8 +167,8 @@ def _shade_terms(light_colors, light_dirs, pixel_normals, pixel_positions, camer
         raise ValueError(f"shininess must be a float, one value or [{NP}] (one per pixel), got {tuple(shininess.shape)}")
     dirs = _shared_grid(light_dirs)
     need_ds = bool(shininess.requires_grad and torch.is_grad_enabled())  # T = dS/ds only when somebody will ask for it
-    return _ShadeTermsFn.apply(light_colors, shininess, pixel_normals, pixel_positions, cam, dirs,
-                               _constant_mask(vis, NP, dirs), need_ds)
+    fn = _ShadeTermsNormalsFn if differentiable_normals else _ShadeTermsFn
+    return fn.apply(light_colors, shininess, pixel_normals, pixel_positions, cam, dirs, _constant_mask(vis, NP, dirs), need_ds)
 
 
 def shade_terms(pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap, shininess, vis=None):
@@ -147,6 +177,15 @@ def shade_terms(pixel_normals, pixel_positions, camera_center, envmap: Environme
     ``compose_materials`` turns them into colours.  Differentiable with respect to ``envmap.environment_map`` and
     ``shininess``; normals, positions, camera, directions and the mask are constants (one that requires grad raises)."""
     return _shade_terms(envmap.environment_map, envmap.directions, pixel_normals, pixel_positions, camera_center, shininess, vis)
+
+
+def shade_terms_normals(pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap, shininess, vis=None):
+    """``shade_terms`` whose ``pixel_normals`` may require grad (normal-mapped materials, ``textures.perturb_normals``): the
+    same forward kernel and the same gradients for the map and the shininess, plus d loss / d pixel_normals through
+    ``ops.envmap_shade_terms_dnormals`` (the normalisation's Jacobian included; strict gates, so a zero normal gets exactly
+    0).  Positions, camera, directions and the mask stay constants."""
+    return _shade_terms(envmap.environment_map, envmap.directions, pixel_normals, pixel_positions, camera_center, shininess, vis,
+                        differentiable_normals=True)
 
 
 def specular_norm(shininess: torch.Tensor) -> torch.Tensor:
@@ -179,10 +218,12 @@ def compose_materials(D: torch.Tensor, S: torch.Tensor, albedo, ks, shininess) -
 
 
 def blinn_phong_shading_materials(pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap, albedo, ks,
-                                  shininess, vis=None) -> torch.Tensor:
+                                  shininess, vis=None, differentiable_normals: bool = False) -> torch.Tensor:
     """colours [B, NP, 3] with a material per pixel: ``compose_materials(*shade_terms(...), albedo, ks, shininess)``.
-    Differentiable with respect to the environment map, albedo, ks and shininess."""
-    D, S = shade_terms(pixel_normals, pixel_positions, camera_center, envmap, shininess, vis=vis)
+    Differentiable with respect to the environment map, albedo, ks and shininess, and, with ``differentiable_normals``
+    (``shade_terms_normals``), the pixel normals."""
+    terms = shade_terms_normals if differentiable_normals else shade_terms
+    D, S = terms(pixel_normals, pixel_positions, camera_center, envmap, shininess, vis=vis)
     return compose_materials(D, S, albedo, ks, shininess)
 
 

@@ -242,6 +242,7 @@ class MeshRasterizer(nn.Module):
         self._vis_cache = None
         self._uv_cache = None
         self._taps_cache = None
+        self._tangent_cache = None
 
     def gbuffer(self, meshes_world: Meshes, R=None, T=None):
         """-> (Fragments, pixel_normals [S*S,3], pixel_positions [S*S,3]) (interpolated, not normalised)."""
@@ -307,6 +308,20 @@ class MeshRasterizer(nn.Module):
         self._uv_cache = (key, (vt, ft), out)
         return out
 
+    def pixel_tangents(self, meshes_world: Meshes, R=None, T=None):
+        """-> (tangent [S*S,3], bitangent [S*S,3], valid [S*S] bool) of the cached G-buffer: the frame a tangent-space normal
+        map is read in (``textures.tangent_frames`` on the pixel's face, its UVs and the G-buffer normal; plain torch, once
+        per scene).  Kept beside ``pixel_uv`` under the same key."""
+        key = self._uv_key(meshes_world, R, T)
+        if self._tangent_cache is not None and self._tangent_cache[0] == key:
+            return self._tangent_cache[2]
+        _, _, valid = self.pixel_uv(meshes_world, R, T)
+        _, (v, f, _, _), (_, nrm, _) = self._cache
+        vt, ft = meshes_world.verts_uvs_packed(), meshes_world.faces_uvs_packed()
+        out = textures.tangent_frames(v, f, vt, ft, valid, nrm)
+        self._tangent_cache = (key, (vt, ft), out)
+        return out
+
     def texture_taps(self, meshes_world: Meshes, R=None, T=None, size=None, levels=None, wrap: str = "clamp",
                      align_corners: bool = False, lod_bias: float = 0.0):
         """-> the ``textures.Taps`` of a texture of ``size`` = (H, W) seen through the cached G-buffer: the level per pixel
@@ -354,7 +369,10 @@ class HipMeshRenderer(nn.Module):
     ``materials=TexturedMaterials(...)``: the material lives in the mesh's UV space (``reni_amd.textures``): the taps come
     from the rasteriser's cache, the textures are fetched per pixel and go down the same terms path; the render is
     differentiable with respect to the textures.  Several renderers -- each with its own rasteriser, camera and, through
-    ``shader_cameras=FoVPerspectiveCameras(R=R, T=T)``, its true camera centre -- may share one such object."""
+    ``shader_cameras=FoVPerspectiveCameras(R=R, T=T)``, its true camera centre -- may share one such object.  With a
+    ``normal`` texture the shader gets ``materials.shading_normals(...)`` (the normal map's) instead of the G-buffer's normals,
+    and the render is differentiable with respect to that texture when it requires grad; the shadow mask and the returned
+    ``pixel_normals`` stay the geometry's (``shading_normals(mesh, R, T)`` returns the bent ones)."""
 
     def __init__(self, rasterizer: MeshRasterizer, kd: float = None, ks: float = None, materials=None, shader_cameras=None,
                  shadows: bool = False):
@@ -386,13 +404,28 @@ class HipMeshRenderer(nn.Module):
         elif self.textured:
             if self.materials.ks.device != nrm.device:
                 self.materials.to(nrm.device)
-            colors = blinn_phong_shading_materials(nrm, pos, self.camera_center, envmap,
-                                                   *self.materials.values(self.rasterizer, meshes_world, R, T), vis=vis)
+            shade_nrm = nrm
+            if self.materials.normal is not None:  # a normal map bends the shading normals; shadows keep the geometry's mask
+                shade_nrm = self.materials.shading_normals(self.rasterizer, meshes_world, R, T, nrm)
+            colors = blinn_phong_shading_materials(shade_nrm, pos, self.camera_center, envmap,
+                                                   *self.materials.values(self.rasterizer, meshes_world, R, T), vis=vis,
+                                                   differentiable_normals=shade_nrm.requires_grad)
         else:
             colors = blinn_phong_shading_gbuffer(nrm, pos, self.camera_center, envmap, self.materials.shininess, self.kd,
                                                  self.ks, vis=vis)
         normals = torch.nn.functional.normalize(nrm, p=2, dim=-1, eps=1e-6).reshape(1, S, S, 3).repeat(B, 1, 1, 1)
         return colors.reshape(B, S, S, 3), normals
+
+    def shading_normals(self, meshes_world: Meshes, R=None, T=None) -> torch.Tensor:
+        """The unit normals the shader uses, [S, S, 3]: the G-buffer's, bent by the materials' normal texture where there is
+        one (``forward`` keeps returning the geometric ones)."""
+        _, nrm, _ = self.rasterizer.gbuffer(meshes_world, R, T)
+        S = self.rasterizer.raster_settings.image_size
+        if self.textured and self.materials.normal is not None:
+            if self.materials.ks.device != nrm.device:
+                self.materials.to(nrm.device)
+            nrm = self.materials.shading_normals(self.rasterizer, meshes_world, R, T, nrm)
+        return torch.nn.functional.normalize(nrm, p=2, dim=-1, eps=1e-6).reshape(S, S, 3)
 
 
 def unpack_visibility(vis: torch.Tensor, J: int) -> torch.Tensor:

@@ -607,7 +607,8 @@ def envmap_shade_backward(normals, positions, camera_center, light_dirs, dcolors
 
 def _terms_call(forward: bool, normals, positions, camera_center, light_dirs, srcs, shininess, vis, need_ds=False):
     """reni_envmap_shade_terms / reni_envmap_shade_terms_backward (include/reni_hip.h) behind the checks of ``_shade_call``.
-    srcs: (light colours [B,J,3],) forward, (gD, gS) [B,NP,3] backward; shininess: a float, a one-element tensor or [NP]."""
+    srcs: (light colours [B,J,3],) forward, (gD, gS) [B,NP,3] backward; shininess: a float, a one-element tensor or [NP].
+    forward None: reni_envmap_shade_terms_dnormals, srcs = (light colours, gD, gS)."""
     _dirs_dims(light_dirs)
     if not isinstance(normals, torch.Tensor) or normals.dim() != 2:
         raise ValueError("normals and positions must be [NP, 3]")
@@ -637,8 +638,9 @@ def _terms_call(forward: bool, normals, positions, camera_center, light_dirs, sr
         if light_dirs.shape[0] != B:
             raise ValueError("light_dirs batch size must match the colours'")
         J, stride = light_dirs.shape[1], light_dirs.shape[1] * 3
-    want = (B, J, 3) if forward else (B, NP, 3)
-    for x in srcs:
+    dnormals = forward is None
+    for i, x in enumerate(srcs):
+        want = (B, J, 3) if (forward or (dnormals and i == 0)) else (B, NP, 3)
         if tuple(x.shape) != want:
             raise ValueError(f"expected a {want} tensor, got {tuple(x.shape)}")
     if isinstance(shininess, torch.Tensor):
@@ -646,7 +648,10 @@ def _terms_call(forward: bool, normals, positions, camera_center, light_dirs, sr
     else:
         shin = torch.full((1,), float(shininess), dtype=f32, device=dev)
     cam = [float(x) for x in torch.as_tensor(camera_center).reshape(-1)[:3].tolist()]
-    nbytes = int(lib.reni_envmap_shade_terms_workspace_bytes(B, NP, J, _lib.SHADE_TERMS_DS if need_ds else 0))
+    if dnormals:
+        nbytes = int(lib.reni_envmap_shade_terms_dnormals_workspace_bytes(B, NP, J))
+    else:
+        nbytes = int(lib.reni_envmap_shade_terms_workspace_bytes(B, NP, J, _lib.SHADE_TERMS_DS if need_ds else 0))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     vptr, vstride = None, 0
     if vis is not None:
@@ -654,6 +659,11 @@ def _terms_call(forward: bool, normals, positions, camera_center, light_dirs, sr
         vptr, vstride = vis.data_ptr(), (0 if vis.shape[0] == 1 else NP * vis.shape[2])
     head = (B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride)
     mats = (shin.data_ptr(), 0 if shin.numel() == 1 else 1, vptr, vstride)
+    if dnormals:
+        out = torch.empty((NP, 3), dtype=f32, device=dev)
+        _call(lib.reni_envmap_shade_terms_dnormals, dev, *head, srcs[0].data_ptr(), *mats, srcs[1].data_ptr(), srcs[2].data_ptr(),
+              out.data_ptr(), ws.data_ptr(), nbytes)
+        return out
     if forward:
         outs = [torch.empty((B, NP, 3), dtype=f32, device=dev) for _ in range(3 if need_ds else 2)]
         _call(lib.reni_envmap_shade_terms, dev, *head, srcs[0].data_ptr(), *mats, outs[0].data_ptr(), outs[1].data_ptr(),
@@ -676,6 +686,12 @@ def envmap_shade_terms(normals, positions, camera_center, light_dirs, light_colo
 def envmap_shade_terms_backward(normals, positions, camera_center, light_dirs, gD, gS, shininess, vis=None):
     """d loss / d light_colors [B,J,3] for upstream gradients gD, gS [B,NP,3] of ``envmap_shade_terms``' D and S."""
     return _terms_call(False, normals, positions, camera_center, light_dirs, (gD, gS), shininess, vis)
+
+
+def envmap_shade_terms_dnormals(normals, positions, camera_center, light_dirs, light_colors, gD, gS, shininess, vis=None):
+    """d loss / d normals [NP,3] for upstream gradients gD, gS [B,NP,3] of ``envmap_shade_terms``' D and S, through
+    F.normalize's Jacobian (the normals are given un-normalised).  Strict gates: a pixel with a zero normal gets exactly 0."""
+    return _terms_call(None, normals, positions, camera_center, light_dirs, (light_colors, gD, gS), shininess, vis)
 
 
 def _vertex_face_csr(faces: torch.Tensor, V: int):

@@ -79,6 +79,57 @@ def sample(texture: torch.Tensor, taps: Taps) -> torch.Tensor:
     return out[:, 0] if flat else out
 
 
+def tangent_frames(verts, faces, verts_uvs, faces_uvs, pix_valid, pixel_normals):
+    """A tangent frame per pixel -> (tangent [P, 3], bitangent [P, 3], valid [P] bool) from the pixel's face (``pix_valid``
+    of ``MeshRasterizer.pixel_uv``: the face, or -1) and its G-buffer normal.  Per face, with world vertices p0..p2 and UVs
+    (u, v)0..2: e1 = p1 - p0, e2 = p2 - p0, det = du1 dv2 - du2 dv1, T_f = (e1 dv2 - e2 dv1) / det (the direction of growing
+    u), B_f = (e2 du1 - e1 du2) / det (of growing v).  Per pixel, with N the normalised pixel normal: t = normalize(T_f -
+    N (N.T_f)), b = h (N x t) with h = sign((N x t).B_f) (-1 on a face whose UVs are mirrored).  Invalid -- pix_valid < 0,
+    det zero or not finite, |T_f - N (N.T_f)| < 1e-12, h = 0 -- gives t = b = 0.  Plain torch, gathers only (no scatter):
+    deterministic, on any device, in the dtype of ``verts``."""
+    seen = pix_valid >= 0
+    face = pix_valid.clamp(min=0)
+    p = verts[faces[face]]                                              # [P, 3, 3]
+    uv = verts_uvs[faces_uvs[face].clamp(0, verts_uvs.shape[0] - 1)]    # (a face named by pix_valid has its three UVs)
+    e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    du1, dv1 = uv[:, 1, 0] - uv[:, 0, 0], uv[:, 1, 1] - uv[:, 0, 1]
+    du2, dv2 = uv[:, 2, 0] - uv[:, 0, 0], uv[:, 2, 1] - uv[:, 0, 1]
+    det = du1 * dv2 - du2 * dv1
+    ok = seen & torch.isfinite(det) & (det != 0)
+    sdet = torch.where(ok, det, torch.ones_like(det))[:, None]
+    Tf = (e1 * dv2[:, None] - e2 * dv1[:, None]) / sdet
+    Bf = (e2 * du1[:, None] - e1 * du2[:, None]) / sdet
+    N = torch.nn.functional.normalize(pixel_normals.to(verts.dtype), p=2, dim=-1, eps=1e-6)
+    tp = Tf - N * (N * Tf).sum(-1, keepdim=True)
+    ln = tp.norm(dim=-1)
+    ok = ok & torch.isfinite(ln) & (ln >= 1e-12)
+    t = tp / torch.where(ok, ln, torch.ones_like(ln))[:, None]
+    c = torch.cross(N, t, dim=-1)
+    h = torch.sign((c * Bf).sum(-1))
+    ok = ok & torch.isfinite(h) & (h != 0)
+    zero = torch.zeros_like(t)
+    return torch.where(ok[:, None], t, zero), torch.where(ok[:, None], h[:, None] * c, zero), ok
+
+
+def perturb_normals(pixel_normals, tangent, bitangent, valid, m, strength: float = 1.0):
+    """Shading normals [P, 3] from a tangent-space normal m = 2 texel - 1 per pixel ([P, 3]; (0, 0, 1) is "flat"): on a
+    valid pixel the direction strength m_x t + strength m_y b + m_z N (N the normalised pixel normal), returned with the
+    length of the pixel's own normal, |n_p| (strength m_x t + strength m_y b) + m_z n_p -- not normalised, the shader does
+    that -- so that a flat m returns ``pixel_normals`` bit for bit.  An invalid or background pixel keeps its normal exactly
+    and sends no gradient to m.  Plain torch with autograd (any device, any float dtype)."""
+    if pixel_normals.dim() != 2 or pixel_normals.shape[1] != 3:
+        raise ValueError("pixel_normals must be [P, 3]")
+    P = pixel_normals.shape[0]
+    for name, x in (("tangent", tangent), ("bitangent", bitangent), ("m", m)):
+        if tuple(x.shape) != (P, 3):
+            raise ValueError(f"{name} must be [{P}, 3] like pixel_normals, got {tuple(x.shape)}")
+    if tuple(valid.shape) != (P,) or valid.dtype != torch.bool:
+        raise ValueError(f"valid must be a bool tensor [{P}], got {valid.dtype} {tuple(valid.shape)}")
+    ln = pixel_normals.norm(dim=-1, keepdim=True).clamp_min(1e-6)
+    bent = ln * ((float(strength) * m[:, 0:1]) * tangent + (float(strength) * m[:, 1:2]) * bitangent) + m[:, 2:3] * pixel_normals
+    return torch.where(valid[:, None], bent, pixel_normals)
+
+
 class TexturedMaterials(nn.Module):
     """A Blinn-Phong material in the mesh's UV space.  Each of albedo, ks and shininess is a scalar (albedo: or [3]) or a
     texture -- [H, W, 3] for the albedo, [H, W] for the other two; the sizes may differ.  The names in ``learn`` become
@@ -87,17 +138,26 @@ class TexturedMaterials(nn.Module):
     [P], shininess [P]) -- or the scalars -- that ``blinn_phong_shading_materials`` takes; the shininess is clamped to
     [shininess_min, shininess_max] AFTER the fetch (a background pixel fetches 0 and is clamped too: it is never shaded).
 
+    ``normal``: a tangent-space normal texture [H, W, 3] encoded in [0, 1] (flat: (0.5, 0.5, 1)), with its own size and
+    pyramid; "normal" may be named in ``learn``.  ``shading_normals(rasterizer, mesh, R, T, pixel_normals)`` bends the
+    G-buffer's normals by it (``perturb_normals`` with ``normal_strength``); ``values`` and ``NAMES`` do not know it, and
+    with ``normal=None`` nothing of it runs.
+
     One object handed to several renderers, each with its own rasteriser and camera, accumulates one texture gradient."""
 
     NAMES = ("albedo", "ks", "shininess")
 
     def __init__(self, albedo=1.0, ks=0.0, shininess=500.0, learn=(), levels=None, wrap: str = "clamp", align_corners: bool = False,
-                 lod_bias: float = 0.0, shininess_min: float = 1.0, shininess_max: float = 2000.0):
+                 lod_bias: float = 0.0, shininess_min: float = 1.0, shininess_max: float = 2000.0, normal=None,
+                 normal_strength: float = 1.0):
         super().__init__()
         learn = (learn,) if isinstance(learn, str) else tuple(learn)
         for name in learn:
-            if name not in self.NAMES:
-                raise ValueError(f"learn names must be among {self.NAMES}, got {name!r}")
+            if name not in self.NAMES + ("normal",):
+                raise ValueError(f"learn names must be among {self.NAMES + ('normal',)}, got {name!r}")
+        if "normal" in learn and normal is None:
+            raise ValueError('learn names "normal", but no normal texture is given')
+        self.normal_strength = float(normal_strength)
         if not 0.0 < float(shininess_min) <= float(shininess_max):
             raise ValueError("0 < shininess_min <= shininess_max is required")
         if wrap not in ("clamp", "repeat"):
@@ -115,6 +175,13 @@ class TexturedMaterials(nn.Module):
             if not (x.dim() == 0 or (x.dim() == 2 and min(x.shape) >= 1)):
                 raise ValueError(f"{name} must be a float or a texture [H, W], got {tuple(x.shape)}")
             vals[name] = x
+        if normal is not None:
+            x = torch.as_tensor(normal, dtype=torch.float32).detach().clone()
+            if not (x.dim() == 3 and x.shape[2] == 3 and min(x.shape[:2]) >= 1):
+                raise ValueError(f"normal must be a texture [H, W, 3], got {tuple(x.shape)}")
+            vals["normal"] = x
+        else:
+            self.normal = None
         for name, x in vals.items():
             if self.is_texture(x):  # the same argument errors as a lookup would raise, now
                 L = ops.texture_levels(x.shape[0], x.shape[1], self.levels)[0]
@@ -139,3 +206,25 @@ class TexturedMaterials(nn.Module):
                 x = sample(x, taps)
             out.append(x)
         return out[0], out[1], out[2].clamp(self.shininess_min, self.shininess_max)
+
+    def shading_normals(self, rasterizer, mesh, R=None, T=None, pixel_normals=None):
+        """The normals the shader is to use, [P, 3] (not normalised): ``pixel_normals`` (the G-buffer's) bent by the normal
+        texture in the pixel's tangent frame; ``pixel_normals`` itself when there is no normal texture;
+        a flat texture gives the input normals exactly (``tangent_space_normals``, ``perturb_normals``)."""
+        if pixel_normals is None:
+            pixel_normals = rasterizer.gbuffer(mesh, R, T)[1]
+        if self.normal is None:
+            return pixel_normals
+        t, b, valid = rasterizer.pixel_tangents(mesh, R, T)
+        return perturb_normals(pixel_normals, t, b, valid, self.tangent_space_normals(rasterizer, mesh, R, T), self.normal_strength)
+
+    def tangent_space_normals(self, rasterizer, mesh, R=None, T=None):
+        """m = 2 texel - 1 per pixel, [P, 3]: the normal texture fetched through the pixel's taps and decoded.  What is
+        fetched is the texture's difference from flat, m = 2 fetch(normal - (0.5, 0.5, 1)) + (0, 0, 1): the same value up to
+        the rounding of the weights' sum, and exactly (0, 0, 1) for a flat texture and on a pixel that sees no texture."""
+        if self.normal is None:
+            raise ValueError("these materials have no normal texture")
+        taps = rasterizer.texture_taps(mesh, R, T, size=tuple(self.normal.shape[:2]), levels=self.levels, wrap=self.wrap,
+                                       align_corners=self.align_corners, lod_bias=self.lod_bias)
+        flat = self.normal.new_tensor([0.5, 0.5, 1.0])
+        return 2.0 * sample(self.normal - flat, taps) + self.normal.new_tensor([0.0, 0.0, 1.0])

@@ -489,6 +489,53 @@ int reni_envmap_shade_terms_dnormals(int64_t B, int64_t NP, int64_t J, const flo
                                      const float* d_diffuse, const float* d_specular, float* d_normals, void* ws,
                                      size_t ws_bytes, void* stream);
 
+/* ---- microfacet (GGX) materials: the shader's terms for a base colour / roughness / metallic surface ------------------
+ * For pixel p with given normal n_p: N = n_p / max(|n_p|, 1e-6), V = normalize(cam - pos_p), a = alpha_p > 0.  For texel j
+ * with direction L, colour C[b,j,:] and visibility bit v(p,j) (1 when vis is NULL):
+ *     H   = (V + L) / max(|V + L|, 1e-6)
+ *     x_l = N.L,  x_h = N.H,  x_v = N.V            nl, nh, nv = clamp(x, 0, 1)
+ *     u   = clamp(V.H, 0, 1)                        f = (1 - u)^5
+ *     s2  = |N x H|^2                               (= 1 - x_h^2 for unit vectors, without the cancellation at the lobe's peak)
+ *     d   = a^2 nh^2 + s2
+ *     lam(x) = sqrt(a^2 + (1 - a^2) x^2)
+ *     k   = [x_h > 0] a^2 nl / ( d^2 (nl + lam(nl)) (nv + lam(nv)) )
+ *
+ *     diffuse[b,p,c] = sum_j v nl  C[b,j,c]         (reni_envmap_shade_terms' diffuse sum, bit for bit)
+ *     spec0 [b,p,c]  = sum_j v k   C[b,j,c]
+ *     spec1 [b,p,c]  = sum_j v k f C[b,j,c]
+ *     dlight_colors[b,j,c] = sum_p v ( nl d_diffuse[b,p,c] + k d_spec0[b,p,c] + k f d_spec1[b,p,c] )
+ *     d_alpha[p]     = sum_b sum_j v (dk/da) ( sum_c d_spec0 C + f sum_c d_spec1 C )
+ *     d_normals[p]   = Jacobian of F.normalize applied to sum_b sum_j v ( [x_l > 0] (sum_c d_diffuse C) L + the d(k, k f)/dN
+ *                      terms ), with strict gates and the projection as in reni_envmap_shade_terms_dnormals
+ * k is the GGX distribution times the separable Smith visibility times nl, without 1 / pi (the diffuse sum carries none
+ * either: both are pi times the physical radiance).  Schlick's Fresnel is affine in F0, so the caller composes
+ * colours = (1 - metallic) base_color diffuse + F0 spec0 + (1 - F0) spec1.  Every denominator is at least a power of a: no
+ * epsilon; a pair with nl = 0 adds exactly 0; a pixel with a zero normal gets exact zeros in every output and gradient.
+ * normals .. light_colors, vis, vis_batch_stride: as for reni_envmap_shade_terms.  alpha: device, a_p = alpha[p * alpha_stride],
+ * alpha_stride 0 (one value for all pixels) or 1 ([NP]).  a_p <= 0 or NaN gives unspecified values for that pixel (backward:
+ * for the texels it lights), never an access outside the buffers.  d_alpha is [NP] at either stride (stride 0: the caller
+ * sums it); d_normals [NP][3] or NULL (not wanted, not computed: d_alpha keeps its bits).  Deterministic (fixed-order partial
+ * sums, no float atomics); an all-ones mask gives the bits of vis = NULL.
+ * ws: reni_envmap_shade_ggx_workspace_bytes(B, NP, J) serves the forward and the backward call,
+ * reni_envmap_shade_ggx_dpixel_workspace_bytes(B, NP, J) the dpixel call, which always needs it (0 for a size < 1). */
+size_t reni_envmap_shade_ggx_workspace_bytes(int64_t B, int64_t NP, int64_t J);
+int reni_envmap_shade_ggx(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                          float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                          const float* light_colors, const float* alpha, int64_t alpha_stride, const uint32_t* vis,
+                          int64_t vis_batch_stride, float* diffuse, float* spec0, float* spec1, void* ws, size_t ws_bytes,
+                          void* stream);
+int reni_envmap_shade_ggx_backward(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                                   float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                                   const float* alpha, int64_t alpha_stride, const uint32_t* vis, int64_t vis_batch_stride,
+                                   const float* d_diffuse, const float* d_spec0, const float* d_spec1, float* dlight_colors,
+                                   void* ws, size_t ws_bytes, void* stream);
+size_t reni_envmap_shade_ggx_dpixel_workspace_bytes(int64_t B, int64_t NP, int64_t J);
+int reni_envmap_shade_ggx_dpixel(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                                 float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                                 const float* light_colors, const float* alpha, int64_t alpha_stride, const uint32_t* vis,
+                                 int64_t vis_batch_stride, const float* d_diffuse, const float* d_spec0, const float* d_spec1,
+                                 float* d_alpha, float* d_normals, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- environment-map baselines: spherical Gaussians and spherical harmonics ----------------------------------------
  * What RENI is compared against.  fp32, deterministic (no float atomics; fixed summation order: two calls give identical
  * bits, and map n's results are the same alone or inside a batch).

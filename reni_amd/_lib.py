@@ -43,6 +43,8 @@ EXPORTS = (
     "reni_envmap_shade_masked", "reni_envmap_shade_masked_backward",
     "reni_envmap_shade_terms_workspace_bytes", "reni_envmap_shade_terms", "reni_envmap_shade_terms_backward",
     "reni_envmap_shade_terms_dnormals_workspace_bytes", "reni_envmap_shade_terms_dnormals",
+    "reni_envmap_shade_ggx_workspace_bytes", "reni_envmap_shade_ggx", "reni_envmap_shade_ggx_backward",
+    "reni_envmap_shade_ggx_dpixel_workspace_bytes", "reni_envmap_shade_ggx_dpixel",
     "reni_sg_workspace_bytes", "reni_sg_render", "reni_sg_loss_grad", "reni_sh_project", "reni_sh_reconstruct",
     "reni_diffuse_workspace_bytes", "reni_diffuse_convolve", "reni_sh_irradiance_l2",
     "reni_lobe_workspace_bytes", "reni_lobe_convolve", "reni_envmap_lookup",
@@ -217,6 +219,17 @@ def load():
     lib.reni_envmap_shade_terms_dnormals.argtypes = (terms + [c_void_p] + mats +  # .. light_colors, materials, gD, gS, d_normals, ws ..
                                                      [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p])
     lib.reni_envmap_shade_terms_dnormals.restype = c_int32
+    for fn in (lib.reni_envmap_shade_ggx_workspace_bytes, lib.reni_envmap_shade_ggx_dpixel_workspace_bytes):
+        fn.argtypes = [c_int64, c_int64, c_int64]
+        fn.restype = c_size_t
+    # the terms' lists with alpha + stride in the shininess's place
+    lib.reni_envmap_shade_ggx.argtypes = terms + [c_void_p] + mats + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_envmap_shade_ggx.restype = c_int32
+    lib.reni_envmap_shade_ggx_backward.argtypes = terms + mats + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_envmap_shade_ggx_backward.restype = c_int32
+    lib.reni_envmap_shade_ggx_dpixel.argtypes = (terms + [c_void_p] + mats +  # .. light_colors, alpha, vis, gD, gS0, gS1, d_alpha, d_normals, ws ..
+                                                 [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p])
+    lib.reni_envmap_shade_ggx_dpixel.restype = c_int32
     lib.reni_sg_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int64]
     lib.reni_sg_workspace_bytes.restype = c_size_t
     lib.reni_sg_render.argtypes = [c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p,

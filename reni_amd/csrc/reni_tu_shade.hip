@@ -574,6 +574,432 @@ __global__ void __launch_bounds__(256) k_terms_dn_reduce(const TermsDnReduceArgs
   }
 }
 
+// ---- microfacet (GGX) materials: the shader's terms for base colour / roughness / metallic ----------------
+// Per pair, with H = (V + L) / max(|V + L|, 1e-6), x_l = N.L, x_h = N.H, x_v = N.V (nl, nh, nv their clamps to [0, 1]),
+// u = clamp(V.H, 0, 1), f = (1 - u)^5, s2 = |N x H|^2, d = a^2 nh^2 + s2, lam(x) = sqrt(a^2 + (1 - a^2) x^2), a = alpha_p:
+//
+//   k(p,j)    = [x_h > 0] a^2 nl / ( d^2 (nl + lam(nl)) (nv + lam(nv)) )      (GGX D x separable Smith x nl, no 1 / pi)
+//   D [b,p,:] = sum_j v nl  C[b,j,:]        S0[b,p,:] = sum_j v k C[b,j,:]        S1[b,p,:] = sum_j v k f C[b,j,:]
+//   dC[b,j,:] = sum_p v ( nl gD[b,p,:] + k gS0[b,p,:] + k f gS1[b,p,:] )
+//
+// Schlick's Fresnel is affine in F0, so S0 and S1 do not depend on the material's colour: the composition behind the
+// kernel (envmap_shader.compose_microfacet) is F0 S0 + (1 - F0) S1.  k_envmap_terms' structure: ownership, stage, splits,
+// BC, packed mask words, fmaf everywhere -- nl is its expression, so D has its bits.  What depends on the pixel alone is
+// hoisted (a^2, 1 - a^2, pv = a^2 / (nv + lam(nv))); per pair one rsq (H), one sqrt (lam(nl)) and one rcp (the whole
+// denominator).  s2 comes from the cross product: 1 - x_h^2 cancels at the lobe's peak, where d is a^2-small.  Every
+// denominator is at least a power of a > 0; the gate is a select, so a zero normal (d = 0) gives exactly 0.
+struct GgxArgs {
+  const float* nrm;        // [NP][3]
+  const float* pos;        // [NP][3]
+  const float* ldir;       // [J][3] texel directions of the image chunk's first image
+  const float* src0;       // forward: C [B][J][3]; backward: gD [B][NP][3]
+  const float* src1;       // backward: gS0 [B][NP][3]
+  const float* src2;       // backward: gS1 [B][NP][3]
+  const float* alpha;      // a_p = alpha[p * alpha_stride]
+  float* out[3];           // forward: D, S0, S1 (partial sums of split 0 when there are splits); backward: out[0] = dC
+  size_t split_stride;     // floats from one split's partial sums to the next split's
+  float cam[3];
+  int alpha_stride;        // 0: one value for all pixels, 1: per pixel
+  int B, NP, J, b0, nb;
+  int per_split;
+  const uint32_t* vis;     // MASKED: as ShadeArgs::vis
+  int JW;
+};
+
+struct GgxPixel { float a2, om, pv; };  // a^2, 1 - a^2, a^2 / (nv + lam(nv))
+
+DEV GgxPixel ggx_pixel(const float (&N)[3], const float (&V)[3], float al) {
+  GgxPixel g;
+  g.a2 = al * al;
+  g.om = fmaf(-al, al, 1.f);
+  const float nv = fminf(fmaxf(fmaf(N[2], V[2], fmaf(N[1], V[1], N[0] * V[0])), 0.f), 1.f);
+  g.pv = g.a2 / (nv + sqrtf(fmaf(g.om, nv * nv, g.a2)));
+  return g;
+}
+
+struct GgxPair { float nl, k, kf; };
+
+DEV GgxPair ggx_pair(const float (&N)[3], const float (&V)[3], const float (&L)[3], const GgxPixel& g) {
+  GgxPair t;
+  t.nl = fminf(fmaxf(fmaf(N[2], L[2], fmaf(N[1], L[1], N[0] * L[0])), 0.f), 1.f);  // shade_pair's
+  const float hx = V[0] + L[0], hy = V[1] + L[1], hz = V[2] + L[2];
+  const float inv = __builtin_amdgcn_rsqf(fmaxf(fmaf(hz, hz, fmaf(hy, hy, hx * hx)), 1e-12f));  // 1 / max(|h|, 1e-6)
+  const float Hx = hx * inv, Hy = hy * inv, Hz = hz * inv;
+  const float xh = fmaf(N[2], Hz, fmaf(N[1], Hy, N[0] * Hx));
+  const float nh = fminf(fmaxf(xh, 0.f), 1.f);
+  const float u = fminf(fmaxf(fmaf(V[2], Hz, fmaf(V[1], Hy, V[0] * Hx)), 0.f), 1.f);
+  const float cx = fmaf(N[1], Hz, -(N[2] * Hy)), cy = fmaf(N[2], Hx, -(N[0] * Hz)), cz = fmaf(N[0], Hy, -(N[1] * Hx));
+  const float d = fmaf(g.a2, nh * nh, fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
+  const float lam = __builtin_amdgcn_sqrtf(fmaf(g.om, t.nl * t.nl, g.a2));
+  const float r = __builtin_amdgcn_rcpf((d * d) * (t.nl + lam));
+  t.k = xh > 0.f ? (g.pv * t.nl) * r : 0.f;  // (a zero normal: d = 0, 0 * inf -- selected away)
+  const float m = 1.f - u, m2 = m * m;
+  t.kf = t.k * ((m2 * m2) * m);
+  return t;
+}
+
+// OWN_PIXEL: forward (a thread owns pixel p: N, V, the hoisted three and 9 BC accumulators); else backward (a thread owns
+// texel j; the stage holds per pixel N, V, the hoisted three and the rows gD, gS0, gS1: 9 BC floats).  MASKED: a select on
+// the pair's three coefficients, read from the packed words as in k_envmap_terms.
+template <bool OWN_PIXEL, int BC, bool MASKED>
+__global__ void __launch_bounds__(256) k_envmap_ggx(const GgxArgs a) {
+  constexpr int NSRC = OWN_PIXEL ? 3 * BC : 9 * BC;  // source floats per staged element
+  constexpr int ROW = 4 * ((NSRC + 3) / 4);
+  constexpr int NT = OWN_PIXEL ? 3 : 1;
+  __shared__ float4 g0[SH_TILE];                      // texel (Lx, Ly, Lz, -) | pixel (Nx, Ny, Nz, Vx)
+  __shared__ float4 g1[OWN_PIXEL ? 1 : SH_TILE];      //                       | pixel (Vy, Vz, a^2, 1 - a^2)
+  __shared__ float g2[OWN_PIXEL ? 1 : SH_TILE];       //                       | pixel pv
+  __shared__ float4 sv[SH_TILE][ROW / 4];             // forward: C rows of the BC images; backward: gD, gS0, gS1 rows
+  __shared__ uint32_t mw[MASKED && !OWN_PIXEL ? SH_TILE : 1][8];
+  const int tid = threadIdx.x;
+  const int n_own = OWN_PIXEL ? a.NP : a.J, n_oth = OWN_PIXEL ? a.J : a.NP;
+  const int o = blockIdx.x * 256 + tid;
+  const bool live = o < n_own;
+  float N[3] = {0.f, 0.f, 0.f}, V[3] = {0.f, 0.f, 0.f}, L[3] = {0.f, 0.f, 0.f};
+  GgxPixel gp = {1.f, 0.f, 1.f};
+  auto load_pixel = [&](int p, float (&n)[3], float (&v)[3]) {
+    n[0] = a.nrm[(size_t)p * 3]; n[1] = a.nrm[(size_t)p * 3 + 1]; n[2] = a.nrm[(size_t)p * 3 + 2];
+    normalize3(n);
+    v[0] = a.cam[0] - a.pos[(size_t)p * 3]; v[1] = a.cam[1] - a.pos[(size_t)p * 3 + 1]; v[2] = a.cam[2] - a.pos[(size_t)p * 3 + 2];
+    normalize3(v);
+    return ggx_pixel(n, v, a.alpha[(size_t)p * a.alpha_stride]);
+  };
+  if (live) {
+    if (OWN_PIXEL) gp = load_pixel(o, N, V);
+    else { L[0] = a.ldir[(size_t)o * 3]; L[1] = a.ldir[(size_t)o * 3 + 1]; L[2] = a.ldir[(size_t)o * 3 + 2]; }
+  }
+  float acc[NT][BC][3];
+#pragma unroll
+  for (int k = 0; k < NT; ++k)
+#pragma unroll
+    for (int b = 0; b < BC; ++b) { acc[k][b][0] = 0.f; acc[k][b][1] = 0.f; acc[k][b][2] = 0.f; }
+
+  // one (p, j) pair: element e of the stage against the thread's own element; `on` is its visibility bit
+  auto pair = [&](int e, bool on) {
+    const float4 q0 = g0[e];
+    GgxPair t;
+    if (OWN_PIXEL) {
+      const float Lo[3] = {q0.x, q0.y, q0.z};
+      t = ggx_pair(N, V, Lo, gp);
+    } else {
+      const float4 q1 = g1[e];
+      const float No[3] = {q0.x, q0.y, q0.z}, Vo[3] = {q0.w, q1.x, q1.y};
+      const GgxPixel go = {q1.z, q1.w, g2[e]};
+      t = ggx_pair(No, Vo, L, go);
+    }
+    if (MASKED) { t.nl = on ? t.nl : 0.f; t.k = on ? t.k : 0.f; t.kf = on ? t.kf : 0.f; }
+    const float* r = (const float*)sv[e];
+#pragma unroll
+    for (int b = 0; b < BC; ++b) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        if (OWN_PIXEL) {
+          acc[0][b][c] = fmaf(t.nl, r[3 * b + c], acc[0][b][c]);
+          acc[1][b][c] = fmaf(t.k, r[3 * b + c], acc[1][b][c]);
+          acc[NT - 1][b][c] = fmaf(t.kf, r[3 * b + c], acc[NT - 1][b][c]);
+        } else {
+          acc[0][b][c] = fmaf(t.kf, r[6 * BC + 3 * b + c], fmaf(t.k, r[3 * BC + 3 * b + c], fmaf(t.nl, r[3 * b + c], acc[0][b][c])));
+        }
+      }
+    }
+  };
+
+  const int t_begin = blockIdx.y * a.per_split, t_end = min(n_oth, t_begin + a.per_split);
+  for (int t0 = t_begin; t0 < t_end; t0 += SH_TILE) {
+    __syncthreads();
+    if (tid < SH_TILE) {
+      const int t = t0 + tid;
+      float4 q0 = {0.f, 0.f, 0.f, 0.f}, q1 = {0.f, 0.f, 1.f, 0.f};
+      float q2 = 1.f;
+      if (t < t_end) {
+        if (OWN_PIXEL) {
+          q0.x = a.ldir[(size_t)t * 3]; q0.y = a.ldir[(size_t)t * 3 + 1]; q0.z = a.ldir[(size_t)t * 3 + 2];
+        } else {
+          float n[3], v[3];
+          const GgxPixel go = load_pixel(t, n, v);
+          q0 = float4{n[0], n[1], n[2], v[0]};
+          q1 = float4{v[1], v[2], go.a2, go.om};
+          q2 = go.pv;
+        }
+      }
+      g0[tid] = q0;
+      if (!OWN_PIXEL) { g1[tid] = q1; g2[tid] = q2; }
+    }
+    {  // source rows, zero beyond the range / the chunk's images
+      float* svf = (float*)sv;
+      for (int i = tid; i < SH_TILE * NSRC; i += 256) {
+        const int e = i / NSRC, r = i - e * NSRC, h = r / (3 * BC), rr = r - h * (3 * BC), b = rr / 3, c = rr - b * 3;
+        const int t = t0 + e;
+        const float* src = h == 0 ? a.src0 : h == 1 ? a.src1 : a.src2;
+        float x = 0.f;
+        if (t < t_end && b < a.nb) x = src[((size_t)(a.b0 + b) * n_oth + t) * 3 + c];
+        svf[e * ROW + r] = x;
+      }
+    }
+    if constexpr (MASKED && !OWN_PIXEL) {
+      for (int i = tid; i < SH_TILE * 8; i += 256) {
+        const int e = i >> 3, w = blockIdx.x * 8 + (i & 7), t = t0 + e;
+        mw[e][i & 7] = (t < t_end && w < a.JW) ? a.vis[(size_t)t * a.JW + w] : 0u;
+      }
+    }
+    __syncthreads();
+    const int cnt = min(SH_TILE, t_end - t0);
+    if constexpr (MASKED) {
+      uint32_t wv[4] = {0u, 0u, 0u, 0u};
+      if (OWN_PIXEL && live) {  // (t0 is a multiple of SH_TILE: per_split is)
+        const uint32_t* row = a.vis + (size_t)o * a.JW;
+        const int w0 = t0 >> 5;
+        if ((a.JW & 3) == 0) {
+          const uint4 q = *(const uint4*)(row + w0);
+          wv[0] = q.x; wv[1] = q.y; wv[2] = q.z; wv[3] = q.w;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) wv[k] = w0 + k < a.JW ? row[w0 + k] : 0u;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {  // the ascending walk of the unmasked instance, 32 elements per mask word
+        const int e_end = min(cnt, 32 * k + 32);
+        for (int e = 32 * k; e < e_end; ++e)
+          pair(e, OWN_PIXEL ? (wv[k] >> (e & 31)) & 1u : (mw[e][tid >> 5] >> (tid & 31)) & 1u);
+      }
+    } else {
+      for (int e = 0; e < cnt; ++e) pair(e, true);
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+#pragma unroll
+      for (int b = 0; b < BC; ++b) {
+        if (b < a.nb) {
+          float* dst = a.out[k] + (size_t)blockIdx.y * a.split_stride + ((size_t)(a.b0 + b) * n_own + o) * 3;
+          dst[0] = acc[k][b][0]; dst[1] = acc[k][b][1]; dst[2] = acc[k][b][2];
+        }
+      }
+    }
+  }
+}
+
+// d loss / d alpha and d loss / d normals of the three sums.  With ad = sum_c gD C, w = sum_c gS0 C + f sum_c gS1 C,
+// kk = k / nl (computed without the division: nl = 0 is no special case), rd = 1 / d, sl = nl + lam(nl):
+//
+//   dk/da   = k ( 2 / a - 4 a nh^2 rd - a (1 - nl^2) / (lam(nl) sl) - a (1 - nv^2) / (lam(nv) (nv + lam(nv))) )
+//   dk/dN  ~= [x_l > 0] ( kk - k (1 + (1 - a^2) nl / lam(nl)) / sl ) L + 4 k (1 - a^2) nh rd H
+//             - [x_v > 0] k (1 + (1 - a^2) nv / lam(nv)) / (nv + lam(nv)) V
+//
+// (~=: up to a multiple of N, which F.normalize's Jacobian removes: d s2 / dN = 2 N |H|^2 - 2 x_h H, and with the a^2 nh^2
+// term d d / dN ~= -2 (1 - a^2) nh H; u and f do not depend on N.)  What multiplies a per-pixel constant is summed as
+// W = sum v k w and applied once per (chunk, split): the first and last terms of dk/da and the V term of dk/dN.  A thread
+// owns a pixel -- N, V, the hoisted values and the rows gD, gS0, gS1 of the chunk's BC images in registers -- and walks the
+// texels through the forward's stage.  The alpha sums do not depend on WANT_DN: asking for the normals' gradient does not
+// move the roughness's.  Strict gates as in k_envmap_terms_dn; rd is 0 where x_h <= 0, so a zero normal gets exact zeros.
+struct GgxDpArgs {
+  const float* nrm;        // [NP][3]
+  const float* pos;        // [NP][3]
+  const float* ldir;       // [J][3] texel directions of the image chunk's first image
+  const float* col;        // C [B][J][3]
+  const float* gD;         // [B][NP][3]
+  const float* gS0;        // [B][NP][3]
+  const float* gS1;        // [B][NP][3]
+  const float* alpha;      // a_p = alpha[p * alpha_stride]
+  float* part_a;           // [S][NP] partial sums of this chunk: d alpha
+  float* part_n;           // [S][NP][3]: d N (WANT_DN)
+  float cam[3];
+  int alpha_stride;
+  int B, NP, J, b0, nb;
+  int per_split;
+  const uint32_t* vis;     // MASKED: as ShadeArgs::vis
+  int JW;
+};
+
+// normalize3 with its sum of squares written out: which products the compiler fuses there depends on the instance, and the
+// WANT_DN instances must agree about N and V to the bit
+DEV void normalize3_fma(float (&v)[3]) {
+  const float n = sqrtf(fmaf(v[2], v[2], fmaf(v[1], v[1], v[0] * v[0])));
+  const float inv = 1.f / fmaxf(n, 1e-6f);
+  v[0] *= inv; v[1] *= inv; v[2] *= inv;
+}
+
+template <int BC, bool MASKED, bool WANT_DN>
+__global__ void __launch_bounds__(256) k_envmap_ggx_dpixel(const GgxDpArgs a) {
+  constexpr int NSRC = 3 * BC;
+  constexpr int ROW = 4 * ((NSRC + 3) / 4);
+  __shared__ float4 g0[SH_TILE];           // texel (Lx, Ly, Lz, -)
+  __shared__ float4 sv[SH_TILE][ROW / 4];  // C rows of the BC images
+  const int tid = threadIdx.x;
+  const int o = blockIdx.x * 256 + tid;
+  const bool live = o < a.NP;
+  float N[3] = {0.f, 0.f, 0.f}, V[3] = {0.f, 0.f, 0.f}, al = 1.f;
+  float gd[BC][3], g0s[BC][3], g1s[BC][3];
+#pragma unroll
+  for (int b = 0; b < BC; ++b)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { gd[b][c] = 0.f; g0s[b][c] = 0.f; g1s[b][c] = 0.f; }
+  if (live) {
+    N[0] = a.nrm[(size_t)o * 3]; N[1] = a.nrm[(size_t)o * 3 + 1]; N[2] = a.nrm[(size_t)o * 3 + 2];
+    normalize3_fma(N);
+    V[0] = a.cam[0] - a.pos[(size_t)o * 3]; V[1] = a.cam[1] - a.pos[(size_t)o * 3 + 1]; V[2] = a.cam[2] - a.pos[(size_t)o * 3 + 2];
+    normalize3_fma(V);
+    al = a.alpha[(size_t)o * a.alpha_stride];
+#pragma unroll
+    for (int b = 0; b < BC; ++b) {
+      if (b < a.nb) {  // (beyond the chunk's images the rows stay 0, as the stage's do: they add nothing)
+        const size_t i = ((size_t)(a.b0 + b) * a.NP + o) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { gd[b][c] = a.gD[i + c]; g0s[b][c] = a.gS0[i + c]; g1s[b][c] = a.gS1[i + c]; }
+      }
+    }
+  }
+  // per pixel: pv as in the forward, the alpha terms that do not depend on the texel (ca) and the V term's factor (gv)
+  const float a2 = al * al, om = fmaf(-al, al, 1.f);
+  const float xv = fmaf(N[2], V[2], fmaf(N[1], V[1], N[0] * V[0]));
+  const float nv = fminf(fmaxf(xv, 0.f), 1.f);
+  const float lamv = sqrtf(fmaf(om, nv * nv, a2));
+  const float rv = 1.f / (nv + lamv);
+  const float pv = a2 * rv;
+  const float ca = 2.f / al - al * fmaf(-nv, nv, 1.f) * rv / lamv;
+  const float gv = xv > 0.f ? fmaf(om, nv / lamv, 1.f) * rv : 0.f;
+  const float om4 = 4.f * om;
+  float accW = 0.f, accA = 0.f, acc[3] = {0.f, 0.f, 0.f};
+
+  auto pair = [&](int e, bool on) {
+    const float4 q0 = g0[e];
+    const float Lo[3] = {q0.x, q0.y, q0.z};
+    const float nl = fminf(fmaxf(fmaf(N[2], Lo[2], fmaf(N[1], Lo[1], N[0] * Lo[0])), 0.f), 1.f);
+    const float hx = V[0] + Lo[0], hy = V[1] + Lo[1], hz = V[2] + Lo[2];
+    const float inv = __builtin_amdgcn_rsqf(fmaxf(fmaf(hz, hz, fmaf(hy, hy, hx * hx)), 1e-12f));
+    const float Hv[3] = {hx * inv, hy * inv, hz * inv};
+    const float xh = fmaf(N[2], Hv[2], fmaf(N[1], Hv[1], N[0] * Hv[0]));
+    const float nh = fminf(fmaxf(xh, 0.f), 1.f);
+    const float u = fminf(fmaxf(fmaf(V[2], Hv[2], fmaf(V[1], Hv[1], V[0] * Hv[0])), 0.f), 1.f);
+    const float cx = fmaf(N[1], Hv[2], -(N[2] * Hv[1])), cy = fmaf(N[2], Hv[0], -(N[0] * Hv[2])), cz = fmaf(N[0], Hv[1], -(N[1] * Hv[0]));
+    const float d = fmaf(a2, nh * nh, fmaf(cz, cz, fmaf(cy, cy, cx * cx)));
+    const float lam = __builtin_amdgcn_sqrtf(fmaf(om, nl * nl, a2));
+    const float rd = xh > 0.f ? __builtin_amdgcn_rcpf(d) : 0.f;  // the gate: everything below is finite
+    const float rsl = __builtin_amdgcn_rcpf(nl + lam), rlam = __builtin_amdgcn_rcpf(lam);
+    const float m = 1.f - u, m2 = m * m, f = (m2 * m2) * m;
+    const float* r = (const float*)sv[e];
+    float ad = 0.f, a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int b = 0; b < BC; ++b) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        ad = fmaf(gd[b][c], r[3 * b + c], ad);
+        a0 = fmaf(g0s[b][c], r[3 * b + c], a0);
+        a1 = fmaf(g1s[b][c], r[3 * b + c], a1);
+      }
+    }
+    const float w = fmaf(f, a1, a0);
+    const float kk = (pv * (rd * rd)) * rsl;  // k / nl
+    const float k = kk * nl;
+    float ks = k;
+    if (MASKED) ks = on ? ks : 0.f;
+    const float kw = ks * w;
+    // alpha: the two terms that depend on the texel, 4 nh^2 / d + (1 - nl^2) / (lam sl)
+    const float ta = fmaf(fmaf(-nl, nl, 1.f), rlam * rsl, (4.f * (nh * nh)) * rd);
+    accA = fmaf(kw, ta, accA);
+    accW = fmaf(ks, w, accW);
+    if (WANT_DN) {
+      // w (kk - k (1 + (1 - a^2) nl / lam) / sl) = w kk (1 - nl (1 + (1 - a^2) nl / lam) / sl)
+      const float tl = fmaf(-(nl * rsl), fmaf(om * nl, rlam, 1.f), 1.f);
+      float cl = nl > 0.f ? fmaf(w * kk, tl, ad) : 0.f;
+      if (MASKED) cl = on ? cl : 0.f;
+      const float ch = kw * ((om4 * nh) * rd);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) acc[q] = fmaf(ch, Hv[q], fmaf(cl, Lo[q], acc[q]));
+    }
+  };
+
+  const int t_begin = blockIdx.y * a.per_split, t_end = min(a.J, t_begin + a.per_split);
+  for (int t0 = t_begin; t0 < t_end; t0 += SH_TILE) {
+    __syncthreads();
+    if (tid < SH_TILE) {
+      const int t = t0 + tid;
+      float4 q0 = {0.f, 0.f, 0.f, 0.f};
+      if (t < t_end) { q0.x = a.ldir[(size_t)t * 3]; q0.y = a.ldir[(size_t)t * 3 + 1]; q0.z = a.ldir[(size_t)t * 3 + 2]; }
+      g0[tid] = q0;
+    }
+    {  // source rows, zero beyond the range / the chunk's images
+      float* svf = (float*)sv;
+      for (int i = tid; i < SH_TILE * NSRC; i += 256) {
+        const int e = i / NSRC, r = i - e * NSRC, b = r / 3, c = r - b * 3;
+        const int t = t0 + e;
+        float x = 0.f;
+        if (t < t_end && b < a.nb) x = a.col[((size_t)(a.b0 + b) * a.J + t) * 3 + c];
+        svf[e * ROW + r] = x;
+      }
+    }
+    __syncthreads();
+    const int cnt = min(SH_TILE, t_end - t0);
+    if constexpr (MASKED) {
+      uint32_t wv[4] = {0u, 0u, 0u, 0u};
+      if (live) {  // (t0 is a multiple of SH_TILE: per_split is)
+        const uint32_t* row = a.vis + (size_t)o * a.JW;
+        const int w0 = t0 >> 5;
+        if ((a.JW & 3) == 0) {
+          const uint4 q = *(const uint4*)(row + w0);
+          wv[0] = q.x; wv[1] = q.y; wv[2] = q.z; wv[3] = q.w;
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) wv[k] = w0 + k < a.JW ? row[w0 + k] : 0u;
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {  // the ascending walk of the unmasked instance, 32 elements per mask word
+        const int e_end = min(cnt, 32 * k + 32);
+        for (int e = 32 * k; e < e_end; ++e) pair(e, (wv[k] >> (e & 31)) & 1u);
+      }
+    } else {
+      for (int e = 0; e < cnt; ++e) pair(e, true);
+    }
+  }
+  if (live) {
+    a.part_a[(size_t)blockIdx.y * a.NP + o] = fmaf(ca, accW, -(al * accA));
+    if (WANT_DN) {
+      float* dst = a.part_n + ((size_t)blockIdx.y * a.NP + o) * 3;
+      const float cv = -(gv * accW);
+      dst[0] = fmaf(cv, V[0], acc[0]); dst[1] = fmaf(cv, V[1], acc[1]); dst[2] = fmaf(cv, V[2], acc[2]);
+    }
+  }
+}
+
+// d_alpha[p] and gN[p] = sum over the image chunks (ascending) of the chunk's sum over its splits (ascending); then, as in
+// k_terms_dn_reduce, d_normals[p] = (gN - N (N.gN)) / |n_p|, or gN / 1e-6 under F.normalize's eps.  part_n NULL: alpha only.
+struct GgxDpReduceArgs { const float* part_a; const float* part_n; const float* nrm; float* d_alpha; float* d_normals; int NP, S, NCH; };
+__global__ void __launch_bounds__(256) k_ggx_dpixel_reduce(const GgxDpReduceArgs a) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.NP) return;
+  float ga = 0.f;
+  for (int ch = 0; ch < a.NCH; ++ch) {
+    float cs = 0.f;
+    for (int q = 0; q < a.S; ++q) cs += a.part_a[((size_t)ch * a.S + q) * a.NP + p];
+    ga += cs;
+  }
+  a.d_alpha[p] = ga;
+  if (!a.part_n) return;
+  float g[3] = {0.f, 0.f, 0.f};
+  for (int ch = 0; ch < a.NCH; ++ch) {
+    float cs[3] = {0.f, 0.f, 0.f};
+    for (int q = 0; q < a.S; ++q) {
+      const float* src = a.part_n + (((size_t)ch * a.S + q) * a.NP + p) * 3;
+      cs[0] += src[0]; cs[1] += src[1]; cs[2] += src[2];
+    }
+    g[0] += cs[0]; g[1] += cs[1]; g[2] += cs[2];
+  }
+  const float n[3] = {a.nrm[(size_t)p * 3], a.nrm[(size_t)p * 3 + 1], a.nrm[(size_t)p * 3 + 2]};
+  const float len = sqrtf(fmaf(n[2], n[2], fmaf(n[1], n[1], n[0] * n[0])));
+  const float inv = 1.f / fmaxf(len, 1e-6f);
+  float* out = a.d_normals + (size_t)p * 3;
+  if (len >= 1e-6f) {
+    const float N[3] = {n[0] * inv, n[1] * inv, n[2] * inv};
+    const float d = fmaf(N[2], g[2], fmaf(N[1], g[1], N[0] * g[0]));
+    out[0] = fmaf(-N[0], d, g[0]) * inv; out[1] = fmaf(-N[1], d, g[1]) * inv; out[2] = fmaf(-N[2], d, g[2]) * inv;
+  } else {
+    out[0] = g[0] * inv; out[1] = g[1] * inv; out[2] = g[2] * inv;
+  }
+}
+
 }  // namespace reni
 
 namespace {
@@ -766,6 +1192,125 @@ int terms_dnormals_common(int64_t B, int64_t NP, int64_t J, const float* normals
   return tu_launch(TU_PLAIN, reni::k_terms_dn_reduce, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, r);
 }
 
+// the argument checks the three microfacet calls share (what: the call's name in the messages); 0 when all hold
+int ggx_checks(const char* what, int64_t B, int64_t NP, int64_t J, bool any_null, int64_t dirs_bstride, int64_t alpha_stride,
+               const uint32_t* vis, int64_t vis_bstride) {
+  const auto fail = [&](const char* text) { return tu_fail(RENI_EINVAL, what, text); };
+  if (B < 1 || NP < 1 || J < 1) return fail("B, NP and J must be >= 1");
+  if (NP > 0x3fffffff || J > 0x3fffffff || B > 0xffff) return fail("problem too large");
+  if (any_null) return fail("NULL argument");
+  if (dirs_bstride != 0 && dirs_bstride < J * 3) return fail("direction batch stride must be 0 or >= 3 J");
+  if (alpha_stride != 0 && alpha_stride != 1) return fail("alpha stride must be 0 (one value) or 1 (per pixel)");
+  const int64_t JW = (J + 31) / 32;
+  if (vis) {
+    if (((uintptr_t)vis & 15) != 0) return fail("the mask must be 16-byte aligned");
+    if (vis_bstride != 0 && (dirs_bstride == 0 || vis_bstride < NP * JW || ((JW & 3) == 0 && (vis_bstride & 3) != 0)))
+      return fail("mask batch stride must be 0 (required with shared directions) or >= NP ceil(J/32) words");
+  }
+  return RENI_OK;
+}
+
+// forward: src0 = C, out = (D, S0, S1); backward: src = (gD, gS0, gS1), out0 = dC
+int ggx_common(bool forward, int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cx, float cy,
+               float cz, const float* light_dirs, int64_t dirs_bstride, const float* src0, const float* src1, const float* src2,
+               const float* alpha, int64_t alpha_stride, const uint32_t* vis, int64_t vis_bstride, float* out0, float* out1,
+               float* out2, void* ws, size_t ws_bytes, void* stream) {
+  const bool any_null = !normals || !positions || !light_dirs || !src0 || !alpha || !out0 ||
+                        (forward ? (!out1 || !out2) : (!src1 || !src2));
+  if (int rc = ggx_checks("envmap shade ggx", B, NP, J, any_null, dirs_bstride, alpha_stride, vis, vis_bstride)) return rc;
+  const bool masked = vis != nullptr;
+  const int NT = forward ? 3 : 1;
+  const int64_t n_own = forward ? NP : J, n_oth = forward ? J : NP;
+  const int S = n_splits(n_own, n_oth);
+  const size_t need = terms_partials(forward, B, NP, J, NT) * sizeof(float);
+  if (need > 0 && (!ws || ws_bytes < need)) return reni_set_error(RENI_EWORKSPACE, "envmap shade ggx: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)B * n_own * 3;
+  reni::GgxArgs a;
+  a.nrm = normals; a.pos = positions; a.src0 = src0; a.src1 = src1; a.src2 = src2;
+  a.alpha = alpha; a.alpha_stride = (int)alpha_stride;
+  float* const outs[3] = {out0, out1, out2};
+  for (int k = 0; k < 3; ++k) a.out[k] = k >= NT ? nullptr : S > 1 ? (float*)ws + (size_t)k * n : outs[k];
+  a.split_stride = (size_t)NT * n;
+  a.cam[0] = cx; a.cam[1] = cy; a.cam[2] = cz;
+  a.B = (int)B; a.NP = (int)NP; a.J = (int)J;
+  const int64_t tiles = (n_oth + reni::SH_TILE - 1) / reni::SH_TILE;
+  a.per_split = (int)((tiles + S - 1) / S) * reni::SH_TILE;
+  a.vis = nullptr; a.JW = (int)((J + 31) / 32);
+  const dim3 grid((unsigned)((n_own + 255) / 256), (unsigned)S);
+  const int step = dirs_bstride == 0 ? SHADE_BC : 1;  // as in shade_common
+  using reni::k_envmap_ggx;
+  void (*k)(const reni::GgxArgs);
+  if (forward) {
+    k = step == 1 ? (masked ? k_envmap_ggx<true, 1, true> : k_envmap_ggx<true, 1, false>)
+                  : (masked ? k_envmap_ggx<true, SHADE_BC, true> : k_envmap_ggx<true, SHADE_BC, false>);
+  } else {
+    k = step == 1 ? (masked ? k_envmap_ggx<false, 1, true> : k_envmap_ggx<false, 1, false>)
+                  : (masked ? k_envmap_ggx<false, SHADE_BC, true> : k_envmap_ggx<false, SHADE_BC, false>);
+  }
+  for (int64_t b0 = 0; b0 < B; b0 += step) {
+    a.b0 = (int)b0; a.nb = (int)((B - b0) < step ? (B - b0) : step);
+    a.ldir = light_dirs + (size_t)b0 * dirs_bstride;
+    if (masked) a.vis = vis + (size_t)b0 * vis_bstride;
+    if (int rc = tu_launch(TU_PLAIN, k, grid, dim3(256), 0, s, a)) return rc;
+  }
+  if (S == 1) return RENI_OK;
+  reni::TermsReduceArgs r;
+  r.part = (const float*)ws; r.n = n; r.S = S; r.NT = NT;
+  for (int k2 = 0; k2 < 3; ++k2) r.out[k2] = k2 < NT ? outs[k2] : nullptr;
+  return tu_launch(TU_PLAIN, reni::k_terms_reduce, dim3((unsigned)((n + 255) / 256), (unsigned)NT), dim3(256), 0, s, r);
+}
+
+// d alpha (and d normals when wanted): one launch per image chunk into its own partial slots, then the fixed-order reduce
+int ggx_dpixel_common(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cx, float cy,
+                      float cz, const float* light_dirs, int64_t dirs_bstride, const float* light_colors, const float* alpha,
+                      int64_t alpha_stride, const uint32_t* vis, int64_t vis_bstride, const float* gD, const float* gS0,
+                      const float* gS1, float* d_alpha, float* d_normals, void* ws, size_t ws_bytes, void* stream) {
+  const bool any_null = !normals || !positions || !light_dirs || !light_colors || !alpha || !gD || !gS0 || !gS1 || !d_alpha;
+  if (int rc = ggx_checks("envmap shade ggx dpixel", B, NP, J, any_null, dirs_bstride, alpha_stride, vis, vis_bstride)) return rc;
+  const bool masked = vis != nullptr, want_dn = d_normals != nullptr;
+  const int step = dirs_bstride == 0 ? SHADE_BC : 1;  // as in shade_common
+  const int64_t n_chunks = (B + step - 1) / step;
+  const int S = n_splits(NP, J);
+  const size_t slots = (size_t)n_chunks * S * NP;
+  const size_t need = slots * (want_dn ? 4 : 1) * sizeof(float);
+  if (!ws || ws_bytes < need) return reni_set_error(RENI_EWORKSPACE, "envmap shade ggx dpixel: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  reni::GgxDpArgs a;
+  a.nrm = normals; a.pos = positions; a.col = light_colors; a.gD = gD; a.gS0 = gS0; a.gS1 = gS1;
+  a.alpha = alpha; a.alpha_stride = (int)alpha_stride;
+  a.cam[0] = cx; a.cam[1] = cy; a.cam[2] = cz;
+  a.B = (int)B; a.NP = (int)NP; a.J = (int)J;
+  const int64_t tiles = (J + reni::SH_TILE - 1) / reni::SH_TILE;
+  a.per_split = (int)((tiles + S - 1) / S) * reni::SH_TILE;
+  a.vis = nullptr; a.JW = (int)((J + 31) / 32);
+  float* const part_a = (float*)ws;
+  float* const part_n = want_dn ? part_a + slots : nullptr;
+  const dim3 grid((unsigned)((NP + 255) / 256), (unsigned)S);
+  using reni::k_envmap_ggx_dpixel;
+  void (*k)(const reni::GgxDpArgs);
+  if (want_dn) {
+    k = step == 1 ? (masked ? k_envmap_ggx_dpixel<1, true, true> : k_envmap_ggx_dpixel<1, false, true>)
+                  : (masked ? k_envmap_ggx_dpixel<SHADE_BC, true, true> : k_envmap_ggx_dpixel<SHADE_BC, false, true>);
+  } else {
+    k = step == 1 ? (masked ? k_envmap_ggx_dpixel<1, true, false> : k_envmap_ggx_dpixel<1, false, false>)
+                  : (masked ? k_envmap_ggx_dpixel<SHADE_BC, true, false> : k_envmap_ggx_dpixel<SHADE_BC, false, false>);
+  }
+  int64_t chunk = 0;
+  for (int64_t b0 = 0; b0 < B; b0 += step, ++chunk) {
+    a.b0 = (int)b0; a.nb = (int)((B - b0) < step ? (B - b0) : step);
+    a.ldir = light_dirs + (size_t)b0 * dirs_bstride;
+    if (masked) a.vis = vis + (size_t)b0 * vis_bstride;
+    a.part_a = part_a + (size_t)chunk * S * NP;
+    a.part_n = want_dn ? part_n + (size_t)chunk * S * NP * 3 : nullptr;
+    if (int rc = tu_launch(TU_PLAIN, k, grid, dim3(256), 0, s, a)) return rc;
+  }
+  reni::GgxDpReduceArgs r;
+  r.part_a = part_a; r.part_n = part_n; r.nrm = normals; r.d_alpha = d_alpha; r.d_normals = d_normals;
+  r.NP = (int)NP; r.S = S; r.NCH = (int)n_chunks;
+  return tu_launch(TU_PLAIN, reni::k_ggx_dpixel_reduce, dim3((unsigned)((NP + 255) / 256)), dim3(256), 0, s, r);
+}
+
 }  // namespace
 
 extern "C" {
@@ -852,6 +1397,47 @@ int reni_envmap_shade_terms_dnormals(int64_t B, int64_t NP, int64_t J, const flo
   return terms_dnormals_common(B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, light_colors,
                                shininess, shininess_stride, vis, vis_batch_stride, d_diffuse, d_specular, d_normals, ws,
                                ws_bytes, stream);
+}
+
+size_t reni_envmap_shade_ggx_workspace_bytes(int64_t B, int64_t NP, int64_t J) {
+  if (B < 1 || NP < 1 || J < 1) return 0;
+  const size_t f = terms_partials(true, B, NP, J, 3) * sizeof(float);
+  const size_t g = terms_partials(false, B, NP, J, 1) * sizeof(float);
+  return (f > g ? f : g) + 256;
+}
+
+int reni_envmap_shade_ggx(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                          float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                          const float* light_colors, const float* alpha, int64_t alpha_stride, const uint32_t* vis,
+                          int64_t vis_batch_stride, float* diffuse, float* spec0, float* spec1, void* ws, size_t ws_bytes,
+                          void* stream) {
+  return ggx_common(true, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, light_colors,
+                    nullptr, nullptr, alpha, alpha_stride, vis, vis_batch_stride, diffuse, spec0, spec1, ws, ws_bytes, stream);
+}
+
+int reni_envmap_shade_ggx_backward(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                                   float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                                   const float* alpha, int64_t alpha_stride, const uint32_t* vis, int64_t vis_batch_stride,
+                                   const float* d_diffuse, const float* d_spec0, const float* d_spec1, float* dlight_colors,
+                                   void* ws, size_t ws_bytes, void* stream) {
+  return ggx_common(false, B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, d_diffuse, d_spec0,
+                    d_spec1, alpha, alpha_stride, vis, vis_batch_stride, dlight_colors, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+size_t reni_envmap_shade_ggx_dpixel_workspace_bytes(int64_t B, int64_t NP, int64_t J) {
+  if (B < 1 || NP < 1 || J < 1) return 0;
+  // one slot of 1 + 3 floats per (image chunk, split, pixel): per-image directions make every image a chunk
+  return (size_t)B * n_splits(NP, J) * NP * 4 * sizeof(float) + 256;
+}
+
+int reni_envmap_shade_ggx_dpixel(int64_t B, int64_t NP, int64_t J, const float* normals, const float* positions, float cam_x,
+                                 float cam_y, float cam_z, const float* light_dirs, int64_t dirs_batch_stride,
+                                 const float* light_colors, const float* alpha, int64_t alpha_stride, const uint32_t* vis,
+                                 int64_t vis_batch_stride, const float* d_diffuse, const float* d_spec0, const float* d_spec1,
+                                 float* d_alpha, float* d_normals, void* ws, size_t ws_bytes, void* stream) {
+  return ggx_dpixel_common(B, NP, J, normals, positions, cam_x, cam_y, cam_z, light_dirs, dirs_batch_stride, light_colors, alpha,
+                           alpha_stride, vis, vis_batch_stride, d_diffuse, d_spec0, d_spec1, d_alpha, d_normals, ws, ws_bytes,
+                           stream);
 }
 
 }  // extern "C"

@@ -273,6 +273,143 @@ class SpatialMaterials(nn.Module):
         return self.albedo, self.ks, self.shininess.clamp(self.shininess_min, self.shininess_max)
 
 
+class _ShadeGgxFn(torch.autograd.Function):
+    """(D, S0, S1) of ``ops.envmap_shade_ggx``.  Gradients: the light colours through the backward kernel; alpha and the
+    (un-normalised) pixel normals through the dpixel kernel, which runs only when one of them is asked for and computes the
+    normals' gradient only when that one is."""
+
+    @staticmethod
+    def forward(ctx, light_colors, alpha, normals, positions, camera_center, light_dirs, vis):
+        ctx.save_for_backward(normals, positions, camera_center, light_dirs, alpha, light_colors)
+        ctx.vis = vis  # a constant of (mesh, camera, directions): see _constant_mask
+        return ops.envmap_shade_ggx(normals, positions, camera_center, light_dirs, light_colors, alpha, vis=vis)
+
+    @staticmethod
+    def backward(ctx, gD, gS0, gS1):
+        normals, positions, camera_center, light_dirs, alpha, light_colors = ctx.saved_tensors
+        gC = ga = gn = None
+        gD, gS0, gS1 = gD.contiguous(), gS0.contiguous(), gS1.contiguous()
+        if ctx.needs_input_grad[0]:
+            gC = ops.envmap_shade_ggx_backward(normals, positions, camera_center, light_dirs, gD, gS0, gS1, alpha, vis=ctx.vis)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            ga, gn = ops.envmap_shade_ggx_dpixel(normals, positions, camera_center, light_dirs, light_colors, gD, gS0, gS1, alpha,
+                                                 vis=ctx.vis, need_dn=ctx.needs_input_grad[2])
+            if ctx.needs_input_grad[1]:
+                ga = (ga.sum() if alpha.numel() == 1 else ga).reshape(alpha.shape).to(alpha.dtype)
+            else:
+                ga = None
+            if gn is not None:
+                gn = gn.to(normals.dtype)
+        return gC, ga, gn, None, None, None, None
+
+
+def shade_terms_ggx(pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap, alpha, vis=None):
+    """(D, S0, S1), each [B, NP, 3]: the diffuse sum and the two specular sums of the microfacet (GGX) material -- S0 =
+    sum_j k C, S1 = sum_j k f C with k the GGX lobe x separable Smith x nl and f Schlick's (1 - V.H)^5 -- for an alpha
+    (= roughness^2) per pixel (a float, one value or [NP]; every value > 0).  ``compose_microfacet`` turns them into colours.
+    Differentiable with respect to ``envmap.environment_map``, ``alpha`` and ``pixel_normals``; positions, camera, directions
+    and the mask are constants (one that requires grad raises)."""
+    _constant("the pixel positions", pixel_positions)
+    _constant("the light directions", envmap.directions)
+    cam = torch.as_tensor(_constant("the camera centre", camera_center), dtype=torch.float32).reshape(-1)[:3].cpu()
+    NP = pixel_normals.shape[0] if isinstance(pixel_normals, torch.Tensor) and pixel_normals.dim() == 2 else -1
+    light_colors = envmap.environment_map
+    if not isinstance(alpha, torch.Tensor):
+        alpha = torch.as_tensor(float(alpha), dtype=torch.float32, device=light_colors.device)
+    if alpha.numel() != 1 and tuple(alpha.shape) != (NP,):
+        raise ValueError(f"alpha must be a float, one value or [{NP}] (one per pixel), got {tuple(alpha.shape)}")
+    dirs = _shared_grid(envmap.directions)
+    return _ShadeGgxFn.apply(light_colors, alpha, pixel_normals, pixel_positions, cam, dirs, _constant_mask(vis, NP, dirs))
+
+
+def compose_microfacet(D: torch.Tensor, S0: torch.Tensor, S1: torch.Tensor, base_color, metallic,
+                       f0_dielectric: float = 0.04) -> torch.Tensor:
+    """colours [B, NP, 3] = (1 - metallic) base_color D + F0 S0 + (1 - F0) S1 with F0 = f0_dielectric (1 - metallic) +
+    base_color metallic, from the terms of ``shade_terms_ggx``.  base_color: a float, [3] or [NP, 3]; metallic: a float, one
+    value or [NP].  Plain torch (any device, any float dtype): its autograd gives the gradients of both."""
+    if not isinstance(D, torch.Tensor) or D.dim() != 3 or D.shape[-1] != 3 or S0.shape != D.shape or S1.shape != D.shape:
+        raise ValueError("D, S0 and S1 must be [B, NP, 3]")
+    NP = D.shape[1]
+    c = torch.as_tensor(base_color, dtype=D.dtype, device=D.device) if not isinstance(base_color, torch.Tensor) else base_color.to(D.dtype)
+    if c.numel() != 1 and tuple(c.shape) not in ((3,), (NP, 3)):
+        raise ValueError(f"base_color must be a float, [3] or [{NP}, 3], got {tuple(c.shape)}")
+    if c.numel() == 1:
+        c = c.reshape(1)
+    m = torch.as_tensor(metallic, dtype=D.dtype, device=D.device) if not isinstance(metallic, torch.Tensor) else metallic.to(D.dtype)
+    if m.numel() != 1 and tuple(m.shape) != (NP,):
+        raise ValueError(f"metallic must be a float, one value or [{NP}] (one per pixel), got {tuple(m.shape)}")
+    m = m.reshape(1, 1) if m.numel() == 1 else m.reshape(NP, 1)
+    F0 = float(f0_dielectric) * (1.0 - m) + c * m
+    return ((1.0 - m) * c) * D + F0 * S0 + (1.0 - F0) * S1
+
+
+def microfacet_shading_materials(pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap, base_color,
+                                 roughness, metallic, vis=None, roughness_min: float = 0.1,
+                                 f0_dielectric: float = 0.04) -> torch.Tensor:
+    """colours [B, NP, 3] of a base-colour / roughness / metallic material per pixel:
+    ``compose_microfacet(*shade_terms_ggx(..., alpha = clamp(roughness, roughness_min, 1)^2), base_color, metallic)``.
+    Differentiable with respect to the environment map, the three material inputs and the pixel normals."""
+    if not float(roughness_min) > 0.0:
+        raise ValueError("roughness_min must be > 0")
+    if not isinstance(roughness, torch.Tensor):
+        roughness = torch.as_tensor(float(roughness), dtype=torch.float32, device=envmap.environment_map.device)
+    r = roughness.clamp(float(roughness_min), 1.0)
+    D, S0, S1 = shade_terms_ggx(pixel_normals, pixel_positions, camera_center, envmap, r * r, vis=vis)
+    return compose_microfacet(D, S0, S1, base_color, metallic, f0_dielectric)
+
+
+class MicrofacetMaterials(nn.Module):
+    """A base-colour / roughness / metallic material per render pixel.  base_color: a float, [3], [NP, 3] or [S, S, 3];
+    roughness and metallic: a float, [NP] or [S, S].  The names in ``learn`` become Parameters (the caller owns their
+    optimiser), the others buffers.  ``values()`` -> (base_color, roughness, metallic) flattened over the pixels, the
+    roughness clamped to [roughness_min, 1] and the metallic to [0, 1], so an optimiser cannot walk them out of the kernels'
+    precondition alpha = roughness^2 > 0."""
+
+    NAMES = ("base_color", "roughness", "metallic")
+
+    def __init__(self, base_color=0.8, roughness=0.5, metallic=0.0, learn=(), roughness_min: float = 0.1,
+                 f0_dielectric: float = 0.04):
+        super().__init__()
+        learn = (learn,) if isinstance(learn, str) else tuple(learn)
+        for name in learn:
+            if name not in self.NAMES:
+                raise ValueError(f"learn names must be among {self.NAMES}, got {name!r}")
+        if not 0.0 < float(roughness_min) <= 1.0:
+            raise ValueError("0 < roughness_min <= 1 is required")
+        self.roughness_min, self.f0_dielectric = float(roughness_min), float(f0_dielectric)
+        a = torch.as_tensor(base_color, dtype=torch.float32).detach().clone()
+        if a.dim() == 3 and a.shape[0] == a.shape[1] and a.shape[2] == 3:
+            a = a.reshape(-1, 3)
+        if a.dim() > 2 or (a.dim() == 1 and a.shape[0] != 3) or (a.dim() == 2 and a.shape[1] != 3):
+            raise ValueError(f"base_color must be a float, [3], [NP, 3] or [S, S, 3], got {tuple(a.shape)}")
+        vals = {"base_color": a}
+        for name, x in (("roughness", roughness), ("metallic", metallic)):
+            x = torch.as_tensor(x, dtype=torch.float32).detach().clone()
+            if x.dim() == 2 and x.shape[0] == x.shape[1]:
+                x = x.reshape(-1)
+            if x.dim() > 1:
+                raise ValueError(f"{name} must be a float, [NP] or [S, S], got {tuple(x.shape)}")
+            vals[name] = x
+        sizes = {a.shape[0]} if a.dim() == 2 else set()
+        sizes |= {vals[k].shape[0] for k in ("roughness", "metallic") if vals[k].numel() > 1}
+        if len(sizes) > 1:
+            raise ValueError(f"the per-pixel materials disagree about the number of pixels: {sorted(sizes)}")
+        for name, x in vals.items():
+            if name in learn:
+                setattr(self, name, nn.Parameter(x))
+            else:
+                self.register_buffer(name, x)
+
+    def values(self):
+        return self.base_color, self.roughness.clamp(self.roughness_min, 1.0), self.metallic.clamp(0.0, 1.0)
+
+    def shade(self, pixel_normals, pixel_positions, camera_center, envmap: EnvironmentMap, vis=None) -> torch.Tensor:
+        """colours [B, NP, 3] of this material on a G-buffer (``microfacet_shading_materials`` with ``values()``)."""
+        c, r, m = self.values()
+        return microfacet_shading_materials(pixel_normals, pixel_positions, camera_center, envmap, c, r, m, vis=vis,
+                                            roughness_min=self.roughness_min, f0_dielectric=self.f0_dielectric)
+
+
 def blinn_phong_shading_env_map(device, meshes, fragments, envmap, cameras, materials, kd, ks):
     """Reference signature (:46-48).  Returns (colors [B,H,W,3], pixel_normals [B,H,W,3])."""
     verts = meshes.verts_packed()

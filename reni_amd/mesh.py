@@ -20,9 +20,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops, textures
-from .envmap_shader import (EnvironmentMap, SpatialMaterials, _Materials, _shared_grid, blinn_phong_shading_gbuffer,
-                            blinn_phong_shading_materials)
-from .textures import TexturedMaterials
+from .envmap_shader import (EnvironmentMap, MicrofacetMaterials, SpatialMaterials, _Materials, _shared_grid,
+                            blinn_phong_shading_gbuffer, blinn_phong_shading_materials, microfacet_shading_materials)
+from .textures import TexturedMaterials, TexturedMicrofacetMaterials
 
 Fragments = namedtuple("Fragments", ["pix_to_face", "zbuf", "bary_coords", "dists"])
 
@@ -372,7 +372,12 @@ class HipMeshRenderer(nn.Module):
     ``shader_cameras=FoVPerspectiveCameras(R=R, T=T)``, its true camera centre -- may share one such object.  With a
     ``normal`` texture the shader gets ``materials.shading_normals(...)`` (the normal map's) instead of the G-buffer's normals,
     and the render is differentiable with respect to that texture when it requires grad; the shadow mask and the returned
-    ``pixel_normals`` stay the geometry's (``shading_normals(mesh, R, T)`` returns the bent ones)."""
+    ``pixel_normals`` stay the geometry's (``shading_normals(mesh, R, T)`` returns the bent ones).
+
+    ``materials=MicrofacetMaterials(...)`` / ``TexturedMicrofacetMaterials(...)``: a base colour, a roughness and a metallic
+    per render pixel / in the mesh's UV space, shaded by the microfacet (GGX) terms
+    (``envmap_shader.microfacet_shading_materials``); everything said above about the two Blinn-Phong classes holds for
+    their microfacet siblings, the normal texture included."""
 
     def __init__(self, rasterizer: MeshRasterizer, kd: float = None, ks: float = None, materials=None, shader_cameras=None,
                  shadows: bool = False):
@@ -380,9 +385,11 @@ class HipMeshRenderer(nn.Module):
         self.rasterizer = rasterizer
         self.shadows = bool(shadows)  # cast shadows: the mesh blocks the texels it hides from a pixel
         self.spatial = isinstance(materials, SpatialMaterials)
-        self.textured = isinstance(materials, TexturedMaterials)
-        if kd is None and not self.spatial and not self.textured:
-            raise ValueError("kd is required unless materials is a SpatialMaterials or a TexturedMaterials")
+        self.microfacet = isinstance(materials, (MicrofacetMaterials, TexturedMicrofacetMaterials))
+        self.textured = isinstance(materials, (TexturedMaterials, TexturedMicrofacetMaterials))
+        if kd is None and not self.spatial and not self.textured and not self.microfacet:
+            raise ValueError("kd is required unless materials is a SpatialMaterials, a TexturedMaterials or one of their "
+                             "microfacet siblings")
         self.kd = 1.0 if kd is None else float(kd)
         self.ks = 1.0 - self.kd if ks is None else float(ks)
         self.materials = materials if materials is not None else _Materials(500.0)
@@ -397,7 +404,20 @@ class HipMeshRenderer(nn.Module):
         vis = None
         if self.shadows:  # the mask of the envmap's directions: one for a shared grid, one per image for per-image lists
             vis = self.rasterizer.visibility(meshes_world, R, T, _shared_grid(envmap.directions))
-        if self.spatial:
+        if self.microfacet:
+            m = self.materials
+            if m.roughness.device != nrm.device:
+                m.to(nrm.device)
+            shade_nrm = nrm
+            if not self.textured:
+                values = m.values()
+            else:
+                values = m.values(self.rasterizer, meshes_world, R, T)
+                if m.normal is not None:  # as below: the normal map bends the shading normals only
+                    shade_nrm = m.shading_normals(self.rasterizer, meshes_world, R, T, nrm)
+            colors = microfacet_shading_materials(shade_nrm, pos, self.camera_center, envmap, *values, vis=vis,
+                                                  roughness_min=m.roughness_min, f0_dielectric=m.f0_dielectric)
+        elif self.spatial:
             if self.materials.ks.device != nrm.device:
                 self.materials.to(nrm.device)
             colors = blinn_phong_shading_materials(nrm, pos, self.camera_center, envmap, *self.materials.values(), vis=vis)
@@ -422,7 +442,7 @@ class HipMeshRenderer(nn.Module):
         _, nrm, _ = self.rasterizer.gbuffer(meshes_world, R, T)
         S = self.rasterizer.raster_settings.image_size
         if self.textured and self.materials.normal is not None:
-            if self.materials.ks.device != nrm.device:
+            if self.materials.normal.device != nrm.device:
                 self.materials.to(nrm.device)
             nrm = self.materials.shading_normals(self.rasterizer, meshes_world, R, T, nrm)
         return torch.nn.functional.normalize(nrm, p=2, dim=-1, eps=1e-6).reshape(S, S, 3)
@@ -447,12 +467,13 @@ def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device, shadows: bo
     camera at look_at_view_transform(2, 0, 0).  ``device`` must be a GPU device (there is no CPU path).  ``shadows=True``:
     the mesh casts shadows on itself (``HipMeshRenderer(shadows=True)``); the default renders what the reference does.
     ``materials``: a ``SpatialMaterials`` of img_size x img_size pixels, or a ``TexturedMaterials`` (the OBJ's ``vt`` are then
-    read, ``load_obj_uv``); kd is not used with either; None: Materials(shininess=500)."""
-    textured = isinstance(materials, TexturedMaterials)
+    read, ``load_obj_uv``), or their microfacet siblings ``MicrofacetMaterials`` / ``TexturedMicrofacetMaterials``; kd is not
+    used with any of them; None: Materials(shininess=500)."""
+    textured = isinstance(materials, (TexturedMaterials, TexturedMicrofacetMaterials))
     if textured:
         verts, faces, vt, ft = load_obj_uv(obj_path)
         if vt.shape[0] < 1:
-            raise ValueError(f"{obj_path} has no texture coordinates (vt lines): TexturedMaterials needs them")
+            raise ValueError(f"{obj_path} has no texture coordinates (vt lines): {type(materials).__name__} needs them")
     else:
         verts, faces = load_obj(obj_path)
     verts = rotate_axis_angle_y(verts, obj_rotation)
@@ -465,8 +486,10 @@ def build_hip_renderer(obj_path, obj_rotation, img_size, kd, device, shadows: bo
     mesh.verts_normals_packed()
     cameras = FoVPerspectiveCameras(device=device)
     raster = MeshRasterizer(cameras=cameras, raster_settings=RasterizationSettings(image_size=int(img_size)))
-    if materials is not None and not isinstance(materials, (SpatialMaterials, TexturedMaterials)):
-        raise ValueError("materials must be a SpatialMaterials, a TexturedMaterials or None")
+    if materials is not None and not isinstance(materials, (SpatialMaterials, TexturedMaterials, MicrofacetMaterials,
+                                                            TexturedMicrofacetMaterials)):
+        raise ValueError("materials must be a SpatialMaterials, a TexturedMaterials, a MicrofacetMaterials, a "
+                         "TexturedMicrofacetMaterials or None")
     renderer = HipMeshRenderer(raster, kd=kd, materials=_Materials(500.0) if materials is None else materials.to(device),
                                shadows=shadows)
     R, T = look_at_view_transform(2.0, 0.0, 0.0, degrees=True, device=device)

@@ -694,6 +694,98 @@ def envmap_shade_terms_dnormals(normals, positions, camera_center, light_dirs, l
     return _terms_call(None, normals, positions, camera_center, light_dirs, (light_colors, gD, gS), shininess, vis)
 
 
+def _ggx_call(mode: str, normals, positions, camera_center, light_dirs, srcs, alpha, vis, need_dn=False):
+    """reni_envmap_shade_ggx / _backward / _dpixel (include/reni_hip.h) behind the checks of ``_shade_call``.  mode "forward":
+    srcs = (light colours [B,J,3],); "backward": (gD, gS0, gS1) [B,NP,3]; "dpixel": (light colours, gD, gS0, gS1).  alpha: a
+    float, a one-element tensor or [NP]."""
+    _dirs_dims(light_dirs)
+    if not isinstance(normals, torch.Tensor) or normals.dim() != 2:
+        raise ValueError("normals and positions must be [NP, 3]")
+    NP = normals.shape[0]
+    if isinstance(alpha, torch.Tensor):
+        if alpha.numel() != 1 and tuple(alpha.shape) != (NP,):
+            raise ValueError(f"alpha must be a float, one value or [{NP}] (one per pixel), got {tuple(alpha.shape)}")
+    elif not isinstance(alpha, (int, float)):
+        raise ValueError(f"alpha must be a float, one value or [{NP}] (one per pixel), got {type(alpha).__name__}")
+    if vis is not None:
+        check_visibility(vis, NP, light_dirs.shape[-2])
+        if vis.shape[0] != 1 and (light_dirs.dim() == 2 or vis.shape[0] != light_dirs.shape[0]):
+            raise ValueError(f"a mask of {vis.shape[0]} images needs per-image directions [{vis.shape[0]}, J, 3]")
+    _require_cuda(normals, positions, light_dirs, *srcs, vis, alpha if isinstance(alpha, torch.Tensor) else None)
+    lib = _lib.load()
+    f32 = torch.float32
+    normals = normals.to(f32).contiguous(); positions = positions.to(f32).contiguous()
+    light_dirs = light_dirs.to(f32).contiguous()
+    srcs = [x.to(f32).contiguous() for x in srcs]
+    dev = srcs[0].device
+    if normals.shape != (NP, 3) or positions.shape != (NP, 3):
+        raise ValueError("normals and positions must be [NP, 3]")
+    B = srcs[0].shape[0]
+    if light_dirs.dim() == 2:
+        J, stride = light_dirs.shape[0], 0
+    else:
+        if light_dirs.shape[0] != B:
+            raise ValueError("light_dirs batch size must match the colours'")
+        J, stride = light_dirs.shape[1], light_dirs.shape[1] * 3
+    for i, x in enumerate(srcs):
+        want = (B, J, 3) if (mode == "forward" or (mode == "dpixel" and i == 0)) else (B, NP, 3)
+        if tuple(x.shape) != want:
+            raise ValueError(f"expected a {want} tensor, got {tuple(x.shape)}")
+    if isinstance(alpha, torch.Tensor):
+        al = alpha.detach().to(device=dev, dtype=f32).reshape(-1).contiguous()
+    else:
+        al = torch.full((1,), float(alpha), dtype=f32, device=dev)
+    cam = [float(x) for x in torch.as_tensor(camera_center).reshape(-1)[:3].tolist()]
+    if mode == "dpixel":
+        nbytes = int(lib.reni_envmap_shade_ggx_dpixel_workspace_bytes(B, NP, J))
+    else:
+        nbytes = int(lib.reni_envmap_shade_ggx_workspace_bytes(B, NP, J))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    vptr, vstride = None, 0
+    if vis is not None:
+        vis = vis.contiguous()
+        vptr, vstride = vis.data_ptr(), (0 if vis.shape[0] == 1 else NP * vis.shape[2])
+    head = (B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride)
+    mats = (al.data_ptr(), 0 if al.numel() == 1 else 1, vptr, vstride)
+    if mode == "dpixel":
+        d_alpha = torch.empty(NP, dtype=f32, device=dev)
+        d_normals = torch.empty((NP, 3), dtype=f32, device=dev) if need_dn else None
+        _call(lib.reni_envmap_shade_ggx_dpixel, dev, *head, srcs[0].data_ptr(), *mats, srcs[1].data_ptr(), srcs[2].data_ptr(),
+              srcs[3].data_ptr(), d_alpha.data_ptr(), d_normals.data_ptr() if need_dn else None, ws.data_ptr(), nbytes)
+        return d_alpha, d_normals
+    if mode == "forward":
+        outs = [torch.empty((B, NP, 3), dtype=f32, device=dev) for _ in range(3)]
+        _call(lib.reni_envmap_shade_ggx, dev, *head, srcs[0].data_ptr(), *mats, outs[0].data_ptr(), outs[1].data_ptr(),
+              outs[2].data_ptr(), ws.data_ptr(), nbytes)
+        return tuple(outs)
+    out = torch.empty((B, J, 3), dtype=f32, device=dev)
+    _call(lib.reni_envmap_shade_ggx_backward, dev, *head, *mats, srcs[0].data_ptr(), srcs[1].data_ptr(), srcs[2].data_ptr(),
+          out.data_ptr(), ws.data_ptr(), nbytes)
+    return out
+
+
+def envmap_shade_ggx(normals, positions, camera_center, light_dirs, light_colors, alpha, vis=None):
+    """The microfacet shader's terms -> (D, S0, S1), each [B,NP,3]: D = sum_j nl C (``envmap_shade_terms``' bits), S0 =
+    sum_j k C and S1 = sum_j k f C with k the GGX lobe x separable Smith x nl and f = (1 - V.H)^5 (include/reni_hip.h has
+    the definition; ``envmap_shader.compose_microfacet`` applies the material).  alpha (= roughness^2): a float, a one-element
+    tensor or [NP]; every value must be > 0 (anything else gives unspecified values for that pixel)."""
+    return _ggx_call("forward", normals, positions, camera_center, light_dirs, (light_colors,), alpha, vis)
+
+
+def envmap_shade_ggx_backward(normals, positions, camera_center, light_dirs, gD, gS0, gS1, alpha, vis=None):
+    """d loss / d light_colors [B,J,3] for upstream gradients gD, gS0, gS1 [B,NP,3] of ``envmap_shade_ggx``' three terms."""
+    return _ggx_call("backward", normals, positions, camera_center, light_dirs, (gD, gS0, gS1), alpha, vis)
+
+
+def envmap_shade_ggx_dpixel(normals, positions, camera_center, light_dirs, light_colors, gD, gS0, gS1, alpha, vis=None,
+                            need_dn=False):
+    """(d loss / d alpha [NP], d loss / d normals [NP,3] | None) for upstream gradients of ``envmap_shade_ggx``' terms.  d alpha
+    is per pixel also when one alpha serves all pixels (its gradient is then the sum); the normals' gradient goes through
+    F.normalize's Jacobian with strict gates (a zero normal gets exactly 0) and is computed only with need_dn, which does not
+    move d alpha's bits."""
+    return _ggx_call("dpixel", normals, positions, camera_center, light_dirs, (light_colors, gD, gS0, gS1), alpha, vis, need_dn)
+
+
 def _vertex_face_csr(faces: torch.Tensor, V: int):
     """The faces of every vertex as corner indices 3 f + k, ascending per vertex (a stable sort of the flattened index list on
     the device), and the [V+1] offsets into that list.  Corners whose index lies outside [0, V) are left out."""

@@ -130,27 +130,15 @@ def perturb_normals(pixel_normals, tangent, bitangent, valid, m, strength: float
     return torch.where(valid[:, None], bent, pixel_normals)
 
 
-class TexturedMaterials(nn.Module):
-    """A Blinn-Phong material in the mesh's UV space.  Each of albedo, ks and shininess is a scalar (albedo: or [3]) or a
-    texture -- [H, W, 3] for the albedo, [H, W] for the other two; the sizes may differ.  The names in ``learn`` become
-    Parameters (the caller owns their optimiser), the others buffers.  ``levels=None``: the full pyramid of each texture
-    (one level where its size is no power of two).  ``values(rasterizer, mesh, R, T)`` -> the per-pixel (albedo [P, 3], ks
-    [P], shininess [P]) -- or the scalars -- that ``blinn_phong_shading_materials`` takes; the shininess is clamped to
-    [shininess_min, shininess_max] AFTER the fetch (a background pixel fetches 0 and is clamped too: it is never shaded).
+class _UVMaterials(nn.Module):
+    """What the materials in UV space share: the lookup options, the registration of scalars and textures (the names in
+    ``learn`` as Parameters, the others as buffers), the fetch through the rasteriser's cached taps and the optional normal
+    texture.  A subclass names its inputs in ``NAMES``; the first is the colour (a float, [3] or [H, W, 3]), the others are
+    scalars (a float or [H, W])."""
 
-    ``normal``: a tangent-space normal texture [H, W, 3] encoded in [0, 1] (flat: (0.5, 0.5, 1)), with its own size and
-    pyramid; "normal" may be named in ``learn``.  ``shading_normals(rasterizer, mesh, R, T, pixel_normals)`` bends the
-    G-buffer's normals by it (``perturb_normals`` with ``normal_strength``); ``values`` and ``NAMES`` do not know it, and
-    with ``normal=None`` nothing of it runs.
+    NAMES = ()
 
-    One object handed to several renderers, each with its own rasteriser and camera, accumulates one texture gradient."""
-
-    NAMES = ("albedo", "ks", "shininess")
-
-    def __init__(self, albedo=1.0, ks=0.0, shininess=500.0, learn=(), levels=None, wrap: str = "clamp", align_corners: bool = False,
-                 lod_bias: float = 0.0, shininess_min: float = 1.0, shininess_max: float = 2000.0, normal=None,
-                 normal_strength: float = 1.0):
-        super().__init__()
+    def _register(self, given, learn, levels, wrap, align_corners, lod_bias, normal, normal_strength):
         learn = (learn,) if isinstance(learn, str) else tuple(learn)
         for name in learn:
             if name not in self.NAMES + ("normal",):
@@ -158,21 +146,17 @@ class TexturedMaterials(nn.Module):
         if "normal" in learn and normal is None:
             raise ValueError('learn names "normal", but no normal texture is given')
         self.normal_strength = float(normal_strength)
-        if not 0.0 < float(shininess_min) <= float(shininess_max):
-            raise ValueError("0 < shininess_min <= shininess_max is required")
         if wrap not in ("clamp", "repeat"):
             raise ValueError(f'wrap must be "clamp" or "repeat", got {wrap!r}')
-        self.shininess_min, self.shininess_max = float(shininess_min), float(shininess_max)
         self.levels = None if levels is None else int(levels)
         self.wrap, self.align_corners, self.lod_bias = wrap, bool(align_corners), float(lod_bias)
         vals = {}
-        a = torch.as_tensor(albedo, dtype=torch.float32).detach().clone()
-        if not (a.dim() == 0 or tuple(a.shape) == (3,) or (a.dim() == 3 and a.shape[2] == 3 and min(a.shape[:2]) >= 1)):
-            raise ValueError(f"albedo must be a float, [3] or a texture [H, W, 3], got {tuple(a.shape)}")
-        vals["albedo"] = a
-        for name, x in (("ks", ks), ("shininess", shininess)):
+        for name, x in zip(self.NAMES, given):
             x = torch.as_tensor(x, dtype=torch.float32).detach().clone()
-            if not (x.dim() == 0 or (x.dim() == 2 and min(x.shape) >= 1)):
+            if name == self.NAMES[0]:
+                if not (x.dim() == 0 or tuple(x.shape) == (3,) or (x.dim() == 3 and x.shape[2] == 3 and min(x.shape[:2]) >= 1)):
+                    raise ValueError(f"{name} must be a float, [3] or a texture [H, W, 3], got {tuple(x.shape)}")
+            elif not (x.dim() == 0 or (x.dim() == 2 and min(x.shape) >= 1)):
                 raise ValueError(f"{name} must be a float or a texture [H, W], got {tuple(x.shape)}")
             vals[name] = x
         if normal is not None:
@@ -196,16 +180,17 @@ class TexturedMaterials(nn.Module):
     def is_texture(x: torch.Tensor) -> bool:
         return x.dim() >= 2
 
-    def values(self, rasterizer, mesh, R=None, T=None):
+    def _taps(self, x, rasterizer, mesh, R, T):
+        return rasterizer.texture_taps(mesh, R, T, size=tuple(x.shape[:2]), levels=self.levels, wrap=self.wrap,
+                                       align_corners=self.align_corners, lod_bias=self.lod_bias)
+
+    def _fetched(self, rasterizer, mesh, R=None, T=None):
+        """The inputs of ``NAMES`` per pixel (a texture: fetched through its taps) or as they are (a scalar)."""
         out = []
         for name in self.NAMES:
             x = getattr(self, name)
-            if self.is_texture(x):
-                taps = rasterizer.texture_taps(mesh, R, T, size=tuple(x.shape[:2]), levels=self.levels, wrap=self.wrap,
-                                               align_corners=self.align_corners, lod_bias=self.lod_bias)
-                x = sample(x, taps)
-            out.append(x)
-        return out[0], out[1], out[2].clamp(self.shininess_min, self.shininess_max)
+            out.append(sample(x, self._taps(x, rasterizer, mesh, R, T)) if self.is_texture(x) else x)
+        return out
 
     def shading_normals(self, rasterizer, mesh, R=None, T=None, pixel_normals=None):
         """The normals the shader is to use, [P, 3] (not normalised): ``pixel_normals`` (the G-buffer's) bent by the normal
@@ -224,7 +209,63 @@ class TexturedMaterials(nn.Module):
         the rounding of the weights' sum, and exactly (0, 0, 1) for a flat texture and on a pixel that sees no texture."""
         if self.normal is None:
             raise ValueError("these materials have no normal texture")
-        taps = rasterizer.texture_taps(mesh, R, T, size=tuple(self.normal.shape[:2]), levels=self.levels, wrap=self.wrap,
-                                       align_corners=self.align_corners, lod_bias=self.lod_bias)
         flat = self.normal.new_tensor([0.5, 0.5, 1.0])
-        return 2.0 * sample(self.normal - flat, taps) + self.normal.new_tensor([0.0, 0.0, 1.0])
+        return 2.0 * sample(self.normal - flat, self._taps(self.normal, rasterizer, mesh, R, T)) + self.normal.new_tensor([0.0, 0.0, 1.0])
+
+
+class TexturedMaterials(_UVMaterials):
+    """A Blinn-Phong material in the mesh's UV space.  Each of albedo, ks and shininess is a scalar (albedo: or [3]) or a
+    texture -- [H, W, 3] for the albedo, [H, W] for the other two; the sizes may differ.  The names in ``learn`` become
+    Parameters (the caller owns their optimiser), the others buffers.  ``levels=None``: the full pyramid of each texture
+    (one level where its size is no power of two).  ``values(rasterizer, mesh, R, T)`` -> the per-pixel (albedo [P, 3], ks
+    [P], shininess [P]) -- or the scalars -- that ``blinn_phong_shading_materials`` takes; the shininess is clamped to
+    [shininess_min, shininess_max] AFTER the fetch (a background pixel fetches 0 and is clamped too: it is never shaded).
+
+    ``normal``: a tangent-space normal texture [H, W, 3] encoded in [0, 1] (flat: (0.5, 0.5, 1)), with its own size and
+    pyramid; "normal" may be named in ``learn``.  ``shading_normals(rasterizer, mesh, R, T, pixel_normals)`` bends the
+    G-buffer's normals by it (``perturb_normals`` with ``normal_strength``); ``values`` and ``NAMES`` do not know it, and
+    with ``normal=None`` nothing of it runs.
+
+    One object handed to several renderers, each with its own rasteriser and camera, accumulates one texture gradient."""
+
+    NAMES = ("albedo", "ks", "shininess")
+
+    def __init__(self, albedo=1.0, ks=0.0, shininess=500.0, learn=(), levels=None, wrap: str = "clamp", align_corners: bool = False,
+                 lod_bias: float = 0.0, shininess_min: float = 1.0, shininess_max: float = 2000.0, normal=None,
+                 normal_strength: float = 1.0):
+        super().__init__()
+        if not 0.0 < float(shininess_min) <= float(shininess_max):
+            raise ValueError("0 < shininess_min <= shininess_max is required")
+        self.shininess_min, self.shininess_max = float(shininess_min), float(shininess_max)
+        self._register((albedo, ks, shininess), learn, levels, wrap, align_corners, lod_bias, normal, normal_strength)
+
+    def values(self, rasterizer, mesh, R=None, T=None):
+        out = self._fetched(rasterizer, mesh, R, T)
+        return out[0], out[1], out[2].clamp(self.shininess_min, self.shininess_max)
+
+
+class TexturedMicrofacetMaterials(_UVMaterials):
+    """A base-colour / roughness / metallic material in the mesh's UV space (``envmap_shader.MicrofacetMaterials`` is its
+    per-render-pixel sibling).  base_color: a float, [3] or a texture [H, W, 3]; roughness and metallic: a float or a texture
+    [H, W]; the sizes may differ.  ``learn``, ``levels``, ``wrap``, ``align_corners``, ``lod_bias``, ``normal`` and
+    ``normal_strength`` are ``TexturedMaterials``'.  ``values(rasterizer, mesh, R, T)`` -> the per-pixel (base_color [P, 3],
+    roughness [P], metallic [P]) -- or the scalars -- that ``microfacet_shading_materials`` takes; AFTER the fetch the
+    roughness is clamped to [roughness_min, 1] (a background pixel fetches 0 and is clamped too: it is never shaded) and the
+    metallic to [0, 1].
+
+    One object handed to several renderers, each with its own rasteriser and camera, accumulates one texture gradient."""
+
+    NAMES = ("base_color", "roughness", "metallic")
+
+    def __init__(self, base_color=0.8, roughness=0.5, metallic=0.0, learn=(), levels=None, wrap: str = "clamp",
+                 align_corners: bool = False, lod_bias: float = 0.0, roughness_min: float = 0.1, f0_dielectric: float = 0.04,
+                 normal=None, normal_strength: float = 1.0):
+        super().__init__()
+        if not 0.0 < float(roughness_min) <= 1.0:
+            raise ValueError("0 < roughness_min <= 1 is required")
+        self.roughness_min, self.f0_dielectric = float(roughness_min), float(f0_dielectric)
+        self._register((base_color, roughness, metallic), learn, levels, wrap, align_corners, lod_bias, normal, normal_strength)
+
+    def values(self, rasterizer, mesh, R=None, T=None):
+        out = self._fetched(rasterizer, mesh, R, T)
+        return out[0], out[1].clamp(self.roughness_min, 1.0), out[2].clamp(0.0, 1.0)

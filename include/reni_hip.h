@@ -673,6 +673,37 @@ int reni_envmap_lookup_backward(int64_t N, int64_t Lv, int64_t H, int64_t W, int
                                 const float* tap_weight, const int64_t* tap_order, const int64_t* offsets, float* grad_src,
                                 void* stream);
 
+/* ---- split-sum microfacet shading from a prefiltered chain (reni_tu_splitsum.hip; reni_amd/glossy.py: sample, ggx_dfg,
+ * shade_split_sum).  No reference counterpart.  fp32, deterministic (no float atomics, fixed summation orders).
+ * reni_envmap_lookup_dquery: the derivative of the lookup's out with respect to its QUERY, contracted with grad_out [N][P][3].
+ *   The arguments up to level_const are the lookup's, with its checks, limits and messages.  With (row, col) and the four
+ *   folded taps b00 .. b11 of the lookup's own coordinate chain, fr, fc its fractions and gr = 1 - fr, gc = 1 - fc:
+ *       d out / d row = gc (b10 - b00) + fc (b11 - b01)       d out / d col = gr (b01 - b00) + fr (b11 - b10)
+ *   mixed over the two levels with the forward's weights; Gr = sum_c grad_out[c] d out[c] / d row, Gc likewise, and with
+ *   rho^2 = q_x^2 + q_z^2 for the direction q (any length)
+ *       d_dirs = row_scale Gr (q_y q_x / rho, -rho, q_y q_z / rho) / |q|^2 + col_scale Gc (-q_z, 0, q_x) / rho^2
+ *   exactly 0 where the row clamp is active, where rho^2 = 0 (a pole direction) or |q|^2 = 0; never NaN or Inf for finite maps.
+ *       d_level = [0 <= level <= Lv - 1] sum_c grad_out[c] (v(la + 1) - v(la))[c],  la = min(floor(level), Lv - 2)
+ *   with v(l) the bilinear sample of level l: the slope of the piecewise-linear mix, right-sided at interior knots, left-sided
+ *   at the top knot; 0 for Lv = 1, for a level outside the closed range and for a NaN level.
+ *   d_dirs is [N][P][3] for per-map directions and [P][3], the sum over n ascending, for shared ones (dirs_stride_n = 0; Gr and
+ *   Gc are summed, the chain rule applied once); d_level is [N][P] or, for a shared level array, [P].  Either may be NULL (that
+ *   half is then not computed, and the other's bits do not change); both NULL is RENI_EINVAL, and so is d_level without a level
+ *   array.  One launch, no workspace.
+ * reni_ggx_dfg: out [2][R_r][R_v], the directional albedo of the microfacet material of reni_envmap_shade_ggx:
+ *   out[0] = int k d omega, out[1] = int k f d omega over the hemisphere for N = (0, 0, 1), V = (sqrt(1 - x^2), 0, x),
+ *   x = i / (R_v - 1), roughness r = r_min + j (1 - r_min) / (R_r - 1), alpha = r^2.  DEFINED as the midpoint rule on
+ *   M_u x M_phi nodes u = (a + 1/2) / M_u, phi = 2 pi (b + 1/2) / M_phi of GGX's inverse-CDF parametrisation of the half vector,
+ *   cos^2 theta_h = (1 - u) / (1 + (alpha^2 - 1) u), L = 2 (V.H) H - V, under which
+ *       out[0] = int int 2 nl (V.H) / (nh (nl + lam(nl)) (nv + lam(nv))) [nl > 0][V.H > 0] du dphi,  lam(t) = sqrt(alpha^2 + (1 - alpha^2) t^2)
+ *   and out[1] has the factor (1 - min(V.H, 1))^5 more.  2 <= R_v, R_r <= 1024, 1 <= M_u, M_phi <= 1024,
+ *   R_v R_r M_u M_phi <= 2^28, 1e-3 <= r_min < 1.  One launch (a workgroup per entry), no workspace. */
+int reni_envmap_lookup_dquery(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* src,
+                              const int64_t src_strides[5], const float* dirs, int64_t dirs_stride_n, const float* level,
+                              int64_t level_stride_n, float level_const, const float* grad_out, float* d_dirs, float* d_level,
+                              void* stream);
+int reni_ggx_dfg(int64_t R_v, int64_t R_r, float r_min, int64_t M_u, int64_t M_phi, float* out, void* stream);
+
 /* ---- UV-space textures: a material that lives on the surface (reni_tu_texture.hip; reni_amd/textures.py) --
  * A texture in the mesh's UV space is looked up per render pixel through the G-buffer, with a mip pyramid, and its gradient is
  * gathered back per texel.  No reference counterpart.  fp32, deterministic (no float atomics, fixed summation orders).

@@ -50,6 +50,7 @@ EXPORTS = (
     "reni_lobe_workspace_bytes", "reni_lobe_convolve", "reni_envmap_lookup",
     "reni_lobe_denominators_workspace_bytes", "reni_lobe_denominators", "reni_lobe_backward_workspace_bytes",
     "reni_lobe_convolve_backward", "reni_envmap_lookup_taps", "reni_envmap_lookup_backward",
+    "reni_envmap_lookup_dquery", "reni_ggx_dfg",
     "reni_mesh_pixel_uv", "reni_texture_taps", "reni_texture_pyramid", "reni_texture_pyramid_backward", "reni_texture_fetch",
     "reni_texture_fetch_backward",
     "reni_image_workspace_bytes", "reni_unnormalise_srgb", "reni_minmax_normalise",
@@ -275,6 +276,11 @@ def load():
     lib.reni_envmap_lookup_backward.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_void_p]
     lib.reni_envmap_lookup_backward.restype = c_int32
+    lib.reni_envmap_lookup_dquery.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, POINTER(c_int64), c_void_p,
+                                              c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.reni_envmap_lookup_dquery.restype = c_int32
+    lib.reni_ggx_dfg.argtypes = [c_int64, c_int64, c_float, c_int64, c_int64, c_void_p, c_void_p]
+    lib.reni_ggx_dfg.restype = c_int32
     lib.reni_mesh_pixel_uv.argtypes = [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_float),
                                        POINTER(c_float), c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.reni_mesh_pixel_uv.restype = c_int32

@@ -1268,6 +1268,56 @@ def envmap_lookup_backward(grad_out, Lv: int, H: int, W: int, dirs=None, level=N
     return out
 
 
+def envmap_lookup_dquery(maps, dirs, level, grad_out, need_dirs: bool = True, need_level: bool = False):
+    """reni_envmap_lookup_dquery: (d loss / d dirs, d loss / d level) of ``envmap_lookup(maps, dirs, level)`` for the upstream
+    grad_out [N, P, 3]; a half that is not needed is None and is not computed.  d dirs has the shape of dirs ([P, 3], the sum
+    over the maps, or [N, P, 3]), d level the shape of the level tensor ([P] or [N, P]); need_level needs a level tensor.  The
+    chain rule runs through the lookup's own coordinate chain: exact zeros at a pole direction, for the zero vector and for a
+    level outside [0, Lv - 1]; at a knot the level's slope is the right-sided one, at Lv - 1 the left-sided one."""
+    if not (need_dirs or need_level):
+        raise ValueError("neither d dirs nor d level is asked for")
+    _require_cuda(maps, dirs, grad_out, level if isinstance(level, torch.Tensor) and level.dim() > 0 else None)
+    if maps.dtype != torch.float32:
+        maps = maps.float()
+    if maps.dim() == 4:
+        maps = maps.unsqueeze(1)
+    if maps.dim() != 5 or maps.shape[4] != 3:
+        raise ValueError(f"maps must be [N, H, W, 3] or [N, Lv, H, W, 3], got {tuple(maps.shape)}")
+    N, Lv, H, W, _ = maps.shape
+    if min(N, Lv, H, W) < 1 or W % 2:
+        raise ValueError(f"expected non-empty maps of even width, got {tuple(maps.shape)}")
+    dev = maps.device
+    dirs, P, dn, level, lp, ln, lc = _lookup_dirs_level(N, dirs, level, dev)
+    if need_level and lp is None:
+        raise ValueError("d level needs the level as a tensor [P] or [N, P]")
+    grad_out = _f32c(grad_out)
+    if tuple(grad_out.shape) != (N, P, 3) or grad_out.device != dev:
+        raise ValueError(f"grad_out must be [{N}, {P}, 3] on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
+    d_dirs = torch.empty_like(dirs) if need_dirs else None
+    d_level = torch.empty_like(level) if need_level else None
+    st = (ctypes.c_int64 * 5)(*maps.stride())
+    _call(_lib.load().reni_envmap_lookup_dquery, dev, N, Lv, H, W, P, maps.data_ptr(), st, dirs.data_ptr(), dn, lp, ln, lc,
+          grad_out.data_ptr(), d_dirs.data_ptr() if need_dirs else None, d_level.data_ptr() if need_level else None)
+    return d_dirs, d_level
+
+
+def ggx_dfg(size_v: int = 32, size_r: int = 32, roughness_min: float = 0.1, nodes_u: int = 128, nodes_phi: int = 128,
+            device="cuda") -> torch.Tensor:
+    """reni_ggx_dfg: the directional-albedo table [2, size_r, size_v] of the microfacet material -- A0 = int k d omega and
+    A1 = int k f d omega (k, f of ``envmap_shade_ggx``) at N.V = i / (size_v - 1) and roughness = roughness_min +
+    j (1 - roughness_min) / (size_r - 1) -- by the midpoint rule on nodes_u x nodes_phi nodes of GGX's inverse-CDF
+    parametrisation of the half vector."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.RENILibraryError("RENI HIP ops need tensors on a GPU device (got a CPU device); there is no CPU fallback")
+    size_v, size_r, nodes_u, nodes_phi = int(size_v), int(size_r), int(nodes_u), int(nodes_phi)
+    if min(size_v, size_r) < 2 or min(nodes_u, nodes_phi) < 1:
+        raise ValueError(f"need table sizes >= 2 and node counts >= 1, got {(size_v, size_r, nodes_u, nodes_phi)}")
+    out = torch.empty(2, size_r, size_v, dtype=torch.float32, device=dev)
+    _call(_lib.load().reni_ggx_dfg, dev, size_v, size_r, float(roughness_min), nodes_u, nodes_phi, out.data_ptr())
+    return out
+
+
 def texture_levels(H0: int, W0: int, levels=None):
     """(L, E, sizes): the number of levels of an H0 x W0 texture's pyramid (``levels=None``: the full one, 1 + log2(max(H0, W0))
     for powers of two and 1 otherwise), the element count E = sum H_l W_l and the [(H_l, W_l)] list.  Raises on a pyramid

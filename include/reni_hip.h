@@ -965,7 +965,9 @@ int reni_allreduce_grads(void* comm, float* flat, size_t n, float scale, void* s
 int reni_launch_info(const reni_plan* plan, int64_t B, int64_t P, int32_t* info4);
 
 /* Which kernels a backward call of this shape will take (diagnostics; no reference counterpart -- the reference has one path).
- * info8 = { persistent kernels (k_reni_train_bf16) 0/1, dW_1 kernel 0 none / 1 k_reni_dw1_ring / 2 k_reni_dw1,
+ * info8 = { persistent kernels (k_reni_train_bf16) 0/1, dW_1 kernel 0 none / 1 k_reni_dw1_ring / 2 k_reni_dw1 /
+ *           3 k_reni_l0_ring behind the L0X training instance (then, and only then, the training kernel's weight-gradient partials of
+ *           layers >= 2 are in the quad-row layout and are summed by the quad-row reducer: DESIGN.md 4.2e, 4.3),
  *           side stream 0/1 (1: a side stream is ALLOWED for this plan -- a call then forks onto it only if it is not an L0X call and,
  *           for a concat decoder, has at least eight tiles per workgroup), images per chunk of the H = 256 training path (= B: one pass), operand stream 0/1,
  *           fragment stream 0 / 1 bf16 / 2 fp32, environment overrides in force (bit 0 RENI_NO_PERSIST, 1 RENI_NO_SIDE_STREAM,

@@ -215,6 +215,9 @@ Layout make_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uin
     if (p->d.dtype == RENI_F32 && H == 256 && L >= 1 && !film && (flags & RENI_NEED_DW)) l.frag = 2;
     l.o_stash = o; o += al256(l.stash_per_wg * (l.frag ? (size_t)l.n_tiles : (size_t)l.nwg));
     l.dwp_per_wg = (flags & RENI_NEED_DW) ? (size_t)(p->n_params - p->n_first) : 0;
+    // (the persistent training instances: every workgroup's slot starts on a 256-byte line -- the L0X instance flushes, and the quad-row
+    //  reducer loads, 16 bytes at a time; the stride is the only thing that changes for the others)
+    if (l.pdw) l.dwp_per_wg = (l.dwp_per_wg + 63) & ~(size_t)63;
     // image runs of the persistent training kernel: a workgroup's contiguous tile range meets at most this many images
     l.pkmax = ((l.n_tiles + l.nwg - 1) / l.nwg + l.tpi - 1) / l.tpi + 1;
     // (FiLM on the persistent path: one partial slot per image RUN -- the accumulators leave the registers with the image)
@@ -414,8 +417,14 @@ int launch_dw1(const reni::MainArgs& a, int nwg, bool ring, hipStream_t s, bool 
 
 // k_reduce_partials: elements [lo, hi) of `nslot` per-workgroup partials (`per_wg` floats apart; `valid`: a tag per slot, or NULL = every
 // slot counts) summed in a fixed order into out[lo .. hi)
+// (quad_H > 0: the hidden layers' H x H slices are in the quad-row layout -- BwdPath::part_quad -- and H = quad_H: k_reduce_partials_quad)
 int reduce_partials(const float* part, size_t per_wg, int nslot, float* out, int lo, int hi, const int* valid, const reni::LayerScale& lsc,
-                    hipStream_t s) {
+                    hipStream_t s, int quad_H = 0) {
+  if (quad_H > 0) {
+    if (valid != nullptr || (per_wg & 3) || (lo & 3) || ((uintptr_t)part & 15)) return fail(RENI_EINVAL, "internal: quad-row partials need untagged, 16-byte aligned slots");
+    RENI_LAUNCH(reni::k_reduce_partials_quad, dim3((unsigned)((hi - lo + reni::QUAD_BLK_WORDS - 1) / reni::QUAD_BLK_WORDS)), dim3(256), 0, s, part, per_wg, nslot, out, lo, hi, quad_H, lsc);
+    return RENI_OK;
+  }
   RENI_LAUNCH(reni::k_reduce_partials, dim3((unsigned)((hi - lo + 63) / 64)), dim3(256), 0, s, part, per_wg, nslot, out, lo, hi, valid, lsc);
   return RENI_OK;
 }
@@ -727,6 +736,8 @@ struct BwdPath {
   bool cos_const;   // no statistics pass, no k_stats_image: the coefficients are the zeros the cached lists' build left
   bool dw1_ring;    // which dW_1 kernel runs, and how many partial slots its reduction sums (dw1_slots)
   bool l0x;         // the L0X training instance + k_reni_l0_ring: no fork, the per-image epilogue behind the ring on the one stream
+  bool part_quad;   // the training kernel's weight-gradient partials (dwp: layers >= 2) are in the quad-row layout: their reduction takes the
+                    // matching reducer (reduce_partials' quad_H, TailFusedArgs::rp_quad) -- decided here, nowhere else.  (dw1p stays flat.)
   bool fork;        // the per-image epilogue goes to the side stream, if one can be had (bwd_fork_dw1)
   bool early_rest;  // layers >= 2 and the head are reduced apart from layer 1: alone in front of dW_1, or in k_tail_a's launch (rp_in_tail)
   bool dp_early;    // the data-parallel step wants that early slice all-reduced on the communication stream, beside dW_1
@@ -782,6 +793,7 @@ BwdPath bwd_path(const reni_plan* p, const Layout& l, const BwdCall& c, const re
   t.cos_const = t.sparse && c.lists && (c.lists->flags & RENI_WEIGHT_COS_CONSTANT);
   t.dw1_ring = dw1_ring_plan_ok(p, c.P) && dw1_ring_call_ok(a);
   t.l0x = l0x_plan_ok(p, l, c.P, c.flags) && l0x_call_ok(a);  // (decided once: the training kernel, the ring and the tail's order follow it)
+  t.part_quad = t.l0x;  // (the L0X instance is the only writer of that layout; RENI_NO_L0X, RENI_NO_PERSIST and FiLM never get here)
   // persistent path: fork.  `s` continues with k_reni_dw1 -> weight-gradient reduction -> first-layer weight tail;
   // `se` (side stream) takes everything that only needs the per-tile partials; joined before returning.
   // (small problems -- fewer than eight tiles per workgroup: the multi-resolution curriculum's first stages -- stay on ONE stream:
@@ -939,7 +951,7 @@ int bwd_fork_dw1(Bwd& x, std::unique_lock<std::mutex>& side_lock, SideJoin& side
   if (path.early_rest && !path.rp_in_tail) {
     // (alone in front of k_reni_dw1, not beside it on a stream of its own: measured again in round 4 with the fused epilogue --
     // beside, everything crawls and the step is 30 us longer: profiles/r04_tail.md)
-    int rc = reduce_partials(x.a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, path.n_l1, path.n_rest, nullptr, x.lsc, s);
+    int rc = reduce_partials(x.a.dwp, l.dwp_per_wg, l.nwg, c.dparams + p->n_first, path.n_l1, path.n_rest, nullptr, x.lsc, s, path.part_quad ? p->d.hidden_features : 0);
     if (rc) return rc;
     // the gradient of layers >= 2 and of the head is final HERE, a whole k_reni_dw1 before the call ends: a data-parallel caller
     // starts their all-reduce on another stream behind this event (TrainEngine(overlap_comm=True))
@@ -1081,7 +1093,10 @@ int bwd_epilogue_concat(Bwd& x) {
     unsigned gx = (unsigned)c.B;
     if (path.rp_in_tail) {
       f.rp_part = a.dwp; f.rp_per_wg = l.dwp_per_wg; f.rp_nwg = l.nwg; f.rp_out = c.dparams + p->n_first; f.rp_lo = path.n_l1; f.rp_n = path.n_rest; f.rp_ls = x.lsc;
-      gx += ((unsigned)((path.n_rest - path.n_l1 + 63) / 64) + ny - 1) / ny;
+      f.rp_quad = path.part_quad ? 1 : 0;
+      if (f.rp_quad && ((l.dwp_per_wg | (size_t)path.n_l1) & 3)) return fail(RENI_EINVAL, "internal: quad-row partials need 16-byte aligned slots");
+      const int per_blk = f.rp_quad ? reni::QUAD_BLK_WORDS : 64;  // (buffer words per block: reduce_partials_quad_body / reduce_partials_body)
+      gx += ((unsigned)((path.n_rest - path.n_l1 + per_blk - 1) / per_blk) + ny - 1) / ny;
     }
     RENI_LAUNCH(reni::k_tail_a, dim3(gx, ny), dim3(256), (size_t)reni::tail_a_lds_bytes(H), se, f);
   } else if (c.flags & RENI_NEED_DZ) {

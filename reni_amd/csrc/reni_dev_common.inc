@@ -613,6 +613,30 @@ DEV void dw_flush(const f32x16 (&acc_in)[MYB], float dbacc, float* dst_w, float*
   }
 }
 
+// The QUAD-ROW layout of a hidden layer's H x H partial (the L0X training instance only; the bias behind it, the head, k_reni_l0_ring's
+// layer-1 partials and every other writer keep the flat layout): element (row, col) lives at word ((row / 4) * H + col) * 4 + row % 4 of the layer's
+// slice.  Registers 4 i .. 4 i + 3 of a 32 x 32 accumulator block are four consecutive rows of one column (rowmap), so a lane's sixteen
+// values leave in four 16-byte stores, and a wave instruction covers two 512-byte runs instead of two 128-byte row pieces.
+// The reader is reduce_partials_quad_body (reni_dev_small.inc), which undoes the permutation where it writes the sum.
+DEV constexpr unsigned quad_word(int row, int col, int H) { return (unsigned)((((row >> 2) * H + col) << 2) + (row & 3)); }
+// dw_flush<.., DW_HIDDEN, MYB>'s plain store (`first`, no atomics, no row scale) of the pinned form -- wave w owns row block w and the
+// MYB column blocks -- into a quad-row slice: the same values, the same bias sum, 16-byte stores
+template <int H, int NBR, int MYB>
+DEV void dw_flush_quad(const f32x16 (&acc)[MYB], float dbacc, float* dst_w, float* dst_b, int wave, int lane) {
+  static_assert(NBR == 4 && MYB == H / 32, "pinned form: wave w owns row block w and every column block");
+  static_assert(rowmap(4, 0) == 8 && rowmap(3, 1) == 7, "registers 4 i .. 4 i + 3: rows 8 i + 4 hi .. + 3 of the block");
+  const int hi = lane >> 5, j = lane & 31;
+  float* const base = dst_w + ((size_t)((8 * wave + hi) * H + j) << 2);  // row quad 8 wave + 2 i + hi, column 32 m + j
+#pragma unroll
+  for (int m = 0; m < MYB; ++m) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *(f32x4*)(base + ((2 * i * H + 32 * m) << 2)) = f32x4{acc[m][4 * i], acc[m][4 * i + 1], acc[m][4 * i + 2], acc[m][4 * i + 3]};
+  }
+  dbacc += __shfl_xor(dbacc, 32, 64);
+  if (hi == 0) dst_b[32 * wave + j] = dbacc;
+}
+
 // FiLM extras of a hidden-layer dW phase.  The accumulators hold M = g_theta h^T (g_theta = cos(angle) g_h):
 //   d(phase)[f] = sum_s g_theta[f][s]                 (the bias sum)
 //   d(freq)[f]  = sum_s g_theta[f][s] a[f][s],  a = W h + b   =  sum_k W[f][k] M[f][k] + b[f] d(phase)[f]

@@ -514,6 +514,65 @@ DEV void reduce_partials_body(const float* part, size_t per_wg, int nwg, float* 
   __syncthreads();
   if (grp == 0 && e < n) dparams[e] = ((red2[0][lane] + red2[1][lane]) + (red2[2][lane] + red2[3][lane])) * layer_scale(ls, e);
 }
+// The same sum over partials whose hidden layers' H x H slices are in the QUAD-ROW layout (quad_word, reni_dev_common.inc: the L0X training
+// instance's): 16-byte loads.  A block is still 64 consecutive buffer words x the four slot groups (wave g: slots g, g + 4, ...), but sixteen
+// lanes cover the 64 words, four words each, and the four quarters of a wave share out reduce_partials_body's eight accumulators: quarter uq
+// owns s[2 uq] and s[2 uq + 1], so one wave instruction fetches 256 contiguous bytes of four slots.  Per word the arithmetic is
+// reduce_partials_body's, operation for operation: s[u] takes slots grp + 4 u + 32 k in ascending k, the remainder goes into s[0], then
+// ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)) -- the inner pairs per quarter, the rest through LDS -- and (r0 + r1) + (r2 + r3) over the
+// groups.  The permutation is undone where the sum leaves: buffer word w of the slot is handed to emit(e, sum) with e its element index in the
+// flat layout (what layer_scale expects).
+// Needs per_wg % 4 == 0 and lo % 4 == 0 (16-byte aligned loads, and the last thread's load stays inside its slot): make_layout pads the stride.
+// red4: [4][64] of 16 bytes.  part: the slots' base; [lo, n): the words summed; hidden layers of n_hid = H H + H words from word 0.
+DEV int quad_word_to_flat(int w, int H, int n_hid, int L) {
+  const int k = w / n_hid, t = w - k * n_hid;
+  if (k >= L || t >= H * H) return w;  // biases, the head: flat
+  const int q = t >> 2, rq = q / H, col = q - rq * H;
+  return k * n_hid + (4 * rq + (t & 3)) * H + col;
+}
+constexpr int QUAD_BLK_WORDS = 64;
+template <class Emit>
+DEV void reduce_partials_quad_body(const float* part, size_t per_wg, int nwg, int lo, int n, int blk, f32x4 (*red4)[64], int H, int n_hid, int L,
+                                   Emit&& emit) {
+  const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
+  const int l16 = lane & 15, uq = lane >> 4;  // sixteen lanes x 16 bytes = the block's 64 words; quarter uq of the wave owns s[2 uq], s[2 uq + 1]
+  const int w = lo + blk * QUAD_BLK_WORDS + 4 * l16;
+  f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
+  if (w < n) {
+    const float* const p = part + w + (size_t)(8 * uq) * per_wg;  // slot grp + 4 (2 uq) + 32 k, and the one four behind it
+    int q = grp;
+    // (four trips of the 32-slot loop at a time while they last: their eight loads are issued before the first add -- left to itself the
+    //  compiler waits for every 16-byte load in turn -- and the adds follow in trip order.  Sixteen loads at a time cost k_tail_a a wave of
+    //  occupancy, 116 VGPRs, and gave back most of the gain: profiles/partials_path.md)
+    for (; q + 124 < nwg; q += 128) {
+      f32x4 v[8];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        v[2 * k] = *(const f32x4*)(p + (size_t)(q + 32 * k) * per_wg);
+        v[2 * k + 1] = *(const f32x4*)(p + (size_t)(q + 32 * k + 4) * per_wg);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { s0 += v[2 * k]; s1 += v[2 * k + 1]; }
+    }
+    for (; q + 28 < nwg; q += 32) {
+      const f32x4 a = *(const f32x4*)(p + (size_t)q * per_wg), b = *(const f32x4*)(p + (size_t)(q + 4) * per_wg);
+      s0 += a; s1 += b;
+    }
+    if (uq == 0) {  // the remainder goes into s[0]
+      for (; q < nwg; q += 4) s0 += *(const f32x4*)(p + (size_t)q * per_wg);
+    }
+  }
+  red4[grp][lane] = s0 + s1;  // s[2 uq] + s[2 uq + 1]: the leaves of reduce_partials_body's first tree
+  __syncthreads();
+  if (threadIdx.x < QUAD_BLK_WORDS) {  // one word per thread: word i of the block is component i % 4 of lane i / 4's quad
+    const int m = (int)threadIdx.x >> 2, c = (int)threadIdx.x & 3, ww = lo + blk * QUAD_BLK_WORDS + (int)threadIdx.x;
+    float g[4];
+#pragma unroll
+    for (int gg = 0; gg < 4; ++gg) g[gg] = (red4[gg][m][c] + red4[gg][16 + m][c]) + (red4[gg][32 + m][c] + red4[gg][48 + m][c]);
+    if (ww < n) emit(quad_word_to_flat(ww, H, n_hid, L), (g[0] + g[1]) + (g[2] + g[3]));
+  }
+}
 // (the tagged path's block `blk`: slot w counts only if valid[w] >= 0; also run by k_film_reduce2's second group of blocks)
 DEV void reduce_partials_valid_body(const float* part, size_t per_wg, int nwg, float* dparams, int lo, int n, const int* valid, int blk) {
   // a block = 64 consecutive elements x 4 slot groups (wave g sums used slots g, g + 4, ...; eight loads in flight), the
@@ -568,6 +627,13 @@ __global__ void __launch_bounds__(256) k_reduce_partials(const float* part, size
   (void)i;
   __shared__ float red2[4][64];
   reduce_partials_body(part, per_wg, nwg, dparams, lo, n, (int)blockIdx.x, red2, ls);
+}
+// quad-row partials (every slot counts): grid = ceil((n - lo) / QUAD_BLK_WORDS) blocks of reduce_partials_quad_body
+__global__ void __launch_bounds__(256) k_reduce_partials_quad(const float* part, size_t per_wg, int nwg, float* dparams, int lo, int n, int H,
+                                                               const LayerScale ls) {
+  __shared__ f32x4 red4[4][64];
+  reduce_partials_quad_body(part, per_wg, nwg, lo, n, (int)blockIdx.x, red4, H, ls.n_hid, ls.L,
+                            [&](int e, float v) { dparams[e] = v * layer_scale(ls, e); });
 }
 
 // FiLM, persistent path: k_reduce_film_runs' blocks and the tagged layer-1 partial reduction's, which both wait for k_reni_dw1 and for
@@ -1083,6 +1149,7 @@ struct TailFusedArgs {
   // k_tail_a on ONE stream (small problems: no side stream): the blocks with blockIdx.x >= t.B are k_reduce_partials' plain blocks
   // for the weight-gradient partials of layers >= 2 -- 85 MB of bandwidth-bound reads beside the per-image latency chains, one launch less
   const float* rp_part; size_t rp_per_wg; int rp_nwg, rp_lo, rp_n; float* rp_out; LayerScale rp_ls;
+  int rp_quad;  // the partials are in the quad-row layout (the L0X training instance's): reduce_partials_quad_body's blocks
 };
 constexpr int TF_LMAX = 512;  // runs of one image kept in the LDS list (an image meets at most one run per workgroup: <= #CUs)
 constexpr int tail_a_lds_bytes(int H) { return (H * 8 + 16) * 4 + 4 * 64 * 4 * 4 + TF_LMAX * 4; }
@@ -1090,6 +1157,12 @@ __global__ void __launch_bounds__(256) k_tail_a(const TailFusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if ((int)blockIdx.x >= a.t.B) {  // (uniform per block) the partial reduction's blocks, see TailFusedArgs
     const int blk = ((int)blockIdx.x - a.t.B) * (int)gridDim.y + (int)blockIdx.y;
+    if (a.rp_quad) {
+      static_assert(tail_a_lds_bytes(32) >= 4 * 64 * 16, "red4 fits the dynamic LDS at every width");
+      reduce_partials_quad_body(a.rp_part, a.rp_per_wg, a.rp_nwg, a.rp_lo, a.rp_n, blk, (f32x4 (*)[64])smem, a.t.H, a.rp_ls.n_hid, a.rp_ls.L,
+                                [&](int e, float v) { a.rp_out[e] = v * layer_scale(a.rp_ls, e); });
+      return;
+    }
     reduce_partials_body(a.rp_part, a.rp_per_wg, a.rp_nwg, a.rp_out, a.rp_lo, a.rp_n, blk, (float (*)[64])smem, a.rp_ls);
     return;
   }

@@ -392,8 +392,10 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
 #endif
   const bool trace_on = a.trace != nullptr && blockIdx.x == 0 && __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == RENI_TRACE_WAVE;
 #define TRACE(tag) do { __builtin_amdgcn_sched_barrier(0); if (trace_on && trace_n < 500) { trace_lds[trace_n] = ((unsigned long long)__builtin_amdgcn_s_memtime() & 0xffffffffffffull) | ((unsigned long long)(tag) << 48); ++trace_n; } __builtin_amdgcn_sched_barrier(0); } while (0)
+#define TRACE_FLUSH(slot, tag) do { __builtin_amdgcn_sched_barrier(0); if (trace_on) trace_lds[slot] = ((unsigned long long)__builtin_amdgcn_s_memtime() & 0xffffffffffffull) | ((unsigned long long)(tag) << 48); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define TRACE(tag) do {} while (0)
+#define TRACE_FLUSH(slot, tag) do {} while (0)
 #endif
   const int tid = threadIdx.x;
   // The frozen instance runs EIGHT waves (two per SIMD: it has no accumulator tiles to hold and is latency-bound at one)
@@ -1532,11 +1534,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     if constexpr (INCR) { cur_b = nxt_b; cur_tin = nxt_tin; }
     TRACE(9);
   }
-#ifdef RENI_TRACE
-  if (trace_on) {
-    for (int i = lane; i < trace_n; i += 64) a.trace[i] = (long long)trace_lds[i];
-  }
-#endif
   int tid_e = L0X ? (int)((unsigned)tid16 >> 4) : tid;  // opaque copy for the epilogue: addresses derived from tid before the tile loop are not kept alive across it
                                                        // (L0X: from the loop-carried tid16 -- tid itself, kept for this line alone, was spilled and reloaded every tile)
   asm volatile("" : "+v"(tid_e));
@@ -1568,12 +1565,15 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     for (int i = tid_e; i < 3 * H; i += 256) dwp[a.p_off_w[L + 1] + i] = hdw[i];
     if (tid_e < 3) dwp[a.p_off_b[L + 1] + tid_e] = (hdb[tid_e] + hdb[4 + tid_e]) + (hdb[8 + tid_e] + hdb[12 + tid_e]);
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    TRACE_FLUSH(510, 10);
     auto flush_layer = [&](auto lc) {
       constexpr int l = decltype(lc)::value;
       if (l <= L) {
         f32x16 t[MYB_H] = {agpr_read_tile<4 * (l - 2) + 0>(), agpr_read_tile<4 * (l - 2) + 1>(),
                            agpr_read_tile<4 * (l - 2) + 2>(), agpr_read_tile<4 * (l - 2) + 3>()};
-        dw_flush<Pol, H, NRB, NRB, DW_HIDDEN, MYB_H>(t, pdb[l - 1], dwp + a.p_off_w[l], dwp + a.p_off_b[l], H, true, wave, L0X ? (tid_e & 63) : lane);
+        // (L0X: the layer's H x H slice in the quad-row layout, 16-byte stores -- dw_flush_quad; the host sums it with the matching reducer)
+        if constexpr (L0X) dw_flush_quad<H, NRB, MYB_H>(t, pdb[l - 1], dwp + a.p_off_w[l], dwp + a.p_off_b[l], wave, tid_e & 63);
+        else dw_flush<Pol, H, NRB, NRB, DW_HIDDEN, MYB_H>(t, pdb[l - 1], dwp + a.p_off_w[l], dwp + a.p_off_b[l], H, true, wave, L0X ? (tid_e & 63) : lane);
       }
     };
     flush_layer(std::integral_constant<int, 2>{});
@@ -1581,6 +1581,15 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     flush_layer(std::integral_constant<int, 4>{});
     flush_layer(std::integral_constant<int, 5>{});
   }
+#ifdef RENI_TRACE
+  if constexpr (DW && !FILM) {  // (the flush's own stamps, slots 510 / 511 behind the tile loop's: before it, and when its stores have left)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    TRACE_FLUSH(511, 11);
+  }
+  if (trace_on) {
+    for (int i = (int)(threadIdx.x & 63); i < 512; i += 64) a.trace[i] = (i < trace_n || (DW && !FILM && i >= 510)) ? (long long)trace_lds[i] : 0ll;
+  }
+#endif
 }
 #ifdef RENI_TU_CORE
 template __global__ void k_reni_train_bf16<128, true>(const MainArgs);

@@ -5,6 +5,7 @@ PyTorch is plumbing here (device memory, streams); all arithmetic happens in lib
 from __future__ import annotations
 
 import ctypes
+import types
 from typing import Optional, Tuple
 
 import torch
@@ -547,50 +548,84 @@ def check_visibility(vis, NP: int, J: int, NB=None):
                          f"directions, got {tuple(vis.shape)}")
 
 
-def _shade_call(forward: bool, normals, positions, camera_center, light_dirs, src, shininess, kd, ks, vis=None):
-    """reni_envmap_shade / reni_envmap_shade_backward and their _masked forms (include/reni_hip.h).  normals, positions [NP,3];
-    light_dirs [J,3] (shared grid) or [B,J,3]; src = light colours [B,J,3] (forward) or d colours [B,NP,3] (backward);
-    vis = None or the int32 mask [1,NP,JW] (shared grid; also accepted with per-image directions) / [B,NP,JW]."""
-    if vis is not None:  # argument errors of the new argument come before the library, as everywhere else
+def _shade_inputs(normals, positions, camera_center, light_dirs, srcs, on_texels, vis, mat=None, mat_name=None, early=True):
+    """The prologue the shader's calls share (include/reni_hip.h): the argument checks that come before the library is touched,
+    the casts to contiguous fp32, B, NP, J and the direction stride, the sources' shapes, the camera and the mask.  normals,
+    positions [NP,3]; light_dirs [J,3] (shared grid) or [B,J,3]; srcs[i] is [B,J,3] where on_texels[i], else [B,NP,3]; vis = None
+    or the int32 mask [1,NP,JW] (shared grid; also accepted with per-image directions) / [B,NP,JW]; mat (named mat_name in the
+    messages) = the per-pixel scalar: a float, a one-element tensor or [NP].  early False: the checks of light_dirs, the normals'
+    rank and the mask are left to what follows.  -> a record: lib, dev, B, NP, J, srcs (the cast tensors), head (the calls'
+    first ten arguments), vis (mask pointer, batch stride), mats (scalar pointer, stride, then vis); keep holds the cast tensors."""
+    if early:
         _dirs_dims(light_dirs)
         if not isinstance(normals, torch.Tensor) or normals.dim() != 2:
             raise ValueError("normals and positions must be [NP, 3]")
-        J_ = light_dirs.shape[-2]
-        check_visibility(vis, normals.shape[0], J_)
-        if vis.shape[0] != 1 and (light_dirs.dim() == 2 or vis.shape[0] != light_dirs.shape[0]):
-            raise ValueError(f"a mask of {vis.shape[0]} images needs per-image directions [{vis.shape[0]}, J, 3]")
-    _require_cuda(normals, positions, light_dirs, src, vis)
+        NP = normals.shape[0]
+        if mat_name is not None:
+            if isinstance(mat, torch.Tensor):
+                if mat.numel() != 1 and tuple(mat.shape) != (NP,):
+                    raise ValueError(f"{mat_name} must be a float, one value or [{NP}] (one per pixel), got {tuple(mat.shape)}")
+            elif not isinstance(mat, (int, float)):
+                raise ValueError(f"{mat_name} must be a float, one value or [{NP}] (one per pixel), got {type(mat).__name__}")
+        if vis is not None:
+            check_visibility(vis, NP, light_dirs.shape[-2])
+            if vis.shape[0] != 1 and (light_dirs.dim() == 2 or vis.shape[0] != light_dirs.shape[0]):
+                raise ValueError(f"a mask of {vis.shape[0]} images needs per-image directions [{vis.shape[0]}, J, 3]")
+    _require_cuda(normals, positions, light_dirs, *srcs, vis, mat if isinstance(mat, torch.Tensor) else None)
     lib = _lib.load()
     f32 = torch.float32
     normals = normals.to(f32).contiguous(); positions = positions.to(f32).contiguous()
-    light_dirs = light_dirs.to(f32).contiguous(); src = src.to(f32).contiguous()
+    light_dirs = light_dirs.to(f32).contiguous()
+    srcs = [x.to(f32).contiguous() for x in srcs]
+    dev = srcs[0].device
     NP = normals.shape[0]
     if normals.shape != (NP, 3) or positions.shape != (NP, 3):
         raise ValueError("normals and positions must be [NP, 3]")
-    B = src.shape[0]
+    B = srcs[0].shape[0]
     if light_dirs.dim() == 2:
         J, stride = light_dirs.shape[0], 0
     else:
         if light_dirs.shape[0] != B:
             raise ValueError("light_dirs batch size must match the colours'")
         J, stride = light_dirs.shape[1], light_dirs.shape[1] * 3
-    want = (B, J, 3) if forward else (B, NP, 3)
-    if tuple(src.shape) != want:
-        raise ValueError(f"expected a {want} tensor, got {tuple(src.shape)}")
+    for x, texels in zip(srcs, on_texels):
+        want = (B, J, 3) if texels else (B, NP, 3)
+        if tuple(x.shape) != want:
+            raise ValueError(f"expected a {want} tensor, got {tuple(x.shape)}")
+    if isinstance(mat, torch.Tensor):
+        mat = mat.detach().to(device=dev, dtype=f32).reshape(-1).contiguous()
+    elif mat_name is not None:
+        mat = torch.full((1,), float(mat), dtype=f32, device=dev)
     cam = [float(x) for x in torch.as_tensor(camera_center).reshape(-1)[:3].tolist()]
-    out = torch.empty((B, NP, 3) if forward else (B, J, 3), dtype=f32, device=src.device)
-    nbytes = int(lib.reni_envmap_shade_workspace_bytes(B, NP, J))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
-    head = (B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride,
-            src.data_ptr(), float(shininess), float(kd), float(ks))
+    vargs = (None, 0)
+    if vis is not None:
+        vis = vis.contiguous()
+        vargs = (vis.data_ptr(), 0 if vis.shape[0] == 1 else NP * vis.shape[2])
+    head = (B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride)
+    mats = None if mat is None else (mat.data_ptr(), 0 if mat.numel() == 1 else 1, *vargs)
+    return types.SimpleNamespace(lib=lib, dev=dev, B=B, NP=NP, J=J, srcs=srcs, head=head, vis=vargs, mats=mats,
+                                 keep=(normals, positions, light_dirs, mat, vis))
+
+
+def _workspace(p, nbytes):
+    """-> (uint8 workspace tensor on the call's device, its size)"""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=p.dev), int(nbytes)
+
+
+def _shade_call(forward: bool, normals, positions, camera_center, light_dirs, src, shininess, kd, ks, vis=None):
+    """reni_envmap_shade / reni_envmap_shade_backward and their _masked forms (include/reni_hip.h).  src = light colours [B,J,3]
+    (forward) or d colours [B,NP,3] (backward).  Without a mask the checks of the mask's arguments are the library's."""
+    p = _shade_inputs(normals, positions, camera_center, light_dirs, (src,), (forward,), vis, early=vis is not None)
+    lib, f32 = p.lib, torch.float32
+    out = torch.empty((p.B, p.NP, 3) if forward else (p.B, p.J, 3), dtype=f32, device=p.dev)
+    ws, nbytes = _workspace(p, lib.reni_envmap_shade_workspace_bytes(p.B, p.NP, p.J))
+    head = (*p.head, p.srcs[0].data_ptr(), float(shininess), float(kd), float(ks))
     if vis is None:
-        _call(lib.reni_envmap_shade if forward else lib.reni_envmap_shade_backward, src.device, *head, out.data_ptr(),
+        _call(lib.reni_envmap_shade if forward else lib.reni_envmap_shade_backward, p.dev, *head, out.data_ptr(),
               ws.data_ptr(), nbytes)
     else:
-        vis = vis.contiguous()
-        vstride = 0 if vis.shape[0] == 1 else NP * vis.shape[2]
-        _call(lib.reni_envmap_shade_masked if forward else lib.reni_envmap_shade_masked_backward, src.device, *head,
-              vis.data_ptr(), vstride, out.data_ptr(), ws.data_ptr(), nbytes)
+        _call(lib.reni_envmap_shade_masked if forward else lib.reni_envmap_shade_masked_backward, p.dev, *head, *p.vis,
+              out.data_ptr(), ws.data_ptr(), nbytes)
     return out
 
 
@@ -606,72 +641,27 @@ def envmap_shade_backward(normals, positions, camera_center, light_dirs, dcolors
 
 
 def _terms_call(forward: bool, normals, positions, camera_center, light_dirs, srcs, shininess, vis, need_ds=False):
-    """reni_envmap_shade_terms / reni_envmap_shade_terms_backward (include/reni_hip.h) behind the checks of ``_shade_call``.
+    """reni_envmap_shade_terms / reni_envmap_shade_terms_backward (include/reni_hip.h) behind ``_shade_inputs``.
     srcs: (light colours [B,J,3],) forward, (gD, gS) [B,NP,3] backward; shininess: a float, a one-element tensor or [NP].
     forward None: reni_envmap_shade_terms_dnormals, srcs = (light colours, gD, gS)."""
-    _dirs_dims(light_dirs)
-    if not isinstance(normals, torch.Tensor) or normals.dim() != 2:
-        raise ValueError("normals and positions must be [NP, 3]")
-    NP = normals.shape[0]
-    if isinstance(shininess, torch.Tensor):
-        if shininess.numel() != 1 and tuple(shininess.shape) != (NP,):
-            raise ValueError(f"shininess must be a float, one value or [{NP}] (one per pixel), got {tuple(shininess.shape)}")
-    elif not isinstance(shininess, (int, float)):
-        raise ValueError(f"shininess must be a float, one value or [{NP}] (one per pixel), got {type(shininess).__name__}")
-    if vis is not None:
-        check_visibility(vis, NP, light_dirs.shape[-2])
-        if vis.shape[0] != 1 and (light_dirs.dim() == 2 or vis.shape[0] != light_dirs.shape[0]):
-            raise ValueError(f"a mask of {vis.shape[0]} images needs per-image directions [{vis.shape[0]}, J, 3]")
-    _require_cuda(normals, positions, light_dirs, *srcs, vis, shininess if isinstance(shininess, torch.Tensor) else None)
-    lib = _lib.load()
-    f32 = torch.float32
-    normals = normals.to(f32).contiguous(); positions = positions.to(f32).contiguous()
-    light_dirs = light_dirs.to(f32).contiguous()
-    srcs = [x.to(f32).contiguous() for x in srcs]
-    dev = srcs[0].device
-    if normals.shape != (NP, 3) or positions.shape != (NP, 3):
-        raise ValueError("normals and positions must be [NP, 3]")
-    B = srcs[0].shape[0]
-    if light_dirs.dim() == 2:
-        J, stride = light_dirs.shape[0], 0
-    else:
-        if light_dirs.shape[0] != B:
-            raise ValueError("light_dirs batch size must match the colours'")
-        J, stride = light_dirs.shape[1], light_dirs.shape[1] * 3
     dnormals = forward is None
-    for i, x in enumerate(srcs):
-        want = (B, J, 3) if (forward or (dnormals and i == 0)) else (B, NP, 3)
-        if tuple(x.shape) != want:
-            raise ValueError(f"expected a {want} tensor, got {tuple(x.shape)}")
-    if isinstance(shininess, torch.Tensor):
-        shin = shininess.detach().to(device=dev, dtype=f32).reshape(-1).contiguous()
-    else:
-        shin = torch.full((1,), float(shininess), dtype=f32, device=dev)
-    cam = [float(x) for x in torch.as_tensor(camera_center).reshape(-1)[:3].tolist()]
+    on_texels = (True,) if forward else (True, False, False) if dnormals else (False, False)
+    p = _shade_inputs(normals, positions, camera_center, light_dirs, srcs, on_texels, vis, shininess, "shininess")
+    lib, f32, ptr = p.lib, torch.float32, [x.data_ptr() for x in p.srcs]
     if dnormals:
-        nbytes = int(lib.reni_envmap_shade_terms_dnormals_workspace_bytes(B, NP, J))
-    else:
-        nbytes = int(lib.reni_envmap_shade_terms_workspace_bytes(B, NP, J, _lib.SHADE_TERMS_DS if need_ds else 0))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    vptr, vstride = None, 0
-    if vis is not None:
-        vis = vis.contiguous()
-        vptr, vstride = vis.data_ptr(), (0 if vis.shape[0] == 1 else NP * vis.shape[2])
-    head = (B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride)
-    mats = (shin.data_ptr(), 0 if shin.numel() == 1 else 1, vptr, vstride)
-    if dnormals:
-        out = torch.empty((NP, 3), dtype=f32, device=dev)
-        _call(lib.reni_envmap_shade_terms_dnormals, dev, *head, srcs[0].data_ptr(), *mats, srcs[1].data_ptr(), srcs[2].data_ptr(),
-              out.data_ptr(), ws.data_ptr(), nbytes)
+        ws, nbytes = _workspace(p, lib.reni_envmap_shade_terms_dnormals_workspace_bytes(p.B, p.NP, p.J))
+        out = torch.empty((p.NP, 3), dtype=f32, device=p.dev)
+        _call(lib.reni_envmap_shade_terms_dnormals, p.dev, *p.head, ptr[0], *p.mats, ptr[1], ptr[2], out.data_ptr(),
+              ws.data_ptr(), nbytes)
         return out
+    ws, nbytes = _workspace(p, lib.reni_envmap_shade_terms_workspace_bytes(p.B, p.NP, p.J, _lib.SHADE_TERMS_DS if need_ds else 0))
     if forward:
-        outs = [torch.empty((B, NP, 3), dtype=f32, device=dev) for _ in range(3 if need_ds else 2)]
-        _call(lib.reni_envmap_shade_terms, dev, *head, srcs[0].data_ptr(), *mats, outs[0].data_ptr(), outs[1].data_ptr(),
+        outs = [torch.empty((p.B, p.NP, 3), dtype=f32, device=p.dev) for _ in range(3 if need_ds else 2)]
+        _call(lib.reni_envmap_shade_terms, p.dev, *p.head, ptr[0], *p.mats, outs[0].data_ptr(), outs[1].data_ptr(),
               outs[2].data_ptr() if need_ds else None, ws.data_ptr(), nbytes)
         return outs[0], outs[1], (outs[2] if need_ds else None)
-    out = torch.empty((B, J, 3), dtype=f32, device=dev)
-    _call(lib.reni_envmap_shade_terms_backward, dev, *head, *mats, srcs[0].data_ptr(), srcs[1].data_ptr(), out.data_ptr(),
-          ws.data_ptr(), nbytes)
+    out = torch.empty((p.B, p.J, 3), dtype=f32, device=p.dev)
+    _call(lib.reni_envmap_shade_terms_backward, p.dev, *p.head, *p.mats, ptr[0], ptr[1], out.data_ptr(), ws.data_ptr(), nbytes)
     return out
 
 
@@ -695,72 +685,27 @@ def envmap_shade_terms_dnormals(normals, positions, camera_center, light_dirs, l
 
 
 def _ggx_call(mode: str, normals, positions, camera_center, light_dirs, srcs, alpha, vis, need_dn=False):
-    """reni_envmap_shade_ggx / _backward / _dpixel (include/reni_hip.h) behind the checks of ``_shade_call``.  mode "forward":
+    """reni_envmap_shade_ggx / _backward / _dpixel (include/reni_hip.h) behind ``_shade_inputs``.  mode "forward":
     srcs = (light colours [B,J,3],); "backward": (gD, gS0, gS1) [B,NP,3]; "dpixel": (light colours, gD, gS0, gS1).  alpha: a
     float, a one-element tensor or [NP]."""
-    _dirs_dims(light_dirs)
-    if not isinstance(normals, torch.Tensor) or normals.dim() != 2:
-        raise ValueError("normals and positions must be [NP, 3]")
-    NP = normals.shape[0]
-    if isinstance(alpha, torch.Tensor):
-        if alpha.numel() != 1 and tuple(alpha.shape) != (NP,):
-            raise ValueError(f"alpha must be a float, one value or [{NP}] (one per pixel), got {tuple(alpha.shape)}")
-    elif not isinstance(alpha, (int, float)):
-        raise ValueError(f"alpha must be a float, one value or [{NP}] (one per pixel), got {type(alpha).__name__}")
-    if vis is not None:
-        check_visibility(vis, NP, light_dirs.shape[-2])
-        if vis.shape[0] != 1 and (light_dirs.dim() == 2 or vis.shape[0] != light_dirs.shape[0]):
-            raise ValueError(f"a mask of {vis.shape[0]} images needs per-image directions [{vis.shape[0]}, J, 3]")
-    _require_cuda(normals, positions, light_dirs, *srcs, vis, alpha if isinstance(alpha, torch.Tensor) else None)
-    lib = _lib.load()
-    f32 = torch.float32
-    normals = normals.to(f32).contiguous(); positions = positions.to(f32).contiguous()
-    light_dirs = light_dirs.to(f32).contiguous()
-    srcs = [x.to(f32).contiguous() for x in srcs]
-    dev = srcs[0].device
-    if normals.shape != (NP, 3) or positions.shape != (NP, 3):
-        raise ValueError("normals and positions must be [NP, 3]")
-    B = srcs[0].shape[0]
-    if light_dirs.dim() == 2:
-        J, stride = light_dirs.shape[0], 0
-    else:
-        if light_dirs.shape[0] != B:
-            raise ValueError("light_dirs batch size must match the colours'")
-        J, stride = light_dirs.shape[1], light_dirs.shape[1] * 3
-    for i, x in enumerate(srcs):
-        want = (B, J, 3) if (mode == "forward" or (mode == "dpixel" and i == 0)) else (B, NP, 3)
-        if tuple(x.shape) != want:
-            raise ValueError(f"expected a {want} tensor, got {tuple(x.shape)}")
-    if isinstance(alpha, torch.Tensor):
-        al = alpha.detach().to(device=dev, dtype=f32).reshape(-1).contiguous()
-    else:
-        al = torch.full((1,), float(alpha), dtype=f32, device=dev)
-    cam = [float(x) for x in torch.as_tensor(camera_center).reshape(-1)[:3].tolist()]
+    on_texels = {"forward": (True,), "backward": (False, False, False), "dpixel": (True, False, False, False)}[mode]
+    p = _shade_inputs(normals, positions, camera_center, light_dirs, srcs, on_texels, vis, alpha, "alpha")
+    lib, f32, ptr = p.lib, torch.float32, [x.data_ptr() for x in p.srcs]
     if mode == "dpixel":
-        nbytes = int(lib.reni_envmap_shade_ggx_dpixel_workspace_bytes(B, NP, J))
-    else:
-        nbytes = int(lib.reni_envmap_shade_ggx_workspace_bytes(B, NP, J))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    vptr, vstride = None, 0
-    if vis is not None:
-        vis = vis.contiguous()
-        vptr, vstride = vis.data_ptr(), (0 if vis.shape[0] == 1 else NP * vis.shape[2])
-    head = (B, NP, J, normals.data_ptr(), positions.data_ptr(), cam[0], cam[1], cam[2], light_dirs.data_ptr(), stride)
-    mats = (al.data_ptr(), 0 if al.numel() == 1 else 1, vptr, vstride)
-    if mode == "dpixel":
-        d_alpha = torch.empty(NP, dtype=f32, device=dev)
-        d_normals = torch.empty((NP, 3), dtype=f32, device=dev) if need_dn else None
-        _call(lib.reni_envmap_shade_ggx_dpixel, dev, *head, srcs[0].data_ptr(), *mats, srcs[1].data_ptr(), srcs[2].data_ptr(),
-              srcs[3].data_ptr(), d_alpha.data_ptr(), d_normals.data_ptr() if need_dn else None, ws.data_ptr(), nbytes)
+        ws, nbytes = _workspace(p, lib.reni_envmap_shade_ggx_dpixel_workspace_bytes(p.B, p.NP, p.J))
+        d_alpha = torch.empty(p.NP, dtype=f32, device=p.dev)
+        d_normals = torch.empty((p.NP, 3), dtype=f32, device=p.dev) if need_dn else None
+        _call(lib.reni_envmap_shade_ggx_dpixel, p.dev, *p.head, ptr[0], *p.mats, ptr[1], ptr[2], ptr[3], d_alpha.data_ptr(),
+              d_normals.data_ptr() if need_dn else None, ws.data_ptr(), nbytes)
         return d_alpha, d_normals
+    ws, nbytes = _workspace(p, lib.reni_envmap_shade_ggx_workspace_bytes(p.B, p.NP, p.J))
     if mode == "forward":
-        outs = [torch.empty((B, NP, 3), dtype=f32, device=dev) for _ in range(3)]
-        _call(lib.reni_envmap_shade_ggx, dev, *head, srcs[0].data_ptr(), *mats, outs[0].data_ptr(), outs[1].data_ptr(),
+        outs = [torch.empty((p.B, p.NP, 3), dtype=f32, device=p.dev) for _ in range(3)]
+        _call(lib.reni_envmap_shade_ggx, p.dev, *p.head, ptr[0], *p.mats, outs[0].data_ptr(), outs[1].data_ptr(),
               outs[2].data_ptr(), ws.data_ptr(), nbytes)
         return tuple(outs)
-    out = torch.empty((B, J, 3), dtype=f32, device=dev)
-    _call(lib.reni_envmap_shade_ggx_backward, dev, *head, *mats, srcs[0].data_ptr(), srcs[1].data_ptr(), srcs[2].data_ptr(),
-          out.data_ptr(), ws.data_ptr(), nbytes)
+    out = torch.empty((p.B, p.J, 3), dtype=f32, device=p.dev)
+    _call(lib.reni_envmap_shade_ggx_backward, p.dev, *p.head, *p.mats, ptr[0], ptr[1], ptr[2], out.data_ptr(), ws.data_ptr(), nbytes)
     return out
 
 

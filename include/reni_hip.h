@@ -400,6 +400,43 @@ int reni_rasterize_mesh(int64_t V, int64_t F, const float* verts, const int64_t*
                         float* zbuf, float* bary, float* dists, float* pixel_normals, float* pixel_positions, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---- backward of the mesh G-buffer: pixel normals / positions -> vertex positions (reni_tu_raster_bwd.hip) ------------
+ * The "interpolate" half of a differentiable rasteriser: pix_to_face is held fixed (no silhouette or occlusion gradient),
+ * the camera is a constant.  Definitions, restating reni_tu_raster.hip (E = the edge function
+ * E(p, a, b) = (p_x - a_x)(b_y - a_y) - (p_y - a_y)(b_x - a_x)):
+ *   projection      q_i = p_i R + T,  t = tan_half_fov,  x_i = q_ix / (q_iz t),  y_i = q_iy / (q_iz t)
+ *   barycentrics    pixel p with centre (px, py) and face f = (i0, i1, i2):  A = E((x2,y2), (x0,y0), (x1,y1)) + 1e-8,
+ *                   w0 = E(p, 1, 2) / A,  w1 = E(p, 2, 0) / A,  w2 = E(p, 0, 1) / A
+ *   interpolation   N_p = sum_k w_k n_ik,  X_p = sum_k w_k p_ik   (no perspective correction)
+ *   vertex normals  n_v = u_v / max(|u_v|, 1e-6),  u_v = sum over the corners (f, k) naming v of
+ *                   (p_f1 - p_f0) x (p_f2 - p_f0), over faces whose three indices are in range (k_vertex_normals' rule)
+ * Computed, for gN, gX [S*S][3]:   g_verts = d/dp  sum_p (gN_p . N_p + gX_p . X_p)        [V][3]
+ * differentiated as written: 1e-8 is a constant; in the max branch (|u| <= 1e-6) dn/du = I 1e6.  Four paths reach p: the
+ * direct weights w_k of X_p; n_ik, through the normalisation and the cross products, to all vertices of all incident faces;
+ * w_k -> (x, y) of the three corners, A included; (x, y) -> q -> p with d/dp_i = sum_j R[i][j] d/dq_j.  Background pixels
+ * (pix_to_face -1) add nothing; a face the forward skips (an index outside [0, V), max view z < 0, |area| <= 1e-8) adds
+ * nothing through the pixel paths but still through the vertex-normal path when its indices are in range; a vertex no face
+ * names gets exactly 0.  fp32, no float atomics: every sum has one fixed order and two calls give identical bits.
+ * Malformed input (an index outside [0, V), a list entry outside [0, 3F) or [0, S*S), a pix_to_face outside [-1, F)) adds
+ * nothing and is never turned into an address.
+ * reni_mesh_vertex_normals_backward: the vertex-normal chain alone, grad_verts [V][3] = d/dp sum_v grad_normals[v] . n_v;
+ *   vf_offsets / vf_corners as for reni_mesh_vertex_normals.
+ * reni_gbuffer_backward: R, T (host memory), tan_half_fov, H == W = S and pix_to_face [S*S] as reni_rasterize_mesh took and
+ *   gave them; vert_normals [V][3] the normals it interpolated.  face_pixel_list [S*S]: the pixel indices in ascending
+ *   order of their face (a stable sort of pix_to_face), face_pixel_offsets [F+1]: face f's pixels are
+ *   face_pixel_list[face_pixel_offsets[f] .. face_pixel_offsets[f+1]).  The weights w_k are recomputed from the projected
+ *   corners exactly as the forward computes them; `bary` is not read.  grad_pixel_normals / grad_pixel_positions [S*S][3]:
+ *   either may be NULL (taken as 0), not both.  grad_verts [V][3] is overwritten.
+ *   ws: reni_gbuffer_backward_workspace_bytes(V, F, H, W) bytes, 256-byte aligned (the per-face records, g u_v). */
+int reni_mesh_vertex_normals_backward(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int64_t* vf_offsets,
+                                      const int64_t* vf_corners, const float* grad_normals, float* grad_verts, void* stream);
+size_t reni_gbuffer_backward_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W);
+int reni_gbuffer_backward(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* vert_normals,
+                          const float* R, const float* T, float tan_half_fov, int64_t H, int64_t W, const int64_t* pix_to_face,
+                          const int64_t* face_pixel_offsets, const int64_t* face_pixel_list, const int64_t* vf_offsets,
+                          const int64_t* vf_corners, const float* grad_pixel_normals, const float* grad_pixel_positions,
+                          float* grad_verts, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- cast shadows: visibility masks of the mesh for the shader (reni_tu_visibility.hip, the MASKED shader instances) ----
  * The shader above lets light pass through the mesh: M(p, j) knows the pixel's own normal and nothing else.  The lights are at
  * infinity, so whether texel direction j reaches pixel p is a constant of (mesh, camera, directions), as the G-buffer is.

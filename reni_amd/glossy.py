@@ -526,7 +526,8 @@ class PrefilteredRenderer(torch.nn.Module):
     values and, with a normal texture, the bent shading normals are fetched as ``mesh.HipMeshRenderer`` fetches them (a textured
     material needs a rasteriser), ``shader_cameras`` gives the camera centre as it does there, and the returned
     ``pixel_normals`` stay the geometry's.  The render is differentiable with respect to the map, the materials and the normal
-    texture.  Shadows are not supported.  Without ``materials`` kd is required and nothing changes."""
+    texture.  Shadows are not supported.  Without ``materials`` kd is required and nothing changes.  A mesh whose vertices
+    require grad raises a ValueError (geometry gradients go through ``mesh.HipMeshRenderer``)."""
 
     def __init__(self, rasterizer_or_gbuffer, kd: float = None, shininess: float = 500.0, out_width: int = 64, ks=None,
                  camera_center=None, materials=None, chain_roughness=CHAIN_ROUGHNESS, dfg_size: int = 32, shader_cameras=None):
@@ -570,6 +571,9 @@ class PrefilteredRenderer(torch.nn.Module):
                 g.to(dev)
             nrm, pos, (Hr, Wr) = g.pixel_normals, g.pixel_positions, g.image_size
         else:
+            if meshes_world.verts_packed().requires_grad and torch.is_grad_enabled():
+                raise ValueError("PrefilteredRenderer cannot be rendered while the mesh's vertices require grad: the prefiltered "
+                                 "lookup has no gradient with respect to geometry (detach the vertices, or use mesh.HipMeshRenderer)")
             _, nrm, pos = self.rasterizer.gbuffer(meshes_world, R, T)
             Hr = Wr = self.rasterizer.raster_settings.image_size
         B = envmap.environment_map.shape[0]

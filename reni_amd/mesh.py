@@ -8,7 +8,9 @@ per-vertex normals and the rasteriser + interpolation on the device (``reni_mesh
 
 Conventions (pytorch3d's): world -> view is ``p @ R + T`` with row vectors; NDC +X points left and +Y up, so image row 0
 is the top and column 0 the left edge at +x; the depth kept in ``zbuf`` is view-space z; barycentrics are NDC-space.
-Only the environment map carries a gradient (as in the reference): the mesh and the camera are constants.
+In the reference only the environment map carries a gradient.  Here the vertex positions may too (``verts.requires_grad``):
+the G-buffer's normals and positions then carry a gradient to them through ``ops.gbuffer_backward`` with the face assignment
+held fixed (no silhouette or occlusion gradient); the camera stays a constant.
 """
 from __future__ import annotations
 
@@ -21,7 +23,8 @@ import torch.nn as nn
 
 from . import _lib, ops, textures
 from .envmap_shader import (EnvironmentMap, MicrofacetMaterials, SpatialMaterials, _Materials, _shared_grid,
-                            blinn_phong_shading_gbuffer, blinn_phong_shading_materials, microfacet_shading_materials)
+                            blinn_phong_shading_gbuffer, blinn_phong_shading_materials, compose_materials,
+                            microfacet_shading_materials, shade_terms_normals)
 from .textures import TexturedMaterials, TexturedMicrofacetMaterials
 
 Fragments = namedtuple("Fragments", ["pix_to_face", "zbuf", "bary_coords", "dists"])
@@ -165,9 +168,53 @@ class FoVPerspectiveCameras:
         return self
 
 
+class _VertexNormalsFn(torch.autograd.Function):
+    """The cached vertex normals as a function of the vertices: the forward hands out the buffer ``ops.vertex_normals``
+    filled, the backward is ``ops.vertex_normals_backward``."""
+
+    @staticmethod
+    def forward(ctx, verts, faces, normals, vf):
+        ctx.save_for_backward(verts, faces)
+        ctx.vf = vf
+        return normals.detach()
+
+    @staticmethod
+    def backward(ctx, g):
+        verts, faces = ctx.saved_tensors
+        return ops.vertex_normals_backward(verts.detach(), faces, g.contiguous(), vf=ctx.vf), None, None, None
+
+
+class _GBufferFn(torch.autograd.Function):
+    """The cached G-buffer as a function of the vertices: the forward hands out the buffers ``ops.rasterize_mesh`` filled
+    (same kernel, same bits), the backward is ``ops.gbuffer_backward`` over the record's pix_to_face -- the vertex-normal
+    chain included, so the normals the rasteriser interpolated enter as a constant.  A node per call: two renders of one
+    cached G-buffer are back-propagated separately."""
+
+    @staticmethod
+    def forward(ctx, verts, rec):
+        ctx.save_for_backward(verts)
+        ctx.rec = rec
+        ctx.set_materialize_grads(False)
+        return rec["nrm"].detach(), rec["pos"].detach()
+
+    @staticmethod
+    def backward(ctx, gN, gX):
+        (verts,) = ctx.saved_tensors
+        rec = ctx.rec
+        if gN is None and gX is None:
+            return torch.zeros_like(verts), None
+        if rec.get("table") is None:  # the pixels sorted by face: once per G-buffer, on the device
+            rec["table"] = ops.face_pixel_table(rec["p2f"], rec["faces"].shape[0])
+        g = ops.gbuffer_backward(verts.detach(), rec["faces"], rec["normals"], rec["R"], rec["T"], rec["S"], rec["p2f"],
+                                 None if gN is None else gN.contiguous(), None if gX is None else gX.contiguous(),
+                                 tan_half_fov=rec["tan_half_fov"], table=rec["table"], vf=rec["vf"])
+        return g, None
+
+
 class Meshes:
     """One triangle mesh in pytorch3d's packed form: ``Meshes(verts=[v], faces=[f])``; the vertex normals come from the
-    HIP kernel (a device tensor is needed for them) and are computed once.  ``verts_uvs=[vt], faces_uvs=[ft]`` (both or
+    HIP kernel (a device tensor is needed for them) and are kept until the vertices or faces are modified in place (the key
+    is their ``_version``).  When the vertices require grad the normals carry a gradient to them.  ``verts_uvs=[vt], faces_uvs=[ft]`` (both or
     neither; ``load_obj_uv``) give the mesh texture coordinates: vt [Tn,2], ft [F,3] with its own indexing, an entry
     outside [0, Tn) marking a face without them."""
 
@@ -177,6 +224,7 @@ class Meshes:
         self._verts = verts[0].to(torch.float32).contiguous()
         self._faces = faces[0].to(torch.int64).contiguous()
         self._normals = None
+        self._vf = None
         self._verts_uvs = self._faces_uvs = None
         if (verts_uvs is None) != (faces_uvs is None):
             raise ValueError("verts_uvs and faces_uvs come together")
@@ -196,10 +244,25 @@ class Meshes:
     def faces_packed(self) -> torch.Tensor:
         return self._faces
 
+    def _vertex_faces(self):
+        """the vertex -> (face, corner) lists of the backward kernels, kept per in-place version of the faces"""
+        key = self._faces._version
+        if self._vf is None or self._vf[0] != key:
+            self._vf = (key, ops.vertex_face_lists(self._faces, self._verts.shape[0]))
+        return self._vf[1]
+
+    def _normals_value(self) -> torch.Tensor:
+        """the normals of the current vertices as a constant (no autograd node)"""
+        key = (self._verts._version, self._faces._version)
+        if self._normals is None or self._normals[0] != key:
+            self._normals = (key, ops.vertex_normals(self._verts.detach(), self._faces, vf=self._vertex_faces()))
+        return self._normals[1]
+
     def verts_normals_packed(self) -> torch.Tensor:
-        if self._normals is None:
-            self._normals = ops.vertex_normals(self._verts, self._faces)
-        return self._normals
+        n = self._normals_value()
+        if self._verts.requires_grad and torch.is_grad_enabled():
+            return _VertexNormalsFn.apply(self._verts, self._faces, n, self._vertex_faces())
+        return n
 
     def verts_uvs_packed(self):
         return self._verts_uvs
@@ -244,19 +307,31 @@ class MeshRasterizer(nn.Module):
         self._taps_cache = None
         self._tangent_cache = None
 
-    def gbuffer(self, meshes_world: Meshes, R=None, T=None):
-        """-> (Fragments, pixel_normals [S*S,3], pixel_positions [S*S,3]) (interpolated, not normalised)."""
+    def gbuffer(self, meshes_world: Meshes, R=None, T=None, differentiable: bool = True):
+        """-> (Fragments, pixel_normals [S*S,3], pixel_positions [S*S,3]) (interpolated, not normalised).
+
+        When the mesh's vertices require grad (and grad is enabled, and ``differentiable``) the two G-buffers carry a
+        gradient to them: the same cached buffers behind an autograd node built for this call (``ops.gbuffer_backward``:
+        the face assignment is held fixed -- no silhouette or occlusion gradient -- and the camera is a constant).  The
+        Fragments never carry one.  Otherwise the cached tensors themselves are returned, as before."""
         R = self.cameras.R if R is None else torch.as_tensor(R)
         T = self.cameras.T if T is None else torch.as_tensor(T)
         S = self.raster_settings.image_size
         v, f = meshes_world.verts_packed(), meshes_world.faces_packed()
         key = tuple((id(t), t._version) for t in (v, f, R, T)) + (S, self.cameras.tan_half_fov())
-        if self._cache is not None and self._cache[0] == key:
-            return self._cache[2]
-        p2f, zbuf, bary, dists, nrm, pos = ops.rasterize_mesh(v, f, meshes_world.verts_normals_packed(), R, T, S,
-                                                              self.cameras.tan_half_fov())
-        out = (Fragments(p2f, zbuf, bary, dists), nrm, pos)
-        self._cache = (key, (v, f, R, T), out)  # (the tensors are held so that their ids stay theirs)
+        if self._cache is None or self._cache[0] != key:
+            normals = meshes_world._normals_value()
+            p2f, zbuf, bary, dists, nrm, pos = ops.rasterize_mesh(v.detach(), f, normals, R, T, S, self.cameras.tan_half_fov())
+            out = (Fragments(p2f, zbuf, bary, dists), nrm, pos)
+            rec = {"faces": f, "normals": normals, "R": R, "T": T, "S": S, "tan_half_fov": self.cameras.tan_half_fov(),
+                   "p2f": p2f, "nrm": nrm, "pos": pos, "table": None, "vf": None}
+            self._cache = (key, (v, f, R, T), out, rec)  # (the tensors are held so that their ids stay theirs)
+        out, rec = self._cache[2], self._cache[3]
+        if differentiable and v.requires_grad and torch.is_grad_enabled():
+            if rec["vf"] is None:
+                rec["vf"] = meshes_world._vertex_faces()
+            nrm, pos = _GBufferFn.apply(v, rec)
+            return out[0], nrm, pos
         return out
 
     def visibility(self, meshes_world: Meshes, R=None, T=None, dirs=None, t_min=None, no_cull: bool = False):
@@ -268,13 +343,13 @@ class MeshRasterizer(nn.Module):
         and in-place version, t_min), like the G-buffer itself."""
         if not isinstance(dirs, torch.Tensor):
             raise ValueError("dirs must be a tensor [J, 3] or [B, J, 3]")
-        frags, _, pos = self.gbuffer(meshes_world, R, T)
+        frags, _, pos = self.gbuffer(meshes_world, R, T, differentiable=False)  # the mask is a constant of the geometry
         gkey = self._cache[0]
         v, f = meshes_world.verts_packed(), meshes_world.faces_packed()
         akey = tuple((id(t), t._version) for t in (v, f))
         if self._accel_cache is None or self._accel_cache[0] != akey:
-            diag = float((v.max(dim=0).values - v.min(dim=0).values).norm())
-            self._accel_cache = (akey, (v, f), ops.mesh_visibility_prepare(v, f), diag)
+            diag = float((v.detach().max(dim=0).values - v.detach().min(dim=0).values).norm())
+            self._accel_cache = (akey, (v, f), ops.mesh_visibility_prepare(v.detach(), f), diag)
         _, _, accel, diag = self._accel_cache
         t_min = 1e-4 * diag if t_min is None else float(t_min)
         # a view of the same memory (directions.expand(B, -1, -1)[0], a fresh Python object every step) is the same grid
@@ -290,7 +365,7 @@ class MeshRasterizer(nn.Module):
         vt, ft = meshes_world.verts_uvs_packed(), meshes_world.faces_uvs_packed()
         if vt is None:
             raise ValueError("the mesh has no texture coordinates (Meshes(verts_uvs=, faces_uvs=); load_obj_uv reads them)")
-        self.gbuffer(meshes_world, R, T)
+        self.gbuffer(meshes_world, R, T, differentiable=False)
         return (self._cache[0], tuple((id(t), t._version) for t in (vt, ft)))
 
     def pixel_uv(self, meshes_world: Meshes, R=None, T=None):
@@ -301,7 +376,7 @@ class MeshRasterizer(nn.Module):
         if self._uv_cache is not None and self._uv_cache[0] == key:
             return self._uv_cache[2]
         frags = self._cache[2][0]
-        _, (v, f, Rk, Tk), _ = self._cache
+        _, (v, f, Rk, Tk), _, _ = self._cache
         vt, ft = meshes_world.verts_uvs_packed(), meshes_world.faces_uvs_packed()
         out = ops.mesh_pixel_uv(v, f, vt, ft, Rk, Tk, self.raster_settings.image_size, frags.pix_to_face, frags.bary_coords,
                                 self.cameras.tan_half_fov())
@@ -316,7 +391,7 @@ class MeshRasterizer(nn.Module):
         if self._tangent_cache is not None and self._tangent_cache[0] == key:
             return self._tangent_cache[2]
         _, _, valid = self.pixel_uv(meshes_world, R, T)
-        _, (v, f, _, _), (_, nrm, _) = self._cache
+        _, (v, f, _, _), (_, nrm, _), _ = self._cache
         vt, ft = meshes_world.verts_uvs_packed(), meshes_world.faces_uvs_packed()
         out = textures.tangent_frames(v, f, vt, ft, valid, nrm)
         self._tangent_cache = (key, (vt, ft), out)
@@ -345,7 +420,7 @@ class MeshRasterizer(nn.Module):
         return found
 
     def forward(self, meshes_world: Meshes, R=None, T=None, **kwargs) -> Fragments:
-        return self.gbuffer(meshes_world, R, T)[0]
+        return self.gbuffer(meshes_world, R, T, differentiable=False)[0]
 
 
 class HipMeshRenderer(nn.Module):
@@ -377,7 +452,16 @@ class HipMeshRenderer(nn.Module):
     ``materials=MicrofacetMaterials(...)`` / ``TexturedMicrofacetMaterials(...)``: a base colour, a roughness and a metallic
     per render pixel / in the mesh's UV space, shaded by the microfacet (GGX) terms
     (``envmap_shader.microfacet_shading_materials``); everything said above about the two Blinn-Phong classes holds for
-    their microfacet siblings, the normal texture included."""
+    their microfacet siblings, the normal texture included.
+
+    Geometry: when the mesh's vertices require grad the render and the returned ``pixel_normals`` carry a gradient to them
+    through the G-buffer's normals (``MeshRasterizer.gbuffer``): shape from shading under a fixed silhouette.  The scalar
+    kd / ks renderer then goes through ``shade_terms_normals`` + ``compose_materials`` (equal to the fused scalar kernel to
+    rounding; the fused kernel stays whenever the vertices need no gradient), ``SpatialMaterials`` through the same terms,
+    ``MicrofacetMaterials`` as always.  Deliberately dropped: the positions are handed to the shader detached (the view
+    vector's dependence on the geometry), the shadow mask is computed from detached tensors and stays constant, pixels do
+    not change face.  ``TexturedMaterials`` / ``TexturedMicrofacetMaterials`` raise a ValueError: UVs, taps and tangent
+    frames under moving geometry are out of scope."""
 
     def __init__(self, rasterizer: MeshRasterizer, kd: float = None, ks: float = None, materials=None, shader_cameras=None,
                  shadows: bool = False):
@@ -399,6 +483,13 @@ class HipMeshRenderer(nn.Module):
 
     def forward(self, meshes_world: Meshes = None, R=None, T=None, envmap: EnvironmentMap = None, **kwargs):
         _, nrm, pos = self.rasterizer.gbuffer(meshes_world, R, T)
+        geometry = nrm.requires_grad  # the mesh's vertices require grad: the G-buffer carries a gradient to them
+        if geometry:
+            if self.textured:
+                raise ValueError(f"{type(self.materials).__name__} cannot be rendered while the mesh's vertices require grad: "
+                                 "UVs, taps and tangent frames under moving geometry are out of scope (detach the vertices, "
+                                 "or use SpatialMaterials / MicrofacetMaterials)")
+            pos = pos.detach()  # the view vector's dependence on the geometry is dropped: the shader's positions are constants
         S = self.rasterizer.raster_settings.image_size
         B = envmap.environment_map.shape[0]
         vis = None
@@ -420,7 +511,8 @@ class HipMeshRenderer(nn.Module):
         elif self.spatial:
             if self.materials.ks.device != nrm.device:
                 self.materials.to(nrm.device)
-            colors = blinn_phong_shading_materials(nrm, pos, self.camera_center, envmap, *self.materials.values(), vis=vis)
+            colors = blinn_phong_shading_materials(nrm, pos, self.camera_center, envmap, *self.materials.values(), vis=vis,
+                                                   differentiable_normals=geometry)
         elif self.textured:
             if self.materials.ks.device != nrm.device:
                 self.materials.to(nrm.device)
@@ -430,6 +522,10 @@ class HipMeshRenderer(nn.Module):
             colors = blinn_phong_shading_materials(shade_nrm, pos, self.camera_center, envmap,
                                                    *self.materials.values(self.rasterizer, meshes_world, R, T), vis=vis,
                                                    differentiable_normals=shade_nrm.requires_grad)
+        elif geometry:  # the scalar shader through its terms: the fused kernel has no gradient with respect to the normals
+            shininess = float(torch.as_tensor(self.materials.shininess).reshape(-1)[0])
+            D, Sp = shade_terms_normals(nrm, pos, self.camera_center, envmap, shininess, vis=vis)
+            colors = compose_materials(D, Sp, self.kd, self.ks, shininess)
         else:
             colors = blinn_phong_shading_gbuffer(nrm, pos, self.camera_center, envmap, self.materials.shininess, self.kd,
                                                  self.ks, vis=vis)

@@ -756,14 +756,13 @@ def _mesh_inputs(verts, faces):
     return verts, faces
 
 
-def vertex_normals(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+def vertex_normals(verts: torch.Tensor, faces: torch.Tensor, vf=None) -> torch.Tensor:
     """reni_mesh_vertex_normals: Meshes.verts_normals_packed() of one mesh, [V, 3] -- the area-weighted sum of the adjacent
-    faces' cross(v1 - v0, v2 - v0), normalised with max(|n|, 1e-6).  Deterministic (a gather in ascending face order)."""
+    faces' cross(v1 - v0, v2 - v0), normalised with max(|n|, 1e-6).  Deterministic (a gather in ascending face order).
+    ``vf``: ``vertex_face_lists(faces, V)`` when the caller keeps it (the same lists, the same bits)."""
     verts, faces = _mesh_inputs(verts, faces)
     V, F = verts.shape[0], faces.shape[0]
-    offsets, corners = _vertex_face_csr(faces, V)
-    if corners.numel() == 0:
-        corners = torch.zeros(1, dtype=torch.int64, device=verts.device)  # (never read: every vertex's range is empty)
+    offsets, corners = _vf_lists(faces, V, vf)
     out = torch.empty(V, 3, dtype=torch.float32, device=verts.device)
     _call(_lib.load().reni_mesh_vertex_normals, verts.device, V, F, verts.data_ptr(), faces.data_ptr(), offsets.data_ptr(),
           corners.data_ptr(), out.data_ptr())
@@ -803,6 +802,116 @@ def rasterize_mesh(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch
     _call(lib.reni_rasterize_mesh, dev, V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th, float(tan_half_fov),
           S, S, p2f.data_ptr(), zbuf.data_ptr(), bary.data_ptr(), dists.data_ptr(), nrm.data_ptr(), pos.data_ptr(), wp, wn)
     return p2f, zbuf, bary, dists, nrm, pos
+
+
+def _mesh_shapes(verts, faces):
+    """The shape rules of ``_mesh_inputs``, asked first: a bad shape is a ValueError before any device is looked at."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError(f"verts must be a tensor [V, 3] with V >= 1, got {tuple(getattr(verts, 'shape', ()))}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError(f"faces must be a tensor [F, 3] with F >= 1, got {tuple(getattr(faces, 'shape', ()))}")
+
+
+def vertex_face_lists(faces: torch.Tensor, V: int):
+    """(offsets [V + 1], corners) int64: the faces of every vertex as corner indices 3 f + k, ascending per vertex -- what
+    ``vertex_normals_backward`` and ``gbuffer_backward`` gather through (``vf=``).  It depends on the faces alone: a caller
+    whose vertices move every step keeps it."""
+    offsets, corners = _vertex_face_csr(faces.to(torch.int64).contiguous(), int(V))
+    if corners.numel() == 0:
+        corners = torch.zeros(1, dtype=torch.int64, device=faces.device)  # (never read: every vertex's range is empty)
+    return offsets, corners
+
+
+def _vf_lists(faces, V, vf):
+    if vf is None:
+        return vertex_face_lists(faces, V)
+    offsets, corners = vf
+    if (not isinstance(offsets, torch.Tensor) or not isinstance(corners, torch.Tensor) or tuple(offsets.shape) != (V + 1,)
+            or corners.dim() != 1 or corners.numel() < 1 or offsets.dtype != torch.int64 or corners.dtype != torch.int64
+            or offsets.device != faces.device or corners.device != faces.device):
+        raise ValueError(f"vf must be vertex_face_lists(faces, {V}) on {faces.device}")
+    return offsets.contiguous(), corners.contiguous()
+
+
+def vertex_normals_backward(verts: torch.Tensor, faces: torch.Tensor, grad_normals: torch.Tensor, vf=None) -> torch.Tensor:
+    """reni_mesh_vertex_normals_backward: grad_verts [V, 3] = d/d verts of sum_v grad_normals[v] . n_v for the normals of
+    ``vertex_normals`` (the Jacobian of u / max(|u|, 1e-6), then the cross products to every vertex of every incident face).
+    Deterministic: gathers in ascending face order, no atomics."""
+    _mesh_shapes(verts, faces)
+    if not isinstance(grad_normals, torch.Tensor) or tuple(grad_normals.shape) != tuple(verts.shape):
+        raise ValueError(f"grad_normals must be [V, 3] like verts, got {tuple(getattr(grad_normals, 'shape', ()))}")
+    verts, faces = _mesh_inputs(verts, faces)
+    _require_cuda(grad_normals)
+    grad_normals = _f32c(grad_normals)
+    if grad_normals.device != verts.device:
+        raise ValueError("grad_normals is not on the mesh's device")
+    V, F = verts.shape[0], faces.shape[0]
+    offsets, corners = _vf_lists(faces, V, vf)
+    out = torch.empty(V, 3, dtype=torch.float32, device=verts.device)
+    _call(_lib.load().reni_mesh_vertex_normals_backward, verts.device, V, F, verts.data_ptr(), faces.data_ptr(), offsets.data_ptr(),
+          corners.data_ptr(), grad_normals.data_ptr(), out.data_ptr())
+    return out
+
+
+def face_pixel_table(pix_to_face: torch.Tensor, F: int):
+    """What ``gbuffer_backward`` walks a face's pixels through: (offsets [F + 1] int64, pixels [S*S] int64) from the
+    rasteriser's pix_to_face -- a stable sort on the device and a searchsorted that bins the pixels per face, as
+    ``texture_table`` does.  The background (-1) sorts in front of offsets[0], anything >= F behind offsets[F]."""
+    keys, order = torch.sort(pix_to_face.reshape(-1), stable=True)
+    offsets = torch.searchsorted(keys, torch.arange(int(F) + 1, device=keys.device, dtype=torch.int64))
+    return offsets.contiguous(), order.contiguous()
+
+
+def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch.Tensor, R, T, image_size: int,
+                     pix_to_face: torch.Tensor, grad_pixel_normals=None, grad_pixel_positions=None,
+                     tan_half_fov: float = 0.5773502691896258, table=None, vf=None) -> torch.Tensor:
+    """reni_gbuffer_backward: grad_verts [V, 3] = d/d verts of sum_p (gN_p . N_p + gX_p . X_p) for the G-buffer of
+    ``rasterize_mesh`` (N = pixel_normals, X = pixel_positions) with pix_to_face held fixed: through the interpolation
+    weights' dependence on the projected corners, the interpolated positions, and -- for gN -- the vertex normals
+    (``vertex_normals``' chain included: vert_normals must be the normals of verts, and is a constant here).  Either upstream
+    gradient ([S*S, 3]) may be None, not both.  ``table``: ``face_pixel_table(pix_to_face, F)``, ``vf``: ``vertex_face_lists(faces, V)``, when the caller keeps them.
+    Deterministic, no atomics; no silhouette / occlusion gradient, the camera is a constant."""
+    _mesh_shapes(verts, faces)
+    S = int(image_size)
+    if S < 1:
+        raise ValueError("image_size must be >= 1")
+    if not isinstance(vert_normals, torch.Tensor) or tuple(vert_normals.shape) != tuple(verts.shape):
+        raise ValueError("vert_normals must be [V, 3] like verts")
+    if not isinstance(pix_to_face, torch.Tensor) or pix_to_face.dtype != torch.int64 or pix_to_face.numel() != S * S:
+        raise ValueError(f"pix_to_face must be an int64 tensor of {S * S} entries (the rasteriser's)")
+    if grad_pixel_normals is None and grad_pixel_positions is None:
+        raise ValueError("grad_pixel_normals and grad_pixel_positions cannot both be None")
+    for name, g in (("grad_pixel_normals", grad_pixel_normals), ("grad_pixel_positions", grad_pixel_positions)):
+        if g is not None and (not isinstance(g, torch.Tensor) or tuple(g.shape) != (S * S, 3)):
+            raise ValueError(f"{name} must be [{S * S}, 3] or None, got {tuple(getattr(g, 'shape', ()))}")
+    Rv = [float(x) for x in torch.as_tensor(R).reshape(-1).tolist()]
+    Tv = [float(x) for x in torch.as_tensor(T).reshape(-1).tolist()]
+    if len(Rv) != 9 or len(Tv) != 3:
+        raise ValueError("R must hold 9 values ([1,3,3] or [3,3]) and T 3 ([1,3] or [3])")
+    verts, faces = _mesh_inputs(verts, faces)
+    _require_cuda(vert_normals, pix_to_face, grad_pixel_normals, grad_pixel_positions)
+    dev = verts.device
+    vert_normals = _f32c(vert_normals)
+    p2f = pix_to_face.reshape(-1).contiguous()
+    gN = None if grad_pixel_normals is None else _f32c(grad_pixel_normals)
+    gX = None if grad_pixel_positions is None else _f32c(grad_pixel_positions)
+    if any(t is not None and t.device != dev for t in (vert_normals, p2f, gN, gX)):
+        raise ValueError(f"the G-buffer and its gradients are not on {dev}")
+    V, F = verts.shape[0], faces.shape[0]
+    foff, flist = face_pixel_table(p2f, F) if table is None else table
+    if (tuple(foff.shape) != (F + 1,) or tuple(flist.shape) != (S * S,) or foff.dtype != torch.int64 or flist.dtype != torch.int64
+            or foff.device != dev or flist.device != dev):
+        raise ValueError(f"the table is not one of {S * S} pixels over {F} faces on {dev}")
+    offsets, corners = _vf_lists(faces, V, vf)
+    Rh, Th = (ctypes.c_float * 9)(*Rv), (ctypes.c_float * 3)(*Tv)
+    lib = _lib.load()
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_gbuffer_backward_workspace_bytes(V, F, S, S)), dev)
+    _call(lib.reni_gbuffer_backward, dev, V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th,
+          float(tan_half_fov), S, S, p2f.data_ptr(), foff.contiguous().data_ptr(), flist.contiguous().data_ptr(),
+          offsets.data_ptr(), corners.data_ptr(), None if gN is None else gN.data_ptr(), None if gX is None else gX.data_ptr(),
+          out.data_ptr(), wp, wn)
+    return out
 
 
 def _morton_order(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:

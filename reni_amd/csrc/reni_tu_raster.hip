@@ -3,7 +3,8 @@
 // Reference: build_renderer, src/utils/pytorch3d_envmap_shader.py:177-217 -- pytorch3d's Meshes.verts_normals_packed,
 // FoVPerspectiveCameras (defaults), MeshRasterizer(image_size = S, blur_radius = 0, faces_per_pixel = 1,
 // perspective_correct = False) and the two interpolate_face_attributes calls of the shader (:68-73).  Restated from
-// pytorch3d's documented behaviour; all arithmetic is fp32 as there.  Three kernels, none with a float atomic:
+// pytorch3d's documented behaviour; all arithmetic is fp32 as there.  Three kernels, none with a float atomic; the mesh_*
+// pieces (projection, edge function, weights, face rule, list walk) are reni_mesh.inc's, shared with the backward:
 //
 //   k_vertex_normals  one thread per vertex gathers cross(v1 - v0, v2 - v0) of its faces in ascending face order
 //                     through a vertex -> (face, corner) CSR list, then v / max(|v|, 1e-6)        (pytorch3d: index_add)
@@ -24,12 +25,10 @@
 #include "reni_hip.h"
 #include "reni_internal.h"
 #include "reni_tu_host.inc"
-
-#define DEV __device__ __forceinline__
+#include "reni_mesh.inc"
 
 namespace reni {
 
-constexpr float RS_EPS = 1e-8f;   // pytorch3d kEpsilon (rasterize_meshes)
 constexpr int RS_TILE = 16;       // pixels per tile side
 constexpr int RS_CHUNK = 256;     // faces per LDS stage (= threads per workgroup)
 
@@ -40,14 +39,10 @@ struct FaceRec {  // 64 bytes, read as four float4 (world order of the corners)
   float4 box;     // NDC xmin xmax ymin ymax; empty (+inf, -inf, +inf, -inf) for a skipped face
 };
 
-DEV float edge_fn(float px, float py, float ax, float ay, float bx, float by) {  // EdgeFunctionForward(p, a, b)
-  return (px - ax) * (by - ay) - (py - ay) * (bx - ax);
-}
-
 DEV float point_line_dist2(float px, float py, float ax, float ay, float bx, float by) {  // PointLineDistanceForward
   const float bax = bx - ax, bay = by - ay;
   const float l2 = bax * bax + bay * bay;
-  if (l2 <= RS_EPS) return (px - bx) * (px - bx) + (py - by) * (py - by);
+  if (l2 <= MESH_EPS) return (px - bx) * (px - bx) + (py - by) * (py - by);
   const float t = fminf(fmaxf((bax * (px - ax) + bay * (py - ay)) / l2, 0.f), 1.f);
   const float dx = ax + t * bax - px, dy = ay + t * bay - py;
   return dx * dx + dy * dy;
@@ -59,60 +54,23 @@ __global__ void __launch_bounds__(256) k_vertex_normals(int V, int F, const floa
                                                         const int64_t* __restrict__ corner, float* __restrict__ nrm) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= V) return;
-  const int64_t n3 = 3 * (int64_t)F;
-  const int64_t b = min(max(off[v], (int64_t)0), n3), e = min(max(off[v + 1], b), n3);
-  float nx = 0.f, ny = 0.f, nz = 0.f;
-  for (int64_t k = b; k < e; ++k) {
-    const int64_t c = corner[k];
-    if (c < 0 || c >= n3 || faces[c] != v) continue;  // a malformed list entry adds nothing
-    const int64_t f = c / 3;
-    const int64_t i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-    if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) continue;
-    const float* p0 = verts + 3 * i0;
-    const float* p1 = verts + 3 * i1;
-    const float* p2 = verts + 3 * i2;
-    const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
-    const float bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
-    nx += ay * bz - az * by;
-    ny += az * bx - ax * bz;
-    nz += ax * by - ay * bx;
-  }
-  const float inv = 1.f / fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-6f);
+  const GbMesh m{verts, faces, off, corner, V, F};
+  float nx, ny, nz;
+  mesh_u(m, v, nx, ny, nz);
+  const float inv = 1.f / fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), MESH_NRM_EPS);
   nrm[3 * (size_t)v] = nx * inv;
   nrm[3 * (size_t)v + 1] = ny * inv;
   nrm[3 * (size_t)v + 2] = nz * inv;
 }
 
 // ---- face setup --------------------------------------------------------------------------------------------------------
-struct Camera {
-  float R[9];  // row-major, p_view[j] = sum_i p[i] R[i][j] + T[j]
-  float T[3];
-  float tan_half_fov;
-};
-
 __global__ void __launch_bounds__(256) k_face_setup(int V, int F, const float* __restrict__ verts,
                                                     const int64_t* __restrict__ faces, const Camera cam,
                                                     FaceRec* __restrict__ rec) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= F) return;
-  float x[3] = {0.f, 0.f, 0.f}, y[3] = {0.f, 0.f, 0.f}, z[3] = {0.f, 0.f, 0.f};
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int64_t i = faces[3 * (size_t)f + k];
-    if (i < 0 || i >= V) { ok = false; continue; }
-    const float px = verts[3 * i], py = verts[3 * i + 1], pz = verts[3 * i + 2];
-    const float vx = px * cam.R[0] + py * cam.R[3] + pz * cam.R[6] + cam.T[0];
-    const float vy = px * cam.R[1] + py * cam.R[4] + pz * cam.R[7] + cam.T[1];
-    const float vz = px * cam.R[2] + py * cam.R[5] + pz * cam.R[8] + cam.T[2];
-    const float w = vz * cam.tan_half_fov;
-    x[k] = vx / w;
-    y[k] = vy / w;
-    z[k] = vz;
-  }
-  const float area = edge_fn(x[0], y[0], x[1], y[1], x[2], y[2]);
-  const float zmax = fmaxf(z[0], fmaxf(z[1], z[2]));
-  ok = ok && !(zmax < 0.f) && !(fabsf(area) <= RS_EPS);
+  float x[3], y[3], z[3], area;
+  const bool ok = mesh_face(cam, V, verts, faces, (size_t)f, x, y, z, area);
   FaceRec r;
   r.xy01 = float4{x[0], y[0], x[1], y[1]};
   r.xy2z01 = float4{x[2], y[2], z[0], z[1]};
@@ -138,8 +96,6 @@ struct RasterArgs {
   int F, S;
 };
 
-DEV float pix_ndc(int i, int S) { return -1.f + (2.f * (float)i + 1.f) / (float)S; }  // PixToNdc, i counted from +x / +y
-
 __global__ void __launch_bounds__(256) k_raster_tile(const RasterArgs a) {
   __shared__ float4 s_geo[RS_CHUNK][3];  // the overlapping faces' xy01, xy2z01, z2a, compacted in ascending face order
   __shared__ int s_idx[RS_CHUNK];
@@ -149,11 +105,11 @@ __global__ void __launch_bounds__(256) k_raster_tile(const RasterArgs a) {
   const int r = blockIdx.y * RS_TILE + (wave >> 1) * 8 + (lane >> 3);
   const int c = blockIdx.x * RS_TILE + (wave & 1) * 8 + (lane & 7);
   const bool live = r < S && c < S;
-  const float px = pix_ndc(S - 1 - c, S), py = pix_ndc(S - 1 - r, S);
+  const float px = mesh_pix_ndc(S - 1 - c, S), py = mesh_pix_ndc(S - 1 - r, S);
   // the tile's pixel-centre extent (rows / columns beyond the image excluded); x decreases with c, y with r
   const int c_hi = min(S, (int)(blockIdx.x + 1) * RS_TILE) - 1, r_hi = min(S, (int)(blockIdx.y + 1) * RS_TILE) - 1;
-  const float tx_max = pix_ndc(S - 1 - blockIdx.x * RS_TILE, S), tx_min = pix_ndc(S - 1 - c_hi, S);
-  const float ty_max = pix_ndc(S - 1 - blockIdx.y * RS_TILE, S), ty_min = pix_ndc(S - 1 - r_hi, S);
+  const float tx_max = mesh_pix_ndc(S - 1 - blockIdx.x * RS_TILE, S), tx_min = mesh_pix_ndc(S - 1 - c_hi, S);
+  const float ty_max = mesh_pix_ndc(S - 1 - blockIdx.y * RS_TILE, S), ty_min = mesh_pix_ndc(S - 1 - r_hi, S);
 
   float best_z = INFINITY, w0b = -1.f, w1b = -1.f, w2b = -1.f;
   int best_f = -1;
@@ -188,10 +144,9 @@ __global__ void __launch_bounds__(256) k_raster_tile(const RasterArgs a) {
       const float x0 = g0.x, y0 = g0.y, x1 = g0.z, y1 = g0.w, x2 = g1.x, y2 = g1.y;
       if (px > fmaxf(x0, fmaxf(x1, x2)) || px < fminf(x0, fminf(x1, x2)) ||
           py > fmaxf(y0, fmaxf(y1, y2)) || py < fminf(y0, fminf(y1, y2))) continue;
-      const float A = edge_fn(x2, y2, x0, y0, x1, y1) + RS_EPS;  // BarycentricCoordsForward
-      const float w0 = edge_fn(px, py, x1, y1, x2, y2) / A;
-      const float w1 = edge_fn(px, py, x2, y2, x0, y0) / A;
-      const float w2 = edge_fn(px, py, x0, y0, x1, y1) / A;
+      const float A = mesh_bary_area(x0, y0, x1, y1, x2, y2);
+      float w0, w1, w2;
+      mesh_bary(px, py, x0, y0, x1, y1, x2, y2, A, w0, w1, w2);
       if (!(w0 > 0.f && w1 > 0.f && w2 > 0.f)) continue;  // blur_radius 0: inside only
       const float pz = w0 * g1.z + w1 * g1.w + w2 * g2.x;
       if (pz < 0.f || !(pz < best_z)) continue;
@@ -233,24 +188,18 @@ __global__ void __launch_bounds__(256) k_raster_tile(const RasterArgs a) {
 
 }  // namespace reni
 
-namespace {
-
-using reni::reni_set_error;
-constexpr int64_t RS_MAX_ELEMS = 0x3fffffff;  // V, F; S * S
-
-}  // namespace
-
 extern "C" {
 
 size_t reni_raster_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W) {
-  if (V < 1 || F < 1 || H < 1 || W < 1 || V > RS_MAX_ELEMS || F > RS_MAX_ELEMS) return 0;
+  if (V < 1 || F < 1 || H < 1 || W < 1 || V > MESH_MAX_ELEMS || F > MESH_MAX_ELEMS) return 0;
   return (size_t)F * sizeof(reni::FaceRec) + 256;
 }
 
 int reni_mesh_vertex_normals(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int64_t* vf_offsets,
                              const int64_t* vf_corners, float* normals, void* stream) {
-  if (V < 1 || F < 1 || V > RS_MAX_ELEMS || F > RS_MAX_ELEMS) return reni_set_error(RENI_EINVAL, "vertex normals: bad V / F");
-  if (!verts || !faces || !vf_offsets || !vf_corners || !normals) return reni_set_error(RENI_EINVAL, "vertex normals: NULL argument");
+  const char* who = "vertex normals";
+  if (int rc = mesh_check_sizes(who, V, F)) return rc;
+  if (!verts || !faces || !vf_offsets || !vf_corners || !normals) return tu_fail(RENI_EINVAL, who, "NULL argument");
   return tu_launch(TU_PLAIN, reni::k_vertex_normals, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)V,
                    (int)F, verts, faces, vf_offsets, vf_corners, normals);
 }
@@ -259,21 +208,18 @@ int reni_rasterize_mesh(int64_t V, int64_t F, const float* verts, const int64_t*
                         const float* R, const float* T, float tan_half_fov, int64_t H, int64_t W, int64_t* pix_to_face,
                         float* zbuf, float* bary, float* dists, float* pixel_normals, float* pixel_positions, void* ws,
                         size_t ws_bytes, void* stream) {
-  if (V < 1 || F < 1 || V > RS_MAX_ELEMS || F > RS_MAX_ELEMS) return reni_set_error(RENI_EINVAL, "rasterize: bad V / F");
-  if (H < 1 || H != W || H * W > RS_MAX_ELEMS) return reni_set_error(RENI_EINVAL, "rasterize: the image must be square, H == W >= 1");
+  const char* who = "rasterize";
+  if (int rc = mesh_check_sizes(who, V, F)) return rc;
+  if (int rc = mesh_check_image(who, H, W)) return rc;
   if (!verts || !faces || !vert_normals || !R || !T || !pix_to_face || !zbuf || !bary || !dists || !pixel_normals ||
       !pixel_positions)
-    return reni_set_error(RENI_EINVAL, "rasterize: NULL argument");
-  if (!(tan_half_fov > 0.f) || !isfinite(tan_half_fov)) return reni_set_error(RENI_EINVAL, "rasterize: tan_half_fov must be positive");
-  if (int rc = tu_check_ws("rasterize", ws, ws_bytes, (size_t)F * sizeof(reni::FaceRec))) return rc;
+    return tu_fail(RENI_EINVAL, who, "NULL argument");
+  if (int rc = mesh_check_fov(who, tan_half_fov)) return rc;
+  if (int rc = tu_check_ws(who, ws, ws_bytes, (size_t)F * sizeof(reni::FaceRec))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  reni::Camera cam;
-  for (int i = 0; i < 9; ++i) cam.R[i] = R[i];
-  for (int i = 0; i < 3; ++i) cam.T[i] = T[i];
-  cam.tan_half_fov = tan_half_fov;
   reni::FaceRec* rec = (reni::FaceRec*)ws;
   if (int rc = tu_launch(TU_PLAIN, reni::k_face_setup, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, (int)V, (int)F, verts, faces,
-                         cam, rec))
+                         mesh_camera(R, T, tan_half_fov), rec))
     return rc;
   reni::RasterArgs a;
   a.rec = rec; a.verts = verts; a.vnrm = vert_normals; a.faces = faces;

@@ -8,8 +8,8 @@
 // sum has one fixed order, two calls give identical bits.  Three kernels:
 //
 //   k_gb_face      one wave64 per face.  The face's pixels come from a sorted list (a stable sort of pix_to_face); the lanes
-//                  walk it with stride 64, each recomputing its pixel's weights from the projected corners as the forward
-//                  does, and sum 25 partials: w_k gN (9), w_k gX (9), the NDC gradients of the three corners through the
+//                  walk it with stride 64, each recomputing its pixel's weights from the projected corners with the forward's
+//                  own functions (reni_mesh.inc: mesh_face, mesh_bary), and sum 25 partials: w_k gN (9), w_k gX (9), the NDC gradients of the three corners through the
 //                  edge functions (6) and d loss / dA (1).  A butterfly of shuffles adds the lanes in one fixed order; lane 0
 //                  folds dA into the corners, takes (x, y) -> q -> p and writes the face's record: per corner the sum
 //                  w_k gN (for the vertex normal) and the gradient of the corner's position (direct + projection).
@@ -19,7 +19,8 @@
 //   k_vn_bwd       one thread per vertex, over its faces ascending: G_f = g u_f0 + g u_f1 + g u_f2, a = p_f1 - p_f0,
 //                  b = p_f2 - p_f0; corner 1 gets b x G_f, corner 2 G_f x a, corner 0 minus both.  <true>: g u read from the
 //                  workspace (the G-buffer backward); <false>: recomputed from g n on the fly (reni_mesh_vertex_normals_backward,
-//                  which has no workspace; the thread's own vertex once), the same arithmetic.
+//                  which has no workspace; the thread's own vertex once), the same arithmetic; u_v is mesh_u, the sum
+//                  k_vertex_normals normalises.
 //
 // Malformed input adds nothing and reads nothing out of range: a vertex index outside [0, V), a list entry outside [0, 3F) or
 // one that does not name the vertex, offsets outside their list, a pixel entry outside [0, S S) or one whose pix_to_face is
@@ -31,20 +32,11 @@
 #include "reni_hip.h"
 #include "reni_internal.h"
 #include "reni_tu_host.inc"
-
-#define DEV __device__ __forceinline__
+#include "reni_mesh.inc"
 
 namespace reni {
 
-constexpr float GB_EPS = 1e-8f;     // pytorch3d kEpsilon, as the forward
-constexpr float GB_NRM_EPS = 1e-6f; // the floor of |u_v|
-constexpr int GB_REC = 18;          // floats per face record: per corner (sum w_k gN [3], g position [3])
-
-struct GbCamera {
-  float R[9];  // row-major, p_view[j] = sum_i p[i] R[i][j] + T[j]
-  float T[3];
-  float tan_half_fov;
-};
+constexpr int GB_REC = 18;  // floats per face record: per corner (sum w_k gN [3], g position [3])
 
 struct GbArgs {
   const float* verts;
@@ -56,15 +48,9 @@ struct GbArgs {
   const float* gN;       // [S S][3] or NULL
   const float* gX;       // [S S][3] or NULL
   float* rec;            // [F][GB_REC]
-  GbCamera cam;
+  Camera cam;
   int V, F, S;
 };
-
-DEV float gb_edge(float px, float py, float ax, float ay, float bx, float by) {  // EdgeFunctionForward(p, a, b)
-  return (px - ax) * (by - ay) - (py - ay) * (bx - ax);
-}
-
-DEV float gb_pix_ndc(int i, int S) { return -1.f + (2.f * (float)i + 1.f) / (float)S; }
 
 DEV float gb_wave_sum(float s) {  // all 64 lanes, one fixed order
 #pragma unroll
@@ -79,37 +65,21 @@ __global__ void __launch_bounds__(256) k_gb_face(const GbArgs a) {
   if (f >= a.F) return;  // wave-uniform
   float* out = a.rec + (size_t)f * GB_REC;
   const int64_t P = (int64_t)a.S * a.S;
-  float x[3] = {0.f, 0.f, 0.f}, y[3] = {0.f, 0.f, 0.f}, z[3] = {0.f, 0.f, 0.f};
-  float n[3][3], p[3][3];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int64_t i = a.faces[3 * (size_t)f + k];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) n[k][d] = p[k][d] = 0.f;
-    if (i < 0 || i >= a.V) { ok = false; continue; }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      p[k][d] = a.verts[3 * i + d];
-      n[k][d] = a.vnrm[3 * i + d];
-    }
-    const float vx = p[k][0] * a.cam.R[0] + p[k][1] * a.cam.R[3] + p[k][2] * a.cam.R[6] + a.cam.T[0];
-    const float vy = p[k][0] * a.cam.R[1] + p[k][1] * a.cam.R[4] + p[k][2] * a.cam.R[7] + a.cam.T[1];
-    const float vz = p[k][0] * a.cam.R[2] + p[k][1] * a.cam.R[5] + p[k][2] * a.cam.R[8] + a.cam.T[2];
-    const float w = vz * a.cam.tan_half_fov;
-    x[k] = vx / w;
-    y[k] = vy / w;
-    z[k] = vz;
-  }
-  const float area = gb_edge(x[0], y[0], x[1], y[1], x[2], y[2]);
-  const float zmax = fmaxf(z[0], fmaxf(z[1], z[2]));
-  ok = ok && !(zmax < 0.f) && !(fabsf(area) <= GB_EPS);  // k_face_setup's rule: a skipped face has no pixel
+  float x[3], y[3], z[3], area;
+  const bool ok = mesh_face(a.cam, a.V, a.verts, a.faces, (size_t)f, x, y, z, area);  // k_face_setup's corners and its rule
   const int64_t b = min(max(a.foff[f], (int64_t)0), P), e = min(max(a.foff[f + 1], b), P);
-  if (!ok || b == e) {
+  if (!ok || b == e) {  // a skipped face has no pixel
     if (lane < GB_REC) out[lane] = 0.f;
     return;
   }
-  const float A = gb_edge(x[2], y[2], x[0], y[0], x[1], y[1]) + GB_EPS;
+  float n[3][3], p[3][3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int64_t i = a.faces[3 * (size_t)f + k];  // in [0, V): ok
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { p[k][d] = a.verts[3 * i + d]; n[k][d] = a.vnrm[3 * i + d]; }
+  }
+  const float A = mesh_bary_area(x[0], y[0], x[1], y[1], x[2], y[2]);
   float wn[3][3], wx[3][3], gx[3], gy[3], sA = 0.f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -121,11 +91,9 @@ __global__ void __launch_bounds__(256) k_gb_face(const GbArgs a) {
     const int64_t pix = a.flist[j];
     if ((uint64_t)pix >= (uint64_t)P || a.p2f[pix] != f) continue;  // a malformed list entry adds nothing
     const int r = (int)(pix / a.S), c = (int)(pix - (int64_t)r * a.S);
-    const float px = gb_pix_ndc(a.S - 1 - c, a.S), py = gb_pix_ndc(a.S - 1 - r, a.S);
+    const float px = mesh_pix_ndc(a.S - 1 - c, a.S), py = mesh_pix_ndc(a.S - 1 - r, a.S);
     float w[3];
-    w[0] = gb_edge(px, py, x[1], y[1], x[2], y[2]) / A;
-    w[1] = gb_edge(px, py, x[2], y[2], x[0], y[0]) / A;
-    w[2] = gb_edge(px, py, x[0], y[0], x[1], y[1]) / A;
+    mesh_bary(px, py, x[0], y[0], x[1], y[1], x[2], y[2], A, w[0], w[1], w[2]);  // the rasteriser's weights
     float gn[3] = {0.f, 0.f, 0.f}, gp[3] = {0.f, 0.f, 0.f};
     if (a.gN) { gn[0] = a.gN[3 * pix]; gn[1] = a.gN[3 * pix + 1]; gn[2] = a.gN[3 * pix + 2]; }
     if (a.gX) { gp[0] = a.gX[3 * pix]; gp[1] = a.gX[3 * pix + 1]; gp[2] = a.gX[3 * pix + 2]; }
@@ -181,47 +149,12 @@ __global__ void __launch_bounds__(256) k_gb_face(const GbArgs a) {
 }
 
 // ---- vertex normals: u_v, and g u_v from g n_v -------------------------------------------------------------------------
-struct GbMesh {
-  const float* verts;
-  const int64_t* faces;
-  const int64_t* off;
-  const int64_t* corner;
-  int V, F;
-};
-
-DEV bool gb_face_of(const GbMesh& m, int64_t c, int v, int64_t& i0, int64_t& i1, int64_t& i2) {
-  const int64_t n3 = 3 * (int64_t)m.F;
-  if (c < 0 || c >= n3 || m.faces[c] != v) return false;  // a malformed list entry adds nothing
-  const int64_t f = c / 3;
-  i0 = m.faces[3 * f]; i1 = m.faces[3 * f + 1]; i2 = m.faces[3 * f + 2];
-  return !(i0 < 0 || i0 >= m.V || i1 < 0 || i1 >= m.V || i2 < 0 || i2 >= m.V);
-}
-
-DEV void gb_range(const GbMesh& m, int v, int64_t& b, int64_t& e) {
-  const int64_t n3 = 3 * (int64_t)m.F;
-  b = min(max(m.off[v], (int64_t)0), n3);
-  e = min(max(m.off[v + 1], b), n3);
-}
-
-// g u_v of vertex v for its g n_v: u_v summed as k_vertex_normals does, then the Jacobian of u / max(|u|, 1e-6)
+// g u_v of vertex v for its g n_v: mesh_u (k_vertex_normals' sum), then the Jacobian of u / max(|u|, 1e-6)
 DEV void gb_gu(const GbMesh& m, int v, const float gn[3], float gu[3]) {
-  int64_t b, e;
-  gb_range(m, v, b, e);
-  float ux = 0.f, uy = 0.f, uz = 0.f;
-  for (int64_t k = b; k < e; ++k) {
-    int64_t i0, i1, i2;
-    if (!gb_face_of(m, m.corner[k], v, i0, i1, i2)) continue;
-    const float* p0 = m.verts + 3 * i0;
-    const float* p1 = m.verts + 3 * i1;
-    const float* p2 = m.verts + 3 * i2;
-    const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
-    const float bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
-    ux += ay * bz - az * by;
-    uy += az * bx - ax * bz;
-    uz += ax * by - ay * bx;
-  }
+  float ux, uy, uz;
+  mesh_u(m, v, ux, uy, uz);
   const float len = sqrtf(ux * ux + uy * uy + uz * uz);
-  if (len > GB_NRM_EPS) {
+  if (len > MESH_NRM_EPS) {
     const float inv = 1.f / len;
     const float nx = ux * inv, ny = uy * inv, nz = uz * inv;
     const float d = nx * gn[0] + ny * gn[1] + nz * gn[2];
@@ -229,7 +162,7 @@ DEV void gb_gu(const GbMesh& m, int v, const float gn[3], float gu[3]) {
     gu[1] = (gn[1] - ny * d) * inv;
     gu[2] = (gn[2] - nz * d) * inv;
   } else {  // the max branch: n = u 1e6
-    const float s = 1.f / GB_NRM_EPS;
+    const float s = 1.f / MESH_NRM_EPS;
     gu[0] = gn[0] * s; gu[1] = gn[1] * s; gu[2] = gn[2] * s;
   }
 }
@@ -240,12 +173,11 @@ __global__ void __launch_bounds__(256) k_gb_vertex(const GbMesh m, const float* 
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= m.V) return;
   int64_t b, e;
-  gb_range(m, v, b, e);
-  const int64_t n3 = 3 * (int64_t)m.F;
+  mesh_corner_range(m, v, b, e);
   float gn[3] = {0.f, 0.f, 0.f}, gd[3] = {0.f, 0.f, 0.f};
   for (int64_t k = b; k < e; ++k) {
     const int64_t c = m.corner[k];
-    if (c < 0 || c >= n3 || m.faces[c] != v) continue;
+    if (!mesh_corner_names(m, c, v)) continue;
     const int64_t f = c / 3;
     const float* r = rec + (size_t)f * GB_REC + 6 * (int)(c - 3 * f);
     gn[0] += r[0]; gn[1] += r[1]; gn[2] += r[2];
@@ -268,7 +200,7 @@ __global__ void __launch_bounds__(256) k_vn_bwd(const GbMesh m, const float* __r
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= m.V) return;
   int64_t b, e;
-  gb_range(m, v, b, e);
+  mesh_corner_range(m, v, b, e);
   float own[3] = {0.f, 0.f, 0.f};
   if (!STORED && b < e) {
     const float gn[3] = {g[3 * (size_t)v], g[3 * (size_t)v + 1], g[3 * (size_t)v + 2]};
@@ -278,7 +210,7 @@ __global__ void __launch_bounds__(256) k_vn_bwd(const GbMesh m, const float* __r
   for (int64_t k = b; k < e; ++k) {
     const int64_t c = m.corner[k];
     int64_t idx[3];
-    if (!gb_face_of(m, c, v, idx[0], idx[1], idx[2])) continue;
+    if (!mesh_corner_face(m, c, v, idx[0], idx[1], idx[2])) continue;
     float Gx = 0.f, Gy = 0.f, Gz = 0.f;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -310,8 +242,6 @@ __global__ void __launch_bounds__(256) k_vn_bwd(const GbMesh m, const float* __r
 
 namespace {
 
-constexpr int64_t GB_MAX_ELEMS = 0x3fffffff;  // V, F; S * S
-
 size_t gb_rec_bytes(int64_t F) { return ((size_t)F * reni::GB_REC * sizeof(float) + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -321,16 +251,15 @@ extern "C" {
 int reni_mesh_vertex_normals_backward(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int64_t* vf_offsets,
                                       const int64_t* vf_corners, const float* grad_normals, float* grad_verts, void* stream) {
   const char* who = "vertex normals backward";
-  if (V < 1 || F < 1 || V > GB_MAX_ELEMS || F > GB_MAX_ELEMS) return tu_fail(RENI_EINVAL, who, "bad V / F");
+  if (int rc = mesh_check_sizes(who, V, F)) return rc;
   if (!verts || !faces || !vf_offsets || !vf_corners || !grad_normals || !grad_verts) return tu_fail(RENI_EINVAL, who, "NULL argument");
-  reni::GbMesh m;
-  m.verts = verts; m.faces = faces; m.off = vf_offsets; m.corner = vf_corners; m.V = (int)V; m.F = (int)F;
+  const reni::GbMesh m{verts, faces, vf_offsets, vf_corners, (int)V, (int)F};
   return tu_launch(TU_PLAIN, reni::k_vn_bwd<false>, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m,
                    grad_normals, 0, grad_verts);
 }
 
 size_t reni_gbuffer_backward_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W) {
-  if (V < 1 || F < 1 || H < 1 || W < 1 || V > GB_MAX_ELEMS || F > GB_MAX_ELEMS) return 0;
+  if (V < 1 || F < 1 || H < 1 || W < 1 || V > MESH_MAX_ELEMS || F > MESH_MAX_ELEMS) return 0;
   return gb_rec_bytes(F) + (size_t)V * 3 * sizeof(float) + 256;
 }
 
@@ -340,26 +269,23 @@ int reni_gbuffer_backward(int64_t V, int64_t F, const float* verts, const int64_
                           const int64_t* vf_corners, const float* grad_pixel_normals, const float* grad_pixel_positions,
                           float* grad_verts, void* ws, size_t ws_bytes, void* stream) {
   const char* who = "gbuffer backward";
-  if (V < 1 || F < 1 || V > GB_MAX_ELEMS || F > GB_MAX_ELEMS) return tu_fail(RENI_EINVAL, who, "bad V / F");
-  if (H < 1 || H != W || H * W > GB_MAX_ELEMS) return tu_fail(RENI_EINVAL, who, "the image must be square, H == W >= 1");
+  if (int rc = mesh_check_sizes(who, V, F)) return rc;
+  if (int rc = mesh_check_image(who, H, W)) return rc;
   if (!verts || !faces || !vert_normals || !R || !T || !pix_to_face || !face_pixel_offsets || !face_pixel_list || !vf_offsets ||
       !vf_corners || !grad_verts)
     return tu_fail(RENI_EINVAL, who, "NULL argument");
   if (!grad_pixel_normals && !grad_pixel_positions) return tu_fail(RENI_EINVAL, who, "both upstream gradients are NULL");
-  if (!(tan_half_fov > 0.f) || !isfinite(tan_half_fov)) return tu_fail(RENI_EINVAL, who, "tan_half_fov must be positive");
+  if (int rc = mesh_check_fov(who, tan_half_fov)) return rc;
   if (int rc = tu_check_ws(who, ws, ws_bytes, gb_rec_bytes(F) + (size_t)V * 3 * sizeof(float))) return rc;
   hipStream_t s = (hipStream_t)stream;
   reni::GbArgs a;
   a.verts = verts; a.vnrm = vert_normals; a.faces = faces; a.p2f = pix_to_face; a.foff = face_pixel_offsets;
   a.flist = face_pixel_list; a.gN = grad_pixel_normals; a.gX = grad_pixel_positions;
   a.rec = (float*)ws;
-  for (int i = 0; i < 9; ++i) a.cam.R[i] = R[i];
-  for (int i = 0; i < 3; ++i) a.cam.T[i] = T[i];
-  a.cam.tan_half_fov = tan_half_fov;
+  a.cam = mesh_camera(R, T, tan_half_fov);
   a.V = (int)V; a.F = (int)F; a.S = (int)H;
   if (int rc = tu_launch(TU_PLAIN, reni::k_gb_face, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, a)) return rc;
-  reni::GbMesh m;
-  m.verts = verts; m.faces = faces; m.off = vf_offsets; m.corner = vf_corners; m.V = (int)V; m.F = (int)F;
+  const reni::GbMesh m{verts, faces, vf_offsets, vf_corners, (int)V, (int)F};
   // without an upstream for the normals g n_v is 0 everywhere: the vertex-normal chain adds nothing and is not run
   float* gu = grad_pixel_normals ? (float*)((char*)ws + gb_rec_bytes(F)) : nullptr;
   const dim3 vgrid((unsigned)((V + 255) / 256));

@@ -6,7 +6,7 @@
 // the tap table only, so two calls give identical bits.
 //
 //   k_pixel_uv          one lane per pixel: uv = fmaf(b2, t2, fmaf(b1, t1, b0 t0)) from the rasteriser's own barycentrics, and the
-//                       face's constant d(uv) / d(col, row) from its NDC vertices (k_face_setup's chain: p R + T, x / (z tan)).
+//                       face's constant d(uv) / d(col, row) from its NDC vertices (reni_mesh.inc: mesh_project, mesh_bary_area).
 //   k_texture_taps      one lane per pixel: lambda from the footprint, then the 8 (element index, weight) pairs of the fetch.
 //   k_pyramid_down      one lane per texel of level l + 1: ((a00 + a01) + (a10 + a11)) / 4; where level l is one texel wide or high,
 //                       (a0 + a1) / 2.  One launch per level, in place in the [E][C] buffer.
@@ -27,20 +27,12 @@
 #include "reni_hip.h"
 #include "reni_internal.h"
 #include "reni_tu_host.inc"
-
-#define DEV __device__ __forceinline__
+#include "reni_mesh.inc"
 
 namespace reni {
 
-constexpr float TX_EPS = 1e-8f;  // the rasteriser's kEpsilon (BarycentricCoordsForward)
 constexpr int TX_SHORT = 128;    // the longest tap range one lane walks alone
 constexpr int TX_MAX_LEVELS = 31;
-
-struct TxCamera {
-  float R[9];  // row-major, p_view[j] = sum_i p[i] R[i][j] + T[j]
-  float T[3];
-  float tan_half_fov;
-};
 
 struct PuvArgs {
   const float* verts;      // [V][3]
@@ -52,7 +44,7 @@ struct PuvArgs {
   float* uv;               // [P][2]
   float* jac;              // [P][4]
   int64_t* valid;          // [P] or NULL: the pixel's face, -1 where the pixel is invalid
-  TxCamera cam;
+  Camera cam;
   int V, F, Tn, P;
   float step;  // d NDC / d pixel = -2 / S (NDC +x points left and +y up: both decrease with the column / row)
 };
@@ -76,13 +68,8 @@ __global__ void __launch_bounds__(256) k_pixel_uv(const PuvArgs a) {
     float x[3], y[3], tu[3], tv[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const float px = a.verts[3 * vi[k]], py = a.verts[3 * vi[k] + 1], pz = a.verts[3 * vi[k] + 2];
-      const float vx = px * a.cam.R[0] + py * a.cam.R[3] + pz * a.cam.R[6] + a.cam.T[0];
-      const float vy = px * a.cam.R[1] + py * a.cam.R[4] + pz * a.cam.R[7] + a.cam.T[1];
-      const float vz = px * a.cam.R[2] + py * a.cam.R[5] + pz * a.cam.R[8] + a.cam.T[2];
-      const float w = vz * a.cam.tan_half_fov;
-      x[k] = vx / w;
-      y[k] = vy / w;
+      float z;
+      mesh_project(a.cam, a.verts[3 * vi[k]], a.verts[3 * vi[k] + 1], a.verts[3 * vi[k] + 2], x[k], y[k], z);
       tu[k] = a.vuv[2 * ti[k]];
       tv[k] = a.vuv[2 * ti[k] + 1];
     }
@@ -91,7 +78,7 @@ __global__ void __launch_bounds__(256) k_pixel_uv(const PuvArgs a) {
     v = fmaf(b2, tv[2], fmaf(b1, tv[1], b0 * tv[0]));
     // w0 = edge(p, v1, v2) / A, w1 = edge(p, v2, v0) / A, w2 = edge(p, v0, v1) / A with edge(p, a, b) = (px - ax)(by - ay) - (py - ay)(bx - ax):
     // d w / d px = (by - ay) / A, d w / d py = -(bx - ax) / A
-    const float A = ((x[2] - x[0]) * (y[1] - y[0]) - (y[2] - y[0]) * (x[1] - x[0])) + TX_EPS;  // edge(v2, v0, v1) + eps
+    const float A = mesh_bary_area(x[0], y[0], x[1], y[1], x[2], y[2]);
     const float sx = a.step / A;
     const float wx0 = y[2] - y[1], wx1 = y[0] - y[2], wx2 = y[1] - y[0];
     const float wy0 = x[1] - x[2], wy1 = x[2] - x[0], wy2 = x[0] - x[1];
@@ -385,17 +372,15 @@ int reni_mesh_pixel_uv(int64_t V, int64_t F, int64_t Tn, const float* verts, con
                        const int64_t* faces_uvs, const float* R, const float* T, float tan_half_fov, int64_t S,
                        const int64_t* pix_to_face, const float* bary, float* uv, float* jac, int64_t* pix_valid, void* stream) {
   if (V < 1 || F < 1 || Tn < 1 || S < 1) return reni_set_error(RENI_EINVAL, "pixel uv: V, F, Tn and S must be >= 1");
-  if (V > 0x3fffffff || F > 0x3fffffff || Tn > 0x3fffffff || S * S > TX_MAX_PIXELS)
+  if (V > MESH_MAX_ELEMS || F > MESH_MAX_ELEMS || Tn > MESH_MAX_ELEMS || S * S > TX_MAX_PIXELS)
     return reni_set_error(RENI_EINVAL, "pixel uv: too large: need V, F, Tn < 2^30 and S S < 2^28");
   if (!verts || !faces || !verts_uvs || !faces_uvs || !R || !T || !pix_to_face || !bary || !uv || !jac)
     return reni_set_error(RENI_EINVAL, "pixel uv: NULL argument");
-  if (!(tan_half_fov > 0.f) || !isfinite(tan_half_fov)) return reni_set_error(RENI_EINVAL, "pixel uv: tan_half_fov must be positive");
+  if (int rc = mesh_check_fov("pixel uv", tan_half_fov)) return rc;
   reni::PuvArgs a = {};
   a.verts = verts; a.faces = faces; a.vuv = verts_uvs; a.fuv = faces_uvs; a.p2f = pix_to_face; a.bary = bary;
   a.uv = uv; a.jac = jac; a.valid = pix_valid;
-  for (int i = 0; i < 9; ++i) a.cam.R[i] = R[i];
-  for (int i = 0; i < 3; ++i) a.cam.T[i] = T[i];
-  a.cam.tan_half_fov = tan_half_fov;
+  a.cam = mesh_camera(R, T, tan_half_fov);
   a.V = (int)V; a.F = (int)F; a.Tn = (int)Tn; a.P = (int)(S * S);
   a.step = -2.f / (float)S;
   return tu_launch(TU_PLAIN, reni::k_pixel_uv, dim3((unsigned)((S * S + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);

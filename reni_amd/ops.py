@@ -743,17 +743,38 @@ def _vertex_face_csr(faces: torch.Tensor, V: int):
     return offsets.contiguous(), corners[order].contiguous()
 
 
+def _mesh_shapes(verts, faces, a_tensor="a tensor "):
+    """The shape rules of a mesh.  Asked first by the callers whose bad shape is a ValueError before any device is looked at
+    (anything may arrive: the message says "a tensor"), and by ``_mesh_inputs`` on the cast tensors (``a_tensor=""``)."""
+    for name, t, n in (("verts", verts, "V"), ("faces", faces, "F")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError(f"{name} must be {a_tensor}[{n}, 3] with {n} >= 1, got {tuple(getattr(t, 'shape', ()))}")
+
+
 def _mesh_inputs(verts, faces):
     _require_cuda(verts, faces)
     verts = verts.to(torch.float32).contiguous()
     faces = faces.to(torch.int64).contiguous()
-    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
-        raise ValueError(f"verts must be [V, 3] with V >= 1, got {tuple(verts.shape)}")
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-        raise ValueError(f"faces must be [F, 3] with F >= 1, got {tuple(faces.shape)}")
+    _mesh_shapes(verts, faces, "")
     if faces.device != verts.device:
         raise ValueError("verts and faces must be on the same device")
     return verts, faces
+
+
+def _image_size(image_size) -> int:
+    S = int(image_size)
+    if S < 1:
+        raise ValueError("image_size must be >= 1")
+    return S
+
+
+def _camera_arrays(R, T):
+    """R ([1,3,3] or [3,3]) and T ([1,3] or [3]) as the C ABI's float[9] and float[3]."""
+    Rv = [float(x) for x in torch.as_tensor(R).reshape(-1).tolist()]
+    Tv = [float(x) for x in torch.as_tensor(T).reshape(-1).tolist()]
+    if len(Rv) != 9 or len(Tv) != 3:
+        raise ValueError("R must hold 9 values ([1,3,3] or [3,3]) and T 3 ([1,3] or [3])")
+    return (ctypes.c_float * 9)(*Rv), (ctypes.c_float * 3)(*Tv)
 
 
 def vertex_normals(verts: torch.Tensor, faces: torch.Tensor, vf=None) -> torch.Tensor:
@@ -781,14 +802,8 @@ def rasterize_mesh(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch
     vert_normals = vert_normals.to(torch.float32).contiguous()
     if tuple(vert_normals.shape) != tuple(verts.shape):
         raise ValueError("vert_normals must be [V, 3] like verts")
-    S = int(image_size)
-    if S < 1:
-        raise ValueError("image_size must be >= 1")
-    Rv = [float(x) for x in torch.as_tensor(R).reshape(-1).tolist()]
-    Tv = [float(x) for x in torch.as_tensor(T).reshape(-1).tolist()]
-    if len(Rv) != 9 or len(Tv) != 3:
-        raise ValueError("R must hold 9 values ([1,3,3] or [3,3]) and T 3 ([1,3] or [3])")
-    Rh, Th = (ctypes.c_float * 9)(*Rv), (ctypes.c_float * 3)(*Tv)
+    S = _image_size(image_size)
+    Rh, Th = _camera_arrays(R, T)
     lib = _lib.load()
     V, F = verts.shape[0], faces.shape[0]
     dev = verts.device
@@ -802,14 +817,6 @@ def rasterize_mesh(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch
     _call(lib.reni_rasterize_mesh, dev, V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th, float(tan_half_fov),
           S, S, p2f.data_ptr(), zbuf.data_ptr(), bary.data_ptr(), dists.data_ptr(), nrm.data_ptr(), pos.data_ptr(), wp, wn)
     return p2f, zbuf, bary, dists, nrm, pos
-
-
-def _mesh_shapes(verts, faces):
-    """The shape rules of ``_mesh_inputs``, asked first: a bad shape is a ValueError before any device is looked at."""
-    if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
-        raise ValueError(f"verts must be a tensor [V, 3] with V >= 1, got {tuple(getattr(verts, 'shape', ()))}")
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-        raise ValueError(f"faces must be a tensor [F, 3] with F >= 1, got {tuple(getattr(faces, 'shape', ()))}")
 
 
 def vertex_face_lists(faces: torch.Tensor, V: int):
@@ -872,9 +879,7 @@ def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: tor
     gradient ([S*S, 3]) may be None, not both.  ``table``: ``face_pixel_table(pix_to_face, F)``, ``vf``: ``vertex_face_lists(faces, V)``, when the caller keeps them.
     Deterministic, no atomics; no silhouette / occlusion gradient, the camera is a constant."""
     _mesh_shapes(verts, faces)
-    S = int(image_size)
-    if S < 1:
-        raise ValueError("image_size must be >= 1")
+    S = _image_size(image_size)
     if not isinstance(vert_normals, torch.Tensor) or tuple(vert_normals.shape) != tuple(verts.shape):
         raise ValueError("vert_normals must be [V, 3] like verts")
     if not isinstance(pix_to_face, torch.Tensor) or pix_to_face.dtype != torch.int64 or pix_to_face.numel() != S * S:
@@ -884,10 +889,7 @@ def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: tor
     for name, g in (("grad_pixel_normals", grad_pixel_normals), ("grad_pixel_positions", grad_pixel_positions)):
         if g is not None and (not isinstance(g, torch.Tensor) or tuple(g.shape) != (S * S, 3)):
             raise ValueError(f"{name} must be [{S * S}, 3] or None, got {tuple(getattr(g, 'shape', ()))}")
-    Rv = [float(x) for x in torch.as_tensor(R).reshape(-1).tolist()]
-    Tv = [float(x) for x in torch.as_tensor(T).reshape(-1).tolist()]
-    if len(Rv) != 9 or len(Tv) != 3:
-        raise ValueError("R must hold 9 values ([1,3,3] or [3,3]) and T 3 ([1,3] or [3])")
+    Rh, Th = _camera_arrays(R, T)
     verts, faces = _mesh_inputs(verts, faces)
     _require_cuda(vert_normals, pix_to_face, grad_pixel_normals, grad_pixel_positions)
     dev = verts.device
@@ -903,7 +905,6 @@ def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: tor
             or foff.device != dev or flist.device != dev):
         raise ValueError(f"the table is not one of {S * S} pixels over {F} faces on {dev}")
     offsets, corners = _vf_lists(faces, V, vf)
-    Rh, Th = (ctypes.c_float * 9)(*Rv), (ctypes.c_float * 3)(*Tv)
     lib = _lib.load()
     out = torch.empty(V, 3, dtype=torch.float32, device=dev)
     ws, wp, wn = _ws256(int(lib.reni_gbuffer_backward_workspace_bytes(V, F, S, S)), dev)
@@ -1406,20 +1407,14 @@ def mesh_pixel_uv(verts, faces, verts_uvs, faces_uvs, R, T, image_size: int, pix
         raise ValueError(f"verts_uvs must be [Tn, 2] with Tn >= 1, got {tuple(verts_uvs.shape)}")
     if tuple(faces_uvs.shape) != tuple(faces.shape):
         raise ValueError(f"faces_uvs must be [F, 3] like faces, got {tuple(faces_uvs.shape)}")
-    S = int(image_size)
-    if S < 1:
-        raise ValueError("image_size must be >= 1")
+    S = _image_size(image_size)
     p2f = pix_to_face.to(torch.int64).contiguous()
     bary = bary.to(torch.float32).contiguous()
     if p2f.numel() != S * S or bary.numel() != 3 * S * S:
         raise ValueError(f"pix_to_face and bary must hold {S * S} pixels (and 3 barycentrics each)")
     if any(t.device != dev for t in (verts_uvs, faces_uvs, p2f, bary)):
         raise ValueError("the mesh, its UVs and the G-buffer must be on the same device")
-    Rv = [float(x) for x in torch.as_tensor(R).reshape(-1).tolist()]
-    Tv = [float(x) for x in torch.as_tensor(T).reshape(-1).tolist()]
-    if len(Rv) != 9 or len(Tv) != 3:
-        raise ValueError("R must hold 9 values ([1,3,3] or [3,3]) and T 3 ([1,3] or [3])")
-    Rh, Th = (ctypes.c_float * 9)(*Rv), (ctypes.c_float * 3)(*Tv)
+    Rh, Th = _camera_arrays(R, T)
     uv = torch.empty(S * S, 2, dtype=torch.float32, device=dev)
     jac = torch.empty(S * S, 4, dtype=torch.float32, device=dev)
     valid = torch.empty(S * S, dtype=torch.int64, device=dev)

@@ -171,8 +171,9 @@ def test_c_abi_rejects_bad_sizes_null_pointers_and_short_workspaces():
 
 
 def test_raster_backward_unit_has_no_float_atomics():
-    src = open(os.path.join(ROOT, "reni_amd", "csrc", "reni_tu_raster_bwd.hip")).read()
-    assert "atomic" not in src.replace("no float atomic", "")
+    for name in ("reni_tu_raster_bwd.hip", "reni_mesh.inc"):  # the unit and the header its projection and list walks live in
+        src = open(os.path.join(ROOT, "reni_amd", "csrc", name)).read()
+        assert "atomic" not in src.replace("no float atomic", "")
 
 
 def test_raster_backward_translation_unit_isa_audit():

@@ -18,6 +18,7 @@ from tests import normal_map_ref as NR
 from tests import shade_materials_ref as MR
 from tests import texture_ref as TR
 from tests import visibility_ref as VR
+from tests.util import uv_sphere
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -170,34 +171,10 @@ def test_shade_terms_normals_is_shade_terms_plus_the_normals_gradient(monkeypatc
 
 
 # ------------------------------------------------------------------------------------------------- renderer
-def _uv_sphere(n_lon=16, n_lat=8, radius=1.0):
-    """tests/test_gpu_texture.py's latitude / longitude sphere: the seam column is duplicated in UV space only."""
-    verts, uvs = [], []
-    for j in range(n_lat + 1):
-        th = math.pi * j / n_lat
-        for i in range(n_lon + 1):
-            ph = 2 * math.pi * i / n_lon
-            if i < n_lon:
-                verts.append([radius * math.sin(th) * math.sin(ph), radius * math.cos(th), radius * math.sin(th) * math.cos(ph)])
-            uvs.append([i / n_lon, 1.0 - j / n_lat])
-    faces, fuv = [], []
-    for j in range(n_lat):
-        for i in range(n_lon):
-            a, b = j * n_lon + i, j * n_lon + (i + 1) % n_lon
-            c, d = a + n_lon, b + n_lon
-            ta, tb = j * (n_lon + 1) + i, j * (n_lon + 1) + i + 1
-            tc, td = ta + n_lon + 1, tb + n_lon + 1
-            if j > 0:
-                faces.append([a, c, b]); fuv.append([ta, tc, tb])
-            if j < n_lat - 1:
-                faces.append([b, c, d]); fuv.append([tb, tc, td])
-    return (torch.tensor(verts, dtype=torch.float32), torch.tensor(faces), torch.tensor(uvs, dtype=torch.float32), torch.tensor(fuv))
-
-
 @functools.lru_cache(maxsize=None)
 def _sphere_mesh():
     from reni_amd.mesh import Meshes
-    parts = _uv_sphere()
+    parts = uv_sphere()
     v, f, vt, ft = (t.to(DEV) for t in parts)
     return Meshes(verts=[v], faces=[f], verts_uvs=[vt], faces_uvs=[ft]), parts
 

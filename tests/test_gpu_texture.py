@@ -7,7 +7,6 @@ transpose of the bounds (texture_ref.grad_bound / level0_grad_bound); a texel th
 it either, has bound 0 and its gradient must be exactly 0.  K and K' are four times the worst ratio the fp32 numpy emulation
 reaches over these very cases (texture_ref.emulation_constants; the margin is for FMA contraction and the device's log2)."""
 import functools
-import math
 import os
 
 import pytest
@@ -15,6 +14,7 @@ import torch
 
 from tests import shade_materials_ref as MR
 from tests import texture_ref as TR
+from tests.util import uv_sphere
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -197,31 +197,6 @@ def test_malformed_table_and_indices_stay_inside_guard_bands():
 
 
 # ------------------------------------------------------------------------------------------------- meshes
-def _uv_sphere(n_lon=16, n_lat=8, radius=1.0):
-    """A latitude / longitude sphere whose seam column is duplicated in UV space only: V = n_lon (n_lat + 1) positions,
-    Tn = (n_lon + 1)(n_lat + 1) texture coordinates."""
-    verts, uvs = [], []
-    for j in range(n_lat + 1):
-        th = math.pi * j / n_lat
-        for i in range(n_lon + 1):
-            ph = 2 * math.pi * i / n_lon
-            if i < n_lon:
-                verts.append([radius * math.sin(th) * math.sin(ph), radius * math.cos(th), radius * math.sin(th) * math.cos(ph)])
-            uvs.append([i / n_lon, 1.0 - j / n_lat])
-    faces, fuv = [], []
-    for j in range(n_lat):
-        for i in range(n_lon):
-            a, b = j * n_lon + i, j * n_lon + (i + 1) % n_lon
-            c, d = a + n_lon, b + n_lon
-            ta, tb = j * (n_lon + 1) + i, j * (n_lon + 1) + i + 1
-            tc, td = ta + n_lon + 1, tb + n_lon + 1
-            if j > 0:
-                faces.append([a, c, b]); fuv.append([ta, tc, tb])
-            if j < n_lat - 1:
-                faces.append([b, c, d]); fuv.append([tb, tc, td])
-    return (torch.tensor(verts, dtype=torch.float32), torch.tensor(faces), torch.tensor(uvs, dtype=torch.float32), torch.tensor(fuv))
-
-
 def _quad():
     verts = torch.tensor([[-0.9, -0.7, 0.1], [0.8, -0.6, -0.2], [0.7, 0.9, 0.0], [-0.8, 0.6, 0.3]])
     faces = torch.tensor([[0, 1, 2], [0, 2, 3]])
@@ -240,7 +215,7 @@ def _mesh(parts):
 @pytest.mark.parametrize("which", ["sphere", "quad", "sphere_missing"])
 def test_pixel_uv_and_jacobian_match_float64(S, which):
     from reni_amd.mesh import FoVPerspectiveCameras, MeshRasterizer, RasterizationSettings, look_at_view_transform
-    parts = _quad() if which == "quad" else _uv_sphere()
+    parts = _quad() if which == "quad" else uv_sphere()
     if which == "sphere_missing":   # every third face loses a texture coordinate, one keeps an index past Tn
         ft = parts[3].clone()
         ft[::3, 1] = -1
@@ -322,7 +297,7 @@ _MESH = [None, None]
 
 def _sphere_mesh():
     if _MESH[0] is None:
-        _MESH[1] = _uv_sphere()
+        _MESH[1] = uv_sphere()
         _MESH[0] = _mesh(_MESH[1])
     return _MESH
 

@@ -1,4 +1,5 @@
 """Shared helpers for the GPU parity tests (oracle = checker only)."""
+import math
 import os
 
 import numpy as np
@@ -52,3 +53,28 @@ def random_problem(spec: O.DecoderSpec, B, P, seed=0, per_image_dirs=False, grid
         W = torch.rand(1, P, 3, generator=g)
     T = torch.rand(B, P, 3, generator=g) * 2 - 1
     return params, Z, D, W, T
+
+
+def uv_sphere(n_lon=16, n_lat=8, radius=1.0):
+    """A latitude / longitude sphere whose seam column is duplicated in UV space only: V = n_lon (n_lat + 1) positions,
+    Tn = (n_lon + 1)(n_lat + 1) texture coordinates."""
+    verts, uvs = [], []
+    for j in range(n_lat + 1):
+        th = math.pi * j / n_lat
+        for i in range(n_lon + 1):
+            ph = 2 * math.pi * i / n_lon
+            if i < n_lon:
+                verts.append([radius * math.sin(th) * math.sin(ph), radius * math.cos(th), radius * math.sin(th) * math.cos(ph)])
+            uvs.append([i / n_lon, 1.0 - j / n_lat])
+    faces, fuv = [], []
+    for j in range(n_lat):
+        for i in range(n_lon):
+            a, b = j * n_lon + i, j * n_lon + (i + 1) % n_lon
+            c, d = a + n_lon, b + n_lon
+            ta, tb = j * (n_lon + 1) + i, j * (n_lon + 1) + i + 1
+            tc, td = ta + n_lon + 1, tb + n_lon + 1
+            if j > 0:
+                faces.append([a, c, b]); fuv.append([ta, tc, tb])
+            if j < n_lat - 1:
+                faces.append([b, c, d]); fuv.append([tb, tc, td])
+    return (torch.tensor(verts, dtype=torch.float32), torch.tensor(faces), torch.tensor(uvs, dtype=torch.float32), torch.tensor(fuv))

@@ -114,11 +114,15 @@ def main():
     ap.add_argument("--window", type=float, default=0.5, help="seconds of timed calls per variant, at least")
     ap.add_argument("--chunk", type=int, default=10, help="calls per round")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only", default=None, choices=("query", "fit"), help="one row family")
     a = ap.parse_args()
     dev = torch.device("cuda")
-    variants, sibling = query_variants(dev)
-    lines = measure("chain 8x32x64, 16384 queries, per-query level", variants, sibling, a.chunk, a.window)
-    for S, W in ((64, 128), (64, 256), (128, 128), (128, 256), (256, 256)):  # (the last: where pixels x texels outgrows the chain)
+    lines = []
+    if a.only in (None, "query"):
+        variants, sibling = query_variants(dev)
+        lines += measure("chain 8x32x64, 16384 queries, per-query level", variants, sibling, a.chunk, a.window)
+    shapes = ((64, 128), (64, 256), (128, 128), (128, 256), (256, 256))  # (the last: where pixels x texels outgrows the chain)
+    for S, W in shapes if a.only in (None, "fit") else ():
         variants, sibling = fit_variants(S, W, dev)
         lines += measure(f"teapot {S}x{S} render, {W // 2}x{W} map, B=1", variants, sibling, a.chunk, a.window)
     if a.out:

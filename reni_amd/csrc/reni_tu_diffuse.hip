@@ -11,8 +11,8 @@
 //                       (n, c) columns; the four waves of a workgroup share the columns (their src reads hit the same lines).
 //                       blockIdx.z splits the i range into S chunks, S a function of (P, Q) only (dg_split); with S > 1 the
 //                       partial sums go to the workspace and k_diffuse_reduce adds them in split order.
-//                       Tile constants, result-row map, drain and split rule are reni_sphere.inc's, shared with the lobe
-//                       convolution and its transpose; the body is written out here as it is there.
+//                       Tile constants, result-row map, drain, split rule and the k-step are reni_sphere.inc's, shared with
+//                       the lobe convolution and its transpose; the rest of the body is written out here as it is there.
 //   k_diffuse_reduce    out = ((part_0 + part_1) + part_2) + ...
 //   k_sh_irradiance_l2  shRenderL2 per (map, pixel), the reference's term order and constants, then / pi.
 #include <hip/hip_runtime.h>
@@ -23,7 +23,7 @@
 #include "reni_internal.h"
 #include "reni_tu_host.inc"
 
-#include "reni_sphere.inc"  // tile constants, result-row map, drain, split rule
+#include "reni_sphere.inc"  // tile constants, result-row map, drain, split rule, k-step
 
 namespace reni {
 
@@ -90,15 +90,7 @@ __global__ void __launch_bounds__(256) k_diffuse_convolve(const DfArgs a) {
       const float x = *colp[v];
       b[v] = cok[v] && iok ? x : 0.f;
     }
-#pragma unroll
-    for (int u = 0; u < DG_OT; ++u) {
-      float t = ox[u] * dx;
-      t = fmaf(oy[u], dy, t);
-      t = fmaf(oz[u], dz, t);
-      const float av = fmaxf(t, 0.f) * w;
-#pragma unroll
-      for (int v = 0; v < CT; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[v], acc[u][v], 0, 0, 0);
-    }
+    dg_kstep(ox, oy, oz, dx, dy, dz, w, b, DgCosine(), acc);
   };
   int i0 = ilo;
   for (; i0 + 1 < ihi; i0 += 2) {

@@ -8,7 +8,7 @@
 //
 //   k_lobe_convolve<KIND, CT>  part[s][l][col][o] = sum_(i in chunk s) f_l(o . d_i) (w_i scale) B[i][col], the GEMM of
 //                       k_diffuse_convolve (reni_tu_diffuse.hip: same tiles, same i split, same v_mfma_f32_32x32x2_f32 chain;
-//                       tiles, split, row map and drain are reni_sphere.inc's, the body is written out again)
+//                       tiles, split, row map, drain and the k-step are reni_sphere.inc's)
 //                       with another A generator: t = fma(oz, dz, fma(oy, dy, ox dx)), then the lobe, one straight-line
 //                       generator per KIND with the lobe's parameter a uniform argument.  B's columns are the batch's 3 N
 //                       colour columns and, when the call normalises, ONE column of ones behind them: the denominator
@@ -21,9 +21,9 @@
 //                       forward's own launch, so the bits the forward divided by), for the transpose in
 //                       reni_tu_glossy_bwd.hip.
 //   k_envmap_lookup     out[n][p][c] = the bilinear sample of src[n][level][.][.][c] at direction dirs[p] (or dirs[n][p]),
-//                       mixed linearly between floor(level) and the next level.  Direction -> (row, col) and the level are
-//                       reni_sphere.inc's (sph_rowcol, sph_level), the functions k_rotate_envmap and k_envmap_lookup_taps
-//                       call; the four taps are k_rotate_envmap's, written out again.  One lane per direction computes the
+//                       mixed linearly between floor(level) and the next level.  Direction -> (row, col), the four taps and
+//                       the level are reni_sphere.inc's (sph_rowcol, sph_taps, sph_level), the functions k_rotate_envmap,
+//                       k_envmap_lookup_taps and k_envmap_lookup_dquery call.  One lane per direction computes the
 //                       coordinate once and serves the channels and both levels with it.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -35,7 +35,7 @@
 
 #pragma clang fp contract(off)
 
-#include "reni_sphere.inc"  // tiles, lobes, drain, split rule, (row, col) and level: shared with reni_tu_glossy_bwd.hip
+#include "reni_sphere.inc"  // GEMM pieces, lobes, split rule, (row, col), taps, level, query: shared with reni_tu_glossy_bwd.hip
 
 namespace reni {
 
@@ -61,7 +61,7 @@ template <int KIND, int CT>
 __global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hi = lane >> 5;
   const int ll = (int)blockIdx.z / a.S, sp = (int)blockIdx.z - ll * a.S;  // lobe of this launch, split
-  const float par = a.par[ll];
+  const DgLobe<KIND> lobe = {a.par[ll]};
   const int64_t o0 = (int64_t)blockIdx.x * DG_ROWS + wave * (32 * DG_OT);
   float ox[DG_OT], oy[DG_OT], oz[DG_OT];
 #pragma unroll
@@ -111,15 +111,7 @@ __global__ void __launch_bounds__(256) k_lobe_convolve(const LbArgs a) {
       const float x = *colp[v];
       b[v] = iok ? (img[v] ? x : fill[v]) : 0.f;  // (every lane loads: map 0 where there is no map, the value dropped)
     }
-#pragma unroll
-    for (int u = 0; u < DG_OT; ++u) {
-      float t = ox[u] * dx;
-      t = fmaf(oy[u], dy, t);
-      t = fmaf(oz[u], dz, t);
-      const float av = lb_lobe<KIND>(t, par) * w;
-#pragma unroll
-      for (int v = 0; v < CT; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[v], acc[u][v], 0, 0, 0);
-    }
+    dg_kstep(ox, oy, oz, dx, dy, dz, w, b, lobe, acc);
   };
   int i0 = ilo;
   for (; i0 + 1 < ihi; i0 += 2) {
@@ -194,18 +186,8 @@ __global__ void __launch_bounds__(256) k_lobe_den_finish(const float* __restrict
   den[e] = x;
 }
 
-struct LkArgs {
-  const float* src;  // element (n, level, y, x, c) at n sn + level sl + y sy + x sx + c sc
-  int64_t sn, sl, sc;
-  int sy, sx;  // (< 2^31, checked, as in reni_rotate_envmap)
-  const float* dirs;  // direction p of map n at dirs + n dn + 3 p
-  int64_t dn;
-  const float* level;  // NULL: level_const for every direction; else level[n ln + p]
-  int64_t ln;
-  float level_const;
+struct LkArgs : SphQuery {
   float* out;  // [N][P][3]
-  int Lv, H, W, P;
-  float row_scale, col_scale, col_bias;  // fp32(H / pi), fp32(W / 2 pi), W/2 - 1/2
 };
 
 __global__ void __launch_bounds__(256) k_envmap_lookup(const LkArgs a) {
@@ -214,28 +196,13 @@ __global__ void __launch_bounds__(256) k_envmap_lookup(const LkArgs a) {
   const int64_t n = blockIdx.y;
   const float* d = a.dirs + n * a.dn + 3 * (int64_t)p;
   const float sx = d[0], sy = d[1], sz = d[2];
-  // ---- k_rotate_envmap's four taps (written out again: see the header)
   float row, col;
   sph_rowcol(sx, sy, sz, a.H, a.W, a.row_scale, a.col_scale, a.col_bias, row, col);
-  const float fi = floorf(row), fj = floorf(col);
-  const int i = (int)fi, j = (int)fj;
-  const float fr = row - fi, fc = col - fj;
-  const float gr = 1.f - fr, gc = 1.f - fc;
-  const int half = a.W >> 1;
-  int i0 = i, i1 = i + 1;
-  const bool x0 = i0 < 0 || i0 >= a.H, x1 = i1 >= a.H;  // beyond a pole: the far side
-  if (i0 < 0) i0 = -1 - i0;
-  if (i0 >= a.H) i0 = 2 * a.H - 1 - i0;
-  if (i1 >= a.H) i1 = 2 * a.H - 1 - i1;
-  i0 = min(max(i0, 0), a.H - 1);
-  i1 = min(max(i1, 0), a.H - 1);
-  int j0 = j < 0 ? j + a.W : (j >= a.W ? j - a.W : j);
-  int j1 = j + 1 >= a.W ? j + 1 - a.W : j + 1;
-  if (j1 >= a.W) j1 -= a.W;
-  const int j0f = j0 + half >= a.W ? j0 - half : j0 + half, j1f = j1 + half >= a.W ? j1 - half : j1 + half;
-  const int64_t r0 = (int64_t)i0 * (int64_t)a.sy, r1 = (int64_t)i1 * (int64_t)a.sy;
-  const int64_t o00 = r0 + (int64_t)(x0 ? j0f : j0) * (int64_t)a.sx, o01 = r0 + (int64_t)(x0 ? j1f : j1) * (int64_t)a.sx;
-  const int64_t o10 = r1 + (int64_t)(x1 ? j0f : j0) * (int64_t)a.sx, o11 = r1 + (int64_t)(x1 ? j1f : j1) * (int64_t)a.sx;
+  const SphTaps t = sph_taps(row, col, a.H, a.W);
+  const float fr = t.fr, gr = t.gr, fc = t.fc, gc = t.gc;
+  const int64_t r0 = (int64_t)t.i0 * (int64_t)a.sy, r1 = (int64_t)t.i1 * (int64_t)a.sy;
+  const int64_t o00 = r0 + (int64_t)t.j00 * (int64_t)a.sx, o01 = r0 + (int64_t)t.j01 * (int64_t)a.sx;
+  const int64_t o10 = r1 + (int64_t)t.j10 * (int64_t)a.sx, o11 = r1 + (int64_t)t.j11 * (int64_t)a.sx;
   // ---- the level: clamped to [0, Lv - 1] (fmaxf drops a NaN), one more lerp in the same fma order
   const SphLevel L = sph_level(a.level ? a.level[n * a.ln + p] : a.level_const, a.Lv);
   const int l0 = L.l0, l1 = L.l1;
@@ -278,21 +245,11 @@ int lb_launch(TuCount count, const reni::LbArgs& a, hipStream_t s) {
 
 // one launch per kind present, its lobes along z; counted or not as the caller's other launches are
 int lb_launch_kinds(TuCount count, reni::LbArgs& a, int n_lobes, const int32_t* kinds, const float* params, hipStream_t s) {
-  for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind) {
-    a.nl = 0;
-    for (int l = 0; l < n_lobes; ++l) {
-      if (kinds[l] != kind) continue;
-      a.lobe[a.nl] = l;
-      a.par[a.nl] = lb_kernel_param(kind, params[l]);
-      ++a.nl;
-    }
-    if (!a.nl) continue;
-    const int rc = kind == RENI_LOBE_PHONG   ? lb_launch<RENI_LOBE_PHONG>(count, a, s)
-                   : kind == RENI_LOBE_BLINN ? lb_launch<RENI_LOBE_BLINN>(count, a, s)
-                                             : lb_launch<RENI_LOBE_GGX>(count, a, s);
-    if (rc) return rc;
-  }
-  return RENI_OK;
+  return lb_for_kinds(a, n_lobes, kinds, params, [&](int kind, const reni::LbArgs& a) {
+    return kind == RENI_LOBE_PHONG   ? lb_launch<RENI_LOBE_PHONG>(count, a, s)
+           : kind == RENI_LOBE_BLINN ? lb_launch<RENI_LOBE_BLINN>(count, a, s)
+                                     : lb_launch<RENI_LOBE_GGX>(count, a, s);
+  });
 }
 
 bool lb_den_shape_ok(int64_t P, int64_t Q, int64_t Lv) {
@@ -377,25 +334,11 @@ int reni_lobe_denominators(int64_t P, int64_t Q, const float* out_dirs, const fl
 int reni_envmap_lookup(int64_t N, int64_t Lv, int64_t H, int64_t W, int64_t P, const float* src, const int64_t src_strides[5],
                        const float* dirs, int64_t dirs_stride_n, const float* level, int64_t level_stride_n, float level_const,
                        float* out, void* stream) {
-  if (N < 1 || Lv < 1 || H < 1 || W < 1 || P < 1) return reni_set_error(RENI_EINVAL, "lookup: sizes must be >= 1");
-  if (W & 1) return reni_set_error(RENI_EINVAL, "lookup: W must be even (the far side of a pole is W / 2 columns away)");
-  if (N > 65535 || Lv > 65535 || H > 0x3fffffff / W || P > 0x3fffffff / 3 || N > 0x3fffffff / (3 * P))
-    return reni_set_error(RENI_EINVAL, "lookup: need N, Lv <= 65535, H W < 2^30 and N P < 2^28");
-  if (!src || !src_strides || !dirs || !out) return reni_set_error(RENI_EINVAL, "lookup: NULL argument");
-  if (int rc = tu_check_strides("lookup", "src strides", src_strides, 5)) return rc;
-  if (src_strides[2] > 0x7fffffff || src_strides[3] > 0x7fffffff)
-    return reni_set_error(RENI_EINVAL, "lookup: the row and column strides must be < 2^31 elements");
-  if (dirs_stride_n != 0 && dirs_stride_n != 3 * P)
-    return reni_set_error(RENI_EINVAL, "lookup: dirs_stride_n must be 0 (shared) or 3 P (per map)");
-  if (level && level_stride_n != 0 && level_stride_n != P)
-    return reni_set_error(RENI_EINVAL, "lookup: level_stride_n must be 0 (shared) or P (per map)");
+  if (int rc = sph_check_query(true, N, Lv, H, W, P, src, src_strides, dirs, dirs_stride_n, level, level_stride_n, out != nullptr))
+    return rc;
   reni::LkArgs a = {};
-  a.src = src; a.sn = src_strides[0]; a.sl = src_strides[1]; a.sy = (int)src_strides[2]; a.sx = (int)src_strides[3];
-  a.sc = src_strides[4];
-  a.dirs = dirs; a.dn = dirs_stride_n; a.level = level; a.ln = level ? level_stride_n : 0; a.level_const = level_const;
+  sph_fill_query(a, N, Lv, H, W, P, src, src_strides, dirs, dirs_stride_n, level, level_stride_n, level_const);
   a.out = out;
-  a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
-  sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
   return tu_launch(TU_PLAIN, reni::k_envmap_lookup, dim3((unsigned)((P + 255) / 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream, a);
 }
 

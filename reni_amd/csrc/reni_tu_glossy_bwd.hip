@@ -9,17 +9,17 @@
 //   k_lobe_convolve_t<KIND, CT>  part[s][col][i] = sum_(l of KIND) sum_(o in chunk s) f_l(o . d_i) r[l][o] g[o][col of lobe l]:
 //                       k_lobe_convolve with the roles swapped.  Rows are the Q texels (the same 32-row tiles, DG_OT a
 //                       wave, 4 waves), the reduction runs over o, two a step with lanes 32..63 feeding k = 1, and t is
-//                       built in the forward's order (ox dx, then two fma), so both directions use one kernel matrix up to
-//                       the lobe's rounding.  r sits where the forward has w_i, a per-k scalar.  The lobes of a kind are
-//                       looped INSIDE the workgroup into the same accumulators; the o range is split by the forward's rule
-//                       with P and Q exchanged.
+//                       built in the order of the forwards' k-step (dg_kstep of reni_sphere.inc: ox dx, then two fma; here
+//                       a copy with the roles exchanged), so both directions use one kernel matrix up to the lobe's rounding.  r sits where the forward has w_i, a per-k scalar.  The lobes of a
+//                       kind are looped INSIDE the workgroup into the same accumulators; the o range is split by the
+//                       forward's rule with P and Q exchanged.
 //   k_lobe_finish_t     dsrc(n, i, c) = w_i ((slab_0 + slab_1) + ...) of column 3 n + c over the (kind, split) slabs in that
 //                       order, written through element strides: every element is written.
 //   k_envmap_lookup_taps  per direction the 8 texels k_envmap_lookup reads (4 on floor(level), 4 on the next level) as
 //                       element indices level H W + y W + x, and their effective weights {gr gc, gr fc, fr gc, fr fc} x
-//                       {gl, fl}; the second level weighs 0 unless fl > 0, as the forward reads it only then.  (row, col)
-//                       and the level come from the functions k_envmap_lookup calls (sph_rowcol, sph_level); the four taps
-//                       are k_envmap_lookup's, written out again.
+//                       {gl, fl}; the second level weighs 0 unless fl > 0, as the forward reads it only then.  (row, col),
+//                       the four taps and the level come from the functions k_envmap_lookup calls (sph_rowcol, sph_taps,
+//                       sph_level).
 //   k_envmap_lookup_bwd one lane per (map, element): the sum of weight x upstream over the element's taps, in the order a
 //                       stable sort of the indices left them -- the scatter as a gather (as reni_mesh_vertex_normals does
 //                       with the faces of a vertex).  A texel sampled by very many directions is summed by ONE lane.
@@ -33,7 +33,7 @@
 
 #pragma clang fp contract(off)
 
-#include "reni_sphere.inc"  // tiles, lobes, drains, split rule, (row, col) and level: shared with reni_tu_glossy.hip
+#include "reni_sphere.inc"  // GEMM pieces, lobes, split rule, (row, col), taps, level, query: shared with reni_tu_glossy.hip
 
 namespace reni {
 
@@ -118,6 +118,8 @@ __global__ void __launch_bounds__(256) k_lobe_convolve_t(const LbtArgs a) {
         const float x = *bp[v];
         b[v] = ook && cok[v] ? x : 0.f;
       }
+      // (dg_kstep of reni_sphere.inc with rows and k-side exchanged, as a copy: the shared call moved eight lines of the listing
+      // and was not at or below the previous library's times in every row, profiles/sphere_body_refactor.md)
 #pragma unroll
       for (int u = 0; u < DG_OT; ++u) {
         float t = ox * dx[u];
@@ -179,16 +181,9 @@ __global__ void __launch_bounds__(256) k_lobe_finish_t(const float* __restrict__
   }
 }
 
-struct LtArgs {
-  const float* dirs;  // direction p of table t at dirs + t dn + 3 p
-  int64_t dn;
-  const float* level;  // NULL: level_const for every direction; else level[t ln + p]
-  int64_t ln;
-  float level_const;
+struct LtArgs : SphQuery {  // (no source: the maps of the query are its T tables)
   int32_t* idx;  // [T][P][8]
   float* wgt;    // [T][P][8]
-  int Lv, H, W, P;
-  float row_scale, col_scale, col_bias;  // fp32(H / pi), fp32(W / 2 pi), W/2 - 1/2
 };
 
 __global__ void __launch_bounds__(256) k_envmap_lookup_taps(const LtArgs a) {
@@ -197,29 +192,12 @@ __global__ void __launch_bounds__(256) k_envmap_lookup_taps(const LtArgs a) {
   const int64_t n = blockIdx.y;
   const float* d = a.dirs + n * a.dn + 3 * (int64_t)p;
   const float sx = d[0], sy = d[1], sz = d[2];
-  // ---- k_envmap_lookup's four taps (written out again: see the header)
   float row, col;
   sph_rowcol(sx, sy, sz, a.H, a.W, a.row_scale, a.col_scale, a.col_bias, row, col);
-  const float fi = floorf(row), fj = floorf(col);
-  const int i = (int)fi, j = (int)fj;
-  const float fr = row - fi, fc = col - fj;
-  const float gr = 1.f - fr, gc = 1.f - fc;
-  const int half = a.W >> 1;
-  int i0 = i, i1 = i + 1;
-  const bool x0 = i0 < 0 || i0 >= a.H, x1 = i1 >= a.H;  // beyond a pole: the far side
-  if (i0 < 0) i0 = -1 - i0;
-  if (i0 >= a.H) i0 = 2 * a.H - 1 - i0;
-  if (i1 >= a.H) i1 = 2 * a.H - 1 - i1;
-  i0 = min(max(i0, 0), a.H - 1);
-  i1 = min(max(i1, 0), a.H - 1);
-  int j0 = j < 0 ? j + a.W : (j >= a.W ? j - a.W : j);
-  int j1 = j + 1 >= a.W ? j + 1 - a.W : j + 1;
-  if (j1 >= a.W) j1 -= a.W;
-  const int j0f = j0 + half >= a.W ? j0 - half : j0 + half, j1f = j1 + half >= a.W ? j1 - half : j1 + half;
-  const int r0 = i0 * a.W, r1 = i1 * a.W;
-  const int c00 = x0 ? j0f : j0, c01 = x0 ? j1f : j1, c10 = x1 ? j0f : j0, c11 = x1 ? j1f : j1;
-  const int e4[4] = {r0 + c00, r0 + c01, r1 + c10, r1 + c11};
-  const float w4[4] = {gr * gc, gr * fc, fr * gc, fr * fc};
+  const SphTaps t = sph_taps(row, col, a.H, a.W);
+  const int r0 = t.i0 * a.W, r1 = t.i1 * a.W;
+  const int e4[4] = {r0 + t.j00, r0 + t.j01, r1 + t.j10, r1 + t.j11};
+  const float w4[4] = {t.gr * t.gc, t.gr * t.fc, t.fr * t.gc, t.fr * t.fc};
   // ---- the level, as the forward: the next level is read, and so weighs, only when fl > 0
   const SphLevel L = sph_level(a.level ? a.level[n * a.ln + p] : a.level_const, a.Lv);
   const int l0 = L.l0, l1 = L.l1;
@@ -339,22 +317,15 @@ int reni_lobe_convolve_backward(int64_t N, int64_t P, int64_t Q, const float* ou
   dg_split(Q, P, S, chunk);
   a.chunk = (int)chunk; a.S = (int)S; a.Lv = n_lobes;
   int nslab = 0;
-  for (int kind = RENI_LOBE_PHONG; kind <= RENI_LOBE_GGX; ++kind) {  // one launch per kind present, its lobes inside
-    a.nl = 0;
-    for (int l = 0; l < n_lobes; ++l) {
-      if (kinds[l] != kind) continue;
-      a.lobe[a.nl] = l;
-      a.par[a.nl] = lb_kernel_param(kind, params[l]);
-      ++a.nl;
-    }
-    if (!a.nl) continue;
-    a.ws = slabs + (int64_t)nslab * (3 * N) * Q;
-    const int rc = kind == RENI_LOBE_PHONG   ? lbt_launch<RENI_LOBE_PHONG>(TU_COUNTED, a, s)
-                   : kind == RENI_LOBE_BLINN ? lbt_launch<RENI_LOBE_BLINN>(TU_COUNTED, a, s)
-                                             : lbt_launch<RENI_LOBE_GGX>(TU_COUNTED, a, s);
-    if (rc) return rc;
-    nslab += (int)S;
-  }
+  // one launch per kind present, its lobes inside, into the kind's own S slabs
+  if (int rc = lb_for_kinds(a, n_lobes, kinds, params, [&](int kind, reni::LbtArgs& a) {
+        a.ws = slabs + (int64_t)nslab * (3 * N) * Q;
+        nslab += (int)S;
+        return kind == RENI_LOBE_PHONG   ? lbt_launch<RENI_LOBE_PHONG>(TU_COUNTED, a, s)
+               : kind == RENI_LOBE_BLINN ? lbt_launch<RENI_LOBE_BLINN>(TU_COUNTED, a, s)
+                                         : lbt_launch<RENI_LOBE_GGX>(TU_COUNTED, a, s);
+      }))
+    return rc;
   const int64_t total = N * Q;
   return tu_launch(TU_COUNTED, reni::k_lobe_finish_t, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, slabs, in_w, (int)N, (int)Q,
                    nslab, grad_src, grad_stride_n, grad_stride_i, grad_stride_c);
@@ -364,16 +335,12 @@ int reni_envmap_lookup_taps(int64_t n_tables, int64_t Lv, int64_t H, int64_t W, 
                             const float* level, int64_t level_stride_n, float level_const, int32_t* tap_index, float* tap_weight,
                             void* stream) {
   if (int rc = lk_check_sizes(n_tables, Lv, H, W, P, n_tables)) return rc;
-  if (!dirs || !tap_index || !tap_weight) return reni_set_error(RENI_EINVAL, "lookup taps: NULL argument");
-  if (dirs_stride_n != 0 && dirs_stride_n != 3 * P)
-    return reni_set_error(RENI_EINVAL, "lookup taps: dirs_stride_n must be 0 (shared) or 3 P (per map)");
-  if (level && level_stride_n != 0 && level_stride_n != P)
-    return reni_set_error(RENI_EINVAL, "lookup taps: level_stride_n must be 0 (shared) or P (per map)");
+  if (int rc = sph_check_query(false, n_tables, Lv, H, W, P, nullptr, nullptr, dirs, dirs_stride_n, level, level_stride_n,
+                               tap_index && tap_weight))
+    return rc;
   reni::LtArgs a = {};
-  a.dirs = dirs; a.dn = dirs_stride_n; a.level = level; a.ln = level ? level_stride_n : 0; a.level_const = level_const;
+  sph_fill_query(a, n_tables, Lv, H, W, P, nullptr, nullptr, dirs, dirs_stride_n, level, level_stride_n, level_const);
   a.idx = tap_index; a.wgt = tap_weight;
-  a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
-  sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
   return tu_launch(TU_COUNTED, reni::k_envmap_lookup_taps, dim3((unsigned)((P + 255) / 256), (unsigned)n_tables), dim3(256), 0,
                    (hipStream_t)stream, a);
 }

@@ -31,7 +31,7 @@
 
 #pragma clang fp contract(off)
 
-#include "reni_sphere.inc"  // direction -> (row, col) and the three constants: shared with the lookup (reni_tu_glossy.hip)
+#include "reni_sphere.inc"  // direction -> (row, col), the taps and the three constants: shared with the lookup (reni_tu_glossy.hip)
 
 namespace reni {
 
@@ -49,17 +49,6 @@ struct RotArgs {
   int C, H, W;
   float row_scale, col_scale, col_bias;  // fp32(H / pi), fp32(W / 2 pi), W/2 - 1/2
 };
-
-// element offset of the tap (i, j) of the sphere: -1 <= i <= H, -1 <= j <= W + 1
-DEV int64_t tap_offset(int i, int j, const RotArgs& a) {
-  if (i < 0) { i = -1 - i; j += a.W >> 1; }
-  if (i >= a.H) { i = 2 * a.H - 1 - i; j += a.W >> 1; }
-  if (j < 0) j += a.W;
-  if (j >= a.W) j -= a.W;
-  if (j >= a.W) j -= a.W;  // j < W + 2 + W/2 <= 3 W
-  i = min(max(i, 0), a.H - 1);  // (H == 1 with both poles crossed; a no-op otherwise)
-  return (int64_t)i * (int64_t)a.sy + (int64_t)j * (int64_t)a.sx;
-}
 
 template <bool BILINEAR>
 __global__ void __launch_bounds__(256) k_rotate_envmap(const RotArgs a) {
@@ -81,34 +70,19 @@ __global__ void __launch_bounds__(256) k_rotate_envmap(const RotArgs a) {
   const float* base = a.src + n * a.sn;
   float* o = a.out + (int64_t)b * a.C * a.H * a.W + p;
   if (BILINEAR) {
-    const float fi = floorf(row), fj = floorf(col);
-    const int i = (int)fi, j = (int)fj;
-    const float fr = row - fi, fc = col - fj;
-    const float gr = 1.f - fr, gc = 1.f - fc;
-    // the four taps share two rows and two columns: what tap_offset does, once per row and per column (-1 <= i < H, -1 <= j < W
-    // up to the clamps above, so i + 1 <= H + 1 and j + 1 <= W + 1)
-    const int half = a.W >> 1;
-    int i0 = i, i1 = i + 1;
-    const bool x0 = i0 < 0 || i0 >= a.H, x1 = i1 >= a.H;  // beyond a pole: the far side
-    if (i0 < 0) i0 = -1 - i0;
-    if (i0 >= a.H) i0 = 2 * a.H - 1 - i0;
-    if (i1 >= a.H) i1 = 2 * a.H - 1 - i1;
-    i0 = min(max(i0, 0), a.H - 1);
-    i1 = min(max(i1, 0), a.H - 1);
-    int j0 = j < 0 ? j + a.W : (j >= a.W ? j - a.W : j);
-    int j1 = j + 1 >= a.W ? j + 1 - a.W : j + 1;
-    if (j1 >= a.W) j1 -= a.W;
-    const int j0f = j0 + half >= a.W ? j0 - half : j0 + half, j1f = j1 + half >= a.W ? j1 - half : j1 + half;
-    const int64_t r0 = (int64_t)i0 * (int64_t)a.sy, r1 = (int64_t)i1 * (int64_t)a.sy;
-    const int64_t o00 = r0 + (int64_t)(x0 ? j0f : j0) * (int64_t)a.sx, o01 = r0 + (int64_t)(x0 ? j1f : j1) * (int64_t)a.sx;
-    const int64_t o10 = r1 + (int64_t)(x1 ? j0f : j0) * (int64_t)a.sx, o11 = r1 + (int64_t)(x1 ? j1f : j1) * (int64_t)a.sx;
+    const SphTaps t = sph_taps(row, col, a.H, a.W);
+    const float fr = t.fr, gr = t.gr, fc = t.fc, gc = t.gc;
+    const int64_t r0 = (int64_t)t.i0 * (int64_t)a.sy, r1 = (int64_t)t.i1 * (int64_t)a.sy;
+    const int64_t o00 = r0 + (int64_t)t.j00 * (int64_t)a.sx, o01 = r0 + (int64_t)t.j01 * (int64_t)a.sx;
+    const int64_t o10 = r1 + (int64_t)t.j10 * (int64_t)a.sx, o11 = r1 + (int64_t)t.j11 * (int64_t)a.sx;
     for (int ch = 0; ch < a.C; ++ch, base += a.sc, o += (int64_t)a.H * a.W) {
       const float top = fmaf(fc, base[o01], gc * base[o00]);
       const float bot = fmaf(fc, base[o11], gc * base[o10]);
       *o = fmaf(fr, bot, gr * top);
     }
   } else {
-    const int64_t o00 = tap_offset((int)floorf(row + 0.5f), (int)floorf(col + 0.5f), a);
+    const SphTaps t = sph_taps(row + 0.5f, col + 0.5f, a.H, a.W);  // the one-tap case: its first tap
+    const int64_t o00 = (int64_t)t.i0 * (int64_t)a.sy + (int64_t)t.j00 * (int64_t)a.sx;
     for (int ch = 0; ch < a.C; ++ch, base += a.sc, o += (int64_t)a.H * a.W) *o = base[o00];
   }
 }

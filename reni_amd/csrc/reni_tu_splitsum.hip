@@ -7,9 +7,8 @@
 //
 //   k_envmap_lookup_dquery<WANT_DIRS, WANT_LEVEL>   the derivative of k_envmap_lookup's output with respect to its QUERY -- the
 //                       direction and the level -- contracted with grad_out [N][P][3].  One lane per direction; the coordinate
-//                       chain is the lookup's (sph_rowcol, sph_level of reni_sphere.inc; the four taps with the pole fold and
-//                       the seam wrap written out again).  With b00 .. b11 the folded taps of a level and (fr, gr, fc, gc) the
-//                       lookup's fractions
+//                       chain is the lookup's (sph_rowcol, sph_taps, sph_level of reni_sphere.inc).  With b00 .. b11 the folded
+//                       taps of a level and (fr, gr, fc, gc) the lookup's fractions
 //                           d out / d row = gc (b10 - b00) + fc (b11 - b01)        d out / d col = gr (b01 - b00) + fr (b11 - b10)
 //                       mixed over the two levels as the forward mixes the values; Gr = <g, d out / d row>, Gc likewise, and
 //                           d_dirs = row_scale Gr d phi / d q + col_scale Gc d theta / d q
@@ -40,25 +39,15 @@
 
 #pragma clang fp contract(off)
 
-#include "reni_sphere.inc"  // (row, col) and level of a lookup, the host's three constants
+#include "reni_sphere.inc"  // (row, col), taps and level of a lookup, the query record with its checks
 
 namespace reni {
 
-struct DqArgs {
-  const float* src;  // element (n, level, y, x, c) at n sn + level sl + y sy + x sx + c sc
-  int64_t sn, sl, sc;
-  int sy, sx;
-  const float* dirs;  // direction p of map n at dirs + n dn + 3 p
-  int64_t dn;
-  const float* level;  // NULL: level_const for every direction; else level[n ln + p]
-  int64_t ln;
-  float level_const;
+struct DqArgs : SphQuery {
   const float* grad_out;  // [N][P][3]
   float* d_dirs;          // [P][3] when dn == 0, else [N][P][3]
   float* d_level;         // [P] when ln == 0, else [N][P]
-  int N, Lv, H, W, P;
   int loop;  // 1: one lane serves every map of its direction (a wanted output is shared); 0: blockIdx.y is the map
-  float row_scale, col_scale, col_bias;
 };
 
 // what of a direction the chain rule needs, or ok = false where the derivative is defined as 0
@@ -89,7 +78,6 @@ __global__ void __launch_bounds__(256) k_envmap_lookup_dquery(const DqArgs a) {
   if (p >= a.P) return;
   const int n_lo = a.loop ? 0 : (int)blockIdx.y, n_hi = a.loop ? a.N : n_lo + 1;
   const bool dirs_shared = a.dn == 0, level_shared = a.ln == 0;
-  const int half = a.W >> 1;
   float fr = 0.f, gr = 1.f, fc = 0.f, gc = 1.f;
   int64_t o00 = 0, o01 = 0, o10 = 0, o11 = 0;
   DqGeom geo = {};
@@ -100,27 +88,13 @@ __global__ void __launch_bounds__(256) k_envmap_lookup_dquery(const DqArgs a) {
     if (nn == n_lo || !dirs_shared) {
       const float* d = a.dirs + n * a.dn + 3 * (int64_t)p;
       const float sx = d[0], sy = d[1], sz = d[2];
-      // ---- k_envmap_lookup's four taps (written out again: see the header)
       float row, col;
       sph_rowcol(sx, sy, sz, a.H, a.W, a.row_scale, a.col_scale, a.col_bias, row, col);
-      const float fi = floorf(row), fj = floorf(col);
-      const int i = (int)fi, j = (int)fj;
-      fr = row - fi, fc = col - fj;
-      gr = 1.f - fr, gc = 1.f - fc;
-      int i0 = i, i1 = i + 1;
-      const bool x0 = i0 < 0 || i0 >= a.H, x1 = i1 >= a.H;  // beyond a pole: the far side
-      if (i0 < 0) i0 = -1 - i0;
-      if (i0 >= a.H) i0 = 2 * a.H - 1 - i0;
-      if (i1 >= a.H) i1 = 2 * a.H - 1 - i1;
-      i0 = min(max(i0, 0), a.H - 1);
-      i1 = min(max(i1, 0), a.H - 1);
-      int j0 = j < 0 ? j + a.W : (j >= a.W ? j - a.W : j);
-      int j1 = j + 1 >= a.W ? j + 1 - a.W : j + 1;
-      if (j1 >= a.W) j1 -= a.W;
-      const int j0f = j0 + half >= a.W ? j0 - half : j0 + half, j1f = j1 + half >= a.W ? j1 - half : j1 + half;
-      const int64_t r0 = (int64_t)i0 * (int64_t)a.sy, r1 = (int64_t)i1 * (int64_t)a.sy;
-      o00 = r0 + (int64_t)(x0 ? j0f : j0) * (int64_t)a.sx, o01 = r0 + (int64_t)(x0 ? j1f : j1) * (int64_t)a.sx;
-      o10 = r1 + (int64_t)(x1 ? j0f : j0) * (int64_t)a.sx, o11 = r1 + (int64_t)(x1 ? j1f : j1) * (int64_t)a.sx;
+      const SphTaps t = sph_taps(row, col, a.H, a.W);
+      fr = t.fr, gr = t.gr, fc = t.fc, gc = t.gc;
+      const int64_t r0 = (int64_t)t.i0 * (int64_t)a.sy, r1 = (int64_t)t.i1 * (int64_t)a.sy;
+      o00 = r0 + (int64_t)t.j00 * (int64_t)a.sx, o01 = r0 + (int64_t)t.j01 * (int64_t)a.sx;
+      o10 = r1 + (int64_t)t.j10 * (int64_t)a.sx, o11 = r1 + (int64_t)t.j11 * (int64_t)a.sx;
       if (WANT_DIRS) geo = dq_geom(sx, sy, sz, row, a.H);
     }
     // ---- the level: the forward's (l0, fl, gl), read as weights (wa, wb) of the pair (la, la + 1) the slope is taken over
@@ -245,29 +219,14 @@ int reni_envmap_lookup_dquery(int64_t N, int64_t Lv, int64_t H, int64_t W, int64
                               const int64_t src_strides[5], const float* dirs, int64_t dirs_stride_n, const float* level,
                               int64_t level_stride_n, float level_const, const float* grad_out, float* d_dirs, float* d_level,
                               void* stream) {
-  // the lookup's checks, in its wording
-  if (N < 1 || Lv < 1 || H < 1 || W < 1 || P < 1) return reni_set_error(RENI_EINVAL, "lookup: sizes must be >= 1");
-  if (W & 1) return reni_set_error(RENI_EINVAL, "lookup: W must be even (the far side of a pole is W / 2 columns away)");
-  if (N > 65535 || Lv > 65535 || H > 0x3fffffff / W || P > 0x3fffffff / 3 || N > 0x3fffffff / (3 * P))
-    return reni_set_error(RENI_EINVAL, "lookup: need N, Lv <= 65535, H W < 2^30 and N P < 2^28");
-  if (!src || !src_strides || !dirs || !grad_out) return reni_set_error(RENI_EINVAL, "lookup: NULL argument");
-  if (int rc = tu_check_strides("lookup", "src strides", src_strides, 5)) return rc;
-  if (src_strides[2] > 0x7fffffff || src_strides[3] > 0x7fffffff)
-    return reni_set_error(RENI_EINVAL, "lookup: the row and column strides must be < 2^31 elements");
-  if (dirs_stride_n != 0 && dirs_stride_n != 3 * P)
-    return reni_set_error(RENI_EINVAL, "lookup: dirs_stride_n must be 0 (shared) or 3 P (per map)");
-  if (level && level_stride_n != 0 && level_stride_n != P)
-    return reni_set_error(RENI_EINVAL, "lookup: level_stride_n must be 0 (shared) or P (per map)");
+  if (int rc = sph_check_query(true, N, Lv, H, W, P, src, src_strides, dirs, dirs_stride_n, level, level_stride_n, grad_out != nullptr))
+    return rc;
   if (!d_dirs && !d_level) return reni_set_error(RENI_EINVAL, "lookup dquery: d_dirs and d_level are both NULL");
   if (d_level && !level) return reni_set_error(RENI_EINVAL, "lookup dquery: d_level needs a level array");
   reni::DqArgs a = {};
-  a.src = src; a.sn = src_strides[0]; a.sl = src_strides[1]; a.sy = (int)src_strides[2]; a.sx = (int)src_strides[3];
-  a.sc = src_strides[4];
-  a.dirs = dirs; a.dn = dirs_stride_n; a.level = level; a.ln = level ? level_stride_n : 0; a.level_const = level_const;
+  sph_fill_query(a, N, Lv, H, W, P, src, src_strides, dirs, dirs_stride_n, level, level_stride_n, level_const);
   a.grad_out = grad_out; a.d_dirs = d_dirs; a.d_level = d_level;
-  a.N = (int)N; a.Lv = (int)Lv; a.H = (int)H; a.W = (int)W; a.P = (int)P;
   a.loop = ((d_dirs && a.dn == 0) || (d_level && a.ln == 0)) ? 1 : 0;
-  sph_scales(H, W, a.row_scale, a.col_scale, a.col_bias);
   const auto k = d_dirs && d_level ? reni::k_envmap_lookup_dquery<true, true>
                  : d_dirs          ? reni::k_envmap_lookup_dquery<true, false>
                                    : reni::k_envmap_lookup_dquery<false, true>;

@@ -304,7 +304,7 @@ def test_rotate_stores_nothing_beyond_its_output(mode):
 
 def test_a_non_finite_matrix_never_becomes_an_address():
     """NaN, inf, overflow and the zero matrix: the row and column are clamped before they are taps (fminf / fmaxf drop a NaN),
-    tap_offset and the bilinear branch's own wraps keep every tap inside the map.  The output is finite and every value lies
+    sph_taps' fold and wraps keep every tap inside the map.  The output is finite and every value lies
     within its source map's range."""
     from reni_amd import ops
     for H, W in E.NONFINITE_SHAPES:

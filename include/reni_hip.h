@@ -456,7 +456,12 @@ int reni_gbuffer_backward(int64_t V, int64_t F, const float* verts, const int64_
  *   its extent and position so that the fp32 slab test stays conservative.  The record is opaque and holds no pointer.
  * reni_mesh_visibility: positions [NP][3], pix_to_face [NP] int64 (the rasteriser's), dirs [J][3] of image b at
  *   dirs + b * dirs_batch_stride (floats; 0 = shared), 0 <= t_min finite (hits nearer than this are the surface itself).
- *   flags: RENI_VIS_NO_CULL visits every cluster of every ray (no box test, no early exit): brute force, the same bits. */
+ *   flags: RENI_VIS_NO_CULL visits every cluster of every ray (no box test, no early exit): brute force, the same bits.
+ *   d need not be a unit vector: the formulas are evaluated as they stand (t scales by 1 / |d|).  A direction that is zero or
+ *   has a NaN or infinite component hits no face (a is 0 or NaN, or u and v are NaN): its bit is 1 on every foreground pixel.
+ *   An accel buffer that reni_mesh_visibility_prepare never filled (no magic number in its first word) is not walked: it
+ *   stands for a mesh without faces, foreground bits 1, background bits 0; nothing beyond its 64-byte header is read.  A
+ *   pix_to_face that is no face's id (>= F, or the id of a skipped face) excludes nothing. */
 #define RENI_VIS_NO_CULL 1u
 size_t reni_mesh_visibility_accel_bytes(int64_t F);
 int reni_mesh_visibility_prepare(int64_t V, int64_t F, const float* verts, const int64_t* faces, const int64_t* order,

@@ -163,8 +163,12 @@ __global__ void __launch_bounds__(VIS_WAVES * 64) k_mesh_visibility(const VisArg
     if (!a.no_cull) {
       if (__ballot(!occ) == 0ull) break;  // every ray of the wave is occluded
       const float4 blo = boxes[(size_t)c * 2], bhi = boxes[(size_t)c * 2 + 1];
-      // slabs: the ray is inside the box for t in [tn, tf]; NaN (0 * inf: the origin on a slab plane of a direction
-      // parallel to it) drops out of fminf / fmaxf, which errs towards "touches"
+      // slabs: the ray is inside the box for t in [tn, tf].  NaN (0 * inf: the origin exactly on a slab plane of a
+      // direction parallel to it) drops out of fminf / fmaxf, which return the pair's other quotient, +inf on a lo plane
+      // (tn = +inf) and -inf on a hi plane (tf = -inf): the cluster is SKIPPED.  That is right, not merely safe: the
+      // margin is > 0 on every axis, so every face lies strictly inside the box and a ray within one of its planes
+      // meets none (tests/test_gpu_visibility_edges.py, the box-plane probes).  A zero, NaN or inf direction hits no
+      // face (den is 0 or NaN, or u and v are), so whatever the slabs make of it moves no bit
       const float x0 = (blo.x - o[0]) * inv[0], x1 = (bhi.x - o[0]) * inv[0];
       const float y0 = (blo.y - o[1]) * inv[1], y1 = (bhi.y - o[1]) * inv[1];
       const float z0 = (blo.z - o[2]) * inv[2], z1 = (bhi.z - o[2]) * inv[2];

@@ -437,6 +437,49 @@ int reni_gbuffer_backward(int64_t V, int64_t F, const float* verts, const int64_
                           const int64_t* vf_corners, const float* grad_pixel_normals, const float* grad_pixel_positions,
                           float* grad_verts, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- soft silhouette: a differentiable coverage mask of the mesh and its vertex gradient (reni_tu_silhouette.hip) -------
+ * What the G-buffer backward above leaves out: the gradient that moves the outline.  The classic soft coverage of SoftRas and
+ * pytorch3d's SoftSilhouetteShader, restated from their documented behaviour.  Camera, projection, H == W = S, pixel
+ * p = row * S + col and its NDC centre (px, py): exactly reni_rasterize_mesh's.  sigma > 0 and blur_radius r >= 0, both finite;
+ * r is in squared NDC units.
+ *   taking part     face f takes part iff reni_rasterize_mesh does not skip it for its indices or its area (every index in
+ *                   [0, V), |area| > 1e-8), all three view z are > 0, and its three projected corners are finite.  The second
+ *                   condition is deliberately narrower than the rasteriser's max z >= 0: a face that straddles the camera
+ *                   plane has no meaningful outline.
+ *   nearest point   c = the nearest point of the triangle's boundary to (px, py): over the edges (0,1), (0,2), (1,2) in this
+ *                   order (a, b = the edge's corners), c_e = a + t (b - a), t = clamp(((b - a) . (p - a)) / |b - a|^2, 0, 1);
+ *                   |b - a|^2 <= 1e-8: c_e = b and t = 1.  The first edge with the strictly smallest |c_e - p|^2 wins.
+ *   signed distance inside <=> w0 > 0 and w1 > 0 and w2 > 0 (the barycentrics above);  d = |c - p|^2;  sd = -d inside, +d outside
+ *   membership      f takes part AT p iff inside or d < r
+ *   coverage        prob_f(p) = 1 / (1 + exp(sd / sigma));  trans_p = prod_f (1 - prob_f(p)) over the faces taking part at p,
+ *                   multiplied in ascending face order starting from 1.0f;  alpha_p = 1 - trans_p.  A pixel no face takes part
+ *                   at has trans = 1 and alpha = 0 exactly.
+ * Two deviations from pytorch3d: every face near the pixel enters, there is no K-nearest cut (this is pytorch3d's result
+ * whenever its faces_per_pixel is at least the overlap count); and the narrowed taking-part rule above.
+ * Gradient, for an upstream gA [S*S]:   g_verts = d/dverts sum_p gA_p alpha_p        [V][3]
+ * with membership, inside, the winning edge and a clamped t held constant:
+ *   d alpha_p / d sd_f = -trans_p prob_f / sigma      (no division by 1 - prob_f: where the product is 0 the true value is 0 too)
+ *   with s = -1 inside, +1 outside:  d sd / da = 2 s (1 - t)(c - p),  d sd / db = 2 s t (c - p)  (the clamped and the
+ *   degenerate-edge cases included); the third corner gets 0.  NDC -> view -> world exactly as reni_gbuffer_backward
+ *   (x = q_x / (q_z tan_half_fov), d/dp_i = sum_j R[i][j] d/dq_j).  The camera is a constant.
+ * A vertex that no taking-part face names gets exactly 0.  Malformed input (an index outside [0, V), a list entry outside
+ * [0, 3F), offsets outside their list) adds nothing and is never turned into an address.  fp32, no float atomics: every sum
+ * and product has one fixed order, two calls give identical bits.
+ * reni_soft_silhouette: R [9], T [3] (host memory) as reni_rasterize_mesh; alpha, trans [S*S] are overwritten.
+ *   ws: reni_soft_silhouette_workspace_bytes(V, F, H, W) bytes, 256-byte aligned (the per-face records).
+ * reni_soft_silhouette_backward: the same geometry arguments, sigma and blur_radius; trans [S*S] as the forward gave it;
+ *   grad_alpha [S*S]; vf_offsets / vf_corners as for reni_mesh_vertex_normals; grad_verts [V][3] is overwritten.
+ *   ws: reni_soft_silhouette_backward_workspace_bytes(V, F, H, W) bytes, 256-byte aligned (the records, 9 floats per face). */
+size_t reni_soft_silhouette_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W);
+int reni_soft_silhouette(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* R, const float* T,
+                         float tan_half_fov, int64_t H, int64_t W, float sigma, float blur_radius, float* alpha, float* trans,
+                         void* ws, size_t ws_bytes, void* stream);
+size_t reni_soft_silhouette_backward_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W);
+int reni_soft_silhouette_backward(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* R, const float* T,
+                                  float tan_half_fov, int64_t H, int64_t W, float sigma, float blur_radius, const float* trans,
+                                  const float* grad_alpha, const int64_t* vf_offsets, const int64_t* vf_corners,
+                                  float* grad_verts, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- cast shadows: visibility masks of the mesh for the shader (reni_tu_visibility.hip, the MASKED shader instances) ----
  * The shader above lets light pass through the mesh: M(p, j) knows the pixel's own normal and nothing else.  The lights are at
  * infinity, so whether texel direction j reaches pixel p is a constant of (mesh, camera, directions), as the G-buffer is.

@@ -211,6 +211,36 @@ class _GBufferFn(torch.autograd.Function):
         return g, None
 
 
+class _SilhouetteFn(torch.autograd.Function):
+    """The cached soft silhouette as a function of the vertices: the forward hands out the buffer ``ops.soft_silhouette``
+    filled, the backward is ``ops.soft_silhouette_backward`` over the record's trans.  A node per call, as ``_GBufferFn``."""
+
+    @staticmethod
+    def forward(ctx, verts, rec):
+        ctx.save_for_backward(verts)
+        ctx.rec = rec
+        return rec["alpha"].detach()
+
+    @staticmethod
+    def backward(ctx, gA):
+        (verts,) = ctx.saved_tensors
+        rec = ctx.rec
+        g = ops.soft_silhouette_backward(verts.detach(), rec["faces"], rec["R"], rec["T"], rec["S"], rec["tan_half_fov"],
+                                         rec["sigma"], rec["blur_radius"], rec["trans"], gA.contiguous(), vf=rec["vf"])
+        return g, None
+
+
+def silhouette_iou(alpha: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """The soft IoU loss of a coverage ``alpha`` against a target ``mask`` of the same number of pixels (values in [0, 1]):
+    1 - sum(a m) / sum(a + m - a m).  Plain torch; 0 where both are empty."""
+    a, m = alpha.reshape(-1), mask.reshape(-1).to(alpha.dtype)
+    if a.numel() != m.numel():
+        raise ValueError(f"alpha has {a.numel()} pixels, the mask {m.numel()}")
+    inter = (a * m).sum()
+    union = (a + m - a * m).sum()
+    return 1.0 - inter / union.clamp_min(1e-12)
+
+
 class Meshes:
     """One triangle mesh in pytorch3d's packed form: ``Meshes(verts=[v], faces=[f])``; the vertex normals come from the
     HIP kernel (a device tensor is needed for them) and are kept until the vertices or faces are modified in place (the key
@@ -306,6 +336,7 @@ class MeshRasterizer(nn.Module):
         self._uv_cache = None
         self._taps_cache = None
         self._tangent_cache = None
+        self._sil_cache = None
 
     def gbuffer(self, meshes_world: Meshes, R=None, T=None, differentiable: bool = True):
         """-> (Fragments, pixel_normals [S*S,3], pixel_positions [S*S,3]) (interpolated, not normalised).
@@ -333,6 +364,36 @@ class MeshRasterizer(nn.Module):
             nrm, pos = _GBufferFn.apply(v, rec)
             return out[0], nrm, pos
         return out
+
+    def silhouette(self, meshes_world: Meshes, R=None, T=None, sigma: float = 1e-4, blur_radius=None):
+        """-> alpha [S, S], the soft coverage of the mesh (``ops.soft_silhouette``): 1 - prod over the faces near a pixel of
+        (1 - sigmoid(-sd / sigma)), sd the signed squared NDC distance to the face's outline.  ``blur_radius`` (squared NDC
+        units) cuts a face off where it is further away; None means log(1 / 1e-4 - 1) sigma, pytorch3d's convention.  It is an
+        argument of this call: ``RasterizationSettings`` keeps blur_radius 0 for the hard rasteriser.
+
+        Kept like the G-buffer, under the same key plus (sigma, blur_radius).  When the mesh's vertices require grad (and grad
+        is enabled) the same cached buffer is returned behind an autograd node built for this call
+        (``ops.soft_silhouette_backward``): this is the gradient that moves the outline; the camera is a constant.  Otherwise
+        the cached tensor itself is returned."""
+        R = self.cameras.R if R is None else torch.as_tensor(R)
+        T = self.cameras.T if T is None else torch.as_tensor(T)
+        S = self.raster_settings.image_size
+        sigma = float(sigma)
+        blur_radius = math.log(1.0 / 1e-4 - 1.0) * sigma if blur_radius is None else float(blur_radius)
+        v, f = meshes_world.verts_packed(), meshes_world.faces_packed()
+        tanf = self.cameras.tan_half_fov()
+        key = tuple((id(t), t._version) for t in (v, f, R, T)) + (S, tanf, sigma, blur_radius)
+        if self._sil_cache is None or self._sil_cache[0] != key:
+            alpha, trans = ops.soft_silhouette(v.detach(), f, R, T, S, tanf, sigma, blur_radius)
+            rec = {"faces": f, "R": R, "T": T, "S": S, "tan_half_fov": tanf, "sigma": sigma, "blur_radius": blur_radius,
+                   "alpha": alpha.reshape(S, S), "trans": trans, "vf": None}
+            self._sil_cache = (key, (v, f, R, T), rec)  # (the tensors are held so that their ids stay theirs)
+        rec = self._sil_cache[2]
+        if v.requires_grad and torch.is_grad_enabled():
+            if rec["vf"] is None:
+                rec["vf"] = meshes_world._vertex_faces()
+            return _SilhouetteFn.apply(v, rec)
+        return rec["alpha"]
 
     def visibility(self, meshes_world: Meshes, R=None, T=None, dirs=None, t_min=None, no_cull: bool = False):
         """-> the int32 visibility mask [NB, S*S, ceil(J/32)] of ``dirs`` ([J,3] shared, NB = 1, or [B,J,3], NB = B) over the

@@ -5,6 +5,7 @@ PyTorch is plumbing here (device memory, streams); all arithmetic happens in lib
 from __future__ import annotations
 
 import ctypes
+import math
 import types
 from typing import Optional, Tuple
 
@@ -912,6 +913,67 @@ def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: tor
           float(tan_half_fov), S, S, p2f.data_ptr(), foff.contiguous().data_ptr(), flist.contiguous().data_ptr(),
           offsets.data_ptr(), corners.data_ptr(), None if gN is None else gN.data_ptr(), None if gX is None else gX.data_ptr(),
           out.data_ptr(), wp, wn)
+    return out
+
+
+def _silhouette_scalars(sigma, blur_radius):
+    sigma, blur_radius = float(sigma), float(blur_radius)
+    if not (sigma > 0.0) or not math.isfinite(sigma):
+        raise ValueError(f"sigma must be positive and finite, got {sigma}")
+    if not (blur_radius >= 0.0) or not math.isfinite(blur_radius):
+        raise ValueError(f"blur_radius must be >= 0 and finite, got {blur_radius}")
+    return sigma, blur_radius
+
+
+def soft_silhouette(verts: torch.Tensor, faces: torch.Tensor, R, T, image_size: int, tan_half_fov: float, sigma: float,
+                    blur_radius: float):
+    """reni_soft_silhouette: (alpha [S*S], trans [S*S]) of one mesh under ``rasterize_mesh``'s camera and pixel grid -- the soft
+    coverage alpha_p = 1 - prod_f (1 - prob_f(p)), prob = 1 / (1 + exp(sd / sigma)) with sd the signed squared NDC distance of
+    the pixel centre to the face's boundary (negative inside), over every face with all view z > 0 that holds the pixel or lies
+    within ``blur_radius`` (squared NDC units) of it, in ascending face order.  trans = 1 - alpha's product is what
+    ``soft_silhouette_backward`` reads.  Deterministic, no atomics."""
+    _mesh_shapes(verts, faces)
+    S = _image_size(image_size)
+    sigma, blur_radius = _silhouette_scalars(sigma, blur_radius)
+    Rh, Th = _camera_arrays(R, T)
+    verts, faces = _mesh_inputs(verts, faces)
+    lib = _lib.load()
+    V, F = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    alpha = torch.empty(S * S, dtype=torch.float32, device=dev)
+    trans = torch.empty(S * S, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_soft_silhouette_workspace_bytes(V, F, S, S)), dev)
+    _call(lib.reni_soft_silhouette, dev, V, F, verts.data_ptr(), faces.data_ptr(), Rh, Th, float(tan_half_fov), S, S, sigma,
+          blur_radius, alpha.data_ptr(), trans.data_ptr(), wp, wn)
+    return alpha, trans
+
+
+def soft_silhouette_backward(verts: torch.Tensor, faces: torch.Tensor, R, T, image_size: int, tan_half_fov: float, sigma: float,
+                             blur_radius: float, trans: torch.Tensor, grad_alpha: torch.Tensor, vf=None) -> torch.Tensor:
+    """reni_soft_silhouette_backward: grad_verts [V, 3] = d/d verts of sum_p grad_alpha_p alpha_p for the alpha of
+    ``soft_silhouette`` (``trans`` as it returned it), with membership, inside / outside, the nearest edge and a clamped edge
+    parameter held constant; the camera is a constant.  ``vf``: ``vertex_face_lists(faces, V)`` when the caller keeps it.
+    Deterministic, no atomics."""
+    _mesh_shapes(verts, faces)
+    S = _image_size(image_size)
+    sigma, blur_radius = _silhouette_scalars(sigma, blur_radius)
+    for name, t in (("trans", trans), ("grad_alpha", grad_alpha)):
+        if not isinstance(t, torch.Tensor) or t.numel() != S * S:
+            raise ValueError(f"{name} must be a tensor of {S * S} entries, got {tuple(getattr(t, 'shape', ()))}")
+    Rh, Th = _camera_arrays(R, T)
+    verts, faces = _mesh_inputs(verts, faces)
+    _require_cuda(trans, grad_alpha)
+    dev = verts.device
+    trans, grad_alpha = _f32c(trans).reshape(-1), _f32c(grad_alpha).reshape(-1)
+    if trans.device != dev or grad_alpha.device != dev:
+        raise ValueError(f"trans and grad_alpha are not on {dev}")
+    V, F = verts.shape[0], faces.shape[0]
+    offsets, corners = _vf_lists(faces, V, vf)
+    lib = _lib.load()
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_soft_silhouette_backward_workspace_bytes(V, F, S, S)), dev)
+    _call(lib.reni_soft_silhouette_backward, dev, V, F, verts.data_ptr(), faces.data_ptr(), Rh, Th, float(tan_half_fov), S, S, sigma,
+          blur_radius, trans.data_ptr(), grad_alpha.data_ptr(), offsets.data_ptr(), corners.data_ptr(), out.data_ptr(), wp, wn)
     return out
 
 

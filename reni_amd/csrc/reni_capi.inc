@@ -31,7 +31,8 @@ struct reni_plan {
   // on the caller's stream instead of a forked one
   int no_persist, no_side_stream, dw1_old;  // (RENI_DW1_OLD: k_reni_dw1 instead of k_reni_dw1_ring -- the A/B switch of profiles/tools)
   int no_l0x;          // RENI_NO_L0X: layer 0's backward stays inside the training kernel (round 4's split) instead of k_reni_l0_ring
-  int env_overrides;   // which of them the environment set: 1 RENI_NO_PERSIST, 2 RENI_NO_SIDE_STREAM, 4 RENI_FRAG_WS_CAP_MB, 8 RENI_DW1_OLD, 16 RENI_NO_L0X
+  int train_wg;        // RENI_TRAIN_WG=n: at most n workgroups for the persistent training instances (0: one per CU) -- longer tile ranges at small shapes
+  int env_overrides;   // which of them the environment set: 1 RENI_NO_PERSIST, 2 RENI_NO_SIDE_STREAM, 4 RENI_FRAG_WS_CAP_MB, 8 RENI_DW1_OLD, 16 RENI_NO_L0X, 32 RENI_TRAIN_WG
                        // (reni_path_info reports it, bench.py prints it: a stray variable must not silently change what is measured)
   size_t frag_ws_cap;  // bytes of stash + fragment stream one chunk of the H = 256 training path may use (run_backward_chunked);
                        // RENI_FRAG_WS_CAP_MB overrides the 3 GB default (tests force the chunked path at small sizes with it)
@@ -179,6 +180,9 @@ Layout make_layout(const reni_plan* p, const GeoRt& g, int64_t B, int64_t P, uin
     const int rounds = (l.n_tiles + cap - 1) / cap;
     l.nwg = (l.n_tiles + rounds - 1) / rounds;
   }
+  // (RENI_TRAIN_WG: fewer workgroups for the persistent training instances -- every one a longer contiguous range; the tests reach
+  //  ranges of one, two and more tiles at shapes of a few tiles with it)
+  if (l.pdw && p->train_wg > 0 && p->train_wg < l.nwg) l.nwg = p->train_wg;
   if (l.nwg < 1) l.nwg = 1;
   size_t o = 0;
   for (int st = 0; st < 2; ++st) {  // (two copies: see `stage`; 0.7 MB each at config 2)
@@ -483,7 +487,10 @@ struct DeviceGuard {
 // prologue shared by all entry points: A_b / xconst and the packed weight images
 int run_prologue(const reni_plan* p, const GeoRt& g, const Layout& l, int64_t B, const float* Z,
                  const float* params, char* ws, bool backward, hipStream_t s, const int64_t* idx = nullptr,
-                 const float* film_A = nullptr, int64_t n_rows = 0) {
+                 const float* film_A = nullptr, int64_t n_rows = 0, bool shared_img = false) {
+  // shared_img (BwdPath::l0x): the L0X training instance reads ONE image per hidden layer in both passes -- the forward images of the
+  // hidden layers are written in the shared cell order (PackDesc::swz) and the W^T images of layers >= 2 are not packed at all
+  // (layer 1's stays: k_reni_l0_ring's resident operand; the head's: resident in the training kernel)
   const int H = p->d.hidden_features, L = p->d.hidden_layers;
   const bool film = p->d.conditioning == RENI_COND_FILM;
   reni::PrepArgs pa;
@@ -505,7 +512,7 @@ int run_prologue(const reni_plan* p, const GeoRt& g, const Layout& l, int64_t B,
     const bool head = (i == L + 1);
     reni::PackDesc d;
     d.src = p->p_off_w[i]; d.bias_src = p->p_off_b[i]; d.dst = l.fwd_off[i];
-    d.M = head ? 3 : H; d.K = H; d.transposed = 0;
+    d.M = head ? 3 : H; d.K = H; d.transposed = 0; d.swz = (shared_img && !head) ? 1 : 0;
     d.nrb = head ? 1 : g.nrb; d.nks = g.nks;
     d.bias_n = head ? 3 : H; d.bias_n_pad = head ? 32 : H;
     // persistent training kernel: omega / 2 pi rides on the hidden forward images (its sine argument is in
@@ -517,8 +524,8 @@ int run_prologue(const reni_plan* p, const GeoRt& g, const Layout& l, int64_t B,
     //  frequency -- reni_dev_wide.inc)
     if (film && l.persist && H == 256 && !head) d.scale = 0.15915494309189535f;
     ka.d[n++] = d;
-    if (backward) {
-      d.dst = l.bwd_off[i]; d.transposed = 1;
+    if (backward && !(shared_img && i >= 2 && !head)) {
+      d.dst = l.bwd_off[i]; d.transposed = 1; d.swz = 0;
       d.nrb = g.nrb; d.nks = head ? g.head_bwd_ks : g.nks;
       d.bias_n = 0; d.bias_n_pad = 0;
       d.scale = !l.persist ? 1.f : film ? ((i == 1 || H == 256) ? 1.f : 6.283185307179586f) : (i == 1 ? p->d.first_omega_0 : p->d.hidden_omega_0);
@@ -763,6 +770,7 @@ struct Bwd {
   hipStream_t s, se;       // the caller's stream; the side stream once forked (else = s)
   const float* Z;          // the call's latents: the batch's rows, gathered by k_prep_image, when the call came with a table and indices
   int stage_in;            // the copy the previous call staged this call's prologue into, -1: it staged none
+  bool staged_shared;      // ... with the hidden layers' images in the shared form (run_prologue's shared_img)
   float *img_loss, *stats, *dA, *part2;
   ListDst ld;
   reni::LayerScale lsc;
@@ -840,6 +848,7 @@ int bwd_layout(Bwd& x) {
   const BwdCall& c = x.c;
   const bool staged = c.fuse && (*c.fuse->state & 1u);          // this call's prologue was run by the previous call
   x.stage_in = staged ? (int)((*c.fuse->state >> 1) & 1u) : -1;
+  x.staged_shared = staged && ((*c.fuse->state >> 2) & 1u);
   x.l = make_layout(x.p, x.g, c.B, c.P, c.flags, true, true, staged ? x.stage_in : 0);
   const Layout& l = x.l;
   if (c.ws_bytes < l.total) return fail(RENI_EWORKSPACE, "workspace too small: need %zu bytes, got %zu", l.total, c.ws_bytes);
@@ -888,6 +897,17 @@ void bwd_main_args(Bwd& x) {
   }
   a.loss_kind = (c.loss_kind == LOSS_DOUT) ? LOSS_DOUT : (call_uses_cos(c) ? 1 : 0);  // (the statistics pass takes a copy with its own)
   x.path = bwd_path(x.p, x.l, c, a, x.stage_in);
+  if (x.path.l0x) {
+    // Shared images: the dX operand of the steps of layers L..2 is Wf_l^T, not 8 Wf_l^T.  The L - 1 factors of 8 ride on d loss / d y
+    // instead, so that g_1 -- the stream k_reni_l0_ring reads -- and everything behind it are what they were, bit for bit; g_l (l >= 2)
+    // and with it the partials of dW_l / db_l are 8^(l-1) times what they were, the head's 8^(L-1) times, and their constants
+    // (reni::LayerScale) give the powers of two back: every product exact (DESIGN.md section 4.2f).
+    const int L = x.p->d.hidden_layers;
+    float up = 1.f;
+    for (int i = 1; i < L; ++i) { up *= 8.f; x.lsc.c[i] /= up; }
+    a.gy_scale *= up;
+    x.lsc.c[L] /= up;
+  }
 }
 
 // BwdPath::sparse: bind the caller's cached lists or build them in the workspace; BwdPath::cos_const: the cached zero coefficients
@@ -1158,8 +1178,10 @@ int bwd_fused_step(Bwd& x, SideJoin& side_join) {
   RENI_LAUNCH(reni::k_adam2, dim3((unsigned)(ad.nb_dec + (ad.tn + 255) / 256 + ad.nb_l1)), dim3(256), 0, s, ad);
   if (fu.idx_next) {
     const Layout ln = make_layout(p, x.g, c.B, c.P, c.flags, true, true, 1 - path.stage);
-    if (const int rc = run_prologue(p, x.g, ln, c.B, fu.table, fu.params, x.ws, true, s, fu.idx_next, nullptr, c.n_rows)) return rc;
-    *fu.state = 1u | ((uint32_t)(1 - path.stage) << 1);
+    // (the images are packed for the kernels THIS call ran -- the next call of a training loop runs the same; bit 2 says which, and a
+    //  call that decides otherwise runs its own prologue: run_backward)
+    if (const int rc = run_prologue(p, x.g, ln, c.B, fu.table, fu.params, x.ws, true, s, fu.idx_next, nullptr, c.n_rows, path.l0x)) return rc;
+    *fu.state = 1u | ((uint32_t)(1 - path.stage) << 1) | (path.l0x ? 4u : 0u);
   }
   return RENI_OK;
 }
@@ -1176,7 +1198,9 @@ int run_backward(const reni_plan* p, const BwdCall& c) {
   if ((rc = bwd_layout(x))) return rc;
   bwd_layer_scales(x);
   bwd_main_args(x);  // (+ BwdPath: from here on every decision is on record)
-  if (!x.path.staged && (rc = run_prologue(p, x.g, x.l, c.B, c.Z, c.params, x.ws, true, x.s, c.idx, c.fio ? c.fio->A : nullptr, c.n_rows))) return rc;
+  // (a staged prologue whose images are not in the form this call's kernels read is not used: the call packs its own, into the same copy)
+  if (x.path.staged && x.staged_shared != x.path.l0x) x.path.staged = false;
+  if (!x.path.staged && (rc = run_prologue(p, x.g, x.l, c.B, c.Z, c.params, x.ws, true, x.s, c.idx, c.fio ? c.fio->A : nullptr, c.n_rows, x.path.l0x))) return rc;
   if ((rc = bwd_weight_lists(x))) return rc;
   if ((rc = bwd_stats_pass(x))) return rc;
   rc = x.l.persist ? launch_train(p, x.a, x.l.nwg, x.s, false, x.path.l0x) : launch_main(p, reni::MODE_FWD_BWD, x.a, x.l.nwg, x.s);
@@ -1463,6 +1487,7 @@ int reni_plan_create(const reni_desc* d, reni_plan** out) {
     }
   }
   if (const char* e = getenv("RENI_FRAG_WS_CAP_MB")) { const long long mb = atoll(e); if (mb > 0) { p->frag_ws_cap = (size_t)mb << 20; p->env_overrides |= 4; } }
+  if (const char* e = getenv("RENI_TRAIN_WG")) { const int n = atoi(e); if (n > 0) { p->train_wg = n; p->env_overrides |= 32; } }
   p->env_overrides |= (p->no_persist ? 1 : 0) | (p->no_side_stream ? 2 : 0) | (p->dw1_old ? 8 : 0) | (p->no_l0x ? 16 : 0);
   const int nd = d->ndims, H = d->hidden_features, L = d->hidden_layers;
   if (d->conditioning == RENI_COND_FILM) {

@@ -439,7 +439,8 @@ DEV void pack_body(const PackArgs& a, const int bx, const int by, const int gx) 
         else { if (Fk < d.M && R < d.K) val = a.params[d.src + (size_t)Fk * d.K + R]; }
         o[e] = (__bf16)(val * d.scale);
       }
-      *(bf16x8*)(a.wimg + d.dst + (size_t)t * 16) = o;
+      const int cell = d.swz ? (t ^ ((hi << 2) | ((ks & 1) << 3))) : t;  // (a shared image: wimg_cell, reni_dev_train.inc)
+      *(bf16x8*)(a.wimg + d.dst + (size_t)cell * 16) = o;
     } else {
       const int Fk = kfeat<Pol>(ks, hi, 0);
       float val = 0.f;

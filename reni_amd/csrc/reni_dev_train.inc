@@ -108,6 +108,23 @@ DEV void dma_group(const DmaJob& jb, int g, int wave, int nwaves = 4) {
 }
 constexpr int DMA_GROUPS = 3;  // per wave: 4 x 3 x 3 KB = 36 KB >= the largest image
 struct NoFill { DEV void operator()(int) const {} DEV void operator()(int, int) const {} };
+// SHARED weight image (the L0X training instance: one image per hidden layer serves the forward GEMM and the backward step's dX GEMM).
+// Fragment (row block, k-step ks) of the forward layout is 1 KB = 64 cells of 16 bytes, cell = lane; in a shared image lane (hi, r)'s cell
+// sits at lane ^ (4 hi + 8 (ks & 1)) -- written so by k_pack (PackDesc::swz), copied as it lies by the LDS-DMA.  The forward ds_read_b128
+// stays free of bank conflicts (an XOR with a constant per 32-lane half), and so are the transposing 8-byte reads that assemble the
+// fragments of W^T from it (wimg_tr_base): the two halves of a k pair (hi) and the two k-steps of a column group (ks & 1), which lie
+// 512 B and 1 KB apart -- the same banks -- in the plain layout, land in different 64-byte quarters of the 256-byte bank row.
+DEV int wimg_cell(int lane, int ks) { return lane ^ (((lane >> 5) << 2) | ((ks & 1) << 3)); }
+// per-lane byte offset (row block 0 of W^T, k-step 0, first half) of the transposing reads of a shared image.  A bf16 fragment holds the
+// k indices kfeat(ks, hi, e) = 16 ks + 4 hi + (e & 3) + 8 (e >> 2): its 8-byte half e >> 2 is four consecutive k.  Fragment (kb, s) of W^T
+// needs, in lane (khi, j), W[16 s + 8 q + 4 khi + 0..3][32 kb + j] in half q, so source lane (khi, g, u) of read q supplies row
+// o = 8 q + 4 khi + (u >> 2) of W, columns 16 g + 4 (u & 3) .. + 3: forward fragment k-step g (+ 2 per row block kb), its half hi = u & 1,
+// 8-byte half (u >> 1) & 1 of cell o.  Second read (q = 1): ^ 128; row block kb of W^T: + 2048 kb; k-step s: + 8192 (s >> 1) + 256 (s & 1)
+// -- immediates.
+DEV unsigned wimg_tr_base(int lane) {
+  const int khi = lane >> 5, g = (lane >> 4) & 1, u = lane & 15, h = u & 1;
+  return (unsigned)(g * 1024 + h * 512 + (((4 * khi + (u >> 2)) ^ (4 * h + 8 * g)) << 4) + ((u >> 1) & 1) * 8);
+}
 
 // acc[rbo] (+)= W-image[rbo] . bop   (row-block-outer order so the caller's per-row-block epilogue
 // overlaps the next row block's MFMAs)
@@ -135,12 +152,26 @@ DEV f32x16 gemm_rb(const char* wb, int rbo, const bf16x8 (&bop)[NKS], f32x16 acc
 
 // two row blocks at once: their MFMA chains are independent, so alternating them keeps the matrix pipe
 // busy instead of waiting out each dependent-accumulator latency
-template <int NKS, class F = NoFill, bool ZERO = false>
+// SWZ: the image is a SHARED one (wimg_cell): the lane's 16-byte cell of fragment (row block, k-step) is XOR-ed with 4 hi + 8 (ks & 1)
+template <int NKS, class F = NoFill, bool ZERO = false, bool SWZ = false>
 DEV void gemm_rb2(const char* wb, int rbo0, const bf16x8 (&bop)[NKS], f32x16& acc0, f32x16& acc1, int lane,
                   const F& fill = F()) {  // ZERO: the accumulators start at zero (inline-constant SrcC, nothing to initialise)
   // A fragments are fetched two k-steps ahead of the MFMAs that use them (three and four: no faster, measured): with four waves and the LDS-DMA
   // writes on the LDS at once a ds_read_b128 takes longer than two MFMA pairs
-  auto fa = [&](int r, int ks) { return *(const bf16x8*)(wb + (((rbo0 + r) * NKS + ks) * 64 + lane) * 16); };
+  // (SWZ: two per-lane bases, the cell XOR-ed with 4 hi and -- odd k-steps -- with 8: an XOR of the address with 128, the buffers being
+  // 1 KB aligned.  Both made HERE, per GEMM, and opaque: kept across the tile they would be two registers the instance does not have;
+  // made at every odd k-step's read they were sixteen more VALU instructions per layer in an issue-bound kernel)
+  typedef __attribute__((address_space(3))) const bf16x8* lbp;
+  unsigned sb = SWZ ? (unsigned)(size_t)wb + (unsigned)(wimg_cell(lane, 0) * 16) : 0u, sb1 = sb ^ 0x80u;
+  if constexpr (SWZ) asm volatile("" : "+v"(sb), "+v"(sb1));
+  auto fa = [&](int r, int ks) {
+    if constexpr (SWZ) {
+      const unsigned ad = (ks & 1) ? sb1 : sb;
+      return *(lbp)(uintptr_t)(ad + (unsigned)(((rbo0 + r) * NKS + ks) * 1024));
+    } else {
+      return *(const bf16x8*)(wb + (((rbo0 + r) * NKS + ks) * 64 + lane) * 16);
+    }
+  };
   constexpr int D = NKS >= 2 ? 2 : 1;
   bf16x8 q0[D], q1[D];
 #pragma unroll
@@ -263,10 +294,11 @@ DEV TsBase ts_base(const char* T, int lane) {
   return b;
 }
 // block blk (its 64-byte column group XORs into the low address byte), k-step ks (an immediate offset)
-DEV bf16x8 ts_read(const TsBase& b, int blk, int ks) {
+// (img_off: the same fragment of the image that lies img_off bytes behind b's -- one more immediate, no bases of its own)
+DEV bf16x8 ts_read(const TsBase& b, int blk, int ks, unsigned img_off = 0) {
   typedef __attribute__((address_space(3))) s16x4* lp;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(uintptr_t)((b.q[0] ^ (unsigned)(blk << 6)) + (unsigned)(ks * 4096)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(uintptr_t)((b.q[1] ^ (unsigned)(blk << 6)) + (unsigned)(ks * 4096)));
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(uintptr_t)((b.q[0] ^ (unsigned)(blk << 6)) + (unsigned)(ks * 4096) + img_off));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(uintptr_t)((b.q[1] ^ (unsigned)(blk << 6)) + (unsigned)(ks * 4096) + img_off));
   typedef short s16x8 __attribute__((ext_vector_type(8)));
   const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8, v);
@@ -352,8 +384,13 @@ DEV void dw_gemm_s(const char* TA, const char* TB, f32x16 (&acc)[NBC], float& db
 // step of layer 2 -- whose dX epilogue produces g_1 -- and the g_1 stream's stores; layer 1's dX GEMM, its cosine epilogue, the
 // layer-0 phase rebuild and the dA GEMM (13 % of a tile: profiles/r04_cycle_trace.txt, tags 191-214 and 8-9) are done by
 // k_reni_l0_ring (reni_dev_l0ring.inc), which reads the g_1 stream anyway, holds W_1^T in registers and is bound by HBM, not by
-// issue.  A tile then consumes 2 L + 1 weight images (odd): the LDS buffer of image k alternates with the TILE's parity as well
-// (`wpar`), so that the next tile's first image never lands in the buffer the last step reads.  The g_1 stream is stored with its
+// issue.  ONE weight image per hidden layer serves both passes (SHARED images: wimg_cell): the backward step of layer l reads
+// W_l^T out of the forward image with transposing reads, in the buffer the forward pass used for it -- layer l's image lives in buffer
+// (l - 1) & 1, whatever the tile.  Copies per tile (L = 5: six, where two images per layer made nine): the forward pass loads layers
+// 3 .. L (layer 1's came with the previous tile's last step, layer 2's is still in its buffer from that step; the FIRST tile of a range
+// loads both), the backward pass finds layers L and L - 1 where the forward pass left them and loads L - 2 .. 2, and the last step
+// (layer 2's, reading buffer 1) fetches the next tile's layer 1 into buffer 0 -- nothing after the range's last tile.  Every copy goes
+// into the buffer whose last reader lies behind the barrier the copy is issued after.  The g_1 stream is stored with its
 // 16-byte cells XOR-swizzled (cell ^ 4 hi ^ 8 (chunk & 1)): both of the ring kernel's reads of the raw slot -- plain b128 operands and
 // the transposing reads -- are then free of LDS bank conflicts.
 template <int H, bool DW, bool STATS = false, bool FILM = false, bool SPEC = false, bool L0X = false>
@@ -414,7 +451,6 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
   float* const dwp = a.dwp + (size_t)blockIdx.x * a.dwp_per_wg;
   const int L = a.L;
   const int nstep = L0X ? 2 * L + 1 : 2 * L + 2;  // weight images consumed per tile (L0X: no step for layer 1)
-  int wpar_v = 0;                                    // (L0X) parity of the tile within the workgroup's range: see the header
 
   static_assert(MYB_H == 4, "sixteen AGPR tiles = 4 layers x 4 column blocks");
   if constexpr (DW) agpr_zero_seq(std::make_integer_sequence<int, 256>{});  // dW_2..dW_5 accumulators: a[0:255]
@@ -449,11 +485,15 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
   // then hidden bwd for layer 2L+2-k.  Buffer = k & 1.
   const char* wimg_f1 = a.wimg + a.fwd_off[1];  // layer 1's forward / W^T image; layer l's = + (l - 1) strides (GeoP)
   const char* wimg_b1 = a.wimg + a.bwd_off[1];
-  auto make_job = [&](int k, bool next_tile = false) -> DmaJob {
+  auto make_job = [&](int k) -> DmaJob {
     if (k == L || k == L + 1) k = STATS ? 0 : L + 2;  // the head steps use the resident images: next in line is layer L's W^T
                                                       // (statistics instance: the next tile's first image)
-    const int wpar = L0X ? (wpar_v ^ (next_tile ? 1 : 0)) : 0;
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(smem + ((k ^ wpar) & 1) * GP::WBSZ));
+    if constexpr (L0X) {  // the shared image of the step's layer (bias included: the next forward pass may find it resident), buffer (layer - 1) & 1
+      const int layer = k < L ? k + 1 : 2 * L + 2 - k;
+      const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(smem + ((layer - 1) & 1) * GP::WBSZ));
+      return DmaJob{wimg_f1 + (unsigned)(layer - 1) * GP::FWD_STRIDE, (unsigned)lane16, dst, (G::IMG_HID + G::BIAS_HID + 3071) / 3072};
+    }
+    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(smem + (k & 1) * GP::WBSZ));
     const char* img;
     int bytes;
     if constexpr (FILM && DW && !SPEC) {  // (the generic FiLM training instance has not one register for the two bases: 254 of 256, see DESIGN.md)
@@ -577,6 +617,8 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
     // reloaded at the end of every tile)
     const int jx = L0X ? (int)(((unsigned)lane16 >> 4) & 31u) : j, hix = L0X ? (int)((unsigned)lane16 >> 9) : hi;
     const int j = jx, hi = hix;  // (shadow the kernel-wide coordinates for the whole tile body; the other instances: the same values)
+    // (L0X: the lane the shared images' read bases are formed from -- wimg_cell, wimg_tr_base -- for the same reason)
+    const int lanex = L0X ? (int)((unsigned)lane16 >> 4) : lane;
     TRACE(1);
     // this wave's tile; a half without one (odd tile count) runs on the last tile's addresses with everything masked
     const bool tvalid = tile0 + half < t_stop;
@@ -787,6 +829,9 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       }
       TRACE(10 + l);
       DmaJob jb = make_job(l);  // next step's image: one group per k-step of the first GEMM below
+      // (L0X, shared images: layer L's is still in its buffer at the first backward step; layer 2's is there from the previous tile's
+      // last step -- in every tile of the range but the first)
+      if (L0X && (l == L || (l == 1 && tile0 != t_first))) jb.ng = 0;
       // statistics instance, last layer: the next image is the next tile's first, into buffer 0 -- which this very layer
       // reads when L is odd (then it is issued behind a barrier after the GEMMs, below)
       if (STATS && l == L && ((L & 1) || last_tile)) jb.ng = 0;
@@ -797,7 +842,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       // fillers of the first GEMM (rows 0..63): behind the MFMAs of k-steps 0..3 (they read only row blocks 0 and 1 of the
       // layer below) the PENDING row blocks 2 and 3 of the layer below are activated, two pairs per MFMA; the layer
       // below's eight phase chunks go to the stash one per k-step.
-      const char* wb = smem + (((l - 1) ^ (L0X ? wpar_v : 0)) & 1) * GP::WBSZ;
+      const char* wb = smem + ((l - 1) & 1) * GP::WBSZ;
       const float* bias = (const float*)(wb + G::IMG_HID);
       auto fill = [&](int ks, int part) {
         if (part == 0 && ks < DG) dma_group(jb, ks, wave, NW);
@@ -855,16 +900,17 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         acc1[r] = bias[32 + rowmap(r, hi)];
       }
       TRACE(100 + l);
-      gemm_rb2<NKS>(wb, 0, hin, acc0, acc1, lane, fill);
+      gemm_rb2<NKS, std::decay_t<decltype(fill)>, false, L0X>(wb, 0, hin, acc0, acc1, lanex, fill);
       TRACE(110 + l);
-      gemm_rb2<NKS>(wb, 2, hin, poa, pob, lane, [&](int ks, int part) {
+      auto fill2 = [&](int ks, int part) {
         if constexpr (FILM) {  // the two pairs that share one table fetch sit in consecutive slots (one live FilmQ, not two)
           if ((ks & 1) == 0) act_pair(acc0, 0, ks + part, hout, tp_cur, &fs0);
           else act_pair(acc1, 1, ks - 1 + part, hout, tp_cur, &fs0);
         } else {
           if (part == 0) act_pair(acc0, 0, ks, hout); else act_pair(acc1, 1, ks, hout);
         }
-      });
+      };
+      gemm_rb2<NKS, decltype(fill2), false, L0X>(wb, 2, hin, poa, pob, lanex, fill2);
       TRACE(120 + l);
       if (STATS && l == L && (L & 1) && !last_tile) {
         __syncthreads();  // every wave is done reading buffer 0
@@ -905,7 +951,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = bias[rowmap(r, hi)];
-      acc = gemm_rb<NKS>(wb, 0, hb, acc, lane);
+      acc = gemm_rb<NKS>(wb, 0, hb, acc, lanex);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         ylin[c] = acc[c];
@@ -1013,7 +1059,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
                              const float* tq = nullptr) {
       constexpr int NK = decltype(nks_tag)::value;
       f32x16 acc0, acc1;
-      gemm_rb2<NK, std::decay_t<decltype(fill)>, true>(wb, rbi, bop, acc0, acc1, lane, fill);
+      gemm_rb2<NK, std::decay_t<decltype(fill)>, true>(wb, rbi, bop, acc0, acc1, lanex, fill);
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
         float r0, r1;
@@ -1099,13 +1145,36 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         const unsigned off = ((t ^ ((t >> 3) & 64u)) ^ (unsigned)((c & 1) << 7)) + (unsigned)(c * 4096);
         asm volatile("global_store_dwordx4 %0, %1, %2" :: "v"(off), "v"(ghb[c]), "s"(g1b) : "memory");
       };
-      const TsBase bA = ts_base(TA, lane), bB = ts_base(TB, lane);
-      auto fx = [&](int i) { return *(const bf16x8*)(wb + (((i >> 3) * NKS + (i & 7)) * 64 + lane) * 16); };
+      // (L0X: TB lies TSZ bytes behind TA, so its fragments are read from TA's bases with one more immediate -- the two registers of
+      // bases of its own are the ones the shared image's second read base takes: rdB, xq1)
+      const TsBase bA = ts_base(TA, lanex), bB = L0X ? bA : ts_base(TB, lanex);
+      auto rdB = [&](int m, int ks) { return L0X ? ts_read(bA, m, ks, (unsigned)GP::TSZ) : ts_read(bB, m, ks); };
+      // (L0X: the A operand of the dX GEMM is fragment (row block i >> 3, k-step i & 7) of W_l^T read out of the layer's SHARED image --
+      // two transposing reads, every address one base made here plus immediates: wimg_tr_base)
+      unsigned xq = 0, xq1 = 0;
+      if constexpr (L0X) {
+        xq = lds_u32(wb) + wimg_tr_base(lanex);
+        xq1 = xq ^ 0x80u;  // (the second read's base: per fragment it was 32 more VALU instructions per step)
+        asm volatile("" : "+v"(xq), "+v"(xq1));  // (keeps the bases out of the tile loop's invariants: see ts_write)
+      }
+      auto fx = [&](int i) {
+        if constexpr (L0X) {
+          typedef __attribute__((address_space(3))) s16x4* lp;
+          typedef short s16x8 __attribute__((ext_vector_type(8)));
+          const unsigned off = (unsigned)((i >> 3) * 2048 + ((i & 7) >> 1) * 8192 + (i & 1) * 256);
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(uintptr_t)(xq + off));
+          const s16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(uintptr_t)(xq1 + off));
+          const s16x8 v = {lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
+          return __builtin_bit_cast(bf16x8, v);
+        } else {
+          return *(const bf16x8*)(wb + (((i >> 3) * NKS + (i & 7)) * 64 + lane) * 16);
+        }
+      };
       constexpr int D = 2;  // (W^T fragments in flight: two slots = four MFMAs ahead; a third set is four registers the kernel does not have)
       bf16x8 q[D];
 #pragma unroll
       for (int d = 0; d < D; ++d) q[d] = fx(d);
-      bf16x8 fa = ts_read(bA, wave, 0), fan = fa, fb0 = ts_read(bB, 0, 0), fb1 = ts_read(bB, 1, 0), fb2 = ts_read(bB, 2, 0), fb3 = ts_read(bB, 3, 0);
+      bf16x8 fa = ts_read(bA, wave, 0), fan = fa, fb0 = rdB(0, 0), fb1 = rdB(1, 0), fb2 = rdB(2, 0), fb3 = rdB(3, 0);
       f32x16 a0, a1, a2, a3;
       f32x4 fq4;
       auto slot = [&](auto ic, f32x16& acc, const f32x16& accp) {
@@ -1121,10 +1190,10 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         if (i == 31) mfma_bf16_agpr_tile<BASE + m, true, TAIL_DWDX_A>(fa, bx);
         else mfma_bf16_agpr_tile<BASE + m, false>(fa, bx);
         if constexpr (kk < 7) {  // the next k-step's fragments: B fragment m behind its use, the A fragment behind the k-step's first MFMA
-          if (m == 0) { fb0 = ts_read(bB, 0, kk + 1); fan = ts_read(bA, wave, kk + 1); }
-          else if (m == 1) fb1 = ts_read(bB, 1, kk + 1);
-          else if (m == 2) fb2 = ts_read(bB, 2, kk + 1);
-          else fb3 = ts_read(bB, 3, kk + 1);
+          if (m == 0) { fb0 = rdB(0, kk + 1); fan = ts_read(bA, wave, kk + 1); }
+          else if (m == 1) fb1 = rdB(1, kk + 1);
+          else if (m == 2) fb2 = rdB(2, kk + 1);
+          else fb3 = rdB(3, kk + 1);
         }
         if constexpr (m == 3) { dbacc = frag_sum<PolBF16>(fa, dbacc); fa = fan; }  // (bias-gradient sums of the k-step)
         if constexpr (i % 4 == 2 && i / 4 < DG) dma_group(jb, i / 4, wave, NW);  // next step's image, one group per dW k-step
@@ -1284,8 +1353,9 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
         }
       }
       // next step's image (or the next tile's first): one LDS-DMA group per k-step of the GEMM below
-      DmaJob jb = make_job(k + 1 < nstep ? k + 1 : 0, LASTSTEP);  // (L0X: k + 1 == nstep in the last step)
+      DmaJob jb = make_job(k + 1 < nstep ? k + 1 : 0);  // (L0X: k + 1 == nstep in the last step)
       if (k + 1 >= nstep && last_tile) jb.ng = 0;
+      if (L0X && l == L) jb.ng = 0;  // (shared images: layer L - 1's is still in the other buffer)
       TRACE(70 + l);
       // (l == 2: instead of layer 0's phases, the image's layer-0 A operands, through the SAME eight loads -- no second
       // code path: with the 512-byte chunk stride and the lane offset, chunk 2r is operand r of this lane; the odd chunks are
@@ -1303,7 +1373,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       if constexpr (!L0X) { if (l == 1) load_d(dre); }  // for the dA phase after the loop; in flight during the dX GEMM
       if constexpr (L0X) { if (l == 2) dma_dirs(last_tile ? cur_b : nxt_b, last_tile ? cur_tin : nxt_tin); }  // the next tile's directions
       if constexpr (L0X) { if (l == L) dma_tw(last_tile ? cur_b : nxt_b, last_tile ? cur_tin : nxt_tin); }  // ... target / weight rows
-      const char* wb = smem + ((k ^ (L0X ? wpar_v : 0)) & 1) * GP::WBSZ;
+      const char* wb = smem + ((L0X ? l - 1 : k) & 1) * GP::WBSZ;  // (L0X: the buffer the forward pass used for this layer)
       const float* const tq_prev = FILM ? ftab + (l - 1) * 2 * H : nullptr;  // frequencies of layer l - 1 (slot 0: ones)
       {
         const bool had_dw = DW && l >= 2;  // (then the image's groups went behind the dW GEMM's k-steps)
@@ -1375,9 +1445,7 @@ __global__ void __launch_bounds__(DW ? 256 : 512, 1) k_reni_train_bf16(const Mai
       // g_1 stores (the next tile's first barrier has no vmcnt; tests/test_build_audit.py checks the order on the emitted ISA)
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
 #pragma unroll
-      for (int rbo = 0; rbo < NRB; ++rbo) aop0_n[rbo] = __builtin_bit_cast(bf16x8, wB[2 * rbo]);
-      wpar_v ^= 1;
-    } else
+      for (int rbo = 0; rbo < NRB; ++rbo) aop0_n[rbo] = __builtin_bit_cast(bf16x8, wB[2 * rbo]);    } else
     // ---- layer 0: dA (per tile) = g_0 (x_hi | x_lo)^T
     {
       bf16x8 xcb[2];

@@ -20,6 +20,8 @@ struct MainArgs {
   // multiples (x 8) of the forward images' rounded weights -- the backward pass is the transpose of the very network the forward pass
   // evaluates -- and the constant that is then missing from the gradient, (2 pi)^L omega_first / 8^(L+1), rides on d loss / d y (the
   // weight gradients' per-layer constants are multiplied back where their partials are summed: reni::LayerScale).  1 everywhere else.
+  // (The L0X training instance reads the forward images themselves in the backward steps of layers L .. 2 -- no factor 8 there -- and
+  // takes 8^(L-1) times this value: bwd_main_args, reni_capi.inc.)
   float gy_scale;
   // inputs
   const float* Z;
@@ -136,6 +138,7 @@ struct PackDesc {
   int nrb, nks;       // image geometry
   int bias_n, bias_n_pad;
   float scale;        // every weight and bias of the image is multiplied by this (1 = plain copy)
+  int swz;            // 1: a SHARED image of the L0X training instance -- lane (hi, r)'s cell of fragment (rb, ks) sits at lane ^ (4 hi + 8 (ks & 1)): wimg_cell
 };
 
 struct PackArgs {

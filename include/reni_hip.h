@@ -480,6 +480,44 @@ int reni_soft_silhouette_backward(int64_t V, int64_t F, const float* verts, cons
                                   const float* grad_alpha, const int64_t* vf_offsets, const int64_t* vf_corners,
                                   float* grad_verts, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- camera gradients of the G-buffer and of the soft silhouette: R, T and tan_half_fov (reni_tu_camera.hip) -------------
+ * What the two backwards above hold constant: the pose.  With q = p R + T, t = tan_half_fov, x = q_x / (q_z t),
+ * y = q_y / (q_z t) as above, let (tx_fk, ty_fk) be the gradient of the scalar objective with respect to the NDC position of
+ * corner k of face f:
+ *   soft silhouette   the corner's NDC sums of reni_soft_silhouette_backward (d sd / da, d sd / db over the face's pairs)
+ *   G-buffer          the barycentric path alone: the corner's sums through the edge functions plus (d L / dA) dA / d(x, y)_k.
+ *                     The vertex normals and the direct weights of X_p are world-space and do not see the camera.
+ * Both kernels already form the view-space gradient of the corner, g_q = (tx / (z t), ty / (z t), -(tx x + ty y) / z).  Then,
+ * with p_fk the corner's world position,
+ *   gT[j]    = sum_{f,k} g_q,fk[j]
+ *   gR[i][j] = sum_{f,k} p_fk[i] g_q,fk[j]          (row-major, R's own layout; R is differentiated as nine free numbers)
+ *   g_tan    = -sum_{f,k} (tx_fk x_fk + ty_fk y_fk) / t
+ * Held constant, as in the vertex gradients: the face assignment; membership, inside, the winning edge and a clamped t;
+ * blur_radius and the grown boxes; 1e-8.  A face the forward skips, or one that does not take part, adds exactly 0.
+ * grad_camera [13] (device) = gR [9], gT [3], g_tan [1], overwritten.  fp32, no float atomics: per face the three corners are
+ * added in ascending order from 0, the faces are added by a store-then-sum reducer (chunks of 512 consecutive faces, a fixed
+ * lane stride, a fixed butterfly, the waves in ascending order, then the same pass over the chunk sums until one is left)
+ * whose order depends on F alone; two calls give identical bits.  Malformed input adds nothing and is never turned into an
+ * address.
+ * reni_gbuffer_backward_camera / reni_soft_silhouette_backward_camera: the arguments of reni_gbuffer_backward /
+ *   reni_soft_silhouette_backward with grad_camera behind grad_verts.  grad_verts, when given, gets the bits of those entry
+ *   points.  grad_verts, vf_offsets and vf_corners may be NULL together (the mesh is known, only the pose is fitted): the
+ *   vertex kernels are then not launched and no list is needed.  grad_camera must not be NULL.
+ *   ws: the _camera_workspace_bytes(V, F, H, W) of the entry point, 256-byte aligned. */
+size_t reni_gbuffer_backward_camera_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W);
+int reni_gbuffer_backward_camera(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* vert_normals,
+                                 const float* R, const float* T, float tan_half_fov, int64_t H, int64_t W,
+                                 const int64_t* pix_to_face, const int64_t* face_pixel_offsets, const int64_t* face_pixel_list,
+                                 const int64_t* vf_offsets, const int64_t* vf_corners, const float* grad_pixel_normals,
+                                 const float* grad_pixel_positions, float* grad_verts, float* grad_camera /* [13] device */,
+                                 void* ws, size_t ws_bytes, void* stream);
+size_t reni_soft_silhouette_backward_camera_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W);
+int reni_soft_silhouette_backward_camera(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* R,
+                                         const float* T, float tan_half_fov, int64_t H, int64_t W, float sigma, float blur_radius,
+                                         const float* trans, const float* grad_alpha, const int64_t* vf_offsets,
+                                         const int64_t* vf_corners, float* grad_verts, float* grad_camera /* [13] device */,
+                                         void* ws, size_t ws_bytes, void* stream);
+
 /* ---- cast shadows: visibility masks of the mesh for the shader (reni_tu_visibility.hip, the MASKED shader instances) ----
  * The shader above lets light pass through the mesh: M(p, j) knows the pixel's own normal and nothing else.  The lights are at
  * infinity, so whether texel direction j reaches pixel p is a constant of (mesh, camera, directions), as the G-buffer is.

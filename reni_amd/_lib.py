@@ -42,6 +42,8 @@ EXPORTS = (
     "reni_mesh_vertex_normals_backward", "reni_gbuffer_backward_workspace_bytes", "reni_gbuffer_backward",
     "reni_soft_silhouette_workspace_bytes", "reni_soft_silhouette", "reni_soft_silhouette_backward_workspace_bytes",
     "reni_soft_silhouette_backward",
+    "reni_gbuffer_backward_camera_workspace_bytes", "reni_gbuffer_backward_camera",
+    "reni_soft_silhouette_backward_camera_workspace_bytes", "reni_soft_silhouette_backward_camera",
     "reni_mesh_visibility_accel_bytes", "reni_mesh_visibility_prepare", "reni_mesh_visibility",
     "reni_envmap_shade_masked", "reni_envmap_shade_masked_backward",
     "reni_envmap_shade_terms_workspace_bytes", "reni_envmap_shade_terms", "reni_envmap_shade_terms_backward",
@@ -214,6 +216,15 @@ def load():
     lib.reni_soft_silhouette.restype = c_int32
     lib.reni_soft_silhouette_backward.argtypes = sil + [c_void_p] * 6 + [c_size_t, c_void_p]  # trans, gA, lists, grad_verts, ws ..
     lib.reni_soft_silhouette_backward.restype = c_int32
+    # the camera variants: the same arguments with grad_camera [13] behind grad_verts
+    for fn in (lib.reni_gbuffer_backward_camera_workspace_bytes, lib.reni_soft_silhouette_backward_camera_workspace_bytes):
+        fn.argtypes = [c_int64, c_int64, c_int64, c_int64]
+        fn.restype = c_size_t
+    lib.reni_gbuffer_backward_camera.argtypes = ([c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_float), POINTER(c_float),
+                                                  c_float, c_int64, c_int64] + [c_void_p] * 10 + [c_size_t, c_void_p])
+    lib.reni_gbuffer_backward_camera.restype = c_int32
+    lib.reni_soft_silhouette_backward_camera.argtypes = sil + [c_void_p] * 7 + [c_size_t, c_void_p]
+    lib.reni_soft_silhouette_backward_camera.restype = c_int32
     lib.reni_mesh_visibility_accel_bytes.argtypes = [c_int64]
     lib.reni_mesh_visibility_accel_bytes.restype = c_size_t
     lib.reni_mesh_visibility_prepare.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]

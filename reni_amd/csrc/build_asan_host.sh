@@ -6,7 +6,7 @@ set -e
 cd "$(dirname "$0")"
 mkdir -p _build/asan
 FLAGS="--offload-arch=gfx950 --cuda-host-only -O1 -g -std=c++17 -fPIC -fsanitize=address -fno-omit-frame-pointer -I../../include"
-UNITS="core main_f32 main_bf16 film_f32 film_bf16 train_film wide shade image raster raster_bwd baselines diffuse glossy glossy_bwd resample rotate metrics lights visibility texture splitsum"
+UNITS="core main_f32 main_bf16 film_f32 film_bf16 train_film wide shade image raster raster_bwd camera baselines diffuse glossy glossy_bwd resample rotate metrics lights visibility texture splitsum"
 pids=()
 rm -f _build/asan/*.o _build/asan/*.stub
 for tu in $UNITS; do

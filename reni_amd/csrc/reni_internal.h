@@ -114,6 +114,14 @@ int wide256_film_max_layers();  // hidden FiLM layers whose per-image tables fit
 int wide256_film_train_max_layers();  // ... and the training form's (4: the default model's; its tables alias the dA exchange alone)
 hipError_t launch_wide_head_dw(const MainArgs& a, int grid, hipStream_t s);
 
+// the camera gradient of the two mesh backwards (reni_tu_camera.hip): k_gb_face<true> / k_sil_face<true> write one record
+// of CAM_REC floats per face -- gR [9] row-major, gT [3], g_tan [1] -- and the reducer adds the records in an order that
+// depends on F alone.  part: camera_part_floats(F) floats of workspace for the chunk sums (none when F <= CAM_CHUNK).
+constexpr int CAM_REC = 13;
+constexpr int CAM_CHUNK = 512;  // records per workgroup of the reducer
+size_t camera_part_floats(int64_t F);
+int launch_camera_reduce(const float* rec, int64_t F, float* part, float* grad_camera, hipStream_t s);  // RENI_OK or the launch's error set
+
 struct PrepArgs {
   const long long* idx;  // optional: image b's latent is row idx[b] of Z (a latent TABLE); the batch's rows are copied to Zc
   long long n_rows;      // rows of that table: an index outside [0, n_rows) poisons the image's results with NaN

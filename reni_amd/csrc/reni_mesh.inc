@@ -1,5 +1,6 @@
 // reni_mesh.inc -- the ONE definition of what the mesh units share: reni_tu_raster.hip (rasteriser, vertex normals),
-// reni_tu_raster_bwd.hip (their gradients with respect to the vertex positions) and reni_tu_texture.hip (k_pixel_uv).
+// reni_tu_raster_bwd.hip (their gradients with respect to the vertex positions), reni_tu_silhouette.hip and reni_tu_texture.hip
+// (k_pixel_uv); the camera record of the two face kernels (mesh_camera_record).
 // pytorch3d's conventions restated from its documented behaviour, fp32, no float atomic: the camera and its projection, the
 // edge function, PixToNdc, kEpsilon, the barycentric weights, the rule by which a face is skipped, the walk of a vertex's
 // (face, corner) list and the sum u_v of the vertex normals; on the host the camera fill, MESH_MAX_ELEMS and the checks whose
@@ -63,6 +64,43 @@ DEV bool mesh_face(const Camera& cam, int V, const float* verts, const int64_t* 
   area = mesh_edge(x[0], y[0], x[1], y[1], x[2], y[2]);
   const float zmax = fmaxf(z[0], fmaxf(z[1], z[2]));
   return ok && !(zmax < 0.f) && !(fabsf(area) <= MESH_EPS);
+}
+
+// A face's camera record (reni_internal.h: gR [9] row-major, gT [3], g_tan [1]) from its corners' NDC gradients (tx, ty), NDC
+// positions (x, y), view z and world positions p: per corner g_q = (tx / (z t), ty / (z t), -(tx x + ty y) / z), then
+// gT += g_q, gR[i][j] += p[i] g_q[j] (q = p R + T: d q_j / d R[i][j] = p_i) and g_tan -= (tx x + ty y) / t, the corners in
+// ascending order from 0.  grad_verts must keep the bits of the CAM = false instance, and which of two products hipcc fuses
+// into an a b + c d of the vertex gradient depends on what else uses them.  So the face kernels call this behind a branch of
+// its own and hand it copies the compiler cannot see through (mesh_opaque) of the NDC gradients and the corners, not the g_q
+// they form for the vertices: nothing of the vertex gradient gets a second use.
+DEV float mesh_opaque(float v) {
+  asm volatile("" : "+v"(v));  // no instruction: v in a VGPR, its origin hidden
+  return v;
+}
+DEV void mesh_opaque3(const float (&v)[3], float (&o)[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) o[k] = mesh_opaque(v[k]);
+}
+DEV void mesh_camera_record(const Camera& cam, const float (&tx)[3], const float (&ty)[3], const float (&x)[3], const float (&y)[3],
+                            const float (&z)[3], const float (&p)[3][3], float* __restrict__ out) {
+  float cr[CAM_REC];
+#pragma unroll
+  for (int c = 0; c < CAM_REC; ++c) cr[c] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float wz = z[k] * cam.tan_half_fov, s = tx[k] * x[k] + ty[k] * y[k];
+    const float q[3] = {tx[k] / wz, ty[k] / wz, -s / z[k]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) cr[3 * i + j] += p[k][i] * q[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) cr[9 + j] += q[j];
+    cr[12] -= s / cam.tan_half_fov;
+  }
+#pragma unroll
+  for (int c = 0; c < CAM_REC; ++c) out[c] = cr[c];
 }
 
 // ---- the vertex -> (face, corner) list ---------------------------------------------------------------------------------

@@ -22,6 +22,9 @@
 //                  which has no workspace; the thread's own vertex once), the same arithmetic; u_v is mesh_u, the sum
 //                  k_vertex_normals normalises.
 //
+// reni_gbuffer_backward_camera adds the gradient with respect to the camera (R, T, tan_half_fov; the barycentric path alone):
+// k_gb_face<true> stores a camera record per face, the reducer of reni_tu_camera.hip adds them; without grad_verts k_gb_vertex
+// and k_vn_bwd are not launched.
 // Malformed input adds nothing and reads nothing out of range: a vertex index outside [0, V), a list entry outside [0, 3F) or
 // one that does not name the vertex, offsets outside their list, a pixel entry outside [0, S S) or one whose pix_to_face is
 // not the face, a face that k_face_setup skips (it has no pixel in a real pix_to_face).
@@ -50,6 +53,7 @@ struct GbArgs {
   float* rec;            // [F][GB_REC]
   Camera cam;
   int V, F, S;
+  float* crec;           // [F][CAM_REC], k_gb_face<true> alone
 };
 
 DEV float gb_wave_sum(float s) {  // all 64 lanes, one fixed order
@@ -59,6 +63,9 @@ DEV float gb_wave_sum(float s) {  // all 64 lanes, one fixed order
 }
 
 // ---- per-face reduction ------------------------------------------------------------------------------------------------
+// CAM: lane 0 also writes the face's camera record (CAM_REC floats: gR, gT, g_tan; reni_mesh.inc: mesh_camera_record) from
+// the NDC gradients and the corners it holds -- no second pixel walk.  <false> is the kernel as it was.
+template <bool CAM>
 __global__ void __launch_bounds__(256) k_gb_face(const GbArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -70,6 +77,7 @@ __global__ void __launch_bounds__(256) k_gb_face(const GbArgs a) {
   const int64_t b = min(max(a.foff[f], (int64_t)0), P), e = min(max(a.foff[f + 1], b), P);
   if (!ok || b == e) {  // a skipped face has no pixel
     if (lane < GB_REC) out[lane] = 0.f;
+    if (CAM && lane < CAM_REC) a.crec[(size_t)f * CAM_REC + lane] = 0.f;
     return;
   }
   float n[3][3], p[3][3];
@@ -145,6 +153,26 @@ __global__ void __launch_bounds__(256) k_gb_face(const GbArgs a) {
       out[6 * k + d] = wn[k][d];
       out[6 * k + 3 + d] = wx[k][d] + (a.cam.R[3 * d] * qx + a.cam.R[3 * d + 1] * qy + a.cam.R[3 * d + 2] * qz);
     }
+  }
+  // a.crec is never NULL in a <true> launch.  The test is NOT redundant and must stay: it puts the record in a block of its
+  // own, which with mesh_opaque keeps grad_verts' bits those of the <false> instance (mesh_camera_record, reni_mesh.inc;
+  // only the device's bit-equality tests, tests/test_gpu_camera_grad.py, notice when that is lost).
+  if (CAM && a.crec) {  // the barycentric path alone: wx is world-space
+    Camera cam = a.cam;
+    cam.tan_half_fov = mesh_opaque(cam.tan_half_fov);
+    float tx[3], ty[3], xo[3], yo[3], zo[3], po[3][3];
+    mesh_opaque3(gx, tx); mesh_opaque3(gy, ty); mesh_opaque3(x, xo); mesh_opaque3(y, yo); mesh_opaque3(z, zo);
+    const float sAo = mesh_opaque(sA);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) mesh_opaque3(p[k], po[k]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {  // A = E(v2, v0, v1) + eps folded in, as above
+      const int i1 = (k + 1) % 3, i2 = (k + 2) % 3;
+      const float dx = sAo * (yo[i2] - yo[i1]), dy = sAo * (xo[i1] - xo[i2]);
+      tx[k] += dx;
+      ty[k] += dy;
+    }
+    mesh_camera_record(cam, tx, ty, xo, yo, zo, po, a.crec + (size_t)f * CAM_REC);
   }
 }
 
@@ -243,6 +271,51 @@ __global__ void __launch_bounds__(256) k_vn_bwd(const GbMesh m, const float* __r
 namespace {
 
 size_t gb_rec_bytes(int64_t F) { return ((size_t)F * reni::GB_REC * sizeof(float) + 255) & ~(size_t)255; }
+size_t gb_gu_bytes(int64_t V) { return ((size_t)V * 3 * sizeof(float) + 255) & ~(size_t)255; }
+// the camera records [F][CAM_REC] and, behind them, the reducer's chunk sums
+size_t gb_cam_rec_bytes(int64_t F) { return ((size_t)F * reni::CAM_REC * sizeof(float) + 255) & ~(size_t)255; }
+size_t gb_cam_bytes(int64_t F) { return gb_cam_rec_bytes(F) + ((reni::camera_part_floats(F) * sizeof(float) + 255) & ~(size_t)255); }
+
+// reni_gbuffer_backward (camera false: grad_camera is not looked at, today's checks and launches) and
+// reni_gbuffer_backward_camera (camera true: grad_verts and the vertex lists are optional, together)
+int gb_backward(const char* who, bool camera, int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* vert_normals,
+                const float* R, const float* T, float tan_half_fov, int64_t H, int64_t W, const int64_t* pix_to_face,
+                const int64_t* face_pixel_offsets, const int64_t* face_pixel_list, const int64_t* vf_offsets, const int64_t* vf_corners,
+                const float* grad_pixel_normals, const float* grad_pixel_positions, float* grad_verts, float* grad_camera, void* ws,
+                size_t ws_bytes, void* stream) {
+  if (int rc = mesh_check_sizes(who, V, F)) return rc;
+  if (int rc = mesh_check_image(who, H, W)) return rc;
+  if (camera && !grad_verts && !grad_camera) return tu_fail(RENI_EINVAL, who, "grad_verts and grad_camera are both NULL");
+  if (camera && !grad_camera) return tu_fail(RENI_EINVAL, who, "NULL grad_camera (reni_gbuffer_backward computes grad_verts alone)");
+  const bool need_verts = !camera || grad_verts;
+  if (!verts || !faces || !vert_normals || !R || !T || !pix_to_face || !face_pixel_offsets || !face_pixel_list ||
+      (need_verts && (!vf_offsets || !vf_corners || !grad_verts)))
+    return tu_fail(RENI_EINVAL, who, "NULL argument");
+  if (!grad_pixel_normals && !grad_pixel_positions) return tu_fail(RENI_EINVAL, who, "both upstream gradients are NULL");
+  if (int rc = mesh_check_fov(who, tan_half_fov)) return rc;
+  const size_t need = camera ? gb_rec_bytes(F) + gb_gu_bytes(V) + gb_cam_bytes(F) : gb_rec_bytes(F) + (size_t)V * 3 * sizeof(float);
+  if (int rc = tu_check_ws(who, ws, ws_bytes, need)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  reni::GbArgs a;
+  a.verts = verts; a.vnrm = vert_normals; a.faces = faces; a.p2f = pix_to_face; a.foff = face_pixel_offsets;
+  a.flist = face_pixel_list; a.gN = grad_pixel_normals; a.gX = grad_pixel_positions;
+  a.rec = (float*)ws;
+  a.cam = mesh_camera(R, T, tan_half_fov);
+  a.V = (int)V; a.F = (int)F; a.S = (int)H;
+  a.crec = camera ? (float*)((char*)ws + gb_rec_bytes(F) + gb_gu_bytes(V)) : nullptr;
+  const auto k = camera ? reni::k_gb_face<true> : reni::k_gb_face<false>;
+  if (int rc = tu_launch(TU_PLAIN, k, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, a)) return rc;
+  if (camera)
+    if (int rc = reni::launch_camera_reduce(a.crec, F, (float*)((char*)a.crec + gb_cam_rec_bytes(F)), grad_camera, s)) return rc;
+  if (!need_verts) return RENI_OK;  // the mesh is known and only the pose is fitted: no vertex kernel, no list
+  const reni::GbMesh m{verts, faces, vf_offsets, vf_corners, (int)V, (int)F};
+  // without an upstream for the normals g n_v is 0 everywhere: the vertex-normal chain adds nothing and is not run
+  float* gu = grad_pixel_normals ? (float*)((char*)ws + gb_rec_bytes(F)) : nullptr;
+  const dim3 vgrid((unsigned)((V + 255) / 256));
+  if (int rc = tu_launch(TU_PLAIN, reni::k_gb_vertex, vgrid, dim3(256), 0, s, m, (const float*)a.rec, gu, grad_verts)) return rc;
+  if (!gu) return RENI_OK;
+  return tu_launch(TU_PLAIN, reni::k_vn_bwd<true>, vgrid, dim3(256), 0, s, m, (const float*)gu, 1, grad_verts);
+}
 
 }  // namespace
 
@@ -268,30 +341,25 @@ int reni_gbuffer_backward(int64_t V, int64_t F, const float* verts, const int64_
                           const int64_t* face_pixel_offsets, const int64_t* face_pixel_list, const int64_t* vf_offsets,
                           const int64_t* vf_corners, const float* grad_pixel_normals, const float* grad_pixel_positions,
                           float* grad_verts, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "gbuffer backward";
-  if (int rc = mesh_check_sizes(who, V, F)) return rc;
-  if (int rc = mesh_check_image(who, H, W)) return rc;
-  if (!verts || !faces || !vert_normals || !R || !T || !pix_to_face || !face_pixel_offsets || !face_pixel_list || !vf_offsets ||
-      !vf_corners || !grad_verts)
-    return tu_fail(RENI_EINVAL, who, "NULL argument");
-  if (!grad_pixel_normals && !grad_pixel_positions) return tu_fail(RENI_EINVAL, who, "both upstream gradients are NULL");
-  if (int rc = mesh_check_fov(who, tan_half_fov)) return rc;
-  if (int rc = tu_check_ws(who, ws, ws_bytes, gb_rec_bytes(F) + (size_t)V * 3 * sizeof(float))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  reni::GbArgs a;
-  a.verts = verts; a.vnrm = vert_normals; a.faces = faces; a.p2f = pix_to_face; a.foff = face_pixel_offsets;
-  a.flist = face_pixel_list; a.gN = grad_pixel_normals; a.gX = grad_pixel_positions;
-  a.rec = (float*)ws;
-  a.cam = mesh_camera(R, T, tan_half_fov);
-  a.V = (int)V; a.F = (int)F; a.S = (int)H;
-  if (int rc = tu_launch(TU_PLAIN, reni::k_gb_face, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, a)) return rc;
-  const reni::GbMesh m{verts, faces, vf_offsets, vf_corners, (int)V, (int)F};
-  // without an upstream for the normals g n_v is 0 everywhere: the vertex-normal chain adds nothing and is not run
-  float* gu = grad_pixel_normals ? (float*)((char*)ws + gb_rec_bytes(F)) : nullptr;
-  const dim3 vgrid((unsigned)((V + 255) / 256));
-  if (int rc = tu_launch(TU_PLAIN, reni::k_gb_vertex, vgrid, dim3(256), 0, s, m, (const float*)a.rec, gu, grad_verts)) return rc;
-  if (!gu) return RENI_OK;
-  return tu_launch(TU_PLAIN, reni::k_vn_bwd<true>, vgrid, dim3(256), 0, s, m, (const float*)gu, 1, grad_verts);
+  return gb_backward("gbuffer backward", false, V, F, verts, faces, vert_normals, R, T, tan_half_fov, H, W, pix_to_face,
+                     face_pixel_offsets, face_pixel_list, vf_offsets, vf_corners, grad_pixel_normals, grad_pixel_positions, grad_verts,
+                     nullptr, ws, ws_bytes, stream);
+}
+
+size_t reni_gbuffer_backward_camera_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W) {
+  if (V < 1 || F < 1 || H < 1 || W < 1 || V > MESH_MAX_ELEMS || F > MESH_MAX_ELEMS) return 0;
+  return gb_rec_bytes(F) + gb_gu_bytes(V) + gb_cam_bytes(F) + 256;
+}
+
+int reni_gbuffer_backward_camera(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* vert_normals,
+                                 const float* R, const float* T, float tan_half_fov, int64_t H, int64_t W,
+                                 const int64_t* pix_to_face, const int64_t* face_pixel_offsets, const int64_t* face_pixel_list,
+                                 const int64_t* vf_offsets, const int64_t* vf_corners, const float* grad_pixel_normals,
+                                 const float* grad_pixel_positions, float* grad_verts, float* grad_camera, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  return gb_backward("gbuffer backward camera", true, V, F, verts, faces, vert_normals, R, T, tan_half_fov, H, W, pix_to_face,
+                     face_pixel_offsets, face_pixel_list, vf_offsets, vf_corners, grad_pixel_normals, grad_pixel_positions, grad_verts,
+                     grad_camera, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -31,6 +31,8 @@
 // The nearest-point walk is this unit's own (sil_nearest): the rasteriser's point_line_dist2 returns the distance alone, the
 // silhouette needs c and t beside it, so nothing of reni_tu_raster.hip moves and its emitted code stays what it was.
 // exp is expf, not the bare hardware exponential: the tests' error bound is derived with a correctly rounded exp.
+// reni_soft_silhouette_backward_camera adds the gradient with respect to the camera (R, T, tan_half_fov): k_sil_face<true>
+// stores a camera record per face, the reducer of reni_tu_camera.hip adds them; without grad_verts k_sil_vertex is not launched.
 // Malformed input adds nothing and reads nothing out of range: a vertex index outside [0, V) (mesh_face), a list entry outside
 // [0, 3F) or one that does not name the vertex, offsets outside their list (mesh_corner_range, mesh_corner_names).
 #include <hip/hip_runtime.h>
@@ -192,6 +194,11 @@ struct SilBwdArgs {
   Camera cam;
   float sigma, r;
   int F, S;
+  // k_sil_face<true> alone: the camera records [F][CAM_REC], and the mesh for the corners' world positions
+  float* crec;
+  const float* verts;
+  const int64_t* faces;
+  int V;
 };
 
 DEV float sil_wave_sum(float s) {  // all 64 lanes, one fixed order (as gb_wave_sum)
@@ -203,6 +210,9 @@ DEV float sil_wave_sum(float s) {  // all 64 lanes, one fixed order (as gb_wave_
 // the grid index i (counted from +x / +y, mesh_pix_ndc) nearest below / above NDC coordinate v, clamped to [-1, S]
 DEV int sil_grid_floor(float v, int S) { return (int)floorf(fminf(fmaxf(((v + 1.f) * (float)S - 1.f) * 0.5f, -1.f), (float)S)); }
 
+// CAM: lane 0 also writes the face's camera record (CAM_REC floats: gR, gT, g_tan; reni_mesh.inc: mesh_camera_record) from
+// the NDC gradients and the corners it holds -- no second pixel walk.  <false> is the kernel as it was.
+template <bool CAM>
 __global__ void __launch_bounds__(256) k_sil_face(const SilBwdArgs a) {
   const int lane = threadIdx.x & 63;
   const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -216,6 +226,7 @@ __global__ void __launch_bounds__(256) k_sil_face(const SilBwdArgs a) {
   const int iy_lo = max(sil_grid_floor(box.z, S) - 1, 0), iy_hi = min(sil_grid_floor(box.w, S) + 2, S - 1);
   if (!(g2.y > 0.f) || ix_lo > ix_hi || iy_lo > iy_hi) {  // the face does not take part, or its box holds no pixel
     if (lane < SIL_REC) out[lane] = 0.f;
+    if (CAM && lane < CAM_REC) a.crec[(size_t)f * CAM_REC + lane] = 0.f;
     return;
   }
   const float x[3] = {g0.x, g0.z, g1.x}, y[3] = {g0.y, g0.w, g1.y}, z[3] = {g1.z, g1.w, g2.x};
@@ -256,6 +267,24 @@ __global__ void __launch_bounds__(256) k_sil_face(const SilBwdArgs a) {
 #pragma unroll
     for (int d = 0; d < 3; ++d) out[3 * k + d] = a.cam.R[3 * d] * qx + a.cam.R[3 * d + 1] * qy + a.cam.R[3 * d + 2] * qz;
   }
+  // a.crec is never NULL in a <true> launch.  The test is NOT redundant and must stay: it puts the record in a block of its
+  // own, which with mesh_opaque keeps grad_verts' bits those of the <false> instance (mesh_camera_record, reni_mesh.inc;
+  // only the device's bit-equality tests, tests/test_gpu_camera_grad.py, notice when that is lost).
+  if (CAM && a.crec) {
+    float p[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int64_t i = a.faces[3 * (size_t)f + k];  // in [0, V) for a face that takes part (mesh_face); checked all the same
+      const bool ok = i >= 0 && i < a.V;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) p[k][d] = ok ? a.verts[3 * i + d] : 0.f;
+    }
+    Camera cam = a.cam;
+    cam.tan_half_fov = mesh_opaque(cam.tan_half_fov);
+    float tx[3], ty[3], xo[3], yo[3], zo[3];
+    mesh_opaque3(gx, tx); mesh_opaque3(gy, ty); mesh_opaque3(x, xo); mesh_opaque3(y, yo); mesh_opaque3(z, zo);
+    mesh_camera_record(cam, tx, ty, xo, yo, zo, p, a.crec + (size_t)f * CAM_REC);
+  }
 }
 
 // ---- backward: per-vertex gather of the face records -------------------------------------------------------------------
@@ -292,6 +321,47 @@ int sil_setup(int64_t V, int64_t F, const float* verts, const int64_t* faces, co
   const float grow = sqrtf(blur_radius) * reni::SIL_GROW_REL + reni::SIL_GROW_ABS;
   return tu_launch(TU_PLAIN, reni::k_sil_setup, dim3((unsigned)((F + 255) / 256)), dim3(256), 0, s, (int)V, (int)F, verts, faces, cam,
                    grow, rec);
+}
+
+// the camera records [F][CAM_REC] and, behind them, the reducer's chunk sums
+size_t sil_cam_rec_bytes(int64_t F) { return ((size_t)F * reni::CAM_REC * sizeof(float) + 255) & ~(size_t)255; }
+size_t sil_cam_bytes(int64_t F) { return sil_cam_rec_bytes(F) + ((reni::camera_part_floats(F) * sizeof(float) + 255) & ~(size_t)255); }
+
+// reni_soft_silhouette_backward (camera false: grad_camera is not looked at, today's checks and launches) and
+// reni_soft_silhouette_backward_camera (camera true: grad_verts and the vertex lists are optional, together)
+int sil_backward(const char* who, bool camera, int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* R,
+                 const float* T, float tan_half_fov, int64_t H, int64_t W, float sigma, float blur_radius, const float* trans,
+                 const float* grad_alpha, const int64_t* vf_offsets, const int64_t* vf_corners, float* grad_verts,
+                 float* grad_camera, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = mesh_check_sizes(who, V, F)) return rc;
+  if (int rc = mesh_check_image(who, H, W)) return rc;
+  if (camera && !grad_verts && !grad_camera) return tu_fail(RENI_EINVAL, who, "grad_verts and grad_camera are both NULL");
+  if (camera && !grad_camera)
+    return tu_fail(RENI_EINVAL, who, "NULL grad_camera (reni_soft_silhouette_backward computes grad_verts alone)");
+  const bool need_verts = !camera || grad_verts;
+  if (!verts || !faces || !R || !T || !trans || !grad_alpha || (need_verts && (!vf_offsets || !vf_corners || !grad_verts)))
+    return tu_fail(RENI_EINVAL, who, "NULL argument");
+  if (int rc = mesh_check_fov(who, tan_half_fov)) return rc;
+  if (int rc = sil_check_blur(who, sigma, blur_radius)) return rc;
+  const size_t base = sil_rec_bytes(F) + sil_grad_bytes(F);
+  if (int rc = tu_check_ws(who, ws, ws_bytes, base + (camera ? sil_cam_bytes(F) : 0))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  reni::SilBwdArgs a;
+  a.cam = mesh_camera(R, T, tan_half_fov);
+  reni::SilRec* rec = (reni::SilRec*)ws;
+  if (int rc = sil_setup(V, F, verts, faces, a.cam, blur_radius, rec, s)) return rc;
+  a.rec = rec; a.trans = trans; a.gA = grad_alpha; a.out = (float*)((char*)ws + sil_rec_bytes(F));
+  a.sigma = sigma; a.r = blur_radius; a.F = (int)F; a.S = (int)H;
+  a.crec = camera ? (float*)((char*)ws + base) : nullptr;
+  a.verts = verts; a.faces = faces; a.V = (int)V;
+  const auto k = camera ? reni::k_sil_face<true> : reni::k_sil_face<false>;
+  if (int rc = tu_launch(TU_PLAIN, k, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, a)) return rc;
+  if (camera)
+    if (int rc = reni::launch_camera_reduce(a.crec, F, (float*)((char*)a.crec + sil_cam_rec_bytes(F)), grad_camera, s)) return rc;
+  if (!need_verts) return RENI_OK;  // the mesh is known and only the pose is fitted: no vertex kernel, no list
+  const reni::GbMesh m{verts, faces, vf_offsets, vf_corners, (int)V, (int)F};
+  return tu_launch(TU_PLAIN, reni::k_sil_vertex, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, s, m, (const float*)a.out,
+                   grad_verts);
 }
 
 }  // namespace
@@ -331,25 +401,22 @@ int reni_soft_silhouette_backward(int64_t V, int64_t F, const float* verts, cons
                                   float tan_half_fov, int64_t H, int64_t W, float sigma, float blur_radius, const float* trans,
                                   const float* grad_alpha, const int64_t* vf_offsets, const int64_t* vf_corners,
                                   float* grad_verts, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "soft silhouette backward";
-  if (int rc = mesh_check_sizes(who, V, F)) return rc;
-  if (int rc = mesh_check_image(who, H, W)) return rc;
-  if (!verts || !faces || !R || !T || !trans || !grad_alpha || !vf_offsets || !vf_corners || !grad_verts)
-    return tu_fail(RENI_EINVAL, who, "NULL argument");
-  if (int rc = mesh_check_fov(who, tan_half_fov)) return rc;
-  if (int rc = sil_check_blur(who, sigma, blur_radius)) return rc;
-  if (int rc = tu_check_ws(who, ws, ws_bytes, sil_rec_bytes(F) + sil_grad_bytes(F))) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  reni::SilBwdArgs a;
-  a.cam = mesh_camera(R, T, tan_half_fov);
-  reni::SilRec* rec = (reni::SilRec*)ws;
-  if (int rc = sil_setup(V, F, verts, faces, a.cam, blur_radius, rec, s)) return rc;
-  a.rec = rec; a.trans = trans; a.gA = grad_alpha; a.out = (float*)((char*)ws + sil_rec_bytes(F));
-  a.sigma = sigma; a.r = blur_radius; a.F = (int)F; a.S = (int)H;
-  if (int rc = tu_launch(TU_PLAIN, reni::k_sil_face, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, s, a)) return rc;
-  const reni::GbMesh m{verts, faces, vf_offsets, vf_corners, (int)V, (int)F};
-  return tu_launch(TU_PLAIN, reni::k_sil_vertex, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, s, m, (const float*)a.out,
-                   grad_verts);
+  return sil_backward("soft silhouette backward", false, V, F, verts, faces, R, T, tan_half_fov, H, W, sigma, blur_radius, trans,
+                      grad_alpha, vf_offsets, vf_corners, grad_verts, nullptr, ws, ws_bytes, stream);
+}
+
+size_t reni_soft_silhouette_backward_camera_workspace_bytes(int64_t V, int64_t F, int64_t H, int64_t W) {
+  if (V < 1 || F < 1 || H < 1 || W < 1 || V > MESH_MAX_ELEMS || F > MESH_MAX_ELEMS) return 0;
+  return sil_rec_bytes(F) + sil_grad_bytes(F) + sil_cam_bytes(F) + 256;
+}
+
+int reni_soft_silhouette_backward_camera(int64_t V, int64_t F, const float* verts, const int64_t* faces, const float* R,
+                                         const float* T, float tan_half_fov, int64_t H, int64_t W, float sigma, float blur_radius,
+                                         const float* trans, const float* grad_alpha, const int64_t* vf_offsets,
+                                         const int64_t* vf_corners, float* grad_verts, float* grad_camera, void* ws, size_t ws_bytes,
+                                         void* stream) {
+  return sil_backward("soft silhouette backward camera", true, V, F, verts, faces, R, T, tan_half_fov, H, W, sigma, blur_radius,
+                      trans, grad_alpha, vf_offsets, vf_corners, grad_verts, grad_camera, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -575,6 +575,10 @@ class PrefilteredRenderer(torch.nn.Module):
                 raise ValueError("PrefilteredRenderer cannot be rendered while the mesh's vertices require grad: the prefiltered "
                                  "lookup has no gradient with respect to geometry (detach the vertices, or use mesh.HipMeshRenderer)")
             _, nrm, pos = self.rasterizer.gbuffer(meshes_world, R, T)
+            if nrm.requires_grad:
+                raise ValueError("PrefilteredRenderer cannot be rendered while the camera (R, T or the fov) requires grad: the "
+                                 "prefiltered lookup has no gradient with respect to geometry (detach the camera, or use "
+                                 "mesh.HipMeshRenderer)")
             Hr = Wr = self.rasterizer.raster_settings.image_size
         B = envmap.environment_map.shape[0]
         if self.materials is not None:

@@ -10,7 +10,10 @@ Conventions (pytorch3d's): world -> view is ``p @ R + T`` with row vectors; NDC 
 is the top and column 0 the left edge at +x; the depth kept in ``zbuf`` is view-space z; barycentrics are NDC-space.
 In the reference only the environment map carries a gradient.  Here the vertex positions may too (``verts.requires_grad``):
 the G-buffer's normals and positions then carry a gradient to them through ``ops.gbuffer_backward`` with the face assignment
-held fixed (no silhouette or occlusion gradient); the camera stays a constant.
+held fixed (no silhouette or occlusion gradient).  So may the camera: an ``R``, a ``T`` or a fov tensor that requires grad gets
+the gradient of the G-buffer and of the soft silhouette (``ops.gbuffer_backward_camera``,
+``ops.soft_silhouette_backward_camera``); ``look_at_rotation``, ``camera_from_position`` and ``so3_exp_map`` are the
+parameterisations that keep ``R`` a rotation while a pose is fitted.
 """
 from __future__ import annotations
 
@@ -120,42 +123,106 @@ def rotate_axis_angle_y(verts: torch.Tensor, degrees: float) -> torch.Tensor:
     return verts @ R.t().to(verts.device, verts.dtype)  # row vectors: p @ R^T = (R p^T)^T
 
 
-def look_at_view_transform(dist=1.0, elev=0.0, azim=0.0, degrees: bool = True, device="cpu"):
-    """Camera on a sphere round the origin looking at it with +Y up -> (R [1,3,3], T [1,3]); (2, 0, 0) gives
-    R = diag(-1, 1, -1), T = (0, 0, 2)."""
-    d = torch.tensor([float(dist)], dtype=torch.float32)
-    e = torch.tensor([float(elev)], dtype=torch.float32)
-    a = torch.tensor([float(azim)], dtype=torch.float32)
-    if degrees:
-        e, a = e * (math.pi / 180.0), a * (math.pi / 180.0)
-    C = torch.stack([d * torch.cos(e) * torch.sin(a), d * torch.sin(e), d * torch.cos(e) * torch.cos(a)], dim=1)  # [1,3]
-    up = torch.tensor([[0.0, 1.0, 0.0]])
-    z = torch.nn.functional.normalize(-C, eps=1e-5)  # at (origin) - C
+def _look_at_axes(d: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
+    """R [N,3,3] (world -> view, row vectors) of a camera that looks along ``d`` [N,3] with ``up`` [N,3] (pytorch3d's
+    look_at_rotation: z = d normalised, x = up x z, y = z x x; x = y x z when looking straight up or down)."""
+    z = torch.nn.functional.normalize(d, eps=1e-5)
     x = torch.nn.functional.normalize(torch.cross(up, z, dim=1), eps=1e-5)
     y = torch.nn.functional.normalize(torch.cross(z, x, dim=1), eps=1e-5)
     if bool(torch.isclose(x, torch.zeros_like(x), atol=5e-3).all()):  # looking straight up or down
         x = torch.nn.functional.normalize(torch.cross(y, z, dim=1), eps=1e-5)
-    R = torch.cat([x[:, None], y[:, None], z[:, None]], dim=1).transpose(1, 2)
+    return torch.cat([x[:, None], y[:, None], z[:, None]], dim=1).transpose(1, 2)
+
+
+def _row3(v, like: torch.Tensor = None) -> torch.Tensor:
+    """three numbers or a tensor of three as [1,3]: a tensor keeps its graph, dtype and device, anything else takes ``like``'s"""
+    if isinstance(v, torch.Tensor):
+        return v.reshape(1, 3)
+    ref = like if like is not None else torch.zeros((), dtype=torch.float32)
+    return torch.tensor([float(x) for x in v], dtype=ref.dtype, device=ref.device).reshape(1, 3)
+
+
+def look_at_rotation(camera_position, at=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0)) -> torch.Tensor:
+    """R [1,3,3] of a camera at ``camera_position`` ([3] or [1,3]) looking at ``at`` with ``up`` up (pytorch3d's function of
+    that name).  Plain torch on the position's device and dtype, differentiable: an orthonormal R whatever the position, which
+    is what makes the position a parameter a pose fit can step."""
+    C = _row3(camera_position)
+    return _look_at_axes(_row3(at, C) - C, _row3(up, C))
+
+
+def camera_from_position(camera_position, at=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0)):
+    """(R [1,3,3], T [1,3]) of the camera at ``camera_position`` looking at ``at``: ``look_at_rotation`` and T = -C R, the
+    translation that puts the camera's centre at the view-space origin.  Differentiable in the position."""
+    C = _row3(camera_position)
+    R = look_at_rotation(C, at, up)
+    return R, -torch.bmm(C[:, None, :], R)[:, 0, :]
+
+
+def so3_exp_map(log_rot: torch.Tensor) -> torch.Tensor:
+    """R [N,3,3] = exp(hat(w)) for axis-angle vectors w ([3] or [N,3]) by Rodrigues' formula, I + A K + B K^2 with
+    A = sin(th) / th, B = (1 - cos(th)) / th^2, K = hat(w) (pytorch3d's convention).  Below th^2 = 1e-4 A and B come from
+    their series (1 - th^2/6 + th^4/120, 1/2 - th^2/24 + th^4/720: exact to rounding there), so the value and the gradient are
+    finite at w = 0.  Plain torch, differentiable, on the input's device and dtype."""
+    w = log_rot.reshape(-1, 3)
+    t2 = (w * w).sum(dim=1)
+    small = t2 < 1e-4
+    th = torch.sqrt(torch.where(small, torch.ones_like(t2), t2))
+    A = torch.where(small, 1.0 - t2 / 6.0 + t2 * t2 / 120.0, torch.sin(th) / th)
+    B = torch.where(small, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, (1.0 - torch.cos(th)) / (th * th))
+    zero = torch.zeros_like(t2)
+    K = torch.stack([zero, -w[:, 2], w[:, 1], w[:, 2], zero, -w[:, 0], -w[:, 1], w[:, 0], zero], dim=1).reshape(-1, 3, 3)
+    eye = torch.eye(3, dtype=w.dtype, device=w.device)[None]
+    return eye + A[:, None, None] * K + B[:, None, None] * torch.bmm(K, K)
+
+
+def look_at_view_transform(dist=1.0, elev=0.0, azim=0.0, degrees: bool = True, device=None):
+    """Camera on a sphere round the origin looking at it with +Y up -> (R [1,3,3], T [1,3]); (2, 0, 0) gives
+    R = diag(-1, 1, -1), T = (0, 0, 2).  ``dist``, ``elev`` and ``azim`` may be tensors (one value each): the result then keeps
+    their graph and, unless ``device`` says otherwise, their device.  With numbers: float32 on ``device`` (default the CPU)."""
+    given = [v for v in (dist, elev, azim) if isinstance(v, torch.Tensor)]
+    at = given[0].device if given else "cpu"
+    d, e, a = (v.to(torch.float32).reshape(1).to(at) if isinstance(v, torch.Tensor) else torch.tensor([float(v)], dtype=torch.float32, device=at)
+               for v in (dist, elev, azim))
+    if degrees:
+        e, a = e * (math.pi / 180.0), a * (math.pi / 180.0)
+    C = torch.stack([d * torch.cos(e) * torch.sin(a), d * torch.sin(e), d * torch.cos(e) * torch.cos(a)], dim=1)  # [1,3]
+    R = _look_at_axes(-C, torch.tensor([[0.0, 1.0, 0.0]], device=at))  # at (origin) - C
     T = -torch.bmm(R.transpose(1, 2), C[:, :, None])[:, :, 0]
+    device = at if device is None else device
     return R.to(device), T.to(device)
 
 
 class FoVPerspectiveCameras:
     """pytorch3d's FoVPerspectiveCameras as ``build_renderer`` creates it: fov 60 deg, znear 1, zfar 100, aspect 1, and
-    R = I, T = 0 unless given (R, T passed to a renderer call override them for that call)."""
+    R = I, T = 0 unless given (R, T passed to a renderer call override them for that call).  ``fov`` may be a 0-d tensor: it
+    is kept as given (so one that requires grad gets the rasteriser's gradient, ``tan_half_fov_tensor`` being the torch chain
+    tan(fov / 2)), and ``tan_half_fov()`` reads its current value, so an optimiser's in-place step re-rasterises."""
 
     def __init__(self, znear=1.0, zfar=100.0, aspect_ratio=1.0, fov=60.0, degrees=True, R=None, T=None, device="cpu"):
         if float(aspect_ratio) != 1.0:
             raise ValueError("only aspect_ratio 1 (square images) is supported")
         self.znear, self.zfar, self.aspect_ratio = float(znear), float(zfar), 1.0
-        self.fov = float(fov) * (math.pi / 180.0 if degrees else 1.0)
+        self._fov_scale = math.pi / 180.0 if degrees else 1.0
+        if isinstance(fov, torch.Tensor):
+            if fov.dim() != 0:
+                raise ValueError(f"a fov tensor must be 0-d (one camera), got {tuple(fov.shape)}")
+            self.fov = fov
+        else:
+            self.fov, self._fov_scale = float(fov) * self._fov_scale, 1.0  # radians
         self.R = torch.eye(3)[None] if R is None else torch.as_tensor(R, dtype=torch.float32).reshape(1, 3, 3)
         self.T = torch.zeros(1, 3) if T is None else torch.as_tensor(T, dtype=torch.float32).reshape(1, 3)
         self.device = device
         self.R, self.T = self.R.to(device), self.T.to(device)
 
     def tan_half_fov(self) -> float:
-        return math.tan(self.fov / 2.0)
+        fov = float(self.fov.detach()) if isinstance(self.fov, torch.Tensor) else self.fov
+        return math.tan(fov * self._fov_scale / 2.0)
+
+    def tan_half_fov_tensor(self):
+        """tan(fov / 2) as a function of the fov tensor, or None when the fov is a number or needs no gradient"""
+        if not isinstance(self.fov, torch.Tensor) or not self.fov.requires_grad:
+            return None
+        return torch.tan(self.fov * (self._fov_scale / 2.0))
 
     def get_camera_center(self, R=None, T=None) -> torch.Tensor:
         """World position of the camera [1,3]: the C with C @ R + T = 0."""
@@ -184,50 +251,68 @@ class _VertexNormalsFn(torch.autograd.Function):
         return ops.vertex_normals_backward(verts.detach(), faces, g.contiguous(), vf=ctx.vf), None, None, None
 
 
+def _camera_grads(ctx, R, T, tanf, gR, gT, g_tan):
+    """the kernel's camera gradient in the shapes, dtypes and devices of the inputs that asked for one"""
+    need = ctx.needs_input_grad
+    return (gR.reshape(R.shape).to(R.device, R.dtype) if need[1] else None,
+            gT.reshape(T.shape).to(T.device, T.dtype) if need[2] else None,
+            g_tan.reshape(tanf.shape).to(tanf.device, tanf.dtype) if need[3] else None)
+
+
 class _GBufferFn(torch.autograd.Function):
-    """The cached G-buffer as a function of the vertices: the forward hands out the buffers ``ops.rasterize_mesh`` filled
-    (same kernel, same bits), the backward is ``ops.gbuffer_backward`` over the record's pix_to_face -- the vertex-normal
-    chain included, so the normals the rasteriser interpolated enter as a constant.  A node per call: two renders of one
-    cached G-buffer are back-propagated separately."""
+    """The cached G-buffer as a function of the vertices and of the camera (R, T, tan(fov / 2); the latter a tensor or
+    None): the forward hands out the buffers ``ops.rasterize_mesh`` filled (same kernel, same bits), the backward is
+    ``ops.gbuffer_backward`` over the record's pix_to_face -- the vertex-normal chain included, so the normals the rasteriser
+    interpolated enter as a constant -- or, when something of the camera needs a gradient, ``ops.gbuffer_backward_camera``
+    (without the vertex kernels when the vertices need none).  A node per call: two renders of one cached G-buffer are
+    back-propagated separately."""
 
     @staticmethod
-    def forward(ctx, verts, rec):
-        ctx.save_for_backward(verts)
+    def forward(ctx, verts, R, T, tanf, rec):
+        ctx.save_for_backward(verts, R, T, tanf)
         ctx.rec = rec
         ctx.set_materialize_grads(False)
         return rec["nrm"].detach(), rec["pos"].detach()
 
     @staticmethod
     def backward(ctx, gN, gX):
-        (verts,) = ctx.saved_tensors
+        verts, R, T, tanf = ctx.saved_tensors
         rec = ctx.rec
+        need_verts, need_cam = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:4])
         if gN is None and gX is None:
-            return torch.zeros_like(verts), None
+            return torch.zeros_like(verts) if need_verts else None, None, None, None, None
         if rec.get("table") is None:  # the pixels sorted by face: once per G-buffer, on the device
             rec["table"] = ops.face_pixel_table(rec["p2f"], rec["faces"].shape[0])
-        g = ops.gbuffer_backward(verts.detach(), rec["faces"], rec["normals"], rec["R"], rec["T"], rec["S"], rec["p2f"],
-                                 None if gN is None else gN.contiguous(), None if gX is None else gX.contiguous(),
-                                 tan_half_fov=rec["tan_half_fov"], table=rec["table"], vf=rec["vf"])
-        return g, None
+        args = (verts.detach(), rec["faces"], rec["normals"], rec["R"], rec["T"], rec["S"], rec["p2f"],
+                None if gN is None else gN.contiguous(), None if gX is None else gX.contiguous())
+        if not need_cam:
+            return ops.gbuffer_backward(*args, tan_half_fov=rec["tan_half_fov"], table=rec["table"], vf=rec["vf"]), None, None, None, None
+        g, gR, gT, g_tan = ops.gbuffer_backward_camera(*args, tan_half_fov=rec["tan_half_fov"], table=rec["table"], vf=rec["vf"],
+                                                       need_verts=need_verts)
+        return (g,) + _camera_grads(ctx, R, T, tanf, gR, gT, g_tan) + (None,)
 
 
 class _SilhouetteFn(torch.autograd.Function):
-    """The cached soft silhouette as a function of the vertices: the forward hands out the buffer ``ops.soft_silhouette``
-    filled, the backward is ``ops.soft_silhouette_backward`` over the record's trans.  A node per call, as ``_GBufferFn``."""
+    """The cached soft silhouette as a function of the vertices and of the camera: the forward hands out the buffer
+    ``ops.soft_silhouette`` filled, the backward is ``ops.soft_silhouette_backward`` over the record's trans, or
+    ``ops.soft_silhouette_backward_camera`` when something of the camera needs a gradient.  A node per call, as ``_GBufferFn``."""
 
     @staticmethod
-    def forward(ctx, verts, rec):
-        ctx.save_for_backward(verts)
+    def forward(ctx, verts, R, T, tanf, rec):
+        ctx.save_for_backward(verts, R, T, tanf)
         ctx.rec = rec
         return rec["alpha"].detach()
 
     @staticmethod
     def backward(ctx, gA):
-        (verts,) = ctx.saved_tensors
+        verts, R, T, tanf = ctx.saved_tensors
         rec = ctx.rec
-        g = ops.soft_silhouette_backward(verts.detach(), rec["faces"], rec["R"], rec["T"], rec["S"], rec["tan_half_fov"],
-                                         rec["sigma"], rec["blur_radius"], rec["trans"], gA.contiguous(), vf=rec["vf"])
-        return g, None
+        args = (verts.detach(), rec["faces"], rec["R"], rec["T"], rec["S"], rec["tan_half_fov"], rec["sigma"], rec["blur_radius"],
+                rec["trans"], gA.contiguous())
+        if not any(ctx.needs_input_grad[1:4]):
+            return ops.soft_silhouette_backward(*args, vf=rec["vf"]), None, None, None, None
+        g, gR, gT, g_tan = ops.soft_silhouette_backward_camera(*args, vf=rec["vf"], need_verts=ctx.needs_input_grad[0])
+        return (g,) + _camera_grads(ctx, R, T, tanf, gR, gT, g_tan) + (None,)
 
 
 def silhouette_iou(alpha: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
@@ -343,7 +428,8 @@ class MeshRasterizer(nn.Module):
 
         When the mesh's vertices require grad (and grad is enabled, and ``differentiable``) the two G-buffers carry a
         gradient to them: the same cached buffers behind an autograd node built for this call (``ops.gbuffer_backward``:
-        the face assignment is held fixed -- no silhouette or occlusion gradient -- and the camera is a constant).  The
+        the face assignment is held fixed -- no silhouette or occlusion gradient).  The same holds for ``R``, ``T`` and a fov
+        tensor of the cameras that require grad (``ops.gbuffer_backward_camera``: through the barycentric weights).  The
         Fragments never carry one.  Otherwise the cached tensors themselves are returned, as before."""
         R = self.cameras.R if R is None else torch.as_tensor(R)
         T = self.cameras.T if T is None else torch.as_tensor(T)
@@ -358,10 +444,11 @@ class MeshRasterizer(nn.Module):
                    "p2f": p2f, "nrm": nrm, "pos": pos, "table": None, "vf": None}
             self._cache = (key, (v, f, R, T), out, rec)  # (the tensors are held so that their ids stay theirs)
         out, rec = self._cache[2], self._cache[3]
-        if differentiable and v.requires_grad and torch.is_grad_enabled():
-            if rec["vf"] is None:
+        tanf = self.cameras.tan_half_fov_tensor()
+        if differentiable and torch.is_grad_enabled() and (v.requires_grad or R.requires_grad or T.requires_grad or tanf is not None):
+            if v.requires_grad and rec["vf"] is None:
                 rec["vf"] = meshes_world._vertex_faces()
-            nrm, pos = _GBufferFn.apply(v, rec)
+            nrm, pos = _GBufferFn.apply(v, R, T, tanf, rec)
             return out[0], nrm, pos
         return out
 
@@ -373,8 +460,9 @@ class MeshRasterizer(nn.Module):
 
         Kept like the G-buffer, under the same key plus (sigma, blur_radius).  When the mesh's vertices require grad (and grad
         is enabled) the same cached buffer is returned behind an autograd node built for this call
-        (``ops.soft_silhouette_backward``): this is the gradient that moves the outline; the camera is a constant.  Otherwise
-        the cached tensor itself is returned."""
+        (``ops.soft_silhouette_backward``): this is the gradient that moves the outline.  ``R``, ``T`` and a fov tensor of the
+        cameras that require grad get theirs from the same node (``ops.soft_silhouette_backward_camera``): the gradient a pose
+        fit steps along.  Otherwise the cached tensor itself is returned."""
         R = self.cameras.R if R is None else torch.as_tensor(R)
         T = self.cameras.T if T is None else torch.as_tensor(T)
         S = self.raster_settings.image_size
@@ -389,10 +477,11 @@ class MeshRasterizer(nn.Module):
                    "alpha": alpha.reshape(S, S), "trans": trans, "vf": None}
             self._sil_cache = (key, (v, f, R, T), rec)  # (the tensors are held so that their ids stay theirs)
         rec = self._sil_cache[2]
-        if v.requires_grad and torch.is_grad_enabled():
-            if rec["vf"] is None:
+        tanf_t = self.cameras.tan_half_fov_tensor()
+        if torch.is_grad_enabled() and (v.requires_grad or R.requires_grad or T.requires_grad or tanf_t is not None):
+            if v.requires_grad and rec["vf"] is None:
                 rec["vf"] = meshes_world._vertex_faces()
-            return _SilhouetteFn.apply(v, rec)
+            return _SilhouetteFn.apply(v, R, T, tanf_t, rec)
         return rec["alpha"]
 
     def visibility(self, meshes_world: Meshes, R=None, T=None, dirs=None, t_min=None, no_cull: bool = False):
@@ -522,7 +611,12 @@ class HipMeshRenderer(nn.Module):
     ``MicrofacetMaterials`` as always.  Deliberately dropped: the positions are handed to the shader detached (the view
     vector's dependence on the geometry), the shadow mask is computed from detached tensors and stays constant, pixels do
     not change face.  ``TexturedMaterials`` / ``TexturedMicrofacetMaterials`` raise a ValueError: UVs, taps and tangent
-    frames under moving geometry are out of scope."""
+    frames under moving geometry are out of scope.
+
+    Camera: an ``R``, a ``T`` or a fov tensor that requires grad takes the same branches as vertices that do, through the same
+    G-buffer node (``ops.gbuffer_backward_camera``).  Deliberately dropped as well: the shader's positions and its
+    ``camera_center`` stay constants (the view vector's dependence on the pose), and the shadow mask stays constant.  The
+    UV-space materials raise a ValueError that names the camera."""
 
     def __init__(self, rasterizer: MeshRasterizer, kd: float = None, ks: float = None, materials=None, shader_cameras=None,
                  shadows: bool = False):
@@ -544,8 +638,12 @@ class HipMeshRenderer(nn.Module):
 
     def forward(self, meshes_world: Meshes = None, R=None, T=None, envmap: EnvironmentMap = None, **kwargs):
         _, nrm, pos = self.rasterizer.gbuffer(meshes_world, R, T)
-        geometry = nrm.requires_grad  # the mesh's vertices require grad: the G-buffer carries a gradient to them
+        geometry = nrm.requires_grad  # the vertices or the camera require grad: the G-buffer carries a gradient to them
         if geometry:
+            if self.textured and not meshes_world.verts_packed().requires_grad:
+                raise ValueError(f"{type(self.materials).__name__} cannot be rendered while the camera (R, T or the fov) requires "
+                                 "grad: UVs, taps and tangent frames under a moving camera are out of scope (detach the camera, "
+                                 "or use SpatialMaterials / MicrofacetMaterials)")
             if self.textured:
                 raise ValueError(f"{type(self.materials).__name__} cannot be rendered while the mesh's vertices require grad: "
                                  "UVs, taps and tangent frames under moving geometry are out of scope (detach the vertices, "

@@ -870,6 +870,40 @@ def face_pixel_table(pix_to_face: torch.Tensor, F: int):
     return offsets.contiguous(), order.contiguous()
 
 
+def _gbuffer_backward_inputs(verts, faces, vert_normals, R, T, image_size, pix_to_face, grad_pixel_normals, grad_pixel_positions,
+                             table, vf, need_lists):
+    """The checked and cast arguments of ``gbuffer_backward_camera`` (``gbuffer_backward``'s checks, in its order) and the
+    vertex lists (None when not needed)."""
+    _mesh_shapes(verts, faces)
+    S = _image_size(image_size)
+    if not isinstance(vert_normals, torch.Tensor) or tuple(vert_normals.shape) != tuple(verts.shape):
+        raise ValueError("vert_normals must be [V, 3] like verts")
+    if not isinstance(pix_to_face, torch.Tensor) or pix_to_face.dtype != torch.int64 or pix_to_face.numel() != S * S:
+        raise ValueError(f"pix_to_face must be an int64 tensor of {S * S} entries (the rasteriser's)")
+    if grad_pixel_normals is None and grad_pixel_positions is None:
+        raise ValueError("grad_pixel_normals and grad_pixel_positions cannot both be None")
+    for name, g in (("grad_pixel_normals", grad_pixel_normals), ("grad_pixel_positions", grad_pixel_positions)):
+        if g is not None and (not isinstance(g, torch.Tensor) or tuple(g.shape) != (S * S, 3)):
+            raise ValueError(f"{name} must be [{S * S}, 3] or None, got {tuple(getattr(g, 'shape', ()))}")
+    Rh, Th = _camera_arrays(R, T)
+    verts, faces = _mesh_inputs(verts, faces)
+    _require_cuda(vert_normals, pix_to_face, grad_pixel_normals, grad_pixel_positions)
+    dev = verts.device
+    vert_normals = _f32c(vert_normals)
+    p2f = pix_to_face.reshape(-1).contiguous()
+    gN = None if grad_pixel_normals is None else _f32c(grad_pixel_normals)
+    gX = None if grad_pixel_positions is None else _f32c(grad_pixel_positions)
+    if any(t is not None and t.device != dev for t in (vert_normals, p2f, gN, gX)):
+        raise ValueError(f"the G-buffer and its gradients are not on {dev}")
+    V, F = verts.shape[0], faces.shape[0]
+    foff, flist = face_pixel_table(p2f, F) if table is None else table
+    if (tuple(foff.shape) != (F + 1,) or tuple(flist.shape) != (S * S,) or foff.dtype != torch.int64 or flist.dtype != torch.int64
+            or foff.device != dev or flist.device != dev):
+        raise ValueError(f"the table is not one of {S * S} pixels over {F} faces on {dev}")
+    lists = _vf_lists(faces, V, vf) if need_lists else None
+    return (verts, faces, vert_normals, Rh, Th, S, p2f, foff.contiguous(), flist.contiguous(), gN, gX), lists
+
+
 def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch.Tensor, R, T, image_size: int,
                      pix_to_face: torch.Tensor, grad_pixel_normals=None, grad_pixel_positions=None,
                      tan_half_fov: float = 0.5773502691896258, table=None, vf=None) -> torch.Tensor:
@@ -916,6 +950,35 @@ def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: tor
     return out
 
 
+def _camera_gradient(cam: torch.Tensor):
+    """grad_camera [13] -> (gR [3,3], gT [3], g_tan [])"""
+    return cam[:9].reshape(3, 3), cam[9:12], cam[12]
+
+
+def gbuffer_backward_camera(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch.Tensor, R, T, image_size: int,
+                            pix_to_face: torch.Tensor, grad_pixel_normals=None, grad_pixel_positions=None,
+                            tan_half_fov: float = 0.5773502691896258, table=None, vf=None, need_verts: bool = True):
+    """reni_gbuffer_backward_camera: ``gbuffer_backward`` with the camera's gradient beside the vertices' ->
+    (g_verts [V,3] | None, gR [3,3], gT [3], g_tan []): d/d R, d/d T and d/d tan_half_fov of the same objective, through the
+    barycentric weights alone (the vertex normals and the interpolated positions are world-space), pix_to_face held fixed; R is
+    differentiated as nine free numbers.  g_verts has ``gbuffer_backward``'s bits.  ``need_verts=False``: the mesh is known and
+    only the pose is fitted -- the vertex kernels are not launched, no vertex list is built, g_verts is None; the camera's bits
+    do not move.  Deterministic, no atomics."""
+    (verts, faces, vert_normals, Rh, Th, S, p2f, foff, flist, gN, gX), lists = _gbuffer_backward_inputs(
+        verts, faces, vert_normals, R, T, image_size, pix_to_face, grad_pixel_normals, grad_pixel_positions, table, vf, need_verts)
+    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    lib = _lib.load()
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev) if need_verts else None
+    cam = torch.empty(13, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_gbuffer_backward_camera_workspace_bytes(V, F, S, S)), dev)
+    _call(lib.reni_gbuffer_backward_camera, dev, V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th,
+          float(tan_half_fov), S, S, p2f.data_ptr(), foff.data_ptr(), flist.data_ptr(),
+          None if lists is None else lists[0].data_ptr(), None if lists is None else lists[1].data_ptr(),
+          None if gN is None else gN.data_ptr(), None if gX is None else gX.data_ptr(), None if out is None else out.data_ptr(),
+          cam.data_ptr(), wp, wn)
+    return (out,) + _camera_gradient(cam)
+
+
 def _silhouette_scalars(sigma, blur_radius):
     sigma, blur_radius = float(sigma), float(blur_radius)
     if not (sigma > 0.0) or not math.isfinite(sigma):
@@ -948,6 +1011,27 @@ def soft_silhouette(verts: torch.Tensor, faces: torch.Tensor, R, T, image_size: 
     return alpha, trans
 
 
+def _silhouette_backward_inputs(verts, faces, R, T, image_size, sigma, blur_radius, trans, grad_alpha, vf, need_lists):
+    """The checked and cast arguments of ``soft_silhouette_backward_camera`` (``soft_silhouette_backward``'s checks, in its
+    order) and the vertex lists (None when not needed)."""
+    _mesh_shapes(verts, faces)
+    S = _image_size(image_size)
+    sigma, blur_radius = _silhouette_scalars(sigma, blur_radius)
+    for name, t in (("trans", trans), ("grad_alpha", grad_alpha)):
+        if not isinstance(t, torch.Tensor) or t.numel() != S * S:
+            raise ValueError(f"{name} must be a tensor of {S * S} entries, got {tuple(getattr(t, 'shape', ()))}")
+    Rh, Th = _camera_arrays(R, T)
+    verts, faces = _mesh_inputs(verts, faces)
+    _require_cuda(trans, grad_alpha)
+    dev = verts.device
+    trans, grad_alpha = _f32c(trans).reshape(-1), _f32c(grad_alpha).reshape(-1)
+    if trans.device != dev or grad_alpha.device != dev:
+        raise ValueError(f"trans and grad_alpha are not on {dev}")
+    V, F = verts.shape[0], faces.shape[0]
+    lists = _vf_lists(faces, V, vf) if need_lists else None
+    return (verts, faces, Rh, Th, S, sigma, blur_radius, trans, grad_alpha), lists
+
+
 def soft_silhouette_backward(verts: torch.Tensor, faces: torch.Tensor, R, T, image_size: int, tan_half_fov: float, sigma: float,
                              blur_radius: float, trans: torch.Tensor, grad_alpha: torch.Tensor, vf=None) -> torch.Tensor:
     """reni_soft_silhouette_backward: grad_verts [V, 3] = d/d verts of sum_p grad_alpha_p alpha_p for the alpha of
@@ -975,6 +1059,28 @@ def soft_silhouette_backward(verts: torch.Tensor, faces: torch.Tensor, R, T, ima
     _call(lib.reni_soft_silhouette_backward, dev, V, F, verts.data_ptr(), faces.data_ptr(), Rh, Th, float(tan_half_fov), S, S, sigma,
           blur_radius, trans.data_ptr(), grad_alpha.data_ptr(), offsets.data_ptr(), corners.data_ptr(), out.data_ptr(), wp, wn)
     return out
+
+
+def soft_silhouette_backward_camera(verts: torch.Tensor, faces: torch.Tensor, R, T, image_size: int, tan_half_fov: float,
+                                    sigma: float, blur_radius: float, trans: torch.Tensor, grad_alpha: torch.Tensor, vf=None,
+                                    need_verts: bool = True):
+    """reni_soft_silhouette_backward_camera: ``soft_silhouette_backward`` with the camera's gradient beside the vertices' ->
+    (g_verts [V,3] | None, gR [3,3], gT [3], g_tan []): d/d R, d/d T and d/d tan_half_fov of sum_p grad_alpha_p alpha_p under
+    the same constants (membership, inside / outside, the nearest edge, a clamped edge parameter, blur_radius); R is
+    differentiated as nine free numbers.  g_verts has ``soft_silhouette_backward``'s bits.  ``need_verts=False``: the mesh is
+    known and only the pose is fitted -- the vertex kernel is not launched, no vertex list is built, g_verts is None; the
+    camera's bits do not move.  Deterministic, no atomics."""
+    (verts, faces, Rh, Th, S, sigma, blur_radius, trans, grad_alpha), lists = _silhouette_backward_inputs(
+        verts, faces, R, T, image_size, sigma, blur_radius, trans, grad_alpha, vf, need_verts)
+    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    lib = _lib.load()
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev) if need_verts else None
+    cam = torch.empty(13, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_soft_silhouette_backward_camera_workspace_bytes(V, F, S, S)), dev)
+    _call(lib.reni_soft_silhouette_backward_camera, dev, V, F, verts.data_ptr(), faces.data_ptr(), Rh, Th, float(tan_half_fov), S, S,
+          sigma, blur_radius, trans.data_ptr(), grad_alpha.data_ptr(), None if lists is None else lists[0].data_ptr(),
+          None if lists is None else lists[1].data_ptr(), None if out is None else out.data_ptr(), cam.data_ptr(), wp, wn)
+    return (out,) + _camera_gradient(cam)
 
 
 def _morton_order(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:

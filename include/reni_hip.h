@@ -518,6 +518,61 @@ int reni_soft_silhouette_backward_camera(int64_t V, int64_t F, const float* vert
                                          const int64_t* vf_corners, float* grad_verts, float* grad_camera /* [13] device */,
                                          void* ws, size_t ws_bytes, void* stream);
 
+/* ---- mesh regularisers: edge length, Laplacian smoothing, normal consistency (reni_tu_meshreg.hip) ------------------------
+ * What keeps a fitted mesh a surface: the three terms of SoftRas / pytorch3d.loss (mesh_edge_loss, mesh_laplacian_smoothing,
+ * mesh_normal_consistency) as ONE weighted objective  L = w_e L_e + w_l L_l + w_n L_n,  its three values and d L / d verts,
+ * from one call.  Where pytorch3d differs from the text below, the text holds.
+ * Topology.  A face TAKES PART iff its three indices lie in [0, V) and are pairwise different.  edges [E][2] are the unique
+ *   undirected edges (a < b) of the faces taking part, in ascending (a, b).  The multiplicity of an edge is the number of
+ *   faces taking part that hold it (a repeated face counts twice).  A PAIR is an unordered pair of faces on one edge: an edge
+ *   of multiplicity m has m (m - 1) / 2 pairs, enumerated in ascending (edge, face, face); P is their number.
+ * Edge loss.         L_e = (1 / E) sum_e (|x_a - x_b| - target_length)^2;  d|u| / du = 0 at u = 0;  E = 0 gives 0.
+ * Laplacian, uniform (RENI_LAPLACIAN_UNIFORM).
+ *                    r_v = mean_{j in N(v)} x_j - x_v over the unique neighbours of v;  L_l = (1 / V) sum_v |r_v|;
+ *                    d|r| / dr = r / |r|, and 0 at r = 0.
+ * Laplacian, cot (RENI_LAPLACIAN_COT).
+ *                    With the side lengths A, B, C opposite corners 0, 1, 2 of a face, s = (A + B + C) / 2:
+ *                    area = max(sqrt(max(s (s - A)(s - B)(s - C), 0)), 1e-12)  (Heron, clamped below at 1e-12);
+ *                    cot_0 = (B^2 + C^2 - A^2) / (4 area), the other corners by the same pattern;
+ *                    w_e = the sum over the edge's faces of the cotangent of the angle opposite the edge;
+ *                    s_v = sum_j w_vj;  n_v = 1 / s_v if s_v > 0, else s_v;  r_v = (sum_j w_vj x_j) n_v - x_v.
+ *                    The weights and n_v are CONSTANTS of the gradient (pytorch3d computes them without grad); they are
+ *                    recomputed from the current vertices at every call.  "cotcurv" is not implemented.
+ * Normal consistency.  For a pair on edge (a, b) with the opposite vertices c, d:
+ *                    n0 = (x_b - x_a) x (x_c - x_a),  n1 = -(x_b - x_a) x (x_d - x_a),
+ *                    cos = n0 . n1 / (max(|n0|, 1e-8) max(|n1|, 1e-8));  L_n = (1 / P) sum (1 - cos);  P = 0 gives 0.
+ *                    Independent of the winding; a flat pair gives 0, a repeated face gives 2.  Where a max takes its floor,
+ *                    the floor is a constant of the gradient.
+ * Deviations from pytorch3d: a vertex WITHOUT NEIGHBOURS has r_v = 0 under either method (pytorch3d pulls it to the origin); it
+ *   still counts in V.  The clamp of Heron's formula is on the area, not on the product under the root.  Faces with a
+ *   repeated or out-of-range index take no part (pytorch3d has no such faces).
+ * The lists (ops.mesh_edge_lists builds them once per face tensor; all int64, ascending; they depend on the faces alone):
+ *   edges [E][2];  ef_offsets [E + 1] into ef_corners [H]: per edge the corners 3 f + k OPPOSITE it of the faces that hold it,
+ *   ascending;  ve_offsets [V + 1] into ve_edges [2 E]: per vertex its edges, ascending;  vf_offsets [V + 1] into
+ *   vf_corners [NC]: per vertex its corners (as for reni_mesh_vertex_normals);  corner_edges [3 F]: per corner the edge
+ *   opposite it, -1 for a face that takes no part.  None of them is trusted: an offset is clamped into its list, an edge must
+ *   be 0 <= a < b < V, an ef entry a corner of a face taking part whose opposite edge is that edge, a ve entry an edge that
+ *   holds the vertex, a corner must name the vertex, corner_edges must agree with the face.  What fails adds nothing and is
+ *   never turned into an address (a corner that an ef range repeats pairs with nothing).  An empty list is still a non-NULL
+ *   pointer.  An edge of multiplicity m costs one thread m (m - 1) / 2 pairs; P must stay below 2^31 (a 32-bit count).
+ * values [4] (device) = L, L_e, L_l, L_n, overwritten.  grad_verts [V][3] (device) = d L / d verts, overwritten; NULL: the
+ *   values alone (the same bits).  A weight of 0 skips that loss's work: its value is 0 and it adds exactly 0.  Weights and
+ *   target_length must be >= 0 and finite.
+ * fp32, no float atomics and no in-launch ticket: per edge the pairs in ascending order, per vertex its edges then its corners in
+ *   list order, and a store-then-sum reducer (chunks of 4096 rows, a fixed lane stride, a fixed butterfly, the waves in
+ *   ascending order, relaunched on the chunk sums until one is left) whose order depends on V and E alone: two calls give
+ *   identical bits.
+ * ws: reni_mesh_regularizers_workspace_bytes(V, F, E) bytes, 256-byte aligned (0 for sizes out of range). */
+#define RENI_LAPLACIAN_UNIFORM 0
+#define RENI_LAPLACIAN_COT 1
+size_t reni_mesh_regularizers_workspace_bytes(int64_t V, int64_t F, int64_t E);
+int reni_mesh_regularizers(int64_t V, int64_t F, int64_t E, int64_t H, int64_t NC, const float* verts, const int64_t* faces,
+                           const int64_t* edges, const int64_t* ef_offsets, const int64_t* ef_corners, const int64_t* ve_offsets,
+                           const int64_t* ve_edges, const int64_t* vf_offsets, const int64_t* vf_corners,
+                           const int64_t* corner_edges, float w_edge, float w_laplacian, float w_normal, float target_length,
+                           int32_t method, float* values /* [4] device */, float* grad_verts /* [V][3] device, or NULL */,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* ---- cast shadows: visibility masks of the mesh for the shader (reni_tu_visibility.hip, the MASKED shader instances) ----
  * The shader above lets light pass through the mesh: M(p, j) knows the pixel's own normal and nothing else.  The lights are at
  * infinity, so whether texel direction j reaches pixel p is a constant of (mesh, camera, directions), as the G-buffer is.

@@ -28,6 +28,7 @@ SSIM_MODE = {"sphere": 0, "planar": 1}
 VIS_NO_CULL = 1  # RENI_VIS_NO_CULL
 SHADE_TERMS_DS = 1  # RENI_SHADE_TERMS_DS
 TEX_WRAP = {"clamp": 0, "repeat": 1}  # RENI_TEX_*
+LAPLACIAN = {"uniform": 0, "cot": 1}  # RENI_LAPLACIAN_*
 
 # every symbol include/reni_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -44,6 +45,7 @@ EXPORTS = (
     "reni_soft_silhouette_backward",
     "reni_gbuffer_backward_camera_workspace_bytes", "reni_gbuffer_backward_camera",
     "reni_soft_silhouette_backward_camera_workspace_bytes", "reni_soft_silhouette_backward_camera",
+    "reni_mesh_regularizers_workspace_bytes", "reni_mesh_regularizers",
     "reni_mesh_visibility_accel_bytes", "reni_mesh_visibility_prepare", "reni_mesh_visibility",
     "reni_envmap_shade_masked", "reni_envmap_shade_masked_backward",
     "reni_envmap_shade_terms_workspace_bytes", "reni_envmap_shade_terms", "reni_envmap_shade_terms_backward",
@@ -225,6 +227,12 @@ def load():
     lib.reni_gbuffer_backward_camera.restype = c_int32
     lib.reni_soft_silhouette_backward_camera.argtypes = sil + [c_void_p] * 7 + [c_size_t, c_void_p]
     lib.reni_soft_silhouette_backward_camera.restype = c_int32
+    lib.reni_mesh_regularizers_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    lib.reni_mesh_regularizers_workspace_bytes.restype = c_size_t
+    # V, F, E, H, NC; verts, faces and the eight lists; three weights, target_length; method; values, grad_verts, ws ..
+    lib.reni_mesh_regularizers.argtypes = ([c_int64] * 5 + [c_void_p] * 10 + [c_float] * 4 + [c_int32, c_void_p, c_void_p, c_void_p,
+                                                                                              c_size_t, c_void_p])
+    lib.reni_mesh_regularizers.restype = c_int32
     lib.reni_mesh_visibility_accel_bytes.argtypes = [c_int64]
     lib.reni_mesh_visibility_accel_bytes.restype = c_size_t
     lib.reni_mesh_visibility_prepare.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]

@@ -340,6 +340,7 @@ class Meshes:
         self._faces = faces[0].to(torch.int64).contiguous()
         self._normals = None
         self._vf = None
+        self._el = None
         self._verts_uvs = self._faces_uvs = None
         if (verts_uvs is None) != (faces_uvs is None):
             raise ValueError("verts_uvs and faces_uvs come together")
@@ -365,6 +366,18 @@ class Meshes:
         if self._vf is None or self._vf[0] != key:
             self._vf = (key, ops.vertex_face_lists(self._faces, self._verts.shape[0]))
         return self._vf[1]
+
+    def _edge_lists(self):
+        """the topology lists of the regularisers (``ops.mesh_edge_lists``), kept per in-place version of the faces"""
+        key = self._faces._version
+        if self._el is None or self._el[0] != key:
+            self._el = (key, ops.mesh_edge_lists(self._faces, self._verts.shape[0]))
+        return self._el[1]
+
+    def edges_packed(self) -> torch.Tensor:
+        """[E, 2] int64: the unique undirected edges (a < b) of the faces taking part, in ascending (a, b)"""
+        lists = self._edge_lists()
+        return lists["edges"][:lists["E"]]
 
     def _normals_value(self) -> torch.Tensor:
         """the normals of the current vertices as a constant (no autograd node)"""

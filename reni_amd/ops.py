@@ -1083,6 +1083,113 @@ def soft_silhouette_backward_camera(verts: torch.Tensor, faces: torch.Tensor, R,
     return (out,) + _camera_gradient(cam)
 
 
+_EDGE_LIST_NAMES = ("edges", "ef_offsets", "ef_corners", "ve_offsets", "ve_edges", "vf_offsets", "vf_corners", "corner_edges")
+
+
+def _pad1(t: torch.Tensor) -> torch.Tensor:
+    """an empty list as one never-read entry, so that it still has an address"""
+    return t if t.numel() else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+
+
+def mesh_edge_lists(faces: torch.Tensor, V: int) -> dict:
+    """The topology lists of ``mesh_regularizers`` (``lists=``), all int64 and ascending, built by stable sorts on the faces'
+    device.  A face takes part iff its indices lie in [0, V) and are pairwise different.
+
+    ``edges`` [E, 2]: the unique undirected edges (a < b) of the faces taking part, in ascending (a, b);
+    ``ef_offsets`` [E + 1] / ``ef_corners``: per edge the corners 3 f + k OPPOSITE it of the faces holding it, ascending (so an
+    edge of multiplicity m has m entries and m (m - 1) / 2 pairs);  ``ve_offsets`` [V + 1] / ``ve_edges`` [2 E]: per vertex its
+    edges, ascending;  ``vf_offsets`` / ``vf_corners``: ``vertex_face_lists``;  ``corner_edges`` [3 F]: the edge opposite each
+    corner, -1 for a face that takes no part;  ``E``, ``H`` (half edges), ``NC`` (corners), ``P`` (pairs), ``V``, ``F``: ints.
+    The lists depend on the faces alone: a caller whose vertices move every step keeps them."""
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError(f"faces must be a tensor [F, 3] with F >= 1, got {tuple(getattr(faces, 'shape', ()))}")
+    V = int(V)
+    if V < 1:
+        raise ValueError("V must be >= 1")
+    faces = faces.to(torch.int64).contiguous()
+    dev, F = faces.device, faces.shape[0]
+    part = ((faces >= 0) & (faces < V)).all(dim=1)
+    part = part & (faces[:, 0] != faces[:, 1]) & (faces[:, 0] != faces[:, 2]) & (faces[:, 1] != faces[:, 2])
+    f = part.nonzero()[:, 0]
+    tri = faces[f]
+    # corner k of face f is opposite the edge of the other two corners
+    p = torch.stack([tri[:, 1], tri[:, 0], tri[:, 0]], 1).reshape(-1)
+    q = torch.stack([tri[:, 2], tri[:, 2], tri[:, 1]], 1).reshape(-1)
+    corners = (3 * f[:, None] + torch.arange(3, device=dev, dtype=torch.int64)[None, :]).reshape(-1)
+    keys, order = torch.sort(torch.minimum(p, q) * V + torch.maximum(p, q), stable=True)  # ascending (a, b), then corner
+    ef_corners = corners[order]
+    ukeys, counts = torch.unique_consecutive(keys, return_counts=True)
+    E = int(ukeys.numel())
+    edges = torch.stack([ukeys // V, ukeys % V], 1)
+    ef_offsets = torch.zeros(E + 1, dtype=torch.int64, device=dev)
+    ef_offsets[1:] = torch.cumsum(counts, 0)
+    corner_edges = torch.full((3 * F,), -1, dtype=torch.int64, device=dev)
+    corner_edges[ef_corners] = torch.repeat_interleave(torch.arange(E, device=dev, dtype=torch.int64), counts)
+    ends = edges.reshape(-1)  # entry 2 e + s names edge e
+    vkeys, vorder = torch.sort(ends, stable=True)
+    ve_edges = torch.div(vorder, 2, rounding_mode="floor")
+    ve_offsets = torch.searchsorted(vkeys, torch.arange(V + 1, device=dev, dtype=torch.int64))
+    vf_offsets, vf_corners = _vertex_face_csr(faces, V)
+    NC = int(vf_corners.numel())
+    P = int((counts * (counts - 1) // 2).sum()) if E else 0
+    out = {"edges": _pad1(edges.contiguous()), "ef_offsets": ef_offsets, "ef_corners": _pad1(ef_corners.contiguous()),
+           "ve_offsets": ve_offsets.contiguous(), "ve_edges": _pad1(ve_edges.contiguous()), "vf_offsets": vf_offsets,
+           "vf_corners": _pad1(vf_corners), "corner_edges": corner_edges, "V": V, "F": F, "E": E, "H": int(ef_corners.numel()),
+           "NC": NC, "P": P}
+    return out
+
+
+def _edge_lists(faces, V, lists):
+    """``lists`` checked by shape, dtype and device (their CONTENT is checked on the device, entry by entry)"""
+    if lists is None:
+        return mesh_edge_lists(faces, V)
+    F = faces.shape[0]
+    try:
+        E, H, NC = int(lists["E"]), int(lists["H"]), int(lists["NC"])
+        t = {k: lists[k] for k in _EDGE_LIST_NAMES}
+    except (KeyError, TypeError, ValueError):
+        raise ValueError(f"lists must be mesh_edge_lists(faces, {V})") from None
+    want = {"edges": (max(E, 1), 2), "ef_offsets": (E + 1,), "ef_corners": (max(H, 1),), "ve_offsets": (V + 1,),
+            "ve_edges": (max(2 * E, 1),), "vf_offsets": (V + 1,), "vf_corners": (max(NC, 1),), "corner_edges": (3 * F,)}
+    ok = E >= 0 and 0 <= H <= 3 * F and 0 <= NC <= 3 * F and int(lists.get("V", V)) == V and int(lists.get("F", F)) == F
+    for k in _EDGE_LIST_NAMES:
+        x = t[k]
+        ok = ok and isinstance(x, torch.Tensor) and x.dtype == torch.int64 and x.device == faces.device and tuple(x.shape) == want[k]
+    if not ok:
+        raise ValueError(f"lists must be mesh_edge_lists(faces, {V}) on {faces.device}")
+    out = dict(lists)
+    out.update({k: t[k].contiguous() for k in _EDGE_LIST_NAMES})
+    return out
+
+
+def mesh_regularizers(verts: torch.Tensor, faces: torch.Tensor, edge: float = 0.0, laplacian: float = 0.0, normal: float = 0.0,
+                      target_length: float = 0.0, method: str = "uniform", lists=None, need_grad: bool = True):
+    """reni_mesh_regularizers: (values [4] = (L, L_e, L_l, L_n), grad_verts [V, 3] | None) of
+    L = edge L_e + laplacian L_l + normal L_n -- the edge-length, Laplacian-smoothing (``method`` "uniform" or "cot") and
+    normal-consistency terms of SoftRas / pytorch3d.loss (include/reni_hip.h has the definitions) and d L / d verts, from one
+    call.  A weight of 0 skips that term.  ``lists``: ``mesh_edge_lists(faces, V)`` when the caller keeps it (the same bits).
+    ``need_grad=False``: the values alone (the same bits).  Deterministic, no atomics."""
+    _mesh_shapes(verts, faces)
+    if method not in _lib.LAPLACIAN:
+        raise ValueError(f"method must be one of {tuple(_lib.LAPLACIAN)}, got {method!r}")
+    w = [float(edge), float(laplacian), float(normal)]
+    target_length = float(target_length)
+    for name, x in (("edge", w[0]), ("laplacian", w[1]), ("normal", w[2]), ("target_length", target_length)):
+        if not (x >= 0.0) or not math.isfinite(x):
+            raise ValueError(f"{name} must be >= 0 and finite, got {x}")
+    verts, faces = _mesh_inputs(verts, faces)
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    L = _edge_lists(faces, V, lists)
+    lib = _lib.load()
+    values = torch.empty(4, dtype=torch.float32, device=dev)
+    grad = torch.empty(V, 3, dtype=torch.float32, device=dev) if need_grad else None
+    ws, wp, wn = _ws256(int(lib.reni_mesh_regularizers_workspace_bytes(V, F, L["E"])), dev)
+    _call(lib.reni_mesh_regularizers, dev, V, F, L["E"], L["H"], L["NC"], verts.data_ptr(), faces.data_ptr(),
+          *[L[k].data_ptr() for k in _EDGE_LIST_NAMES], w[0], w[1], w[2], target_length, _lib.LAPLACIAN[method], values.data_ptr(),
+          None if grad is None else grad.data_ptr(), wp, wn)
+    return values, grad
+
+
 def _morton_order(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """A permutation of the faces that keeps neighbours together: the stable argsort of the 30-bit Morton codes of the
     centroids (10 bits per axis over the mesh's bounding box).  Faces with an index outside [0, V) sort last."""

@@ -207,8 +207,8 @@ def load():
     lib.reni_mesh_vertex_normals_backward.restype = c_int32
     lib.reni_gbuffer_backward_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int64]
     lib.reni_gbuffer_backward_workspace_bytes.restype = c_size_t
-    lib.reni_gbuffer_backward.argtypes = ([c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_float), POINTER(c_float),
-                                           c_float, c_int64, c_int64] + [c_void_p] * 9 + [c_size_t, c_void_p])
+    gbuf = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_float), POINTER(c_float), c_float, c_int64, c_int64]
+    lib.reni_gbuffer_backward.argtypes = gbuf + [c_void_p] * 9 + [c_size_t, c_void_p]  # p2f, table, lists, gN, gX, grad_verts, ws ..
     lib.reni_gbuffer_backward.restype = c_int32
     for fn in (lib.reni_soft_silhouette_workspace_bytes, lib.reni_soft_silhouette_backward_workspace_bytes):
         fn.argtypes = [c_int64, c_int64, c_int64, c_int64]
@@ -222,8 +222,7 @@ def load():
     for fn in (lib.reni_gbuffer_backward_camera_workspace_bytes, lib.reni_soft_silhouette_backward_camera_workspace_bytes):
         fn.argtypes = [c_int64, c_int64, c_int64, c_int64]
         fn.restype = c_size_t
-    lib.reni_gbuffer_backward_camera.argtypes = ([c_int64, c_int64, c_void_p, c_void_p, c_void_p, POINTER(c_float), POINTER(c_float),
-                                                  c_float, c_int64, c_int64] + [c_void_p] * 10 + [c_size_t, c_void_p])
+    lib.reni_gbuffer_backward_camera.argtypes = gbuf + [c_void_p] * 10 + [c_size_t, c_void_p]
     lib.reni_gbuffer_backward_camera.restype = c_int32
     lib.reni_soft_silhouette_backward_camera.argtypes = sil + [c_void_p] * 7 + [c_size_t, c_void_p]
     lib.reni_soft_silhouette_backward_camera.restype = c_int32

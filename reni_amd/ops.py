@@ -1,4 +1,4 @@
-"""Thin tensor-level wrappers over the C ABI: plans, workspace, and the three compute calls.
+"""Thin tensor-level wrappers over the C ABI: plans, workspace and the compute calls.
 
 PyTorch is plumbing here (device memory, streams); all arithmetic happens in libreni_hip.so.
 """
@@ -44,6 +44,30 @@ def _call(fn, device, *args):
     """fn(*args, stream) with `device` current and its current stream as the last argument; raises on a library error."""
     with torch.cuda.device(device):
         _lib.check(fn(*args, torch.cuda.current_stream(device).cuda_stream))
+
+
+def _ptr(t):
+    """t's address, or None (the C ABI's NULL) for an optional tensor that is not given"""
+    return None if t is None else t.data_ptr()
+
+
+def _strides(t):
+    """t's element strides as the C ABI's int64 array (None, like ``_ptr``, for an optional tensor that is not given)"""
+    return None if t is None else (ctypes.c_int64 * t.dim())(*t.stride())
+
+
+def _f32(t):
+    """t as float32: t itself, strides and all, where it already is"""
+    return t if t.dtype == torch.float32 else t.float()
+
+
+def _ws256(nbytes, device):
+    """-> (the uint8 tensor that owns a call's workspace, a 256-byte aligned pointer into it, the bytes behind that pointer: at
+    least nbytes).  Every wrapper below takes its workspace here: the library wants the alignment, no allocator promises it."""
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
+    p = ws.data_ptr()
+    ap = (p + 255) & ~255
+    return ws, ap, ws.numel() - (ap - p)
 
 
 class Plan:
@@ -608,25 +632,19 @@ def _shade_inputs(normals, positions, camera_center, light_dirs, srcs, on_texels
                                  keep=(normals, positions, light_dirs, mat, vis))
 
 
-def _workspace(p, nbytes):
-    """-> (uint8 workspace tensor on the call's device, its size)"""
-    return torch.empty(int(nbytes), dtype=torch.uint8, device=p.dev), int(nbytes)
-
-
 def _shade_call(forward: bool, normals, positions, camera_center, light_dirs, src, shininess, kd, ks, vis=None):
     """reni_envmap_shade / reni_envmap_shade_backward and their _masked forms (include/reni_hip.h).  src = light colours [B,J,3]
     (forward) or d colours [B,NP,3] (backward).  Without a mask the checks of the mask's arguments are the library's."""
     p = _shade_inputs(normals, positions, camera_center, light_dirs, (src,), (forward,), vis, early=vis is not None)
     lib, f32 = p.lib, torch.float32
     out = torch.empty((p.B, p.NP, 3) if forward else (p.B, p.J, 3), dtype=f32, device=p.dev)
-    ws, nbytes = _workspace(p, lib.reni_envmap_shade_workspace_bytes(p.B, p.NP, p.J))
+    ws, wp, wn = _ws256(int(lib.reni_envmap_shade_workspace_bytes(p.B, p.NP, p.J)), p.dev)
     head = (*p.head, p.srcs[0].data_ptr(), float(shininess), float(kd), float(ks))
     if vis is None:
-        _call(lib.reni_envmap_shade if forward else lib.reni_envmap_shade_backward, p.dev, *head, out.data_ptr(),
-              ws.data_ptr(), nbytes)
+        _call(lib.reni_envmap_shade if forward else lib.reni_envmap_shade_backward, p.dev, *head, out.data_ptr(), wp, wn)
     else:
         _call(lib.reni_envmap_shade_masked if forward else lib.reni_envmap_shade_masked_backward, p.dev, *head, *p.vis,
-              out.data_ptr(), ws.data_ptr(), nbytes)
+              out.data_ptr(), wp, wn)
     return out
 
 
@@ -650,19 +668,18 @@ def _terms_call(forward: bool, normals, positions, camera_center, light_dirs, sr
     p = _shade_inputs(normals, positions, camera_center, light_dirs, srcs, on_texels, vis, shininess, "shininess")
     lib, f32, ptr = p.lib, torch.float32, [x.data_ptr() for x in p.srcs]
     if dnormals:
-        ws, nbytes = _workspace(p, lib.reni_envmap_shade_terms_dnormals_workspace_bytes(p.B, p.NP, p.J))
+        ws, wp, wn = _ws256(int(lib.reni_envmap_shade_terms_dnormals_workspace_bytes(p.B, p.NP, p.J)), p.dev)
         out = torch.empty((p.NP, 3), dtype=f32, device=p.dev)
-        _call(lib.reni_envmap_shade_terms_dnormals, p.dev, *p.head, ptr[0], *p.mats, ptr[1], ptr[2], out.data_ptr(),
-              ws.data_ptr(), nbytes)
+        _call(lib.reni_envmap_shade_terms_dnormals, p.dev, *p.head, ptr[0], *p.mats, ptr[1], ptr[2], out.data_ptr(), wp, wn)
         return out
-    ws, nbytes = _workspace(p, lib.reni_envmap_shade_terms_workspace_bytes(p.B, p.NP, p.J, _lib.SHADE_TERMS_DS if need_ds else 0))
+    ws, wp, wn = _ws256(int(lib.reni_envmap_shade_terms_workspace_bytes(p.B, p.NP, p.J, _lib.SHADE_TERMS_DS if need_ds else 0)), p.dev)
     if forward:
         outs = [torch.empty((p.B, p.NP, 3), dtype=f32, device=p.dev) for _ in range(3 if need_ds else 2)]
         _call(lib.reni_envmap_shade_terms, p.dev, *p.head, ptr[0], *p.mats, outs[0].data_ptr(), outs[1].data_ptr(),
-              outs[2].data_ptr() if need_ds else None, ws.data_ptr(), nbytes)
+              outs[2].data_ptr() if need_ds else None, wp, wn)
         return outs[0], outs[1], (outs[2] if need_ds else None)
     out = torch.empty((p.B, p.J, 3), dtype=f32, device=p.dev)
-    _call(lib.reni_envmap_shade_terms_backward, p.dev, *p.head, *p.mats, ptr[0], ptr[1], out.data_ptr(), ws.data_ptr(), nbytes)
+    _call(lib.reni_envmap_shade_terms_backward, p.dev, *p.head, *p.mats, ptr[0], ptr[1], out.data_ptr(), wp, wn)
     return out
 
 
@@ -693,20 +710,20 @@ def _ggx_call(mode: str, normals, positions, camera_center, light_dirs, srcs, al
     p = _shade_inputs(normals, positions, camera_center, light_dirs, srcs, on_texels, vis, alpha, "alpha")
     lib, f32, ptr = p.lib, torch.float32, [x.data_ptr() for x in p.srcs]
     if mode == "dpixel":
-        ws, nbytes = _workspace(p, lib.reni_envmap_shade_ggx_dpixel_workspace_bytes(p.B, p.NP, p.J))
+        ws, wp, wn = _ws256(int(lib.reni_envmap_shade_ggx_dpixel_workspace_bytes(p.B, p.NP, p.J)), p.dev)
         d_alpha = torch.empty(p.NP, dtype=f32, device=p.dev)
         d_normals = torch.empty((p.NP, 3), dtype=f32, device=p.dev) if need_dn else None
         _call(lib.reni_envmap_shade_ggx_dpixel, p.dev, *p.head, ptr[0], *p.mats, ptr[1], ptr[2], ptr[3], d_alpha.data_ptr(),
-              d_normals.data_ptr() if need_dn else None, ws.data_ptr(), nbytes)
+              _ptr(d_normals), wp, wn)
         return d_alpha, d_normals
-    ws, nbytes = _workspace(p, lib.reni_envmap_shade_ggx_workspace_bytes(p.B, p.NP, p.J))
+    ws, wp, wn = _ws256(int(lib.reni_envmap_shade_ggx_workspace_bytes(p.B, p.NP, p.J)), p.dev)
     if mode == "forward":
         outs = [torch.empty((p.B, p.NP, 3), dtype=f32, device=p.dev) for _ in range(3)]
         _call(lib.reni_envmap_shade_ggx, p.dev, *p.head, ptr[0], *p.mats, outs[0].data_ptr(), outs[1].data_ptr(),
-              outs[2].data_ptr(), ws.data_ptr(), nbytes)
+              outs[2].data_ptr(), wp, wn)
         return tuple(outs)
     out = torch.empty((p.B, p.J, 3), dtype=f32, device=p.dev)
-    _call(lib.reni_envmap_shade_ggx_backward, p.dev, *p.head, *p.mats, ptr[0], ptr[1], ptr[2], out.data_ptr(), ws.data_ptr(), nbytes)
+    _call(lib.reni_envmap_shade_ggx_backward, p.dev, *p.head, *p.mats, ptr[0], ptr[1], ptr[2], out.data_ptr(), wp, wn)
     return out
 
 
@@ -871,9 +888,10 @@ def face_pixel_table(pix_to_face: torch.Tensor, F: int):
 
 
 def _gbuffer_backward_inputs(verts, faces, vert_normals, R, T, image_size, pix_to_face, grad_pixel_normals, grad_pixel_positions,
-                             table, vf, need_lists):
-    """The checked and cast arguments of ``gbuffer_backward_camera`` (``gbuffer_backward``'s checks, in its order) and the
-    vertex lists (None when not needed)."""
+                             tan_half_fov, table, vf, need_lists):
+    """What ``gbuffer_backward`` and ``gbuffer_backward_camera`` share: the checks, in their order, the casts, the pixel table
+    and the vertex lists (not built, and NULL in the call, when not needed) -> (device, V, F, S, the arguments the two entry
+    points have in common -- everything in front of grad_verts --, the tensors those point into)."""
     _mesh_shapes(verts, faces)
     S = _image_size(image_size)
     if not isinstance(vert_normals, torch.Tensor) or tuple(vert_normals.shape) != tuple(verts.shape):
@@ -900,8 +918,11 @@ def _gbuffer_backward_inputs(verts, faces, vert_normals, R, T, image_size, pix_t
     if (tuple(foff.shape) != (F + 1,) or tuple(flist.shape) != (S * S,) or foff.dtype != torch.int64 or flist.dtype != torch.int64
             or foff.device != dev or flist.device != dev):
         raise ValueError(f"the table is not one of {S * S} pixels over {F} faces on {dev}")
-    lists = _vf_lists(faces, V, vf) if need_lists else None
-    return (verts, faces, vert_normals, Rh, Th, S, p2f, foff.contiguous(), flist.contiguous(), gN, gX), lists
+    foff, flist = foff.contiguous(), flist.contiguous()
+    offsets, corners = _vf_lists(faces, V, vf) if need_lists else (None, None)
+    head = (V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th, float(tan_half_fov), S, S, p2f.data_ptr(),
+            foff.data_ptr(), flist.data_ptr(), _ptr(offsets), _ptr(corners), _ptr(gN), _ptr(gX))
+    return dev, V, F, S, head, (verts, faces, vert_normals, p2f, foff, flist, offsets, corners, gN, gX)
 
 
 def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: torch.Tensor, R, T, image_size: int,
@@ -913,40 +934,12 @@ def gbuffer_backward(verts: torch.Tensor, faces: torch.Tensor, vert_normals: tor
     (``vertex_normals``' chain included: vert_normals must be the normals of verts, and is a constant here).  Either upstream
     gradient ([S*S, 3]) may be None, not both.  ``table``: ``face_pixel_table(pix_to_face, F)``, ``vf``: ``vertex_face_lists(faces, V)``, when the caller keeps them.
     Deterministic, no atomics; no silhouette / occlusion gradient, the camera is a constant."""
-    _mesh_shapes(verts, faces)
-    S = _image_size(image_size)
-    if not isinstance(vert_normals, torch.Tensor) or tuple(vert_normals.shape) != tuple(verts.shape):
-        raise ValueError("vert_normals must be [V, 3] like verts")
-    if not isinstance(pix_to_face, torch.Tensor) or pix_to_face.dtype != torch.int64 or pix_to_face.numel() != S * S:
-        raise ValueError(f"pix_to_face must be an int64 tensor of {S * S} entries (the rasteriser's)")
-    if grad_pixel_normals is None and grad_pixel_positions is None:
-        raise ValueError("grad_pixel_normals and grad_pixel_positions cannot both be None")
-    for name, g in (("grad_pixel_normals", grad_pixel_normals), ("grad_pixel_positions", grad_pixel_positions)):
-        if g is not None and (not isinstance(g, torch.Tensor) or tuple(g.shape) != (S * S, 3)):
-            raise ValueError(f"{name} must be [{S * S}, 3] or None, got {tuple(getattr(g, 'shape', ()))}")
-    Rh, Th = _camera_arrays(R, T)
-    verts, faces = _mesh_inputs(verts, faces)
-    _require_cuda(vert_normals, pix_to_face, grad_pixel_normals, grad_pixel_positions)
-    dev = verts.device
-    vert_normals = _f32c(vert_normals)
-    p2f = pix_to_face.reshape(-1).contiguous()
-    gN = None if grad_pixel_normals is None else _f32c(grad_pixel_normals)
-    gX = None if grad_pixel_positions is None else _f32c(grad_pixel_positions)
-    if any(t is not None and t.device != dev for t in (vert_normals, p2f, gN, gX)):
-        raise ValueError(f"the G-buffer and its gradients are not on {dev}")
-    V, F = verts.shape[0], faces.shape[0]
-    foff, flist = face_pixel_table(p2f, F) if table is None else table
-    if (tuple(foff.shape) != (F + 1,) or tuple(flist.shape) != (S * S,) or foff.dtype != torch.int64 or flist.dtype != torch.int64
-            or foff.device != dev or flist.device != dev):
-        raise ValueError(f"the table is not one of {S * S} pixels over {F} faces on {dev}")
-    offsets, corners = _vf_lists(faces, V, vf)
+    dev, V, F, S, head, keep = _gbuffer_backward_inputs(verts, faces, vert_normals, R, T, image_size, pix_to_face, grad_pixel_normals,
+                                                        grad_pixel_positions, tan_half_fov, table, vf, True)
     lib = _lib.load()
     out = torch.empty(V, 3, dtype=torch.float32, device=dev)
     ws, wp, wn = _ws256(int(lib.reni_gbuffer_backward_workspace_bytes(V, F, S, S)), dev)
-    _call(lib.reni_gbuffer_backward, dev, V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th,
-          float(tan_half_fov), S, S, p2f.data_ptr(), foff.contiguous().data_ptr(), flist.contiguous().data_ptr(),
-          offsets.data_ptr(), corners.data_ptr(), None if gN is None else gN.data_ptr(), None if gX is None else gX.data_ptr(),
-          out.data_ptr(), wp, wn)
+    _call(lib.reni_gbuffer_backward, dev, *head, out.data_ptr(), wp, wn)
     return out
 
 
@@ -964,18 +957,13 @@ def gbuffer_backward_camera(verts: torch.Tensor, faces: torch.Tensor, vert_norma
     differentiated as nine free numbers.  g_verts has ``gbuffer_backward``'s bits.  ``need_verts=False``: the mesh is known and
     only the pose is fitted -- the vertex kernels are not launched, no vertex list is built, g_verts is None; the camera's bits
     do not move.  Deterministic, no atomics."""
-    (verts, faces, vert_normals, Rh, Th, S, p2f, foff, flist, gN, gX), lists = _gbuffer_backward_inputs(
-        verts, faces, vert_normals, R, T, image_size, pix_to_face, grad_pixel_normals, grad_pixel_positions, table, vf, need_verts)
-    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    dev, V, F, S, head, keep = _gbuffer_backward_inputs(verts, faces, vert_normals, R, T, image_size, pix_to_face, grad_pixel_normals,
+                                                        grad_pixel_positions, tan_half_fov, table, vf, need_verts)
     lib = _lib.load()
     out = torch.empty(V, 3, dtype=torch.float32, device=dev) if need_verts else None
     cam = torch.empty(13, dtype=torch.float32, device=dev)
     ws, wp, wn = _ws256(int(lib.reni_gbuffer_backward_camera_workspace_bytes(V, F, S, S)), dev)
-    _call(lib.reni_gbuffer_backward_camera, dev, V, F, verts.data_ptr(), faces.data_ptr(), vert_normals.data_ptr(), Rh, Th,
-          float(tan_half_fov), S, S, p2f.data_ptr(), foff.data_ptr(), flist.data_ptr(),
-          None if lists is None else lists[0].data_ptr(), None if lists is None else lists[1].data_ptr(),
-          None if gN is None else gN.data_ptr(), None if gX is None else gX.data_ptr(), None if out is None else out.data_ptr(),
-          cam.data_ptr(), wp, wn)
+    _call(lib.reni_gbuffer_backward_camera, dev, *head, _ptr(out), cam.data_ptr(), wp, wn)
     return (out,) + _camera_gradient(cam)
 
 
@@ -1011,9 +999,10 @@ def soft_silhouette(verts: torch.Tensor, faces: torch.Tensor, R, T, image_size: 
     return alpha, trans
 
 
-def _silhouette_backward_inputs(verts, faces, R, T, image_size, sigma, blur_radius, trans, grad_alpha, vf, need_lists):
-    """The checked and cast arguments of ``soft_silhouette_backward_camera`` (``soft_silhouette_backward``'s checks, in its
-    order) and the vertex lists (None when not needed)."""
+def _silhouette_backward_inputs(verts, faces, R, T, image_size, tan_half_fov, sigma, blur_radius, trans, grad_alpha, vf, need_lists):
+    """What ``soft_silhouette_backward`` and ``soft_silhouette_backward_camera`` share: the checks, in their order, the casts
+    and the vertex lists (not built, and NULL in the call, when not needed) -> (device, V, F, S, the arguments the two entry
+    points have in common -- everything in front of grad_verts --, the tensors those point into)."""
     _mesh_shapes(verts, faces)
     S = _image_size(image_size)
     sigma, blur_radius = _silhouette_scalars(sigma, blur_radius)
@@ -1028,8 +1017,10 @@ def _silhouette_backward_inputs(verts, faces, R, T, image_size, sigma, blur_radi
     if trans.device != dev or grad_alpha.device != dev:
         raise ValueError(f"trans and grad_alpha are not on {dev}")
     V, F = verts.shape[0], faces.shape[0]
-    lists = _vf_lists(faces, V, vf) if need_lists else None
-    return (verts, faces, Rh, Th, S, sigma, blur_radius, trans, grad_alpha), lists
+    offsets, corners = _vf_lists(faces, V, vf) if need_lists else (None, None)
+    head = (V, F, verts.data_ptr(), faces.data_ptr(), Rh, Th, float(tan_half_fov), S, S, sigma, blur_radius, trans.data_ptr(),
+            grad_alpha.data_ptr(), _ptr(offsets), _ptr(corners))
+    return dev, V, F, S, head, (verts, faces, trans, grad_alpha, offsets, corners)
 
 
 def soft_silhouette_backward(verts: torch.Tensor, faces: torch.Tensor, R, T, image_size: int, tan_half_fov: float, sigma: float,
@@ -1038,26 +1029,12 @@ def soft_silhouette_backward(verts: torch.Tensor, faces: torch.Tensor, R, T, ima
     ``soft_silhouette`` (``trans`` as it returned it), with membership, inside / outside, the nearest edge and a clamped edge
     parameter held constant; the camera is a constant.  ``vf``: ``vertex_face_lists(faces, V)`` when the caller keeps it.
     Deterministic, no atomics."""
-    _mesh_shapes(verts, faces)
-    S = _image_size(image_size)
-    sigma, blur_radius = _silhouette_scalars(sigma, blur_radius)
-    for name, t in (("trans", trans), ("grad_alpha", grad_alpha)):
-        if not isinstance(t, torch.Tensor) or t.numel() != S * S:
-            raise ValueError(f"{name} must be a tensor of {S * S} entries, got {tuple(getattr(t, 'shape', ()))}")
-    Rh, Th = _camera_arrays(R, T)
-    verts, faces = _mesh_inputs(verts, faces)
-    _require_cuda(trans, grad_alpha)
-    dev = verts.device
-    trans, grad_alpha = _f32c(trans).reshape(-1), _f32c(grad_alpha).reshape(-1)
-    if trans.device != dev or grad_alpha.device != dev:
-        raise ValueError(f"trans and grad_alpha are not on {dev}")
-    V, F = verts.shape[0], faces.shape[0]
-    offsets, corners = _vf_lists(faces, V, vf)
+    dev, V, F, S, head, keep = _silhouette_backward_inputs(verts, faces, R, T, image_size, tan_half_fov, sigma, blur_radius, trans,
+                                                           grad_alpha, vf, True)
     lib = _lib.load()
     out = torch.empty(V, 3, dtype=torch.float32, device=dev)
     ws, wp, wn = _ws256(int(lib.reni_soft_silhouette_backward_workspace_bytes(V, F, S, S)), dev)
-    _call(lib.reni_soft_silhouette_backward, dev, V, F, verts.data_ptr(), faces.data_ptr(), Rh, Th, float(tan_half_fov), S, S, sigma,
-          blur_radius, trans.data_ptr(), grad_alpha.data_ptr(), offsets.data_ptr(), corners.data_ptr(), out.data_ptr(), wp, wn)
+    _call(lib.reni_soft_silhouette_backward, dev, *head, out.data_ptr(), wp, wn)
     return out
 
 
@@ -1070,16 +1047,13 @@ def soft_silhouette_backward_camera(verts: torch.Tensor, faces: torch.Tensor, R,
     differentiated as nine free numbers.  g_verts has ``soft_silhouette_backward``'s bits.  ``need_verts=False``: the mesh is
     known and only the pose is fitted -- the vertex kernel is not launched, no vertex list is built, g_verts is None; the
     camera's bits do not move.  Deterministic, no atomics."""
-    (verts, faces, Rh, Th, S, sigma, blur_radius, trans, grad_alpha), lists = _silhouette_backward_inputs(
-        verts, faces, R, T, image_size, sigma, blur_radius, trans, grad_alpha, vf, need_verts)
-    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    dev, V, F, S, head, keep = _silhouette_backward_inputs(verts, faces, R, T, image_size, tan_half_fov, sigma, blur_radius, trans,
+                                                           grad_alpha, vf, need_verts)
     lib = _lib.load()
     out = torch.empty(V, 3, dtype=torch.float32, device=dev) if need_verts else None
     cam = torch.empty(13, dtype=torch.float32, device=dev)
     ws, wp, wn = _ws256(int(lib.reni_soft_silhouette_backward_camera_workspace_bytes(V, F, S, S)), dev)
-    _call(lib.reni_soft_silhouette_backward_camera, dev, V, F, verts.data_ptr(), faces.data_ptr(), Rh, Th, float(tan_half_fov), S, S,
-          sigma, blur_radius, trans.data_ptr(), grad_alpha.data_ptr(), None if lists is None else lists[0].data_ptr(),
-          None if lists is None else lists[1].data_ptr(), None if out is None else out.data_ptr(), cam.data_ptr(), wp, wn)
+    _call(lib.reni_soft_silhouette_backward_camera, dev, *head, _ptr(out), cam.data_ptr(), wp, wn)
     return (out,) + _camera_gradient(cam)
 
 
@@ -1186,7 +1160,7 @@ def mesh_regularizers(verts: torch.Tensor, faces: torch.Tensor, edge: float = 0.
     ws, wp, wn = _ws256(int(lib.reni_mesh_regularizers_workspace_bytes(V, F, L["E"])), dev)
     _call(lib.reni_mesh_regularizers, dev, V, F, L["E"], L["H"], L["NC"], verts.data_ptr(), faces.data_ptr(),
           *[L[k].data_ptr() for k in _EDGE_LIST_NAMES], w[0], w[1], w[2], target_length, _lib.LAPLACIAN[method], values.data_ptr(),
-          None if grad is None else grad.data_ptr(), wp, wn)
+          _ptr(grad), wp, wn)
     return values, grad
 
 
@@ -1299,9 +1273,7 @@ def sg_loss_grad(params, theta_c, phi_c, theta_range: float, phi_range: float, l
     params, theta_c, phi_c, Np, K, H, W = _sg_check(params, theta_c, phi_c, H, W)
     if Np != N:
         raise ValueError("params and log_target disagree on N")
-    if weight.dtype != torch.float32:
-        weight = weight.float()
-    weight = weight.expand(N, 3, H, W)
+    weight = _f32(weight).expand(N, 3, H, W)
     dev = params.device
     loss_map = torch.empty(N, dtype=torch.float32, device=dev)
     total = torch.empty((), dtype=torch.float32, device=dev)
@@ -1341,17 +1313,23 @@ def sh_reconstruct(coeffs, row_table, col_table, H: int, W: int, lmax: int) -> t
     return _sh_call(False, coeffs, row_table, col_table, int(H), int(W), int(lmax))
 
 
-def _convolve_args(src, in_dirs, in_weight, out_dirs):
-    """The operands the convolutions over the sphere share: (src float32, in_dirs, in_weight, out_dirs contiguous float32,
-    N, P, Q, src's element strides (map, texel, channel)) for src [N, Q, 3] or channel-planar [N, 3, Q]."""
+def _sphere_operands(in_dirs, in_weight, out_dirs):
+    """in_dirs [Q, 3], in_weight [Q] and out_dirs [P, 3] of a convolution over the sphere as contiguous float32, checked, then
+    P and Q."""
     in_dirs, in_weight, out_dirs = _f32c(in_dirs), _f32c(in_weight), _f32c(out_dirs)
     if in_dirs.dim() != 2 or in_dirs.shape[1] != 3 or out_dirs.dim() != 2 or out_dirs.shape[1] != 3:
         raise ValueError("in_dirs and out_dirs must be [Q, 3] and [P, 3]")
     Q, P = in_dirs.shape[0], out_dirs.shape[0]
     if tuple(in_weight.shape) != (Q,):
         raise ValueError(f"in_weight must be [Q] = [{Q}], got {tuple(in_weight.shape)}")
-    if src.dtype != torch.float32:
-        src = src.float()
+    return in_dirs, in_weight, out_dirs, P, Q
+
+
+def _convolve_args(src, in_dirs, in_weight, out_dirs):
+    """The operands the convolutions over the sphere share: (src float32, in_dirs, in_weight, out_dirs contiguous float32,
+    N, P, Q, src's element strides (map, texel, channel)) for src [N, Q, 3] or channel-planar [N, 3, Q]."""
+    in_dirs, in_weight, out_dirs, P, Q = _sphere_operands(in_dirs, in_weight, out_dirs)
+    src = _f32(src)
     if src.dim() != 3:
         raise ValueError(f"src must be [N, Q, 3] or [N, 3, Q], got {tuple(src.shape)}")
     N = src.shape[0]
@@ -1380,6 +1358,16 @@ def diffuse_convolve(src, in_dirs, in_weight, out_dirs, scale: float) -> torch.T
     return out
 
 
+def _per_map_operand(t, N):
+    """(P, the map stride in elements) of an operand [P, 3] that N maps share (stride 0) or [N, P, 3] with one set per map;
+    None when t is neither.  What it is called, and whether P = 0 is an error, is the caller's."""
+    if t.dim() == 2 and t.shape[1] == 3:
+        return t.shape[0], 0
+    if t.dim() == 3 and t.shape[0] == N and t.shape[2] == 3:
+        return t.shape[1], 3 * t.shape[1]
+    return None
+
+
 def sh_irradiance_l2(coeffs, normals) -> torch.Tensor:
     """reni_sh_irradiance_l2: shRenderL2 of coeffs [N, 9, 3] at normals [P, 3] (shared) or [N, P, 3] (per map) -> [N, P, 3]."""
     _require_cuda(coeffs, normals)
@@ -1387,24 +1375,14 @@ def sh_irradiance_l2(coeffs, normals) -> torch.Tensor:
     if coeffs.dim() != 3 or coeffs.shape[1:] != (9, 3):
         raise ValueError(f"coeffs must be [N, 9, 3], got {tuple(coeffs.shape)}")
     N = coeffs.shape[0]
-    if normals.dim() == 2 and normals.shape[1] == 3:
-        P, stride = normals.shape[0], 0
-    elif normals.dim() == 3 and normals.shape[0] == N and normals.shape[2] == 3:
-        P = normals.shape[1]
-        stride = 3 * P
-    else:
+    shape = _per_map_operand(normals, N)
+    if shape is None:
         raise ValueError(f"normals must be [P, 3] or [N, P, 3], got {tuple(normals.shape)}")
+    P, stride = shape
     dev = coeffs.device
     out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
     _call(_lib.load().reni_sh_irradiance_l2, dev, N, P, coeffs.data_ptr(), normals.data_ptr(), stride, out.data_ptr())
     return out
-
-
-def _ws256(nbytes, device):
-    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    p = ws.data_ptr()
-    ap = (p + 255) & ~255
-    return ws, ap, ws.numel() - (ap - p)
 
 
 def _lobe_args(kinds, params):
@@ -1437,21 +1415,23 @@ def lobe_convolve(src, in_dirs, in_weight, out_dirs, kinds, params, normalise: b
     return out
 
 
+def _level_tensor(level):
+    """level where it is a tensor of per-direction levels; None for None, a number or a 0-d tensor (one constant level)"""
+    return level if isinstance(level, torch.Tensor) and level.dim() > 0 else None
+
+
 def _lookup_dirs_level(N, dirs, level, dev):
     """The directions and the level of a lookup of N maps on dev, checked: (dirs float32 contiguous, P, the directions' map
     stride, the level tensor or None, its pointer or None, its map stride, the constant level)."""
     dirs = _f32c(dirs)
-    if dirs.dim() == 2 and dirs.shape[1] == 3:
-        P, dn = dirs.shape[0], 0
-    elif dirs.dim() == 3 and dirs.shape[0] == N and dirs.shape[2] == 3:
-        P = dirs.shape[1]
-        dn = 3 * P
-    else:
+    shape = _per_map_operand(dirs, N)
+    if shape is None:
         raise ValueError(f"dirs must be [P, 3] or [{N}, P, 3], got {tuple(dirs.shape)}")
+    P, dn = shape
     if P < 1:
         raise ValueError("no directions")
     lp, ln, lc = None, 0, 0.0
-    if isinstance(level, torch.Tensor) and level.dim() > 0:
+    if _level_tensor(level) is not None:
         level = _f32c(level)
         if tuple(level.shape) == (P,):
             ln = 0
@@ -1469,14 +1449,10 @@ def _lookup_dirs_level(N, dirs, level, dev):
     return dirs, P, dn, level if lp is not None else None, lp, ln, lc
 
 
-def envmap_lookup(maps, dirs, level=None) -> torch.Tensor:
-    """reni_envmap_lookup: the bilinear sample, on the sphere, of equirectangular maps [N, H, W, 3] or chains of maps
-    [N, Lv, H, W, 3] (any strides, read in place) at directions dirs [P, 3] (shared) or [N, P, 3] (per map), which need not
-    have unit length -> [N, P, 3].  level: None (level 0), a number, or a float tensor [P] / [N, P]; it is clamped to
-    [0, Lv - 1] and the result mixes floor(level) and the next level linearly."""
-    _require_cuda(maps, dirs, level if isinstance(level, torch.Tensor) and level.dim() > 0 else None)
-    if maps.dtype != torch.float32:
-        maps = maps.float()
+def _lookup_maps(maps):
+    """The maps of a lookup, [N, H, W, 3] or a chain [N, Lv, H, W, 3] with any strides, as a float32 view [N, Lv, H, W, 3],
+    checked, then N, Lv, H, W."""
+    maps = _f32(maps)
     if maps.dim() == 4:
         maps = maps.unsqueeze(1)
     if maps.dim() != 5 or maps.shape[4] != 3:
@@ -1484,11 +1460,20 @@ def envmap_lookup(maps, dirs, level=None) -> torch.Tensor:
     N, Lv, H, W, _ = maps.shape
     if min(N, Lv, H, W) < 1 or W % 2:
         raise ValueError(f"expected non-empty maps of even width, got {tuple(maps.shape)}")
+    return maps, N, Lv, H, W
+
+
+def envmap_lookup(maps, dirs, level=None) -> torch.Tensor:
+    """reni_envmap_lookup: the bilinear sample, on the sphere, of equirectangular maps [N, H, W, 3] or chains of maps
+    [N, Lv, H, W, 3] (any strides, read in place) at directions dirs [P, 3] (shared) or [N, P, 3] (per map), which need not
+    have unit length -> [N, P, 3].  level: None (level 0), a number, or a float tensor [P] / [N, P]; it is clamped to
+    [0, Lv - 1] and the result mixes floor(level) and the next level linearly."""
+    _require_cuda(maps, dirs, _level_tensor(level))
+    maps, N, Lv, H, W = _lookup_maps(maps)
     dev = maps.device
     dirs, P, dn, level, lp, ln, lc = _lookup_dirs_level(N, dirs, level, dev)
     out = torch.empty(N, P, 3, dtype=torch.float32, device=dev)
-    st = (ctypes.c_int64 * 5)(*maps.stride())
-    _call(_lib.load().reni_envmap_lookup, dev, N, Lv, H, W, P, maps.data_ptr(), st, dirs.data_ptr(), dn, lp, ln, lc,
+    _call(_lib.load().reni_envmap_lookup, dev, N, Lv, H, W, P, maps.data_ptr(), _strides(maps), dirs.data_ptr(), dn, lp, ln, lc,
           out.data_ptr())
     return out
 
@@ -1498,12 +1483,7 @@ def lobe_denominators(in_dirs, in_weight, out_dirs, kinds, params) -> torch.Tens
     ``lobe_convolve`` divides by when it normalises, bit for bit (the forward's own launch without maps)."""
     _require_cuda(in_dirs, in_weight, out_dirs)
     Lv, ck, cp = _lobe_args(kinds, params)
-    in_dirs, in_weight, out_dirs = _f32c(in_dirs), _f32c(in_weight), _f32c(out_dirs)
-    if in_dirs.dim() != 2 or in_dirs.shape[1] != 3 or out_dirs.dim() != 2 or out_dirs.shape[1] != 3:
-        raise ValueError("in_dirs and out_dirs must be [Q, 3] and [P, 3]")
-    Q, P = in_dirs.shape[0], out_dirs.shape[0]
-    if tuple(in_weight.shape) != (Q,):
-        raise ValueError(f"in_weight must be [Q] = [{Q}], got {tuple(in_weight.shape)}")
+    in_dirs, in_weight, out_dirs, P, Q = _sphere_operands(in_dirs, in_weight, out_dirs)
     dev = in_dirs.device
     den = torch.empty(Lv, P, dtype=torch.float32, device=dev)
     lib = _lib.load()
@@ -1520,12 +1500,8 @@ def lobe_convolve_backward(grad_out, in_dirs, in_weight, out_dirs, kinds, params
     ``lobe_denominators`` for these operands (computed here when None and normalising; not needed otherwise)."""
     _require_cuda(grad_out, in_dirs, in_weight, out_dirs, den)
     Lv, ck, cp = _lobe_args(kinds, params)
-    in_dirs, in_weight, out_dirs, grad_out = _f32c(in_dirs), _f32c(in_weight), _f32c(out_dirs), _f32c(grad_out)
-    if in_dirs.dim() != 2 or in_dirs.shape[1] != 3 or out_dirs.dim() != 2 or out_dirs.shape[1] != 3:
-        raise ValueError("in_dirs and out_dirs must be [Q, 3] and [P, 3]")
-    Q, P = in_dirs.shape[0], out_dirs.shape[0]
-    if tuple(in_weight.shape) != (Q,):
-        raise ValueError(f"in_weight must be [Q] = [{Q}], got {tuple(in_weight.shape)}")
+    in_dirs, in_weight, out_dirs, P, Q = _sphere_operands(in_dirs, in_weight, out_dirs)
+    grad_out = _f32c(grad_out)
     if grad_out.dim() != 4 or tuple(grad_out.shape[1:]) != (Lv, P, 3) or grad_out.shape[0] < 1:
         raise ValueError(f"grad_out must be [N, {Lv}, {P}, 3], got {tuple(grad_out.shape)}")
     N = grad_out.shape[0]
@@ -1554,7 +1530,7 @@ def envmap_lookup_table(N: int, Lv: int, H: int, W: int, dirs, level=None):
     N, Lv, H, W = int(N), int(Lv), int(H), int(W)
     if min(N, Lv, H, W) < 1 or W % 2 or Lv * H * W >= 2 ** 31:
         raise ValueError(f"expected N, Lv, H, W >= 1, an even width and Lv H W < 2^31, got {(N, Lv, H, W)}")
-    _require_cuda(dirs, level if isinstance(level, torch.Tensor) and level.dim() > 0 else None)
+    _require_cuda(dirs, _level_tensor(level))
     dev = dirs.device
     dirs, P, dn, level, lp, ln, lc = _lookup_dirs_level(N, dirs, level, dev)
     T = 1 if dn == 0 and ln == 0 else N
@@ -1606,16 +1582,8 @@ def envmap_lookup_dquery(maps, dirs, level, grad_out, need_dirs: bool = True, ne
     level outside [0, Lv - 1]; at a knot the level's slope is the right-sided one, at Lv - 1 the left-sided one."""
     if not (need_dirs or need_level):
         raise ValueError("neither d dirs nor d level is asked for")
-    _require_cuda(maps, dirs, grad_out, level if isinstance(level, torch.Tensor) and level.dim() > 0 else None)
-    if maps.dtype != torch.float32:
-        maps = maps.float()
-    if maps.dim() == 4:
-        maps = maps.unsqueeze(1)
-    if maps.dim() != 5 or maps.shape[4] != 3:
-        raise ValueError(f"maps must be [N, H, W, 3] or [N, Lv, H, W, 3], got {tuple(maps.shape)}")
-    N, Lv, H, W, _ = maps.shape
-    if min(N, Lv, H, W) < 1 or W % 2:
-        raise ValueError(f"expected non-empty maps of even width, got {tuple(maps.shape)}")
+    _require_cuda(maps, dirs, grad_out, _level_tensor(level))
+    maps, N, Lv, H, W = _lookup_maps(maps)
     dev = maps.device
     dirs, P, dn, level, lp, ln, lc = _lookup_dirs_level(N, dirs, level, dev)
     if need_level and lp is None:
@@ -1625,9 +1593,8 @@ def envmap_lookup_dquery(maps, dirs, level, grad_out, need_dirs: bool = True, ne
         raise ValueError(f"grad_out must be [{N}, {P}, 3] on {dev}, got {tuple(grad_out.shape)} on {grad_out.device}")
     d_dirs = torch.empty_like(dirs) if need_dirs else None
     d_level = torch.empty_like(level) if need_level else None
-    st = (ctypes.c_int64 * 5)(*maps.stride())
-    _call(_lib.load().reni_envmap_lookup_dquery, dev, N, Lv, H, W, P, maps.data_ptr(), st, dirs.data_ptr(), dn, lp, ln, lc,
-          grad_out.data_ptr(), d_dirs.data_ptr() if need_dirs else None, d_level.data_ptr() if need_level else None)
+    _call(_lib.load().reni_envmap_lookup_dquery, dev, N, Lv, H, W, P, maps.data_ptr(), _strides(maps), dirs.data_ptr(), dn, lp, ln, lc,
+          grad_out.data_ptr(), _ptr(d_dirs), _ptr(d_level))
     return d_dirs, d_level
 
 
@@ -1733,9 +1700,8 @@ def texture_taps(uv, size, levels=None, jac=None, pix_valid=None, wrap: str = "c
         raise ValueError(f"jac and pix_valid must be on {dev}")
     idx = torch.empty(P, 8, dtype=torch.int32, device=dev)
     wgt = torch.empty(P, 8, dtype=torch.float32, device=dev)
-    _call(_lib.load().reni_texture_taps, dev, P, uv.data_ptr(), None if jac is None else jac.data_ptr(),
-          None if pix_valid is None else pix_valid.data_ptr(), L, H0, W0, lod_bias, _lib.TEX_WRAP[wrap], 1 if align_corners else 0,
-          idx.data_ptr(), wgt.data_ptr())
+    _call(_lib.load().reni_texture_taps, dev, P, uv.data_ptr(), _ptr(jac), _ptr(pix_valid), L, H0, W0, lod_bias, _lib.TEX_WRAP[wrap],
+          1 if align_corners else 0, idx.data_ptr(), wgt.data_ptr())
     return idx, wgt
 
 
@@ -1846,17 +1812,15 @@ def unnormalise_srgb(img: torch.Tensor, minmax=None, srgb: bool = True, want_lin
         img = img.unsqueeze(0)
     if img.dim() != 4 or img.shape[1] != 3:
         raise ValueError(f"expected [B,3,H,W] or [3,H,W], got {tuple(img.shape)}")
-    if img.dtype != torch.float32:
-        img = img.float()
+    img = _f32(img)
     B, _, H, W = img.shape
-    st = (ctypes.c_int64 * 4)(*img.stride())
     dev = img.device
     out = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if srgb else None
     lin = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev) if (want_linear or not srgb) else None
     ws, wp, wn = _ws256(int(lib.reni_image_workspace_bytes(B, H, W)), dev) if srgb else (None, None, 0)
     m0, m1 = (float(minmax[0]), float(minmax[1])) if minmax is not None else (0.0, 1.0)
-    _call(lib.reni_unnormalise_srgb, dev, B, H, W, img.data_ptr(), st, 0 if minmax is None else 1, m0, m1, 1 if srgb else 0,
-          out.data_ptr() if out is not None else None, lin.data_ptr() if lin is not None else None, wp, wn)
+    _call(lib.reni_unnormalise_srgb, dev, B, H, W, img.data_ptr(), _strides(img), 0 if minmax is None else 1, m0, m1, 1 if srgb else 0,
+          _ptr(out), _ptr(lin), wp, wn)
     if srgb and want_linear:
         return out, lin
     return out if srgb else lin
@@ -1932,9 +1896,7 @@ def resample(src: torch.Tensor, size, mode: str = "bilinear", layout: str = "aut
     Hd, Wd = int(size[0]), int(size[1])
     if Hd < 1 or Wd < 1:
         raise ValueError(f"size must be (height >= 1, width >= 1), got {tuple(size)}")
-    if src.dtype != torch.float32:
-        src = src.float()
-    x, unview = _image_layout(src, layout)
+    x, unview = _image_layout(_f32(src), layout)
     N, C, Hs, Ws = x.shape
     if min(N, C, Hs, Ws) < 1:
         raise ValueError(f"empty image {tuple(src.shape)}")
@@ -1942,8 +1904,7 @@ def resample(src: torch.Tensor, size, mode: str = "bilinear", layout: str = "aut
     ri, rw = device_tables(Hs, Hd, mode, dev)
     ci, cw = device_tables(Ws, Wd, mode, dev)
     out = torch.empty(N, C, Hd, Wd, dtype=torch.float32, device=dev)
-    st = (ctypes.c_int64 * 4)(*x.stride())
-    _call(_lib.load().reni_resample, dev, N, C, Hs, Ws, Hd, Wd, x.data_ptr(), st, ri.data_ptr(), rw.data_ptr(), TAPS[mode],
+    _call(_lib.load().reni_resample, dev, N, C, Hs, Ws, Hd, Wd, x.data_ptr(), _strides(x), ri.data_ptr(), rw.data_ptr(), TAPS[mode],
           ci.data_ptr(), cw.data_ptr(), TAPS[mode], out.data_ptr())
     return unview(out)
 
@@ -1957,7 +1918,7 @@ def gaussian_blur(img: torch.Tensor, sigma: float, layout: str = "auto") -> torc
     if img.dim() not in (2, 3):
         raise ValueError(f"expected one image [H,W], [H,W,C] or [C,H,W], got {tuple(img.shape)}")
     w, r = gaussian_weights(sigma)
-    x = img if img.dtype == torch.float32 else img.float()
+    x = _f32(img)
     out = torch.empty_like(x)
     if out.stride() != x.stride():
         x = x.contiguous()
@@ -1969,9 +1930,8 @@ def gaussian_blur(img: torch.Tensor, sigma: float, layout: str = "auto") -> torc
     dev = x.device
     lib = _lib.load()
     wt = torch.from_numpy(w.astype("float32")).to(dev)
-    st = (ctypes.c_int64 * 3)(*v.stride()[1:])
     ws, wp, wn = _ws256(int(lib.reni_blur_workspace_bytes(C, H, W)), dev)
-    _call(lib.reni_gaussian_blur, dev, C, H, W, x.data_ptr(), st, wt.data_ptr(), r, out.data_ptr(), wp, wn)
+    _call(lib.reni_gaussian_blur, dev, C, H, W, x.data_ptr(), _strides(v[0]), wt.data_ptr(), r, out.data_ptr(), wp, wn)
     return out
 
 
@@ -2002,9 +1962,7 @@ def rotate_envmap(src: torch.Tensor, rot: torch.Tensor, mode: str = "bilinear", 
     _require_cuda(src, rot, index if isinstance(index, torch.Tensor) else None)
     if mode not in _lib.ROTATE_MODE:
         raise ValueError(f"mode must be one of {tuple(_lib.ROTATE_MODE)}, got {mode!r}")
-    if src.dtype != torch.float32:
-        src = src.float()
-    x, unview = _image_layout(src, layout)
+    x, unview = _image_layout(_f32(src), layout)
     N, C, H, W = x.shape
     if min(N, C, H, W) < 1 or W % 2:
         raise ValueError(f"expected non-empty maps of even width, got {tuple(src.shape)}")
@@ -2027,8 +1985,7 @@ def rotate_envmap(src: torch.Tensor, rot: torch.Tensor, mode: str = "bilinear", 
         raise ValueError(f"rot must be [3, 3] or [{B}, 3, 3], got {tuple(rot.shape)}")
     rt, ct = _rotate_trig(H, W, dev)
     out = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
-    st = (ctypes.c_int64 * 4)(*x.stride())
-    _call(_lib.load().reni_rotate_envmap, dev, B, C, H, W, x.data_ptr(), st, None if index is None else index.data_ptr(), N,
+    _call(_lib.load().reni_rotate_envmap, dev, B, C, H, W, x.data_ptr(), _strides(x), _ptr(index), N,
           rot.data_ptr(), rot_stride, rt.data_ptr(), ct.data_ptr(), _lib.ROTATE_MODE[mode], out.data_ptr())
     return unview(out)
 
@@ -2038,7 +1995,6 @@ def _pair_args(pred, target, weight, size=None, check_weight=True):
     ValueError.  An image batch is [B, 3, H, W] with any strides or a model output [B, P, 3] (``size`` = (H, W); default: the
     other operand's, else P = H x 2H); the weight is anything that broadcasts to [B, H, W] (sin(phi) per row: [H, 1]) or a
     mask / sineweight [1 | B, P, 3] (channel 0 is read).  Negative weights raise (check_weight: one read-back per call)."""
-    import math
     if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor):
         raise ValueError("pred and target must be tensors")
     if size is None:
@@ -2060,7 +2016,7 @@ def _pair_args(pred, target, weight, size=None, check_weight=True):
             v = x.unflatten(1, (int(size[0]), int(size[1]))).permute(0, 3, 1, 2)
         else:
             raise ValueError(f"{name} must be [B, 3, H, W] or a model output [B, P, 3], got {tuple(x.shape)}")
-        views.append(v if v.dtype == torch.float32 else v.float())
+        views.append(_f32(v))
     p, t = views
     if p.shape != t.shape:
         raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} are not the same batch of images")
@@ -2073,7 +2029,7 @@ def _pair_args(pred, target, weight, size=None, check_weight=True):
     if weight is not None:
         if not isinstance(weight, torch.Tensor):
             raise ValueError("weight must be a tensor or None")
-        w = weight if weight.dtype == torch.float32 else weight.float()
+        w = _f32(weight)
         if w.dim() == 3 and w.shape[2] == 3 and w.shape[1] == H * W and w.shape[0] in (1, B) and (H, W) != (H * W, 3):
             w = w[..., 0].unflatten(1, (H, W))
         try:
@@ -2109,9 +2065,8 @@ def _space_args(space, minmax, exposure, B, device):
 
 def _pair_call_head(p, t, w, space, m0, m1, exposure):
     B, _, H, W = p.shape
-    return (B, H, W, p.data_ptr(), (ctypes.c_int64 * 4)(*p.stride()), t.data_ptr(), (ctypes.c_int64 * 4)(*t.stride()),
-            None if w is None else w.data_ptr(), None if w is None else (ctypes.c_int64 * 3)(*w.stride()), _lib.SPACE[space],
-            m0, m1, None if exposure is None else exposure.data_ptr())
+    return (B, H, W, p.data_ptr(), _strides(p), t.data_ptr(), _strides(t), _ptr(w), _strides(w),
+            _lib.SPACE[space], m0, m1, _ptr(exposure))
 
 
 def pair_stats(pred, target, weight=None, space: str = "stored", minmax=None, exposure=None, size=None,
@@ -2157,7 +2112,7 @@ def ssim(pred, target, weight=None, space: str = "stored", minmax=None, exposure
     smap = torch.empty(B, H, W, dtype=torch.float32, device=p.device) if return_map else None
     ws, wp, wn = _ws256(int(lib.reni_pair_stats_workspace_bytes(B, H, W)), p.device)
     _call(lib.reni_ssim, p.device, *_pair_call_head(p, t, w, space, m0, m1, exposure), float(L),
-          _lib.SSIM_MODE["sphere" if sphere else "planar"], out.data_ptr(), None if smap is None else smap.data_ptr(), wp, wn)
+          _lib.SSIM_MODE["sphere" if sphere else "planar"], out.data_ptr(), _ptr(smap), wp, wn)
     return (out, smap) if return_map else out
 
 
@@ -2226,8 +2181,8 @@ def light_table_build(maps, space: str = "linear", minmax=None, mask=None, unifo
     cond = torch.empty(B, H, W, dtype=torch.float32, device=dev)
     marg = torch.empty(B, H, dtype=torch.float32, device=dev)
     ws, wp, wn = _ws256(int(lib.reni_light_table_workspace_bytes(B, H, W)), dev)
-    _call(lib.reni_light_table_build, dev, B, H, W, v.data_ptr(), (ctypes.c_int64 * 4)(*v.stride()),
-          None if w is None else w.data_ptr(), None if w is None else (ctypes.c_int64 * 3)(*w.stride()), _lib.SPACE[space], m0, m1,
+    _call(lib.reni_light_table_build, dev, B, H, W, v.data_ptr(), _strides(v), _ptr(w), _strides(w),
+          _lib.SPACE[space], m0, m1,
           sa.data_ptr(), float(uniform_mix), pmf.data_ptr(), cond.data_ptr(), marg.data_ptr(), wp, wn)
     return pmf, cond, marg
 
@@ -2256,8 +2211,8 @@ def light_sample(pmf, cond, marg, maps, u, space: str = "linear", minmax=None, t
     dirs, radiance, colors = (torch.empty(B, S, 3, dtype=torch.float32, device=dev) for _ in range(3))
     pdf = torch.empty(B, S, dtype=torch.float32, device=dev)
     _call(lib.reni_light_sample, dev, B, H, W, S, pmf.data_ptr(), cond.data_ptr(), marg.data_ptr(), v.data_ptr(),
-          (ctypes.c_int64 * 4)(*v.stride()), _lib.SPACE[space], m0, m1, u.data_ptr(), 0 if u.dim() == 2 else 2 * S, dt.data_ptr(),
-          sa.data_ptr(), rc.data_ptr(), None if tw is None else tw.data_ptr(), 1 if jitter else 0, index.data_ptr(), dirs.data_ptr(),
+          _strides(v), _lib.SPACE[space], m0, m1, u.data_ptr(), 0 if u.dim() == 2 else 2 * S, dt.data_ptr(),
+          sa.data_ptr(), rc.data_ptr(), _ptr(tw), 1 if jitter else 0, index.data_ptr(), dirs.data_ptr(),
           pdf.data_ptr(), radiance.data_ptr(), colors.data_ptr())
     return index, dirs, pdf, radiance, colors
 
@@ -2271,13 +2226,10 @@ def lights_irradiance(normals, dirs, colors, scale: float) -> torch.Tensor:
     if dirs.dim() != 3 or dirs.shape[2] != 3 or dirs.shape != colors.shape or min(dirs.shape[:2]) < 1:
         raise ValueError(f"dirs and colors must both be [B, S, 3], got {tuple(dirs.shape)} and {tuple(colors.shape)}")
     B, S = int(dirs.shape[0]), int(dirs.shape[1])
-    if normals.dim() == 2 and normals.shape[1] == 3 and normals.shape[0] >= 1:
-        P, stride = int(normals.shape[0]), 0
-    elif normals.dim() == 3 and normals.shape[0] == B and normals.shape[2] == 3 and normals.shape[1] >= 1:
-        P = int(normals.shape[1])
-        stride = 3 * P
-    else:
+    shape = _per_map_operand(normals, B)
+    if shape is None or shape[0] < 1:
         raise ValueError(f"normals must be [P, 3] or [{B}, P, 3], got {tuple(normals.shape)}")
+    P, stride = shape
     _require_cuda(normals, dirs, colors)
     normals, dirs, colors = _f32c(normals), _f32c(dirs), _f32c(colors)
     out = torch.empty(B, P, 3, dtype=torch.float32, device=dirs.device)

@@ -573,6 +573,65 @@ int reni_mesh_regularizers(int64_t V, int64_t F, int64_t E, int64_t H, int64_t N
                            int32_t method, float* values /* [4] device */, float* grad_verts /* [V][3] device, or NULL */,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* ---- point clouds: nearest points, the chamfer gradient, samples of a mesh's surface (reni_tu_points.hip) -----------------
+ * What scores a recovered shape against the true one, and pulls a mesh towards a cloud: sample both surfaces, take the chamfer
+ * distance and the F-score (reni_amd/mesh_losses.py).  fp32, no float atomics, no in-launch ticket, no host synchronisation,
+ * launches on `stream` only: two calls give identical bits.  One cloud per call (no batches), no spatial index: brute force.
+ *
+ * reni_nearest_points.  For x [N][3], y [M][3]:  d(i, j) = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) with dx = x_i0 - y_j0, dy, dz
+ *   likewise (exactly this form: the bits are defined).  idx[i] (int64) = the LOWEST j among those with the smallest d(i, j) as
+ *   computed; dist2[i] = d(i, idx[i]).  The comparison is a strict <: where none succeeds (NaN coordinates, or every d = +inf),
+ *   idx[i] = 0 and dist2[i] is what d(i, 0) computes.  A result is never turned into an address outside [0, M).
+ *   Structure: 2 queries per lane in registers, 512 per workgroup; the targets pass through LDS in tiles of 1024 16-byte
+ *   records that every lane reads at the same address.  grid.y cuts the target range into `slices` contiguous slices; with
+ *   more than one, a second launch takes the lexicographic minimum of the slices' (d, j), so the result has the same bits for
+ *   ANY slicing.  slices = 0: the library's choice, min(cap, ceil(M / 1024)); slices > 0 is clamped to min(cap, M), where
+ *   cap = max(1, 512 / ceil(N / 512)) -- so slicing stops once the queries alone give 512 workgroups.
+ *   Launches (counted by reni_launch_count): 1 with one slice, else 2.
+ *   Limits: 1 <= N, M <= 2^31 - 1025.  ws: reni_nearest_points_workspace_bytes(N, M) bytes, 256-byte aligned (0 for sizes out of
+ *   range): two 4-byte partials per (query, slice) for cap slices when cap > 1 -- at most 2 MiB + 256 bytes whatever N, and
+ *   independent of M.  It is never N x M.
+ *
+ * reni_chamfer_grad.  For  L = (w_x / N) sum_i dist2_x[i] + (w_y / M) sum_j dist2_y[j]  with idx_xy [N] (x's nearest y) and
+ *   idx_yx [M] (y's nearest x) from two searches, held CONSTANT:
+ *     grad_x[i] = g (2 w_x / N) (x_i - y_idx_xy[i]) + g (2 w_y / M) sum_{j : idx_yx[j] = i} (x_i - y_j),
+ *   evaluated as (g cx) t1 + (g cy) t2 with cx = (2 w_x) / N, cy = (2 w_y) / M in fp32; g is read from the device.  The second
+ *   term is gathered through the sorted table (order [M] = the stable argsort of idx_yx, offsets [N + 1] = where each i's
+ *   range starts; ops.chamfer_table) by reni_texture_fetch_backward's rule: a range of at most 128 entries is summed by its
+ *   lane from 0 in order; a longer one in chunks of 64 consecutive entries by the 64 lanes of the wave (lane l adds entries
+ *   l, l + 64, ...), combined by the xor butterfly 32, 16, 8, 4, 2, 1.  An idx_xy entry or an order entry outside [0, M) adds
+ *   nothing, offsets are clamped into [0, M]: nothing of them is trusted as an address.  A weight of 0 skips its term, which
+ *   adds exactly 0, and its lists may be NULL.  Weights must be >= 0 and finite.  Called with the roles swapped it gives
+ *   grad_y.  grad_x [N][3] is overwritten.  1 launch.
+ *
+ * reni_mesh_sample_table.  table [2][F] (device): table[0][f] = the area of face f, 0.5 |(x_1 - x_0) x (x_2 - x_0)| in fp32; a
+ *   face that does not TAKE PART (the regularisers' rule: indices in [0, V), pairwise different) and an area that is 0 or not
+ *   finite count as 0.  table[1][f] = the CDF: the inclusive prefix sums of the areas in double by a parallel scan in a fixed
+ *   order (Hillis-Steele in a wave, waves, 256-entry tiles and 1024-face chunks in ascending order), divided by the scan's own
+ *   value at the last chunk with mass and rounded once; made ascending, and flat over a face without area, by a running
+ *   maximum behind the division, as reni_light_table_build's CDFs are.  The last face with area and everything behind it hold
+ *   exactly 1.0f.  Total area 0: the CDF is 0 everywhere.  3 launches.  ws: reni_mesh_sample_table_workspace_bytes(F).
+ *
+ * reni_mesh_sample_points.  For u [S][3] (each clamped into [0, 1), NaN -> 0):  face = the number of CDF entries <= u0, at most
+ *   F - 1 -- a face without area is never chosen;  r = sqrtf(u1),  w = (1 - r, r (1 - u2), r u2)  (pytorch3d's).  The output is
+ *   a tap table of the texture unit: tap_index [S][8] int32 = the face's three vertices then 0, tap_weight [S][8] = w then 0;
+ *   and face_idx [S] int64.  Positions are reni_texture_fetch(P = S, E = V, C = 3, tex = verts) and the gradient with respect to
+ *   the vertices is reni_texture_fetch_backward: the face choice and the barycentrics are CONSTANTS of the gradient.  A table
+ *   without mass (its last CDF entry is not 1.0f) gives all-zero weights and index 0, so the points are exactly 0; no host
+ *   check.  tap_index and tap_weight must be 16-byte aligned for the fetch.  1 launch.  Limits: V, F < 2^30, S < 2^28. */
+size_t reni_nearest_points_workspace_bytes(int64_t N, int64_t M);
+int reni_nearest_points(int64_t N, int64_t M, const float* x, const float* y, int32_t slices, float* dist2 /* [N] */,
+                        int64_t* idx /* [N] */, void* ws, size_t ws_bytes, void* stream);
+int reni_chamfer_grad(int64_t N, int64_t M, const float* x, const float* y, const int64_t* idx_xy /* [N], or NULL with w_x = 0 */,
+                      const int64_t* order /* [M] */, const int64_t* offsets /* [N + 1]; both may be NULL with w_y = 0 */,
+                      float w_x, float w_y, const float* g /* [1] device */, float* grad_x /* [N][3] */, void* stream);
+size_t reni_mesh_sample_table_workspace_bytes(int64_t F);
+int reni_mesh_sample_table(int64_t V, int64_t F, const float* verts, const int64_t* faces, float* table /* [2][F] */, void* ws,
+                           size_t ws_bytes, void* stream);
+int reni_mesh_sample_points(int64_t V, int64_t F, int64_t S, const int64_t* faces, const float* table, const float* u /* [S][3] */,
+                            int32_t* tap_index /* [S][8] */, float* tap_weight /* [S][8] */, int64_t* face_idx /* [S] */,
+                            void* stream);
+
 /* ---- cast shadows: visibility masks of the mesh for the shader (reni_tu_visibility.hip, the MASKED shader instances) ----
  * The shader above lets light pass through the mesh: M(p, j) knows the pixel's own normal and nothing else.  The lights are at
  * infinity, so whether texel direction j reaches pixel p is a constant of (mesh, camera, directions), as the G-buffer is.

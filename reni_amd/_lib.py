@@ -46,6 +46,8 @@ EXPORTS = (
     "reni_gbuffer_backward_camera_workspace_bytes", "reni_gbuffer_backward_camera",
     "reni_soft_silhouette_backward_camera_workspace_bytes", "reni_soft_silhouette_backward_camera",
     "reni_mesh_regularizers_workspace_bytes", "reni_mesh_regularizers",
+    "reni_nearest_points_workspace_bytes", "reni_nearest_points", "reni_chamfer_grad",
+    "reni_mesh_sample_table_workspace_bytes", "reni_mesh_sample_table", "reni_mesh_sample_points",
     "reni_mesh_visibility_accel_bytes", "reni_mesh_visibility_prepare", "reni_mesh_visibility",
     "reni_envmap_shade_masked", "reni_envmap_shade_masked_backward",
     "reni_envmap_shade_terms_workspace_bytes", "reni_envmap_shade_terms", "reni_envmap_shade_terms_backward",
@@ -232,6 +234,21 @@ def load():
     lib.reni_mesh_regularizers.argtypes = ([c_int64] * 5 + [c_void_p] * 10 + [c_float] * 4 + [c_int32, c_void_p, c_void_p, c_void_p,
                                                                                               c_size_t, c_void_p])
     lib.reni_mesh_regularizers.restype = c_int32
+    lib.reni_nearest_points_workspace_bytes.argtypes = [c_int64, c_int64]
+    lib.reni_nearest_points_workspace_bytes.restype = c_size_t
+    # N, M; x, y; slices; dist2, idx, ws ..
+    lib.reni_nearest_points.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_nearest_points.restype = c_int32
+    # N, M; x, y, idx_xy, order, offsets; w_x, w_y; g, grad_x
+    lib.reni_chamfer_grad.argtypes = [c_int64, c_int64] + [c_void_p] * 5 + [c_float, c_float, c_void_p, c_void_p, c_void_p]
+    lib.reni_chamfer_grad.restype = c_int32
+    lib.reni_mesh_sample_table_workspace_bytes.argtypes = [c_int64]
+    lib.reni_mesh_sample_table_workspace_bytes.restype = c_size_t
+    lib.reni_mesh_sample_table.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_mesh_sample_table.restype = c_int32
+    # V, F, S; faces, table, u; tap_index, tap_weight, face_idx
+    lib.reni_mesh_sample_points.argtypes = [c_int64] * 3 + [c_void_p] * 7
+    lib.reni_mesh_sample_points.restype = c_int32
     lib.reni_mesh_visibility_accel_bytes.argtypes = [c_int64]
     lib.reni_mesh_visibility_accel_bytes.restype = c_size_t
     lib.reni_mesh_visibility_prepare.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]

@@ -341,6 +341,7 @@ class Meshes:
         self._normals = None
         self._vf = None
         self._el = None
+        self._st = None
         self._verts_uvs = self._faces_uvs = None
         if (verts_uvs is None) != (faces_uvs is None):
             raise ValueError("verts_uvs and faces_uvs come together")
@@ -374,6 +375,14 @@ class Meshes:
             self._el = (key, ops.mesh_edge_lists(self._faces, self._verts.shape[0]))
         return self._el[1]
 
+    def _sample_table(self):
+        """the area table of ``sample_points_from_meshes`` (``ops.mesh_sample_table``), kept per in-place version of the vertices
+        and faces"""
+        key = (self._verts._version, self._faces._version)
+        if self._st is None or self._st[0] != key:
+            self._st = (key, ops.mesh_sample_table(self._verts.detach(), self._faces))
+        return self._st[1]
+
     def edges_packed(self) -> torch.Tensor:
         """[E, 2] int64: the unique undirected edges (a < b) of the faces taking part, in ascending (a, b)"""
         lists = self._edge_lists()
@@ -401,6 +410,37 @@ class Meshes:
     @property
     def device(self):
         return self._verts.device
+
+
+_ICO_FACES = ((0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+              (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1))
+
+
+def ico_sphere(level: int = 0, device="cpu") -> Meshes:
+    """The unit icosphere as a ``Meshes``: level 0 is the icosahedron (12 vertices, 20 faces, outward winding); every level
+    splits each face in four with ONE midpoint per edge, shared by the two faces on it, re-projected to the unit sphere.
+    V = 10 * 4^level + 2, F = 20 * 4^level, E = 30 * 4^level.  Plain torch; a template to start a vertex fit from."""
+    level = int(level)
+    if level < 0:
+        raise ValueError("level must be >= 0")
+    t = (1.0 + math.sqrt(5.0)) / 2.0
+    v = torch.tensor([(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1),
+                      (t, 0, 1), (-t, 0, -1), (-t, 0, 1)], dtype=torch.float64)  # the cyclic permutations of (+-1, +-phi, 0)
+    v = v / v.norm(dim=1, keepdim=True)
+    f = torch.tensor(_ICO_FACES, dtype=torch.int64)
+    for _ in range(level):
+        V = v.shape[0]
+        a = torch.cat([f[:, 0], f[:, 1], f[:, 2]])
+        b = torch.cat([f[:, 1], f[:, 2], f[:, 0]])
+        keys = torch.minimum(a, b) * V + torch.maximum(a, b)
+        ukeys, inv = torch.unique(keys, return_inverse=True)  # one midpoint per undirected edge, in ascending (a, b)
+        mid = v[ukeys // V] + v[ukeys % V]
+        v = torch.cat([v, mid / mid.norm(dim=1, keepdim=True)])
+        F = f.shape[0]
+        m01, m12, m20 = V + inv[:F], V + inv[F:2 * F], V + inv[2 * F:]
+        f = torch.cat([torch.stack([f[:, 0], m01, m20], 1), torch.stack([f[:, 1], m12, m01], 1),
+                       torch.stack([f[:, 2], m20, m12], 1), torch.stack([m01, m12, m20], 1)])
+    return Meshes(verts=[v.to(torch.float32).to(device)], faces=[f.to(device)])
 
 
 class RasterizationSettings:

@@ -7,7 +7,14 @@ and where they deviate from pytorch3d).  They return 0-d tensors; the gradient a
 renderer's and the silhouette's, and it is bit-reproducible: no float atomics, every sum in an order that depends on the
 topology alone.  The kernel produces the gradient with the value (the objective is a scalar), so the backward is one multiply.
 The topology lists are kept by the ``Meshes`` per in-place version of its faces; the values are computed anew at every call, so
-an in-place optimiser step on the vertices is seen.  There is no CPU path: CPU tensors raise."""
+an in-place optimiser step on the vertices is seen.  There is no CPU path: CPU tensors raise.
+
+Point clouds (reni_tu_points.hip, include/reni_hip.h "point clouds"): ``nearest_points``, ``chamfer_distance`` (an autograd
+function: both searches in the forward, the sort and the gather in the backward, only for the inputs that require grad),
+``sample_points_from_meshes`` (area-weighted samples, differentiable with respect to the vertices through the texture unit's
+fetch) and ``geometry_scores`` (chamfer, precision, recall and F-score of a recovered mesh against the true one).  The same
+guarantees: no N x M matrix, no float atomics, identical bits on a second call.  Not provided: a normals term, point-to-triangle
+distance, batches of clouds, a spatial index (brute force is the design up to the sizes DESIGN 4.4u measures)."""
 import torch
 
 from . import _lib, ops
@@ -65,3 +72,129 @@ def mesh_regularizer(mesh, edge: float = 0.0, laplacian: float = 0.0, normal: fl
     """edge * mesh_edge_loss + laplacian * mesh_laplacian_smoothing + normal * mesh_normal_consistency from ONE call of the
     kernels (a weight of 0 skips that term's work)"""
     return _apply(mesh, (edge, laplacian, normal), target_length, method, 0)
+
+
+# ---------------------------------------------------------------------------------------------------------- point clouds
+def nearest_points(x: torch.Tensor, y: torch.Tensor):
+    """(dist2 [N] float32, idx [N] int64): for every x_i the squared distance to, and the lowest index of, its nearest y_j
+    (``ops.nearest_points``).  It carries no gradient."""
+    with torch.no_grad():
+        return ops.nearest_points(x, y)
+
+
+class _ChamferFn(torch.autograd.Function):
+    """(w_x / N) sum_i min_j |x_i - y_j|^2 + (w_y / M) sum_j min_i |x_i - y_j|^2; the matches are constants of the gradient"""
+
+    @staticmethod
+    def forward(ctx, x, y, wx, wy):
+        xd, yd = x.detach(), y.detach()
+        value = torch.zeros((), dtype=torch.float32, device=xd.device)
+        idx_xy = idx_yx = None
+        if wx > 0.0:  # (a weight of 0 skips that direction's search and adds exactly 0)
+            d, idx_xy = ops.nearest_points(xd, yd)
+            value = value + wx * d.mean()
+        if wy > 0.0:
+            d, idx_yx = ops.nearest_points(yd, xd)
+            value = value + wy * d.mean()
+        ctx.save_for_backward(xd, yd, idx_xy, idx_yx)
+        ctx.w = (wx, wy)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, yd, idx_xy, idx_yx = ctx.saved_tensors
+        wx, wy = ctx.w
+        gx = gy = None
+        g = g.to(torch.float32)
+        if ctx.needs_input_grad[0]:
+            table = ops.chamfer_table(idx_yx, xd.shape[0]) if wy > 0.0 else None
+            gx = ops.chamfer_grad(xd, yd, idx_xy, table, (wx, wy), g)
+        if ctx.needs_input_grad[1]:
+            table = ops.chamfer_table(idx_xy, yd.shape[0]) if wx > 0.0 else None
+            gy = ops.chamfer_grad(yd, xd, idx_yx, table, (wy, wx), g)
+        return gx, gy, None, None
+
+
+def chamfer_distance(x: torch.Tensor, y: torch.Tensor, weights=(1.0, 1.0)) -> torch.Tensor:
+    """weights[0] mean_i min_j |x_i - y_j|^2 + weights[1] mean_j min_i |x_i - y_j|^2 for the clouds x [N, 3], y [M, 3] (squared
+    distances, pytorch3d's default), a 0-d tensor.  Differentiable in both clouds with the matches held constant; ``x.grad`` and
+    ``y.grad`` are bit-reproducible.  A weight of 0 skips that direction."""
+    ops._cloud(x, "x")
+    ops._cloud(y, "y")
+    wx, wy = (float(w) for w in weights)
+    for name, w in (("weights[0]", wx), ("weights[1]", wy)):
+        if not (w >= 0.0) or w == float("inf"):
+            raise ValueError(f"{name} must be >= 0 and finite, got {w}")
+    ops._require_cuda(x, y)
+    if x.device != y.device:
+        raise ValueError("x and y must be on the same device")
+    return _ChamferFn.apply(x, y, wx, wy)
+
+
+class _SamplePointsFn(torch.autograd.Function):
+    """points [S, 3] = the taps' weighted vertices (``ops.texture_fetch``); the taps are constants of the gradient"""
+
+    @staticmethod
+    def forward(ctx, verts, idx, wgt):
+        ctx.save_for_backward(idx, wgt)
+        ctx.V = verts.shape[0]
+        return ops.texture_fetch(verts.detach(), idx, wgt)
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, wgt = ctx.saved_tensors
+        table = ops.texture_table(idx, ctx.V, wgt)
+        return ops.texture_fetch_backward(g.contiguous(), wgt, table, ctx.V), None, None
+
+
+def _draw(n, device, generator):
+    gdev = generator.device if generator is not None else device
+    return torch.rand(n, 3, dtype=torch.float32, device=gdev, generator=generator).to(device)
+
+
+def sample_points_from_meshes(mesh, n: int = 10000, u=None, generator=None, return_faces: bool = False):
+    """n points on the mesh's surface, uniform by area (pytorch3d's ``sample_points_from_meshes`` for one mesh): [n, 3], and with
+    ``return_faces`` the face of each, [n] int64.  ``u`` [n, 3] in [0, 1) are the random numbers (face, two barycentrics); without
+    it they are drawn from ``generator`` (``torch.rand``).  Differentiable with respect to ``mesh.verts_packed()``: the face choice
+    and the barycentrics are constants of the gradient.  The area table is kept by the ``Meshes`` per in-place version of its
+    vertices.  A mesh without area gives points that are exactly 0."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    verts, faces = mesh.verts_packed(), mesh.faces_packed()
+    if u is not None and (not isinstance(u, torch.Tensor) or tuple(u.shape) != (n, 3)):
+        raise ValueError(f"u must be a tensor [{n}, 3]")
+    ops._require_cuda(verts, faces, u)
+    if u is None:
+        u = _draw(n, verts.device, generator)
+    idx, wgt, face_idx = ops.mesh_sample_points(faces, mesh._sample_table(), u, verts.shape[0])
+    points = _SamplePointsFn.apply(verts, idx, wgt)
+    return (points, face_idx) if return_faces else points
+
+
+def geometry_scores(pred_mesh, true_mesh, n: int = 10000, thresholds=(0.01, 0.02), u=None, generator=None) -> dict:
+    """How close the surface of ``pred_mesh`` is to that of ``true_mesh``, from n samples of each, under ``no_grad``: a dict of 0-d
+    tensors -- ``chamfer`` = ``chamfer_pred`` + ``chamfer_true`` (the mean squared distance from the pred samples to their nearest
+    true sample, and the other way round), and per threshold t ``precision@t`` (the share of pred samples within DISTANCE t --
+    not squared -- of a true sample), ``recall@t`` (the share of true samples within t of a pred sample) and
+    ``fscore@t`` = 2 P R / (P + R), 0 when both are 0.  ``u`` [n, 3] is used for BOTH meshes; without it two sets are drawn from
+    ``generator``.  Distances are between samples, not from a point to the other surface: they are biased upwards by the sampling
+    density (about the mean spacing of n samples, squared), so compare scores at one n."""
+    with torch.no_grad():
+        dev = pred_mesh.verts_packed().device
+        ops._require_cuda(pred_mesh.verts_packed(), true_mesh.verts_packed())
+        up = u if u is not None else _draw(int(n), dev, generator)
+        ut = u if u is not None else _draw(int(n), dev, generator)
+        p = sample_points_from_meshes(pred_mesh, n, u=up)
+        t = sample_points_from_meshes(true_mesh, n, u=ut)
+        d_p, _ = ops.nearest_points(p, t)
+        d_t, _ = ops.nearest_points(t, p)
+        out = {"chamfer_pred": d_p.mean(), "chamfer_true": d_t.mean()}
+        out["chamfer"] = out["chamfer_pred"] + out["chamfer_true"]
+        dist_p, dist_t = d_p.sqrt(), d_t.sqrt()
+        for tau in thresholds:
+            tau = float(tau)
+            P, R = (dist_p <= tau).float().mean(), (dist_t <= tau).float().mean()
+            out[f"precision@{tau:g}"], out[f"recall@{tau:g}"] = P, R
+            out[f"fscore@{tau:g}"] = torch.where(P + R > 0, 2 * P * R / (P + R).clamp_min(1e-30), torch.zeros_like(P))
+        return out

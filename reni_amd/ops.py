@@ -1164,6 +1164,134 @@ def mesh_regularizers(verts: torch.Tensor, faces: torch.Tensor, edge: float = 0.
     return values, grad
 
 
+def _cloud(t, name):
+    """The shape rule of a point cloud, a ValueError before any device is looked at"""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{name} must be a tensor [N, 3] with N >= 1, got {tuple(getattr(t, 'shape', ()))}")
+
+
+def _cloud_pair(x, y):
+    _cloud(x, "x")
+    _cloud(y, "y")
+    _require_cuda(x, y)
+    x, y = _f32c(x.detach()), _f32c(y.detach())
+    if y.device != x.device:
+        raise ValueError("x and y must be on the same device")
+    return x, y
+
+
+def nearest_points(x: torch.Tensor, y: torch.Tensor, slices: int = 0):
+    """reni_nearest_points: (dist2 [N] float32, idx [N] int64) -- for every x_i the LOWEST index of the nearest y_j under
+    d = fmaf(dz, dz, fmaf(dy, dy, dx dx)) and that d.  Brute force through LDS tiles, never an N x M matrix; ``slices`` cuts the
+    target range over more workgroups (0: the library's choice) and never changes a bit of the result."""
+    slices = int(slices)
+    if slices < 0:
+        raise ValueError("slices must be >= 0")
+    x, y = _cloud_pair(x, y)
+    N, M, dev = x.shape[0], y.shape[0], x.device
+    lib = _lib.load()
+    dist2 = torch.empty(N, dtype=torch.float32, device=dev)
+    idx = torch.empty(N, dtype=torch.int64, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_nearest_points_workspace_bytes(N, M)), dev)
+    _call(lib.reni_nearest_points, dev, N, M, x.data_ptr(), y.data_ptr(), slices, dist2.data_ptr(), idx.data_ptr(), wp, wn)
+    return dist2, idx
+
+
+def chamfer_table(idx_yx: torch.Tensor, N: int):
+    """What ``chamfer_grad`` gathers its second term through: (order [M] int64, offsets [N + 1] int64) from idx_yx [M], the
+    nearest x of every y -- a stable sort and a searchsorted, as ``texture_table``'s.  An entry outside [0, N) falls outside
+    every range."""
+    if not isinstance(idx_yx, torch.Tensor) or idx_yx.dim() != 1 or idx_yx.dtype != torch.int64 or idx_yx.numel() < 1:
+        raise ValueError("idx_yx must be an int64 tensor [M] with M >= 1")
+    N = int(N)
+    if N < 1:
+        raise ValueError("N must be >= 1")
+    keys, order = torch.sort(idx_yx, stable=True)
+    offsets = torch.searchsorted(keys, torch.arange(N + 1, device=idx_yx.device, dtype=torch.int64))
+    return order.contiguous(), offsets.to(torch.int64).contiguous()
+
+
+def chamfer_grad(x: torch.Tensor, y: torch.Tensor, idx_xy, table, weights=(1.0, 1.0), g=None) -> torch.Tensor:
+    """reni_chamfer_grad: grad_x [N, 3] of L = (w_x / N) sum_i dist2_x[i] + (w_y / M) sum_j dist2_y[j] times the device scalar
+    ``g`` (None: 1), with the matches held constant: idx_xy [N] is x's nearest y, table = ``chamfer_table(idx_yx, N)``.  A weight
+    of 0 skips its term (its list may be None).  Deterministic, no atomics.  With x, y and the weights swapped it is grad_y."""
+    _cloud(x, "x")
+    _cloud(y, "y")
+    wx, wy = (float(w) for w in weights)
+    for name, w in (("w_x", wx), ("w_y", wy)):
+        if not (w >= 0.0) or not math.isfinite(w):
+            raise ValueError(f"{name} must be >= 0 and finite, got {w}")
+    N, M = x.shape[0], y.shape[0]
+    if wx > 0.0 and (not isinstance(idx_xy, torch.Tensor) or tuple(idx_xy.shape) != (N,) or idx_xy.dtype != torch.int64):
+        raise ValueError(f"idx_xy must be an int64 tensor [{N}]")
+    order = offsets = None
+    if wy > 0.0:
+        try:
+            order, offsets = table
+        except (TypeError, ValueError):
+            raise ValueError(f"table must be chamfer_table(idx_yx, {N})") from None
+        if (not isinstance(order, torch.Tensor) or not isinstance(offsets, torch.Tensor) or tuple(order.shape) != (M,)
+                or tuple(offsets.shape) != (N + 1,) or order.dtype != torch.int64 or offsets.dtype != torch.int64):
+            raise ValueError(f"table must be chamfer_table(idx_yx, {N}) of {M} points")
+    if wx == 0.0:
+        idx_xy = None
+    x, y = _cloud_pair(x, y)
+    dev = x.device
+    _require_cuda(idx_xy, order, offsets, g)
+    for t in (idx_xy, order, offsets, g):
+        if t is not None and t.device != dev:
+            raise ValueError(f"the lists and g must be on {dev}")
+    if g is None:
+        g = torch.ones(1, dtype=torch.float32, device=dev)
+    elif not isinstance(g, torch.Tensor) or g.numel() != 1:
+        raise ValueError("g must hold one value")
+    g = _f32c(g.detach()).reshape(1)
+    idx_xy, order, offsets = (None if t is None else t.contiguous() for t in (idx_xy, order, offsets))
+    grad = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    _call(_lib.load().reni_chamfer_grad, dev, N, M, x.data_ptr(), y.data_ptr(), _ptr(idx_xy), _ptr(order), _ptr(offsets), wx, wy,
+          g.data_ptr(), grad.data_ptr())
+    return grad
+
+
+def mesh_sample_table(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """reni_mesh_sample_table: table [2, F] float32 -- the faces' areas (0 for a face that takes no part or has no finite area)
+    and their CDF, ascending, flat over faces without area, ending on exactly 1 (all 0 for a mesh without area)."""
+    _mesh_shapes(verts, faces)
+    verts, faces = _mesh_inputs(verts.detach(), faces)
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    lib = _lib.load()
+    table = torch.empty(2, F, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_mesh_sample_table_workspace_bytes(F)), dev)
+    _call(lib.reni_mesh_sample_table, dev, V, F, verts.data_ptr(), faces.data_ptr(), table.data_ptr(), wp, wn)
+    return table
+
+
+def mesh_sample_points(faces: torch.Tensor, table: torch.Tensor, u: torch.Tensor, V: int):
+    """reni_mesh_sample_points: (tap_index [S, 8] int32, tap_weight [S, 8] float32, face_idx [S] int64) for u [S, 3] in [0, 1):
+    the face by area from u[:, 0] through ``table = mesh_sample_table(verts, faces)``, pytorch3d's barycentrics from the other
+    two.  The taps are the texture unit's: the points are ``texture_fetch(verts, tap_index, tap_weight)``."""
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError(f"faces must be a tensor [F, 3] with F >= 1, got {tuple(getattr(faces, 'shape', ()))}")
+    F, V = faces.shape[0], int(V)
+    if V < 1:
+        raise ValueError("V must be >= 1")
+    if not isinstance(table, torch.Tensor) or tuple(table.shape) != (2, F) or table.dtype != torch.float32:
+        raise ValueError(f"table must be mesh_sample_table(verts, faces): float32 [2, {F}]")
+    if not isinstance(u, torch.Tensor) or u.dim() != 2 or u.shape[1] != 3 or u.shape[0] < 1:
+        raise ValueError(f"u must be a tensor [S, 3] with S >= 1, got {tuple(getattr(u, 'shape', ()))}")
+    _require_cuda(faces, table, u)
+    faces, table, u = faces.to(torch.int64).contiguous(), table.contiguous(), _f32c(u)
+    dev, S = faces.device, u.shape[0]
+    if table.device != dev or u.device != dev:
+        raise ValueError(f"table and u must be on {dev}")
+    idx = torch.empty(S, 8, dtype=torch.int32, device=dev)
+    wgt = torch.empty(S, 8, dtype=torch.float32, device=dev)
+    face_idx = torch.empty(S, dtype=torch.int64, device=dev)
+    _call(_lib.load().reni_mesh_sample_points, dev, V, F, S, faces.data_ptr(), table.data_ptr(), u.data_ptr(), idx.data_ptr(),
+          wgt.data_ptr(), face_idx.data_ptr())
+    return idx, wgt, face_idx
+
+
 def _morton_order(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """A permutation of the faces that keeps neighbours together: the stable argsort of the 30-bit Morton codes of the
     centroids (10 bits per axis over the mesh's bounding box).  Faces with an index outside [0, V) sort last."""

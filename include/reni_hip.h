@@ -632,6 +632,62 @@ int reni_mesh_sample_points(int64_t V, int64_t F, int64_t S, const int64_t* face
                             int32_t* tap_index /* [S][8] */, float* tap_weight /* [S][8] */, int64_t* face_idx /* [S] */,
                             void* stream);
 
+/* ---- points against a mesh: the nearest triangle of a point, the nearest point of a triangle (reni_tu_pointmesh.hip) -------
+ * What the sample-based scores above cannot give: the distance from a point to the SURFACE (pytorch3d's
+ * point_mesh_face_distance, both directions), so a mesh scored against itself scores 0 and a scan pulls on the surface
+ * itself (reni_amd/mesh_losses.py: nearest_surface, point_mesh_distance, geometry_scores(surface=True)).  fp32, no float
+ * atomics, no in-launch ticket, no host synchronisation, launches on `stream` only: two calls give identical bits.  One mesh
+ * and one cloud per call, no spatial index and no culling: brute force.
+ *
+ * The pair function.  For a point p and the triangle (a, b, c), every operation in fp32, none contracted, dot(u, v) =
+ * fmaf(u2, v2, fmaf(u1, v1, u0 * v0)):
+ *     ab = b - a, ac = c - a;  ap = p - a, bp = ap - ab, cp = ap - ac;
+ *     d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
+ *     vc = fmaf(d1, d4, -(d3 * d2)), vb = fmaf(d5, d2, -(d1 * d6)), va = fmaf(d3, d6, -(d5 * d4));
+ *   the FIRST of these regions that holds gives (nv, nw, den):
+ *     vertex a:  d1 <= 0 and d2 <= 0                          (0, 0, 1)
+ *     vertex b:  d3 >= 0 and d4 <= d3                         (1, 0, 1)
+ *     edge ab:   vc <= 0 and d1 >= 0 and d3 <= 0              (d1, 0, d1 - d3)
+ *     vertex c:  d6 >= 0 and d5 <= d6                         (0, 1, 1)
+ *     edge ac:   vb <= 0 and d2 >= 0 and d6 <= 0              (0, d2, d2 - d6)
+ *     edge bc:   va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0    (d5 - d6, d4 - d3, (d4 - d3) + (d5 - d6))
+ *     interior:                                               (vb, vc, (va + vb) + vc)
+ *   r = 1 / den (correctly rounded);  v = min(max(nv r, 0), 1);  w = min(max(nw r, 0), 1 - v)  with fmaxf / fminf, so a NaN
+ *   quotient (0 / 0: a triangle without area) becomes 0.  The weights are (u, v, w) with u = (1 - v) - w: every one is >= 0
+ *   and they sum to 1, so q = a + v ab + w ac, evaluated as fmaf(w, ac, fmaf(v, ab, a)) per component, is a point of the
+ *   triangle.  d = fmaf(rz, rz, fmaf(ry, ry, rx * rx)) with r = p - q.  A vertex that is not finite makes q, and so d, a NaN.
+ *   A face TAKES PART by the regularisers' rule: indices in [0, V), pairwise different.  A face that takes no part is
+ *   compared as NaN.  Every comparison is a strict <, so a NaN and a face that takes no part win none.
+ *
+ * reni_nearest_faces.  For points [N][3], verts [V][3], faces [F][3] (int64):  face_idx[i] (int64) = the LOWEST f among those
+ *   with the smallest d(p_i, f) as computed, dist2[i] = that d, and a tap row of the texture unit as reni_mesh_sample_points
+ *   writes it: tap_index [N][8] int32 = the face's three vertices then 0, tap_weight [N][8] = (u, v, w) then 0.  The closest
+ *   points are reni_texture_fetch(P = N, E = V, C = 3, tex = verts) (u a + v b + w c by its fmaf chain: the same point up to
+ *   rounding) and reni_texture_fetch_backward carries their gradient to the vertices.  Where no face wins: face_idx = -1,
+ *   dist2 = +inf, all-zero taps at index 0.  A result is never turned into an address outside [0, V) or [0, F).
+ * reni_faces_nearest_points.  The other direction: point_idx[f] (int64) = the LOWEST i among those with the smallest
+ *   d(p_i, f), dist2[f] = that d, and the tap row [F][8] of the closest point of face f to that p_i.  A face that takes no
+ *   part, or against which no point wins: -1, +inf, zero taps.
+ * Structure (both: one templated kernel, two instances): 2 queries per lane in registers, 512 per workgroup; the targets pass
+ *   through LDS in tiles of 256 records that every lane reads at the same address -- a triangle as (a, ab, ac) in three
+ *   16-byte words, prepared once per tile, or a point in one.  grid.y cuts the target range into `slices` contiguous slices;
+ *   with more than one, a second launch takes the lexicographic minimum of the slices' (d, j), so the result has the same bits
+ *   for ANY slicing.  slices = 0: the library's choice, min(cap, ceil(targets / 256)); slices > 0 is clamped to
+ *   min(cap, targets), where cap = max(1, 512 / ceil(queries / 512)).  The tap row is computed from the winning pair by the
+ *   pair function once more: the same bits.
+ *   Launches (counted by reni_launch_count): 1 with one slice, else 2.
+ *   Limits: 1 <= N, F <= 2^31 - 257, 1 <= V < 2^30; tap_index and tap_weight 16-byte aligned.  ws:
+ *   reni_*_workspace_bytes(N, V, F) bytes, 256-byte aligned (0 for sizes out of range): two 4-byte partials per (query, slice)
+ *   for cap slices when cap > 1 -- at most 2 MiB + 768 bytes, independent of the number of targets.  It is never N x F. */
+size_t reni_nearest_faces_workspace_bytes(int64_t N, int64_t V, int64_t F);
+int reni_nearest_faces(int64_t N, int64_t V, int64_t F, const float* points, const float* verts, const int64_t* faces, int32_t slices,
+                       float* dist2 /* [N] */, int64_t* face_idx /* [N] */, int32_t* tap_index /* [N][8] */,
+                       float* tap_weight /* [N][8] */, void* ws, size_t ws_bytes, void* stream);
+size_t reni_faces_nearest_points_workspace_bytes(int64_t N, int64_t V, int64_t F);
+int reni_faces_nearest_points(int64_t N, int64_t V, int64_t F, const float* points, const float* verts, const int64_t* faces,
+                              int32_t slices, float* dist2 /* [F] */, int64_t* point_idx /* [F] */, int32_t* tap_index /* [F][8] */,
+                              float* tap_weight /* [F][8] */, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- cast shadows: visibility masks of the mesh for the shader (reni_tu_visibility.hip, the MASKED shader instances) ----
  * The shader above lets light pass through the mesh: M(p, j) knows the pixel's own normal and nothing else.  The lights are at
  * infinity, so whether texel direction j reaches pixel p is a constant of (mesh, camera, directions), as the G-buffer is.

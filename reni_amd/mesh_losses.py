@@ -13,8 +13,13 @@ Point clouds (reni_tu_points.hip, include/reni_hip.h "point clouds"): ``nearest_
 function: both searches in the forward, the sort and the gather in the backward, only for the inputs that require grad),
 ``sample_points_from_meshes`` (area-weighted samples, differentiable with respect to the vertices through the texture unit's
 fetch) and ``geometry_scores`` (chamfer, precision, recall and F-score of a recovered mesh against the true one).  The same
-guarantees: no N x M matrix, no float atomics, identical bits on a second call.  Not provided: a normals term, point-to-triangle
-distance, batches of clouds, a spatial index (brute force is the design up to the sizes DESIGN 4.4u measures)."""
+guarantees: no N x M matrix, no float atomics, identical bits on a second call.
+
+Points against a mesh (reni_tu_pointmesh.hip, include/reni_hip.h "points against a mesh"): ``nearest_surface`` (the nearest
+triangle of every point, its barycentrics and the closest point), ``point_mesh_distance`` (pytorch3d's
+``point_mesh_face_distance`` for one mesh and one cloud, an autograd function in the points and the vertices) and
+``geometry_scores(surface=True)``.  Not provided: a normals term, batches of clouds or meshes, a spatial index (brute force is
+the design up to the sizes DESIGN 4.4u and 4.4v measure)."""
 import torch
 
 from . import _lib, ops
@@ -131,6 +136,107 @@ def chamfer_distance(x: torch.Tensor, y: torch.Tensor, weights=(1.0, 1.0)) -> to
     return _ChamferFn.apply(x, y, wx, wy)
 
 
+# --------------------------------------------------------------------------------------------------- points against a mesh
+def nearest_surface(points: torch.Tensor, mesh):
+    """(dist2 [N] float32, face_idx [N] int64, bary [N, 3] float32, closest [N, 3] float32): for every point the squared distance
+    to the mesh's surface, the lowest index of the nearest triangle, the barycentric weights of the closest point with respect
+    to that face's three vertices, and the closest point (``ops.nearest_faces`` and ``ops.texture_fetch``).  Where no face takes
+    part: +inf, -1, zero weights and a point at 0.  It carries no gradient."""
+    with torch.no_grad():
+        verts = mesh.verts_packed()
+        dist2, face_idx, tap_index, tap_weight = ops.nearest_faces(points, verts, mesh.faces_packed())
+        return dist2, face_idx, tap_weight[:, :3].clone(), ops.texture_fetch(verts, tap_index, tap_weight)
+
+
+def _matched_mean(d, idx):
+    """(the mean of d over the entries with idx >= 0, 0 where there is none; the mask; their number, at least 1, as a float32
+    0-d tensor) -- on the device, nothing is read back"""
+    ok = idx >= 0
+    n = ok.sum().clamp_min(1).to(torch.float32)
+    return torch.where(ok, d, torch.zeros_like(d)).sum() / n, ok, n
+
+
+class _PointMeshFn(torch.autograd.Function):
+    """w0 mean_i min_f d(p_i, f) + w1 mean_f min_i d(p_i, f); the matches and the barycentrics are constants of the gradient (the
+    envelope theorem: at the closest point the derivative with respect to the barycentrics vanishes or is blocked by a bound)"""
+
+    @staticmethod
+    def forward(ctx, points, verts, faces, w0, w1):
+        pd, vd = points.detach(), verts.detach()
+        value = torch.zeros((), dtype=torch.float32, device=pd.device)
+        saved = [pd, vd]
+        if w0 > 0.0:  # (a weight of 0 skips that direction's search and adds exactly 0)
+            d, idx, tap_index, tap_weight = ops.nearest_faces(pd, vd, faces)
+            mean, ok, n = _matched_mean(d, idx)
+            value = value + w0 * mean
+            saved += [tap_index, tap_weight, ok, n]
+        if w1 > 0.0:
+            d, idx, tap_index, tap_weight = ops.faces_nearest_points(pd, vd, faces)
+            mean, ok, n = _matched_mean(d, idx)
+            value = value + w1 * mean
+            saved += [tap_index, tap_weight, idx, n]
+        ctx.save_for_backward(*saved)
+        ctx.w = (w0, w1)
+        return value
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = list(ctx.saved_tensors)
+        pd, vd = saved[:2]
+        del saved[:2]
+        w0, w1 = ctx.w
+        need_p, need_v = ctx.needs_input_grad[:2]
+        N, V = pd.shape[0], vd.shape[0]
+        g = g.to(torch.float32)
+        gp = torch.zeros_like(pd) if need_p else None
+        rows = []  # (tap_index, tap_weight, d L / d closest point) of every term that reaches the vertices
+        if w0 > 0.0:
+            tap_index, tap_weight, ok, n = saved[:4]
+            del saved[:4]
+            q = ops.texture_fetch(vd, tap_index, tap_weight)
+            r = torch.where(ok[:, None], pd - q, torch.zeros_like(q)) * (g * (2.0 * w0) / n)  # d L / d p_i = -(d L / d q_i)
+            if need_p:
+                gp = r
+            rows.append((tap_index, tap_weight, -r))
+        if w1 > 0.0:
+            tap_index, tap_weight, idx, n = saved[:4]
+            F = idx.shape[0]
+            q = ops.texture_fetch(vd, tap_index, tap_weight)  # [F, 3]; a face without a match: 0, and its idx -1 adds nothing
+            gf = g * (float(F) / n)  # chamfer_grad divides by F: the mean is over the n matched faces
+            if need_p:
+                gp = gp + ops.chamfer_grad(pd, q, None, ops.chamfer_table(idx, N), (0.0, w1), gf)
+            if need_v:
+                rows.append((tap_index, tap_weight, ops.chamfer_grad(q, pd, idx, None, (w1, 0.0), gf)))
+        gv = None
+        if need_v:
+            if rows:
+                tap_index, tap_weight, gq = (torch.cat(t) for t in zip(*rows))
+                gv = ops.texture_fetch_backward(gq, tap_weight, ops.texture_table(tap_index, V, tap_weight), V)
+            else:
+                gv = torch.zeros_like(vd)
+        return gp, gv, None, None, None
+
+
+def point_mesh_distance(points: torch.Tensor, mesh, weights=(1.0, 1.0)) -> torch.Tensor:
+    """weights[0] mean_i min_f d(p_i, f) + weights[1] mean_f min_i d(p_i, f) for the cloud points [N, 3] and the triangles f of
+    ``mesh``, d the squared distance from a point to a triangle (pytorch3d's ``point_mesh_face_distance`` for one mesh and one
+    cloud), a 0-d tensor.  The second mean is over the faces that take part (indices in [0, V), pairwise different); where a
+    coordinate is not finite, a mean is over the entries that found a match.  Differentiable in ``points`` and in
+    ``mesh.verts_packed()`` with the matches and the barycentrics held constant -- the exact gradient; both gradients are
+    bit-reproducible, and ``verts.grad`` accumulates beside ``mesh_regularizer``'s and ``chamfer_distance``'s.  A weight of 0 skips
+    that direction's search and adds exactly 0."""
+    ops._cloud(points, "points")
+    w0, w1 = (float(w) for w in weights)
+    for name, w in (("weights[0]", w0), ("weights[1]", w1)):
+        if not (w >= 0.0) or w == float("inf"):
+            raise ValueError(f"{name} must be >= 0 and finite, got {w}")
+    verts, faces = mesh.verts_packed(), mesh.faces_packed()
+    ops._require_cuda(points, verts, faces)
+    if points.device != verts.device:
+        raise ValueError("points and the mesh must be on the same device")
+    return _PointMeshFn.apply(points, verts, faces, w0, w1)
+
+
 class _SamplePointsFn(torch.autograd.Function):
     """points [S, 3] = the taps' weighted vertices (``ops.texture_fetch``); the taps are constants of the gradient"""
 
@@ -172,14 +278,18 @@ def sample_points_from_meshes(mesh, n: int = 10000, u=None, generator=None, retu
     return (points, face_idx) if return_faces else points
 
 
-def geometry_scores(pred_mesh, true_mesh, n: int = 10000, thresholds=(0.01, 0.02), u=None, generator=None) -> dict:
+def geometry_scores(pred_mesh, true_mesh, n: int = 10000, thresholds=(0.01, 0.02), u=None, generator=None,
+                    surface: bool = False) -> dict:
     """How close the surface of ``pred_mesh`` is to that of ``true_mesh``, from n samples of each, under ``no_grad``: a dict of 0-d
     tensors -- ``chamfer`` = ``chamfer_pred`` + ``chamfer_true`` (the mean squared distance from the pred samples to their nearest
     true sample, and the other way round), and per threshold t ``precision@t`` (the share of pred samples within DISTANCE t --
     not squared -- of a true sample), ``recall@t`` (the share of true samples within t of a pred sample) and
     ``fscore@t`` = 2 P R / (P + R), 0 when both are 0.  ``u`` [n, 3] is used for BOTH meshes; without it two sets are drawn from
-    ``generator``.  Distances are between samples, not from a point to the other surface: they are biased upwards by the sampling
-    density (about the mean spacing of n samples, squared), so compare scores at one n."""
+    ``generator``.  ``surface=False`` (the default): distances are between samples, not from a point to the other surface: they
+    are biased upwards by the sampling density (about the mean spacing of n samples, squared), so compare scores at one n.
+    ``surface=True``: the same keys, but every distance is from a sample to the nearest TRIANGLE of the other mesh
+    (``ops.nearest_faces``: the pred samples against the true mesh, the true samples against the pred mesh) -- exact up to
+    rounding, so a mesh scored against itself scores 0 with any samples and the scores no longer depend on n through a bias."""
     with torch.no_grad():
         dev = pred_mesh.verts_packed().device
         ops._require_cuda(pred_mesh.verts_packed(), true_mesh.verts_packed())
@@ -187,8 +297,12 @@ def geometry_scores(pred_mesh, true_mesh, n: int = 10000, thresholds=(0.01, 0.02
         ut = u if u is not None else _draw(int(n), dev, generator)
         p = sample_points_from_meshes(pred_mesh, n, u=up)
         t = sample_points_from_meshes(true_mesh, n, u=ut)
-        d_p, _ = ops.nearest_points(p, t)
-        d_t, _ = ops.nearest_points(t, p)
+        if surface:
+            d_p = ops.nearest_faces(p, true_mesh.verts_packed(), true_mesh.faces_packed())[0]
+            d_t = ops.nearest_faces(t, pred_mesh.verts_packed(), pred_mesh.faces_packed())[0]
+        else:
+            d_p, _ = ops.nearest_points(p, t)
+            d_t, _ = ops.nearest_points(t, p)
         out = {"chamfer_pred": d_p.mean(), "chamfer_true": d_t.mean()}
         out["chamfer"] = out["chamfer_pred"] + out["chamfer_true"]
         dist_p, dist_t = d_p.sqrt(), d_t.sqrt()

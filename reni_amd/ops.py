@@ -1292,6 +1292,48 @@ def mesh_sample_points(faces: torch.Tensor, table: torch.Tensor, u: torch.Tensor
     return idx, wgt, face_idx
 
 
+def _point_mesh(entry, points, verts, faces, slices):
+    slices = int(slices)
+    if slices < 0:
+        raise ValueError("slices must be >= 0")
+    _cloud(points, "points")
+    _mesh_shapes(verts, faces)
+    _require_cuda(points)
+    points = _f32c(points.detach())
+    verts, faces = _mesh_inputs(verts.detach(), faces)
+    if verts.device != points.device:
+        raise ValueError("points and the mesh must be on the same device")
+    N, V, F, dev = points.shape[0], verts.shape[0], faces.shape[0], points.device
+    lib = _lib.load()
+    n = F if entry == "reni_faces_nearest_points" else N
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev)
+    idx = torch.empty(n, dtype=torch.int64, device=dev)
+    # (fresh allocations: 16-byte aligned, as the library's row stores and the fetch want -- the library checks)
+    tap_index = torch.empty(n, 8, dtype=torch.int32, device=dev)
+    tap_weight = torch.empty(n, 8, dtype=torch.float32, device=dev)
+    ws, wp, wn = _ws256(int(getattr(lib, entry + "_workspace_bytes")(N, V, F)), dev)
+    _call(getattr(lib, entry), dev, N, V, F, points.data_ptr(), verts.data_ptr(), faces.data_ptr(), slices, dist2.data_ptr(),
+          idx.data_ptr(), tap_index.data_ptr(), tap_weight.data_ptr(), wp, wn)
+    return dist2, idx, tap_index, tap_weight
+
+
+def nearest_faces(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, slices: int = 0):
+    """reni_nearest_faces: (dist2 [N] float32, face_idx [N] int64, tap_index [N, 8] int32, tap_weight [N, 8] float32) -- for every
+    point the LOWEST index of the nearest triangle under the pair function of include/reni_hip.h, that squared distance, and
+    the closest point as a tap row of the texture unit: the face's vertices and the barycentric weights, so the closest points
+    are ``texture_fetch(verts, tap_index, tap_weight)``.  Where no face takes part: -1, +inf and zero taps.  Brute force through
+    LDS tiles, never an N x F matrix; ``slices`` cuts the faces over more workgroups (0: the library's choice) and never changes
+    a bit of the result."""
+    return _point_mesh("reni_nearest_faces", points, verts, faces, slices)
+
+
+def faces_nearest_points(points: torch.Tensor, verts: torch.Tensor, faces: torch.Tensor, slices: int = 0):
+    """reni_faces_nearest_points: (dist2 [F] float32, point_idx [F] int64, tap_index [F, 8] int32, tap_weight [F, 8] float32) -- for
+    every face the LOWEST index of the nearest point, that squared distance and the face's closest point to it as a tap row.  A
+    face that takes no part: -1, +inf and zero taps.  ``slices`` cuts the points over more workgroups and never changes a bit."""
+    return _point_mesh("reni_faces_nearest_points", points, verts, faces, slices)
+
+
 def _morton_order(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """A permutation of the faces that keeps neighbours together: the stable argsort of the 30-bit Morton codes of the
     centroids (10 bits per axis over the mesh's bounding box).  Faces with an index outside [0, V) sort last."""

@@ -688,6 +688,55 @@ int reni_faces_nearest_points(int64_t N, int64_t V, int64_t F, const float* poin
                               int32_t slices, float* dist2 /* [F] */, int64_t* point_idx /* [F] */, int32_t* tap_index /* [F][8] */,
                               float* tap_weight /* [F][8] */, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- cloud neighbourhoods: the K nearest points, normals from their principal axes (reni_tu_knn.hip) ---------------------
+ * What lets a scan pull on ORIENTATION and scores normal consistency: a scan arrives without normals, they are estimated from
+ * the K nearest neighbours of every point (pytorch3d's knn_points and estimate_pointcloud_normals; reni_amd/mesh_losses.py:
+ * knn_points, estimate_normals, chamfer_distance(x_normals=, y_normals=), geometry_scores(normals=True)).  fp32, no float
+ * atomics, no in-launch ticket, no host synchronisation, launches on `stream` only: two calls give identical bits.  One cloud
+ * per call, no spatial index: brute force, never N x M.
+ *
+ * reni_knn_points.  d(i, j) is reni_nearest_points' expression, fmaf(dz, dz, fmaf(dy, dy, dx * dx)), uncontracted.  Row i of
+ *   dist2 [N][K] (float32) and idx [N][K] (int64) lists the K smallest pairs (d, j) in ascending LEXICOGRAPHIC order: ties in d
+ *   go by ascending j.  A j whose d is NaN or +inf is never listed.  Slots left unfilled (M < K, a NaN query, every distance
+ *   overflowing) hold +inf and -1.  No index outside [-1, M) is ever written.  Column 0 has reni_nearest_points' bits wherever
+ *   slot 0 is filled.  1 <= K <= 32.
+ *   Structure: ONE query per lane, 256 per workgroup, its list of KB pairs in registers, KB the next of {4, 8, 16, 32} at or
+ *   above K (a smaller K runs in that bucket and stores its first K slots); the targets pass through LDS in tiles of 1024
+ *   16-byte records that every lane reads at the same address.  Per target one comparison against the lane's last slot; the
+ *   fully unrolled insertion runs only where a wave ballot says some lane improved.  grid.y cuts the target range into `slices`
+ *   contiguous slices; with more than one, a second launch merges the slices' lists lexicographically, so the result has the
+ *   same bits for ANY slicing.  slices = 0: the library's choice, min(cap, ceil(M / 1024)); slices > 0 is clamped to
+ *   min(cap, M), where cap = max(1, 512 / ceil(N / 256)) -- reni_nearest_points' rule for 256 queries per workgroup.
+ *   Launches (counted by reni_launch_count): 1 with one slice, else 2.
+ *   Limits: 1 <= N, M <= 2^31 - 1025.  ws: reni_knn_points_workspace_bytes(N, M, K) bytes, 256-byte aligned (0 for sizes or a K
+ *   out of range): the partials, cap N K pairs of two 4-byte values when cap > 1 -- N cap <= 131072, so at most K MiB + 768
+ *   bytes whatever N, and independent of M.
+ *
+ * reni_cloud_normals.  For y [M][3] and neighbour lists idx [N][K] (reni_knn_points' format), one lane per row, in fp32 with no
+ *   contraction, in THIS order:
+ *     mean:     s = 0; for the slots k = 0 .. K - 1 in list order, skipping a slot that is -1 or outside [0, M): s += y_j,
+ *               per component; c = the number of slots used; m = s / c.
+ *     moments:  for the same slots in the same order, e = y_j - m:  Cxx = fmaf(ex, ex, Cxx), Cxy = fmaf(ex, ey, Cxy), Cxz, Cyy,
+ *               Cyz, Czz likewise from 0; each divided by c.
+ *     solve:    cyclic Jacobi on the symmetric 3 x 3 matrix, 6 sweeps of the rotations (0,1), (0,2), (1,2); a rotation (p, q)
+ *               with a_pq != 0:  theta = (a_qq - a_pp) / (2 a_pq),  t = copysign(1, theta) / (|theta| + sqrt(fmaf(theta, theta,
+ *               1))),  c = 1 / sqrt(fmaf(t, t, 1)),  s = t c;  a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, the third row r:
+ *               (a_rp, a_rq) <- (c a_rp - s a_rq, s a_rp + c a_rq); the columns p, q of V (from the identity) likewise.
+ *     eigenvalues [N][3] = the diagonal, ASCENDING (three compare-exchanges that carry V's columns), clamped at 0 from below.
+ *     normals [N][3] = V's column of the smallest eigenvalue divided by its length: a unit vector.
+ *   Sign.  With viewpoint ([3], device): row i is point y_i (needs N <= M) and the normal is negated where
+ *   n . (viewpoint - y_i) < 0, so n . (viewpoint - y_i) >= 0.  With viewpoint = NULL: the component of largest magnitude is
+ *   made positive, the lowest index on ties.
+ *   Degenerate.  Fewer than 3 usable slots: normal exactly (0, 0, 0), eigenvalues 0.  A neighbourhood on a line or in a point:
+ *   some finite unit vector orthogonal to the rest (coincident points: (1, 0, 0)).  Moments that are not finite: (0, 0, 1),
+ *   eigenvalues clamped (NaN -> 0).  Never a NaN.  1 launch. */
+size_t reni_knn_points_workspace_bytes(int64_t N, int64_t M, int64_t K);
+int reni_knn_points(int64_t N, int64_t M, int64_t K, const float* x, const float* y, int32_t slices, float* dist2 /* [N][K] */,
+                    int64_t* idx /* [N][K] */, void* ws, size_t ws_bytes, void* stream);
+int reni_cloud_normals(int64_t N, int64_t M, int64_t K, const float* y, const int64_t* idx /* [N][K] */,
+                       const float* viewpoint /* [3] device, or NULL */, float* normals /* [N][3] */,
+                       float* eigenvalues /* [N][3] */, void* stream);
+
 /* ---- cast shadows: visibility masks of the mesh for the shader (reni_tu_visibility.hip, the MASKED shader instances) ----
  * The shader above lets light pass through the mesh: M(p, j) knows the pixel's own normal and nothing else.  The lights are at
  * infinity, so whether texel direction j reaches pixel p is a constant of (mesh, camera, directions), as the G-buffer is.

@@ -49,6 +49,7 @@ EXPORTS = (
     "reni_nearest_points_workspace_bytes", "reni_nearest_points", "reni_chamfer_grad",
     "reni_mesh_sample_table_workspace_bytes", "reni_mesh_sample_table", "reni_mesh_sample_points",
     "reni_nearest_faces_workspace_bytes", "reni_nearest_faces", "reni_faces_nearest_points_workspace_bytes", "reni_faces_nearest_points",
+    "reni_knn_points_workspace_bytes", "reni_knn_points", "reni_cloud_normals",
     "reni_mesh_visibility_accel_bytes", "reni_mesh_visibility_prepare", "reni_mesh_visibility",
     "reni_envmap_shade_masked", "reni_envmap_shade_masked_backward",
     "reni_envmap_shade_terms_workspace_bytes", "reni_envmap_shade_terms", "reni_envmap_shade_terms_backward",
@@ -256,6 +257,14 @@ def load():
         # N, V, F; points, verts, faces; slices; dist2, idx, tap_index, tap_weight, ws ..
         getattr(lib, name).argtypes = [c_int64] * 3 + [c_void_p] * 3 + [c_int32] + [c_void_p] * 5 + [c_size_t, c_void_p]
         getattr(lib, name).restype = c_int32
+    lib.reni_knn_points_workspace_bytes.argtypes = [c_int64] * 3
+    lib.reni_knn_points_workspace_bytes.restype = c_size_t
+    # N, M, K; x, y; slices; dist2, idx, ws ..
+    lib.reni_knn_points.argtypes = [c_int64] * 3 + [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.reni_knn_points.restype = c_int32
+    # N, M, K; y, idx, viewpoint; normals, eigenvalues
+    lib.reni_cloud_normals.argtypes = [c_int64] * 3 + [c_void_p] * 6
+    lib.reni_cloud_normals.restype = c_int32
     lib.reni_mesh_visibility_accel_bytes.argtypes = [c_int64]
     lib.reni_mesh_visibility_accel_bytes.restype = c_size_t
     lib.reni_mesh_visibility_prepare.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]

@@ -18,9 +18,18 @@ guarantees: no N x M matrix, no float atomics, identical bits on a second call.
 Points against a mesh (reni_tu_pointmesh.hip, include/reni_hip.h "points against a mesh"): ``nearest_surface`` (the nearest
 triangle of every point, its barycentrics and the closest point), ``point_mesh_distance`` (pytorch3d's
 ``point_mesh_face_distance`` for one mesh and one cloud, an autograd function in the points and the vertices) and
-``geometry_scores(surface=True)``.  Not provided: a normals term, batches of clouds or meshes, a spatial index (brute force is
-the design up to the sizes DESIGN 4.4u and 4.4v measure)."""
+``geometry_scores(surface=True)``.
+
+Cloud neighbourhoods (reni_tu_knn.hip, include/reni_hip.h "cloud neighbourhoods"): ``knn_points``, ``estimate_normals`` (PCA
+normals of a scan from its k nearest neighbours), the normals term of ``chamfer_distance(x_normals=, y_normals=)``, face
+normals of the samples (``sample_points_from_meshes(return_normals=True)``) and ``geometry_scores(normals=True)`` (normal
+consistency).  Every gather of a normal goes through the texture unit's one-tap fetch, so these gradients are bit-reproducible
+too.  Not provided: batches of clouds or meshes, a spatial index (brute force is the design up to the sizes DESIGN 4.4u - 4.4w
+measure), k > 32, gradients of ``knn_points``' distances."""
+import sys
+
 import torch
+import torch.nn.functional as F
 
 from . import _lib, ops
 
@@ -87,23 +96,28 @@ def nearest_points(x: torch.Tensor, y: torch.Tensor):
         return ops.nearest_points(x, y)
 
 
+def _chamfer_forward(ctx, x, y, wx, wy):
+    """the forward of both chamfer functions: (value, idx_xy | None, idx_yx | None)"""
+    xd, yd = x.detach(), y.detach()
+    value = torch.zeros((), dtype=torch.float32, device=xd.device)
+    idx_xy = idx_yx = None
+    if wx > 0.0:  # (a weight of 0 skips that direction's search and adds exactly 0)
+        d, idx_xy = ops.nearest_points(xd, yd)
+        value = value + wx * d.mean()
+    if wy > 0.0:
+        d, idx_yx = ops.nearest_points(yd, xd)
+        value = value + wy * d.mean()
+    ctx.save_for_backward(xd, yd, idx_xy, idx_yx)
+    ctx.w = (wx, wy)
+    return value, idx_xy, idx_yx
+
+
 class _ChamferFn(torch.autograd.Function):
     """(w_x / N) sum_i min_j |x_i - y_j|^2 + (w_y / M) sum_j min_i |x_i - y_j|^2; the matches are constants of the gradient"""
 
     @staticmethod
     def forward(ctx, x, y, wx, wy):
-        xd, yd = x.detach(), y.detach()
-        value = torch.zeros((), dtype=torch.float32, device=xd.device)
-        idx_xy = idx_yx = None
-        if wx > 0.0:  # (a weight of 0 skips that direction's search and adds exactly 0)
-            d, idx_xy = ops.nearest_points(xd, yd)
-            value = value + wx * d.mean()
-        if wy > 0.0:
-            d, idx_yx = ops.nearest_points(yd, xd)
-            value = value + wy * d.mean()
-        ctx.save_for_backward(xd, yd, idx_xy, idx_yx)
-        ctx.w = (wx, wy)
-        return value
+        return _chamfer_forward(ctx, x, y, wx, wy)[0]
 
     @staticmethod
     def backward(ctx, g):
@@ -120,20 +134,107 @@ class _ChamferFn(torch.autograd.Function):
         return gx, gy, None, None
 
 
-def chamfer_distance(x: torch.Tensor, y: torch.Tensor, weights=(1.0, 1.0)) -> torch.Tensor:
+class _ChamferMatchesFn(torch.autograd.Function):
+    """``_ChamferFn`` that also hands out the matches of its two searches (an empty list for a direction of weight 0)"""
+
+    @staticmethod
+    def forward(ctx, x, y, wx, wy):
+        value, idx_xy, idx_yx = _chamfer_forward(ctx, x, y, wx, wy)
+        idx_xy, idx_yx = (torch.empty(0, dtype=torch.int64, device=value.device) if t is None else t for t in (idx_xy, idx_yx))
+        ctx.mark_non_differentiable(idx_xy, idx_yx)
+        return value, idx_xy, idx_yx
+
+    @staticmethod
+    def backward(ctx, g, _gxy, _gyx):
+        return _ChamferFn.backward(ctx, g)
+
+
+def _one_tap_rows(index: torch.Tensor, E: int):
+    """(tap_index [P, 8] int32, tap_weight [P, 8] float32) of the texture unit that fetch row index[p] of a table of E rows
+    with weight 1 -- one live tap; an index outside [0, E) fetches nothing (weight 0).  The seven unused taps name row 0 with
+    weight 0: reni_texture_fetch and its backward skip a tap of weight 0 without reading it, so a row 0 that is not finite
+    does not reach the other rows"""
+    ok = (index >= 0) & (index < E)
+    tap_index = torch.zeros(index.shape[0], 8, dtype=torch.int32, device=index.device)
+    tap_weight = torch.zeros(index.shape[0], 8, dtype=torch.float32, device=index.device)
+    tap_index[:, 0] = torch.where(ok, index, torch.zeros_like(index)).to(torch.int32)
+    tap_weight[:, 0] = ok.to(torch.float32)
+    return tap_index, tap_weight
+
+
+def _gather_rows(table: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """table[index] for table [E, 3] through the texture unit's fetch: the backward is its sorted gather, no atomics"""
+    return _SamplePointsFn.apply(table, *_one_tap_rows(index, table.shape[0]))
+
+
+def _one_minus_cos(a, b, abs_cosine):
+    c = F.cosine_similarity(a, b, dim=1, eps=1e-6)
+    return 1.0 - (c.abs() if abs_cosine else c)
+
+
+def chamfer_distance(x: torch.Tensor, y: torch.Tensor, weights=(1.0, 1.0), x_normals=None, y_normals=None,
+                     abs_cosine: bool = True):
     """weights[0] mean_i min_j |x_i - y_j|^2 + weights[1] mean_j min_i |x_i - y_j|^2 for the clouds x [N, 3], y [M, 3] (squared
     distances, pytorch3d's default), a 0-d tensor.  Differentiable in both clouds with the matches held constant; ``x.grad`` and
-    ``y.grad`` are bit-reproducible.  A weight of 0 skips that direction."""
+    ``y.grad`` are bit-reproducible.  A weight of 0 skips that direction.
+
+    With ``x_normals`` [N, 3] and ``y_normals`` [M, 3] it returns (distance, normal_term) as pytorch3d does:
+    normal_term = weights[0] mean_i (1 - c(nx_i, ny_match(i))) + weights[1] mean_j (1 - c(ny_j, nx_match(j))), c the cosine
+    similarity (eps 1e-6), taken absolute with ``abs_cosine``.  The matches are those of the distance's own searches (no search
+    is added), the distance and the gradients of the positions are the same bits as without normals, the positions get no
+    gradient from the normal term, and it is differentiable in both normal sets through the texture unit's one-tap fetch:
+    those gradients are bit-reproducible too."""
     ops._cloud(x, "x")
     ops._cloud(y, "y")
     wx, wy = (float(w) for w in weights)
     for name, w in (("weights[0]", wx), ("weights[1]", wy)):
         if not (w >= 0.0) or w == float("inf"):
             raise ValueError(f"{name} must be >= 0 and finite, got {w}")
-    ops._require_cuda(x, y)
+    if (x_normals is None) != (y_normals is None):
+        raise ValueError("x_normals and y_normals must be given together")
+    if x_normals is not None:
+        for name, t, ref in (("x_normals", x_normals, x), ("y_normals", y_normals, y)):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(ref.shape):
+                raise ValueError(f"{name} must be a tensor {list(ref.shape)}")
+    ops._require_cuda(x, y, x_normals, y_normals)
     if x.device != y.device:
         raise ValueError("x and y must be on the same device")
-    return _ChamferFn.apply(x, y, wx, wy)
+    if x_normals is None:
+        return _ChamferFn.apply(x, y, wx, wy)
+    if x_normals.device != x.device or y_normals.device != x.device:
+        raise ValueError("the normals must be on the clouds' device")
+    value, idx_xy, idx_yx = _ChamferMatchesFn.apply(x, y, wx, wy)
+    nx, ny = x_normals.to(torch.float32), y_normals.to(torch.float32)
+    term = torch.zeros((), dtype=torch.float32, device=value.device)
+    if wx > 0.0:
+        term = term + wx * _one_minus_cos(nx, _gather_rows(ny, idx_xy), abs_cosine).mean()
+    if wy > 0.0:
+        term = term + wy * _one_minus_cos(ny, _gather_rows(nx, idx_yx), abs_cosine).mean()
+    return value, term
+
+
+# ---------------------------------------------------------------------------------------------------- cloud neighbourhoods
+def knn_points(x: torch.Tensor, y: torch.Tensor, k: int):
+    """(dist2 [N, k] float32, idx [N, k] int64): for every x_i its k nearest y_j, nearest first, ties by the lower index
+    (``ops.knn_points``; pytorch3d's ``knn_points`` for one cloud).  Slots that cannot be filled hold +inf and -1.  k <= 32.  It
+    carries no gradient."""
+    with torch.no_grad():
+        return ops.knn_points(x, y, k)
+
+
+def estimate_normals(points: torch.Tensor, k: int = 16, viewpoint=None, return_eigenvalues: bool = False):
+    """Unit normals [N, 3] of the cloud ``points`` [N, 3] from the principal axes of every point's k nearest neighbours
+    (pytorch3d's ``estimate_pointcloud_normals`` for one cloud): ``knn_points(points, points, k)``, then ``ops.cloud_normals``.
+    The point itself is one of its neighbours, as in pytorch3d.  pytorch3d's default of 50 neighbours is above the register
+    budget of the search (k <= 32), hence the default of 16.  The sign: towards ``viewpoint`` where one is given
+    (n . (viewpoint - p) >= 0), else the component of largest magnitude is positive -- pytorch3d's vote among neighbours is
+    not provided.  With ``return_eigenvalues`` also the covariance's eigenvalues [N, 3], ascending.  No gradient."""
+    with torch.no_grad():
+        ops._cloud(points, "points")
+        k = ops._knn_k(k)
+        _, idx = ops.knn_points(points, points, k)
+        normals, eig = ops.cloud_normals(points, idx, viewpoint)
+        return (normals, eig) if return_eigenvalues else normals
 
 
 # --------------------------------------------------------------------------------------------------- points against a mesh
@@ -258,9 +359,18 @@ def _draw(n, device, generator):
     return torch.rand(n, 3, dtype=torch.float32, device=gdev, generator=generator).to(device)
 
 
-def sample_points_from_meshes(mesh, n: int = 10000, u=None, generator=None, return_faces: bool = False):
+def _unit_face_normals(v0, v1, v2):
+    """cross(v1 - v0, v2 - v0) over its norm, the norm clamped from below as pytorch3d does"""
+    nrm = torch.cross(v1 - v0, v2 - v0, dim=1)
+    return nrm / nrm.norm(dim=1, keepdim=True).clamp_min(sys.float_info.epsilon)
+
+
+def sample_points_from_meshes(mesh, n: int = 10000, u=None, generator=None, return_faces: bool = False,
+                              return_normals: bool = False):
     """n points on the mesh's surface, uniform by area (pytorch3d's ``sample_points_from_meshes`` for one mesh): [n, 3], and with
-    ``return_faces`` the face of each, [n] int64.  ``u`` [n, 3] in [0, 1) are the random numbers (face, two barycentrics); without
+    ``return_faces`` the face of each, [n] int64.  With ``return_normals`` also the unit normals [n, 3] of the sampled faces,
+    differentiable in the vertices (the three corners are fetched through one-tap rows of the texture unit, the cross product
+    and the division are torch's); the order is points, normals, faces.  ``u`` [n, 3] in [0, 1) are the random numbers (face, two barycentrics); without
     it they are drawn from ``generator`` (``torch.rand``).  Differentiable with respect to ``mesh.verts_packed()``: the face choice
     and the barycentrics are constants of the gradient.  The area table is kept by the ``Meshes`` per in-place version of its
     vertices.  A mesh without area gives points that are exactly 0."""
@@ -275,11 +385,30 @@ def sample_points_from_meshes(mesh, n: int = 10000, u=None, generator=None, retu
         u = _draw(n, verts.device, generator)
     idx, wgt, face_idx = ops.mesh_sample_points(faces, mesh._sample_table(), u, verts.shape[0])
     points = _SamplePointsFn.apply(verts, idx, wgt)
-    return (points, face_idx) if return_faces else points
+    out = (points,)
+    if return_normals:
+        corners = faces[face_idx].t().reshape(-1)  # [3 n]: every sample's first corner, then the second, then the third
+        c = _SamplePointsFn.apply(verts, *_one_tap_rows(corners, verts.shape[0])).reshape(3, n, 3)
+        out += (_unit_face_normals(c[0], c[1], c[2]),)
+    if return_faces:
+        out += (face_idx,)
+    return out if len(out) > 1 else points
+
+
+def _mesh_face_normals(mesh):
+    verts, faces = mesh.verts_packed(), mesh.faces_packed()
+    tri = verts[faces.clamp(0, verts.shape[0] - 1)]
+    return _unit_face_normals(tri[:, 0], tri[:, 1], tri[:, 2])
+
+
+def _abs_cos_mean(a, b, idx):
+    """mean_i |a_i . b_idx[i]| of unit vectors; an entry without a match (idx < 0) counts 0"""
+    c = (a * b[idx.clamp_min(0)]).sum(1).abs()
+    return torch.where(idx >= 0, c, torch.zeros_like(c)).mean()
 
 
 def geometry_scores(pred_mesh, true_mesh, n: int = 10000, thresholds=(0.01, 0.02), u=None, generator=None,
-                    surface: bool = False) -> dict:
+                    surface: bool = False, normals: bool = False) -> dict:
     """How close the surface of ``pred_mesh`` is to that of ``true_mesh``, from n samples of each, under ``no_grad``: a dict of 0-d
     tensors -- ``chamfer`` = ``chamfer_pred`` + ``chamfer_true`` (the mean squared distance from the pred samples to their nearest
     true sample, and the other way round), and per threshold t ``precision@t`` (the share of pred samples within DISTANCE t --
@@ -289,21 +418,33 @@ def geometry_scores(pred_mesh, true_mesh, n: int = 10000, thresholds=(0.01, 0.02
     are biased upwards by the sampling density (about the mean spacing of n samples, squared), so compare scores at one n.
     ``surface=True``: the same keys, but every distance is from a sample to the nearest TRIANGLE of the other mesh
     (``ops.nearest_faces``: the pred samples against the true mesh, the true samples against the pred mesh) -- exact up to
-    rounding, so a mesh scored against itself scores 0 with any samples and the scores no longer depend on n through a bias."""
+    rounding, so a mesh scored against itself scores 0 with any samples and the scores no longer depend on n through a bias.
+    ``normals=True`` adds ``normal_consistency_pred``, ``normal_consistency_true`` and their mean ``normal_consistency``: the mean
+    |cos| between the face normal of a sample and the face normal of its match -- the matched sample's with ``surface=False``,
+    the nearest triangle's (``ops.nearest_faces``) with ``surface=True``.  The other keys keep their bits."""
     with torch.no_grad():
         dev = pred_mesh.verts_packed().device
         ops._require_cuda(pred_mesh.verts_packed(), true_mesh.verts_packed())
         up = u if u is not None else _draw(int(n), dev, generator)
         ut = u if u is not None else _draw(int(n), dev, generator)
-        p = sample_points_from_meshes(pred_mesh, n, u=up)
-        t = sample_points_from_meshes(true_mesh, n, u=ut)
-        if surface:
-            d_p = ops.nearest_faces(p, true_mesh.verts_packed(), true_mesh.faces_packed())[0]
-            d_t = ops.nearest_faces(t, pred_mesh.verts_packed(), pred_mesh.faces_packed())[0]
+        if normals:
+            p, n_p = sample_points_from_meshes(pred_mesh, n, u=up, return_normals=True)
+            t, n_t = sample_points_from_meshes(true_mesh, n, u=ut, return_normals=True)
         else:
-            d_p, _ = ops.nearest_points(p, t)
-            d_t, _ = ops.nearest_points(t, p)
+            p = sample_points_from_meshes(pred_mesh, n, u=up)
+            t = sample_points_from_meshes(true_mesh, n, u=ut)
+        if surface:
+            d_p, i_p = ops.nearest_faces(p, true_mesh.verts_packed(), true_mesh.faces_packed())[:2]
+            d_t, i_t = ops.nearest_faces(t, pred_mesh.verts_packed(), pred_mesh.faces_packed())[:2]
+        else:
+            d_p, i_p = ops.nearest_points(p, t)
+            d_t, i_t = ops.nearest_points(t, p)
         out = {"chamfer_pred": d_p.mean(), "chamfer_true": d_t.mean()}
+        if normals:
+            m_t, m_p = (_mesh_face_normals(true_mesh), _mesh_face_normals(pred_mesh)) if surface else (n_t, n_p)
+            out["normal_consistency_pred"] = _abs_cos_mean(n_p, m_t, i_p)
+            out["normal_consistency_true"] = _abs_cos_mean(n_t, m_p, i_t)
+            out["normal_consistency"] = 0.5 * (out["normal_consistency_pred"] + out["normal_consistency_true"])
         out["chamfer"] = out["chamfer_pred"] + out["chamfer_true"]
         dist_p, dist_t = d_p.sqrt(), d_t.sqrt()
         for tau in thresholds:

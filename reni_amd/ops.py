@@ -1334,6 +1334,67 @@ def faces_nearest_points(points: torch.Tensor, verts: torch.Tensor, faces: torch
     return _point_mesh("reni_faces_nearest_points", points, verts, faces, slices)
 
 
+KNN_MAX_K = 32  # the register budget of a lane's list (reni_tu_knn.hip)
+
+
+def _knn_k(k):
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k must be an int in [1, {KNN_MAX_K}], got {k!r}")
+    return k
+
+
+def knn_points(x: torch.Tensor, y: torch.Tensor, k: int, slices: int = 0):
+    """reni_knn_points: (dist2 [N, k] float32, idx [N, k] int64) -- for every x_i the k smallest pairs (d, j) over the y_j in
+    ascending lexicographic order (ties in d by ascending j), d = fmaf(dz, dz, fmaf(dy, dy, dx dx)) as ``nearest_points``
+    computes it: column 0 has its bits.  A target at a NaN or +inf distance is never listed; slots left unfilled hold +inf and
+    -1.  1 <= k <= 32: the lists live in registers.  Brute force through LDS tiles, never an N x M matrix; ``slices`` cuts the
+    target range over more workgroups (0: the library's choice) and never changes a bit of the result."""
+    k = _knn_k(k)
+    slices = int(slices)
+    if slices < 0:
+        raise ValueError("slices must be >= 0")
+    x, y = _cloud_pair(x, y)
+    N, M, dev = x.shape[0], y.shape[0], x.device
+    lib = _lib.load()
+    dist2 = torch.empty(N, k, dtype=torch.float32, device=dev)
+    idx = torch.empty(N, k, dtype=torch.int64, device=dev)
+    ws, wp, wn = _ws256(int(lib.reni_knn_points_workspace_bytes(N, M, k)), dev)
+    _call(lib.reni_knn_points, dev, N, M, k, x.data_ptr(), y.data_ptr(), slices, dist2.data_ptr(), idx.data_ptr(), wp, wn)
+    return dist2, idx
+
+
+def cloud_normals(y: torch.Tensor, idx: torch.Tensor, viewpoint=None):
+    """reni_cloud_normals: (normals [N, 3], eigenvalues [N, 3] ascending, >= 0) from the neighbour lists idx [N, k] int64 into
+    y [M, 3] (``knn_points``' format; a slot of -1 is skipped): the unit eigenvector of the smallest eigenvalue of each
+    neighbourhood's covariance, by cyclic Jacobi in fp32 (include/reni_hip.h has the order of operations).  With ``viewpoint``
+    (three numbers or a tensor [3]) row i is point y_i and n . (viewpoint - y_i) >= 0; without, the component of largest
+    magnitude is positive.  Fewer than 3 usable neighbours: exactly 0.  Never a NaN."""
+    _cloud(y, "y")
+    if (not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype != torch.int64 or idx.shape[0] < 1
+            or not 1 <= idx.shape[1] <= KNN_MAX_K):
+        raise ValueError(f"idx must be an int64 tensor [N, k] with N >= 1 and 1 <= k <= {KNN_MAX_K}")
+    N, K, M = idx.shape[0], idx.shape[1], y.shape[0]
+    if viewpoint is not None:
+        if not isinstance(viewpoint, torch.Tensor):
+            viewpoint = torch.tensor([float(v) for v in viewpoint], dtype=torch.float32, device=y.device)
+        if viewpoint.numel() != 3:
+            raise ValueError("viewpoint must hold three values")
+        if N > M:
+            raise ValueError("with a viewpoint row i is point y_i: idx must not have more rows than y")
+    _require_cuda(y, idx, viewpoint)
+    y, idx = _f32c(y.detach()), idx.contiguous()
+    dev = y.device
+    if idx.device != dev or (viewpoint is not None and viewpoint.device != dev):
+        raise ValueError(f"idx and viewpoint must be on {dev}")
+    if viewpoint is not None:
+        viewpoint = _f32c(viewpoint.detach()).reshape(3)
+    normals = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    eig = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    _call(_lib.load().reni_cloud_normals, dev, N, M, K, y.data_ptr(), idx.data_ptr(), _ptr(viewpoint), normals.data_ptr(),
+          eig.data_ptr())
+    return normals, eig
+
+
 def _morton_order(verts: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
     """A permutation of the faces that keeps neighbours together: the stable argsort of the 30-bit Morton codes of the
     centroids (10 bits per axis over the mesh's bounding box).  Faces with an index outside [0, V) sort last."""
